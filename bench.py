@@ -11,6 +11,9 @@ path over one batch of synthetic input, closed loop against a host plant step, l
 
 What the ONE JSON line holds:
   value / ms_per_step   the timed region: K calls at the boundary named in config.boundary, samples as in config.samples
+
+A plain run stops there: it sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR) and
+prints the line.  With --full it goes on to measure what follows, each pass outside the timed region:
   modes                 the same K-step protocol repeated (outside the timed region) for the other three combinations of
                         boundary in {controller_mpc.step, engine (ctypes ctk_step)} x samples in {buffer, device-rng}:
                         "buffer" = [N,P,C] N(0,1) draws resident in HBM before the region starts (a pool of 16);
@@ -19,6 +22,12 @@ What the ONE JSON line holds:
   roofline              dominant kernel, timed by its dispatch timestamps in a SEPARATE pass after the timed region
   cpu_baseline          the CPU restatement on this box's host cores (bounded sample): oracle/ctk_cpu.c (C + OpenMP) where it covers the
                         workload, with the single-thread NumPy oracle beside it (cpu_baseline_numpy); else the NumPy oracle
+  resident, roofline_large_n, and for G > 1 exchange_us / step_decomposition_us / roofline_per_rank / single_gpu_same_workload
+
+--dump-outputs DIR: what the timed path returned in its last timed step, as DIR/<name>.npy (float32): `u` = the control
+controller.step / engine.step returned, `u_nom` = the optimizer's plan after that step (optimizer.u_nom, the device buffer
+U_NOM).  The inputs (initial state, sample pool, seeds) depend on the arguments only, so two builds can be compared output
+for output.
 
 G > 1: strong scaling of BASELINE configs[4] — N = 65536 rollouts split over the ranks, one RCCL all-gather of the
 (2+P)-float soft-min record per step (control_toolkit_amd/dist.py).  Other BASELINE configs are parity-test cases;
@@ -355,6 +364,11 @@ def main():
     ap.add_argument("--no-large-n", action="store_true", help="skip the scaled-N roofline point (same kernel family, N = 2^20)")
     ap.add_argument("--no-modes", action="store_true", help="skip the three extra boundary x samples passes")
     ap.add_argument("--force-sharded", action="store_true", help="use the begin / all-gather / end path even with one rank")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timed region, also measure the other modes, the resident form, the dominant kernel's "
+                         "roofline, the scaled-N point and the CPU baselines (the --no-* switches still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     # `python bench.py --gpus G` as a bare command (no launcher in the environment): start the one-process-per-GPU job as a CHILD process
@@ -499,9 +513,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         per_step = np.empty(steps)
+        u = None
         t0 = time.perf_counter(); ta = t0
         for i in range(steps):
-            plant_step(s, np.asarray(step_fn(s, i)).reshape(-1)[0])   # controller.step, then the plant: closed loop
+            u = step_fn(s, i)
+            plant_step(s, np.asarray(u).reshape(-1)[0])   # controller.step, then the plant: closed loop
             tb = time.perf_counter(); per_step[i] = tb - ta; ta = tb
         if before_close is not None:
             before_close()
@@ -515,6 +531,7 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        bracket["last_u"] = u
         return elapsed, per_step
 
     boundary = "sharded" if sharded is not None else args.boundary
@@ -522,11 +539,18 @@ def main():
     elapsed, per_step = run_region(make_step(boundary, samples), args.steps, args.warmup, True)
     bracket_close_ms = bracket.get("close_ms")
 
+    # ---- --dump-outputs: what a caller of the timed path received in its last timed step (read after the closing synchronize) --------
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        u_nom = ctrl.optimizer.u_nom if boundary == "controller" else eng.read("U_NOM")
+        for name, arr in (("u", bracket["last_u"]), ("u_nom", u_nom)):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.array(arr, dtype=np.float32))
+
     # ---- the resident form (opt-in, include/ctk_hip.h: ctk_resident_*): the same K-step protocol at the same boundary with the steps served
     #      by a kernel that stays on the device.  A SEPARATE field: `value` above stays one launch per step.  The kernel is ended inside the
     #      timed region, before the closing synchronize (which would otherwise wait for its idle time-out).
     resident = None
-    if sharded is None and w["opt"] == "mppi" and w["pred"] == "ODE" and not args.no_modes:
+    if args.full and sharded is None and w["opt"] == "mppi" and w["pred"] == "ODE" and not args.no_modes:
         try:
             r_eng = ctrl.optimizer.engine if boundary == "controller" else eng
             # buffers: read when the request arrives (the default, safe for a buffer refilled in place); the pool here is static, so the
@@ -554,7 +578,7 @@ def main():
 
     # ---- the other boundary x sample-mode combinations, same protocol, outside the timed region ------------------
     modes = {}
-    if sharded is None and not args.no_modes:
+    if args.full and sharded is None and not args.no_modes:
         for b in ("controller", "engine"):
             for sm in ("buffer", "device-rng"):
                 if (b, sm) == (boundary, samples):
@@ -566,72 +590,73 @@ def main():
 
     # ---- dominant-kernel time: a separate pass with every launch timed through its dispatch timestamps (timing a
     #      launch costs host time, so it stays out of the timed region) --------------------------------------------
-    kstep = make_step("sharded" if sharded is not None else "engine", samples)
-    kpass = max(8, min(64, args.steps))
-    s = s0.copy()
-    eng.profile_enable(True, every=1)
-    if sharded is not None:
-        sharded.enable_timing(True)          # four stream events per step: begin kernels | exchange | end kernels
-    for i in range(kpass):
-        plant_step(s, np.asarray(kstep(s, i)).reshape(-1)[0])
-    kern_ms = eng.profile_read()
-    eng.profile_enable(False)
-    exch = None
-    if sharded is not None:
-        torch.cuda.synchronize()
-        exch = sharded.timing_us()
-        sharded.enable_timing(False)
-    # every rank's dominant-kernel time and exchange time to rank 0 (a scaling curve is read per rank: the slowest one sets the step)
-    per_rank = None
-    if use_pg:
-        mine = torch.tensor([float(np.mean(kern_ms)) * 1e3 if len(kern_ms) else float("nan"),
-                             float(np.mean(exch["begin_us"])) if exch and exch["begin_us"] else float("nan"),
-                             float(np.mean(exch["exchange_us"])) if exch and exch["exchange_us"] else float("nan"),
-                             float(np.mean(exch["end_us"])) if exch and exch["end_us"] else float("nan")], dtype=torch.float64,
-                            device=dev if backend == "nccl" else "cpu")
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        per_rank = [[float(v) for v in t.cpu()] for t in allr]
+    kern_ms, exch, per_rank = [], None, None
+    if args.full:
+        kstep = make_step("sharded" if sharded is not None else "engine", samples)
+        kpass = max(8, min(64, args.steps))
+        s = s0.copy()
+        eng.profile_enable(True, every=1)
+        if sharded is not None:
+            sharded.enable_timing(True)          # four stream events per step: begin kernels | exchange | end kernels
+        for i in range(kpass):
+            plant_step(s, np.asarray(kstep(s, i)).reshape(-1)[0])
+        kern_ms = eng.profile_read()
+        eng.profile_enable(False)
+        if sharded is not None:
+            torch.cuda.synchronize()
+            exch = sharded.timing_us()
+            sharded.enable_timing(False)
+        # every rank's dominant-kernel time and exchange time to rank 0 (a scaling curve is read per rank: the slowest one sets the step)
+        if use_pg:
+            mine = torch.tensor([float(np.mean(kern_ms)) * 1e3 if len(kern_ms) else float("nan"),
+                                 float(np.mean(exch["begin_us"])) if exch and exch["begin_us"] else float("nan"),
+                                 float(np.mean(exch["exchange_us"])) if exch and exch["exchange_us"] else float("nan"),
+                                 float(np.mean(exch["end_us"])) if exch and exch["end_us"] else float("nan")], dtype=torch.float64,
+                                device=dev if backend == "nccl" else "cpu")
+            allr = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allr, mine)
+            per_rank = [[float(v) for v in t.cpu()] for t in allr]
 
     if rank == 0:
         total_units = Ng * H * args.steps
-        kms = float(np.mean(kern_ms)) if len(kern_ms) else float("nan")
-        samples_in_hbm = samples == "buffer" and w["opt"] in ("mppi", "cem", "random_action")
-        kname = eng.dominant_kernel()
-        alg_bytes, alg_flops = algorithmic(w, N, P, samples_in_hbm, kname)
-        ok = kms == kms and kms > 0
-        if alg_flops is not None:
-            ach = alg_flops / (kms * 1e-3) / 1e12 if ok else None
-            roof = {"bound": "mfma", "achieved": ach, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
-                    "frac": ach / MFMA_F32_PEAK_TF if ach else None, "traffic": None, "algorithmic_flops": alg_flops,
-                    "note": "fp32-input MFMA (v_mfma_f32_16x16x4_f32) for exact-fp32 parity; per launch of this rank's shard"}
-        else:
-            ach = alg_bytes / (kms * 1e-3) / 1e9 if ok else None
-            traffic, tnote = recorded_traffic(wname, samples, kname)
-            roof = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": ach / HBM_PEAK_GBS if ach else None, "traffic": traffic, "traffic_source": tnote,
-                    "note": "issue/latency-bound at this size, not HBM-bound: 0.2 MB per launch vs an H-step dependent recurrence on one "
-                            "wave per 64 trajectories (DESIGN.md 5); the large-N point below is where the chip is full"}
-        roof.update({"kernel": kname, "kernel_us": kms * 1e3, "algorithmic_bytes": alg_bytes,
-                     "kernel_timed_launches": int(len(kern_ms)), "kernel_timing": "separate pass after the timed region, every launch"})
-        sharded_fields = {}
-        if sharded is not None:
-            # where a sharded step's time goes, on the device timeline of this rank (events on the stream the engine and the collective share):
-            # begin = rollout (+ local merge / selection), exchange = the collective incl. the wait for the slowest peer, end = merge / update
-            mean = lambda k: (float(np.mean(exch[k])) if exch and exch[k] else None)
-            sharded_fields["exchange_us"] = mean("exchange_us")
-            sharded_fields["step_decomposition_us"] = {"begin_kernels": mean("begin_us"), "exchange": mean("exchange_us"), "end_kernels": mean("end_us"),
-                                                       "exchange_kind": ("p2p stores" if getattr(sharded, "exchange", "rccl") == "p2p" else
-                                                                         ("RCCL all-gather" if backend == "nccl" else f"{backend} all-gather (rehearsal)") if use_pg else "none (one rank)"),
-                                                       "note": "stream events around begin / collective / end in the kernel-timing pass; p2p: one launch, not decomposed"}
-            if per_rank is not None:
-                unit_alg = alg_flops if alg_flops is not None else alg_bytes
-                scale = 1e12 if alg_flops is not None else 1e9
-                peak = MFMA_F32_PEAK_TF if alg_flops is not None else HBM_PEAK_GBS
-                sharded_fields["roofline_per_rank"] = [
-                    {"rank": r, "kernel_us": v[0], "achieved": (unit_alg / (v[0] * 1e-6) / scale) if v[0] == v[0] and v[0] > 0 else None,
-                     "frac": (unit_alg / (v[0] * 1e-6) / scale / peak) if v[0] == v[0] and v[0] > 0 else None,
-                     "begin_us": v[1], "exchange_us": v[2], "end_us": v[3]} for r, v in enumerate(per_rank)]
+        roof, sharded_fields = None, {}
+        if args.full:
+            kms = float(np.mean(kern_ms)) if len(kern_ms) else float("nan")
+            samples_in_hbm = samples == "buffer" and w["opt"] in ("mppi", "cem", "random_action")
+            kname = eng.dominant_kernel()
+            alg_bytes, alg_flops = algorithmic(w, N, P, samples_in_hbm, kname)
+            ok = kms == kms and kms > 0
+            if alg_flops is not None:
+                ach = alg_flops / (kms * 1e-3) / 1e12 if ok else None
+                roof = {"bound": "mfma", "achieved": ach, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
+                        "frac": ach / MFMA_F32_PEAK_TF if ach else None, "traffic": None, "algorithmic_flops": alg_flops,
+                        "note": "fp32-input MFMA (v_mfma_f32_16x16x4_f32) for exact-fp32 parity; per launch of this rank's shard"}
+            else:
+                ach = alg_bytes / (kms * 1e-3) / 1e9 if ok else None
+                traffic, tnote = recorded_traffic(wname, samples, kname)
+                roof = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": ach / HBM_PEAK_GBS if ach else None, "traffic": traffic, "traffic_source": tnote,
+                        "note": "issue/latency-bound at this size, not HBM-bound: 0.2 MB per launch vs an H-step dependent recurrence on one "
+                                "wave per 64 trajectories (DESIGN.md 5); the large-N point below is where the chip is full"}
+            roof.update({"kernel": kname, "kernel_us": kms * 1e3, "algorithmic_bytes": alg_bytes,
+                         "kernel_timed_launches": int(len(kern_ms)), "kernel_timing": "separate pass after the timed region, every launch"})
+            if sharded is not None:
+                # where a sharded step's time goes, on the device timeline of this rank (events on the stream the engine and the collective share):
+                # begin = rollout (+ local merge / selection), exchange = the collective incl. the wait for the slowest peer, end = merge / update
+                mean = lambda k: (float(np.mean(exch[k])) if exch and exch[k] else None)
+                sharded_fields["exchange_us"] = mean("exchange_us")
+                sharded_fields["step_decomposition_us"] = {"begin_kernels": mean("begin_us"), "exchange": mean("exchange_us"), "end_kernels": mean("end_us"),
+                                                           "exchange_kind": ("p2p stores" if getattr(sharded, "exchange", "rccl") == "p2p" else
+                                                                             ("RCCL all-gather" if backend == "nccl" else f"{backend} all-gather (rehearsal)") if use_pg else "none (one rank)"),
+                                                           "note": "stream events around begin / collective / end in the kernel-timing pass; p2p: one launch, not decomposed"}
+                if per_rank is not None:
+                    unit_alg = alg_flops if alg_flops is not None else alg_bytes
+                    scale = 1e12 if alg_flops is not None else 1e9
+                    peak = MFMA_F32_PEAK_TF if alg_flops is not None else HBM_PEAK_GBS
+                    sharded_fields["roofline_per_rank"] = [
+                        {"rank": r, "kernel_us": v[0], "achieved": (unit_alg / (v[0] * 1e-6) / scale) if v[0] == v[0] and v[0] > 0 else None,
+                         "frac": (unit_alg / (v[0] * 1e-6) / scale / peak) if v[0] == v[0] and v[0] > 0 else None,
+                         "begin_us": v[1], "exchange_us": v[2], "end_us": v[3]} for r, v in enumerate(per_rank)]
         ps = per_step * 1e3
         out = {
             "metric": "trajectory-steps/sec (N*H per controller.step)", "value": total_units / elapsed,
@@ -647,8 +672,9 @@ def main():
                        "samples": samples if (sharded is None or w["opt"] == "mppi") else "device-rng",
                        "global_rollouts": Ng, "parallelism": exchange_note},
             "step_ms_median": float(np.median(ps)),
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         out.update(sharded_fields)
         # what the barrier + synchronize bracket itself contributes to `ms_per_step` (fixed per region, so 1/K of it per step: a K = 20
         # run reads ~2 us per step higher than a K = 200 run of the same steady state; the median does not move)
@@ -662,9 +688,9 @@ def main():
             out["modes"] = modes
         if resident is not None:
             out["resident"] = resident
-        if not args.no_large_n and world == 1 and wname == "mppi_cfg2":
+        if args.full and not args.no_large_n and world == 1 and wname == "mppi_cfg2":
             out["roofline_large_n"] = large_n_point(torch, CtkEngine, dev, H, p)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             numpy_leg = cpu_baseline(w, budget_s=8.0)
             native = cpu_baseline_native(w)
             # `cpu_baseline` = the fastest CPU restatement available for this workload (the native C + OpenMP port where it exists);
@@ -674,7 +700,7 @@ def main():
                 out["cpu_baseline_numpy"] = numpy_leg
             if w["opt"] == "mppi" and w["pred"] == "ODE":
                 out["cpu_baseline_torch"] = cpu_baseline_torch(w)
-        if world > 1 and w["opt"] == "mppi":
+        if args.full and world > 1 and w["opt"] == "mppi":
             # the ONE-GPU point of the same workload, measured on rank 0's GPU while the others wait: lets a reader
             # turn the strong-scaling value into an efficiency without a second launch of this script
             e1 = CtkEngine("mppi", w["pred"], num_rollouts=Ng, mpc_horizon=H, dt=0.02, period_interpolation_inducing_points=p,

@@ -35,6 +35,35 @@ sys.path.insert(0, REPO)
 
 from oracle import ctk_oracle as O  # noqa: E402  (only for EnvParams/derived constants + plant step)
 
+PART_RAW_BYTES = 960_000     # raw bytes per part file: deflate never grows data past 1 MiB from here
+
+
+def save_fixture(path, **arrays):
+    """np.savez_compressed, or — when that file would exceed 1 MiB — `<stem>.part<k>.npz` files of at most PART_RAW_BYTES raw
+    bytes each: a larger array is stored flattened as `<key>@<i>` chunks beside `<key>@shape` (tests/helpers.py: load joins them)"""
+    np.savez_compressed(path, **arrays)
+    if os.path.getsize(path) <= 1 << 20:
+        return
+    os.remove(path)
+    items = []
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if v.nbytes <= PART_RAW_BYTES // 2:
+            items.append((k, v))
+            continue
+        flat = v.reshape(-1)
+        step = max(1, (PART_RAW_BYTES // 2) // v.itemsize)
+        items.append((f"{k}@shape", np.array(v.shape, np.int64)))
+        items += [(f"{k}@{i}", flat[j:j + step]) for i, j in enumerate(range(0, flat.size, step))]
+    parts, cur, size = [], {}, 0
+    for k, v in items:
+        if cur and size + v.nbytes > PART_RAW_BYTES:
+            parts.append(cur); cur, size = {}, 0
+        cur[k] = v; size += v.nbytes
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        np.savez_compressed(f"{path[:-len('.npz')]}.part{i}.npz", **part)
+
 
 class RecordingRng:
     """Observer around the reference's generator (globals_and_utils.py:61-83): calls it exactly as
@@ -251,7 +280,7 @@ def record_tf_only_optimizers(out_dir, cm, envs, dt):
                 s = plant_step(plant, s, u)
             assert opt.count == c["steps"]
             d["steps"] = np.int32(c["steps"])
-            np.savez_compressed(os.path.join(out_dir, f"cem_{name}.npz"), **d)
+            save_fixture(os.path.join(out_dir, f"cem_{name}.npz"), **d)
 
         # ---- random-action (Optimizers/optimizer_random_action_tf.py:38-86) -------------------------------------------
         random_cases = {
@@ -280,7 +309,7 @@ def record_tf_only_optimizers(out_dir, cm, envs, dt):
                 d[f"traj_{t}"] = np.asarray(lv["rollout_trajectories_logged"]).copy()
                 s = plant_step(plant, s, u)
             d["steps"] = np.int32(c["steps"])
-            np.savez_compressed(os.path.join(out_dir, f"random_{name}.npz"), **d)
+            save_fixture(os.path.join(out_dir, f"random_{name}.npz"), **d)
 
         # ---- CEM + one clipped-gradient step (Optimizers/optimizer_cem_naive_grad_tf.py:58-119) -----------------------
         naive_cases = {
@@ -309,7 +338,7 @@ def record_tf_only_optimizers(out_dir, cm, envs, dt):
                 d[f"J_{t}"] = np.asarray(lv["J_logged"]).copy(); d[f"Q_{t}"] = np.asarray(lv["Q_logged"]).copy()
                 s = plant_step(plant, s, u)
             d["steps"] = np.int32(c["steps"])
-            np.savez_compressed(os.path.join(out_dir, f"cem_naive_grad_{name}.npz"), **d)
+            save_fixture(os.path.join(out_dir, f"cem_naive_grad_{name}.npz"), **d)
     finally:
         set_computation_library("pytorch")
         pw.ENVIRONMENT = "CartPole"
@@ -347,7 +376,7 @@ def main():
             interp[f"H{H}_p{p}_C{C}_y"] = y
             interp[f"H{H}_p{p}_C{C}_out"] = out
             interp[f"H{H}_p{p}_C{C}_mat"] = I.interp_mat.numpy()   # [P,H,C]
-    np.savez_compressed(os.path.join(out_dir, "interpolator.npz"), **interp)
+    save_fixture(os.path.join(out_dir, "interpolator.npz"), **interp)
 
     # ---- cost aggregation (Cost_Functions/__init__.py:38-93) ----------------------------------
     class _Agg(CostClass.__mro__[1]):   # reference cost_function_base with canned stage/terminal costs
@@ -368,7 +397,7 @@ def main():
     traj = g.standard_normal((6, 8, 4)).astype(np.float32)
     inp = g.uniform(-1, 1, (6, 7, 1)).astype(np.float32)
     Jfull = cc.get_trajectory_cost(torch.tensor(traj), torch.tensor(inp), np.float32(0.25)).numpy()
-    np.savez_compressed(os.path.join(out_dir, "cost_aggregation.npz"), stage=stage, terminal=term, J=J, J_summed=Jsum,
+    save_fixture(os.path.join(out_dir, "cost_aggregation.npz"), stage=stage, terminal=term, J=J, J_summed=Jsum,
                         traj=traj, inputs=inp, u_prev=np.float32(0.25), J_full=Jfull, **common)
 
     # ---- controller_mpc helper ----------------------------------------------------------------
@@ -425,7 +454,7 @@ def main():
         outs = ctrl2.get_outputs()
         assert outs["J_logged"].shape == (c["steps"], c["N"])
         d["steps"] = np.int32(c["steps"])
-        np.savez_compressed(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
+        save_fixture(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
 
     # ---- ADAM torch branch (optimizer_rpgd.py:56-82) ------------------------------------------
     adam = ADAM(lib, learning_rate=0.05, beta_1=0.9, beta_2=0.999, epsilon=1e-8)
@@ -438,7 +467,7 @@ def main():
         ad[f"grad_{t}"] = grad.numpy().copy(); ad[f"var_{t}"] = var.numpy().copy()
     step_count, m_arr, v_arr = adam.get_weights()
     ad.update(step=np.int32(step_count), m=m_arr, v=v_arr)
-    np.savez_compressed(os.path.join(out_dir, "adam.npz"), **ad)
+    save_fixture(os.path.join(out_dir, "adam.npz"), **ad)
 
     # ---- RPGD (Optimizers/optimizer_rpgd.py via controller_mpc) --------------------------------
     rpgd_cases = {
@@ -490,7 +519,7 @@ def main():
             s = plant_step(plant, s, u)
         d["steps"] = np.int32(c["steps"])
         record_rpgd_logged_outputs(d, lambda: make_controller("rpgd", cfg, c["pred"]), c["steps"])
-        np.savez_compressed(os.path.join(out_dir, f"rpgd_{name}.npz"), **d)
+        save_fixture(os.path.join(out_dir, f"rpgd_{name}.npz"), **d)
 
     # ---- second environment, C = 2: the SAME unmodified reference optimizers on the planar quadrotor ---------------
     # pins the [N,P,C] / [N,H,C] logic of optimizer_mppi.py / optimizer_rpgd.py / Interpolator.py for C > 1: per-channel
@@ -533,7 +562,7 @@ def main():
             d[f"traj_{t}"] = lv["rollout_trajectories_logged"].copy()
             s = plant_step(plant, s, u)
         d["steps"] = np.int32(c["steps"])
-        np.savez_compressed(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
+        save_fixture(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
 
     for name, c in {"quad2d": dict(N=32, H=20, p=5, its=3, steps=4, resamp=2, dist="uniform", seed=23, shift=1),
                     "quad2d_its20": dict(N=64, H=30, p=10, its=20, steps=2, resamp=10, dist="normal", seed=24, shift=1)}.items():
@@ -576,7 +605,7 @@ def main():
             s = plant_step(plant, s, u)
         d["steps"] = np.int32(c["steps"])
         record_rpgd_logged_outputs(d, lambda: make_controller("rpgd", cfg, "ODE", "Quad2D", (qlow, qhigh)), c["steps"])
-        np.savez_compressed(os.path.join(out_dir, f"rpgd_{name}.npz"), **d)
+        save_fixture(os.path.join(out_dir, f"rpgd_{name}.npz"), **d)
     # ---- third environment, S + C = 10 (> 8 network inputs), C = 3: the SAME unmodified reference optimizers on the hovercraft ----------
     # ODE and the 10-32-32-7 MLP predictor: pins the C = 3 shapes and, for the MLP, gives the device network a reference-driven fixture
     henv = O.HoverParams(terminal_weight=0.3, target_x=0.2, target_y=-0.1)
@@ -616,7 +645,7 @@ def main():
             d[f"traj_{t}"] = lv["rollout_trajectories_logged"].copy()
             s = plant_step(plant, s, u)
         d["steps"] = np.int32(c["steps"])
-        np.savez_compressed(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
+        save_fixture(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
 
     for name, c in {"hover_ode": dict(N=32, H=16, p=4, its=3, steps=4, resamp=2, dist="uniform", seed=33, shift=1, pred="ODE"),
                     "hover_mlp": dict(N=48, H=14, p=7, its=4, steps=3, resamp=2, dist="normal", seed=34, shift=1, pred="MLP")}.items():
@@ -659,7 +688,7 @@ def main():
             s = plant_step(plant, s, u)
         d["steps"] = np.int32(c["steps"])
         record_rpgd_logged_outputs(d, lambda: make_controller("rpgd", cfg, c["pred"], "Hover", (hlow, hhigh)), c["steps"])
-        np.savez_compressed(os.path.join(out_dir, f"rpgd_{name}.npz"), **d)
+        save_fixture(os.path.join(out_dir, f"rpgd_{name}.npz"), **d)
     pw.ENVIRONMENT = "CartPole"
 
     # ---- the TF-only optimizers (CEM, random-action, CEM + naive gradient) --------------------------------------------
@@ -708,7 +737,7 @@ def main():
             d[f"traj_{t}"] = lv["rollout_trajectories_logged"].copy()
             s = plant_step(plant, s, u)
         d["steps"] = np.int32(3)
-        np.savez_compressed(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
+        save_fixture(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
     inject_constants(env, dt, mlp_w)
 
     print("golden fixtures written to", out_dir)

@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (oracle construction from a golden fixture)."""
+import glob
 import os
 
 import numpy as np
@@ -8,8 +9,36 @@ from oracle import ctk_oracle as O
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+class _Parts(dict):
+    """a fixture joined from its part files (the same keys and arrays as one .npz)"""
+    @property
+    def files(self):
+        return list(self)
+
+
 def load(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """tests/golden/<name>, or its `<stem>.part<k>.npz` files where the whole would exceed the 1 MiB file limit
+    (make_golden.save_fixture: arrays larger than a part are stored flattened as `<key>@<i>` chunks beside `<key>@shape`)"""
+    path = os.path.join(GOLDEN, name)
+    if os.path.exists(path):
+        return np.load(path, allow_pickle=False)
+    parts = sorted(glob.glob(path[:-len(".npz")] + ".part*.npz"), key=lambda p: int(p[:-len(".npz")].rsplit(".part", 1)[1]))
+    if not parts:
+        raise FileNotFoundError(path)
+    merged, chunks = _Parts(), {}
+    for p in parts:
+        with np.load(p, allow_pickle=False) as z:
+            for k in z.files:
+                base, sep, i = k.partition("@")
+                if not sep:
+                    merged[base] = z[k]
+                    continue
+                merged.setdefault(base, None)                       # keep the recorded key order
+                chunks.setdefault(base, {})[i] = z[k]
+    for base, c in chunks.items():
+        shape = tuple(int(x) for x in c.pop("shape"))
+        merged[base] = np.concatenate([c[i] for i in sorted(c, key=int)]).reshape(shape)
+    return merged
 
 
 def env_from(d):

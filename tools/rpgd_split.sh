@@ -8,6 +8,6 @@
 # The variants are loaded through CTK_HIP_LIBRARY (control_toolkit_amd/_capi.py: library_path); the product library is never overwritten.
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/split; mkdir -p $O
-run() { python bench.py --workload rpgd_cfg4 --steps 60 --warmup 10 --no-cpu-baseline --no-modes 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', 'ms_per_step', round(d['ms_per_step'],4), 'kernel_us', d['roofline'].get('kernel_us'))"; }
+run() { python bench.py --full --workload rpgd_cfg4 --steps 60 --warmup 10 --no-cpu-baseline --no-modes 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', 'ms_per_step', round(d['ms_per_step'],4), 'kernel_us', d['roofline'].get('kernel_us'))"; }
 run full | tee $O/split.txt
 for v in "$@"; do CTK_HIP_LIBRARY=$PWD/tools/_variants/libctk_hip_$v.so run $v | tee -a $O/split.txt; done
