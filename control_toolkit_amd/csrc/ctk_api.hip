@@ -671,7 +671,7 @@ int resident_launch(ctk_handle* h, uint32_t first_req) {
     h->res_running = true;
     ++h->res_launches;
     if (h->res_dominant_saved.empty()) h->res_dominant_saved = h->dominant;      // restored when the kernel is ended
-    h->dominant = ctk_mppi_resident_name(h->env);
+    h->dominant = ctk_mppi_resident_name(h->env, (int)h->N, h->P);
     return CTK_OK;
 }
 

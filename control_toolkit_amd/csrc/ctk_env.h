@@ -18,6 +18,7 @@
 // keeps its hand-tuned kernels (ctk_mppi.hip, ctk_sampled.hip, ctk_rpgd.hip); its specialisation here wraps the same
 // device functions, so "generic CartPole" and "tuned CartPole" are the same arithmetic (tests/test_gpu_env.py).
 #pragma once
+#include <type_traits>
 #include "ctk_device.h"
 
 template <int ENV>
@@ -77,6 +78,30 @@ struct Env<CTK_ENV_CARTPOLE> {
                 ode_substep(k, st, f[0], sn2, cs2);
             }
         }
+        s[0] = st.x; s[1] = st.v; s[2] = st.th; s[3] = st.om;
+    }
+    // the FAST recurrence with sin / cos carried one step ahead (recur_env_range, PIPE): lead() forms the pair of a range's first angle;
+    // cost_step_lead<NEXT>() forms the pair of the NEXT angle (theta + dt omega, the operation ode_cost_substep updates theta with) beside
+    // this step's cost and dynamics, which consume the carried pair.  Two independent chains per step in one instruction stream instead of
+    // one twice as long.  The same operations on the same operands as cost_step<true>: bit for bit its state, csum and amax.
+    static constexpr bool PIPELINED = true;
+    struct Lead {
+        float sn, cs;
+    };
+    CTK_DEV static Lead lead_angle(float th, float& amax) {
+        Lead l;
+        ctk_sincosf_fast(th, &l.sn, &l.cs);
+        amax = fmaxf(amax, fabsf(th));
+        return l;
+    }
+    CTK_DEV static Lead lead(const float (&s)[S], float& amax) { return lead_angle(s[2], amax); }
+    template <bool NEXT>
+    CTK_DEV static void cost_step_lead(const K& k, float (&s)[S], const float (&f)[C], float& csum, float& amax, Lead& l) {
+        State4 st{s[0], s[1], s[2], s[3]};
+        Lead nl{};
+        if constexpr (NEXT) nl = lead_angle(fmaf(k.dt, st.om, st.th), amax);
+        ode_cost_substep(k, st, f[0], l.sn, l.cs, csum);
+        if constexpr (NEXT) l = nl;
         s[0] = st.x; s[1] = st.v; s[2] = st.th; s[3] = st.om;
     }
     // ---- hooks of the descent kernels (ctk_generic.hip: ctk_g_rpgd_descent): the forward pass of a gradient iteration needs
@@ -519,13 +544,46 @@ CTK_DEV void store_state(float* dst, const float (&s)[S]) {
     }
 }
 
+// environments with the pipelined FAST recurrence (Env::PIPELINED: Env::lead / Env::cost_step_lead, see CartPole)
+template <int ENV, class = void>
+struct env_pipelined : std::false_type {};
+template <int ENV>
+struct env_pipelined<ENV, std::void_t<decltype(Env<ENV>::PIPELINED)>> : std::bool_constant<Env<ENV>::PIPELINED> {};
+
 // PREP: F holds the raw inputs u (the affine-sampled kernels keep them for the plans they write out); Env::prep_input is applied here
-template <int ENV, bool WRITE_TRAJ, bool FAST, bool PREP = false>
+// PIPE (FAST only, env_pipelined environments): sin / cos of the angle one step ahead (Env::cost_step_lead); the range's last step is
+// peeled, so that the pair of the angle AFTER the range is neither formed nor counted in amax — a split range forms it again at the next
+// range's entry, from the same angle.  The same results, bit for bit, as the loop below.
+template <int ENV, bool WRITE_TRAJ, bool FAST, bool PREP = false, bool PIPE = false>
 CTK_DEV void recur_env_range(const typename Env<ENV>::K& k, float* traj, bool valid, const float* F, int hb, int he,
                              float (&s)[Env<ENV>::S], float& csum, float& amax) {
     using E = Env<ENV>;
     constexpr int C = E::C, S = E::S;
     if (hb >= he) return;
+    if constexpr (PIPE) {
+        static_assert(FAST && env_pipelined<ENV>::value, "the pipelined recurrence is the FAST path of a PIPELINED environment");
+        typename E::Lead l = E::lead(s, amax);
+        float f[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) f[c] = PREP ? E::prep_input(k, F[hb * C + c], c) : F[hb * C + c];
+#pragma unroll 2
+        for (int h = hb; h < he - 1; ++h) {
+            float fn[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) fn[c] = F[(h + 1) * C + c];
+            if constexpr (WRITE_TRAJ) {
+                if (valid && traj) store_state<S>(traj + (size_t)h * S, s);
+            }
+            E::template cost_step_lead<true>(k, s, f, csum, amax, l);
+#pragma unroll
+            for (int c = 0; c < C; ++c) f[c] = PREP ? E::prep_input(k, fn[c], c) : fn[c];
+        }
+        if constexpr (WRITE_TRAJ) {
+            if (valid && traj) store_state<S>(traj + (size_t)(he - 1) * S, s);
+        }
+        E::template cost_step_lead<false>(k, s, f, csum, amax, l);
+        return;
+    }
     float fn[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) fn[c] = F[hb * C + c];

@@ -27,7 +27,8 @@ inline const char* ctk_kernel_name(const char* fmt, int a = 0, int b = 0, int c 
 }
 
 // ---- ctk_mppi.hip ---------------------------------------------------------------------------
-const char* ctk_mppi_rollout_name(int pred, bool log, int N, bool identity_interp = false, bool have_samples = true, bool p2p = false, int H = 0);
+const char* ctk_mppi_rollout_name(int pred, bool log, int N, bool identity_interp = false, bool have_samples = true, bool p2p = false, int H = 0,
+                                  int form = 0);
 int ctk_mppi_num_blocks(int N, int pred);   // workgroups = block records of one rollout launch (64 trajectories each; GRU: 16)
 bool ctk_mppi_uses_throughput_kernel(int pred, int N);
 size_t ctk_mppi_rollout_lds(int P, int H, int pred = 0, int N = 1 << 30, int C = 1);
@@ -46,6 +47,17 @@ constexpr int CTK_MPPI_FUSE_MAX_BLOCKS_LL_NARROW = 512, CTK_MPPI_FUSE_MAX_WORDS_
 inline bool ctk_ll_records_ok(int blocks, int cols) {
     return blocks <= CTK_MPPI_FUSE_MAX_BLOCKS_LL ||
            (blocks <= CTK_MPPI_FUSE_MAX_BLOCKS_LL_NARROW && blocks * (2 + cols) <= CTK_MPPI_FUSE_MAX_WORDS_LL_NARROW);
+}
+// Forms of the 4-wave rollout kernel (ctk_mppi.hip: ctk_mppi_rollout / ctk_mppi_resident), chosen per launch.  Bits:
+//   WIDE_TAIL  the {value, seq} tail of more than CTK_MPPI_FUSE_MAX_BLOCKS_LL records or CTK_MPPI_LL_NARROW_WORDS words: the 16-deep
+//              poll batch and the sliced merge of many narrow records (a configs[4] shard).  Without it the tail has only the 8-deep
+//              batch and one thread per column — what a launch within those sizes runs in either form, so the results do not depend on it
+//   OLD_RECUR  the recurrence without sin / cos one step ahead (ctk_env.h: recur_env_range): diagnostic switch CTK_MPPI_OLD_RECUR,
+//              bit for bit the same results (tests/test_gpu_mppi_pipelined.py)
+constexpr int CTK_MPPI_FORM_WIDE_TAIL = 1, CTK_MPPI_FORM_OLD_RECUR = 2;
+constexpr int CTK_MPPI_LL_NARROW_WORDS = 8 * 256;   // one 8-deep poll batch of the 256-thread merging workgroup
+inline bool ctk_ll_tail_wide(int blocks, int cols) {
+    return blocks > CTK_MPPI_FUSE_MAX_BLOCKS_LL || blocks * (2 + cols) > CTK_MPPI_LL_NARROW_WORDS;
 }
 // can a rollout launch of `blocks` workgroups merge and update in-launch?  (have_ll: the handle owns the LL word buffer)
 bool ctk_mppi_fusable(int P, int blocks, bool have_ll);
@@ -109,7 +121,7 @@ hipError_t ctk_launch_mppi_resident(hipStream_t st, int env, const float* params
                                     float* u_nom0, float* u_nom1, float* parts, const MppiFuse& fuse, const CtkResidentBox* box_dev, int box_local,
                                     CtkResidentStat* stat_dev, CtkResidentBox* relay, double idle_us, uint32_t first_req, void* args_dev, void* args_host);
 constexpr size_t CTK_RES_ARGS_BYTES = 1024;   // device + host staging block for the resident kernel's argument struct
-const char* ctk_mppi_resident_name(int env);
+const char* ctk_mppi_resident_name(int env, int N, int P);   // N rollouts, P inducing points (per control input)
 const char* ctk_mppi_rollout_env_name(int env, bool log);
 hipError_t ctk_launch_mppi_merge_partial(hipStream_t st, const float* parts, int n_parts, int per_block, int P,
                                          float neg_inv_lbd, float* out_rec);

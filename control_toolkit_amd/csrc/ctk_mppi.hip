@@ -152,6 +152,9 @@ struct FuseArgs {
 // recurrence through Env::cost_step, the input-only cost terms through Env::input_cost; CartPole is Env<0>, C = 1.  The network
 // predictors' instantiations are CartPole's (other environments: ctk_generic_net.hip).
 // P_ = inducing points; pmagic_ = magic of the P_*C sample columns of a row.
+// FORM (ctk_launch.h: CTK_MPPI_FORM_*): the four-argument kernel is FORM 0 — the tail of at most CTK_MPPI_FUSE_MAX_BLOCKS_LL records and
+// CTK_MPPI_LL_NARROW_WORDS words (one 8-deep poll batch, one thread per column in the merge), the pipelined recurrence; the launcher
+// takes the five-argument overload for the other forms (many records; the previous recurrence, a diagnostic switch).  One body text.
 template <int ENV, int PRED, bool LOG, bool P2P = false>
 __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_rollout(const float* __restrict__ samples,
                                                                const float* __restrict__ u_nom,
@@ -159,6 +162,18 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_rollout(const float* __re
                                                                const float* __restrict__ wperm,
                                                                float* __restrict__ parts, int N_, int H_, int P_,
                                                                uint32_t pmagic_, RolloutArgs a_in, typename Env<ENV>::K k, MppiK m, FuseArgs fz) {
+    constexpr int FORM = 0;
+    extern __shared__ float lds[];
+#include "ctk_mppi_body.inc"
+}
+template <int ENV, int PRED, bool LOG, bool P2P, int FORM>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_rollout(const float* __restrict__ samples,
+                                                               const float* __restrict__ u_nom,
+                                                               const InterpEntry* __restrict__ interp,
+                                                               const float* __restrict__ wperm,
+                                                               float* __restrict__ parts, int N_, int H_, int P_,
+                                                               uint32_t pmagic_, RolloutArgs a_in, typename Env<ENV>::K k, MppiK m, FuseArgs fz) {
+    static_assert(FORM != 0, "FORM 0 is the four-argument kernel");
     extern __shared__ float lds[];
 #include "ctk_mppi_body.inc"
 }
@@ -202,7 +217,7 @@ struct ResidentArgs {
     FuseArgs fz0;
 };
 
-template <int ENV>
+template <int ENV, int FORM>
 __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_resident(const ResidentArgs<typename Env<ENV>::K>* __restrict__ ra,
                                                                 const CtkResidentBox* box, int box_local, CtkResidentStat* stat, CtkResidentBox* relay,
                                                                 unsigned long long idle_ticks, uint32_t first_req) {
@@ -668,13 +683,31 @@ static bool tps_resident(int H) {
     return on && (size_t)64 * (H | 1) * sizeof(float) <= 16 * 1024;
 }
 
-// name of the kernel ctk_launch_mppi_rollout runs for these arguments (identity_interp as RolloutArgs carries it: period 1 AND P == H)
-const char* ctk_mppi_rollout_name(int pred, bool log, int N, bool identity_interp, bool have_samples, bool p2p, int H) {
+// the previous recurrence (ctk_launch.h: CTK_MPPI_FORM_OLD_RECUR) — diagnostic switch: A/B and the bit-identity test
+static bool mppi_old_recur() {
+    static const bool on = getenv("CTK_MPPI_OLD_RECUR") != nullptr;
+    return on;
+}
+// the form of a 4-wave launch of `blocks` records of `cols` columns (fz.ll: the {value, seq} tail); the old recurrence is the
+// analytic predictor's only
+static int mppi_form(int kp, int blocks, int cols, bool ll) {
+    return (ll && ctk_ll_tail_wide(blocks, cols) ? CTK_MPPI_FORM_WIDE_TAIL : 0) | (kp == CTK_PRED_ODE && mppi_old_recur() ? CTK_MPPI_FORM_OLD_RECUR : 0);
+}
+// ... of an environment's analytic-predictor launch (one recurrence unless env_pipelined)
+template <int ENV>
+static int mppi_env_form(int blocks, int cols, bool ll) {
+    return mppi_form(CTK_PRED_ODE, blocks, cols, ll) & (env_pipelined<ENV>::value ? ~0 : ~CTK_MPPI_FORM_OLD_RECUR);
+}
+
+// name of the kernel ctk_launch_mppi_rollout runs for these arguments (identity_interp as RolloutArgs carries it: period 1 AND P == H;
+// form: the launch's CTK_MPPI_FORM_* bits, known to the launcher)
+const char* ctk_mppi_rollout_name(int pred, bool log, int N, bool identity_interp, bool have_samples, bool p2p, int H, int form) {
     const int tf = throughput_form(pred, N, have_samples, identity_interp);
     if (tf == 2) return ctk_kernel_name("ctk_mppi_rollout_tps<%4$s, %5$s>", 0, 0, 0, log ? "true" : "false", (H > 0 && tps_resident(H)) ? "true" : "false");
     if (tf == 1) return log ? "ctk_mppi_rollout_tp<true>" : "ctk_mppi_rollout_tp<false>";
-    // template arguments <environment, predictor form, materialise, peer-to-peer tail>: what rocprofv3's kernel trace shows
+    // template arguments <environment, predictor form, materialise, peer-to-peer tail[, form]>: what rocprofv3's kernel trace shows
     const int kp = pred == CTK_PRED_ODE ? CTK_PRED_ODE : pred == CTK_PRED_GRU ? CTK_PRED_GRU : kernel_pred(pred, N);
+    if (form != 0) return ctk_kernel_name("ctk_mppi_rollout<0, %1$d, %4$s, %5$s, %2$d>", kp, form, 0, log ? "true" : "false", p2p ? "true" : "false");
     return ctk_kernel_name("ctk_mppi_rollout<0, %d, %4$s, %5$s>", kp, 0, 0, log ? "true" : "false", p2p ? "true" : "false");
 }
 
@@ -709,7 +742,7 @@ hipError_t ctk_launch_mppi_rollout(hipStream_t st, int pred, const RolloutArgs& 
                                    const float* samples, const float* u_nom, const float* wperm, float* parts, bool log,
                                    const MppiFuse& fuse, hipEvent_t e0, hipEvent_t e1, const char** ran) {
     const dim3 grid(ctk_mppi_num_blocks(a.N, pred)), block(MPPI_BLOCK);
-    if (ran) *ran = ctk_mppi_rollout_name(pred, log, a.N, a.identity_interp != 0, samples != nullptr, fuse.mode == 3, a.H);
+    if (ran) *ran = ctk_mppi_rollout_name(pred, log, a.N, a.identity_interp != 0, samples != nullptr, fuse.mode == 3, a.H);   // (4-wave: below)
     if (const int tf = throughput_form(pred, a.N, samples != nullptr, a.identity_interp != 0)) {
         if (tf == 2) {
             if (tps_resident(a.H)) {
@@ -738,18 +771,33 @@ hipError_t ctk_launch_mppi_rollout(hipStream_t st, int pred, const RolloutArgs& 
     fz.ll = (fuse.mode != 0 && fz.stage_ok) ? fuse.ll : nullptr;
     fz.p2p = static_cast<const P2PArgs*>(fuse.p2p); fz.p2p_seq = fuse.p2p_seq;
     fz.up = MppiUpdateArgs{nullptr, nullptr, nullptr, nullptr, a.H, a.interp, u_nom, fuse.u_nom_out, a.lo[0], a.hi[0], fuse.u_dev, fuse.u_host, fuse.seq};
-#define CTK_MPPI_LAUNCH(PREDV, LOGV, P2PV) CTK_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PREDV, LOGV, P2PV>), grid, block, lds, st, e0, e1, samples, u_nom, a.interp, wperm, parts, a.N, a.H, a.P, a.p_magic, a, k, m, fz)
-#define CTK_MPPI_LAUNCH_PRED(PREDV)                                                            \
-    do {                                                                                       \
-        if (fuse.mode == 3) { if (log) CTK_MPPI_LAUNCH(PREDV, true, true); else CTK_MPPI_LAUNCH(PREDV, false, true); } \
-        else { if (log) CTK_MPPI_LAUNCH(PREDV, true, false); else CTK_MPPI_LAUNCH(PREDV, false, false); }             \
-    } while (0)
-    if (pred == CTK_PRED_ODE) CTK_MPPI_LAUNCH_PRED(CTK_PRED_ODE);
-    else if (kernel_pred(pred, a.N) == CTK_PRED_MLP_PAIR) CTK_MPPI_LAUNCH_PRED(CTK_PRED_MLP_PAIR);
-    else if (pred == CTK_PRED_MLP) CTK_MPPI_LAUNCH_PRED(CTK_PRED_MLP);
-    else CTK_MPPI_LAUNCH_PRED(CTK_PRED_GRU);
-#undef CTK_MPPI_LAUNCH_PRED
+    const int kp = pred == CTK_PRED_ODE ? CTK_PRED_ODE : kernel_pred(pred, a.N);
+    const int form = mppi_form(kp, (int)grid.x, a.P, fz.ll != nullptr);
+    if (ran) *ran = ctk_mppi_rollout_name(pred, log, a.N, a.identity_interp != 0, samples != nullptr, fuse.mode == 3, a.H, form);
+    using std::integral_constant;
+    auto launch = [&](auto pred_c, auto log_c, auto p2p_c) {
+        constexpr int PV = decltype(pred_c)::value;
+        constexpr bool LV = decltype(log_c)::value, XV = decltype(p2p_c)::value;
+        constexpr int W = CTK_MPPI_FORM_WIDE_TAIL, O = CTK_MPPI_FORM_OLD_RECUR;
+#define CTK_MPPI_LAUNCH(...) CTK_LAUNCH(__VA_ARGS__)      // (expands CTK_MPPI_ARGS first)
+#define CTK_MPPI_ARGS grid, block, lds, st, e0, e1, samples, u_nom, a.interp, wperm, parts, a.N, a.H, a.P, a.p_magic, a, k, m, fz
+        if (form == 0) CTK_MPPI_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PV, LV, XV>), CTK_MPPI_ARGS);
+        else if (form == W) CTK_MPPI_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PV, LV, XV, W>), CTK_MPPI_ARGS);
+        else if constexpr (PV == CTK_PRED_ODE) {       // the old recurrence: the analytic predictor's only (mppi_form)
+            if (form == O) CTK_MPPI_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PV, LV, XV, O>), CTK_MPPI_ARGS);
+            else CTK_MPPI_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PV, LV, XV, W | O>), CTK_MPPI_ARGS);
+        }
 #undef CTK_MPPI_LAUNCH
+#undef CTK_MPPI_ARGS
+    };
+    auto launch_pred = [&](auto pred_c) {
+        if (fuse.mode == 3) { if (log) launch(pred_c, std::true_type{}, std::true_type{}); else launch(pred_c, std::false_type{}, std::true_type{}); }
+        else { if (log) launch(pred_c, std::true_type{}, std::false_type{}); else launch(pred_c, std::false_type{}, std::false_type{}); }
+    };
+    if (pred == CTK_PRED_ODE) launch_pred(integral_constant<int, CTK_PRED_ODE>{});
+    else if (kp == CTK_PRED_MLP_PAIR) launch_pred(integral_constant<int, CTK_PRED_MLP_PAIR>{});
+    else if (pred == CTK_PRED_MLP) launch_pred(integral_constant<int, CTK_PRED_MLP>{});
+    else launch_pred(integral_constant<int, CTK_PRED_GRU>{});
     return hipGetLastError();
 }
 
@@ -772,8 +820,23 @@ hipError_t ctk_launch_mppi_rollout_env(hipStream_t st, int env, const float* par
         fz.up.C = E::C;
         for (int c = 0; c < E::C; ++c) { fz.up.lo_c[c] = a.lo[c]; fz.up.hi_c[c] = a.hi[c]; }
         const uint32_t pmagic = PC >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)PC - 1) / (uint64_t)PC) : 0u;
-        if (log) CTK_LAUNCH((ctk_mppi_rollout<EV, CTK_PRED_ODE, true, false>), grid, block, lds, st, e0, e1, samples, u_nom, a.interp, (const float*)nullptr, parts, a.N, a.H, a.P, pmagic, a, k, m, fz);
-        else CTK_LAUNCH((ctk_mppi_rollout<EV, CTK_PRED_ODE, false, false>), grid, block, lds, st, e0, e1, samples, u_nom, a.interp, (const float*)nullptr, parts, a.N, a.H, a.P, pmagic, a, k, m, fz);
+        const int form = mppi_env_form<EV>((int)grid.x, PC, fz.ll != nullptr);
+        auto launch = [&](auto log_c, auto form_c) {
+            CTK_LAUNCH((ctk_mppi_rollout<EV, CTK_PRED_ODE, decltype(log_c)::value, false, decltype(form_c)::value>), grid, block, lds, st, e0, e1, samples,
+                       u_nom, a.interp, (const float*)nullptr, parts, a.N, a.H, a.P, pmagic, a, k, m, fz);
+        };
+        auto launch_form = [&](auto log_c) {
+            using std::integral_constant;
+            if (form == 0) CTK_LAUNCH((ctk_mppi_rollout<EV, CTK_PRED_ODE, decltype(log_c)::value, false>), grid, block, lds, st, e0, e1, samples, u_nom,
+                                      a.interp, (const float*)nullptr, parts, a.N, a.H, a.P, pmagic, a, k, m, fz);
+            else if (form == CTK_MPPI_FORM_WIDE_TAIL) launch(log_c, integral_constant<int, CTK_MPPI_FORM_WIDE_TAIL>{});
+            else if constexpr (env_pipelined<EV>::value) {       // (the other environments have one recurrence)
+                if (form == CTK_MPPI_FORM_OLD_RECUR) launch(log_c, integral_constant<int, CTK_MPPI_FORM_OLD_RECUR>{});
+                else launch(log_c, integral_constant<int, CTK_MPPI_FORM_WIDE_TAIL | CTK_MPPI_FORM_OLD_RECUR>{});
+            }
+        };
+        if (log) launch_form(std::true_type{});
+        else launch_form(std::false_type{});
     });
     return hipGetLastError();
 }
@@ -800,11 +863,27 @@ hipError_t ctk_launch_mppi_resident(hipStream_t st, int env, const float* params
         *hostra = RA{a.interp, parts, a.N, a.H, a.P, pmagic, u_nom0, u_nom1, a, k, m, fz};
         const hipError_t ce = hipMemcpyAsync(args_dev, hostra, sizeof(RA), hipMemcpyHostToDevice, st);
         if (ce != hipSuccess) return ce;
-        hipLaunchKernelGGL((ctk_mppi_resident<EV>), grid, block, lds, st, static_cast<const RA*>(args_dev), box_dev, box_local, stat_dev, relay, ticks, first_req);
+        const int form = mppi_env_form<EV>((int)grid.x, PC, true);
+        auto launch = [&](auto form_c) {
+            hipLaunchKernelGGL((ctk_mppi_resident<EV, decltype(form_c)::value>), grid, block, lds, st, static_cast<const RA*>(args_dev), box_dev, box_local,
+                               stat_dev, relay, ticks, first_req);
+        };
+        using std::integral_constant;
+        if (form == 0) launch(integral_constant<int, 0>{});
+        else if (form == CTK_MPPI_FORM_WIDE_TAIL) launch(integral_constant<int, CTK_MPPI_FORM_WIDE_TAIL>{});
+        else if constexpr (env_pipelined<EV>::value) {
+            if (form == CTK_MPPI_FORM_OLD_RECUR) launch(integral_constant<int, CTK_MPPI_FORM_OLD_RECUR>{});
+            else launch(integral_constant<int, CTK_MPPI_FORM_WIDE_TAIL | CTK_MPPI_FORM_OLD_RECUR>{});
+        }
     });
     return hipGetLastError();
 }
-const char* ctk_mppi_resident_name(int env) { return ctk_kernel_name("ctk_mppi_resident<%d>", env); }
+// (the form of a resident launch: ctk_launch_mppi_resident; the handle names the kernel before it knows the launch)
+const char* ctk_mppi_resident_name(int env, int N, int P) {
+    int form = 0;
+    CTK_FOR_ENV(env, EV, { form = mppi_env_form<EV>((N + MPPI_TRAJ - 1) / MPPI_TRAJ, P * Env<EV>::C, true); });
+    return ctk_kernel_name("ctk_mppi_resident<%d, %d>", env, form);
+}
 
 size_t ctk_mppi_rollout_env_lds(int env, int P, int H, int N) {
     int C = 1;

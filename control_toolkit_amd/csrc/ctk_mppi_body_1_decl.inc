@@ -4,7 +4,7 @@
 //   1 decl    step-invariant definitions: the LDS carve, indices           4 phase_a  inputs of the first S1 steps (all four waves)
 //   2 pro1    per-step tables + the sample tile into LDS                   5 post     recurrence (+ phase B), epilogue, record hand-off, merge tail
 //   3 defs    S1, corr_keep, the prologue2 lambda
-// Expects in scope: ENV, PRED, LOG, P2P; samples, u_nom, interp, wperm, parts, N_, H_, P_, pmagic_, a_in, k, m, fz; `extern __shared__ float lds[]`.
+// Expects in scope: ENV, PRED, LOG, P2P, FORM (ctk_launch.h: CTK_MPPI_FORM_*); samples, u_nom, interp, wperm, parts, N_, H_, P_, pmagic_, a_in, k, m, fz; `extern __shared__ float lds[]`.
     using E = Env<ENV>;
     constexpr int C = E::C, S = E::S;
     static_assert(PRED == CTK_PRED_ODE || ENV == CTK_ENV_CARTPOLE, "network predictors: CartPole instantiations only");
@@ -29,5 +29,7 @@
     const int n = row0 + lane;                 // wave 0's view: lane = trajectory of the workgroup
     const bool valid = lane < TRAJ && n < a.N;
     const bool use_ll = fz.mode != 0 && fz.ll != nullptr;   // kernel-argument uniform
+    constexpr bool WIDE_TAIL = (FORM & CTK_MPPI_FORM_WIDE_TAIL) != 0;   // the 16-deep poll and the sliced merge of many narrow records
+    constexpr bool PIPE = (FORM & CTK_MPPI_FORM_OLD_RECUR) == 0 && env_pipelined<ENV>::value;   // recurrence: sin / cos one step ahead
 
     const uint32_t ka_sink = kernarg_prefetch<sizeof(RolloutArgs) + sizeof(typename E::K) + sizeof(MppiK) + 5 * sizeof(void*) + 16 + sizeof(FuseArgs)>();

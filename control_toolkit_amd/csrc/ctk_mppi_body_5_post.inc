@@ -21,7 +21,7 @@
         }
         const bool single = E::fast_ok(k);
         if (wave == 0) {                           // steps [0, S1) while the others prepare [S1, H)
-            if (single) recur_env_range<ENV, LOG, true>(k, traj, valid, myF, 0, S1, sx, csum, amax);
+            if (single) recur_env_range<ENV, LOG, true, false, PIPE>(k, traj, valid, myF, 0, S1, sx, csum, amax);
         } else {
             const int Hb = (H - S1 + MPPI_WAVES - 2) / (MPPI_WAVES - 1);        // phase B: wave w takes its third of [S1, H)
             prologue2(lane, min(H, S1 + (wave - 1) * Hb), min(H, S1 + (wave - 1) * Hb + Hb), wave, corr_keep);
@@ -29,7 +29,7 @@
         __syncthreads();                           // waves 1..3 have been waiting here since ~step 4 of wave 0
         if (wave == 0) {
             if (single) {
-                recur_env_range<ENV, LOG, true>(k, traj, valid, myF, S1, H, sx, csum, amax);
+                recur_env_range<ENV, LOG, true, false, PIPE>(k, traj, valid, myF, S1, H, sx, csum, amax);
                 if constexpr (LOG) {
                     if (valid && traj) store_state<S>(traj + (size_t)H * S, sx);
                 }
@@ -140,7 +140,8 @@
             bool expired = false;                 // a bounded poll ran out: surfaced to the host through the error word
             // LLW words in flight per thread: the first pass over a thread's words is one pipelined batch of loads, not LLW round trips.
             // A SECOND batch starts only when the first has arrived, i.e. after the slowest workgroup's record — a whole extra round trip
-            // (~2 us) behind the launch's critical path: up to 16 words per thread go out as ONE batch (a configs[4] shard: 13 per thread)
+            // (~2 us) behind the launch's critical path: up to 16 words per thread go out as ONE batch (a configs[4] shard: 13 per thread).
+            // Only the WIDE_TAIL form carries the 16-deep batch: the launcher takes it exactly when the records exceed one 8-deep batch.
             auto poll = [&](auto llw_tag) {
                 constexpr int LLW = decltype(llw_tag)::value;
                 for (int i0 = t; i0 < tot; i0 += MPPI_BLOCK * LLW) {
@@ -165,16 +166,20 @@
                     }
                 }
             };
-            if (tot > MPPI_BLOCK * 8 && tot <= MPPI_BLOCK * 16) poll(std::integral_constant<int, 16>{});
-            else poll(std::integral_constant<int, 8>{});
+            if constexpr (WIDE_TAIL) {
+                if (tot > MPPI_BLOCK * 8 && tot <= MPPI_BLOCK * 16) poll(std::integral_constant<int, 16>{});
+                else poll(std::integral_constant<int, 8>{});
+            } else {
+                poll(std::integral_constant<int, 8>{});
+            }
             // ctk_api.hip:finish_step turns a non-zero error word (the dword behind {u, seq}) into CTK_ERR_STATE
             if (expired && fz.up.u_host)
                 __hip_atomic_store(reinterpret_cast<uint32_t*>(fz.up.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __syncthreads();
             const size_t scratch_floats = 8 + P + 1 + min(nb, MERGE_CHUNK) + (size_t)tot + MERGE_BLOCK;   // (+ the column slices of many narrow records)
             if (scratch_floats <= (size_t)(w0_s - lds)) { fz.up.w0_l = w0_s; fz.up.w1_l = w1_s; fz.up.un_l = un_s; fz.up.i0_l = i0_s; }
-            if (fz.mode == 1) mppi_merge_block<true, 0, C>(lds, nullptr, nb, P, m.neg_inv_lbd, nullptr, fz.up, 2);
-            else mppi_merge_block<false, 0, C>(lds, nullptr, nb, P, m.neg_inv_lbd, fz.out_rec, fz.up, 2);
+            if (fz.mode == 1) mppi_merge_block<true, 0, C, WIDE_TAIL>(lds, nullptr, nb, P, m.neg_inv_lbd, nullptr, fz.up, 2);
+            else mppi_merge_block<false, 0, C, WIDE_TAIL>(lds, nullptr, nb, P, m.neg_inv_lbd, fz.out_rec, fz.up, 2);
             if constexpr (P2P) {
                 // sharded step over peer-to-peer stores, all in this launch: the shard's record (just written to
                 // fz.out_rec = this rank's slot of its own exchange buffer by this block) goes to every peer, their
@@ -214,8 +219,8 @@
             // whenever the scratch ends below them
             const size_t scratch_floats = 8 + P + 1 + min((int)gridDim.x, MERGE_CHUNK) + (fz.stage_ok ? (size_t)gridDim.x * (2 + P) + MERGE_BLOCK : 0);
             if (scratch_floats <= (size_t)(w0_s - lds)) { fz.up.w0_l = w0_s; fz.up.w1_l = w1_s; fz.up.un_l = un_s; fz.up.i0_l = i0_s; }
-            if (fz.mode == 1) mppi_merge_block<true, 1, C>(lds, parts, (int)gridDim.x, P, m.neg_inv_lbd, nullptr, fz.up, fz.stage_ok != 0 ? 1 : 0);
-            else mppi_merge_block<false, 1, C>(lds, parts, (int)gridDim.x, P, m.neg_inv_lbd, fz.out_rec, fz.up, fz.stage_ok != 0 ? 1 : 0);
+            if (fz.mode == 1) mppi_merge_block<true, 1, C, WIDE_TAIL>(lds, parts, (int)gridDim.x, P, m.neg_inv_lbd, nullptr, fz.up, fz.stage_ok != 0 ? 1 : 0);
+            else mppi_merge_block<false, 1, C, WIDE_TAIL>(lds, parts, (int)gridDim.x, P, m.neg_inv_lbd, fz.out_rec, fz.up, fz.stage_ok != 0 ? 1 : 0);
             if (t == 0) __hip_atomic_store(fz.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }

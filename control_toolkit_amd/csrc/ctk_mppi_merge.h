@@ -45,7 +45,8 @@ struct MppiUpdateArgs {
 // scratch: >= 8 + (P + 1) + min(cnt, MERGE_CHUNK) floats of LDS, plus cnt*(2+P) more when `stage`
 // (all records fetched into LDS by ONE wide pass: one memory round trip instead of one per record).
 // CH: control inputs of the FINAL update (compile time: the C == 1 instantiations are CartPole's statement sequence, unchanged)
-template <bool FINAL, int SC1, int CH = 1>
+// MANY: the sliced column sums of many narrow records are compiled in (a caller that never merges more than 128 records leaves them out)
+template <bool FINAL, int SC1, int CH = 1, bool MANY = true>
 CTK_DEV void mppi_merge_block(float* scratch, const float* base, int cnt, int P, float neg_inv_lbd, float* out_rec,
                               const MppiUpdateArgs& up, int stage) {
     float* red = scratch;             // [4] cross-wave scratch
@@ -91,7 +92,7 @@ CTK_DEV void mppi_merge_block(float* scratch, const float* base, int cnt, int P,
             a_acc += rec_at(c0 + i, 1) * sc;
         }
         __syncthreads();
-        if (stage != 0 && cnt > 128 && cnt <= MERGE_CHUNK && 2 * P <= MERGE_BLOCK) {
+        if (MANY && stage != 0 && cnt > 128 && cnt <= MERGE_CHUNK && 2 * P <= MERGE_BLOCK) {
             // many narrow records (a shard of configs[4]: 256 records of 11 columns): one thread per column would walk all of them with
             // 245 threads idle.  Thread (slice, column) sums every slices-th record; the slices meet through LDS in slice order.
             // (cnt > 128 with staged records did not exist before round 4: no earlier result changes its association)
