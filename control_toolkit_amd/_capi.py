@@ -16,14 +16,15 @@ _LIB_NAME = "libctk_hip.so"
 _lib = None
 
 OPTIMIZERS = {"mppi": 0, "cem": 1, "rpgd": 2, "random_action": 3, "gradient": 4, "cem_naive_grad": 5,
-              "cem_grad_bharadhwaj": 6}
+              "cem_grad_bharadhwaj": 6, "cem_gmm": 7}
 PREDICTORS = {"ODE": 0, "MLP": 1, "GRU": 2}
 ENVIRONMENTS = {"CartPole": 0, "Quad2D": 1, "Hover": 2}          # include/ctk_hip.h: enum ctk_environment
 MAX_STATES, MAX_INPUTS = 8, 4
 # CartPole's parameter names in id order (enum ctk_param); `environment_params(name)` asks the library for any environment's
 PARAMS = ("g", "m_cart", "m_pole", "L", "u_max", "M_fric", "J_fric", "target_position", "target_equilibrium",
           "dd_weight", "ep_weight", "ekp_weight", "cc_weight", "ccrc_weight", "R", "x_scale", "terminal_weight")
-BUFFERS = {"Q": 0, "J": 1, "TRAJ": 2, "U_NOM": 3, "STD": 4, "ADAM_M": 5, "ADAM_V": 6, "AGES": 7, "BEST_IDX": 8, "PLAN": 9, "AGES_LOGGED": 10}
+BUFFERS = {"Q": 0, "J": 1, "TRAJ": 2, "U_NOM": 3, "STD": 4, "ADAM_M": 5, "ADAM_V": 6, "AGES": 7, "BEST_IDX": 8, "PLAN": 9, "AGES_LOGGED": 10,
+           "MIX_MU": 11, "MIX_STD": 12, "MIX_PROB": 13, "MIX_LABEL": 14}   # CEM-GMM (include/ctk_hip.h: enum ctk_buffer)
 LOC_NONE, LOC_HOST, LOC_DEVICE = 0, 1, 2
 MLP_NUM_WEIGHTS = 1380
 
@@ -533,7 +534,8 @@ class CtkEngine:
         self._check(self._lib.ctk_read(self._h, BUFFERS[name], _ptr(buf), cap, C.byref(n)))
         out = buf[: n.value].copy()
         shapes = {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn), "STD": (1, H, Cn),
-                  "ADAM_M": (N, H, Cn), "ADAM_V": (N, H, Cn), "AGES": (N,), "PLAN": (N, H, Cn), "AGES_LOGGED": (N,)}
+                  "ADAM_M": (N, H, Cn), "ADAM_V": (N, H, Cn), "AGES": (N,), "PLAN": (N, H, Cn), "AGES_LOGGED": (N,),
+                  "MIX_MU": (2, H, Cn), "MIX_STD": (2, H, Cn), "MIX_PROB": (2,), "MIX_LABEL": (-1,)}
         if name == "BEST_IDX":
             return out.astype(np.int64)
         return out.reshape(shapes[name])

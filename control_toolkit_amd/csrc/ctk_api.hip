@@ -59,6 +59,11 @@ struct ctk_handle {
     float* d_unom[2] = {nullptr, nullptr};   // MPPI u_nom ping-pong / CEM mu in [0]
     int cur = 0;
     float* d_std = nullptr;     // CEM
+    float* d_mix = nullptr;     // CEM-GMM: mu[2][HC] | std[2][HC] | probs[2]
+    float* d_mix_label = nullptr;   // CEM-GMM: cluster of each elite of the last refit [K]
+    float* d_plans = nullptr;   // CEM-GMM: the clipped plans of one iteration [N,HC], the rollout's `samples`
+    bool gmm_in_rollout = false;     // CEM-GMM: sample inside the rollout kernel (ctk_affine_rollout_mix: analytic predictor, unless CTK_GMM_MATERIALIZE)
+    bool gmm_two_launches = false;   // CEM-GMM: CTK_GMM_TWO_LAUNCH at creation — labels and refit as two launches whatever K is (diagnostic)
     float* d_base = nullptr;    // affine rollout base/scale scratch [H] each
     float* d_scale = nullptr;
     int* d_idx = nullptr;       // best indices [N]
@@ -432,6 +437,7 @@ int dev_alloc(ctk_handle* h, T** p, size_t n) {
 int cem_iterations(const ctk_handle* h) {   // optimizer_cem_tf.py:92
     return (h->cfg.warmup && h->count == 0) ? h->cfg.warmup_iterations : h->cfg.cem_outer_it;
 }
+bool is_gmm(const ctk_handle* h) { return h->variant == CTK_OPT_CEM_GMM; }
 
 size_t samples_needed(const ctk_handle* h) {
     const size_t N = h->N, H = h->HC, P = h->PC;   // draws per rollout: [H,C] / [P,C] blocks
@@ -440,6 +446,7 @@ size_t samples_needed(const ctk_handle* h) {
         case CTK_OPT_CEM:
             if (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ)   // initial elites + (N-K) fresh samples per iteration
                 return (size_t)h->cfg.cem_best_k * H + (size_t)cem_iterations(h) * (N - (size_t)h->cfg.cem_best_k) * H;
+            if (is_gmm(h)) return (size_t)cem_iterations(h) * (N * H + N);   // per iteration: the normals, then one uniform per rollout
             return (size_t)cem_iterations(h) * N * H;
         case CTK_OPT_RANDOM_ACTION: return N * H;
         case CTK_OPT_RPGD:
@@ -527,8 +534,19 @@ int locate_buffer(ctk_handle* h, int which, const float** src_out, size_t* n_out
         case CTK_BUF_TRAJ:
             if (!h->d_traj) return fail(h, CTK_ERR_STATE, "ctk_read: trajectories not materialised (cfg.materialize_trajectories == 0)");
             src = h->d_traj; n = N * ((size_t)h->H + 1) * h->S; break;
-        case CTK_BUF_U_NOM: src = h->d_unom[h->cfg.optimizer == CTK_OPT_MPPI ? h->cur : 0]; n = H; break;
-        case CTK_BUF_STD: src = h->d_std; n = H; break;
+        case CTK_BUF_U_NOM:
+            if (is_gmm(h)) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_read: a CEM-GMM handle has no U_NOM; its means are CTK_BUF_MIX_MU [2,H,C] (weights: MIX_PROB)");
+            src = h->d_unom[h->cfg.optimizer == CTK_OPT_MPPI ? h->cur : 0]; n = H; break;
+        case CTK_BUF_STD:
+            if (is_gmm(h)) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_read: a CEM-GMM handle has no STD; its stdevs are CTK_BUF_MIX_STD [2,H,C] (weights: MIX_PROB)");
+            src = h->d_std; n = H; break;
+        case CTK_BUF_MIX_MU: case CTK_BUF_MIX_STD: case CTK_BUF_MIX_PROB: case CTK_BUF_MIX_LABEL:
+            if (!is_gmm(h)) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_read: the MIX_* buffers belong to CEM-GMM handles");
+            if (which == CTK_BUF_MIX_MU) { src = h->d_mix; n = 2 * H; }
+            else if (which == CTK_BUF_MIX_STD) { src = h->d_mix + 2 * H; n = 2 * H; }
+            else if (which == CTK_BUF_MIX_PROB) { src = h->d_mix + 4 * H; n = 2; }
+            else { src = h->d_mix_label; n = (size_t)h->cfg.cem_best_k; }
+            break;
         case CTK_BUF_BEST_IDX:
             if (h->idx_stale) {   // one-launch CEM step: the sorted elite indices are materialised from the last iteration's costs
                 HIP_TRY(h, ctk_launch_select_topk(h->stream, h->d_J, h->N, h->cfg.cem_best_k, h->d_idx));
@@ -965,10 +983,46 @@ int cem_bharadhwaj_step(ctk_handle* h, const float* s, const float* u_prev, cons
     return finish_step(h, u_out);
 }
 
+// ---- cem-gmm (variant of the CEM family) ----------------------------------------------------------
+// optimizer_cem_gmm_tf.py:98-129.  Per outer iteration (:57-95): sample + rollout, selection, cluster refit.  Then the shift and u.
+// Sampling, analytic predictor: inside the rollout (ctk_affine_rollout_mix stages both components' tables and picks per row).
+// Otherwise, or with CTK_GMM_MATERIALIZE=1: ctk_gmm_sample_plans writes the clipped plans and the handle's affine rollout evaluates
+// them as they are (samples = plans, base 0, scale 1: 0 + q*1 is exact and the clip idempotent — every environment and predictor
+// through launch_affine).  Same draws, same expression: the two forms agree bit for bit (tests/test_gpu_cem_gmm.py).
+int cem_gmm_step(ctk_handle* h, const float* s, const float* u_prev, const float* samples, int loc, float* u_out) {
+    const ctk_config& c = h->cfg;
+    const int its = cem_iterations(h);
+    const size_t n_norm = (size_t)h->N * h->HC, per_it = n_norm + (size_t)h->N;
+    const float* d_s = nullptr;
+    if (int rc = resolve_samples(h, samples, loc, per_it * its, &d_s)) return rc;
+    const bool log = c.materialize_trajectories != 0;
+    for (int it = 0; it < its; ++it) {
+        RolloutArgs a = make_args(h, s, u_prev, h->N, h->H);
+        a.stream_id = (uint32_t)it;
+        const float* z = d_s ? d_s + per_it * it : nullptr;
+        const uint32_t ustream = CTK_GMM_UNIFORM_STREAM + (uint32_t)it;
+        if (h->gmm_in_rollout) {
+            ProfSlot ps(h);
+            HIP_TRY(h, ctk_launch_affine_rollout_mix(h->stream, h->env, h->params, c.dt, c.intermediate_steps, a, z, z ? z + n_norm : nullptr,
+                                                     h->d_mix, ustream, log, ps.a, ps.b));
+        } else {
+            HIP_TRY(h, ctk_launch_gmm_sample_plans(h->stream, a, z, z ? z + n_norm : nullptr, h->d_mix, ustream, h->d_plans));
+            if (int rc = launch_affine(h, a, h->d_plans, 0, h->d_base, h->d_scale, log)) return rc;
+        }
+        HIP_TRY(h, ctk_launch_select_topk(h->stream, h->d_J, h->N, c.cem_best_k, h->d_idx));
+        HIP_TRY(h, ctk_launch_gmm_refit(h->stream, h->d_Q, h->d_idx, c.cem_best_k, h->HC, h->d_mix, h->d_mix_label, c.cem_stdev_min, 1.0e4f, h->HC,
+                                        h->gmm_two_launches));
+    }
+    HIP_TRY(h, ctk_launch_gmm_finish(h->stream, h->d_Q, h->d_idx, h->HC, h->C, h->d_mix, h->d_u, h->h_u_dev, h->seq, h->HC));
+    ++h->count;
+    return finish_step(h, u_out);
+}
+
 // ---- CEM --------------------------------------------------------------------------------------
 int cem_step(ctk_handle* h, const float* s, const float* u_prev, const float* samples, int loc, float* u_out) {
     if (int rc = check_predictor(h)) return rc;
     if (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ) return cem_bharadhwaj_step(h, s, u_prev, samples, loc, u_out);
+    if (is_gmm(h)) return cem_gmm_step(h, s, u_prev, samples, loc, u_out);
     const int its = cem_iterations(h);
     const size_t per_it = (size_t)h->N * h->HC;
     const float* d_s = nullptr;
@@ -1192,7 +1246,7 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
         return fail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_create: num_rollouts * (mpc_horizon + 1) * num_states must stay below 2^30 (32-bit element indices)");
     for (int c = 0; c < einfo->C; ++c)
         if (!(cfg->action_low[c] <= cfg->action_high[c])) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: action_low must be <= action_high for every control input");
-    if (cfg->optimizer < CTK_OPT_MPPI || cfg->optimizer > CTK_OPT_CEM_GRAD_BHARADHWAJ)
+    if (cfg->optimizer < CTK_OPT_MPPI || cfg->optimizer > CTK_OPT_CEM_GMM)
         return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: unknown optimizer");
     if (cfg->predictor < CTK_PRED_ODE || cfg->predictor > CTK_PRED_GRU) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: unknown predictor");
     if (cfg->predictor != CTK_PRED_ODE && einfo->S + einfo->C > 12)
@@ -1213,6 +1267,12 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
         if (cfg->intermediate_steps != 1)
             return fail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_create: the gradient kernels are built for intermediate_steps == 1");
     }
+    if (cfg->optimizer == CTK_OPT_CEM_GMM) {   // CEM machinery with a mixture as the sampling distribution
+        mapped.optimizer = CTK_OPT_CEM;
+        mapped.warmup = 0;                     // the reference has no warm-up for this optimizer (optimizer_cem_gmm_tf.py:106)
+        if (cfg->cem_best_k < 2)
+            return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: CEM-GMM needs cem_best_k >= 2 (the two best elites seed the two clusters; with one the second is empty)");
+    }
     const int variant = cfg->optimizer;
     cfg = &mapped;
     if (cfg->predictor != CTK_PRED_ODE && cfg->predictor != CTK_PRED_MLP && cfg->predictor != CTK_PRED_GRU)
@@ -1220,7 +1280,7 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     // the template kernels roll the analytic model out; the network predictors have (so far) CartPole-shaped MFMA kernels only
     // template kernels: every environment but CartPole; CartPole on request; and the gradient-based optimizers with the
     // recurrent predictor (reverse mode through the GRU = NetGru::Bwd of ctk_net.h; CartPole's 4-wave GRU kernels are forward only)
-    const bool grad_family = cfg->optimizer == CTK_OPT_RPGD || variant != cfg->optimizer;
+    const bool grad_family = cfg->optimizer == CTK_OPT_RPGD || (variant != cfg->optimizer && variant != CTK_OPT_CEM_GMM);
     // hidden widths of a network predictor (the <h1>H1-<h2>H2 of the reference's network names): 0 = 32; up to 32 the 32-unit kernels;
     // 33..64 (MLP) the 64-unit form of the one-wave template kernels (ctk_mlp_wide.h)
     const int hw1 = cfg->predictor_hidden1 ? cfg->predictor_hidden1 : 32, hw2 = cfg->predictor_hidden2 ? cfg->predictor_hidden2 : 32;
@@ -1305,11 +1365,19 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     TRY_CREATE(dev_alloc(h, &h->d_counter, 1));
     if (ctk_ll_records_ok((int)nblk, (int)PC) && !std::getenv("CTK_NO_LL"))
         TRY_CREATE(dev_alloc(h, &h->d_ll, nblk * (2 + PC)));
-    if (cfg->optimizer == CTK_OPT_CEM && ctk_cem_fusable(cfg->predictor, (int)N, (int)HC) && !std::getenv("CTK_NO_CEM_FUSED"))
+    if (cfg->optimizer == CTK_OPT_CEM && variant != CTK_OPT_CEM_GMM && ctk_cem_fusable(cfg->predictor, (int)N, (int)HC) && !std::getenv("CTK_NO_CEM_FUSED"))
         TRY_CREATE(dev_alloc(h, &h->d_cem_ll, ctk_cem_fused_ll_words((int)N, (int)HC)));   // tuned and template path alike
     TRY_CREATE(dev_alloc(h, &h->d_unom[0], HC));
     TRY_CREATE(dev_alloc(h, &h->d_unom[1], HC));
     TRY_CREATE(dev_alloc(h, &h->d_std, HC));
+    if (variant == CTK_OPT_CEM_GMM) {
+        TRY_CREATE(dev_alloc(h, &h->d_mix, 4 * HC + 2));
+        TRY_CREATE(dev_alloc(h, &h->d_mix_label, (size_t)cfg->cem_best_k));
+        TRY_CREATE(dev_alloc(h, &h->d_plans, N * HC));
+        h->gmm_two_launches = std::getenv("CTK_GMM_TWO_LAUNCH") != nullptr;
+        h->gmm_in_rollout = cfg->predictor == CTK_PRED_ODE && !std::getenv("CTK_GMM_MATERIALIZE") &&
+                            ctk_affine_rollout_mix_lds(h->env, (int)H) <= 160 * 1024;
+    }
     TRY_CREATE(dev_alloc(h, &h->d_base, HC));
     TRY_CREATE(dev_alloc(h, &h->d_scale, HC));
     TRY_CREATE(dev_alloc(h, &h->d_idx, N));
@@ -1365,6 +1433,7 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     if (h->d_cem_ll && h->variant == CTK_OPT_CEM && cfg->cem_best_k <= (int)N) h->dominant = ctk_cem_fused_name(h->env, mat);
     if (cfg->optimizer == CTK_OPT_MPPI && mppi_env_kernel(h)) h->dominant = ctk_mppi_rollout_env_name(h->env, mat);
     if (!descends && cfg->optimizer != CTK_OPT_MPPI && affine_env_kernel(h) && !(h->d_cem_ll && h->variant == CTK_OPT_CEM)) h->dominant = ctk_affine_rollout_env_name(h->env, mat);
+    if (h->gmm_in_rollout) h->dominant = ctk_affine_rollout_mix_name(h->env, mat);
     if (cfg->optimizer != CTK_OPT_RPGD) TRY_CREATE(ctk_reset(h, nullptr, CTK_LOC_NONE));
     HIP_CREATE(hipStreamSynchronize(h->stream));
     *out = h;
@@ -1385,7 +1454,8 @@ void ctk_destroy(ctk_handle* h) {
     for (auto& e : h->events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
     void* bufs[] = {h->d_interp, h->d_samples, h->d_J, h->d_Q, h->d_traj, h->d_parts, h->d_parts2, h->d_parts3, h->d_unom[0], h->d_unom[1],
                     h->d_std, h->d_base, h->d_scale, h->d_idx, h->d_u, h->d_weights, h->d_wperm, h->d_counter, h->d_ll, h->d_cem_ll, h->d_rec,
-                    h->d_pop[0], h->d_pop[1], h->d_m[0], h->d_m[1], h->d_v[0], h->d_v[1], h->d_ages[0], h->d_ages[1], h->d_bc, h->d_scratch, h->d_Jlog};
+                    h->d_pop[0], h->d_pop[1], h->d_m[0], h->d_m[1], h->d_v[0], h->d_v[1], h->d_ages[0], h->d_ages[1], h->d_bc, h->d_scratch, h->d_Jlog,
+                    h->d_mix, h->d_mix_label, h->d_plans};
     for (void* b : bufs) if (b) hipFree(b);
     if (h->d_shard_idx) hipFree(h->d_shard_idx);
     for (float* p : h->d_log) if (p) hipFree(p);
@@ -1436,6 +1506,16 @@ int ctk_reset(ctk_handle* h, const float* draws, int draws_loc) {
             h->cur = 0;
             return fill_rows(h, h->d_unom[0], mid, h->C, h->HC);
         case CTK_OPT_CEM: {  // optimizer_cem_tf.py:113-117 (self.u = 0.0)
+            if (is_gmm(h)) {   // optimizer_cem_gmm_tf.py:131-137: both components (mid, initial stdev), weights (0.5, 0.5); self.u is left alone
+                for (int k = 0; k < 2; ++k) {
+                    if (int rc = fill_rows(h, h->d_mix + k * h->HC, mid, h->C, h->HC)) return rc;
+                    if (int rc = fill_const(h, h->d_mix + (2 + k) * h->HC, h->cfg.cem_initial_action_stdev, h->HC)) return rc;
+                }
+                if (int rc = fill_const(h, h->d_mix + 4 * h->HC, 0.5f, 2)) return rc;
+                if (int rc = fill_const(h, h->d_mix_label, 0.0f, h->cfg.cem_best_k)) return rc;
+                if (int rc = fill_const(h, h->d_base, 0.0f, h->HC)) return rc;     // the rollouts take the sampled plans as they are
+                return fill_const(h, h->d_scale, 1.0f, h->HC);
+            }
             if (int rc = fill_rows(h, h->d_unom[0], mid, h->C, h->HC)) return rc;
             if (int rc = fill_const(h, h->d_std, h->cfg.cem_initial_action_stdev, h->HC)) return rc;
             // only optimizer_cem_tf.py:117 resets self.u; the gradient variants' resets leave it (and Adam) alone
@@ -1709,6 +1789,7 @@ int ctk_shard_iter_begin(ctk_handle* h, const float* s, const float* u_prev, con
     return guarded(h, [&]() -> int {
     const bool cem = h->cfg.optimizer == CTK_OPT_CEM;
     if (!cem && h->cfg.optimizer != CTK_OPT_RANDOM_ACTION) return fail(h, CTK_ERR_STATE, "ctk_shard_iter_begin: CEM / random-action handles only");
+    if (is_gmm(h)) return fail(h, CTK_ERR_STATE, "ctk_shard_iter_begin: a CEM-GMM handle cannot be sharded (the cluster labels need all K elites in one place); use ctk_step on one handle");
     if (h->variant != h->cfg.optimizer) return fail(h, CTK_ERR_UNSUPPORTED, "ctk_shard_iter_begin: not built for this optimizer variant");
     if (h->shard_pending) return fail(h, CTK_ERR_STATE, "ctk_shard_iter_begin: previous iteration not ended");
     if (int rc = check_predictor(h)) return rc;
@@ -1906,7 +1987,9 @@ size_t ctk_state_size(const ctk_handle* h) {
     const size_t H = h->HC, C = h->C;   // [H,C] rows; the optimizer's last output u is C floats
     switch (h->cfg.optimizer) {
         case CTK_OPT_MPPI: return H + C;
-        case CTK_OPT_CEM: return 2 * H + C + 1 + (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ ? 2 * (size_t)h->N * H + 1 : 0);
+        case CTK_OPT_CEM:
+            if (is_gmm(h)) return 4 * H + 2 + C + 1;   // mu[2,H,C] | std[2,H,C] | probs[2] | u[C] | count
+            return 2 * H + C + 1 + (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ ? 2 * (size_t)h->N * H + 1 : 0);
         case CTK_OPT_RANDOM_ACTION: return C;
         case CTK_OPT_RPGD: return 3 * (size_t)h->N * H + (size_t)h->N + C + 2;
     }
@@ -1926,7 +2009,13 @@ int ctk_get_state(ctk_handle* h, float* dst, size_t cap) {
     };
     switch (h->cfg.optimizer) {
         case CTK_OPT_MPPI: HIP_TRY(h, pull(h->d_unom[h->cur], H)); HIP_TRY(h, pull(h->d_u, C)); break;
-        case CTK_OPT_CEM: HIP_TRY(h, pull(h->d_unom[0], H)); HIP_TRY(h, pull(h->d_std, H)); HIP_TRY(h, pull(h->d_u, C));
+        case CTK_OPT_CEM:
+            if (is_gmm(h)) {
+                HIP_TRY(h, pull(h->d_mix, 4 * H + 2)); HIP_TRY(h, pull(h->d_u, C));
+                HIP_TRY(h, hipStreamSynchronize(h->stream)); dst[o++] = (float)h->count;
+                break;
+            }
+            HIP_TRY(h, pull(h->d_unom[0], H)); HIP_TRY(h, pull(h->d_std, H)); HIP_TRY(h, pull(h->d_u, C));
             HIP_TRY(h, hipStreamSynchronize(h->stream)); dst[o++] = (float)h->count;
             if (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ) {   // the Keras optimizer's persistent moments and step count
                 HIP_TRY(h, pull(h->d_m[0], (size_t)h->N * H)); HIP_TRY(h, pull(h->d_v[0], (size_t)h->N * H));
@@ -1961,7 +2050,13 @@ int ctk_set_state(ctk_handle* h, const float* src, size_t n) {
     };
     switch (h->cfg.optimizer) {
         case CTK_OPT_MPPI: HIP_TRY(h, push(h->d_unom[h->cur], H)); HIP_TRY(h, push(h->d_u, C)); break;
-        case CTK_OPT_CEM: HIP_TRY(h, push(h->d_unom[0], H)); HIP_TRY(h, push(h->d_std, H)); HIP_TRY(h, push(h->d_u, C));
+        case CTK_OPT_CEM:
+            if (is_gmm(h)) {
+                HIP_TRY(h, push(h->d_mix, 4 * H + 2)); HIP_TRY(h, push(h->d_u, C));
+                h->count = (int)src[o++];
+                break;
+            }
+            HIP_TRY(h, push(h->d_unom[0], H)); HIP_TRY(h, push(h->d_std, H)); HIP_TRY(h, push(h->d_u, C));
             h->count = (int)src[o++];
             if (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ) {
                 HIP_TRY(h, push(h->d_m[0], (size_t)h->N * H)); HIP_TRY(h, push(h->d_v[0], (size_t)h->N * H));

@@ -179,6 +179,30 @@ hipError_t ctk_launch_pack_candidates(hipStream_t st, const float* J, const floa
 hipError_t ctk_launch_cem_finish(hipStream_t st, const float* Q, const int* idx, int H, float* mu, float* sd,
                                  float std_min, float init_std, float mid, float* u_dev, float* u_host, uint32_t seq, int ldq,
                                  float std_max = 1.0e8f, int u_from_mu = 0);
+// ---- ctk_gmm.hip: CEM with a two-component mixture (optimizer_cem_gmm_tf.py) -------------------
+// mix = mu[2][HC] | std[2][HC] | probs[2] (one allocation); label [K] fp32 0/1 (entries 0 and 1 are the seeds)
+// plans Q[n] = clip(mu_k + z[n] * std_k), k = 0 iff uniform[n] < probs[0]; normals == nullptr: Philox (normals on a.stream_id,
+// the uniform of row n = word 0 of block (row, 0, call, ustream))
+constexpr uint32_t CTK_GMM_UNIFORM_STREAM = 0x40000000u;   // + outer iteration
+hipError_t ctk_launch_gmm_sample_plans(hipStream_t st, const RolloutArgs& a, const float* normals, const float* uniforms, const float* mix,
+                                       uint32_t ustream, float* Q);
+// sampling INSIDE the rollout (ctk_sampled.hip: ctk_affine_rollout_mix<ENV, TRAJ>, analytic predictor of any environment): both components'
+// tables staged in LDS, picked per row — no plan pass and no extra launch; same draws and the same arithmetic as the pair above
+const char* ctk_affine_rollout_mix_name(int env, bool log);
+size_t ctk_affine_rollout_mix_lds(int env, int H);
+hipError_t ctk_launch_affine_rollout_mix(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a,
+                                         const float* normals, const float* uniforms, const float* mix, uint32_t ustream, bool log,
+                                         hipEvent_t e0, hipEvent_t e1);
+// labels + per-cluster mean / clipped population std + probs: ONE launch while the K labels and the two seed plans fit the refit's
+// LDS budget (every workgroup recomputes the labels), a label launch + a refit launch beyond
+constexpr int CTK_GMM_LDS_MAX_FLOATS = 12 * 1024;   // K + 2*HC floats of dynamic LDS (48 KiB) beside the kernel's static words
+bool ctk_gmm_refit_one_launch(int K, int HC);
+// two_launches: take the label launch + refit launch form whatever K is (diagnostic switch CTK_GMM_TWO_LAUNCH, bit for bit the same results)
+hipError_t ctk_launch_gmm_refit(hipStream_t st, const float* Q, const int* idx, int K, int HC, float* mix, float* label, float std_min,
+                                float std_max, int ldq, bool two_launches = false);
+// shift mu / std one step repeating the last row; u = Q[idx[0]][0, :]
+hipError_t ctk_launch_gmm_finish(hipStream_t st, const float* Q, const int* idx, int HC, int C, float* mix, float* u_dev, float* u_host,
+                                 uint32_t seq, int ldq);
 // random-action: u = Q[argmin J, 0]  (optimizer_random_action_tf.py:65-68)
 hipError_t ctk_launch_pick_best_first(hipStream_t st, const float* Q, const int* idx, int H, float* u_dev, float* u_host, uint32_t seq,
                                       int ldq);

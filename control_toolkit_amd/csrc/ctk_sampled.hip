@@ -56,15 +56,20 @@ CTK_DEV uint32_t ll_get(const unsigned long long* p, uint32_t seq, bool* expired
 // ENV: the environment (ctk_env.h); the analytic-predictor instantiation is written against Env<ENV> only (C control inputs:
 // H*C sample columns and inputs per trajectory, per-channel base / scale / clip; recurrence through Env::cost_step); the network
 // predictors' instantiations are CartPole's.  P_ = H*C sample columns of a row, pmagic_ its magic.
-template <int ENV, int PRED, bool WTRAJ>
-// (argument order: see ctk_mppi_rollout — the leading 14 dwords are preloaded into SGPRs at wave launch)
-__global__ __launch_bounds__(SAMP_BLOCK) void ctk_affine_rollout(const float* __restrict__ samples, const float* __restrict__ base,
-                                                                 const float* __restrict__ scale,
-                                                                 const float* __restrict__ wperm, int rng_kind, int N_, int H_,
-                                                                 int P_, uint32_t pmagic_, RolloutArgs a_in, typename Env<ENV>::K k, BestArgs best) {
+// MIX (CEM-GMM, optimizer_cem_gmm_tf.py:59-60; analytic predictor only): the population is drawn from a mixture of TWO diagonal
+// Gaussians, one component per ROW.  base / scale point at component 0's tables inside the mixture state mu[2][HC] | std[2][HC] | probs[2]
+// (base = mu, scale = std: component 1's tables lie HC floats further, probs[0] at base[4*HC]); both components are staged in LDS
+// (component 1 behind the carve, where the GRU's exchange slots would be) and input_at picks by the row's component:
+// 0 iff uniform[n] < probs[0], uniform[n] from `uniforms` or word 0 of the Philox block (row, 0, call, ustream).
+template <int ENV, int PRED, bool WTRAJ, bool MIX>
+CTK_DEV void affine_rollout_body(const float* __restrict__ samples, const float* __restrict__ base, const float* __restrict__ scale,
+                                 const float* __restrict__ wperm, int rng_kind, int N_, int H_, int P_, uint32_t pmagic_,
+                                 const RolloutArgs& a_in, const typename Env<ENV>::K& k, const BestArgs& best,
+                                 const float* __restrict__ uniforms, uint32_t ustream) {
     using E = Env<ENV>;
     constexpr int C = E::C, S = E::S;
     static_assert(PRED == CTK_PRED_ODE || ENV == CTK_ENV_CARTPOLE, "network predictors: CartPole instantiations only");
+    static_assert(!MIX || PRED == CTK_PRED_ODE, "mixture sampling: analytic predictor only");
     extern __shared__ float lds[];
     RolloutArgs a = a_in;
     a.N = N_; a.H = H_; a.P = P_; a.p_magic = pmagic_;
@@ -83,14 +88,25 @@ __global__ __launch_bounds__(SAMP_BLOCK) void ctk_affine_rollout(const float* __
     const bool valid = lane < TRAJ && n < a.N;
 
     load_tile_early<TRAJ, SAMP_BLOCK>(tile, samples, a, row0, 1.0f, rng_kind, [&] {
-        for (int h = t; h < HC; h += SAMP_BLOCK) { base_s[h] = base[h]; scale_s[h] = scale[h]; }
+        for (int h = t; h < HC; h += SAMP_BLOCK) {
+            base_s[h] = base[h]; scale_s[h] = scale[h];
+            if constexpr (MIX) { gru_ex[h] = base[HC + h]; gru_ex[HC + h] = scale[HC + h]; }
+        }
     });
     __syncthreads();
+    const float* mbase = base_s;       // the tables this thread's trajectory (ODE: trajectory = lane) is drawn from
+    const float* mscale = scale_s;
+    if constexpr (MIX) {
+        float u01 = 0.0f;
+        if (uniforms != nullptr) { if (n < a.N) u01 = uniforms[n]; }
+        else u01 = u32_unit_halfopen(philox4x32_10(U4{(uint32_t)(a.global_row0 + n), 0u, a.call, ustream}, a.seed_lo, a.seed_hi).x);
+        if (!(u01 < base[4 * HC])) { mbase = gru_ex; mscale = gru_ex + HC; }
+    }
 
     // inputs of the steps [hbeg, hend) of trajectory ptraj into ubuf + their input-only stage-cost terms (returned)
     auto prepare = [&](int ptraj, int hbeg, int hend) {
         const float* my = tile + ptraj * ts;
-        auto input_at = [&](int h, int c) { return fminf(fmaxf(base_s[h * C + c] + my[h * C + c] * scale_s[h * C + c], a.lo[c]), a.hi[c]); };
+        auto input_at = [&](int h, int c) { return fminf(fmaxf(mbase[h * C + c] + my[h * C + c] * mscale[h * C + c], a.lo[c]), a.hi[c]); };
         float cin = 0.0f;
         float uprev[C];
 #pragma unroll
@@ -240,6 +256,24 @@ __global__ __launch_bounds__(SAMP_BLOCK) void ctk_affine_rollout(const float* __
             a.J[n] = J + cs * a.inv_Hp1;
         }
     }
+}
+
+template <int ENV, int PRED, bool WTRAJ>
+// (argument order: see ctk_mppi_rollout — the leading 14 dwords are preloaded into SGPRs at wave launch)
+__global__ __launch_bounds__(SAMP_BLOCK) void ctk_affine_rollout(const float* __restrict__ samples, const float* __restrict__ base,
+                                                                 const float* __restrict__ scale,
+                                                                 const float* __restrict__ wperm, int rng_kind, int N_, int H_,
+                                                                 int P_, uint32_t pmagic_, RolloutArgs a_in, typename Env<ENV>::K k, BestArgs best) {
+    affine_rollout_body<ENV, PRED, WTRAJ, false>(samples, base, scale, wperm, rng_kind, N_, H_, P_, pmagic_, a_in, k, best, nullptr, 0u);
+}
+
+// the same rollout drawing from the two-component mixture of a CEM-GMM handle (MIX above); mix = mu[2][HC] | std[2][HC] | probs[2]
+template <int ENV, bool WTRAJ>
+__global__ __launch_bounds__(SAMP_BLOCK) void ctk_affine_rollout_mix(const float* __restrict__ normals, const float* __restrict__ mix,
+                                                                     const float* __restrict__ uniforms, uint32_t ustream, int N_, int H_,
+                                                                     int P_, uint32_t pmagic_, RolloutArgs a_in, typename Env<ENV>::K k) {
+    const BestArgs none{nullptr, 0u, nullptr, nullptr, nullptr};
+    affine_rollout_body<ENV, CTK_PRED_ODE, WTRAJ, true>(normals, mix, mix + 2 * P_, nullptr, 0, N_, H_, P_, pmagic_, a_in, k, none, uniforms, ustream);
 }
 
 // predictor.update(s, Q0) for the GRU (optimizer_mppi.py:195-197): one workgroup of four waves (the split
@@ -535,6 +569,30 @@ hipError_t ctk_launch_affine_rollout_env(hipStream_t st, int env, const float* p
         const size_t lds = (size_t)affine_carve_floats(HC, SAMP_TRAJ) * sizeof(float);
         if (log) CTK_LAUNCH((ctk_affine_rollout<EV, CTK_PRED_ODE, true>), grid, block, lds, st, e0, e1, samples, base, scale, (const float*)nullptr, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
         else CTK_LAUNCH((ctk_affine_rollout<EV, CTK_PRED_ODE, false>), grid, block, lds, st, e0, e1, samples, base, scale, (const float*)nullptr, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
+    });
+    return hipGetLastError();
+}
+// CEM-GMM, analytic predictor of any environment: sampling from the mixture inside the rollout (no plan pass, no extra launch)
+const char* ctk_affine_rollout_mix_name(int env, bool log) { return ctk_kernel_name("ctk_affine_rollout_mix<%d, %4$s>", env, 0, 0, log ? "true" : "false"); }
+size_t ctk_affine_rollout_mix_lds(int env, int H) {
+    int C = 1;
+    CTK_FOR_ENV(env, EV, { C = Env<EV>::C; });
+    return (size_t)(affine_carve_floats(H * C, SAMP_TRAJ) + 2 * H * C) * sizeof(float);
+}
+hipError_t ctk_launch_affine_rollout_mix(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a_in,
+                                         const float* normals, const float* uniforms, const float* mix, uint32_t ustream, bool log,
+                                         hipEvent_t e0, hipEvent_t e1) {
+    const dim3 grid((a_in.N + SAMP_TRAJ - 1) / SAMP_TRAJ), block(SAMP_BLOCK);
+    CTK_FOR_ENV(env, EV, {
+        using E = Env<EV>;
+        RolloutArgs a = a_in;
+        const int HC = a.H * E::C;
+        a.C = E::C; a.P = HC;
+        a.p_magic = HC >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)HC - 1) / (uint64_t)HC) : 0u;
+        const typename E::K k = E::derive(params, dt, isteps);
+        const size_t lds = (size_t)(affine_carve_floats(HC, SAMP_TRAJ) + 2 * HC) * sizeof(float);
+        if (log) CTK_LAUNCH((ctk_affine_rollout_mix<EV, true>), grid, block, lds, st, e0, e1, normals, mix, uniforms, ustream, a.N, a.H, a.P, a.p_magic, a, k);
+        else CTK_LAUNCH((ctk_affine_rollout_mix<EV, false>), grid, block, lds, st, e0, e1, normals, mix, uniforms, ustream, a.N, a.H, a.P, a.p_magic, a, k);
     });
     return hipGetLastError();
 }

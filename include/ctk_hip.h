@@ -57,9 +57,18 @@ typedef enum ctk_optimizer {
                                   uses outer_its (= gradient_steps), learning_rate, adam_*, gradmax_clip, warmup*   */
     CTK_OPT_CEM_NAIVE_GRAD = 5,/* Optimizers/optimizer_cem_naive_grad_tf.py: CEM whose samples take one clipped-gradient
                                   SGD step before selection; uses cem_*, learning_rate, gradmax_clip               */
-    CTK_OPT_CEM_GRAD_BHARADHWAJ = 6 /* Optimizers/optimizer_cem_grad_bharadhwaj_tf.py: population = [elites | fresh
+    CTK_OPT_CEM_GRAD_BHARADHWAJ = 6,/* Optimizers/optimizer_cem_grad_bharadhwaj_tf.py: population = [elites | fresh
                                   samples], one Keras-Adam step per outer iteration; uses cem_*, learning_rate,
                                   adam_*, gradmax_clip, warmup*                                                    */
+    CTK_OPT_CEM_GMM = 7        /* Optimizers/optimizer_cem_gmm_tf.py: CEM whose sampling distribution is a mixture of TWO diagonal
+                                  Gaussians (mu_k[H,C], std_k[H,C]) with weights (p, 1-p).  Every rollout draws its WHOLE plan from
+                                  one component (the mixture's Categorical has a scalar batch shape: one index per rollout, not per
+                                  element).  The K elites are split into two clusters seeded by the best and second-best elite
+                                  (nearest seed in the 2-norm over [H,C], a tie to the best), each refitted to mean / population
+                                  std clipped to [cem_stdev_min, 1e4] in EVERY iteration; p = the first cluster's share.  No
+                                  warm-up; needs cem_best_k >= 2; uses cem_outer_it, cem_best_k, cem_initial_action_stdev,
+                                  cem_stdev_min.  State in CTK_BUF_MIX_* (U_NOM / STD are rejected); single handle only
+                                  (the ctk_shard_* entry points refuse it)                                          */
 } ctk_optimizer;
 
 /* The plant + its concrete cost: what the reference selects by `environment_name` (Controllers/__init__.py:32-37),
@@ -143,6 +152,12 @@ typedef enum ctk_buffer {
     CTK_BUF_PLAN = 9,   /* [N,H,C]   RPGD population after warm start (next step's Q_tf)        */
     CTK_BUF_AGES_LOGGED = 10, /* [N] RPGD trajectory ages as the last step's get_action saw them, BEFORE its keep-k gather and
                                  +1 (what optimizer_rpgd.py:432 logs; the device log's AGES ring holds these)   */
+    /* CTK_OPT_CEM_GMM only; component-major: each component's table is a contiguous [H,C] like CEM's mean */
+    CTK_BUF_MIX_MU = 11,   /* [2,H,C]  component means                                          */
+    CTK_BUF_MIX_STD = 12,  /* [2,H,C]  component stdevs (clipped)                               */
+    CTK_BUF_MIX_PROB = 13, /* [2]      mixture weights (p, 1-p)                                 */
+    CTK_BUF_MIX_LABEL = 14,/* [K] as fp32: cluster (0 / 1) of each elite of the last refit, in BEST_IDX order; entries 0 and 1
+                              are the seeds                                                     */
     CTK_BUF_COUNT
 } ctk_buffer;
 
@@ -213,7 +228,8 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out);
 void ctk_destroy(ctk_handle* h);
 
 /* optimizer_reset() (optimizer_mppi.py:227-231, optimizer_cem_tf.py:113-117,
- * optimizer_rpgd.py:527-548).  `draws`: RPGD only — [N,P,C] raw draws (U[0,1) or N(0,1)) for
+ * optimizer_rpgd.py:527-548, optimizer_cem_gmm_tf.py:131-137: both components (mid-range, initial stdev), weights
+ * (0.5, 0.5), u kept).  `draws`: RPGD only — [N,P,C] raw draws (U[0,1) or N(0,1)) for
  * sample_actions (:275-296); loc NONE draws them on device.                                  */
 int ctk_reset(ctk_handle* h, const float* draws, int draws_loc);
 
@@ -276,6 +292,11 @@ int ctk_predictor_set_hidden(ctk_handle* h, const float* src, size_t n); /* src 
  *   cem-naive-grad optimizer_cem_naive_grad_tf.py:89-115  samples: N(0,1) [cem_outer_it,N,H,C]
  *   cem-grad-bharadhwaj optimizer_cem_grad_bharadhwaj_tf.py:151-178  samples: N(0,1) [K,H,C] (initial elites, :158)
  *                                                   then [iters, N-K, H, C] (:94)
+ *   cem-gmm optimizer_cem_gmm_tf.py:98-129          samples: per outer iteration N*H*C N(0,1) (row-major [N,H,C]) FOLLOWED BY
+ *                                                   N U[0,1): [cem_outer_it, N*H*C + N] in all; rollout n takes component 0 iff
+ *                                                   uniform[n] < p.  CTK_LOC_NONE: the normals of iteration `it` are CEM's
+ *                                                   (Philox stream `it`), uniform[n] is word 0 of the Philox block
+ *                                                   (row n, column block 0, call, stream 0x40000000 + it)
  * s: host [S].  u_prev: host [C] previous applied input (cost `previous_input`); NULL = the
  * optimizer's own last output, as the reference passes self.u.  u_out: host [C].
  * Synchronous: returns when u_out is valid.
@@ -361,7 +382,8 @@ int ctk_rpgd_step_end(ctk_handle* h, const float* keep_all_dev, int n_ranks,
 int ctk_read(ctk_handle* h, int which, float* dst, size_t cap, size_t* n_out);
 
 /* Warm-start state (SURVEY.md 5 'checkpoint/resume'): MPPI u_nom,u ; CEM mu,std,count,u ;
- * RPGD Q,m,v,ages,adam_step,count,u.  ctk_state_size() floats.                               */
+ * RPGD Q,m,v,ages,adam_step,count,u ; CEM-GMM mu[2,H,C],std[2,H,C],probs[2],u[C],count.
+ * ctk_state_size() floats.                                                                   */
 size_t ctk_state_size(const ctk_handle* h);
 int ctk_get_state(ctk_handle* h, float* dst, size_t cap);
 int ctk_set_state(ctk_handle* h, const float* src, size_t n);
