@@ -481,7 +481,7 @@ RolloutArgs make_args(ctk_handle* h, const float* s, const float* u_prev, int N,
     a.u_prev_dev = u_prev ? nullptr : h->d_u;
     a.C = h->C;
     a.N = N; a.H = h->H; a.P = P;
-    a.p_magic = P >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)P - 1) / (uint64_t)P) : 0u;
+    a.p_magic = ctk_magic_of(P);
     a.identity_interp = (h->cfg.period_interpolation_inducing_points == 1 && P == h->H) ? 1 : 0;
     a.inv_Hp1 = 1.0f / (float)(h->H + 1);
     a.interp = h->d_interp;
@@ -790,33 +790,25 @@ int mppi_rollout(ctk_handle* h, const float* s, const float* u_prev, const float
     RolloutArgs a = make_args(h, s, u_prev, h->N, h->P);
     const bool log = h->cfg.materialize_trajectories != 0;
     if (int rc = check_predictor(h)) return rc;
+    MppiFuse fz;   // the in-launch hand-off as asked for; every launcher takes of it what its kernel has
+    fz.mode = fuse_mode; fz.counter = h->d_counter; fz.out_rec = partial_dev; fz.ll = h->d_ll;
+    if (fuse_mode == 3) { fz.p2p = h->d_p2p_args; fz.p2p_seq = h->p2p_seq; fz.p2p_world = h->p2p_world; }
+    fz.u_nom_out = h->d_unom[h->cur ^ 1]; fz.u_dev = h->d_u; fz.u_host = h->h_u_dev; fz.seq = h->seq;
+    ProfSlot ps(h);
     if (mppi_env_kernel(h)) {
-        MppiFuse fz;
-        fz.mode = fuse_mode; fz.counter = h->d_counter; fz.out_rec = partial_dev; fz.ll = h->d_ll;
-        fz.u_nom_out = h->d_unom[h->cur ^ 1]; fz.u_dev = h->d_u; fz.u_host = h->h_u_dev; fz.seq = h->seq;
-        ProfSlot ps(h);
         HIP_TRY(h, ctk_launch_mppi_rollout_env(h->stream, h->env, h->params, h->cfg.dt, h->cfg.intermediate_steps, a, h->mk, d_s, h->d_unom[h->cur],
                                                h->d_parts, log, fz, ps.a, ps.b));
         return CTK_OK;
     }
     if (h->generic) {   // template kernels: network predictors hand their records over in-launch when asked to; else block records only
-        ProfSlot ps(h);
-        if (h->cfg.predictor != CTK_PRED_ODE) {
-            MppiFuse fz;
-            fz.mode = fuse_mode; fz.out_rec = partial_dev; fz.ll = h->d_ll;
-            fz.u_nom_out = h->d_unom[h->cur ^ 1]; fz.u_dev = h->d_u; fz.u_host = h->h_u_dev; fz.seq = h->seq;
+        if (h->cfg.predictor != CTK_PRED_ODE)
             HIP_TRY(h, ctk_launch_g_rollout_net(h->stream, h->env, h->net, CTK_G_MODE_MPPI, a, h->params, h->cfg.dt, h->cfg.intermediate_steps,
                                                 h->mk, d_s, h->d_unom[h->cur], nullptr, 0, h->d_wperm, h->d_parts, log, ps.a, ps.b, &fz));
-        } else
+        else
             HIP_TRY(h, ctk_launch_g_rollout(h->stream, h->env, CTK_G_MODE_MPPI, a, h->params, h->cfg.dt, h->cfg.intermediate_steps, h->mk, d_s,
                                             h->d_unom[h->cur], nullptr, 0, h->d_parts, log, ps.a, ps.b));
         return CTK_OK;
     }
-    MppiFuse fz;
-    fz.mode = fuse_mode; fz.counter = h->d_counter; fz.out_rec = partial_dev; fz.ll = h->d_ll;
-    if (fuse_mode == 3) { fz.p2p = h->d_p2p_args; fz.p2p_seq = h->p2p_seq; fz.p2p_world = h->p2p_world; }
-    fz.u_nom_out = h->d_unom[h->cur ^ 1]; fz.u_dev = h->d_u; fz.u_host = h->h_u_dev; fz.seq = h->seq;
-    ProfSlot ps(h);
     const char* ran = nullptr;
     HIP_TRY(h, ctk_launch_mppi_rollout(h->stream, h->cfg.predictor, a, h->k, h->mk, d_s, h->d_unom[h->cur], h->d_wperm,
                                        h->d_parts, log, fz, ps.a, ps.b, &ran));
@@ -931,24 +923,17 @@ int launch_descent(ctk_handle* h, const RolloutArgs& a, float lr, float b1, floa
 
 // random-action: u = first input of the cheapest plan (optimizer_random_action_tf.py:65-68)
 int launch_pick_best(ctk_handle* h, const float* Q, const int* idx, int ldq) {
-    if (h->generic) HIP_TRY(h, ctk_launch_g_pick_best_first(h->stream, Q, idx, h->C, h->d_u, h->h_u_dev, h->seq, ldq));
-    else HIP_TRY(h, ctk_launch_pick_best_first(h->stream, Q, idx, h->H, h->d_u, h->h_u_dev, h->seq, ldq));
+    HIP_TRY(h, ctk_launch_g_pick_best_first(h->stream, Q, idx, h->C, h->d_u, h->h_u_dev, h->seq, ldq));
     return CTK_OK;
 }
 
-// CEM post-loop (optimizer_cem_tf.py:99-102) + publishing u, tuned or template kernel
+// CEM post-loop (optimizer_cem_tf.py:99-102) + publishing u (the kernel reads the per-input limits of `a` only)
 int launch_cem_finish(ctk_handle* h, const float* Q, const int* idx, int ldq, float std_max, int u_from_mu) {
     const ctk_config& c = h->cfg;
-    if (h->generic) {
-        float zero_s[CTK_MAX_STATES] = {};
-        const RolloutArgs a = make_args(h, zero_s, nullptr, h->N, h->H);
-        HIP_TRY(h, ctk_launch_g_cem_finish(h->stream, Q, idx, h->H, h->C, h->d_unom[0], h->d_std, c.cem_stdev_min, c.cem_initial_action_stdev, a,
-                                           h->d_u, h->h_u_dev, h->seq, ldq, std_max, u_from_mu));
-    } else {
-        const float mid = (c.action_low[0] + c.action_high[0]) * 0.5f;
-        HIP_TRY(h, ctk_launch_cem_finish(h->stream, Q, idx, h->H, h->d_unom[0], h->d_std, c.cem_stdev_min, c.cem_initial_action_stdev, mid,
-                                         h->d_u, h->h_u_dev, h->seq, ldq, std_max, u_from_mu));
-    }
+    float zero_s[CTK_MAX_STATES] = {};
+    const RolloutArgs a = make_args(h, zero_s, nullptr, h->N, h->H);
+    HIP_TRY(h, ctk_launch_g_cem_finish(h->stream, Q, idx, h->H, h->C, h->d_unom[0], h->d_std, c.cem_stdev_min, c.cem_initial_action_stdev, a,
+                                       h->d_u, h->h_u_dev, h->seq, ldq, std_max, u_from_mu));
     return CTK_OK;
 }
 

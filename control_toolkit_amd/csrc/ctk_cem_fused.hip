@@ -1,7 +1,7 @@
 // ctk_cem_fused.hip — one CEM step (all outer iterations) in ONE launch, analytic predictor of any environment (ctk_env.h: C control
 // inputs -> H*C columns per plan, below "H" where a column count is meant), <= CTK_CEM_FUSED_MAX_BLOCKS
 // workgroups (all co-resident: one per CU).  Replaces, per outer iteration, the three launches rollout -> ctk_select_topk ->
-// ctk_cem_refit and, after the loop, ctk_cem_finish (optimizer_cem_tf.py:61-80,83-111): SURVEY 8e's all-reduce form of the
+// ctk_cem_refit and, after the loop, ctk_g_cem_finish (optimizer_cem_tf.py:61-80,83-111): SURVEY 8e's all-reduce form of the
 // elite refit applied INSIDE one GPU, with the {value, tag} word hand-off of ctk_mppi.hip between workgroups.
 //
 // Per outer iteration, every workgroup (64 rollouts, 256 threads):
@@ -529,10 +529,8 @@ hipError_t ctk_launch_cem_fused(hipStream_t st, int env, const float* params, fl
     const dim3 grid(nblk), block(CF_BLOCK);
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
-        RolloutArgs a = a_in;
-        const int HC = a.H * E::C;
-        a.C = E::C; a.P = HC;
-        a.p_magic = HC >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)HC - 1) / (uint64_t)HC) : 0u;
+        const int HC = a_in.H * E::C;
+        const RolloutArgs a = ctk_rollout_args(a_in, E::C, HC);
         const typename E::K k = E::derive(params, dt, isteps);
         CemFusedK cf{};
         cf.its = c.its; cf.K = c.K; cf.nblk = nblk; cf.per_it = (unsigned long long)a.N * HC;
@@ -542,8 +540,7 @@ hipError_t ctk_launch_cem_fused(hipStream_t st, int env, const float* params, fl
         cf.mu = c.mu; cf.sd = c.sd; cf.u_dev = c.u_dev; cf.u_host = c.u_host; cf.idx_out = c.idx_out; cf.seq = c.seq;
         cf.timeout_ticks = (unsigned long long)(c.timeout_s * 1.0e8);
         const size_t lds = ctk_cem_fused_lds(a.N, HC);
-        if (log) CTK_LAUNCH((ctk_cem_fused<EV, true>), grid, block, lds, st, e0, e1, samples, a, k, cf);
-        else CTK_LAUNCH((ctk_cem_fused<EV, false>), grid, block, lds, st, e0, e1, samples, a, k, cf);
+        ctk_with_bool(log, [&](auto log_c) { CTK_LAUNCH((ctk_cem_fused<EV, decltype(log_c)::value>), grid, block, lds, st, e0, e1, samples, a, k, cf); });
     });
     return hipGetLastError();
 }

@@ -49,6 +49,9 @@ inline EnvK derive_constants(const float* p /* CTK_P_COUNT primary params (fp32)
     return k;
 }
 
+// ceil(2^32 / d): flat / d == umulhi(flat, magic) for flat * d < 2^32 (RolloutArgs::p_magic); d < 2: 0, the kernels do not divide
+inline uint32_t ctk_magic_of(int d) { return d >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d) : 0u; }
+
 // Column t of the reference's interpolation matrix (others/Interpolator.py:53-77) has at most
 // two non-zeros: u[t] = y[i0]*w0 + y[i0+1]*w1.  Built on the host exactly like the matrix
 // (fp32 (p-j)/p, including the closing-row quirk) — see ctk_api.hip:build_interp_table.

@@ -386,8 +386,6 @@ __global__ __launch_bounds__(GR_BLOCK) void ctk_g_rpgd_descent(RolloutArgs a, ty
 // ---------------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------------
-static uint32_t magic_of(int d) { return d >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d) : 0u; }
-
 size_t ctk_g_rollout_lds(int cols, int H, int C) {
     return (size_t)(G_TRAJ * tile_stride(cols) + G_TRAJ + 2 * H * C + 3 * H) * sizeof(float);
 }
@@ -403,19 +401,18 @@ hipError_t ctk_launch_g_rollout(hipStream_t st, int env, int mode, const Rollout
                                 float* parts, bool log, hipEvent_t e0, hipEvent_t e1) {
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
-        RolloutArgs a = a_in;
         const int cols = (mode == CTK_G_MODE_MPPI ? a_in.P : a_in.H) * E::C;
-        a.P = cols; a.p_magic = magic_of(cols); a.C = E::C;
+        const RolloutArgs a = ctk_rollout_args(a_in, E::C, cols);
         const typename E::K k = E::derive(params, dt, isteps);
         const dim3 grid(ctk_g_rollout_blocks(a.N)), block(G_TRAJ);
         const size_t lds = ctk_g_rollout_lds(cols, a.H, E::C);
-        if (mode == CTK_G_MODE_MPPI) {
-            if (log) CTK_LAUNCH((ctk_g_rollout<EV, CTK_G_MODE_MPPI, true>), grid, block, lds, st, e0, e1, a, k, mk, E::C, samples, base, scale, rng_kind, parts);
-            else CTK_LAUNCH((ctk_g_rollout<EV, CTK_G_MODE_MPPI, false>), grid, block, lds, st, e0, e1, a, k, mk, E::C, samples, base, scale, rng_kind, parts);
-        } else {
-            if (log) CTK_LAUNCH((ctk_g_rollout<EV, CTK_G_MODE_AFFINE, true>), grid, block, lds, st, e0, e1, a, k, mk, E::C, samples, base, scale, rng_kind, parts);
-            else CTK_LAUNCH((ctk_g_rollout<EV, CTK_G_MODE_AFFINE, false>), grid, block, lds, st, e0, e1, a, k, mk, E::C, samples, base, scale, rng_kind, parts);
-        }
+        ctk_with_bool(mode == CTK_G_MODE_MPPI, [&](auto mppi_c) {
+            ctk_with_bool(log, [&](auto log_c) {
+                constexpr int MODE = decltype(mppi_c)::value ? CTK_G_MODE_MPPI : CTK_G_MODE_AFFINE;
+                CTK_LAUNCH((ctk_g_rollout<EV, MODE, decltype(log_c)::value>), grid, block, lds, st, e0, e1, a, k, mk, E::C, samples, base, scale,
+                           rng_kind, parts);
+            });
+        });
     });
     return hipGetLastError();
 }
@@ -469,8 +466,7 @@ hipError_t ctk_launch_g_rpgd_descent(hipStream_t st, int env, const RolloutArgs&
     AdamK ad{lr, b1, b2, (float)(1.0 - (double)b1), (float)(1.0 - (double)b2), eps, clip, rule};
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
-        RolloutArgs a = a_in;
-        a.C = E::C; a.p_magic = magic_of(a.H * E::C);
+        const RolloutArgs a = ctk_descent_args(a_in, E::C);
         const typename E::K k = E::derive(params, dt, isteps);
         bool tape_in_lds = false;
         const size_t lds = ctk_g_rpgd_descent_lds(env, a.H, &tape_in_lds);

@@ -350,8 +350,6 @@ __global__ __launch_bounds__(64) void ctk_g_gru_advance(RolloutArgs a, const flo
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-static uint32_t magic_of(int d) { return d >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d) : 0u; }
-
 size_t ctk_g_net_table_floats(int net) {
     if (net == NET_MLP64) return (size_t)64 * (MLPW_FWD_PER_LANE + MLPW_BWD_PER_LANE);
     return net == NET_GRU ? (size_t)GRUG_TABLE * 64 : (size_t)64 * (MLP_FWD_PER_LANE + MLP_BWD_PER_LANE);
@@ -392,9 +390,7 @@ NetFuse ctk_net_fuse(const MppiFuse* fuse, int mode, const RolloutArgs& a, int C
     if (fuse == nullptr || mode != CTK_G_MODE_MPPI || fuse->mode == 0 || fuse->ll == nullptr) return gz;
     if (!ctk_ll_records_ok(blocks, cols) || !merge_can_stage(cols, blocks)) return gz;
     gz.mode = fuse->mode; gz.ll = fuse->ll; gz.out_rec = fuse->out_rec;
-    gz.up = MppiUpdateArgs{nullptr, nullptr, nullptr, nullptr, a.H, a.interp, u_nom, fuse->u_nom_out, a.lo[0], a.hi[0], fuse->u_dev, fuse->u_host, fuse->seq};
-    gz.up.C = C;
-    for (int c = 0; c < C; ++c) { gz.up.lo_c[c] = a.lo[c]; gz.up.hi_c[c] = a.hi[c]; }
+    gz.up = mppi_update_args(a, C, u_nom, fuse->u_nom_out, fuse->u_dev, fuse->u_host, fuse->seq);
     return gz;
 }
 
@@ -411,22 +407,21 @@ static void launch_rollout_net(hipStream_t st, int mode, const RolloutArgs& a_in
                                const float* samples, const float* base, const float* scale, int rng_kind, const float* wperm,
                                const float* hidden, float* parts, bool log, hipEvent_t e0, hipEvent_t e1, const MppiFuse* fuse) {
     using E = Env<EV>;
-    RolloutArgs a = a_in;
     const int cols = (mode == CTK_G_MODE_MPPI ? a_in.P : a_in.H) * E::C;
-    a.P = cols; a.p_magic = magic_of(cols); a.C = E::C;
+    const RolloutArgs a = ctk_rollout_args(a_in, E::C, cols);
     const typename E::K k = E::derive(params, dt, isteps);
     const dim3 grid(ctk_g_rollout_blocks(a.N)), block(GN_BLOCK);
     const size_t lds0 = ctk_g_rollout_lds(cols, a.H, E::C);
     const NetFuse gz = ctk_net_fuse(fuse, mode, a, E::C, base, (int)grid.x, cols);
     const size_t lds = std::max(lds0 + NETT::LDS_FWD * sizeof(float), gz.mode ? merge_lds_staged(cols, (int)grid.x) : 0);
     const int off = (int)(lds0 / sizeof(float));
-    if (mode == CTK_G_MODE_MPPI) {
-        if (log) CTK_LAUNCH((ctk_g_rollout_net<EV, NETT, CTK_G_MODE_MPPI, true>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind, wperm, hidden, off, parts, gz);
-        else CTK_LAUNCH((ctk_g_rollout_net<EV, NETT, CTK_G_MODE_MPPI, false>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind, wperm, hidden, off, parts, gz);
-    } else {
-        if (log) CTK_LAUNCH((ctk_g_rollout_net<EV, NETT, CTK_G_MODE_AFFINE, true>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind, wperm, hidden, off, parts, gz);
-        else CTK_LAUNCH((ctk_g_rollout_net<EV, NETT, CTK_G_MODE_AFFINE, false>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind, wperm, hidden, off, parts, gz);
-    }
+    ctk_with_bool(mode == CTK_G_MODE_MPPI, [&](auto mppi_c) {
+        ctk_with_bool(log, [&](auto log_c) {
+            constexpr int MODE = decltype(mppi_c)::value ? CTK_G_MODE_MPPI : CTK_G_MODE_AFFINE;
+            CTK_LAUNCH((ctk_g_rollout_net<EV, NETT, MODE, decltype(log_c)::value>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind,
+                       wperm, hidden, off, parts, gz);
+        });
+    });
 }
 
 hipError_t ctk_launch_g_rollout_net(hipStream_t st, int env, int net, int mode, const RolloutArgs& a, const float* params, float dt, int isteps,
@@ -483,8 +478,7 @@ hipError_t ctk_launch_g_rpgd_descent_net(hipStream_t st, int env, int net, const
         return ctk_launch_g_rpgd_descent_split(st, env, net, a_in, params, dt, isteps, ad, Q, m, v, bc_table, bc_len, t0, iters, wperm, wb, hidden, scratch, e0, e1);
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
-        RolloutArgs a = a_in;
-        a.C = E::C; a.p_magic = magic_of(a.H * E::C);
+        const RolloutArgs a = ctk_descent_args(a_in, E::C);
         const typename E::K k = E::derive(params, dt, isteps);
         const dim3 grid((a.N + GN_TRAJ - 1) / GN_TRAJ), block(GN_BLOCK);
         const size_t lds = ctk_g_rpgd_descent_net_lds(env, net, 1 << 30, a.H);   // this (one-wave) form

@@ -11,6 +11,28 @@
         else hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                           \
     } while (0)
 
+// a runtime flag as a compile-time constant: f(std::true_type{}) or f(std::false_type{}), so that a launch whose template takes the
+// flag writes its argument list once (f is a generic lambda, called in place: nothing is stored)
+#include <type_traits>
+template <class F>
+inline void ctk_with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// RolloutArgs as an environment's template kernels take them: C inputs, `cols` flat sample columns per row (P*C or H*C) and their divisor
+inline RolloutArgs ctk_rollout_args(const RolloutArgs& a_in, int C, int cols) {
+    RolloutArgs a = a_in;
+    a.C = C; a.P = cols; a.p_magic = ctk_magic_of(cols);
+    return a;
+}
+// ... and their descent kernels: the rows are the H*C columns of a plan, a.P stays the caller's
+inline RolloutArgs ctk_descent_args(const RolloutArgs& a_in, int C) {
+    RolloutArgs a = a_in;
+    a.C = C; a.p_magic = ctk_magic_of(a.H * C);
+    return a;
+}
+
 // kernel names as rocprofv3's trace prints them, formatted once per (template, arguments) and kept for the process's lifetime
 // (ctk_dominant_kernel returns the pointer); any number of environments
 #include <cstdio>
@@ -175,10 +197,6 @@ hipError_t ctk_launch_cem_build_population(hipStream_t st, const RolloutArgs& a,
 // this shard's best-K records {J, global index, Q[H]} for the sharded selection
 hipError_t ctk_launch_pack_candidates(hipStream_t st, const float* J, const float* Q, const int* idx, int K, int H, int global_offset,
                                       float* cand);
-// CEM post-loop (optimizer_cem_tf.py:99-102) and u = elite[0,0]
-hipError_t ctk_launch_cem_finish(hipStream_t st, const float* Q, const int* idx, int H, float* mu, float* sd,
-                                 float std_min, float init_std, float mid, float* u_dev, float* u_host, uint32_t seq, int ldq,
-                                 float std_max = 1.0e8f, int u_from_mu = 0);
 // ---- ctk_gmm.hip: CEM with a two-component mixture (optimizer_cem_gmm_tf.py) -------------------
 // mix = mu[2][HC] | std[2][HC] | probs[2] (one allocation); label [K] fp32 0/1 (entries 0 and 1 are the seeds)
 // plans Q[n] = clip(mu_k + z[n] * std_k), k = 0 iff uniform[n] < probs[0]; normals == nullptr: Philox (normals on a.stream_id,
@@ -203,9 +221,6 @@ hipError_t ctk_launch_gmm_refit(hipStream_t st, const float* Q, const int* idx, 
 // shift mu / std one step repeating the last row; u = Q[idx[0]][0, :]
 hipError_t ctk_launch_gmm_finish(hipStream_t st, const float* Q, const int* idx, int HC, int C, float* mix, float* u_dev, float* u_host,
                                  uint32_t seq, int ldq);
-// random-action: u = Q[argmin J, 0]  (optimizer_random_action_tf.py:65-68)
-hipError_t ctk_launch_pick_best_first(hipStream_t st, const float* Q, const int* idx, int H, float* u_dev, float* u_host, uint32_t seq,
-                                      int ldq);
 
 // ---- ctk_cem_fused.hip : one CEM step (all outer iterations) in ONE launch, CartPole ODE ---------
 constexpr int CTK_CEM_FUSED_MAX_BLOCKS = 128;     // workgroups of 64 rollouts, all co-resident (one per CU)
@@ -280,9 +295,12 @@ int ctk_g_mppi_update_max_parts();   // records the update launch merges itself
 hipError_t ctk_launch_g_mppi_update(hipStream_t st, const float* parts, int n_parts, float neg_inv_lbd, int P, int C, int H,
                                     const InterpEntry* interp, const float* u_nom_in, float* u_nom_out, const RolloutArgs& a, float* u_dev,
                                     float* u_host, uint32_t seq);
+// CEM post-loop (optimizer_cem_tf.py:99-102: clip std, shift by one step, refill the tail) and u = first input of the best elite,
+// or of the mean with the stdev clipped to [min, std_max] (optimizer_cem_naive_grad_tf.py:101-104); every environment, CartPole: C = 1
 hipError_t ctk_launch_g_cem_finish(hipStream_t st, const float* Q, const int* idx, int H, int C, float* mu, float* sd, float std_min,
                                    float init_std, const RolloutArgs& a, float* u_dev, float* u_host, uint32_t seq, int ldq,
                                    float std_max = 1.0e8f, int u_from_mu = 0);
+// random-action: u = Q[argmin J, 0, :]  (optimizer_random_action_tf.py:65-68)
 hipError_t ctk_launch_g_pick_best_first(hipStream_t st, const float* Q, const int* idx, int C, float* u_dev, float* u_host, uint32_t seq,
                                         int ldq);
 size_t ctk_g_rpgd_descent_lds(int env, int H, bool* tape_in_lds);

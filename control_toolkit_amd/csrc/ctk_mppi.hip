@@ -738,66 +738,94 @@ static size_t rollout_launch_lds(int P, int H, int pred, int N, int blocks, int*
     return lds;
 }
 
+// the kernel-side fuse argument of a 4-wave launch (rollout or resident) of an environment with C inputs; stage_ok: rollout_launch_lds
+static FuseArgs mppi_fuse_args(const MppiFuse& fuse, int stage_ok, const RolloutArgs& a, int C, const float* u_nom_in, float* u_nom_out) {
+    FuseArgs fz{};
+    fz.mode = fuse.mode; fz.stage_ok = stage_ok; fz.counter = fuse.counter; fz.out_rec = fuse.out_rec;
+    fz.ll = (fuse.mode != 0 && stage_ok) ? fuse.ll : nullptr;
+    fz.p2p = static_cast<const P2PArgs*>(fuse.p2p); fz.p2p_seq = fuse.p2p_seq;
+    fz.up = mppi_update_args(a, C, u_nom_in, u_nom_out, fuse.u_dev, fuse.u_host, fuse.seq);
+    return fz;
+}
+
+// a launch's CTK_MPPI_FORM_* bits as a constant: f(integral_constant<int, form>).  OLD: the instantiations with the previous recurrence
+// exist (the analytic predictor of a pipelined environment: mppi_form / mppi_env_form raise that bit nowhere else)
+template <bool OLD, class F>
+static void with_mppi_form(int form, F&& f) {
+    using std::integral_constant;
+    constexpr int W = CTK_MPPI_FORM_WIDE_TAIL, O = CTK_MPPI_FORM_OLD_RECUR;
+    if (form == 0) f(integral_constant<int, 0>{});
+    else if (form == W) f(integral_constant<int, W>{});
+    else if constexpr (OLD) {
+        if (form == O) f(integral_constant<int, O>{});
+        else f(integral_constant<int, W | O>{});
+    }
+}
+
+// One launch of the 4-wave kernel ctk_mppi_rollout<ENV, PRED, log, p2p[, form]>: a.P inducing points of ENV's C inputs, `k` the
+// caller's constants (CartPole: the handle's cached ones), PRED the kernel variant (kernel_pred; the network predictors are CartPole's).
+// Returns the form it launched.
+template <int ENV, int PRED>
+static int launch_mppi_4wave(hipStream_t st, const RolloutArgs& a, const typename Env<ENV>::K& k, const MppiK& m, const float* samples,
+                             const float* u_nom, const float* wperm, float* parts, bool log, const MppiFuse& fuse, hipEvent_t e0, hipEvent_t e1) {
+    constexpr int C = Env<ENV>::C;
+    constexpr bool ODE = PRED == CTK_PRED_ODE;
+    static_assert(ODE || ENV == CTK_ENV_CARTPOLE, "network predictors: CartPole instantiations only");
+    const int PC = a.P * C;
+    const dim3 grid((a.N + mppi_traj(PRED) - 1) / mppi_traj(PRED)), block(MPPI_BLOCK);
+    int stage_ok;
+    size_t lds = rollout_launch_lds(a.P, a.H, PRED, a.N, (int)grid.x, &stage_ok, C);
+    const bool p2p = ENV == CTK_ENV_CARTPOLE && fuse.mode == 3;      // (the peer-to-peer tail is CartPole's)
+    if (p2p) lds = std::max(lds, merge_lds_staged(a.P, fuse.p2p_world));   // the tail also stages the `world` records of the exchange
+    const FuseArgs fz = mppi_fuse_args(fuse, stage_ok, a, C, u_nom, fuse.u_nom_out);
+    const uint32_t pmagic = ctk_magic_of(PC);
+    int form;
+    if constexpr (ODE) form = mppi_env_form<ENV>((int)grid.x, PC, fz.ll != nullptr);
+    else form = mppi_form(PRED, (int)grid.x, PC, fz.ll != nullptr);
+    auto go = [&](auto kernel) { CTK_LAUNCH(kernel, grid, block, lds, st, e0, e1, samples, u_nom, a.interp, wperm, parts, a.N, a.H, a.P, pmagic, a, k, m, fz); };
+    with_mppi_form<ODE && env_pipelined<ENV>::value>(form, [&](auto form_c) {
+        ctk_with_bool(log, [&](auto log_c) {
+            ctk_with_bool(p2p, [&](auto p2p_c) {
+                constexpr int FV = decltype(form_c)::value;
+                constexpr bool LV = decltype(log_c)::value, XV = ENV == CTK_ENV_CARTPOLE && decltype(p2p_c)::value;
+                if constexpr (FV == 0) go(ctk_mppi_rollout<ENV, PRED, LV, XV>);      // (FORM 0 is the four-argument kernel)
+                else go(ctk_mppi_rollout<ENV, PRED, LV, XV, FV>);
+            });
+        });
+    });
+    return form;
+}
+
 hipError_t ctk_launch_mppi_rollout(hipStream_t st, int pred, const RolloutArgs& a, const EnvK& k, const MppiK& m,
                                    const float* samples, const float* u_nom, const float* wperm, float* parts, bool log,
                                    const MppiFuse& fuse, hipEvent_t e0, hipEvent_t e1, const char** ran) {
-    const dim3 grid(ctk_mppi_num_blocks(a.N, pred)), block(MPPI_BLOCK);
-    if (ran) *ran = ctk_mppi_rollout_name(pred, log, a.N, a.identity_interp != 0, samples != nullptr, fuse.mode == 3, a.H);   // (4-wave: below)
     if (const int tf = throughput_form(pred, a.N, samples != nullptr, a.identity_interp != 0)) {
+        const dim3 grid(ctk_mppi_num_blocks(a.N, pred));
+        if (ran) *ran = ctk_mppi_rollout_name(pred, log, a.N, a.identity_interp != 0, samples != nullptr, false, a.H);
         if (tf == 2) {
-            if (tps_resident(a.H)) {
-                const size_t lds_r = (size_t)(64 * (a.H | 1) + 64 + a.H) * sizeof(float);
-                if (log) CTK_LAUNCH((ctk_mppi_rollout_tps<true, true>), grid, dim3(64), lds_r, st, e0, e1, a, k, m, samples, u_nom, parts);
-                else CTK_LAUNCH((ctk_mppi_rollout_tps<false, true>), grid, dim3(64), lds_r, st, e0, e1, a, k, m, samples, u_nom, parts);
-                return hipGetLastError();
-            }
-            const size_t lds_d = (size_t)(64 * TPS_LD + 64 + a.H) * sizeof(float);
-            if (log) CTK_LAUNCH((ctk_mppi_rollout_tps<true>), grid, dim3(64), lds_d, st, e0, e1, a, k, m, samples, u_nom, parts);
-            else CTK_LAUNCH((ctk_mppi_rollout_tps<false>), grid, dim3(64), lds_d, st, e0, e1, a, k, m, samples, u_nom, parts);
+            const bool res = tps_resident(a.H);
+            const size_t lds_s = (size_t)(64 * (res ? (a.H | 1) : TPS_LD) + 64 + a.H) * sizeof(float);
+            ctk_with_bool(log, [&](auto log_c) {
+                ctk_with_bool(res, [&](auto res_c) {
+                    CTK_LAUNCH((ctk_mppi_rollout_tps<decltype(log_c)::value, decltype(res_c)::value>), grid, dim3(64), lds_s, st, e0, e1, a, k, m, samples,
+                               u_nom, parts);
+                });
+            });
             return hipGetLastError();
         }
         const size_t lds_tp = (size_t)(64 * tile_stride(a.P) + 64 + 4 * a.H) * sizeof(float);
-        if (log) CTK_LAUNCH((ctk_mppi_rollout_tp<true>), grid, dim3(64), lds_tp, st, e0, e1, a, k, m, samples, u_nom, a.interp, parts);
-        else CTK_LAUNCH((ctk_mppi_rollout_tp<false>), grid, dim3(64), lds_tp, st, e0, e1, a, k, m, samples, u_nom, a.interp, parts);
+        ctk_with_bool(log, [&](auto log_c) {
+            CTK_LAUNCH((ctk_mppi_rollout_tp<decltype(log_c)::value>), grid, dim3(64), lds_tp, st, e0, e1, a, k, m, samples, u_nom, a.interp, parts);
+        });
         return hipGetLastError();
     }
-    FuseArgs fz{};
-    size_t lds = rollout_launch_lds(a.P, a.H, pred, a.N, (int)grid.x, &fz.stage_ok);
-    if (fuse.mode == 3) {   // the tail also stages the `world` records of the exchange
-        const size_t need = merge_lds_staged(a.P, fuse.p2p_world);
-        if (need > lds) lds = need;
-    }
-    fz.mode = fuse.mode; fz.counter = fuse.counter; fz.out_rec = fuse.out_rec;
-    fz.ll = (fuse.mode != 0 && fz.stage_ok) ? fuse.ll : nullptr;
-    fz.p2p = static_cast<const P2PArgs*>(fuse.p2p); fz.p2p_seq = fuse.p2p_seq;
-    fz.up = MppiUpdateArgs{nullptr, nullptr, nullptr, nullptr, a.H, a.interp, u_nom, fuse.u_nom_out, a.lo[0], a.hi[0], fuse.u_dev, fuse.u_host, fuse.seq};
-    const int kp = pred == CTK_PRED_ODE ? CTK_PRED_ODE : kernel_pred(pred, a.N);
-    const int form = mppi_form(kp, (int)grid.x, a.P, fz.ll != nullptr);
+    const int kp = kernel_pred(pred, a.N);
+    int form;
+    if (kp == CTK_PRED_ODE) form = launch_mppi_4wave<CTK_ENV_CARTPOLE, CTK_PRED_ODE>(st, a, k, m, samples, u_nom, wperm, parts, log, fuse, e0, e1);
+    else if (kp == CTK_PRED_MLP_PAIR) form = launch_mppi_4wave<CTK_ENV_CARTPOLE, CTK_PRED_MLP_PAIR>(st, a, k, m, samples, u_nom, wperm, parts, log, fuse, e0, e1);
+    else if (kp == CTK_PRED_MLP) form = launch_mppi_4wave<CTK_ENV_CARTPOLE, CTK_PRED_MLP>(st, a, k, m, samples, u_nom, wperm, parts, log, fuse, e0, e1);
+    else form = launch_mppi_4wave<CTK_ENV_CARTPOLE, CTK_PRED_GRU>(st, a, k, m, samples, u_nom, wperm, parts, log, fuse, e0, e1);
     if (ran) *ran = ctk_mppi_rollout_name(pred, log, a.N, a.identity_interp != 0, samples != nullptr, fuse.mode == 3, a.H, form);
-    using std::integral_constant;
-    auto launch = [&](auto pred_c, auto log_c, auto p2p_c) {
-        constexpr int PV = decltype(pred_c)::value;
-        constexpr bool LV = decltype(log_c)::value, XV = decltype(p2p_c)::value;
-        constexpr int W = CTK_MPPI_FORM_WIDE_TAIL, O = CTK_MPPI_FORM_OLD_RECUR;
-#define CTK_MPPI_LAUNCH(...) CTK_LAUNCH(__VA_ARGS__)      // (expands CTK_MPPI_ARGS first)
-#define CTK_MPPI_ARGS grid, block, lds, st, e0, e1, samples, u_nom, a.interp, wperm, parts, a.N, a.H, a.P, a.p_magic, a, k, m, fz
-        if (form == 0) CTK_MPPI_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PV, LV, XV>), CTK_MPPI_ARGS);
-        else if (form == W) CTK_MPPI_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PV, LV, XV, W>), CTK_MPPI_ARGS);
-        else if constexpr (PV == CTK_PRED_ODE) {       // the old recurrence: the analytic predictor's only (mppi_form)
-            if (form == O) CTK_MPPI_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PV, LV, XV, O>), CTK_MPPI_ARGS);
-            else CTK_MPPI_LAUNCH((ctk_mppi_rollout<CTK_ENV_CARTPOLE, PV, LV, XV, W | O>), CTK_MPPI_ARGS);
-        }
-#undef CTK_MPPI_LAUNCH
-#undef CTK_MPPI_ARGS
-    };
-    auto launch_pred = [&](auto pred_c) {
-        if (fuse.mode == 3) { if (log) launch(pred_c, std::true_type{}, std::true_type{}); else launch(pred_c, std::false_type{}, std::true_type{}); }
-        else { if (log) launch(pred_c, std::true_type{}, std::false_type{}); else launch(pred_c, std::false_type{}, std::false_type{}); }
-    };
-    if (pred == CTK_PRED_ODE) launch_pred(integral_constant<int, CTK_PRED_ODE>{});
-    else if (kp == CTK_PRED_MLP_PAIR) launch_pred(integral_constant<int, CTK_PRED_MLP_PAIR>{});
-    else if (pred == CTK_PRED_MLP) launch_pred(integral_constant<int, CTK_PRED_MLP>{});
-    else launch_pred(integral_constant<int, CTK_PRED_GRU>{});
     return hipGetLastError();
 }
 
@@ -807,74 +835,37 @@ hipError_t ctk_launch_mppi_rollout(hipStream_t st, int pred, const RolloutArgs& 
 hipError_t ctk_launch_mppi_rollout_env(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                        const float* samples, const float* u_nom, float* parts, bool log, const MppiFuse& fuse,
                                        hipEvent_t e0, hipEvent_t e1) {
-    const dim3 grid((a.N + MPPI_TRAJ - 1) / MPPI_TRAJ), block(MPPI_BLOCK);
     CTK_FOR_ENV(env, EV, {
-        using E = Env<EV>;
-        const int PC = a.P * E::C;
-        const typename E::K k = E::derive(params, dt, isteps);
-        FuseArgs fz{};
-        const size_t lds = rollout_launch_lds(a.P, a.H, CTK_PRED_ODE, a.N, (int)grid.x, &fz.stage_ok, E::C);
-        fz.mode = fuse.mode; fz.counter = fuse.counter; fz.out_rec = fuse.out_rec;
-        fz.ll = (fuse.mode != 0 && fz.stage_ok) ? fuse.ll : nullptr;
-        fz.up = MppiUpdateArgs{nullptr, nullptr, nullptr, nullptr, a.H, a.interp, u_nom, fuse.u_nom_out, a.lo[0], a.hi[0], fuse.u_dev, fuse.u_host, fuse.seq};
-        fz.up.C = E::C;
-        for (int c = 0; c < E::C; ++c) { fz.up.lo_c[c] = a.lo[c]; fz.up.hi_c[c] = a.hi[c]; }
-        const uint32_t pmagic = PC >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)PC - 1) / (uint64_t)PC) : 0u;
-        const int form = mppi_env_form<EV>((int)grid.x, PC, fz.ll != nullptr);
-        auto launch = [&](auto log_c, auto form_c) {
-            CTK_LAUNCH((ctk_mppi_rollout<EV, CTK_PRED_ODE, decltype(log_c)::value, false, decltype(form_c)::value>), grid, block, lds, st, e0, e1, samples,
-                       u_nom, a.interp, (const float*)nullptr, parts, a.N, a.H, a.P, pmagic, a, k, m, fz);
-        };
-        auto launch_form = [&](auto log_c) {
-            using std::integral_constant;
-            if (form == 0) CTK_LAUNCH((ctk_mppi_rollout<EV, CTK_PRED_ODE, decltype(log_c)::value, false>), grid, block, lds, st, e0, e1, samples, u_nom,
-                                      a.interp, (const float*)nullptr, parts, a.N, a.H, a.P, pmagic, a, k, m, fz);
-            else if (form == CTK_MPPI_FORM_WIDE_TAIL) launch(log_c, integral_constant<int, CTK_MPPI_FORM_WIDE_TAIL>{});
-            else if constexpr (env_pipelined<EV>::value) {       // (the other environments have one recurrence)
-                if (form == CTK_MPPI_FORM_OLD_RECUR) launch(log_c, integral_constant<int, CTK_MPPI_FORM_OLD_RECUR>{});
-                else launch(log_c, integral_constant<int, CTK_MPPI_FORM_WIDE_TAIL | CTK_MPPI_FORM_OLD_RECUR>{});
-            }
-        };
-        if (log) launch_form(std::true_type{});
-        else launch_form(std::false_type{});
+        launch_mppi_4wave<EV, CTK_PRED_ODE>(st, a, Env<EV>::derive(params, dt, isteps), m, samples, u_nom, nullptr, parts, log, fuse, e0, e1);
     });
     return hipGetLastError();
 }
 hipError_t ctk_launch_mppi_resident(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                     float* u_nom0, float* u_nom1, float* parts, const MppiFuse& fuse, const CtkResidentBox* box_dev, int box_local,
                                     CtkResidentStat* stat_dev, CtkResidentBox* relay, double idle_us, uint32_t first_req, void* args_dev, void* args_host) {
-    const dim3 grid((a.N + MPPI_TRAJ - 1) / MPPI_TRAJ), block(MPPI_BLOCK);
+    const dim3 grid(ctk_mppi_num_blocks(a.N, CTK_PRED_ODE)), block(MPPI_BLOCK);
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
         const int PC = a.P * E::C;
         const typename E::K k = E::derive(params, dt, isteps);
-        FuseArgs fz{};
-        const size_t lds = rollout_launch_lds(a.P, a.H, CTK_PRED_ODE, a.N, (int)grid.x, &fz.stage_ok, E::C);
-        if (!fz.stage_ok || fuse.ll == nullptr) return hipErrorInvalidValue;          // the resident form is the {value, seq} hand-off only
-        fz.mode = 1; fz.ll = fuse.ll;
-        fz.up = MppiUpdateArgs{nullptr, nullptr, nullptr, nullptr, a.H, a.interp, u_nom0, u_nom1, a.lo[0], a.hi[0], fuse.u_dev, fuse.u_host, 0u};
-        fz.up.C = E::C;
-        for (int c = 0; c < E::C; ++c) { fz.up.lo_c[c] = a.lo[c]; fz.up.hi_c[c] = a.hi[c]; }
-        const uint32_t pmagic = PC >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)PC - 1) / (uint64_t)PC) : 0u;
+        int stage_ok;
+        const size_t lds = rollout_launch_lds(a.P, a.H, CTK_PRED_ODE, a.N, (int)grid.x, &stage_ok, E::C);
+        if (!stage_ok || fuse.ll == nullptr) return hipErrorInvalidValue;          // the resident form is the {value, seq} hand-off only
+        MppiFuse f1 = fuse;                                                            // ... of a merge + update step; the request carries the sequence number
+        f1.mode = 1; f1.seq = 0u;
+        const FuseArgs fz = mppi_fuse_args(f1, stage_ok, a, E::C, u_nom0, u_nom1);
         const unsigned long long ticks = (unsigned long long)(idle_us * 100.0);        // wall_clock64: 100 MHz
         using RA = ResidentArgs<typename E::K>;
         static_assert(sizeof(RA) <= CTK_RES_ARGS_BYTES, "resident argument block");
         RA* hostra = static_cast<RA*>(args_host);               // staging that outlives the asynchronous copy (the handle's)
-        *hostra = RA{a.interp, parts, a.N, a.H, a.P, pmagic, u_nom0, u_nom1, a, k, m, fz};
+        *hostra = RA{a.interp, parts, a.N, a.H, a.P, ctk_magic_of(PC), u_nom0, u_nom1, a, k, m, fz};
         const hipError_t ce = hipMemcpyAsync(args_dev, hostra, sizeof(RA), hipMemcpyHostToDevice, st);
         if (ce != hipSuccess) return ce;
-        const int form = mppi_env_form<EV>((int)grid.x, PC, true);
-        auto launch = [&](auto form_c) {
+        // (every environment has the resident kernel in all four forms, though only a pipelined one's launch can carry OLD_RECUR)
+        with_mppi_form<true>(mppi_env_form<EV>((int)grid.x, PC, true), [&](auto form_c) {
             hipLaunchKernelGGL((ctk_mppi_resident<EV, decltype(form_c)::value>), grid, block, lds, st, static_cast<const RA*>(args_dev), box_dev, box_local,
                                stat_dev, relay, ticks, first_req);
-        };
-        using std::integral_constant;
-        if (form == 0) launch(integral_constant<int, 0>{});
-        else if (form == CTK_MPPI_FORM_WIDE_TAIL) launch(integral_constant<int, CTK_MPPI_FORM_WIDE_TAIL>{});
-        else if constexpr (env_pipelined<EV>::value) {
-            if (form == CTK_MPPI_FORM_OLD_RECUR) launch(integral_constant<int, CTK_MPPI_FORM_OLD_RECUR>{});
-            else launch(integral_constant<int, CTK_MPPI_FORM_WIDE_TAIL | CTK_MPPI_FORM_OLD_RECUR>{});
-        }
+        });
     });
     return hipGetLastError();
 }

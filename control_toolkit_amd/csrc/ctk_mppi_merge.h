@@ -41,6 +41,13 @@ struct MppiUpdateArgs {
     int C = 1;             // control inputs: records carry b[P*C], the update runs per channel
     float lo_c[CTK_MAX_INPUTS] = {}, hi_c[CTK_MAX_INPUTS] = {};   // C > 1
 };
+// ... of an in-launch tail (host side): tables from memory, the limits of `a`'s C inputs
+inline MppiUpdateArgs mppi_update_args(const RolloutArgs& a, int C, const float* u_nom_in, float* u_nom_out, float* u_dev, float* u_host, uint32_t seq) {
+    MppiUpdateArgs up{nullptr, nullptr, nullptr, nullptr, a.H, a.interp, u_nom_in, u_nom_out, a.lo[0], a.hi[0], u_dev, u_host, seq};
+    up.C = C;
+    for (int c = 0; c < C; ++c) { up.lo_c[c] = a.lo[c]; up.hi_c[c] = a.hi[c]; }
+    return up;
+}
 
 // scratch: >= 8 + (P + 1) + min(cnt, MERGE_CHUNK) floats of LDS, plus cnt*(2+P) more when `stage`
 // (all records fetched into LDS by ONE wide pass: one memory round trip instead of one per record).

@@ -1874,7 +1874,6 @@ __global__ __launch_bounds__(256) void ctk_g_gru_advance4(RolloutArgs a, const f
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-static uint32_t g4_magic_of(int d) { return d >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d) : 0u; }
 static int split_waves(int net) { return net == NET_GRU ? SplitGru::WAVES : net == NET_MLP64 ? SplitMlp64<false>::WAVES : SplitMlp<false>::WAVES; }
 static int split_ex_fwd(int net) { return net == NET_GRU ? SplitGru::EX_FWD : net == NET_MLP64 ? SplitMlp64<false>::EX_FWD : SplitMlp<false>::EX_FWD; }
 static int split_ex_bwd(int net) { return net == NET_GRU ? SplitGru::EX_BWD : SplitMlp<false>::EX_BWD; }
@@ -1913,8 +1912,7 @@ static void launch_descent_split(hipStream_t st, const RolloutArgs& a_in, const 
                                  float* v, const float* bc_table, int bc_len, int t0, int iters, const float* wperm, const float* wperm_bwd,
                                  const float* hidden, float* scratch, hipEvent_t e0, hipEvent_t e1) {
     using E = Env<EV>;
-    RolloutArgs a = a_in;
-    a.C = E::C; a.p_magic = g4_magic_of(a.H * E::C);
+    const RolloutArgs a = ctk_descent_args(a_in, E::C);
     const typename E::K k = E::derive(params, dt, isteps);
     const dim3 grid((a.N + G4_TRAJ - 1) / G4_TRAJ), block(64 * SP::WAVES);
     const size_t lds = ctk_g_rpgd_descent_split_lds(SP::NET, a.H, E::C);
@@ -1968,8 +1966,7 @@ static void launch_wide_split(hipStream_t st, const RolloutArgs& a_in, const flo
     // forward passes of the FIRST overlapped phase launch of the process never raise that step's flags
     static const int diag_step = getenv("CTK_DIAG_RPGD_WITHHOLD_FLAG") ? atoi(getenv("CTK_DIAG_RPGD_WITHHOLD_FLAG")) : -1;
     static std::atomic<int> diag_armed{diag_step >= 0 ? 1 : 0};
-    RolloutArgs a = a_in;
-    a.C = E::C; a.p_magic = g4_magic_of(a.H * E::C);
+    const RolloutArgs a = ctk_descent_args(a_in, E::C);
     const typename E::K k = E::derive(params, dt, isteps);
     const int tiles = (a.N + G4_TRAJ - 1) / G4_TRAJ;
     size_t lds = (size_t)(SplitMlp<K3>::EX_FWD + G4_RED + 2 * (a.H + 1) * 128 + gw_gd_floats(a.H, E::C) + a.H * E::C * G4_LD) * sizeof(float);
@@ -2030,8 +2027,7 @@ hipError_t ctk_launch_g_rpgd_persist64(hipStream_t st, int env, const RolloutArg
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
         constexpr bool K3 = E::S + E::C > 8;
-        RolloutArgs a = a_in;
-        a.C = E::C; a.p_magic = g4_magic_of(a.H * E::C);
+        const RolloutArgs a = ctk_descent_args(a_in, E::C);
         const typename E::K k = E::derive(params, dt, isteps);
         const int tiles = (a.N + G4_TRAJ - 1) / G4_TRAJ, per_it = tiles * a.H, W = std::min(240, per_it);
         if (pers->seq0 < 64u || pers->seq0 > 0xffffff00u) pers->seq0 = 64u;
@@ -2083,9 +2079,8 @@ static void launch_rollout_split(hipStream_t st, int mode, const RolloutArgs& a_
                                  const float* samples, const float* base, const float* scale, int rng_kind, const float* wperm, const float* hidden,
                                  float* parts, bool log, hipEvent_t e0, hipEvent_t e1, const MppiFuse* fuse) {
     using E = Env<EV>;
-    RolloutArgs a = a_in;
     const int cols = (mode == CTK_G_MODE_MPPI ? a_in.P : a_in.H) * E::C;
-    a.P = cols; a.p_magic = g4_magic_of(cols); a.C = E::C;
+    const RolloutArgs a = ctk_rollout_args(a_in, E::C, cols);
     const typename E::K k = E::derive(params, dt, isteps);
     const int tiles = ctk_g_rollout_split_blocks(a.N);
     const NetFuse gz = ctk_net_fuse(SP::WAVES == 4 ? fuse : nullptr, mode, a, E::C, base, tiles, cols);   // mppi_ll_tail: 256-thread workgroups
@@ -2094,13 +2089,13 @@ static void launch_rollout_split(hipStream_t st, int mode, const RolloutArgs& a_
         constexpr int T = decltype(tiles_per_wg)::value;
         const dim3 grid(tiles / T), block(64 * SP::WAVES * T);
         const size_t lds = T == 1 ? lds1 : (size_t)T * ctk_g_rollout_split_lds(SP::NET, cols, a.H, E::C);
-        if (mode == CTK_G_MODE_MPPI) {
-            if (log) CTK_LAUNCH((ctk_g_rollout_split<EV, SP, CTK_G_MODE_MPPI, true, T>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind, wperm, hidden, parts, gz);
-            else CTK_LAUNCH((ctk_g_rollout_split<EV, SP, CTK_G_MODE_MPPI, false, T>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind, wperm, hidden, parts, gz);
-        } else {
-            if (log) CTK_LAUNCH((ctk_g_rollout_split<EV, SP, CTK_G_MODE_AFFINE, true, T>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind, wperm, hidden, parts, gz);
-            else CTK_LAUNCH((ctk_g_rollout_split<EV, SP, CTK_G_MODE_AFFINE, false, T>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale, rng_kind, wperm, hidden, parts, gz);
-        }
+        ctk_with_bool(mode == CTK_G_MODE_MPPI, [&](auto mppi_c) {
+            ctk_with_bool(log, [&](auto log_c) {
+                constexpr int MODE = decltype(mppi_c)::value ? CTK_G_MODE_MPPI : CTK_G_MODE_AFFINE;
+                CTK_LAUNCH((ctk_g_rollout_split<EV, SP, MODE, decltype(log_c)::value, T>), grid, block, lds, st, e0, e1, a, k, mk, samples, base, scale,
+                           rng_kind, wperm, hidden, parts, gz);
+            });
+        });
     };
     if constexpr (SP::WAVES == 2) {
         if (rollout_split_two_tiles(SP::NET, a.N, a.H, cols, E::C)) { go(std::integral_constant<int, 2>{}); return; }

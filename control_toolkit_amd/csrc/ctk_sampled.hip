@@ -31,7 +31,7 @@ __host__ __device__ inline int affine_traj(int pred) { return pred == CTK_PRED_G
 // Optional in-launch arg-min tail (random-action, optimizer_random_action_tf.py:62-68: u = first input of the cheapest
 // plan): every block hands {key(J), index, first input} of its cheapest rollout to block 0 as {payload, sequence number}
 // words (the hand-off form of ctk_mppi.hip), block 0 picks the global minimum under the total order (J, index) — what
-// ctk_select_topk(K = 1) + ctk_pick_best_first do in two more launches — and publishes u.
+// ctk_select_topk(K = 1) + ctk_g_pick_best_first do in two more launches — and publishes u.
 struct BestArgs {
     unsigned long long* ll;   // [blocks][2 + C] words {key, index, first input[C]}; nullptr: no tail
     uint32_t seq;
@@ -381,35 +381,6 @@ __global__ __launch_bounds__(256) void ctk_cem_refit(const float* __restrict__ Q
     }
 }
 
-// optimizer_cem_tf.py:99-102: clip std, shift both by one step, refill the tail; u = elite[0,0]
-// std_max / u_from_mu: optimizer_cem_naive_grad_tf.py:101-104 clips the stdev to [min, 10] and applies the
-// MEAN's first input; optimizer_cem_tf.py:99-101 clips to [min, 1e8] and applies the best elite's
-__global__ __launch_bounds__(256) void ctk_cem_finish(const float* __restrict__ Q, int ldq, const int* __restrict__ idx, int H,
-                                                      float* __restrict__ mu, float* __restrict__ sd, float std_min,
-                                                      float init_std, float mid, float* __restrict__ u_dev,
-                                                      float* __restrict__ u_host, uint32_t seq, float std_max, int u_from_mu) {
-    extern __shared__ float lds[];
-    float* m_s = lds;
-    float* s_s = lds + H;
-    const int t = threadIdx.x;
-    for (int h = t; h < H; h += 256) {
-        m_s[h] = mu[h];
-        s_s[h] = fminf(fmaxf(sd[h], std_min), std_max);
-    }
-    __syncthreads();
-    for (int h = t; h < H; h += 256) {
-        mu[h] = (h + 1 < H) ? m_s[h + 1] : mid;
-        sd[h] = (h + 1 < H) ? s_s[h + 1] : init_std;
-    }
-    __syncthreads();
-    if (t == 0) publish_u(u_dev, u_host, u_from_mu ? m_s[0] : Q[(size_t)idx[0] * ldq], seq);
-}
-
-__global__ void ctk_pick_best_first(const float* __restrict__ Q, int ldq, const int* __restrict__ idx, int H,
-                                    float* __restrict__ u_dev, float* __restrict__ u_host, uint32_t seq) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) publish_u(u_dev, u_host, Q[(size_t)idx[0] * ldq], seq);
-}
-
 // plans of a CEM-with-gradient iteration, without rolling them out (the descent kernel does that)
 __global__ __launch_bounds__(256) void ctk_sample_plans(RolloutArgs a, const float* __restrict__ samples,
                                                         const float* __restrict__ mu, const float* __restrict__ sd,
@@ -530,24 +501,28 @@ const char* ctk_affine_rollout_env_name(int env, bool log) {
     return ctk_kernel_name("ctk_affine_rollout<%d, 0, %4$s>", env, 0, 0, log ? "true" : "false");
 }
 
+// one launch of ctk_affine_rollout<ENV, PRED, log>: `a` as the kernel takes it (a.P sample columns per row, a.p_magic their divisor);
+// bst (analytic predictor only): the in-launch arg-min tail
+template <int ENV, int PRED>
+static void launch_affine(hipStream_t st, dim3 grid, size_t lds, const RolloutArgs& a, const typename Env<ENV>::K& k, const float* samples, int rng_kind,
+                          const float* base, const float* scale, const float* wperm, bool log, hipEvent_t e0, hipEvent_t e1, const AffineBest* bst) {
+    BestArgs bargs{nullptr, 0u, nullptr, nullptr, nullptr};
+    if (bst && bst->ll) bargs = BestArgs{bst->ll, bst->seq, bst->u_dev, bst->u_host, bst->idx_out};
+    ctk_with_bool(log, [&](auto log_c) {
+        CTK_LAUNCH((ctk_affine_rollout<ENV, PRED, decltype(log_c)::value>), grid, dim3(SAMP_BLOCK), lds, st, e0, e1, samples, base, scale, wperm, rng_kind,
+                   a.N, a.H, a.P, a.p_magic, a, k, bargs);
+    });
+}
+
+// CartPole, any predictor: `a` and the cached constants `k` are the handle's
 hipError_t ctk_launch_affine_rollout(hipStream_t st, int pred, const RolloutArgs& a, const EnvK& k, const float* samples,
                                      int rng_kind, const float* base, const float* scale, const float* wperm, bool log,
                                      hipEvent_t e0, hipEvent_t e1, const AffineBest* bst) {
-    BestArgs bargs{nullptr, 0u, nullptr, nullptr, nullptr};
-    if (bst && bst->ll && pred == CTK_PRED_ODE) bargs = BestArgs{bst->ll, bst->seq, bst->u_dev, bst->u_host, bst->idx_out};
-    const int tr = affine_traj(pred);
-    const dim3 grid((a.N + tr - 1) / tr), block(SAMP_BLOCK);
+    const dim3 grid(ctk_affine_rollout_blocks(pred, a.N));
     const size_t lds = ctk_affine_rollout_lds(a.H, pred);
-    if (pred == CTK_PRED_ODE) {
-        if (log) CTK_LAUNCH((ctk_affine_rollout<CTK_ENV_CARTPOLE, CTK_PRED_ODE, true>), grid, block, lds, st, e0, e1, samples, base, scale, wperm, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
-        else CTK_LAUNCH((ctk_affine_rollout<CTK_ENV_CARTPOLE, CTK_PRED_ODE, false>), grid, block, lds, st, e0, e1, samples, base, scale, wperm, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
-    } else if (pred == CTK_PRED_MLP) {
-        if (log) CTK_LAUNCH((ctk_affine_rollout<CTK_ENV_CARTPOLE, CTK_PRED_MLP, true>), grid, block, lds, st, e0, e1, samples, base, scale, wperm, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
-        else CTK_LAUNCH((ctk_affine_rollout<CTK_ENV_CARTPOLE, CTK_PRED_MLP, false>), grid, block, lds, st, e0, e1, samples, base, scale, wperm, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
-    } else {
-        if (log) CTK_LAUNCH((ctk_affine_rollout<CTK_ENV_CARTPOLE, CTK_PRED_GRU, true>), grid, block, lds, st, e0, e1, samples, base, scale, wperm, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
-        else CTK_LAUNCH((ctk_affine_rollout<CTK_ENV_CARTPOLE, CTK_PRED_GRU, false>), grid, block, lds, st, e0, e1, samples, base, scale, wperm, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
-    }
+    if (pred == CTK_PRED_ODE) launch_affine<CTK_ENV_CARTPOLE, CTK_PRED_ODE>(st, grid, lds, a, k, samples, rng_kind, base, scale, wperm, log, e0, e1, bst);
+    else if (pred == CTK_PRED_MLP) launch_affine<CTK_ENV_CARTPOLE, CTK_PRED_MLP>(st, grid, lds, a, k, samples, rng_kind, base, scale, wperm, log, e0, e1, nullptr);
+    else launch_affine<CTK_ENV_CARTPOLE, CTK_PRED_GRU>(st, grid, lds, a, k, samples, rng_kind, base, scale, wperm, log, e0, e1, nullptr);
     return hipGetLastError();
 }
 
@@ -556,19 +531,11 @@ hipError_t ctk_launch_affine_rollout(hipStream_t st, int pred, const RolloutArgs
 hipError_t ctk_launch_affine_rollout_env(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a_in,
                                          const float* samples, int rng_kind, const float* base, const float* scale, bool log,
                                          hipEvent_t e0, hipEvent_t e1, const AffineBest* bst) {
-    BestArgs bargs{nullptr, 0u, nullptr, nullptr, nullptr};
-    if (bst && bst->ll) bargs = BestArgs{bst->ll, bst->seq, bst->u_dev, bst->u_host, bst->idx_out};
-    const dim3 grid((a_in.N + SAMP_TRAJ - 1) / SAMP_TRAJ), block(SAMP_BLOCK);
+    const dim3 grid(ctk_affine_rollout_blocks(CTK_PRED_ODE, a_in.N));
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
-        RolloutArgs a = a_in;
-        const int HC = a.H * E::C;
-        a.C = E::C; a.P = HC;
-        a.p_magic = HC >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)HC - 1) / (uint64_t)HC) : 0u;
-        const typename E::K k = E::derive(params, dt, isteps);
-        const size_t lds = (size_t)affine_carve_floats(HC, SAMP_TRAJ) * sizeof(float);
-        if (log) CTK_LAUNCH((ctk_affine_rollout<EV, CTK_PRED_ODE, true>), grid, block, lds, st, e0, e1, samples, base, scale, (const float*)nullptr, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
-        else CTK_LAUNCH((ctk_affine_rollout<EV, CTK_PRED_ODE, false>), grid, block, lds, st, e0, e1, samples, base, scale, (const float*)nullptr, rng_kind, a.N, a.H, a.P, a.p_magic, a, k, bargs);
+        launch_affine<EV, CTK_PRED_ODE>(st, grid, ctk_affine_rollout_env_lds(EV, a_in.H), ctk_rollout_args(a_in, E::C, a_in.H * E::C),
+                                        E::derive(params, dt, isteps), samples, rng_kind, base, scale, nullptr, log, e0, e1, bst);
     });
     return hipGetLastError();
 }
@@ -582,17 +549,16 @@ size_t ctk_affine_rollout_mix_lds(int env, int H) {
 hipError_t ctk_launch_affine_rollout_mix(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a_in,
                                          const float* normals, const float* uniforms, const float* mix, uint32_t ustream, bool log,
                                          hipEvent_t e0, hipEvent_t e1) {
-    const dim3 grid((a_in.N + SAMP_TRAJ - 1) / SAMP_TRAJ), block(SAMP_BLOCK);
+    const dim3 grid(ctk_affine_rollout_blocks(CTK_PRED_ODE, a_in.N)), block(SAMP_BLOCK);
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
-        RolloutArgs a = a_in;
-        const int HC = a.H * E::C;
-        a.C = E::C; a.P = HC;
-        a.p_magic = HC >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)HC - 1) / (uint64_t)HC) : 0u;
+        const RolloutArgs a = ctk_rollout_args(a_in, E::C, a_in.H * E::C);
         const typename E::K k = E::derive(params, dt, isteps);
-        const size_t lds = (size_t)(affine_carve_floats(HC, SAMP_TRAJ) + 2 * HC) * sizeof(float);
-        if (log) CTK_LAUNCH((ctk_affine_rollout_mix<EV, true>), grid, block, lds, st, e0, e1, normals, mix, uniforms, ustream, a.N, a.H, a.P, a.p_magic, a, k);
-        else CTK_LAUNCH((ctk_affine_rollout_mix<EV, false>), grid, block, lds, st, e0, e1, normals, mix, uniforms, ustream, a.N, a.H, a.P, a.p_magic, a, k);
+        const size_t lds = ctk_affine_rollout_mix_lds(EV, a.H);
+        ctk_with_bool(log, [&](auto log_c) {
+            CTK_LAUNCH((ctk_affine_rollout_mix<EV, decltype(log_c)::value>), grid, block, lds, st, e0, e1, normals, mix, uniforms, ustream, a.N, a.H, a.P,
+                       a.p_magic, a, k);
+        });
     });
     return hipGetLastError();
 }
@@ -623,19 +589,5 @@ hipError_t ctk_launch_pack_candidates(hipStream_t st, const float* J, const floa
     const int total = K * (2 + H);
     hipLaunchKernelGGL(ctk_pack_candidates, dim3((total + 255) / 256 > 64 ? 64 : (total + 255) / 256), dim3(256), 0, st, J, Q, idx, K, H,
                        global_offset, cand);
-    return hipGetLastError();
-}
-
-hipError_t ctk_launch_cem_finish(hipStream_t st, const float* Q, const int* idx, int H, float* mu, float* sd, float std_min,
-                                 float init_std, float mid, float* u_dev, float* u_host, uint32_t seq, int ldq, float std_max,
-                                 int u_from_mu) {
-    hipLaunchKernelGGL(ctk_cem_finish, dim3(1), dim3(256), 2 * H * sizeof(float), st, Q, ldq, idx, H, mu, sd, std_min, init_std, mid,
-                       u_dev, u_host, seq, std_max, u_from_mu);
-    return hipGetLastError();
-}
-
-hipError_t ctk_launch_pick_best_first(hipStream_t st, const float* Q, const int* idx, int H, float* u_dev, float* u_host, uint32_t seq,
-                                      int ldq) {
-    hipLaunchKernelGGL(ctk_pick_best_first, dim3(1), dim3(64), 0, st, Q, ldq, idx, H, u_dev, u_host, seq);
     return hipGetLastError();
 }

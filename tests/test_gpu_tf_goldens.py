@@ -116,6 +116,28 @@ def test_random_action_matches_reference_golden(case):
     e.close()
 
 
+def test_random_action_three_launch_step_equals_one_launch_step(monkeypatch):
+    """CartPole through rollout + ctk_select_topk + ctk_g_pick_best_first: a handle created without the hand-off words (CTK_NO_LL,
+    read at ctk_create) has no in-launch arg-min.  Same rollouts, same total order (J, index), same plan read back: u and the
+    winner's index equal the default handle's bit for bit."""
+    d = load("random_cfg1.npz")
+    assert str(d["environment"]) == "CartPole" and str(d["predictor"]) == "ODE"
+    one = engine_from(d, "random_action")
+    monkeypatch.setenv("CTK_NO_LL", "1")
+    three = engine_from(d, "random_action")
+    monkeypatch.delenv("CTK_NO_LL")
+    for t in range(int(d["steps"])):
+        u1 = one.step(d[f"s_{t}"], d[f"u01_{t}"], u_prev=d[f"u_prev_{t}"])
+        u3 = three.step(d[f"s_{t}"], d[f"u01_{t}"], u_prev=d[f"u_prev_{t}"])
+        np.testing.assert_array_equal(np.asarray(u3, np.float32).view(np.uint32), np.asarray(u1, np.float32).view(np.uint32))
+        assert int(three.read("BEST_IDX")[0]) == int(one.read("BEST_IDX")[0]) == int(np.argmin(d[f"J_{t}"]))
+        np.testing.assert_allclose(u3, d[f"u_{t}"], rtol=1e-6, atol=1e-7)
+        for e in (one, three):
+            e.set_state(d[f"u_{t}"].astype(np.float32))
+    one.close()
+    three.close()
+
+
 @pytest.mark.parametrize("case", CEM_NAIVE_GRAD_CASES)
 def test_cem_naive_grad_matches_reference_golden(case):
     d = load(f"cem_naive_grad_{case}.npz")
