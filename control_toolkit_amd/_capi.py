@@ -125,6 +125,22 @@ SYMBOLS = {
     "ctk_resident_enable": (C.c_int, [_H, C.c_int, C.c_double]),
     "ctk_resident_stop": (C.c_int, [_H]),
     "ctk_resident_stats": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    # batched MPPI (ctk_batch_*): _H is the ctk_batch* there
+    "ctk_batch_create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
+    "ctk_batch_destroy": (None, [_H]),
+    "ctk_batch_last_error": (C.c_char_p, [_H]),
+    "ctk_batch_size": (C.c_int, [_H]),
+    "ctk_batch_samples_needed": (C.c_size_t, [_H]),
+    "ctk_batch_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ctk_batch_reset": (C.c_int, [_H, C.c_int, C.c_void_p]),
+    "ctk_batch_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_batch_get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_batch_set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_batch_set_param": (C.c_int, [_H, C.c_int, C.c_float]),
+    "ctk_batch_get_param": (C.c_int, [_H, C.c_int, _FP]),
+    "ctk_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
+    "ctk_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
+    "ctk_batch_dominant_kernel": (C.c_char_p, [_H]),
 }
 
 
@@ -221,6 +237,43 @@ def _f32(a, shape=None) -> np.ndarray:
     return out
 
 
+def _make_config(optimizer: str, predictor: str, env_id: int, environment: str, Cn: int, *, num_rollouts, mpc_horizon, dt, action_low,
+                 action_high, period_interpolation_inducing_points, seed, device, intermediate_steps, materialize_trajectories,
+                 global_rollout_offset, num_states, num_control_inputs, generic_kernels, **kw) -> "CtkConfig":
+    """the ctk_config of an engine (CtkEngine) or of a batch (CtkMppiBatch) from the constructor keywords"""
+    cfg = CtkConfig()
+    cfg.struct_size = C.sizeof(CtkConfig)
+    cfg.optimizer, cfg.predictor, cfg.device = OPTIMIZERS[optimizer], PREDICTORS[predictor], device
+    cfg.num_rollouts, cfg.mpc_horizon = int(num_rollouts), int(mpc_horizon)
+    cfg.num_states, cfg.num_control_inputs = int(num_states), int(num_control_inputs)
+    cfg.period_interpolation_inducing_points = int(period_interpolation_inducing_points)
+    cfg.intermediate_steps = int(intermediate_steps)
+    cfg.materialize_trajectories = int(bool(materialize_trajectories))
+    cfg.global_rollout_offset = int(global_rollout_offset)
+    cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    cfg.dt = float(dt)
+    cfg.environment, cfg.generic_kernels = env_id, int(bool(generic_kernels))
+    lo = np.broadcast_to(np.asarray(action_low, np.float32).reshape(-1), (Cn,)) if np.size(action_low) in (1, Cn) else None
+    hi = np.broadcast_to(np.asarray(action_high, np.float32).reshape(-1), (Cn,)) if np.size(action_high) in (1, Cn) else None
+    if lo is None or hi is None:
+        raise ValueError(f"control limits must be scalars or have {Cn} entries (num_control_inputs of {environment})")
+    for c in range(Cn):
+        cfg.action_low[c], cfg.action_high[c] = float(lo[c]), float(hi[c])
+    # defaults keep unrelated optimizers' fields valid
+    defaults = dict(cc_weight=1.0, R=1.0, LBD=100.0, NU=1000.0, SQRTRHOINV=0.03, cem_outer_it=1, cem_best_k=1,
+                    warmup=0, warmup_iterations=0, cem_initial_action_stdev=0.5, cem_stdev_min=0.01,
+                    outer_its=1, resamp_per=1, shift_previous=1, opt_keep_k=1, sampling_distribution=0,
+                    sample_whole_control_space=0, sample_stdev=0.5, sample_mean=0.0, sample_min=-1.0, sample_max=1.0, learning_rate=0.05,
+                    gradmax_clip=5.0, adam_beta_1=0.9, adam_beta_2=0.999, adam_epsilon=1e-8, adam_rule=0, predictor_hidden1=0, predictor_hidden2=0)
+    unknown = set(kw) - set(defaults)
+    if unknown:
+        raise TypeError(f"unknown engine arguments: {sorted(unknown)}")
+    defaults.update(kw)
+    for k, v in defaults.items():
+        setattr(cfg, k, type(getattr(cfg, k))(v))
+    return cfg
+
+
 class CtkEngine:
     """Owns one ctk_handle (one optimizer instance on one GPU)."""
 
@@ -242,42 +295,18 @@ class CtkEngine:
             raise ValueError(f"unknown optimizer {optimizer!r}")
         if predictor not in PREDICTORS:
             raise NotImplementedError(f"predictor_specification {predictor!r} is not built (have: {list(PREDICTORS)})")
-        cfg = CtkConfig()
-        cfg.struct_size = C.sizeof(CtkConfig)
-        cfg.optimizer, cfg.predictor, cfg.device = OPTIMIZERS[optimizer], PREDICTORS[predictor], device
-        cfg.num_rollouts, cfg.mpc_horizon = int(num_rollouts), int(mpc_horizon)
-        cfg.num_states, cfg.num_control_inputs = int(num_states), int(num_control_inputs)
-        cfg.period_interpolation_inducing_points = int(period_interpolation_inducing_points)
-        cfg.intermediate_steps = int(intermediate_steps)
-        cfg.materialize_trajectories = int(bool(materialize_trajectories))
-        cfg.global_rollout_offset = int(global_rollout_offset)
-        cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        cfg.dt = float(dt)
-        cfg.environment, cfg.generic_kernels = env_id, int(bool(generic_kernels))
         # hidden widths of a network predictor (the <h1>H1-<h2>H2 of the reference's network names): widths above 32 (MLP, up to 64) build
         # the handle on the 64-unit kernels; narrower networks are embedded exactly when their weights are set
         self.predictor_hidden = None if predictor_hidden is None else (int(predictor_hidden[0]), int(predictor_hidden[1]))
         self.native_hidden = (64, 64) if (self.predictor_hidden and max(self.predictor_hidden) > 32) else (32, 32)
-        lo = np.broadcast_to(np.asarray(action_low, np.float32).reshape(-1), (Cn,)) if np.size(action_low) in (1, Cn) else None
-        hi = np.broadcast_to(np.asarray(action_high, np.float32).reshape(-1), (Cn,)) if np.size(action_high) in (1, Cn) else None
-        if lo is None or hi is None:
-            raise ValueError(f"control limits must be scalars or have {Cn} entries (num_control_inputs of {environment})")
-        for c in range(Cn):
-            cfg.action_low[c], cfg.action_high[c] = float(lo[c]), float(hi[c])
-        # defaults keep unrelated optimizers' fields valid
-        defaults = dict(cc_weight=1.0, R=1.0, LBD=100.0, NU=1000.0, SQRTRHOINV=0.03, cem_outer_it=1, cem_best_k=1,
-                        warmup=0, warmup_iterations=0, cem_initial_action_stdev=0.5, cem_stdev_min=0.01,
-                        outer_its=1, resamp_per=1, shift_previous=1, opt_keep_k=1, sampling_distribution=0,
-                        sample_whole_control_space=0, sample_stdev=0.5, sample_mean=0.0, sample_min=-1.0, sample_max=1.0, learning_rate=0.05,
-                        gradmax_clip=5.0, adam_beta_1=0.9, adam_beta_2=0.999, adam_epsilon=1e-8, adam_rule=0, predictor_hidden1=0, predictor_hidden2=0)
-        unknown = set(kw) - set(defaults)
-        if unknown:
-            raise TypeError(f"unknown engine arguments: {sorted(unknown)}")
-        defaults.update(kw)
         if self.predictor_hidden is not None:
-            defaults.update(predictor_hidden1=self.predictor_hidden[0], predictor_hidden2=self.predictor_hidden[1])
-        for k, v in defaults.items():
-            setattr(cfg, k, type(getattr(cfg, k))(v))
+            kw = dict(kw, predictor_hidden1=self.predictor_hidden[0], predictor_hidden2=self.predictor_hidden[1])
+        cfg = _make_config(optimizer, predictor, env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                           action_low=action_low, action_high=action_high,
+                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                           global_rollout_offset=global_rollout_offset, num_states=num_states, num_control_inputs=num_control_inputs,
+                           generic_kernels=generic_kernels, **kw)
         self._lib, self.cfg = lib, cfg
         self.optimizer, self.predictor = optimizer, predictor
         self.N, self.H = int(num_rollouts), int(mpc_horizon)
@@ -596,3 +625,186 @@ class CtkEngine:
 
     def dominant_kernel(self) -> str:
         return self._lib.ctk_dominant_kernel(self._h).decode()
+
+
+# ---- batched MPPI (include/ctk_hip.h: ctk_batch_*) ------------------------------------------------------------------------------------
+def batch_ids(num_problems: int, ids) -> Optional[np.ndarray]:
+    """the id list of a batch call: None (all problems), or strictly ascending problem indices as int32"""
+    if ids is None:
+        return None
+    arr = np.ascontiguousarray(np.asarray(ids).reshape(-1))
+    if arr.size < 1 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("ids must be a non-empty list of problem indices (or None: all problems)")
+    if arr.min() < 0 or arr.max() >= num_problems:
+        raise ValueError(f"ids must lie in 0 .. {num_problems - 1} (the batch holds {num_problems} problems)")
+    if np.any(np.diff(arr) <= 0):
+        raise ValueError("ids must be strictly ascending")
+    return arr.astype(np.int32)
+
+
+def batch_step_args(num_problems: int, S: int, Cn: int, per_problem: int, states, samples=None, u_prev=None, ids=None):
+    """Checks the arguments of CtkMppiBatch.step without touching a device: ids (batch_ids), states [n, S], u_prev None or [n, C],
+    samples None, an int device pointer or a host array of n * per_problem draws ([n, N, P, C]).  Returns (ids, n, samples as fp32 or
+    as given); states and u_prev are copied by the caller into its preallocated buffers."""
+    idv = batch_ids(num_problems, ids)
+    n = num_problems if idv is None else int(idv.size)
+    st = np.asarray(states)
+    if st.shape != (n, S) and not (n == 1 and st.shape == (S,)):
+        raise ValueError(f"states must have shape ({n}, {S}): one row per stepped problem, got {tuple(st.shape)}")
+    if u_prev is not None:
+        up = np.asarray(u_prev)
+        if up.shape != (n, Cn) and not (Cn == 1 and up.shape == (n,)):
+            raise ValueError(f"u_prev must have shape ({n}, {Cn}): one row per stepped problem, got {tuple(up.shape)}")
+    if samples is not None and type(samples) is not int:
+        samples = _f32(samples)
+        if samples.size != n * per_problem or (samples.ndim > 1 and samples.shape[0] != n):
+            raise ValueError(f"step of {n} problems consumes {n} x {per_problem} draws ([n, N, P, C]), got shape {tuple(samples.shape)}")
+    return idv, n, samples
+
+
+class CtkMppiBatch:
+    """Owns one ctk_batch: num_problems independent MPPI controllers of ONE configuration (the MPPI keywords of CtkEngine), stepped by
+    one kernel launch per step.  Problem p behaves bit for bit like CtkEngine("mppi", "ODE", seed=seeds[p], ...) given the same calls.
+    seeds: one per problem (default seed + p)."""
+
+    def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "mppi", predictor: str = "ODE",
+                 num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
+                 period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
+                 materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
+                 num_control_inputs: int = None, generic_kernels: bool = False, **kw):
+        # what needs no device is checked before the library is asked for one
+        if int(num_problems) < 1:
+            raise ValueError(f"a batch holds at least one problem (num_problems == {num_problems})")
+        B = int(num_problems)
+        if optimizer != "mppi":
+            raise NotImplementedError(f"a batch steps MPPI controllers only (optimizer {optimizer!r}); the other optimizers run as CtkEngine")
+        if predictor != "ODE":
+            raise NotImplementedError(f"the batch kernel rolls out the analytic (ODE) predictor only (predictor {predictor!r}); "
+                                      "network predictors run as CtkEngine")
+        if seeds is not None:
+            seeds = np.ascontiguousarray(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in np.asarray(seeds, dtype=object).reshape(-1)], np.uint64))
+            if seeds.size != B:
+                raise ValueError(f"seeds must have one entry per problem ({B}), got {seeds.size}")
+        lib, env_id = environment_library(environment)
+        S, Cn, self.param_names = environment_info(environment)
+        self.environment, self.S, self.C, self.B = environment, S, Cn, B
+        cfg = _make_config("mppi", "ODE", env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                           action_low=action_low, action_high=action_high,
+                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                           global_rollout_offset=global_rollout_offset, num_states=S if num_states is None else num_states,
+                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs, generic_kernels=generic_kernels, **kw)
+        self._lib, self.cfg = lib, cfg
+        self.N, self.H = int(num_rollouts), int(mpc_horizon)
+        self._h = _H()
+        rc = lib.ctk_batch_create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
+        if rc != 0:
+            msg = lib.ctk_batch_last_error(None).decode()
+            self._h = _H()
+            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(msg)
+        self._per = int(lib.ctk_batch_samples_needed(self._h))
+        # preallocated argument buffers, as CtkEngine.step's: rows 0 .. n-1 are the stepped problems'
+        self._s = np.zeros((B, S), np.float32)
+        self._up = np.zeros((B, Cn), np.float32)
+        self._u = np.zeros((B, Cn), np.float32)
+        self._ids = np.zeros(B, np.int32)
+        self._s_p, self._up_p, self._u_p, self._ids_p = (a.ctypes.data for a in (self._s, self._up, self._u, self._ids))
+        self._step_fn = lib.ctk_batch_step
+
+    def _check(self, rc: int):
+        if rc != 0:
+            msg = self._lib.ctk_batch_last_error(self._h).decode()
+            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(f"[ctk {rc}] {msg}")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.ctk_batch_destroy(self._h)
+            self._h = _H()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.B
+
+    def samples_needed(self) -> int:
+        """draws one problem's step consumes (N * P * C)"""
+        return self._per
+
+    def step(self, S, samples=None, u_prev=None, ids=None) -> np.ndarray:
+        """S [n, num_states], one row per stepped problem in the order of ids (None: all problems).  samples: None (device Philox), a
+        host array [n, N, P, C] or an int device pointer to such an array.  u_prev [n, C] or None (every problem's own last output).
+        Returns u [n, C].  CtkError naming the problems whose in-launch hand-off timed out: the other problems' rows are valid (`last_u`)."""
+        idv, n, samples = batch_step_args(self.B, self.S, self.C, self._per, S, samples, u_prev, ids)
+        self._s[:n] = np.asarray(S).reshape(n, self.S)
+        up_p = None
+        if u_prev is not None:
+            self._up[:n] = np.asarray(u_prev).reshape(n, self.C)
+            up_p = self._up_p
+        ids_p = None
+        if idv is not None:
+            self._ids[:n] = idv
+            ids_p = self._ids_p
+        if samples is None:
+            sp, loc = None, LOC_NONE
+        elif type(samples) is int:
+            sp, loc = samples, LOC_DEVICE
+        else:
+            sp, loc = samples.ctypes.data, LOC_HOST
+        rc = self._step_fn(self._h, n, ids_p, self._s_p, up_p, sp, loc, self._u_p)
+        self.last_u = self._u[:n].copy()
+        if rc:
+            self._check(rc)
+        return self.last_u
+
+    def reset(self, ids=None):
+        idv = batch_ids(self.B, ids)
+        self._check(self._lib.ctk_batch_reset(self._h, 0 if idv is None else idv.size, _ptr(idv)))
+
+    def _problem(self, problem: int) -> int:
+        if not 0 <= int(problem) < self.B:
+            raise ValueError(f"problem index {problem} is outside 0 .. {self.B - 1}")
+        return int(problem)
+
+    def read(self, name: str, problem: int) -> np.ndarray:
+        N, H, S, Cn = self.N, self.H, self.S, self.C
+        shapes = {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn)}
+        if name not in shapes:
+            raise ValueError(f"a batch has the buffers {sorted(shapes)}, not {name!r}")
+        out = np.empty(shapes[name], np.float32)
+        self._check(self._lib.ctk_batch_read(self._h, self._problem(problem), BUFFERS[name], _ptr(out), out.size))
+        return out
+
+    def read_all(self, name: str) -> np.ndarray:
+        return np.stack([self.read(name, p) for p in range(self.B)])
+
+    def get_state(self, problem: int) -> np.ndarray:
+        buf = np.empty(self.H * self.C + self.C, np.float32)
+        self._check(self._lib.ctk_batch_get_state(self._h, self._problem(problem), _ptr(buf), buf.size))
+        return buf
+
+    def set_state(self, problem: int, state):
+        st = _f32(state).ravel()
+        self._check(self._lib.ctk_batch_set_state(self._h, self._problem(problem), _ptr(st), st.size))
+
+    def set_param(self, name: str, value: float):
+        self._check(self._lib.ctk_batch_set_param(self._h, self.param_names.index(name), float(value)))
+
+    def get_param(self, name: str) -> float:
+        v = C.c_float()
+        self._check(self._lib.ctk_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
+        return v.value
+
+    def rng_position(self, problem: int) -> int:
+        v = C.c_uint32()
+        self._check(self._lib.ctk_batch_rng_get_position(self._h, self._problem(problem), C.byref(v)))
+        return int(v.value)
+
+    def set_rng_position(self, problem: int, call: int):
+        self._check(self._lib.ctk_batch_rng_set_position(self._h, self._problem(problem), int(call) & 0xFFFFFFFF))
+
+    def dominant_kernel(self) -> str:
+        return self._lib.ctk_batch_dominant_kernel(self._h).decode()

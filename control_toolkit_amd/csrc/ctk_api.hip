@@ -185,11 +185,8 @@ std::vector<InterpEntry> build_interp_table(int H, int p, int P) {
     return tab;
 }
 
-void refresh_constants(ctk_handle* h) {
-    // CartPole's derived constants feed the hand-tuned kernels; the template kernels derive theirs per launch
-    // (ctk_generic.hip: Env<>::derive) from the same primary parameters
-    if (h->env == CTK_ENV_CARTPOLE) h->k = derive_constants(h->params, h->cfg.dt, h->cfg.intermediate_steps);
-    const ctk_config& c = h->cfg;
+// MPPI scalars of a configuration (a handle's, and a batch's: ctk_batch_create)
+MppiK mppi_constants(const ctk_config& c) {
     MppiK m;
     m.stdev = (float)((double)c.SQRTRHOINV * (1.0 / std::sqrt((double)c.dt)));   // optimizer_mppi.py:130
     const float one_m = 1.0f - 1.0f / c.NU;
@@ -198,7 +195,14 @@ void refresh_constants(ctk_handle* h) {
     m.k_uu = 0.5f * c.R;
     m.cc = c.cc_weight;
     m.neg_inv_lbd = (float)(-1.0 / (double)c.LBD);
-    h->mk = m;
+    return m;
+}
+
+void refresh_constants(ctk_handle* h) {
+    // CartPole's derived constants feed the hand-tuned kernels; the template kernels derive theirs per launch
+    // (ctk_generic.hip: Env<>::derive) from the same primary parameters
+    if (h->env == CTK_ENV_CARTPOLE) h->k = derive_constants(h->params, h->cfg.dt, h->cfg.intermediate_steps);
+    h->mk = mppi_constants(h->cfg);
 }
 
 // Per-lane MFMA operand layout of the MLP weights (ctk_mlp.h header comment), for a network with I = S + C <= 8 inputs and
@@ -1200,6 +1204,42 @@ int fill_const(ctk_handle* h, float* d, float v, int n) {
     return CTK_OK;
 }
 
+// what ctk_create and ctk_batch_create check alike, with the caller's name in the message: the struct, the environment and its
+// dimensions, the sizes, the limits (creation failures go to ctk_last_error(NULL))
+int check_config(const char* who, const ctk_config* cfg, const EnvInfo** einfo_out) {
+    const std::string w = std::string(who) + ": ";
+    if (cfg->struct_size != sizeof(ctk_config)) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, w + "ctk_config size mismatch (ABI)");
+    const EnvInfo* einfo = env_info(cfg->environment);
+    if (!einfo) return fail(nullptr, CTK_ERR_UNSUPPORTED, w + "unknown environment (built: CartPole, Quad2D, Hover; CTK_ENV_USER only in a library compiled with a user model, control_toolkit_amd/build_env.py)");
+    if (cfg->num_states != einfo->S || cfg->num_control_inputs != einfo->C)
+        return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, w + "environment " + einfo->name + " has num_states == " +
+                    std::to_string(einfo->S) + ", num_control_inputs == " + std::to_string(einfo->C));
+    if (cfg->num_rollouts < 1 || cfg->mpc_horizon < 1 || cfg->mpc_horizon > 1024)
+        return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, w + "need num_rollouts >= 1 and 1 <= mpc_horizon <= 1024");
+    if (cfg->period_interpolation_inducing_points < 1 || cfg->intermediate_steps < 1)
+        return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, w + "period_interpolation_inducing_points and intermediate_steps must be >= 1");
+    if (!(cfg->dt > 0.0f)) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, w + "dt must be > 0");
+    if ((long long)cfg->num_rollouts * (cfg->mpc_horizon + 1) * std::max(einfo->S, einfo->C) > (1ll << 30))
+        return fail(nullptr, CTK_ERR_UNSUPPORTED, w + "num_rollouts * (mpc_horizon + 1) * num_states must stay below 2^30 (32-bit element indices)");
+    for (int c = 0; c < einfo->C; ++c)
+        if (!(cfg->action_low[c] <= cfg->action_high[c])) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, w + "action_low must be <= action_high for every control input");
+    *einfo_out = einfo;
+    return CTK_OK;
+}
+
+// a usable gfx950 device behind ordinal `device`, or why not
+int probe_device(const char* who, int device, hipDeviceProp_t* prop) {
+    const std::string w = std::string(who) + ": ";
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, CTK_ERR_NO_DEVICE, w + "no HIP device visible (libctk_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, w + "bad device ordinal");
+    if (hipGetDeviceProperties(prop, device) != hipSuccess) return fail(nullptr, CTK_ERR_NO_DEVICE, w + "hipGetDeviceProperties failed");
+    if (std::strncmp(prop->gcnArchName, "gfx950", 6) != 0)
+        return fail(nullptr, CTK_ERR_NO_DEVICE, w + "kernels are built for gfx950 only, device is " + prop->gcnArchName);
+    return CTK_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1215,22 +1255,8 @@ const char* ctk_last_error(const ctk_handle* h) { return h ? h->err.c_str() : g_
 int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     if (out) *out = nullptr;
     if (!cfg || !out) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: NULL argument");
-    if (cfg->struct_size != sizeof(ctk_config))
-        return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: ctk_config size mismatch (ABI)");
-    const EnvInfo* einfo = env_info(cfg->environment);
-    if (!einfo) return fail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_create: unknown environment (built: CartPole, Quad2D, Hover; CTK_ENV_USER only in a library compiled with a user model, control_toolkit_amd/build_env.py)");
-    if (cfg->num_states != einfo->S || cfg->num_control_inputs != einfo->C)
-        return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, std::string("ctk_create: environment ") + einfo->name + " has num_states == " +
-                    std::to_string(einfo->S) + ", num_control_inputs == " + std::to_string(einfo->C));
-    if (cfg->num_rollouts < 1 || cfg->mpc_horizon < 1 || cfg->mpc_horizon > 1024)
-        return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: need num_rollouts >= 1 and 1 <= mpc_horizon <= 1024");
-    if (cfg->period_interpolation_inducing_points < 1 || cfg->intermediate_steps < 1)
-        return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: period_interpolation_inducing_points and intermediate_steps must be >= 1");
-    if (!(cfg->dt > 0.0f)) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: dt must be > 0");
-    if ((long long)cfg->num_rollouts * (cfg->mpc_horizon + 1) * std::max(einfo->S, einfo->C) > (1ll << 30))
-        return fail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_create: num_rollouts * (mpc_horizon + 1) * num_states must stay below 2^30 (32-bit element indices)");
-    for (int c = 0; c < einfo->C; ++c)
-        if (!(cfg->action_low[c] <= cfg->action_high[c])) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: action_low must be <= action_high for every control input");
+    const EnvInfo* einfo = nullptr;
+    if (int rc = check_config("ctk_create", cfg, &einfo)) return rc;
     if (cfg->optimizer < CTK_OPT_MPPI || cfg->optimizer > CTK_OPT_CEM_GMM)
         return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: unknown optimizer");
     if (cfg->predictor < CTK_PRED_ODE || cfg->predictor > CTK_PRED_GRU) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: unknown predictor");
@@ -1289,15 +1315,8 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     if (cfg->optimizer == CTK_OPT_MPPI && !(cfg->LBD > 0.0f && cfg->NU != 0.0f))
         return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: MPPI needs LBD > 0 and NU != 0");
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, CTK_ERR_NO_DEVICE, "ctk_create: no HIP device visible (libctk_hip has no CPU fallback)");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_create: bad device ordinal");
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess)
-        return fail(nullptr, CTK_ERR_NO_DEVICE, "ctk_create: hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(nullptr, CTK_ERR_NO_DEVICE, std::string("ctk_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
+    if (int rc = probe_device("ctk_create", cfg->device, &prop)) return rc;
 
     ctk_handle* h = new ctk_handle();
     h->cfg = *cfg;
@@ -2339,6 +2358,372 @@ int ctk_log_read(ctk_handle* h, int which, size_t first_step, size_t n_steps, fl
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (n_out) *n_out = n_steps * n;
+    return CTK_OK;
+}
+
+}  // extern "C"
+
+// =============================================================================================
+// Batched MPPI (include/ctk_hip.h: ctk_batch_*): B independent problems of one configuration, stepped by ONE launch of
+// ctk_mppi_batch<ENV, LOG> per step (ctk_mppi.hip).  One allocation per buffer kind with a problem stride — no handles inside.
+// Per-problem host state is what a handle keeps: the sequence number of its next step, its Philox position, which u_nom buffer is current.
+// =============================================================================================
+struct ctk_batch {
+    ctk_config cfg{};
+    int B = 0, N = 0, H = 0, P = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, PC = 0, blocks = 0;
+    float params[CTK_MAX_PARAMS]{};
+    MppiK mk{};
+    hipStream_t stream = nullptr;
+    int max_per_launch = 1;                 // problems per launch: half the device's CUs (ctk_batch_create), a diagnostic switch may lower it
+    InterpEntry* d_interp = nullptr;
+    float* d_J = nullptr;                   // [B][N]
+    float* d_Q = nullptr;                   // [B][N,H,C]
+    float* d_traj = nullptr;                // [B][N,H+1,S] (materialize_trajectories)
+    float* d_parts = nullptr;               // [B][blocks][2+PC]
+    unsigned long long* d_ll = nullptr;     // [B][blocks][2+PC] {value, seq} words
+    float* d_unom = nullptr;                // [B][2][H,C]
+    float* d_u = nullptr;                   // [B][CTK_MAX_INPUTS]
+    float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
+    float* h_u_dev = nullptr;
+    CtkBatchDesc* d_desc = nullptr;         // [B]
+    CtkBatchStep* h_steps = nullptr;        // pinned [B]: the step records of the step being issued
+    CtkBatchStep* d_steps = nullptr;        // [B]
+    float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
+    std::vector<uint32_t> seq, call;
+    std::vector<int> cur;
+    std::string err, dominant;
+    size_t unom_stride() const { return (size_t)2 * HC; }
+    float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
+    float* slot(int p) const { return h_u + (size_t)p * 16; }
+};
+
+namespace {
+
+int bfail(ctk_batch* b, int code, const std::string& msg) {
+    if (b) b->err = msg; else g_create_error = msg;
+    return code;
+}
+#define BHIP_TRY(b, expr)                                                                       \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess)                                                                   \
+            return bfail((b), CTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
+    } while (0)
+
+// the problems a call addresses: ids[0..n) strictly ascending, or all of them (ids == NULL)
+int batch_ids(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, int* n_out) {
+    if (!ids) { *n_out = b->B; return CTK_OK; }
+    if (n_ids < 1 || n_ids > b->B) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": n_ids must be 1 .. " + std::to_string(b->B) + " (the batch size)");
+    for (int j = 0; j < n_ids; ++j) {
+        if (ids[j] < 0 || ids[j] >= b->B)
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(ids[j]) + " is outside 0 .. " + std::to_string(b->B - 1));
+        if (j > 0 && ids[j] <= ids[j - 1]) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": ids must be strictly ascending");
+    }
+    *n_out = n_ids;
+    return CTK_OK;
+}
+int batch_problem(ctk_batch* b, const char* who, int p) {
+    if (p < 0 || p >= b->B) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(p) + " is outside 0 .. " + std::to_string(b->B - 1));
+    return CTK_OK;
+}
+
+// the shared template of a launch's RolloutArgs (make_args without what the step records and descriptors supply)
+RolloutArgs batch_args(const ctk_batch* b) {
+    RolloutArgs a{};
+    for (int c = 0; c < b->C; ++c) { a.lo[c] = b->cfg.action_low[c]; a.hi[c] = b->cfg.action_high[c]; }
+    a.C = b->C;
+    a.N = b->N; a.H = b->H; a.P = b->P;
+    a.p_magic = ctk_magic_of(b->P);
+    a.identity_interp = (b->cfg.period_interpolation_inducing_points == 1 && b->P == b->H) ? 1 : 0;
+    a.inv_Hp1 = 1.0f / (float)(b->H + 1);
+    a.interp = b->d_interp;
+    a.stream_id = 0;
+    a.global_row0 = b->cfg.global_rollout_offset;
+    return a;
+}
+
+// optimizer_reset() of problem p (ctk_reset of an MPPI handle): the plan at mid-range in buffer 0; u, the Philox position stay
+int batch_reset_one(ctk_batch* b, int p) {
+    std::vector<float> tmp((size_t)b->HC);
+    for (int i = 0; i < b->HC; ++i) tmp[(size_t)i] = 0.5f * (b->cfg.action_low[i % b->C] + b->cfg.action_high[i % b->C]);
+    b->cur[(size_t)p] = 0;
+    BHIP_TRY(b, hipMemcpyAsync(b->unom(p, 0), tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* ctk_batch_last_error(const ctk_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+int ctk_batch_size(const ctk_batch* b) { return b ? b->B : 0; }
+size_t ctk_batch_samples_needed(const ctk_batch* b) { return b ? (size_t)b->N * b->PC : 0; }
+const char* ctk_batch_dominant_kernel(const ctk_batch* b) { return b ? b->dominant.c_str() : ""; }
+
+void ctk_batch_destroy(ctk_batch* b) {
+    if (!b) return;
+    hipSetDevice(b->cfg.device);
+    if (b->stream) hipStreamSynchronize(b->stream);
+    void* bufs[] = {b->d_interp, b->d_J, b->d_Q, b->d_traj, b->d_parts, b->d_ll, b->d_unom, b->d_u, b->d_desc, b->d_steps, b->d_samples};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (b->h_u) hipHostFree(b->h_u);
+    if (b->h_steps) hipHostFree(b->h_steps);
+    if (b->stream) hipStreamDestroy(b->stream);
+    delete b;
+}
+
+int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: NULL argument");
+    if (n_problems < 1) return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    const EnvInfo* einfo = nullptr;
+    if (int rc = check_config("ctk_batch_create", cfg, &einfo)) return rc;
+    if (cfg->optimizer != CTK_OPT_MPPI)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch steps MPPI controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+                     "); the other optimizers run as single handles (ctk_create)");
+    if (cfg->predictor != CTK_PRED_ODE)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
+                     std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
+    if (!(cfg->LBD > 0.0f && cfg->NU != 0.0f)) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: MPPI needs LBD > 0 and NU != 0");
+    const int N = cfg->num_rollouts, H = cfg->mpc_horizon, P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
+    size_t lds = 0;
+    int blocks = 0;
+    if (const int why = ctk_mppi_batch_fit(cfg->environment, N, H, P, &lds, &blocks)) {
+        const std::string sizes = "num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ", " + std::to_string(P) + " inducing points x " +
+                                  std::to_string(einfo->C) + " inputs = " + std::to_string(blocks) + " block records of " + std::to_string(2 + P * einfo->C) + " words";
+        const char* reason = why == 1 ? ": populations from 32768 rollouts on run the throughput kernels, which a batch does not have"
+                           : why == 2 ? ": the batch kernel has the narrow in-launch hand-off only (at most 128 records and 2048 record words per problem)"
+                           : why == 3 ? ": the block records do not fit the hand-off's LDS staging"
+                                      : ": the rollout tiles need more than 160 KiB of LDS";
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_batch_create: per-problem population outside the batch kernel's sizes (" + sizes + ")" + reason +
+                     (why == 4 ? " (" + std::to_string(lds) + " bytes)" : std::string()) + "; such a controller runs as a single handle (ctk_create)");
+    }
+
+    hipDeviceProp_t prop;
+    if (int rc = probe_device("ctk_batch_create", cfg->device, &prop)) return rc;
+
+    ctk_batch* b = new ctk_batch();
+    b->cfg = *cfg;
+    b->B = n_problems; b->N = N; b->H = H; b->P = P; b->blocks = blocks;
+    b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = H * b->C; b->PC = P * b->C;
+    default_params(b->env, b->params);
+    b->mk = mppi_constants(b->cfg);
+    // Progress: the only workgroup of a launch that ever waits is block 0 of a problem, for workgroups of its own problem.  With at most
+    // CUs / 2 problems in a launch the waiting workgroups cannot fill the machine (every CU holds at least one workgroup of this kernel),
+    // so every other workgroup finds a place whatever the dispatch order.  CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH (diagnostic) only lowers it.
+    b->max_per_launch = std::max(1, prop.multiProcessorCount / 2);
+    if (const char* e = std::getenv("CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH")) {
+        const int v = std::atoi(e);
+        if (v >= 1 && v < b->max_per_launch) b->max_per_launch = v;
+    }
+    b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u); b->cur.assign((size_t)n_problems, 0);
+    b->dominant = ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
+
+    auto bail = [&](int rc) { g_create_error = b->err; ctk_batch_destroy(b); return rc; };
+#define BHIP_CREATE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { b->err = std::string(#expr) + ": " + hipGetErrorString(_e); return bail(CTK_ERR_HIP); } } while (0)
+    BHIP_CREATE(hipSetDevice(cfg->device));
+    BHIP_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    const size_t Bz = (size_t)n_problems, rec = (size_t)blocks * (2 + b->PC);
+    auto dev_zero = [&](void** p, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+        return e != hipSuccess ? e : hipMemsetAsync(*p, 0, bytes ? bytes : 1, b->stream);
+    };
+    BHIP_CREATE(dev_zero((void**)&b->d_interp, (size_t)H * sizeof(InterpEntry)));
+    BHIP_CREATE(dev_zero((void**)&b->d_J, Bz * N * sizeof(float)));
+    BHIP_CREATE(dev_zero((void**)&b->d_Q, Bz * N * b->HC * sizeof(float)));
+    if (cfg->materialize_trajectories) BHIP_CREATE(dev_zero((void**)&b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float)));
+    BHIP_CREATE(dev_zero((void**)&b->d_parts, Bz * rec * sizeof(float)));
+    BHIP_CREATE(dev_zero((void**)&b->d_ll, Bz * rec * sizeof(unsigned long long)));
+    BHIP_CREATE(dev_zero((void**)&b->d_unom, Bz * b->unom_stride() * sizeof(float)));
+    BHIP_CREATE(dev_zero((void**)&b->d_u, Bz * CTK_MAX_INPUTS * sizeof(float)));
+    BHIP_CREATE(dev_zero((void**)&b->d_desc, Bz * sizeof(CtkBatchDesc)));
+    BHIP_CREATE(dev_zero((void**)&b->d_steps, Bz * sizeof(CtkBatchStep)));
+    BHIP_CREATE(hipHostMalloc((void**)&b->h_u, Bz * 64, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(b->h_u, 0, Bz * 64);
+    BHIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
+    BHIP_CREATE(hipHostMalloc((void**)&b->h_steps, Bz * sizeof(CtkBatchStep), hipHostMallocDefault));
+    std::memset(b->h_steps, 0, Bz * sizeof(CtkBatchStep));
+
+    const std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, P);
+    std::vector<CtkBatchDesc> desc(Bz);
+    std::vector<float> plan(Bz * b->unom_stride(), 0.0f);          // optimizer_reset(): buffer 0 of every problem at mid-range
+    for (int p = 0; p < n_problems; ++p) {
+        const size_t z = (size_t)p;
+        const uint64_t seed = seeds ? seeds[p] : cfg->seed + (uint64_t)p;
+        CtkBatchDesc& d = desc[z];
+        d.parts = b->d_parts + z * rec; d.ll = b->d_ll + z * rec;
+        d.J = b->d_J + z * N; d.Q_out = b->d_Q + z * N * b->HC;
+        d.traj_out = b->d_traj ? b->d_traj + z * N * (H + 1) * b->S : nullptr;
+        d.unom[0] = b->unom(p, 0); d.unom[1] = b->unom(p, 1);
+        d.u_dev = b->d_u + z * CTK_MAX_INPUTS; d.u_host = b->h_u_dev + z * 16;
+        d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
+        for (int i = 0; i < b->HC; ++i) plan[z * b->unom_stride() + i] = 0.5f * (cfg->action_low[i % b->C] + cfg->action_high[i % b->C]);
+    }
+    BHIP_CREATE(hipMemcpyAsync(b->d_interp, tab.data(), (size_t)H * sizeof(InterpEntry), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkBatchDesc), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipMemcpyAsync(b->d_unom, plan.data(), plan.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipStreamSynchronize(b->stream));                  // the host vectors go out of scope below
+#undef BHIP_CREATE
+    *out = b;
+    return CTK_OK;
+}
+
+int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
+                   float* u_out) {
+    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_step", n_ids, ids, &n)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const size_t per = (size_t)b->N * b->PC;
+    const float* d_s = nullptr;                        // draws of the step's first problem; row j follows at j * per
+    if (samples_loc != CTK_LOC_NONE) {
+        if (samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+        if (samples_loc == CTK_LOC_DEVICE) d_s = samples;
+        else if (samples_loc == CTK_LOC_HOST) {
+            if ((size_t)n * per > b->samples_cap) {
+                if (b->d_samples) BHIP_TRY(b, hipFree(b->d_samples));
+                b->d_samples = nullptr; b->samples_cap = 0;
+                BHIP_TRY(b, hipMalloc((void**)&b->d_samples, (size_t)n * per * sizeof(float)));
+                b->samples_cap = (size_t)n * per;
+            }
+            BHIP_TRY(b, hipMemcpyAsync(b->d_samples, samples, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice, b->stream));
+            d_s = b->d_samples;
+        } else return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+    }
+    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es)
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        CtkBatchStep& q = b->h_steps[j];
+        q.id = p; q.seq = b->seq[(size_t)p]; q.call = b->call[(size_t)p]; q.cur = (uint32_t)b->cur[(size_t)p];
+        q.dev_uprev = u_prev ? 0u : 1u; q.pad = 0u;
+        q.samples = d_s ? d_s + (size_t)j * per : nullptr;
+        for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
+        for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
+    }
+    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkBatchStep), hipMemcpyHostToDevice, b->stream);
+    const RolloutArgs a = batch_args(b);
+    const bool log = b->cfg.materialize_trajectories != 0;
+    int launched = 0;                                  // consecutive launches of at most max_per_launch problems: the results do not depend on the split
+    while (le == hipSuccess && launched < n) {
+        const int cnt = std::min(b->max_per_launch, n - launched);
+        le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, b->d_steps + launched, cnt, log);
+        if (le == hipSuccess) launched += cnt;
+    }
+    for (int j = 0; j < launched; ++j) b->cur[(size_t)b->h_steps[j].id] ^= 1;
+    // completion: every launched problem's {u, seq} store landing in its pinned slot (finish_step's bounded spin, one budget for all)
+    bool synced = false;
+    int spins = 0;
+    std::string late, timed_out;
+    for (int j = 0; j < launched; ++j) {
+        const int p = b->h_steps[j].id;
+        const uint32_t want = b->seq[(size_t)p];
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 1;
+        while (*slot != want) {
+            if (!synced && ++spins < 4000000) { __builtin_ia32_pause(); continue; }
+            if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
+            break;
+        }
+        if (*slot != want) late += (late.empty() ? "" : ", ") + std::to_string(p);
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int j = 0; j < n; ++j) {
+        const int p = b->h_steps[j].id;
+        ++b->seq[(size_t)p];                           // every launch attempt consumes its sequence number (guarded())
+        if (j >= launched) continue;
+        ++b->call[(size_t)p];
+        volatile float* sl = reinterpret_cast<volatile float*>(b->slot(p));
+        if (u_out) {
+            u_out[(size_t)j * b->C] = sl[0];
+            for (int c = 1; c < b->C; ++c) u_out[(size_t)j * b->C + c] = sl[4 + c];   // publish_u_vec
+        }
+        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;
+        if (errw[0]) { errw[0] = 0; timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(p); }
+    }
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_step: ") + hipGetErrorString(le));
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_step: the step finished without publishing the result of problem(s) " + late);
+    if (!timed_out.empty())
+        return bfail(b, CTK_ERR_STATE, "ctk_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; their outputs are NaN, the other problems' outputs are valid and written");
+    return CTK_OK;
+}
+
+int ctk_batch_reset(ctk_batch* b, int n_ids, const int32_t* ids) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_reset", n_ids, ids, &n)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    for (int j = 0; j < n; ++j)
+        if (int rc = batch_reset_one(b, ids ? ids[j] : j)) return rc;
+    return CTK_OK;
+}
+
+int ctk_batch_read(ctk_batch* b, int problem, int buffer, float* dst, size_t cap) {
+    if (!b || !dst) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_read: NULL destination") : CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, "ctk_batch_read", problem)) return rc;
+    const size_t z = (size_t)problem, N = (size_t)b->N;
+    const float* src = nullptr; size_t n = 0;
+    switch (buffer) {
+        case CTK_BUF_Q: src = b->d_Q + z * N * b->HC; n = N * b->HC; break;
+        case CTK_BUF_J: src = b->d_J + z * N; n = N; break;
+        case CTK_BUF_TRAJ:
+            if (!b->d_traj) return bfail(b, CTK_ERR_STATE, "ctk_batch_read: trajectories not materialised (cfg.materialize_trajectories == 0)");
+            n = N * ((size_t)b->H + 1) * b->S; src = b->d_traj + z * n; break;
+        case CTK_BUF_U_NOM: src = b->unom(problem, b->cur[z]); n = (size_t)b->HC; break;
+        default: return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_read: a batch has Q, J, TRAJ and U_NOM");
+    }
+    if (cap < n) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_read: destination too small (" + std::to_string(n) + " floats)");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+int ctk_batch_get_state(ctk_batch* b, int problem, float* dst, size_t cap) {
+    if (!b || !dst) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, "ctk_batch_get_state", problem)) return rc;
+    if (cap < (size_t)b->HC + b->C) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_get_state: destination too small");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipMemcpyAsync(dst, b->unom(problem, b->cur[(size_t)problem]), (size_t)b->HC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(dst + b->HC, b->d_u + (size_t)problem * CTK_MAX_INPUTS, (size_t)b->C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+int ctk_batch_set_state(ctk_batch* b, int problem, const float* src, size_t n) {
+    if (!b || !src) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, "ctk_batch_set_state", problem)) return rc;
+    if (n != (size_t)b->HC + b->C) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_set_state: wrong state size");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipMemcpyAsync(b->unom(problem, b->cur[(size_t)problem]), src, (size_t)b->HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(b->d_u + (size_t)problem * CTK_MAX_INPUTS, src + b->HC, (size_t)b->C * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+int ctk_batch_set_param(ctk_batch* b, int id, float value) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (id < 0 || id >= env_info(b->env)->n_params) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_set_param: unknown parameter id for this environment");
+    b->params[id] = value;                             // every problem: the kernel constants are derived from the table at each launch
+    return CTK_OK;
+}
+
+int ctk_batch_get_param(const ctk_batch* b, int id, float* value) {
+    if (!b || !value || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->params[id];
+    return CTK_OK;
+}
+
+int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call) {
+    if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *call = b->call[(size_t)problem];
+    return CTK_OK;
+}
+
+int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, "ctk_batch_rng_set_position", problem)) return rc;
+    b->call[(size_t)problem] = call;
     return CTK_OK;
 }
 

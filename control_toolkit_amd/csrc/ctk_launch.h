@@ -145,6 +145,41 @@ hipError_t ctk_launch_mppi_resident(hipStream_t st, int env, const float* params
 constexpr size_t CTK_RES_ARGS_BYTES = 1024;   // device + host staging block for the resident kernel's argument struct
 const char* ctk_mppi_resident_name(int env, int N, int P);   // N rollouts, P inducing points (per control input)
 const char* ctk_mppi_rollout_env_name(int env, bool log);
+// the BATCH form of the same kernel (ctk_mppi.hip: ctk_mppi_batch<ENV, LOG>; include/ctk_hip.h: ctk_batch_*): B independent problems of ONE
+// configuration, grid (workgroups per problem, problems of this launch).  What differs per problem reaches the kernel through two arrays in
+// device memory: the descriptor [B] (where the problem's buffers are; written once, at creation) and the step records [problems of this
+// step] (which problem, its state / previous input / sample pointer / Philox position / sequence number / current plan buffer; written by
+// the host into pinned memory and copied with ONE transfer ahead of the launch).  blockIdx.y picks the step record, its id the descriptor.
+struct CtkBatchDesc {
+    float* parts;                       // [blocks][2 + P*C] block records (the ticket path's; unused by the {value, seq} tail)
+    unsigned long long* ll;             // [blocks][2 + P*C] {value, seq} record words
+    float* J;                           // [N]
+    float* Q_out;                       // [N,H,C]
+    float* traj_out;                    // [N,H+1,S] or nullptr
+    float* unom[2];                     // [H,C] nominal plan, ping-pong
+    float* u_dev;                       // [C] the problem's own last output
+    float* u_host;                      // pinned {u, seq} slot (16 floats) with the error words behind it
+    uint32_t seed_lo, seed_hi;          // Philox key
+};
+struct CtkBatchStep {
+    int32_t id;                         // problem index = descriptor index
+    uint32_t seq;                       // tag of this step's record words and of {u, seq}
+    uint32_t call;                      // Philox position
+    uint32_t cur;                       // which unom buffer holds the current plan (the step writes the other one)
+    uint32_t dev_uprev;                 // 1: the previous input is the problem's own last output (u_prev == NULL at the API)
+    uint32_t pad;
+    const float* samples;               // this problem's draws [N,P,C] (device pointer) or nullptr: the in-kernel sampler
+    float s[CTK_MAX_STATES];
+    float u_prev[CTK_MAX_INPUTS];
+};
+// 0: a problem of these sizes runs in the batch kernel; else why not (1 throughput sizes, 2 more records / words than the FORM 0 tail takes,
+// 3 the records do not fit the tail's LDS staging, 4 LDS over 160 KiB); *lds_out: dynamic LDS of a launch, *blocks_out: workgroups per problem
+int ctk_mppi_batch_fit(int env, int N, int H, int P, size_t* lds_out, int* blocks_out);
+const char* ctk_mppi_batch_name(int env, bool log);
+// n_problems step records from `steps_dev` on, as ONE launch; a: the shared template (limits, sizes, interpolation table; s0 / u_prev / the
+// output pointers / seed / call come from the records and descriptors)
+hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
+                                 const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log);
 hipError_t ctk_launch_mppi_merge_partial(hipStream_t st, const float* parts, int n_parts, int per_block, int P,
                                          float neg_inv_lbd, float* out_rec);
 // direct peer-to-peer record exchange + merge + update (ctk_mppi.hip: ctk_mppi_p2p_exchange)

@@ -412,6 +412,47 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_resident(const ResidentAr
 }
 
 // ---------------------------------------------------------------------------------------------
+// The BATCH form (include/ctk_hip.h: ctk_batch_*): B independent problems of one configuration in ONE launch — the same step, the same
+// statements (ctk_mppi_body.inc, unchanged, FORM 0), around per-problem inputs.  Grid (workgroups per problem, problems of this launch):
+// blockIdx.y picks the step record, the record's id the problem's descriptor (ctk_launch.h: CtkBatchStep / CtkBatchDesc, both in device
+// memory; blockIdx.y is uniform, so both are read with scalar loads, as a launched kernel reads its kernarg segment).  The prologue
+// rebuilds from them what ctk_mppi_rollout takes as arguments (a_in, fz, samples, u_nom, parts); everything the problems share stays by
+// value.  The body addresses its problem through blockIdx.x / gridDim.x and those names only, so workgroup x of problem y computes what
+// workgroup x of a single handle's launch computes, and block 0 of a problem polls the {value, seq} words of ITS problem only.
+// Argument order as ctk_mppi_rollout's (five pointers, then N / H / P / magic: the preloaded dwords), so that the body's kernarg prefetch
+// touches the same span; wperm is the body's (unused: analytic predictor), spare pads the fifth pointer.
+// ---------------------------------------------------------------------------------------------
+template <int ENV, bool LOG>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                             const InterpEntry* __restrict__ interp, const float* __restrict__ wperm,
+                                                             const void* spare, int N_, int H_, int P_, uint32_t pmagic_, RolloutArgs a_tpl,
+                                                             typename Env<ENV>::K k, MppiK m, FuseArgs fz_tpl) {
+    constexpr int PRED = CTK_PRED_ODE, FORM = 0;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+    const CtkBatchStep& q = steps[blockIdx.y];
+    const CtkBatchDesc& d = desc[q.id];
+    RolloutArgs a_in = a_tpl;
+#pragma unroll
+    for (int i = 0; i < Env<ENV>::S; ++i) a_in.s0[i] = q.s[i];
+#pragma unroll
+    for (int c = 0; c < Env<ENV>::C; ++c) a_in.u_prev[c] = q.u_prev[c];
+    a_in.u_prev_dev = q.dev_uprev ? d.u_dev : nullptr;
+    a_in.J = d.J; a_in.Q_out = d.Q_out; a_in.traj_out = d.traj_out;
+    a_in.seed_lo = d.seed_lo; a_in.seed_hi = d.seed_hi; a_in.call = q.call;
+    const float* samples = q.samples;
+    const float* u_nom = q.cur ? d.unom[1] : d.unom[0];
+    float* parts = d.parts;
+    FuseArgs fz = fz_tpl;                      // mode 1, stage_ok, the shared update constants (launcher)
+    fz.ll = d.ll;
+    fz.up.seq = q.seq;
+    fz.up.u_nom_in = u_nom; fz.up.u_nom_out = q.cur ? d.unom[0] : d.unom[1];
+    fz.up.u_dev = d.u_dev; fz.up.u_host = d.u_host;
+    (void)spare;
+#include "ctk_mppi_body.inc"
+}
+
+// ---------------------------------------------------------------------------------------------
 // Throughput variant (ODE, N >= CTK_MPPI_THROUGHPUT_MIN_N): one wave per block, 64 trajectories, the
 // inputs formed inline in the recurrence instead of through an LDS input buffer.  LDS per block is the
 // sample tile only (13.5 KiB at P = 50 instead of 27 KiB), so ~11 recurrence waves are resident per CU
@@ -884,6 +925,44 @@ size_t ctk_mppi_rollout_env_lds(int env, int P, int H, int N) {
 }
 const char* ctk_mppi_rollout_env_name(int env, bool log) {
     return ctk_kernel_name("ctk_mppi_rollout<%d, 0, %4$s, false>", env, 0, 0, log ? "true" : "false");
+}
+
+// ---- the batch form (ctk_mppi_batch): FORM 0 of the 4-wave kernel with the {value, seq} tail, nothing else
+int ctk_mppi_batch_fit(int env, int N, int H, int P, size_t* lds_out, int* blocks_out) {
+    int C = 1;
+    CTK_FOR_ENV(env, EV, { C = Env<EV>::C; });
+    const int blocks = (N + MPPI_TRAJ - 1) / MPPI_TRAJ, PC = P * C;
+    if (blocks_out) *blocks_out = blocks;
+    if (ctk_mppi_uses_throughput_kernel(CTK_PRED_ODE, N)) return 1;
+    if (!ctk_ll_records_ok(blocks, PC) || ctk_ll_tail_wide(blocks, PC)) return 2;
+    int stage_ok;
+    const size_t lds = rollout_launch_lds(P, H, CTK_PRED_ODE, N, blocks, &stage_ok, C);
+    if (lds_out) *lds_out = lds;
+    if (!stage_ok) return 3;
+    if (lds > 160 * 1024) return 4;
+    return 0;
+}
+const char* ctk_mppi_batch_name(int env, bool log) { return ctk_kernel_name("ctk_mppi_batch<%d, %4$s>", env, 0, 0, log ? "true" : "false"); }
+
+hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
+                                 const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log) {
+    size_t lds;
+    int blocks;
+    if (n_problems < 1 || ctk_mppi_batch_fit(env, a.N, a.H, a.P, &lds, &blocks) != 0) return hipErrorInvalidValue;
+    const dim3 grid(blocks, n_problems), block(MPPI_BLOCK);
+    CTK_FOR_ENV(env, EV, {
+        using E = Env<EV>;
+        FuseArgs fz{};                                 // merge + update by block 0 of every problem over the staged {value, seq} words;
+        fz.mode = 1; fz.stage_ok = 1;                  // the pointers and the sequence number are the descriptors' / the step records'
+        fz.up = mppi_update_args(a, E::C, nullptr, nullptr, nullptr, nullptr, 0u);
+        const typename E::K k = E::derive(params, dt, isteps);
+        const uint32_t pmagic = ctk_magic_of(a.P * E::C);
+        ctk_with_bool(log, [&](auto log_c) {
+            hipLaunchKernelGGL((ctk_mppi_batch<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp,
+                               static_cast<const float*>(nullptr), static_cast<const void*>(nullptr), a.N, a.H, a.P, pmagic, a, k, m, fz);
+        });
+    });
+    return hipGetLastError();
 }
 
 hipError_t ctk_launch_mppi_merge_partial(hipStream_t st, const float* parts, int n_parts, int per_block, int P,

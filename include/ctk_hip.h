@@ -463,6 +463,46 @@ int ctk_resident_enable(ctk_handle* h, int on /* 0 off | 1 on | 2 on + read-ahea
 int ctk_resident_stop(ctk_handle* h);
 int ctk_resident_stats(const ctk_handle* h, uint64_t* launches, uint64_t* steps, int* running, int* mailbox_in_device_memory);
 
+/* -------------------------------------------------------------------------------------------
+ * batched MPPI: B independent controllers of ONE configuration stepped by one kernel launch per step (no counterpart in the reference,
+ * whose optimizer object is one controller: Optimizers/__init__.py:67; added without an ABI bump, as CTK_OPT_CEM_GMM was).  A handle's
+ * step at the headline size occupies 16 of the chip's 256 CUs and pays as much again for its launch and completion; data generation over
+ * many experiments, a fleet of plants or a server with several clients step B handles one after another.  A batch steps them together.
+ *  - shared by all problems: everything in ctk_config (environment, N, H, period, limits, MPPI constants) and the parameter table;
+ *    per problem: state, previous input, nominal plan, last output, Philox seed and position, draws and the readable buffers;
+ *  - CONTRACT: problem p behaves bit for bit like a ctk_handle created from the same ctk_config with seed = seeds[p] that received the
+ *    same calls (u, U_NOM, J, Q, TRAJ, the Philox position, the ctk_get_state vector), for every sample source, u_prev given or NULL,
+ *    and any interleaving of whole-batch steps, subset steps and per-problem resets;
+ *  - MPPI with the analytic (ODE) predictor, per-problem sizes of the one-launch regime with the narrow in-launch hand-off (at most 128
+ *    block records and 2048 record words per problem, below the throughput sizes); everything else is CTK_ERR_UNSUPPORTED with the sizes
+ *    in ctk_batch_last_error(NULL), as is n_problems < 1;
+ *  - at most half the device's CU count problems go into one launch; larger batches or id lists are split into consecutive launches on
+ *    the batch's stream (the results do not depend on the split).  CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH (environment, diagnostic) lowers
+ *    that cap, never raises it;
+ *  - ids: n_ids problem indices, strictly ascending; NULL = all problems (n_ids ignored).  Rows of s [n,S], u_prev [n,C] (NULL: every
+ *    problem's own last output), samples [n,N,P,C] and u_out [n,C] follow the order of ids.  Bad ids: CTK_ERR_INVALID_ARGUMENT;
+ *  - ctk_batch_step is synchronous.  CTK_ERR_STATE = a bounded device-side wait ran out for the problems the message names (their
+ *    outputs are NaN); the other problems' outputs are valid and written.  A batch is NOT thread-safe.
+ * Each entry corresponds to the single-handle call named beside it.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct ctk_batch ctk_batch;
+int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds /* NULL: cfg->seed + p */, ctk_batch** out); /* ctk_create */
+void ctk_batch_destroy(ctk_batch* b);                                                   /* ctk_destroy */
+const char* ctk_batch_last_error(const ctk_batch* b);                                   /* ctk_last_error; b may be NULL */
+int ctk_batch_size(const ctk_batch* b);                                                 /* B */
+size_t ctk_batch_samples_needed(const ctk_batch* b);                                    /* ctk_samples_needed, per problem: N*P*C */
+int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev,
+                   const float* samples, int samples_loc, float* u_out);                /* ctk_step of every listed problem */
+int ctk_batch_reset(ctk_batch* b, int n_ids, const int32_t* ids);                       /* ctk_reset of every listed problem */
+int ctk_batch_read(ctk_batch* b, int problem, int buffer, float* dst, size_t cap);      /* ctk_read: CTK_BUF_Q, J, TRAJ, U_NOM */
+int ctk_batch_get_state(ctk_batch* b, int problem, float* dst, size_t cap);             /* ctk_get_state: u_nom [H,C], u [C] */
+int ctk_batch_set_state(ctk_batch* b, int problem, const float* src, size_t n);         /* ctk_set_state */
+int ctk_batch_set_param(ctk_batch* b, int id, float value);                             /* ctk_set_param, all problems */
+int ctk_batch_get_param(const ctk_batch* b, int id, float* value);                      /* ctk_get_param */
+int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call);        /* ctk_rng_get_position */
+int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call);               /* ctk_rng_set_position */
+const char* ctk_batch_dominant_kernel(const ctk_batch* b);                              /* ctk_dominant_kernel */
+
 #ifdef __cplusplus
 }
 #endif
