@@ -141,6 +141,10 @@ SYMBOLS = {
     "ctk_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
     "ctk_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
     "ctk_batch_dominant_kernel": (C.c_char_p, [_H]),
+    # per-problem parameters of a batch (the ctk_batch* again)
+    "ctk_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ctk_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
+    "ctk_problem_params_differ": (C.c_int, [_H]),
 }
 
 
@@ -662,9 +666,36 @@ def batch_step_args(num_problems: int, S: int, Cn: int, per_problem: int, states
     return idv, n, samples
 
 
+_F32_MAX = float(np.finfo(np.float32).max)
+
+
+def batch_param_args(param_names, num_problems: int, name, values, ids=None):
+    """Checks the arguments of CtkMppiBatch.set_problem_params without touching a device: the parameter name against the environment's
+    names, ids (batch_ids), values a finite scalar (every listed problem) or one finite value per listed problem ([n]).  Returns
+    (parameter id, ids, n, values as fp32 [n])."""
+    if name not in param_names:
+        raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(param_names)})")
+    idv = batch_ids(num_problems, ids)
+    n = num_problems if idv is None else int(idv.size)
+    try:
+        vals = np.asarray(values, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"values of {name!r} must be a number or an array of numbers, got {values!r}") from None
+    if vals.ndim == 0:
+        vals = np.full(n, float(vals))
+    if vals.shape != (n,):
+        raise ValueError(f"{name!r}: one value per listed problem ({n}) or a scalar, got shape {tuple(vals.shape)}")
+    if not (np.abs(vals) <= _F32_MAX).all():                       # NaN compares false: refused with the infinities and what overflows fp32
+        j = int(np.flatnonzero(~(np.abs(vals) <= _F32_MAX))[0])
+        raise ValueError(f"{name!r} must be finite in fp32: {vals[j]!r} for problem {j if idv is None else int(idv[j])}")
+    out = vals.astype(np.float32)
+    return param_names.index(name), idv, n, out
+
+
 class CtkMppiBatch:
     """Owns one ctk_batch: num_problems independent MPPI controllers of ONE configuration (the MPPI keywords of CtkEngine), stepped by
-    one kernel launch per step.  Problem p behaves bit for bit like CtkEngine("mppi", "ODE", seed=seeds[p], ...) given the same calls.
+    one kernel launch per step.  Problem p behaves bit for bit like CtkEngine("mppi", "ODE", seed=seeds[p], ...) given the same calls,
+    set_param among them: set_problem_params gives every problem its own plant, cost weights and targets, set_param the same value to all.
     seeds: one per problem (default seed + p)."""
 
     def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "mppi", predictor: str = "ODE",
@@ -794,9 +825,33 @@ class CtkMppiBatch:
         self._check(self._lib.ctk_batch_set_param(self._h, self.param_names.index(name), float(value)))
 
     def get_param(self, name: str) -> float:
+        """the last value set_param gave the whole batch (the default before that); a problem's own value: get_problem_param"""
         v = C.c_float()
         self._check(self._lib.ctk_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
         return v.value
+
+    def set_problem_params(self, name: str, values, ids=None):
+        """parameter `name` of the problems in ids (None: all): values a scalar or [n], one per listed problem in the order of ids.  The
+        next step re-derives the constants of the problems touched; from the first call on the batch runs the per-problem form of its
+        kernel (params_differ, dominant_kernel)."""
+        pid, idv, n, vals = batch_param_args(self.param_names, self.B, name, values, ids)
+        self._check(self._lib.ctk_problem_set_param(self._h, n, _ptr(idv), pid, _ptr(vals)))
+
+    def get_problem_param(self, name: str, problem: int) -> float:
+        if name not in self.param_names:
+            raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(self.param_names)})")
+        v = C.c_float()
+        if self._lib.ctk_problem_get_param(self._h, self._problem(problem), self.param_names.index(name), C.byref(v)) != 0:
+            raise CtkError(f"ctk_problem_get_param({problem}, {name!r}) failed")
+        return v.value
+
+    def get_problem_params(self, name: str) -> np.ndarray:
+        """[B] parameter `name` of every problem"""
+        return np.array([self.get_problem_param(name, p) for p in range(self.B)], np.float32)
+
+    def params_differ(self) -> int:
+        """1 once a set_problem_params has succeeded on this batch (sticky), else 0"""
+        return int(self._lib.ctk_problem_params_differ(self._h))
 
     def rng_position(self, problem: int) -> int:
         v = C.c_uint32()

@@ -2366,12 +2366,20 @@ int ctk_log_read(ctk_handle* h, int which, size_t first_step, size_t n_steps, fl
 // =============================================================================================
 // Batched MPPI (include/ctk_hip.h: ctk_batch_*): B independent problems of one configuration, stepped by ONE launch of
 // ctk_mppi_batch<ENV, LOG> per step (ctk_mppi.hip).  One allocation per buffer kind with a problem stride — no handles inside.
-// Per-problem host state is what a handle keeps: the sequence number of its next step, its Philox position, which u_nom buffer is current.
+// Per-problem host state is what a handle keeps: the sequence number of its next step, its Philox position, which u_nom buffer is current,
+// its parameter table.  While no ctk_problem_set_param has succeeded the launches take the constants of the shared table by value; from
+// then on (`differ`, sticky) they read every problem's constants from d_k, which ctk_batch_step refreshes for the problems marked dirty.
 // =============================================================================================
 struct ctk_batch {
     ctk_config cfg{};
     int B = 0, N = 0, H = 0, P = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, PC = 0, blocks = 0;
-    float params[CTK_MAX_PARAMS]{};
+    float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (ctk_batch_set_param / get_param)
+    std::vector<float> pparams;             // [B][CTK_MAX_PARAMS] every problem's own table
+    std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived into h_k / copied to d_k
+    bool differ = false;                    // a ctk_problem_set_param has succeeded: the per-problem form of the kernel from now on
+    size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes per problem in h_k / d_k
+    unsigned char* h_k = nullptr;           // pinned [B][kstride] derived constants, the staging of the copy to d_k
+    unsigned char* d_k = nullptr;           // [B][kstride]
     MppiK mk{};
     hipStream_t stream = nullptr;
     int max_per_launch = 1;                 // problems per launch: half the device's CUs (ctk_batch_create), a diagnostic switch may lower it
@@ -2395,6 +2403,8 @@ struct ctk_batch {
     size_t unom_stride() const { return (size_t)2 * HC; }
     float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
     float* slot(int p) const { return h_u + (size_t)p * 16; }
+    float* table(int p) { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
+    const float* table(int p) const { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
 };
 
 namespace {
@@ -2442,6 +2452,25 @@ RolloutArgs batch_args(const ctk_batch* b) {
     return a;
 }
 
+// The per-problem form's constants: re-derive those of every dirty problem (stepped now or not) with the function a handle uses
+// (ctk_set_param -> derive_constants / Env<>::derive at its launch), and copy the span from the first to the last dirty problem in ONE
+// transfer on the batch's stream; no transfer when nothing is dirty.  h_k mirrors d_k, so what lies between two dirty problems is current.
+// The caller synchronises before it returns (ctk_batch_step), so the staging is free again at the next call.
+hipError_t batch_flush_constants(ctk_batch* b) {
+    int lo = b->B, hi = -1;
+    for (int p = 0; p < b->B; ++p) {
+        if (!b->dirty[(size_t)p]) continue;
+        ctk_mppi_batch_derive_k(b->env, b->table(p), b->cfg.dt, b->cfg.intermediate_steps, b->h_k + (size_t)p * b->kstride);
+        b->dirty[(size_t)p] = 0;
+        lo = std::min(lo, p); hi = p;
+    }
+    if (hi < 0) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(b->d_k + (size_t)lo * b->kstride, b->h_k + (size_t)lo * b->kstride, (size_t)(hi - lo + 1) * b->kstride,
+                                        hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess) for (int p = lo; p <= hi; ++p) b->dirty[(size_t)p] = 1;       // nothing reached the device: derive and copy again
+    return e;
+}
+
 // optimizer_reset() of problem p (ctk_reset of an MPPI handle): the plan at mid-range in buffer 0; u, the Philox position stay
 int batch_reset_one(ctk_batch* b, int p) {
     std::vector<float> tmp((size_t)b->HC);
@@ -2465,10 +2494,11 @@ void ctk_batch_destroy(ctk_batch* b) {
     if (!b) return;
     hipSetDevice(b->cfg.device);
     if (b->stream) hipStreamSynchronize(b->stream);
-    void* bufs[] = {b->d_interp, b->d_J, b->d_Q, b->d_traj, b->d_parts, b->d_ll, b->d_unom, b->d_u, b->d_desc, b->d_steps, b->d_samples};
+    void* bufs[] = {b->d_interp, b->d_J, b->d_Q, b->d_traj, b->d_parts, b->d_ll, b->d_unom, b->d_u, b->d_desc, b->d_steps, b->d_samples, b->d_k};
     for (void* p : bufs) if (p) hipFree(p);
     if (b->h_u) hipHostFree(b->h_u);
     if (b->h_steps) hipHostFree(b->h_steps);
+    if (b->h_k) hipHostFree(b->h_k);
     if (b->stream) hipStreamDestroy(b->stream);
     delete b;
 }
@@ -2508,6 +2538,10 @@ int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seed
     b->B = n_problems; b->N = N; b->H = H; b->P = P; b->blocks = blocks;
     b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = H * b->C; b->PC = P * b->C;
     default_params(b->env, b->params);
+    b->pparams.resize((size_t)n_problems * CTK_MAX_PARAMS);
+    for (int p = 0; p < n_problems; ++p) std::memcpy(b->table(p), b->params, sizeof(b->params));
+    b->dirty.assign((size_t)n_problems, 1);            // no constants in d_k yet: the first step of the per-problem form derives them all
+    b->kstride = ctk_mppi_batch_k_stride(b->env);
     b->mk = mppi_constants(b->cfg);
     // Progress: the only workgroup of a launch that ever waits is block 0 of a problem, for workgroups of its own problem.  With at most
     // CUs / 2 problems in a launch the waiting workgroups cannot fill the machine (every CU holds at least one workgroup of this kernel),
@@ -2544,6 +2578,9 @@ int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seed
     BHIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
     BHIP_CREATE(hipHostMalloc((void**)&b->h_steps, Bz * sizeof(CtkBatchStep), hipHostMallocDefault));
     std::memset(b->h_steps, 0, Bz * sizeof(CtkBatchStep));
+    BHIP_CREATE(dev_zero((void**)&b->d_k, Bz * b->kstride));
+    BHIP_CREATE(hipHostMalloc((void**)&b->h_k, Bz * b->kstride, hipHostMallocDefault));
+    std::memset(b->h_k, 0, Bz * b->kstride);
 
     const std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, P);
     std::vector<CtkBatchDesc> desc(Bz);
@@ -2601,13 +2638,15 @@ int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, 
         for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
         for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
     }
-    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkBatchStep), hipMemcpyHostToDevice, b->stream);
+    hipError_t le = b->differ ? batch_flush_constants(b) : hipSuccess;          // the constants' transfer goes ahead of the step records'
+    if (le == hipSuccess) le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkBatchStep), hipMemcpyHostToDevice, b->stream);
     const RolloutArgs a = batch_args(b);
     const bool log = b->cfg.materialize_trajectories != 0;
     int launched = 0;                                  // consecutive launches of at most max_per_launch problems: the results do not depend on the split
     while (le == hipSuccess && launched < n) {
         const int cnt = std::min(b->max_per_launch, n - launched);
-        le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, b->d_steps + launched, cnt, log);
+        le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, b->d_steps + launched, cnt, log,
+                                   b->differ ? b->d_k : nullptr);
         if (le == hipSuccess) launched += cnt;
     }
     for (int j = 0; j < launched; ++j) b->cur[(size_t)b->h_steps[j].id] ^= 1;
@@ -2704,7 +2743,8 @@ int ctk_batch_set_state(ctk_batch* b, int problem, const float* src, size_t n) {
 int ctk_batch_set_param(ctk_batch* b, int id, float value) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     if (id < 0 || id >= env_info(b->env)->n_params) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_set_param: unknown parameter id for this environment");
-    b->params[id] = value;                             // every problem: the kernel constants are derived from the table at each launch
+    b->params[id] = value;                             // the shared table: the shared form derives its constants from it at each launch
+    for (int p = 0; p < b->B; ++p) { b->table(p)[id] = value; b->dirty[(size_t)p] = 1; }   // column id of every problem; the other ids stay
     return CTK_OK;
 }
 
@@ -2713,6 +2753,32 @@ int ctk_batch_get_param(const ctk_batch* b, int id, float* value) {
     *value = b->params[id];
     return CTK_OK;
 }
+
+int ctk_problem_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_problem_set_param", n_ids, ids, &n)) return rc;
+    if (id < 0 || id >= env_info(b->env)->n_params) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_problem_set_param: unknown parameter id for this environment");
+    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_problem_set_param: NULL values (one value per listed problem)");
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        b->table(p)[id] = values[j];
+        b->dirty[(size_t)p] = 1;
+    }
+    if (!b->differ) {                                  // sticky: the tables are never compared again
+        b->differ = true;
+        b->dominant = ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    }
+    return CTK_OK;
+}
+
+int ctk_problem_get_param(const ctk_batch* b, int problem, int id, float* value) {
+    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->table(problem)[id];
+    return CTK_OK;
+}
+
+int ctk_problem_params_differ(const ctk_batch* b) { return b && b->differ ? 1 : 0; }
 
 int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call) {
     if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;

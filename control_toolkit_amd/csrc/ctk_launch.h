@@ -175,11 +175,18 @@ struct CtkBatchStep {
 // 0: a problem of these sizes runs in the batch kernel; else why not (1 throughput sizes, 2 more records / words than the FORM 0 tail takes,
 // 3 the records do not fit the tail's LDS staging, 4 LDS over 160 KiB); *lds_out: dynamic LDS of a launch, *blocks_out: workgroups per problem
 int ctk_mppi_batch_fit(int env, int N, int H, int P, size_t* lds_out, int* blocks_out);
-const char* ctk_mppi_batch_name(int env, bool log);
+// per_problem: the form whose constants come from an array in device memory (ctk_mppi_batch_pp<ENV, LOG>), one element per problem
+const char* ctk_mppi_batch_name(int env, bool log, bool per_problem = false);
+// that array: element p at byte p * ctk_mppi_batch_k_stride(env) (sizeof(Env<env>::K) rounded up to 16), filled by
+// ctk_mppi_batch_derive_k = Env<env>::derive(params, dt, isteps), the function behind a handle's constants (double -> fp32 once)
+size_t ctk_mppi_batch_k_stride(int env);
+void ctk_mppi_batch_derive_k(int env, const float* params, float dt, int isteps, void* dst);
 // n_problems step records from `steps_dev` on, as ONE launch; a: the shared template (limits, sizes, interpolation table; s0 / u_prev / the
-// output pointers / seed / call come from the records and descriptors)
+// output pointers / seed / call come from the records and descriptors).  k_dev == nullptr: ctk_mppi_batch, every problem with the
+// constants of `params`; else ctk_mppi_batch_pp, problem p with element p of k_dev (`params` unused)
 hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
-                                 const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log);
+                                 const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
+                                 const void* k_dev = nullptr);
 hipError_t ctk_launch_mppi_merge_partial(hipStream_t st, const float* parts, int n_parts, int per_block, int P,
                                          float neg_inv_lbd, float* out_rec);
 // direct peer-to-peer record exchange + merge + update (ctk_mppi.hip: ctk_mppi_p2p_exchange)

@@ -31,6 +31,7 @@
 #include "ctk_launch.h"
 #include "ctk_mppi_merge.h"
 #include <cstring>
+#include <type_traits>
 
 constexpr int MPPI_TRAJ = 64;     // trajectories per block: one wave runs the recurrence
 constexpr int MPPI_WAVES = 4;     // waves per block: the prologue / epilogue are spread over all four
@@ -411,6 +412,14 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_resident(const ResidentAr
     }
 }
 
+// stride of the per-problem constants array (ctk_mppi_batch_pp): sizeof(K) rounded up to 16, which also keeps every element aligned
+template <int ENV>
+struct CtkBatchKStride {
+    using K = typename Env<ENV>::K;
+    static_assert(std::is_trivially_copyable<K>::value && alignof(K) <= 16, "the derived constants travel as bytes");
+    static constexpr size_t value = (sizeof(K) + 15) & ~(size_t)15;
+};
+
 // ---------------------------------------------------------------------------------------------
 // The BATCH form (include/ctk_hip.h: ctk_batch_*): B independent problems of one configuration in ONE launch — the same step, the same
 // statements (ctk_mppi_body.inc, unchanged, FORM 0), around per-problem inputs.  Grid (workgroups per problem, problems of this launch):
@@ -430,25 +439,26 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch(const CtkBatchDesc*
     constexpr int PRED = CTK_PRED_ODE, FORM = 0;
     constexpr bool P2P = false;
     extern __shared__ float lds[];
-    const CtkBatchStep& q = steps[blockIdx.y];
-    const CtkBatchDesc& d = desc[q.id];
-    RolloutArgs a_in = a_tpl;
-#pragma unroll
-    for (int i = 0; i < Env<ENV>::S; ++i) a_in.s0[i] = q.s[i];
-#pragma unroll
-    for (int c = 0; c < Env<ENV>::C; ++c) a_in.u_prev[c] = q.u_prev[c];
-    a_in.u_prev_dev = q.dev_uprev ? d.u_dev : nullptr;
-    a_in.J = d.J; a_in.Q_out = d.Q_out; a_in.traj_out = d.traj_out;
-    a_in.seed_lo = d.seed_lo; a_in.seed_hi = d.seed_hi; a_in.call = q.call;
-    const float* samples = q.samples;
-    const float* u_nom = q.cur ? d.unom[1] : d.unom[0];
-    float* parts = d.parts;
-    FuseArgs fz = fz_tpl;                      // mode 1, stage_ok, the shared update constants (launcher)
-    fz.ll = d.ll;
-    fz.up.seq = q.seq;
-    fz.up.u_nom_in = u_nom; fz.up.u_nom_out = q.cur ? d.unom[0] : d.unom[1];
-    fz.up.u_dev = d.u_dev; fz.up.u_host = d.u_host;
+#include "ctk_mppi_batch_pro.inc"
     (void)spare;
+#include "ctk_mppi_body.inc"
+}
+
+// The PER-PROBLEM-PARAMETER form of the batch kernel (ctk_problem_set_param): the same prologue and the same body, but the derived
+// constants `k` of the problem come from the array kdev [B] (stride CtkBatchKStride<ENV>, written by the host with Env<ENV>::derive, as a
+// handle's are) instead of the by-value argument; kdev takes the place of `spare`, so the preloaded dwords are where they were.  q.id is
+// uniform, so the constants arrive by scalar loads like the descriptor; they are copied into a local K here, ahead of the body's first
+// global store, and stay in SGPRs through the recurrence.
+template <int ENV, bool LOG>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_pp(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                const InterpEntry* __restrict__ interp, const float* __restrict__ wperm,
+                                                                const unsigned char* __restrict__ kdev, int N_, int H_, int P_, uint32_t pmagic_,
+                                                                RolloutArgs a_tpl, MppiK m, FuseArgs fz_tpl) {
+    constexpr int PRED = CTK_PRED_ODE, FORM = 0;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+#include "ctk_mppi_batch_pro.inc"
+    const typename Env<ENV>::K k = *reinterpret_cast<const typename Env<ENV>::K*>(kdev + (size_t)q.id * CtkBatchKStride<ENV>::value);
 #include "ctk_mppi_body.inc"
 }
 
@@ -942,10 +952,23 @@ int ctk_mppi_batch_fit(int env, int N, int H, int P, size_t* lds_out, int* block
     if (lds > 160 * 1024) return 4;
     return 0;
 }
-const char* ctk_mppi_batch_name(int env, bool log) { return ctk_kernel_name("ctk_mppi_batch<%d, %4$s>", env, 0, 0, log ? "true" : "false"); }
+const char* ctk_mppi_batch_name(int env, bool log, bool per_problem) {
+    return ctk_kernel_name(per_problem ? "ctk_mppi_batch_pp<%d, %4$s>" : "ctk_mppi_batch<%d, %4$s>", env, 0, 0, log ? "true" : "false");
+}
+size_t ctk_mppi_batch_k_stride(int env) {
+    size_t stride = 0;
+    CTK_FOR_ENV(env, EV, { stride = CtkBatchKStride<EV>::value; });
+    return stride;
+}
+void ctk_mppi_batch_derive_k(int env, const float* params, float dt, int isteps, void* dst) {
+    CTK_FOR_ENV(env, EV, {
+        const typename Env<EV>::K k = Env<EV>::derive(params, dt, isteps);
+        std::memcpy(dst, &k, sizeof(k));
+    });
+}
 
 hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
-                                 const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log) {
+                                 const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log, const void* k_dev) {
     size_t lds;
     int blocks;
     if (n_problems < 1 || ctk_mppi_batch_fit(env, a.N, a.H, a.P, &lds, &blocks) != 0) return hipErrorInvalidValue;
@@ -955,12 +978,19 @@ hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, f
         FuseArgs fz{};                                 // merge + update by block 0 of every problem over the staged {value, seq} words;
         fz.mode = 1; fz.stage_ok = 1;                  // the pointers and the sequence number are the descriptors' / the step records'
         fz.up = mppi_update_args(a, E::C, nullptr, nullptr, nullptr, nullptr, 0u);
-        const typename E::K k = E::derive(params, dt, isteps);
         const uint32_t pmagic = ctk_magic_of(a.P * E::C);
-        ctk_with_bool(log, [&](auto log_c) {
-            hipLaunchKernelGGL((ctk_mppi_batch<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp,
-                               static_cast<const float*>(nullptr), static_cast<const void*>(nullptr), a.N, a.H, a.P, pmagic, a, k, m, fz);
-        });
+        if (k_dev) {                                   // per-problem constants: the array the host derived (ctk_mppi_batch_derive_k)
+            ctk_with_bool(log, [&](auto log_c) {
+                hipLaunchKernelGGL((ctk_mppi_batch_pp<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp,
+                                   static_cast<const float*>(nullptr), static_cast<const unsigned char*>(k_dev), a.N, a.H, a.P, pmagic, a, m, fz);
+            });
+        } else {
+            const typename E::K k = E::derive(params, dt, isteps);
+            ctk_with_bool(log, [&](auto log_c) {
+                hipLaunchKernelGGL((ctk_mppi_batch<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp,
+                                   static_cast<const float*>(nullptr), static_cast<const void*>(nullptr), a.N, a.H, a.P, pmagic, a, k, m, fz);
+            });
+        }
     });
     return hipGetLastError();
 }

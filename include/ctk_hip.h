@@ -468,11 +468,13 @@ int ctk_resident_stats(const ctk_handle* h, uint64_t* launches, uint64_t* steps,
  * whose optimizer object is one controller: Optimizers/__init__.py:67; added without an ABI bump, as CTK_OPT_CEM_GMM was).  A handle's
  * step at the headline size occupies 16 of the chip's 256 CUs and pays as much again for its launch and completion; data generation over
  * many experiments, a fleet of plants or a server with several clients step B handles one after another.  A batch steps them together.
- *  - shared by all problems: everything in ctk_config (environment, N, H, period, limits, MPPI constants) and the parameter table;
- *    per problem: state, previous input, nominal plan, last output, Philox seed and position, draws and the readable buffers;
+ *  - shared by all problems: everything in ctk_config (environment, N, H, period, limits, MPPI constants);
+ *    per problem: state, previous input, nominal plan, last output, Philox seed and position, draws, the readable buffers and the
+ *    parameter table (plant, cost weights, targets: ctk_problem_set_param below);
  *  - CONTRACT: problem p behaves bit for bit like a ctk_handle created from the same ctk_config with seed = seeds[p] that received the
  *    same calls (u, U_NOM, J, Q, TRAJ, the Philox position, the ctk_get_state vector), for every sample source, u_prev given or NULL,
- *    and any interleaving of whole-batch steps, subset steps and per-problem resets;
+ *    and any interleaving of whole-batch steps, subset steps, per-problem resets and parameter changes (ctk_set_param is one of those
+ *    calls: ctk_problem_set_param on problem p, or ctk_batch_set_param on all of them);
  *  - MPPI with the analytic (ODE) predictor, per-problem sizes of the one-launch regime with the narrow in-launch hand-off (at most 128
  *    block records and 2048 record words per problem, below the throughput sizes); everything else is CTK_ERR_UNSUPPORTED with the sizes
  *    in ctk_batch_last_error(NULL), as is n_problems < 1;
@@ -483,6 +485,16 @@ int ctk_resident_stats(const ctk_handle* h, uint64_t* launches, uint64_t* steps,
  *    problem's own last output), samples [n,N,P,C] and u_out [n,C] follow the order of ids.  Bad ids: CTK_ERR_INVALID_ARGUMENT;
  *  - ctk_batch_step is synchronous.  CTK_ERR_STATE = a bounded device-side wait ran out for the problems the message names (their
  *    outputs are NaN); the other problems' outputs are valid and written.  A batch is NOT thread-safe.
+ *  - parameters: every problem has its own table, initialised with the environment's defaults.  ctk_batch_set_param(id, v) writes
+ *    column id of EVERY problem's table (the other ids stay per problem) and of the shared table that ctk_batch_get_param reads, so
+ *    ctk_batch_get_param returns the last whole-batch value of id, NOT what a problem holds after a ctk_problem_set_param
+ *    (ctk_problem_get_param reads that).  ctk_problem_set_param sets parameter id of the listed problems (ids as above; values[n], one
+ *    per listed problem, in the order of ids), legal only between steps; a bad id list, a bad parameter id or NULL values is
+ *    CTK_ERR_INVALID_ARGUMENT and nothing is written.  The kernel constants of the problems whose table changed are re-derived at the
+ *    next ctk_batch_step (as ctk_set_param derives a handle's) and travel in one transfer ahead of the step records.  Once a
+ *    ctk_problem_set_param has succeeded, ctk_problem_params_differ is 1 for the rest of the batch's life and the steps launch the
+ *    per-problem form of the kernel (ctk_batch_dominant_kernel names the form the next step launches); a batch that never calls it runs
+ *    the shared form.  ctk_batch_reset leaves the tables alone, as ctk_reset leaves a handle's.
  * Each entry corresponds to the single-handle call named beside it.
  * ----------------------------------------------------------------------------------------- */
 typedef struct ctk_batch ctk_batch;
@@ -502,6 +514,9 @@ int ctk_batch_get_param(const ctk_batch* b, int id, float* value);              
 int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call);        /* ctk_rng_get_position */
 int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call);               /* ctk_rng_set_position */
 const char* ctk_batch_dominant_kernel(const ctk_batch* b);                              /* ctk_dominant_kernel */
+int ctk_problem_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, const float* values);   /* ctk_set_param of every listed problem */
+int ctk_problem_get_param(const ctk_batch* b, int problem, int id, float* value);       /* ctk_get_param of one problem */
+int ctk_problem_params_differ(const ctk_batch* b);                                      /* 1 once a ctk_problem_set_param has succeeded */
 
 #ifdef __cplusplus
 }
