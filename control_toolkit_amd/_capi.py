@@ -145,6 +145,22 @@ SYMBOLS = {
     "ctk_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "ctk_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
     "ctk_problem_params_differ": (C.c_int, [_H]),
+    # batched CEM (ctk_cem_batch_*): _H is the ctk_cem_batch* there
+    "ctk_cem_batch_create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
+    "ctk_cem_batch_destroy": (None, [_H]),
+    "ctk_cem_batch_last_error": (C.c_char_p, [_H]),
+    "ctk_cem_batch_size": (C.c_int, [_H]),
+    "ctk_cem_batch_samples_needed": (C.c_size_t, [_H, C.c_int]),
+    "ctk_cem_batch_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ctk_cem_batch_reset": (C.c_int, [_H, C.c_int, C.c_void_p]),
+    "ctk_cem_batch_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_cem_batch_get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_cem_batch_set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_cem_batch_set_param": (C.c_int, [_H, C.c_int, C.c_float]),
+    "ctk_cem_batch_get_param": (C.c_int, [_H, C.c_int, _FP]),
+    "ctk_cem_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
+    "ctk_cem_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
+    "ctk_cem_batch_dominant_kernel": (C.c_char_p, [_H]),
 }
 
 
@@ -241,6 +257,14 @@ def _f32(a, shape=None) -> np.ndarray:
     return out
 
 
+# the optimizer keywords of a ctk_config; the defaults keep unrelated optimizers' fields valid
+_CONFIG_DEFAULTS = dict(cc_weight=1.0, R=1.0, LBD=100.0, NU=1000.0, SQRTRHOINV=0.03, cem_outer_it=1, cem_best_k=1,
+                        warmup=0, warmup_iterations=0, cem_initial_action_stdev=0.5, cem_stdev_min=0.01,
+                        outer_its=1, resamp_per=1, shift_previous=1, opt_keep_k=1, sampling_distribution=0,
+                        sample_whole_control_space=0, sample_stdev=0.5, sample_mean=0.0, sample_min=-1.0, sample_max=1.0, learning_rate=0.05,
+                        gradmax_clip=5.0, adam_beta_1=0.9, adam_beta_2=0.999, adam_epsilon=1e-8, adam_rule=0, predictor_hidden1=0, predictor_hidden2=0)
+
+
 def _make_config(optimizer: str, predictor: str, env_id: int, environment: str, Cn: int, *, num_rollouts, mpc_horizon, dt, action_low,
                  action_high, period_interpolation_inducing_points, seed, device, intermediate_steps, materialize_trajectories,
                  global_rollout_offset, num_states, num_control_inputs, generic_kernels, **kw) -> "CtkConfig":
@@ -263,12 +287,7 @@ def _make_config(optimizer: str, predictor: str, env_id: int, environment: str, 
         raise ValueError(f"control limits must be scalars or have {Cn} entries (num_control_inputs of {environment})")
     for c in range(Cn):
         cfg.action_low[c], cfg.action_high[c] = float(lo[c]), float(hi[c])
-    # defaults keep unrelated optimizers' fields valid
-    defaults = dict(cc_weight=1.0, R=1.0, LBD=100.0, NU=1000.0, SQRTRHOINV=0.03, cem_outer_it=1, cem_best_k=1,
-                    warmup=0, warmup_iterations=0, cem_initial_action_stdev=0.5, cem_stdev_min=0.01,
-                    outer_its=1, resamp_per=1, shift_previous=1, opt_keep_k=1, sampling_distribution=0,
-                    sample_whole_control_space=0, sample_stdev=0.5, sample_mean=0.0, sample_min=-1.0, sample_max=1.0, learning_rate=0.05,
-                    gradmax_clip=5.0, adam_beta_1=0.9, adam_beta_2=0.999, adam_epsilon=1e-8, adam_rule=0, predictor_hidden1=0, predictor_hidden2=0)
+    defaults = dict(_CONFIG_DEFAULTS)
     unknown = set(kw) - set(defaults)
     if unknown:
         raise TypeError(f"unknown engine arguments: {sorted(unknown)}")
@@ -863,3 +882,165 @@ class CtkMppiBatch:
 
     def dominant_kernel(self) -> str:
         return self._lib.ctk_batch_dominant_kernel(self._h).decode()
+
+
+# ---- batched CEM (include/ctk_hip.h: ctk_cem_batch_*) ---------------------------------------------------------------------------------
+class CtkCemBatch:
+    """Owns one ctk_cem_batch: num_problems independent plain-CEM controllers of ONE configuration (the CEM keywords of CtkEngine),
+    stepped together by launches of one kernel.  Problem p behaves bit for bit like CtkEngine("cem", "ODE", seed=seeds[p], ...) given the
+    same calls.  seeds: one per problem (default seed + p).  The parameter table is shared: set_param reaches every problem."""
+
+    def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "cem", predictor: str = "ODE",
+                 num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
+                 period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
+                 materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
+                 num_control_inputs: int = None, generic_kernels: bool = False, **kw):
+        # what needs no device is checked before the library is asked for one
+        if int(num_problems) < 1:
+            raise ValueError(f"a batch holds at least one problem (num_problems == {num_problems})")
+        B = int(num_problems)
+        if optimizer != "cem":
+            raise NotImplementedError(f"a CEM batch steps plain CEM controllers only (optimizer {optimizer!r}); MPPI has CtkMppiBatch, the CEM "
+                                      "variants and the other optimizers run as CtkEngine")
+        if predictor != "ODE":
+            raise NotImplementedError(f"the batch kernel rolls out the analytic (ODE) predictor only (predictor {predictor!r}); "
+                                      "network predictors run as CtkEngine")
+        if seeds is not None:
+            seeds = np.ascontiguousarray(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in np.asarray(seeds, dtype=object).reshape(-1)], np.uint64))
+            if seeds.size != B:
+                raise ValueError(f"seeds must have one entry per problem ({B}), got {seeds.size}")
+        unknown = set(kw) - set(_CONFIG_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown engine arguments: {sorted(unknown)}")
+        lib, env_id = environment_library(environment)
+        S, Cn, self.param_names = environment_info(environment)
+        self.environment, self.S, self.C, self.B = environment, S, Cn, B
+        cfg = _make_config("cem", "ODE", env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                           action_low=action_low, action_high=action_high,
+                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                           global_rollout_offset=global_rollout_offset, num_states=S if num_states is None else num_states,
+                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs, generic_kernels=generic_kernels, **kw)
+        self._lib, self.cfg = lib, cfg
+        self.N, self.H, self.K = int(num_rollouts), int(mpc_horizon), int(cfg.cem_best_k)
+        self._h = _H()
+        rc = lib.ctk_cem_batch_create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
+        if rc != 0:
+            msg = lib.ctk_cem_batch_last_error(None).decode()
+            self._h = _H()
+            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(msg)
+        # preallocated argument buffers, as CtkEngine.step's: rows 0 .. n-1 are the stepped problems'
+        self._s = np.zeros((B, S), np.float32)
+        self._up = np.zeros((B, Cn), np.float32)
+        self._u = np.zeros((B, Cn), np.float32)
+        self._ids = np.zeros(B, np.int32)
+        self._s_p, self._up_p, self._u_p, self._ids_p = (a.ctypes.data for a in (self._s, self._up, self._u, self._ids))
+        self._step_fn = lib.ctk_cem_batch_step
+
+    def _check(self, rc: int):
+        if rc != 0:
+            msg = self._lib.ctk_cem_batch_last_error(self._h).decode()
+            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(f"[ctk {rc}] {msg}")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.ctk_cem_batch_destroy(self._h)
+            self._h = _H()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.B
+
+    def _problem(self, problem: int) -> int:
+        if not 0 <= int(problem) < self.B:
+            raise ValueError(f"problem index {problem} is outside 0 .. {self.B - 1}")
+        return int(problem)
+
+    def samples_needed(self, problem: int = 0) -> int:
+        """draws the NEXT step of `problem` consumes (its * N * H * C: a warm-up step after creation or reset is longer)"""
+        return int(self._lib.ctk_cem_batch_samples_needed(self._h, self._problem(problem)))
+
+    def step(self, S, samples=None, u_prev=None, ids=None) -> np.ndarray:
+        """S [n, num_states], one row per stepped problem in the order of ids (None: all problems).  samples: None (device Philox), a
+        host array [n, its, N, H, C] or an int device pointer to such an array; with samples every listed problem must run the same
+        number of outer iterations (ValueError naming them otherwise).  u_prev [n, C] or None (every problem's own last output).
+        Returns u [n, C].  CtkError naming the problems whose in-launch hand-off timed out: the other problems' rows are valid (`last_u`)."""
+        idv, n, _ = batch_step_args(self.B, self.S, self.C, 0, S, None, u_prev, ids)       # ids, states, u_prev
+        if samples is not None and type(samples) is not int:
+            # a host array (the parity path): its size against what the listed problems' next steps draw.  Where they differ in their
+            # iteration counts the library refuses the call, naming them, before it reads a sample: the array goes through as it is
+            samples = _f32(samples)
+            needs = {self.samples_needed(p) for p in (range(self.B) if idv is None else idv.tolist())}
+            per = needs.pop()
+            if not needs and (samples.size != n * per or (samples.ndim > 1 and samples.shape[0] != n)):
+                raise ValueError(f"step of {n} problems consumes {n} x {per} draws ([n, its, N, H, C]), got shape {tuple(samples.shape)}")
+        self._s[:n] = np.asarray(S).reshape(n, self.S)
+        up_p = None
+        if u_prev is not None:
+            self._up[:n] = np.asarray(u_prev).reshape(n, self.C)
+            up_p = self._up_p
+        ids_p = None
+        if idv is not None:
+            self._ids[:n] = idv
+            ids_p = self._ids_p
+        if samples is None:
+            sp, loc = None, LOC_NONE
+        elif type(samples) is int:
+            sp, loc = samples, LOC_DEVICE
+        else:
+            sp, loc = samples.ctypes.data, LOC_HOST
+        rc = self._step_fn(self._h, n, ids_p, self._s_p, up_p, sp, loc, self._u_p)
+        self.last_u = self._u[:n].copy()
+        if rc:
+            self._check(rc)
+        return self.last_u
+
+    def reset(self, ids=None):
+        idv = batch_ids(self.B, ids)
+        self._check(self._lib.ctk_cem_batch_reset(self._h, 0 if idv is None else idv.size, _ptr(idv)))
+
+    def read(self, name: str, problem: int) -> np.ndarray:
+        N, H, S, Cn = self.N, self.H, self.S, self.C
+        shapes = {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn), "STD": (1, H, Cn), "BEST_IDX": (self.K,)}
+        if name not in shapes:
+            raise ValueError(f"a CEM batch has the buffers {sorted(shapes)}, not {name!r}")
+        out = np.empty(shapes[name], np.float32)
+        self._check(self._lib.ctk_cem_batch_read(self._h, self._problem(problem), BUFFERS[name], _ptr(out), out.size))
+        return out.astype(np.int64) if name == "BEST_IDX" else out
+
+    def read_all(self, name: str) -> np.ndarray:
+        return np.stack([self.read(name, p) for p in range(self.B)])
+
+    def get_state(self, problem: int) -> np.ndarray:
+        """mu[H,C] | std[H,C] | u[C] | count of one problem (CtkEngine.get_state of a CEM engine)"""
+        buf = np.empty(2 * self.H * self.C + self.C + 1, np.float32)
+        self._check(self._lib.ctk_cem_batch_get_state(self._h, self._problem(problem), _ptr(buf), buf.size))
+        return buf
+
+    def set_state(self, problem: int, state):
+        st = _f32(state).ravel()
+        self._check(self._lib.ctk_cem_batch_set_state(self._h, self._problem(problem), _ptr(st), st.size))
+
+    def set_param(self, name: str, value: float):
+        self._check(self._lib.ctk_cem_batch_set_param(self._h, self.param_names.index(name), float(value)))
+
+    def get_param(self, name: str) -> float:
+        v = C.c_float()
+        self._check(self._lib.ctk_cem_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
+        return v.value
+
+    def rng_position(self, problem: int) -> int:
+        v = C.c_uint32()
+        self._check(self._lib.ctk_cem_batch_rng_get_position(self._h, self._problem(problem), C.byref(v)))
+        return int(v.value)
+
+    def set_rng_position(self, problem: int, call: int):
+        self._check(self._lib.ctk_cem_batch_rng_set_position(self._h, self._problem(problem), int(call) & 0xFFFFFFFF))
+
+    def dominant_kernel(self) -> str:
+        return self._lib.ctk_cem_batch_dominant_kernel(self._h).decode()

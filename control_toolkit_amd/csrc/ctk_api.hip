@@ -2794,3 +2794,415 @@ int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) {
 }
 
 }  // extern "C"
+
+// =============================================================================================
+// Batched CEM (include/ctk_hip.h: ctk_cem_batch_*): B independent CEM problems of one configuration, stepped by launches of
+// ctk_cem_batch<ENV, TRAJ> (ctk_cem_fused.hip).  One allocation per buffer kind with a problem stride — no handles inside.  Per-problem
+// host state is what a CEM handle keeps: the sequence number of its next step, its Philox position, its step count (which decides the
+// outer iterations of its next step: cem_iterations), the next hand-off tag, and whether BEST_IDX has to be rebuilt from J.
+// =============================================================================================
+struct ctk_cem_batch {
+    ctk_config cfg{};
+    int B = 0, N = 0, H = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, K = 0, nblk = 0;
+    float params[CTK_MAX_PARAMS]{};         // one table for all problems (ctk_cem_batch_set_param)
+    hipStream_t stream = nullptr;
+    int max_per_launch = 1;                 // problems per launch: max(1, CUs / nblk) (ctk_cem_batch_create), a diagnostic switch may lower it
+    size_t llw = 0;                         // ctk_cem_fused_ll_words(N, HC): hand-off words per problem
+    unsigned long long* d_ll = nullptr;     // [B][llw], zero at allocation
+    float* d_mu = nullptr;                  // [B][H,C]
+    float* d_sd = nullptr;                  // [B][H,C]
+    float* d_J = nullptr;                   // [B][N]
+    float* d_Q = nullptr;                   // [B][N,H,C]
+    float* d_traj = nullptr;                // [B][N,H+1,S] (materialize_trajectories)
+    int* d_idx = nullptr;                   // [B][N]
+    float* d_u = nullptr;                   // [B][CTK_MAX_INPUTS]
+    float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
+    float* h_u_dev = nullptr;
+    CtkCemBatchDesc* d_desc = nullptr;      // [B]
+    CtkCemBatchStep* h_steps = nullptr;     // pinned [B]: the step records of the step being issued
+    CtkCemBatchStep* d_steps = nullptr;     // [B]
+    float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
+    std::vector<uint32_t> seq, call, cem_tag;
+    std::vector<int> count;
+    std::vector<unsigned char> idx_stale;
+    std::string err, dominant;
+    float* mu(int p) const { return d_mu + (size_t)p * HC; }
+    float* sd(int p) const { return d_sd + (size_t)p * HC; }
+    float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
+    float* slot(int p) const { return h_u + (size_t)p * 16; }
+    int its(int p) const { return (cfg.warmup && count[(size_t)p] == 0) ? cfg.warmup_iterations : cfg.cem_outer_it; }   // cem_iterations
+};
+
+namespace {
+
+int cfail(ctk_cem_batch* b, int code, const std::string& msg) {
+    if (b) b->err = msg; else g_create_error = msg;
+    return code;
+}
+#define CHIP_TRY(b, expr)                                                                       \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess)                                                                   \
+            return cfail((b), CTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
+    } while (0)
+
+// the problems a call addresses (batch_ids of the MPPI family): ids[0..n) strictly ascending, or all of them (ids == NULL)
+int cem_batch_ids(ctk_cem_batch* b, const char* who, int n_ids, const int32_t* ids, int* n_out) {
+    if (!ids) { *n_out = b->B; return CTK_OK; }
+    if (n_ids < 1 || n_ids > b->B) return cfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": n_ids must be 1 .. " + std::to_string(b->B) + " (the batch size)");
+    for (int j = 0; j < n_ids; ++j) {
+        if (ids[j] < 0 || ids[j] >= b->B)
+            return cfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(ids[j]) + " is outside 0 .. " + std::to_string(b->B - 1));
+        if (j > 0 && ids[j] <= ids[j - 1]) return cfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": ids must be strictly ascending");
+    }
+    *n_out = n_ids;
+    return CTK_OK;
+}
+int cem_batch_problem(ctk_cem_batch* b, const char* who, int p) {
+    if (p < 0 || p >= b->B) return cfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(p) + " is outside 0 .. " + std::to_string(b->B - 1));
+    return CTK_OK;
+}
+
+// the shared template of a launch's RolloutArgs (make_args of a CEM handle without what the step records and descriptors supply)
+RolloutArgs cem_batch_args(const ctk_cem_batch* b) {
+    RolloutArgs a{};
+    for (int c = 0; c < b->C; ++c) { a.lo[c] = b->cfg.action_low[c]; a.hi[c] = b->cfg.action_high[c]; }
+    a.C = b->C;
+    a.N = b->N; a.H = b->H; a.P = b->H;
+    a.p_magic = ctk_magic_of(b->H);
+    a.inv_Hp1 = 1.0f / (float)(b->H + 1);
+    a.stream_id = 0;
+    a.global_row0 = b->cfg.global_rollout_offset;
+    return a;
+}
+
+// mean at mid-range, std = cem_initial_action_stdev, u = 0 of problem p into the host images (ctk_reset of a CEM handle)
+void cem_batch_initial(const ctk_cem_batch* b, float* mu, float* sd) {
+    for (int i = 0; i < b->HC; ++i) {
+        mu[i] = 0.5f * (b->cfg.action_low[i % b->C] + b->cfg.action_high[i % b->C]);
+        sd[i] = b->cfg.cem_initial_action_stdev;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* ctk_cem_batch_last_error(const ctk_cem_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+int ctk_cem_batch_size(const ctk_cem_batch* b) { return b ? b->B : 0; }
+size_t ctk_cem_batch_samples_needed(const ctk_cem_batch* b, int problem) {
+    return (b && problem >= 0 && problem < b->B) ? (size_t)b->its(problem) * b->N * b->HC : 0;
+}
+const char* ctk_cem_batch_dominant_kernel(const ctk_cem_batch* b) { return b ? b->dominant.c_str() : ""; }
+
+void ctk_cem_batch_destroy(ctk_cem_batch* b) {
+    if (!b) return;
+    hipSetDevice(b->cfg.device);
+    if (b->stream) hipStreamSynchronize(b->stream);
+    void* bufs[] = {b->d_ll, b->d_mu, b->d_sd, b->d_J, b->d_Q, b->d_traj, b->d_idx, b->d_u, b->d_desc, b->d_steps, b->d_samples};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (b->h_u) hipHostFree(b->h_u);
+    if (b->h_steps) hipHostFree(b->h_steps);
+    if (b->stream) hipStreamDestroy(b->stream);
+    delete b;
+}
+
+int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_cem_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return cfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_create: NULL argument");
+    if (n_problems < 1) return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    const EnvInfo* einfo = nullptr;
+    if (int rc = check_config("ctk_cem_batch_create", cfg, &einfo)) return rc;
+    if (cfg->optimizer != CTK_OPT_CEM)
+        return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: a CEM batch steps plain CEM controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+                     "); MPPI has ctk_batch_create, the CEM variants (naive-grad, Bharadhwaj, GMM) and the other optimizers run as single handles (ctk_create)");
+    if (cfg->predictor != CTK_PRED_ODE)
+        return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
+                     std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
+    const int N = cfg->num_rollouts, H = cfg->mpc_horizon, HC = H * einfo->C, nblk = ctk_cem_fused_blocks(N);
+    if (!ctk_cem_fusable(cfg->predictor, N, HC))
+        return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: per-problem population outside the one-launch CEM step's sizes (num_rollouts " + std::to_string(N) +
+                     " = " + std::to_string(nblk) + " workgroups of 64 rollouts, mpc_horizon " + std::to_string(H) + " x " + std::to_string(einfo->C) + " inputs = " +
+                     std::to_string(HC) + " columns, " + std::to_string(ctk_cem_fused_lds(N, HC)) + " bytes of LDS): the batch kernel takes at most " +
+                     std::to_string(CTK_CEM_FUSED_MAX_BLOCKS) + " workgroups per problem and 131072 bytes (128 KiB) of LDS; such a controller runs as a single handle (ctk_create)");
+    if (cfg->cem_best_k > N)
+        return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: cem_best_k " + std::to_string(cfg->cem_best_k) + " exceeds num_rollouts " + std::to_string(N) +
+                     ": the elite set of a problem is part of its population");
+    if (cfg->cem_best_k < 1 || cfg->cem_outer_it < 1 || (cfg->warmup && cfg->warmup_iterations < 1))
+        return cfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_create: need cem_best_k >= 1, cem_outer_it >= 1 and, with warmup, warmup_iterations >= 1");
+
+    hipDeviceProp_t prop;
+    if (int rc = probe_device("ctk_cem_batch_create", cfg->device, &prop)) return rc;
+
+    ctk_cem_batch* b = new ctk_cem_batch();
+    b->cfg = *cfg;
+    b->B = n_problems; b->N = N; b->H = H; b->K = cfg->cem_best_k; b->nblk = nblk;
+    b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = HC;
+    b->llw = ctk_cem_fused_ll_words(N, HC);
+    default_params(b->env, b->params);
+    // Progress (the proof stands above ctk_cem_batch, ctk_cem_fused.hip): every workgroup of a problem waits for all workgroups of that
+    // problem, so a launch holds at most max(1, CUs / nblk) problems — problems * nblk <= CUs, every CU admits at least one workgroup of
+    // this kernel (LDS <= 128 KiB), so all workgroups of a launch are co-resident whatever the dispatch order or placement.  One problem
+    // alone is the single kernel's case (nblk <= CTK_CEM_FUSED_MAX_BLOCKS).  CTK_CEM_BATCH_MAX_PROBLEMS_PER_LAUNCH (diagnostic) only lowers it.
+    b->max_per_launch = std::max(1, prop.multiProcessorCount / nblk);
+    if (const char* e = std::getenv("CTK_CEM_BATCH_MAX_PROBLEMS_PER_LAUNCH")) {
+        const int v = std::atoi(e);
+        if (v >= 1 && v < b->max_per_launch) b->max_per_launch = v;
+    }
+    b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u); b->cem_tag.assign((size_t)n_problems, 1u);
+    b->count.assign((size_t)n_problems, 0); b->idx_stale.assign((size_t)n_problems, 0);
+    b->dominant = ctk_cem_batch_name(b->env, cfg->materialize_trajectories != 0);
+
+    auto bail = [&](int rc) { g_create_error = b->err; ctk_cem_batch_destroy(b); return rc; };
+#define CHIP_CREATE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { b->err = std::string(#expr) + ": " + hipGetErrorString(_e); return bail(CTK_ERR_HIP); } } while (0)
+    CHIP_CREATE(hipSetDevice(cfg->device));
+    CHIP_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    const size_t Bz = (size_t)n_problems;
+    auto dev_zero = [&](void** p, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+        return e != hipSuccess ? e : hipMemsetAsync(*p, 0, bytes ? bytes : 1, b->stream);
+    };
+    CHIP_CREATE(dev_zero((void**)&b->d_ll, Bz * b->llw * sizeof(unsigned long long)));
+    CHIP_CREATE(dev_zero((void**)&b->d_mu, Bz * HC * sizeof(float)));
+    CHIP_CREATE(dev_zero((void**)&b->d_sd, Bz * HC * sizeof(float)));
+    CHIP_CREATE(dev_zero((void**)&b->d_J, Bz * N * sizeof(float)));
+    CHIP_CREATE(dev_zero((void**)&b->d_Q, Bz * N * HC * sizeof(float)));
+    if (cfg->materialize_trajectories) CHIP_CREATE(dev_zero((void**)&b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float)));
+    CHIP_CREATE(dev_zero((void**)&b->d_idx, Bz * N * sizeof(int)));
+    CHIP_CREATE(dev_zero((void**)&b->d_u, Bz * CTK_MAX_INPUTS * sizeof(float)));
+    CHIP_CREATE(dev_zero((void**)&b->d_desc, Bz * sizeof(CtkCemBatchDesc)));
+    CHIP_CREATE(dev_zero((void**)&b->d_steps, Bz * sizeof(CtkCemBatchStep)));
+    CHIP_CREATE(hipHostMalloc((void**)&b->h_u, Bz * 64, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(b->h_u, 0, Bz * 64);
+    CHIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
+    CHIP_CREATE(hipHostMalloc((void**)&b->h_steps, Bz * sizeof(CtkCemBatchStep), hipHostMallocDefault));
+    std::memset(b->h_steps, 0, Bz * sizeof(CtkCemBatchStep));
+
+    std::vector<CtkCemBatchDesc> desc(Bz);
+    std::vector<float> mu(Bz * HC), sd(Bz * HC);                   // optimizer_reset() of every problem
+    for (int p = 0; p < n_problems; ++p) {
+        const size_t z = (size_t)p;
+        const uint64_t seed = seeds ? seeds[p] : cfg->seed + (uint64_t)p;
+        CtkCemBatchDesc& d = desc[z];
+        d.ll = b->d_ll + z * b->llw;
+        d.mu = b->mu(p); d.sd = b->sd(p);
+        d.J = b->d_J + z * N; d.Q_out = b->d_Q + z * N * HC;
+        d.traj_out = b->d_traj ? b->d_traj + z * N * (H + 1) * b->S : nullptr;
+        d.u_dev = b->u(p); d.u_host = b->h_u_dev + z * 16; d.idx_out = b->d_idx + z * N;
+        d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
+        cem_batch_initial(b, mu.data() + z * HC, sd.data() + z * HC);
+    }
+    CHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkCemBatchDesc), hipMemcpyHostToDevice, b->stream));
+    CHIP_CREATE(hipMemcpyAsync(b->d_mu, mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    CHIP_CREATE(hipMemcpyAsync(b->d_sd, sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    CHIP_CREATE(hipStreamSynchronize(b->stream));                  // the host vectors go out of scope below
+#undef CHIP_CREATE
+    *out = b;
+    return CTK_OK;
+}
+
+int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
+                       float* u_out) {
+    if (!b || !s) return b ? cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = cem_batch_ids(b, "ctk_cem_batch_step", n_ids, ids, &n)) return rc;
+    const size_t per_it = (size_t)b->N * b->HC;
+    const int its0 = b->its(ids ? ids[0] : 0);
+    if (samples_loc != CTK_LOC_NONE) {
+        if (samples == nullptr) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+        // the rows of a caller's buffer have ONE length: refused before anything is launched or consumed
+        bool mixed = false;
+        for (int j = 1; j < n; ++j) mixed |= b->its(ids ? ids[j] : j) != its0;
+        if (mixed) {
+            std::string who;
+            for (int j = 0; j < n; ++j) {
+                const int p = ids ? ids[j] : j;
+                who += (j ? ", " : "") + std::to_string(p) + ": " + std::to_string(b->its(p));
+            }
+            return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: with caller-supplied samples every listed problem must run the same number of outer "
+                         "iterations, but (problem: iterations) " + who + " — the warm-up step of a problem after its creation or reset is longer; step them in "
+                         "separate calls (the in-kernel sampler has no such restriction)");
+        }
+    }
+    CHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const size_t per = per_it * (size_t)its0;          // draws per problem (caller-supplied samples: the same for all listed problems)
+    const float* d_s = nullptr;                        // draws of the step's first problem; row j follows at j * per
+    if (samples_loc == CTK_LOC_DEVICE) d_s = samples;
+    else if (samples_loc == CTK_LOC_HOST) {
+        if ((size_t)n * per > b->samples_cap) {
+            if (b->d_samples) CHIP_TRY(b, hipFree(b->d_samples));
+            b->d_samples = nullptr; b->samples_cap = 0;
+            CHIP_TRY(b, hipMalloc((void**)&b->d_samples, (size_t)n * per * sizeof(float)));
+            b->samples_cap = (size_t)n * per;
+        }
+        CHIP_TRY(b, hipMemcpyAsync(b->d_samples, samples, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        d_s = b->d_samples;
+    }
+    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es).  Every launch attempt
+    // consumes the problem's tags, as it consumes its sequence number (cem_step: the wrap rule keeps tag 0 the never-written value)
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        const size_t z = (size_t)p;
+        const int its = b->its(p);
+        CtkCemBatchStep& q = b->h_steps[j];
+        if ((uint32_t)(b->cem_tag[z] + (uint32_t)its) < b->cem_tag[z]) b->cem_tag[z] = 1;
+        q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.tag0 = b->cem_tag[z]; q.its = its;
+        b->cem_tag[z] += (uint32_t)its;
+        q.dev_uprev = u_prev ? 0u : 1u;
+        q.samples = d_s ? d_s + (size_t)j * per : nullptr;
+        for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
+        for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
+    }
+    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkCemBatchStep), hipMemcpyHostToDevice, b->stream);
+    const RolloutArgs a = cem_batch_args(b);
+    const bool log = b->cfg.materialize_trajectories != 0;
+    const CemFusedLaunch cl{0, b->K, nullptr, 0u, b->cfg.cem_stdev_min, 1.0e8f, b->cfg.cem_initial_action_stdev,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0.5};
+    int launched = 0;                                  // consecutive launches of at most max_per_launch problems; a problem never spans launches
+    while (le == hipSuccess && launched < n) {
+        const int cnt = std::min(b->max_per_launch, n - launched);
+        le = ctk_launch_cem_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, cl, b->d_desc, b->d_steps + launched, cnt, log);
+        if (le == hipSuccess) launched += cnt;
+    }
+    // completion: every launched problem's {u, seq} store landing in its pinned slot (finish_step's bounded spin, one budget for all)
+    bool synced = false;
+    int spins = 0;
+    std::string late, timed_out;
+    for (int j = 0; j < launched; ++j) {
+        const int p = b->h_steps[j].id;
+        const uint32_t want = b->seq[(size_t)p];
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 1;
+        while (*slot != want) {
+            if (!synced && ++spins < 4000000) { __builtin_ia32_pause(); continue; }
+            if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
+            break;
+        }
+        if (*slot != want) late += (late.empty() ? "" : ", ") + std::to_string(p);
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int j = 0; j < n; ++j) {
+        const int p = b->h_steps[j].id;
+        const size_t z = (size_t)p;
+        ++b->seq[z];                                   // every launch attempt consumes its sequence number (guarded())
+        if (j >= launched) continue;
+        ++b->count[z]; b->idx_stale[z] = 1;            // as cem_step: with the launch
+        if (reinterpret_cast<volatile uint32_t*>(b->slot(p))[1] != b->h_steps[j].seq) continue;   // never published (a device fault): finish_step
+        ++b->call[z];                                  // returns before it advances the Philox position or reads u
+        volatile float* sl = reinterpret_cast<volatile float*>(b->slot(p));
+        if (u_out) {
+            u_out[(size_t)j * b->C] = sl[0];
+            for (int c = 1; c < b->C; ++c) u_out[(size_t)j * b->C + c] = sl[4 + c];   // publish_u_vec
+        }
+        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;
+        if (errw[0]) { errw[0] = 0; timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(p); }
+    }
+    if (le != hipSuccess) return cfail(b, CTK_ERR_HIP, std::string("ctk_cem_batch_step: ") + hipGetErrorString(le));
+    if (!late.empty()) return cfail(b, CTK_ERR_HIP, "ctk_cem_batch_step: the step finished without publishing the result of problem(s) " + late);
+    if (!timed_out.empty())
+        return cfail(b, CTK_ERR_STATE, "ctk_cem_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; the other problems' outputs are valid and written");
+    return CTK_OK;
+}
+
+int ctk_cem_batch_reset(ctk_cem_batch* b, int n_ids, const int32_t* ids) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = cem_batch_ids(b, "ctk_cem_batch_reset", n_ids, ids, &n)) return rc;
+    CHIP_TRY(b, hipSetDevice(b->cfg.device));
+    std::vector<float> mu((size_t)b->HC), sd((size_t)b->HC), zero((size_t)b->C, 0.0f);
+    cem_batch_initial(b, mu.data(), sd.data());
+    for (int j = 0; j < n; ++j) {                      // ctk_reset of a CEM handle: parameters, tags and the Philox position stay
+        const int p = ids ? ids[j] : j;
+        b->count[(size_t)p] = 0;
+        CHIP_TRY(b, hipMemcpyAsync(b->mu(p), mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        CHIP_TRY(b, hipMemcpyAsync(b->sd(p), sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        CHIP_TRY(b, hipMemcpyAsync(b->u(p), zero.data(), zero.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    }
+    CHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+int ctk_cem_batch_read(ctk_cem_batch* b, int problem, int buffer, float* dst, size_t cap) {
+    if (!b || !dst) return b ? cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: NULL destination") : CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = cem_batch_problem(b, "ctk_cem_batch_read", problem)) return rc;
+    const size_t z = (size_t)problem, N = (size_t)b->N;
+    const float* src = nullptr; size_t n = 0; bool is_int = false;
+    switch (buffer) {
+        case CTK_BUF_Q: src = b->d_Q + z * N * b->HC; n = N * b->HC; break;
+        case CTK_BUF_J: src = b->d_J + z * N; n = N; break;
+        case CTK_BUF_TRAJ:
+            if (!b->d_traj) return cfail(b, CTK_ERR_STATE, "ctk_cem_batch_read: trajectories not materialised (cfg.materialize_trajectories == 0)");
+            n = N * ((size_t)b->H + 1) * b->S; src = b->d_traj + z * n; break;
+        case CTK_BUF_U_NOM: src = b->mu(problem); n = (size_t)b->HC; break;
+        case CTK_BUF_STD: src = b->sd(problem); n = (size_t)b->HC; break;
+        case CTK_BUF_BEST_IDX: src = reinterpret_cast<const float*>(b->d_idx + z * N); n = (size_t)b->K; is_int = true; break;
+        default: return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: a CEM batch has Q, J, TRAJ, U_NOM, STD and BEST_IDX");
+    }
+    if (cap < n) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: destination too small (" + std::to_string(n) + " floats)");
+    CHIP_TRY(b, hipSetDevice(b->cfg.device));
+    if (is_int && b->idx_stale[z]) {   // the sorted elite indices are materialised from the last iteration's costs (locate_buffer)
+        CHIP_TRY(b, ctk_launch_select_topk(b->stream, b->d_J + z * N, b->N, b->K, b->d_idx + z * N));
+        b->idx_stale[z] = 0;
+    }
+    CHIP_TRY(b, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    CHIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (is_int) for (size_t i = 0; i < n; ++i) { int v; std::memcpy(&v, &dst[i], 4); dst[i] = (float)v; }
+    return CTK_OK;
+}
+
+int ctk_cem_batch_get_state(ctk_cem_batch* b, int problem, float* dst, size_t cap) {
+    if (!b || !dst) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = cem_batch_problem(b, "ctk_cem_batch_get_state", problem)) return rc;
+    const size_t HC = (size_t)b->HC;
+    if (cap < 2 * HC + b->C + 1) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_get_state: destination too small");
+    CHIP_TRY(b, hipSetDevice(b->cfg.device));
+    CHIP_TRY(b, hipMemcpyAsync(dst, b->mu(problem), HC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    CHIP_TRY(b, hipMemcpyAsync(dst + HC, b->sd(problem), HC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    CHIP_TRY(b, hipMemcpyAsync(dst + 2 * HC, b->u(problem), (size_t)b->C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    CHIP_TRY(b, hipStreamSynchronize(b->stream));
+    dst[2 * HC + b->C] = (float)b->count[(size_t)problem];
+    return CTK_OK;
+}
+
+int ctk_cem_batch_set_state(ctk_cem_batch* b, int problem, const float* src, size_t n) {
+    if (!b || !src) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = cem_batch_problem(b, "ctk_cem_batch_set_state", problem)) return rc;
+    const size_t HC = (size_t)b->HC;
+    if (n != 2 * HC + b->C + 1) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_set_state: wrong state size");
+    CHIP_TRY(b, hipSetDevice(b->cfg.device));
+    CHIP_TRY(b, hipMemcpyAsync(b->mu(problem), src, HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    CHIP_TRY(b, hipMemcpyAsync(b->sd(problem), src + HC, HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    CHIP_TRY(b, hipMemcpyAsync(b->u(problem), src + 2 * HC, (size_t)b->C * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    b->count[(size_t)problem] = (int)src[2 * HC + b->C];
+    CHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+int ctk_cem_batch_set_param(ctk_cem_batch* b, int id, float value) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (id < 0 || id >= env_info(b->env)->n_params) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_set_param: unknown parameter id for this environment");
+    b->params[id] = value;                             // every launch derives its constants from the table (Env<>::derive, as a handle's launch does)
+    return CTK_OK;
+}
+
+int ctk_cem_batch_get_param(const ctk_cem_batch* b, int id, float* value) {
+    if (!b || !value || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->params[id];
+    return CTK_OK;
+}
+
+int ctk_cem_batch_rng_get_position(const ctk_cem_batch* b, int problem, uint32_t* call) {
+    if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *call = b->call[(size_t)problem];
+    return CTK_OK;
+}
+
+int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = cem_batch_problem(b, "ctk_cem_batch_rng_set_position", problem)) return rc;
+    b->call[(size_t)problem] = call;
+    return CTK_OK;
+}
+
+}  // extern "C"

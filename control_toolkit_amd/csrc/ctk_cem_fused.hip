@@ -23,15 +23,25 @@
 // ctk_select_topk from those costs (ctk_api.hip: locate_buffer).
 // Every wait is bounded by a wall clock; on expiry the error word behind {u, seq} is raised (ctk_api.hip:finish_step ->
 // CTK_ERR_STATE) — never a silently wrong result.
+// include/ctk_hip.h gives the batch's opaque C type the name ctk_cem_batch; in C++ a type and a template cannot share a name in one scope,
+// and the kernel template below carries that name (it is what a kernel trace prints).  This translation unit never touches the C type, so
+// the header's declarations see it under another name here.  (A different struct TAG in the header would not help: the typedef name itself is
+// what collides.)  Whoever needs the C type in this file must move the code that does into ctk_api.hip; the guard below keeps a second
+// definition of the name, from any header added here later, from passing silently.
+#ifdef ctk_cem_batch
+#error "ctk_cem_batch is already a macro: the renaming below would hide it"
+#endif
+#define ctk_cem_batch ctk_cem_batch_opaque
 #include "ctk_rollout.h"
 #include "ctk_env.h"
 #include "ctk_launch.h"
+#undef ctk_cem_batch
 
 #ifdef CTK_CEM_STAMPS   // diagnostic build (tools/diag_cem_fused.hip); never compiled into libctk_hip.so
 #define CSTAMP(i)                                                                                  \
     do {                                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                         \
-        if (threadIdx.x == 0 && a.stamps) a.stamps[(blockIdx.x * 8 + it) * 16 + (i)] = wall_clock64(); \
+        if (threadIdx.x == 0 && a.stamps) a.stamps[(bx * 8 + it) * 16 + (i)] = wall_clock64(); \
         __builtin_amdgcn_sched_barrier(0);                                                         \
     } while (0)
 #else
@@ -192,322 +202,60 @@ __global__ __launch_bounds__(CF_BLOCK) void ctk_cem_fused(const float* __restric
     constexpr int C = E::C, S = E::S;
     extern __shared__ float lds[];
     RolloutArgs a = a_in;
-    // Hs steps; H = Hs*C flat (step, input) columns of a plan = sample columns of a row (a.P): one sample per step and input
-    const int N = a.N, Hs = a.H, H = Hs * C, ts = tile_stride(a.P), us = (H + 1) | 1, rs = 1 + 2 * H;
-    const CemCarve cv = cem_carve(N, H, cf.nblk);
-    float* tiles[2] = {lds + cv.tile0, lds + cv.tile1};
-    float* ubuf = lds + cv.ubuf;
-    float* cin_s = lds + cv.cin;
-    float* mu_s = lds + cv.mu;
-    float* sd_s = lds + cv.sd;
-    uint32_t* keys = reinterpret_cast<uint32_t*>(lds + cv.keys);
-    float* recs = lds + cv.recs;
-    double* part = reinterpret_cast<double*>(lds + cv.part);
-    int* hist = reinterpret_cast<int*>(lds + cv.hist);
-    int* sel = reinterpret_cast<int*>(lds + cv.misc);            // [0] prefix (as bits) [1] want
-    int* nb_s = reinterpret_cast<int*>(lds + cv.misc) + 8;
-    int* erow = reinterpret_cast<int*>(lds + cv.misc) + 16;       // [64] this workgroup's elite rows, ascending
-    uint32_t* red = reinterpret_cast<uint32_t*>(lds + cv.misc) + 80;   // [2][CF_WAVES]
-    auto red_min = [&](int row) { uint32_t v = 0xFFFFFFFFu;
-#pragma unroll
-        for (int w = 0; w < CF_WAVES; ++w) v = min(v, red[row * CF_WAVES + w]);
-        return v; };
-    auto red_sum = [&](int row) { uint32_t v = 0u;
-#pragma unroll
-        for (int w = 0; w < CF_WAVES; ++w) v += red[row * CF_WAVES + w];
-        return v; };
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int row0 = blockIdx.x * CF_TRAJ;
-    const int n = row0 + lane;
-    const bool valid = n < N;                                     // wave 0: lane = row of the workgroup
-    float up0[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) up0[c] = a.u_prev_dev ? a.u_prev_dev[c] : a.u_prev[c];
-    bool expired = false;
+    const float* mid = cf.mid;
+    const uint32_t bx = blockIdx.x;                // unsigned, as blockIdx.x is: the body's index arithmetic keeps its types
+#include "ctk_cem_body.inc"
+}
 
-    for (int h = t; h < H; h += CF_BLOCK) { mu_s[h] = cf.mu[h]; sd_s[h] = cf.sd[h]; }
-    a.stream_id = 0;
-    cem_fetch_tile(tiles[0], samples, a, row0, t, CF_BLOCK);
-    __syncthreads();
-
-    for (int it = 0; it < cf.its; ++it) {
-        const bool last_it = it + 1 == cf.its;
-        const uint32_t tag = cf.tag0 + (uint32_t)it;
-        float* tile = tiles[it & 1];
-        CSTAMP(0);
-        // ---- 1. rollout ---------------------------------------------------------------------------------------------
-        auto prepare = [&](int ptraj, int hbeg, int hend) {
-            const float* my = tile + ptraj * ts;
-            auto input_at = [&](int h, int c) { return fminf(fmaxf(mu_s[h * C + c] + my[h * C + c] * sd_s[h * C + c], a.lo[c]), a.hi[c]); };   // :64-66
-            float cin = 0.0f;
-            float uprev[C];
+// ---------------------------------------------------------------------------------------------
+// The BATCH form (include/ctk_hip.h: ctk_cem_batch_*): B independent CEM problems of one configuration in ONE launch — the same statements
+// (ctk_cem_body.inc) around per-problem operands.  Grid (workgroups per problem, problems of this launch): blockIdx.y picks the step
+// record, the record's id the problem's descriptor (ctk_launch.h: CtkCemBatchStep / CtkCemBatchDesc, both in device memory; blockIdx.y is
+// uniform, so both are read with scalar loads, as a launched kernel reads its kernarg segment).  The prologue rebuilds from them what
+// ctk_cem_fused takes as arguments (samples, a, cf); what the problems share stays by value (a_tpl, k, cf_tpl).  The leading arguments are
+// the dwords the first loads depend on (the two tables, then the sizes the LDS carve and the tile fetch need): they are the preloaded ones.
+//
+// PROGRESS.  Every workgroup of a problem waits, twice per outer iteration, for ALL workgroups of that problem (ll_gather over llJ / llS),
+// and for no workgroup of another problem: each problem has its own hand-off words and its own tags.  A problem therefore makes progress
+// exactly when its nblk workgroups are resident at the same time.  ctk_cem_fused guarantees that by nblk <= CTK_CEM_FUSED_MAX_BLOCKS <=
+// CUs and LDS <= 128 KiB: a CU without a workgroup of this kernel admits one, so while a workgroup is still pending fewer than nblk are
+// resident, some CU holds none, and the pending one is placed.  The host keeps the same guarantee for a launch of this kernel
+// (ctk_api.hip: ctk_cem_batch_create): problems * nblk <= CUs.  While any workgroup of the launch is pending fewer than CUs workgroups are
+// resident, so some CU holds none and admits it — whatever the dispatch order or placement, all workgroups of the launch become
+// co-resident, and with them all workgroups of every problem.  Problems of one launch may loop a different number of times (its is per
+// record): a problem that finishes early only frees CUs.  Like the single kernel's, the argument assumes that the CUs are this launch's
+// to take while it is placed: a kernel of another process on a shared card, or of this process on another stream (a ctk_select_topk of a
+// BEST_IDX read runs on the batch's own stream, behind the step), can hold CUs and delay a workgroup.  That case is not excluded, it is
+// covered: every wait stays bounded by the wall clock (ll_gather), and one that runs out raises the error word of ITS problem's pinned
+// slot (CTK_ERR_STATE naming the problem) — never a hang, never a silently wrong result.
+// ---------------------------------------------------------------------------------------------
+template <int ENV, bool WTRAJ>
+__global__ __launch_bounds__(CF_BLOCK) void ctk_cem_batch(const CtkCemBatchDesc* __restrict__ desc, const CtkCemBatchStep* __restrict__ steps,
+                                                          int N_, int H_, int P_, uint32_t pmagic_, int nblk_, int K_, RolloutArgs a_tpl,
+                                                          typename Env<ENV>::K k, CemFusedK cf_tpl) {
+    using E = Env<ENV>;
+    constexpr int C = E::C, S = E::S;
+    extern __shared__ float lds[];
+    const CtkCemBatchStep& q = steps[blockIdx.y];
+    const CtkCemBatchDesc& d = desc[q.id];
+    RolloutArgs a = a_tpl;                         // limits, inv_Hp1, global_row0 (launcher)
+    a.N = N_; a.H = H_; a.P = P_; a.p_magic = pmagic_;
 #pragma unroll
-            for (int c = 0; c < C; ++c) uprev[c] = (hbeg == 0 || hbeg >= Hs) ? up0[c] : input_at(hbeg - 1, c);
-#pragma unroll 2
-            for (int h = hbeg; h < hend; ++h) {
-                float u[C];
+    for (int i = 0; i < S; ++i) a.s0[i] = q.s[i];
 #pragma unroll
-                for (int c = 0; c < C; ++c) u[c] = input_at(h, c);
-                cin += E::input_cost(k, u, uprev);
-#pragma unroll
-                for (int c = 0; c < C; ++c) { uprev[c] = u[c]; ubuf[ptraj * us + h * C + c] = u[c]; }
-            }
-            return cin;
-        };
-        const int S1 = min(Hs, 16), Ha = (S1 + CF_WAVES - 1) / CF_WAVES;
-        const float cin_a = prepare(lane, min(S1, wave * Ha), min(S1, wave * Ha + Ha));
-        if (wave == 0) cin_s[lane] = cin_a;
-        __syncthreads();
-        CSTAMP(1);
-        const float* myu = ubuf + lane * us;
-        float sx[S];
-#pragma unroll
-        for (int i = 0; i < S; ++i) sx[i] = a.s0[i];
-        float csum = 0.0f, amax = 0.0f;
-        float* traj = nullptr;
-        if constexpr (WTRAJ) {
-            if (a.traj_out && last_it) traj = a.traj_out + (size_t)n * (Hs + 1) * S;
-        }
-        const bool single = E::fast_ok(k);
-        if (wave == 0) {
-            if (single) recur_env_range<ENV, WTRAJ, true, true>(k, traj, valid, myu, 0, S1, sx, csum, amax);
-        } else {
-            const int Hb = (Hs - S1 + CF_WAVES - 2) / (CF_WAVES - 1);
-            cin_s[wave * CF_TRAJ + lane] = cin_a + prepare(lane, min(Hs, S1 + (wave - 1) * Hb), min(Hs, S1 + (wave - 1) * Hb + Hb));
-        }
-        __syncthreads();
-        if (wave == 0) {
-            float J = 0.0f;
-            if (single) {
-                recur_env_range<ENV, WTRAJ, true, true>(k, traj, valid, myu, S1, Hs, sx, csum, amax);
-                if constexpr (WTRAJ) {
-                    if (valid && traj) store_state<S>(traj + (size_t)Hs * S, sx);
-                }
-                J = csum + E::terminal_cost(k, sx);
-            }
-            if (!single || __builtin_expect(__builtin_amdgcn_ballot_w64(E::out_of_range(amax)) != 0, 0)) {
-#pragma unroll
-                for (int i = 0; i < S; ++i) sx[i] = a.s0[i];
-                csum = 0.0f;
-                recur_env_range<ENV, WTRAJ, false, true>(k, traj, valid, myu, 0, Hs, sx, csum, amax);
-                if constexpr (WTRAJ) {
-                    if (valid && traj) store_state<S>(traj + (size_t)Hs * S, sx);
-                }
-                J = csum + E::terminal_cost(k, sx);
-            }
-            float cin = 0.0f;
-#pragma unroll
-            for (int w = 0; w < CF_WAVES; ++w) cin += cin_s[w * CF_TRAJ + lane];
-            J += cin;
-            J *= a.inv_Hp1;
-            CSTAMP(2);
-            if (valid) {
-                ll_st(cf.llJ + n, f32_sortable(J), tag);          // ---- 2. hop 1: publish
-                if (last_it) a.J[n] = J;
-            }
-        } else {
-            const int tsub = t - 64, nsub = CF_BLOCK - 64;
-            if (last_it && a.Q_out) {                             // the plans, coalesced (ctk_read / logging)
-                const int total = max(0, min(CF_TRAJ, N - row0)) * H;
-                float* dst = a.Q_out + (size_t)row0 * H;
-                for (int i = tsub; i < total; i += nsub) {
-                    const int r = H >= 2 ? (int)__umulhi((uint32_t)i, a.p_magic) : i;
-                    dst[i] = ubuf[r * us + (i - r * H)];
-                }
-            }
-            if (!last_it) {                                       // next iteration's samples: independent of mu / std
-                RolloutArgs an = a;
-                an.stream_id = (uint32_t)(it + 1);
-                cem_fetch_tile(tiles[(it + 1) & 1], samples ? samples + (size_t)cf.per_it * (it + 1) : nullptr, an, row0, tsub, nsub);
-            }
-        }
-        // all N costs into LDS (waves 1..3 start polling while wave 0 still runs the recurrence); their range on the way
-        uint32_t kmin_t = 0xFFFFFFFFu, kmax_t = 0u;
-        expired |= ll_gather(cf.llJ, N, tag, t, CF_BLOCK, cf.timeout_ticks, [&](int i, uint32_t v) {
-            keys[i] = v; kmin_t = min(kmin_t, v); kmax_t = max(kmax_t, v);
-        });
-        CSTAMP(3);
-        kmin_t = wave_min_u32(kmin_t);
-        kmax_t = ~wave_min_u32(~kmax_t);
-        if (lane == 0) { red[wave] = kmin_t; red[CF_WAVES + wave] = ~kmax_t; }
-        __syncthreads();
-        const uint32_t kbase = red_min(0);
-        const uint32_t krange = ~red_min(1) - kbase;
-        if (t == 0) { sel[0] = 0; sel[1] = cf.K; }
-
-        // ---- 3. K-th smallest key: MSB-first radix select over d = key - kbase, 8 bits per pass.  Only the bits the range
-        //      needs are walked, and the first digit buckets the costs LINEARLY over [min, max] (the raw top bits of a float are
-        //      nearly constant over a population's costs: every key in one bin serialises the LDS atomics).  (Compacting the first
-        //      pass's bucket and ranking its keys by brute force instead of the later passes was measured: slower, 4.0 vs 3.0 us.)
-        const int nbits = 32 - __builtin_clz(krange | 1u);
-        const int passes = (nbits + 7) >> 3;
-        for (int pass = 0; pass < passes; ++pass) {
-            const int hi = nbits - 8 * pass, lo = max(hi - 8, 0);   // this pass's digit = bits [lo, hi) of d: the first one is full
-            const uint32_t dmask = (1u << (hi - lo)) - 1u;
-            if (t < 256) hist[t] = 0;
-            __syncthreads();
-            const uint32_t prefix = (uint32_t)sel[0];
-            const int want = sel[1];
-            for (int j0 = t; j0 < N; j0 += CF_BLOCK * CF_CHUNK) { // unconditional LDS reads in flight (keys[] is padded), then the counting
-                uint32_t dj[CF_CHUNK];
-#pragma unroll
-                for (int u = 0; u < CF_CHUNK; ++u) dj[u] = keys[j0 + u * CF_BLOCK] - kbase;
-#pragma unroll
-                for (int u = 0; u < CF_CHUNK; ++u) {
-                    const bool act = (j0 + u * CF_BLOCK < N) & (pass == 0 || (dj[u] >> hi) == prefix);
-                    if (act) atomicAdd(&hist[(dj[u] >> lo) & dmask], 1);
-                }
-            }
-            __syncthreads();
-            if (pass == 0) CSTAMP(9);
-            if (wave == 0) {
-                const int b0 = hist[4 * lane], b1 = hist[4 * lane + 1], b2 = hist[4 * lane + 2], b3 = hist[4 * lane + 3];
-                const int c = b0 + b1 + b2 + b3;
-                // inclusive prefix over the 64 lanes: DPP row shifts inside each row of 16, then the three row totals
-                int inc = c;
-                inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, true);   // row_shr:1, zero fill
-                inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, true);   // row_shr:2
-                inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, true);   // row_shr:4
-                inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, true);   // row_shr:8
-                const int r0 = __builtin_amdgcn_readlane(inc, 15), r1 = __builtin_amdgcn_readlane(inc, 31), r2 = __builtin_amdgcn_readlane(inc, 47);
-                inc += lane >= 48 ? r0 + r1 + r2 : (lane >= 32 ? r0 + r1 : (lane >= 16 ? r0 : 0));
-                const unsigned long long hit = __builtin_amdgcn_ballot_w64(inc >= want);
-                const int first = hit ? __builtin_ctzll(hit) : 64;   // hit != 0: the histogram holds >= want keys
-                if (lane == first) {
-                    int below = inc - c, dgt = 4 * lane, bsel = b0;
-                    if (below + b0 >= want) { dgt += 0; }
-                    else if (below + b0 + b1 >= want) { below += b0; dgt += 1; bsel = b1; }
-                    else if (below + b0 + b1 + b2 >= want) { below += b0 + b1; dgt += 2; bsel = b2; }
-                    else { below += b0 + b1 + b2; dgt += 3; bsel = b3; }
-                    sel[0] = (int)((prefix << (hi - lo)) | (uint32_t)dgt);
-                    sel[1] = want - below;
-                    sel[2] = bsel;                                // keys in the chosen bin (last pass: keys == the K-th smallest)
-                }
-            }
-            __syncthreads();
-            if (pass == 0) CSTAMP(10);
-            if (pass == 1) CSTAMP(11);
-        }
-        CSTAMP(4);
-        const uint32_t T32 = kbase + (uint32_t)sel[0];            // the K-th smallest key
-        const int r_ties = sel[1];                                // of the keys == T32, the first r_ties in index order are elite
-        // ties in front of this workgroup's rows — only when the cut falls INSIDE a group of equal keys (workgroup-uniform)
-        const bool cut_in_tie = sel[2] != r_ties;
-        __syncthreads();                                          // red[] (the range) and sel[] have been read by everyone
-        if (cut_in_tie) {
-            int tb = 0;
-            for (int j = t; j < min(row0, N); j += CF_BLOCK) tb += keys[j] == T32;
-            tb = (int)wave_sum((float)tb);                        // exact: < 2^24
-            if (lane == 0) red[wave] = (uint32_t)tb;
-        } else if (lane == 0) red[wave] = 0u;
-        __syncthreads();
-        const int ties_before = (int)red_sum(0);
-        if (wave == 0) {
-            const uint32_t ki = valid ? keys[n] : 0xFFFFFFFFu;
-            const bool tie = valid && ki == T32;
-            const unsigned long long tm = __builtin_amdgcn_ballot_w64(tie);
-            const int my_tie_rank = ties_before + __builtin_popcountll(tm & ((1ull << lane) - 1ull));
-            const bool elite = valid && (ki < T32 || (tie && my_tie_rank < r_ties));
-            const unsigned long long em = __builtin_amdgcn_ballot_w64(elite);
-            if (elite) erow[__builtin_popcountll(em & ((1ull << lane) - 1ull))] = lane;
-            if (lane == 0) nb_s[0] = __builtin_popcountll(em);
-        }
-        __syncthreads();
-
-        CSTAMP(5);
-        // ---- 4. local moments of the elite rows, hop 2 --------------------------------------------------------------
-        const int nb = nb_s[0];
-        unsigned long long* myrec = cf.llS + (size_t)blockIdx.x * rs;
-        if (t == 0) ll_st(myrec, (uint32_t)nb, tag);
-        for (int h = t; h < H; h += CF_BLOCK) {
-            const double mu0 = (double)mu_s[h];
-            double s1 = 0.0, s2 = 0.0;
-#pragma unroll 4
-            for (int e = 0; e < nb; ++e) { const double d = (double)ubuf[erow[e] * us + h] - mu0; s1 += d; s2 = fma(d, d, s2); }
-            const double mb = nb > 0 ? s1 / (double)nb : 0.0;
-            const double m2 = fma(-mb, s1, s2);                   // sum (d - m_b)^2 = s2 - s1^2 / n_b
-            ll_st(myrec + 1 + h, __builtin_bit_cast(uint32_t, (float)mb), tag);
-            ll_st(myrec + 1 + H + h, __builtin_bit_cast(uint32_t, (float)(m2 > 0.0 ? m2 : 0.0)), tag);
-        }
-        CSTAMP(6);
-        expired |= ll_gather(cf.llS, cf.nblk * rs, tag, t, CF_BLOCK, cf.timeout_ticks,
-                             [&](int i, uint32_t v) { reinterpret_cast<uint32_t*>(recs)[i] = v; });
-        __syncthreads();
-
-        CSTAMP(7);
-        // ---- 5. refit (:77-78; population std): A = sum n_b m_b, B = sum (M2_b + n_b m_b^2) in double, in a fixed order (segments of the
-        //      workgroup range, then the segments): every workgroup arrives at the same bits.  One pass, one barrier.
-        //      (One thread per column walking all workgroups: 4.4 us at cfg3.)
-        {
-            constexpr int SEGMAX = 16;
-            const double invK = 1.0 / (double)cf.K;               // == 1 / sum_b n_b: the elite set has exactly K rows
-            const int* nrec = reinterpret_cast<const int*>(recs);
-            auto add_rec = [&](int bq, int h, double& A, double& B) {
-                const double nbq = (double)nrec[bq * rs], mb = (double)recs[bq * rs + 1 + h];
-                A = fma(nbq, mb, A);
-                B += (double)recs[bq * rs + 1 + H + h] + nbq * mb * mb;
-            };
-            auto finish = [&](int h, double A, double B) {
-                const double mshift = A * invK;
-                const double var = fma(-mshift, mshift, B * invK);
-                mu_s[h] = (float)((double)mu_s[h] + mshift);
-                sd_s[h] = (float)sqrt(var > 0.0 ? var : 0.0);     // tf.math.reduce_std: ddof = 0
-            };
-            const bool multi = H <= CF_BLOCK && cf.nblk > 8;      // few workgroups: the plain walk is shorter than the barrier
-            const int SEG = multi ? min(SEGMAX, CF_BLOCK / H) : 1, per = (cf.nblk + SEG - 1) / SEG;
-            if (multi) {
-                const int hcol = t % H, sg = t / H;
-                if (sg < SEG) {
-                    double A = 0.0, B = 0.0;
-                    const int bb = sg * per, be = min(cf.nblk, bb + per);
-                    for (int bq = bb; bq < be; ++bq) add_rec(bq, hcol, A, B);
-                    part[(sg * H + hcol) * 2] = A; part[(sg * H + hcol) * 2 + 1] = B;
-                }
-                __syncthreads();
-                if (t < H) {
-                    double A = 0.0, B = 0.0;
-                    for (int q = 0; q < SEG; ++q) { A += part[(q * H + t) * 2]; B += part[(q * H + t) * 2 + 1]; }
-                    finish(t, A, B);
-                }
-            } else {
-                for (int h = t; h < H; h += CF_BLOCK) {
-                    double A = 0.0, B = 0.0;
-                    for (int bq = 0; bq < cf.nblk; ++bq) add_rec(bq, h, A, B);
-                    finish(h, A, B);
-                }
-            }
-        }
-        __syncthreads();
-        CSTAMP(8);
-
-        if (last_it) {
-            // u = elite[0,0,:] (:101): first input of the cheapest row under (J, index), published by its owner
-            const uint32_t gk = kbase;                            // the cheapest cost's key (this iteration's range, above)
-            int best = 0x7FFFFFFF;
-            for (int j = t; j < N; j += CF_BLOCK)
-                if (keys[j] == gk) { best = j; break; }           // j ascending per thread: its smallest match
-            best = (int)wave_min_u32((uint32_t)best);
-            __syncthreads();                                      // red[] is read above by everyone
-            if (lane == 0) red[wave] = (uint32_t)best;
-            __syncthreads();
-            const int gbest = (int)red_min(0);
-            if (t == 0 && gbest >= row0 && gbest < row0 + CF_TRAJ) {
-                cf.idx_out[0] = gbest;
-                if (expired) __hip_atomic_store(reinterpret_cast<uint32_t*>(cf.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if constexpr (C == 1) publish_u(cf.u_dev, cf.u_host, ubuf[(gbest - row0) * us], cf.seq);
-                else publish_u_vec(cf.u_dev, cf.u_host, ubuf + (gbest - row0) * us, C, cf.seq);
-            }
-            // :99-102 clip the std, shift both by one step, refill the tail — the handle's distribution for the next MPC step
-            if (blockIdx.x == 0) {
-                for (int h = t; h < H; h += CF_BLOCK) {
-                    cf.mu[h] = (h + C < H) ? mu_s[h + C] : cf.mid[h - (H - C)];      // shift by one STEP = C columns
-                    cf.sd[h] = (h + C < H) ? fminf(fmaxf(sd_s[h + C], cf.std_min), cf.std_max) : cf.init_std;
-                }
-            }
-        }
-    }
-    // a wait that ran out in a workgroup that does not own the best row still has to reach the host
-    if (expired && t == 0) __hip_atomic_store(reinterpret_cast<uint32_t*>(cf.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (int c = 0; c < C; ++c) a.u_prev[c] = q.u_prev[c];
+    a.u_prev_dev = q.dev_uprev ? d.u_dev : nullptr;
+    a.J = d.J; a.Q_out = d.Q_out; a.traj_out = d.traj_out;
+    a.seed_lo = d.seed_lo; a.seed_hi = d.seed_hi; a.call = q.call;
+    const float* samples = q.samples;
+    CemFusedK cf = cf_tpl;                         // per_it, std_min / std_max / init_std, mid[], timeout_ticks (launcher)
+    cf.nblk = nblk_; cf.K = K_;
+    cf.its = q.its; cf.tag0 = q.tag0; cf.seq = q.seq;
+    cf.llJ = d.ll; cf.llS = d.ll + N_;
+    cf.mu = d.mu; cf.sd = d.sd; cf.u_dev = d.u_dev; cf.u_host = d.u_host; cf.idx_out = d.idx_out;
+    const float* mid = cf_tpl.mid;                 // shared by value: read where the kernel argument lies
+    const uint32_t bx = blockIdx.x;                // unsigned, as blockIdx.x is: the body's index arithmetic keeps its types
+#include "ctk_cem_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -541,6 +289,37 @@ hipError_t ctk_launch_cem_fused(hipStream_t st, int env, const float* params, fl
         cf.timeout_ticks = (unsigned long long)(c.timeout_s * 1.0e8);
         const size_t lds = ctk_cem_fused_lds(a.N, HC);
         ctk_with_bool(log, [&](auto log_c) { CTK_LAUNCH((ctk_cem_fused<EV, decltype(log_c)::value>), grid, block, lds, st, e0, e1, samples, a, k, cf); });
+    });
+    return hipGetLastError();
+}
+
+const char* ctk_cem_batch_name(int env, bool log) {
+    return ctk_kernel_name("ctk_cem_batch<%d, %4$s>", env, 0, 0, log ? "true" : "false");
+}
+
+// n_problems step records from steps_dev on, as ONE launch of grid (workgroups per problem, n_problems); the caller keeps
+// n_problems * workgroups per problem within the device's CU count (the progress argument above the kernel)
+hipError_t ctk_launch_cem_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a_in, const CemFusedLaunch& c,
+                                const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* steps_dev, int n_problems, bool log) {
+    const int nblk = ctk_cem_fused_blocks(a_in.N);
+    if (n_problems < 1 || nblk > CTK_CEM_FUSED_MAX_BLOCKS) return hipErrorInvalidValue;
+    const dim3 grid(nblk, n_problems), block(CF_BLOCK);
+    CTK_FOR_ENV(env, EV, {
+        using E = Env<EV>;
+        const int HC = a_in.H * E::C;
+        const RolloutArgs a = ctk_rollout_args(a_in, E::C, HC);
+        const typename E::K k = E::derive(params, dt, isteps);
+        CemFusedK cf{};                                // its, tag0, seq and every pointer come from the records and descriptors
+        cf.K = c.K; cf.nblk = nblk; cf.per_it = (unsigned long long)a.N * HC;
+        cf.std_min = c.std_min; cf.std_max = c.std_max; cf.init_std = c.init_std;
+        for (int i = 0; i < E::C; ++i) cf.mid[i] = 0.5f * (a.lo[i] + a.hi[i]);
+        cf.timeout_ticks = (unsigned long long)(c.timeout_s * 1.0e8);
+        const size_t lds = ctk_cem_fused_lds(a.N, HC);
+        if (lds > 128 * 1024) return hipErrorInvalidValue;
+        ctk_with_bool(log, [&](auto log_c) {
+            hipLaunchKernelGGL((ctk_cem_batch<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.N, a.H, a.P, a.p_magic, nblk,
+                               c.K, a, k, cf);
+        });
     });
     return hipGetLastError();
 }

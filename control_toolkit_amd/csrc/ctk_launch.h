@@ -283,6 +283,39 @@ const char* ctk_cem_fused_name(int env, bool log);
 hipError_t ctk_launch_cem_fused(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const float* samples,
                                 const CemFusedLaunch& c, bool log, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
+// the BATCH form of the same step (ctk_cem_fused.hip: ctk_cem_batch<ENV, TRAJ>; include/ctk_hip.h: ctk_cem_batch_*): B independent problems of
+// ONE configuration, grid (workgroups per problem, problems of this launch).  As for ctk_mppi_batch, what differs per problem reaches the
+// kernel through two arrays in device memory: the descriptor [B] (the problem's buffers; written once, at creation) and the step records
+// [problems of this step] (written by the host into pinned memory, ONE transfer ahead of the launches).
+struct CtkCemBatchDesc {
+    unsigned long long* ll;             // ctk_cem_fused_ll_words(N, H*C) hand-off words of THIS problem, zero at allocation
+    float* mu; float* sd;               // [H*C] the problem's distribution, in / out
+    float* J;                           // [N]
+    float* Q_out;                       // [N,H,C]
+    float* traj_out;                    // [N,H+1,S] or nullptr
+    float* u_dev;                       // [C] the problem's own last output
+    float* u_host;                      // pinned {u, seq} slot (16 floats) with the error words behind it
+    int* idx_out;                       // [N] idx_out[0] = the cheapest row (BEST_IDX is materialised on demand)
+    uint32_t seed_lo, seed_hi;          // Philox key
+};
+struct CtkCemBatchStep {
+    int32_t id;                         // problem index = descriptor index
+    uint32_t seq;                       // published with u
+    uint32_t call;                      // Philox position
+    uint32_t tag0;                      // hand-off tags tag0 .. tag0 + its - 1 (per problem: consecutive across its steps, never 0)
+    int32_t its;                        // outer iterations of THIS problem's step (warm-up or cem_outer_it)
+    uint32_t dev_uprev;                 // 1: the previous input is the problem's own last output (u_prev == NULL at the API)
+    const float* samples;               // this problem's draws [its,N,H,C] (device pointer) or nullptr: the in-kernel sampler
+    float s[CTK_MAX_STATES];
+    float u_prev[CTK_MAX_INPUTS];
+};
+const char* ctk_cem_batch_name(int env, bool log);
+// c: K, the std constants and timeout_s only (its / tag0 / seq and the pointers are the records' and descriptors'); a: the shared template
+hipError_t ctk_launch_cem_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const CemFusedLaunch& c,
+                                const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* steps_dev, int n_problems, bool log);
+int ctk_cem_fused_blocks(int N);        // workgroups of a problem (64 rollouts each)
+size_t ctk_cem_fused_lds(int N, int H); // dynamic LDS of a launch, bytes
+
 // ---- ctk_rpgd.hip ---------------------------------------------------------------------------
 const char* ctk_rpgd_descent_name(int pred, int N, int H = 0);
 bool ctk_rpgd_uses_persistent(int pred, int N, int H);   // the whole descent as one launch: producers + resident Jacobian workers

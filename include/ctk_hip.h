@@ -518,6 +518,53 @@ int ctk_problem_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, c
 int ctk_problem_get_param(const ctk_batch* b, int problem, int id, float* value);       /* ctk_get_param of one problem */
 int ctk_problem_params_differ(const ctk_batch* b);                                      /* 1 once a ctk_problem_set_param has succeeded */
 
+/* -------------------------------------------------------------------------------------------
+ * batched CEM: B independent plain-CEM controllers of ONE configuration stepped together (the counterpart of ctk_batch_* above for
+ * CTK_OPT_CEM; a family of its own, added without an ABI bump).  A handle's one-launch CEM step occupies 64 of the chip's 256 CUs at
+ * the BASELINE size (N 4096) and 8 at N 512; B handles step one after another.  A batch steps them in launches of the kernel
+ * ctk_cem_batch<ENV, TRAJ>, grid (workgroups per problem, problems of the launch).
+ *  - shared by all problems: everything in ctk_config and the parameter table (ctk_cem_batch_set_param writes it for all);
+ *    per problem: state, previous input, mean and stdev, last output, Philox seed and position, step count, draws, readable buffers;
+ *  - CONTRACT: problem p behaves bit for bit like a ctk_handle created from the same ctk_config (optimizer = CTK_OPT_CEM, ODE predictor)
+ *    with seed = seeds[p] that received the same calls: u, CTK_BUF_U_NOM (the mean), STD, J, Q, TRAJ, BEST_IDX, the Philox position and
+ *    the ctk_get_state vector (mu[H,C] | std[H,C] | u[C] | count), for every sample source, u_prev given or NULL, and any interleaving
+ *    of whole-batch steps, subset steps, per-problem resets and ctk_cem_batch_set_state;
+ *  - plain CEM with the analytic (ODE) predictor at the sizes of the one-launch step (at most 128 workgroups of 64 rollouts and 128 KiB
+ *    of LDS per problem) and cem_best_k <= num_rollouts; everything else is CTK_ERR_UNSUPPORTED with the sizes in
+ *    ctk_cem_batch_last_error(NULL), as is n_problems < 1.  The variants (naive-grad, Bharadhwaj, GMM) run as single handles.
+ *    CTK_NO_CEM_FUSED does not apply to a batch;
+ *  - every workgroup of a problem waits for all workgroups of that problem, so all of them must be resident at once: one launch holds
+ *    at most max(1, CUs / workgroups per problem) problems (4 of N 4096, 32 of N 512, 128 of N <= 128 on 256 CUs); larger batches or id
+ *    lists are split into consecutive launches on the batch's stream.  A problem never spans launches, so the results do not depend on
+ *    the split.  CTK_CEM_BATCH_MAX_PROBLEMS_PER_LAUNCH (environment, diagnostic) lowers that cap, never raises it;
+ *  - ids: as for ctk_batch_step.  Rows of s [n,S], u_prev [n,C] (NULL: every problem's own last output), samples and u_out [n,C] follow
+ *    the order of ids.  A problem's step draws its_p * N * H * C samples, its_p = warmup_iterations for its first step after creation or
+ *    reset when cfg.warmup is set and cem_outer_it otherwise: ctk_cem_batch_samples_needed(b, p) is that number for p's NEXT step.
+ *    Problems of one call may run different numbers of iterations with the in-kernel sampler (samples_loc = CTK_LOC_NONE); with
+ *    caller-supplied samples they must all run the same number, else CTK_ERR_INVALID_ARGUMENT names the problems and their counts,
+ *    nothing is launched and nothing is consumed (step them in separate calls);
+ *  - ctk_cem_batch_step is synchronous.  CTK_ERR_STATE = a bounded device-side wait ran out for the problems the message names; the
+ *    other problems' outputs are valid and written.  A batch is NOT thread-safe.
+ * Each entry corresponds to the single-handle call named beside it.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct ctk_cem_batch ctk_cem_batch;
+int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds /* NULL: cfg->seed + p */, ctk_cem_batch** out); /* ctk_create */
+void ctk_cem_batch_destroy(ctk_cem_batch* b);                                                   /* ctk_destroy */
+const char* ctk_cem_batch_last_error(const ctk_cem_batch* b);                                   /* ctk_last_error; b may be NULL */
+int ctk_cem_batch_size(const ctk_cem_batch* b);                                                 /* B */
+size_t ctk_cem_batch_samples_needed(const ctk_cem_batch* b, int problem);                       /* ctk_samples_needed of one problem's next step */
+int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev,
+                       const float* samples, int samples_loc, float* u_out);                    /* ctk_step of every listed problem */
+int ctk_cem_batch_reset(ctk_cem_batch* b, int n_ids, const int32_t* ids);                       /* ctk_reset of every listed problem */
+int ctk_cem_batch_read(ctk_cem_batch* b, int problem, int buffer, float* dst, size_t cap);      /* ctk_read: CTK_BUF_Q, J, TRAJ, U_NOM, STD, BEST_IDX */
+int ctk_cem_batch_get_state(ctk_cem_batch* b, int problem, float* dst, size_t cap);             /* ctk_get_state: mu, std [H,C], u [C], count */
+int ctk_cem_batch_set_state(ctk_cem_batch* b, int problem, const float* src, size_t n);         /* ctk_set_state */
+int ctk_cem_batch_set_param(ctk_cem_batch* b, int id, float value);                             /* ctk_set_param, all problems */
+int ctk_cem_batch_get_param(const ctk_cem_batch* b, int id, float* value);                      /* ctk_get_param */
+int ctk_cem_batch_rng_get_position(const ctk_cem_batch* b, int problem, uint32_t* call);        /* ctk_rng_get_position */
+int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call);               /* ctk_rng_set_position */
+const char* ctk_cem_batch_dominant_kernel(const ctk_cem_batch* b);                              /* ctk_dominant_kernel */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,372 @@
+"""-m gpu: CtkCemBatch (ctk_cem_batch_*, kernel ctk_cem_batch<ENV, TRAJ>) — B independent plain-CEM problems stepped together.
+
+The contract under test: problem p of a batch behaves BIT FOR BIT like a CtkEngine("cem", "ODE", seed=seeds[p]) created from the same
+configuration that received the same calls.  Every comparison against single handles is assert_array_equal; the only tolerances in this
+file are those of tests/test_gpu_tf_goldens.py::test_cem_matches_reference_golden, which is RUN (not restated) on a problem that replays
+a reference-recorded fixture INSIDE a batch."""
+import numpy as np
+import pytest
+
+from oracle import ctk_oracle as O
+from control_toolkit_amd import CtkCemBatch, CtkEngine
+from helpers import env_from
+import test_gpu_tf_goldens as goldens
+
+pytestmark = pytest.mark.gpu
+
+# name -> (environment, N, H, K, outer iterations, extra engine keywords, the oracle's plant parameters): the smallest sizes at which each
+# branch of the kernel is taken
+CONFIGS = {
+    "one_workgroup": ("CartPole", 64, 8, 8, 2, {}, O.EnvParams),                   # no second party in the hops
+    "four_workgroups": ("CartPole", 200, 40, 40, 3, {}, O.EnvParams),              # ragged last block of 8 rows
+    "quad2d": ("Quad2D", 128, 20, 20, 2, {"action_low": [-1.0, -0.8], "action_high": [1.0, 0.9]}, O.Quad2DParams),   # C = 2
+    "hover": ("Hover", 96, 16, 12, 2, {}, O.HoverParams),                          # C = 3, ragged block
+    "nine_workgroups": ("CartPole", 576, 12, 57, 2, {}, O.EnvParams),              # the segmented `multi` refit, ragged tail tile of keys
+}
+SOURCES = [("philox", True), ("host", False), ("devptr", True)]                     # (draws, u_prev given)
+STEPS = 3
+BUFFERS = ("U_NOM", "STD", "J", "Q", "BEST_IDX")
+
+
+def common_kw(config, materialize, **kw):
+    env, N, H, K, its, extra, _ = CONFIGS[config]
+    out = dict(num_rollouts=N, mpc_horizon=H, dt=0.02, environment=env, materialize_trajectories=materialize, cem_outer_it=its, cem_best_k=K,
+               cem_initial_action_stdev=0.5, cem_stdev_min=0.01, **extra)
+    out.update(kw)
+    return out
+
+
+def make(config, B, materialize, seeds=None, **kw):
+    """(batch, B single handles with seeds[p], the plant)"""
+    seeds = [7 + q for q in range(B)] if seeds is None else seeds
+    common = common_kw(config, materialize, **kw)
+    batch = CtkCemBatch(B, seeds=seeds, **common)
+    handles = [CtkEngine("cem", "ODE", seed=seeds[q], **common) for q in range(B)]
+    return batch, handles, O.Predictor("ODE", dt=0.02, env=CONFIGS[config][6]())
+
+
+def first_states(rng, B, S):
+    s = rng.uniform(-0.4, 0.4, (B, S)).astype(np.float32)
+    if S == 4:
+        s[:, 2] += 2.6          # CartPole: the pendulum hangs away from the target
+    return s
+
+
+def differing_states(batch, handles, rng):
+    """every problem starts from a distribution of its own (set_state on both sides)"""
+    HC = batch.H * batch.C
+    for q, h in enumerate(handles):
+        st = np.concatenate([rng.uniform(-0.3, 0.3, HC), rng.uniform(0.2, 0.6, HC), rng.uniform(-0.5, 0.5, batch.C), [0]]).astype(np.float32)
+        batch.set_state(q, st)
+        h.set_state(st)
+
+
+def draws_for(source, rng, ids, batch):
+    """(what the batch is given, what handle row j is given, keep-alive); every listed problem runs the same number of iterations"""
+    if source == "philox":
+        return None, [None] * len(ids), None
+    per = batch.samples_needed(ids[0])
+    assert all(batch.samples_needed(q) == per for q in ids)
+    arr = rng.standard_normal((len(ids), per // (batch.N * batch.H * batch.C), batch.N, batch.H, batch.C)).astype(np.float32)
+    if source == "host":
+        return arr, [arr[j] for j in range(len(ids))], None
+    import torch
+    t = torch.from_numpy(arr).to("cuda")
+    torch.cuda.synchronize()
+    return t.data_ptr(), [t.data_ptr() + 4 * j * arr[0].size for j in range(len(ids))], t
+
+
+def compare(batch, handles, problems, materialize, tag):
+    for q in problems:
+        h = handles[q]
+        for name in BUFFERS + (("TRAJ",) if materialize else ()):
+            np.testing.assert_array_equal(batch.read(name, q), h.read(name).reshape(batch.read(name, q).shape), err_msg=f"{tag}: {name} of problem {q}")
+        np.testing.assert_array_equal(batch.get_state(q), h.get_state(), err_msg=f"{tag}: state vector of problem {q}")
+        assert batch.rng_position(q) == h.rng_position(), f"{tag}: Philox position of problem {q}"
+        assert batch.samples_needed(q) == h.samples_needed(), f"{tag}: samples_needed of problem {q}"
+
+
+def close_all(batch, handles):
+    batch.close()
+    for h in handles:
+        h.close()
+
+
+# ---- 1. batch == single handles, bit for bit ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("materialize", [False, True])
+@pytest.mark.parametrize("config", list(CONFIGS))
+@pytest.mark.parametrize("B", [1, 3, 5])
+def test_batch_equals_single_handles(B, config, materialize):
+    """every sample source, u_prev given and None, one after another on the SAME objects: STEPS closed-loop steps each from differing
+    states, distributions and seeds, the plant being the oracle's Predictor.step with every problem's own output fed back"""
+    batch, handles, plant = make(config, B, materialize)
+    rng = np.random.default_rng(B * 131 + len(config))
+    s = first_states(rng, B, batch.S)
+    differing_states(batch, handles, rng)
+    compare(batch, handles, range(B), materialize, f"{config} B={B} before the first step")
+    for source, given in SOURCES:
+        for t in range(STEPS):
+            up = rng.uniform(-1.0, 1.0, (B, batch.C)).astype(np.float32) if given else None
+            bs, hs, keep = draws_for(source, rng, list(range(B)), batch)
+            u = batch.step(s, bs, u_prev=up)
+            uh = np.stack([handles[q].step(s[q], hs[q], u_prev=None if up is None else up[q]) for q in range(B)])
+            np.testing.assert_array_equal(u, uh, err_msg=f"{config} B={B} {source} u_prev={'given' if given else 'None'} step {t}: u")
+            assert np.all(np.isfinite(u))
+            s = plant.step(s, u).astype(np.float32)
+            del keep
+        compare(batch, handles, range(B), materialize, f"{config} B={B} after {source}/{'given' if given else 'None'}")
+    close_all(batch, handles)
+
+
+def test_split_into_launches_gives_the_same_bits(monkeypatch):
+    """B = 5 of the 4-workgroup shape with CTK_CEM_BATCH_MAX_PROBLEMS_PER_LAUNCH = 2 runs as three launches (2 + 2 + 1) and gives the
+    bits of the unsplit batch"""
+    B, config = 5, "four_workgroups"
+    one, handles, plant = make(config, B, True)
+    monkeypatch.setenv("CTK_CEM_BATCH_MAX_PROBLEMS_PER_LAUNCH", "2")
+    split = CtkCemBatch(B, seeds=[7 + q for q in range(B)], **common_kw(config, True))
+    monkeypatch.delenv("CTK_CEM_BATCH_MAX_PROBLEMS_PER_LAUNCH")
+    rng = np.random.default_rng(40)
+    s = first_states(rng, B, one.S)
+    for t in range(STEPS):
+        u1, u2 = one.step(s), split.step(s)
+        uh = np.stack([handles[q].step(s[q]) for q in range(B)])
+        np.testing.assert_array_equal(u1, u2)
+        np.testing.assert_array_equal(u1, uh)
+        s = plant.step(s, u1).astype(np.float32)
+    compare(one, handles, range(B), True, "one launch")
+    compare(split, handles, range(B), True, "three launches")
+    ids = [0, 2, 3]                                        # an id list longer than the cap is split as well
+    u2 = split.step(s[ids], ids=ids)
+    uh = np.stack([handles[q].step(s[q]) for q in ids])
+    np.testing.assert_array_equal(u2, uh)
+    compare(split, handles, ids, True, "subset over two launches")
+    split.close()
+    close_all(one, handles)
+
+
+# ---- 2. warm-up: problems of one launch loop a different number of times ----------------------------------------------------------------
+def test_warmup_and_mixed_iteration_counts():
+    """the cem_warmup.npz sizes; after reset([1, 3]) the next whole-batch step runs 5 iterations for problems 1 and 3 and 2 for 0 and 2"""
+    B = 4
+    kw = dict(num_rollouts=64, mpc_horizon=12, dt=0.02, cem_outer_it=2, cem_best_k=8, warmup=True, warmup_iterations=5,
+              cem_initial_action_stdev=0.5, cem_stdev_min=0.01)
+    seeds = [21, 22, 23, 24]
+    batch = CtkCemBatch(B, seeds=seeds, **kw)
+    handles = [CtkEngine("cem", "ODE", seed=seeds[q], **kw) for q in range(B)]
+    plant = O.Predictor("ODE", dt=0.02, env=O.EnvParams())
+    per_it = 64 * 12
+    rng = np.random.default_rng(4)
+    s = first_states(rng, B, 4)
+    assert [batch.samples_needed(q) for q in range(B)] == [5 * per_it] * B
+    u = batch.step(s)
+    np.testing.assert_array_equal(u, np.stack([handles[q].step(s[q]) for q in range(B)]))
+    s = plant.step(s, u).astype(np.float32)
+    compare(batch, handles, range(B), False, "after the warm-up step")
+    assert [batch.samples_needed(q) for q in range(B)] == [2 * per_it] * B
+    batch.reset([1, 3])
+    for q in (1, 3):
+        handles[q].reset()
+    compare(batch, handles, range(B), False, "after reset([1, 3])")
+    assert [batch.samples_needed(q) for q in range(B)] == [2 * per_it, 5 * per_it, 2 * per_it, 5 * per_it]
+    # caller-supplied samples have one row length: refused, naming the problems and their counts; nothing launched, nothing consumed
+    before = [(batch.get_state(q), batch.rng_position(q)) for q in range(B)]
+    for samples in (np.zeros((B, 2, 64, 12, 1), np.float32), np.zeros((B, 5, 64, 12, 1), np.float32)):
+        with pytest.raises(ValueError, match=r"0: 2, 1: 5, 2: 2, 3: 5.*separate calls"):
+            batch.step(s, samples)
+    for q in range(B):
+        np.testing.assert_array_equal(batch.get_state(q), before[q][0])
+        assert batch.rng_position(q) == before[q][1]
+    # ... the in-kernel sampler has no such restriction: one launch, mixed iteration counts
+    u = batch.step(s)
+    np.testing.assert_array_equal(u, np.stack([handles[q].step(s[q]) for q in range(B)]))
+    s = plant.step(s, u).astype(np.float32)
+    compare(batch, handles, range(B), False, "after the mixed step")
+    # problems with equal counts take host samples in one call (here: all of them again)
+    arr = rng.standard_normal((B, 2, 64, 12, 1)).astype(np.float32)
+    u = batch.step(s, arr)
+    np.testing.assert_array_equal(u, np.stack([handles[q].step(s[q], arr[q]) for q in range(B)]))
+    compare(batch, handles, range(B), False, "after a host-sample step")
+    close_all(batch, handles)
+
+
+# ---- 3. subset steps, resets, state round trip --------------------------------------------------------------------------------------------
+def snapshot(batch, q):
+    out = {name: batch.read(name, q) for name in BUFFERS + ("TRAJ",)}
+    out.update(state=batch.get_state(q), rng=batch.rng_position(q))
+    return out
+
+
+def assert_unchanged(batch, q, snap, tag):
+    now = snapshot(batch, q)
+    for k, v in snap.items():
+        np.testing.assert_array_equal(now[k], v, err_msg=f"{tag}: {k} of untouched problem {q} changed")
+
+
+def test_subset_steps_and_resets():
+    B, config = 8, "four_workgroups"
+    batch, handles, plant = make(config, B, True)
+    rng = np.random.default_rng(8)
+    s = first_states(rng, B, batch.S)
+    for t in range(2):                                   # two whole-batch steps first: every problem has a distribution and a Philox position of its own
+        u = batch.step(s)
+        np.testing.assert_array_equal(u, np.stack([handles[q].step(s[q]) for q in range(B)]))
+        s = plant.step(s, u).astype(np.float32)
+    ids = [1, 4, 5]
+    rest = [q for q in range(B) if q not in ids]
+    snaps = {q: snapshot(batch, q) for q in rest}
+    for t in range(3):
+        u = batch.step(s[ids], ids=ids)
+        np.testing.assert_array_equal(u, np.stack([handles[q].step(s[q]) for q in ids]))
+        s[ids] = plant.step(s[ids], u).astype(np.float32)
+    for q in rest:
+        assert_unchanged(batch, q, snaps[q], "subset step")
+    compare(batch, handles, range(B), True, "after subset steps")
+    # reset of one problem = ctk_reset of its handle; nobody else moves
+    snaps = {q: snapshot(batch, q) for q in range(B) if q != 4}
+    batch.reset([4])
+    handles[4].reset()
+    for q in snaps:
+        assert_unchanged(batch, q, snaps[q], "reset([4])")
+    compare(batch, handles, [4], True, "after reset([4])")
+    for t in range(2):
+        up = rng.uniform(-1.0, 1.0, (B, 1)).astype(np.float32)
+        u = batch.step(s, u_prev=up)
+        np.testing.assert_array_equal(u, np.stack([handles[q].step(s[q], u_prev=up[q]) for q in range(B)]))
+        s = plant.step(s, u).astype(np.float32)
+    compare(batch, handles, range(B), True, "after the reset and two more steps")
+    # get_state / set_state / set_rng_position: a batch restored into a FRESH batch continues bit for bit
+    fresh = CtkCemBatch(B, seeds=[7 + q for q in range(B)], **common_kw(config, True))
+    for q in range(B):
+        fresh.set_state(q, batch.get_state(q))
+        fresh.set_rng_position(q, batch.rng_position(q))
+        np.testing.assert_array_equal(fresh.get_state(q), batch.get_state(q))
+    for t in range(3):
+        u = batch.step(s)
+        np.testing.assert_array_equal(fresh.step(s), u)
+        s = plant.step(s, u).astype(np.float32)
+    for q in range(B):
+        for k, v in snapshot(batch, q).items():
+            np.testing.assert_array_equal(snapshot(fresh, q)[k], v, err_msg=f"restored batch: {k} of problem {q}")
+    fresh.close()
+    close_all(batch, handles)
+
+
+# ---- 4. the reference-recorded fixture inside a batch -------------------------------------------------------------------------------------
+class ProblemAsEngine:
+    """Problem `me` of a batch behind the CtkEngine calls test_cem_matches_reference_golden makes, with a single handle that receives the
+    same calls beside it: every step and every read asserts the two bit-equal, the neighbours run other seeds, states and draws in the
+    same launches."""
+
+    def __init__(self, batch, me, handle, rng):
+        self.batch, self.me, self.handle, self.rng = batch, me, handle, rng
+        self.S, self.C = batch.S, batch.C
+
+    def dominant_kernel(self):
+        return self.batch.dominant_kernel()
+
+    def samples_needed(self):
+        assert self.batch.samples_needed(self.me) == self.handle.samples_needed()
+        return self.batch.samples_needed(self.me)
+
+    def read(self, name):
+        got, want = self.batch.read(name, self.me), self.handle.read(name)
+        np.testing.assert_array_equal(got, want.reshape(got.shape), err_msg=f"{name} of problem {self.me} against its handle")
+        return want
+
+    def step(self, s, noise, u_prev=None):
+        B, me = len(self.batch), self.me
+        S = first_states(self.rng, B, self.S)
+        S[me] = s
+        noise = np.asarray(noise, np.float32)
+        draws = self.rng.standard_normal((B,) + noise.shape).astype(np.float32)
+        draws[me] = noise
+        up = self.rng.uniform(-0.5, 0.5, (B, self.C)).astype(np.float32)
+        up[me] = np.asarray(u_prev, np.float32).reshape(-1)
+        u = self.batch.step(S, draws, u_prev=up)
+        uh = self.handle.step(s, noise, u_prev=u_prev)
+        np.testing.assert_array_equal(u[me], uh)
+        assert np.all(np.isfinite(u))
+        np.testing.assert_array_equal(self.batch.get_state(me), self.handle.get_state())
+        assert self.batch.rng_position(me) == self.handle.rng_position()
+        return uh
+
+    def set_state(self, st):
+        self.batch.set_state(self.me, st)
+        self.handle.set_state(st)
+
+    def close(self):
+        self.batch.close()
+        self.handle.close()
+
+
+@pytest.mark.parametrize("case", ["default", "quad2d"])
+def test_reference_fixture_inside_a_batch(monkeypatch, case):
+    """cem_<case>.npz fed to problem 2 of B = 3: bit-equal to a handle, and within the reference's tolerances — the body of
+    test_cem_matches_reference_golden itself runs on the problem (its bounds and its elite-set rule, nothing restated)"""
+    real_engine_from = goldens.engine_from
+    made = []
+
+    def batch_engine_from(d, opt, **kw):
+        assert opt == "cem"
+        handle = real_engine_from(d, opt, **kw)
+        batch = CtkCemBatch(3, seeds=[31, 32, 33], environment=str(d["environment"]), num_rollouts=int(d["num_rollouts"]),
+                            mpc_horizon=int(d["mpc_horizon"]), dt=float(d["dt"]), action_low=d["low"], action_high=d["high"], **kw)
+        env = env_from(d)
+        for n in env.param_names():
+            batch.set_param(n, float(getattr(env, n)))
+        made.append(batch.dominant_kernel())        # the golden test closes its engine, and with it the batch
+        return ProblemAsEngine(batch, 2, handle, np.random.default_rng(33))
+
+    monkeypatch.setattr(goldens, "engine_from", batch_engine_from)
+    goldens.test_cem_matches_reference_golden(monkeypatch, case, "batch")
+    assert len(made) == 1 and made[0].startswith("ctk_cem_batch<")
+
+
+# ---- 5. set_param reaches every problem -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("config,name", [("four_workgroups", "dd_weight"), ("four_workgroups", "m_pole"), ("quad2d", "target_x")])
+def test_set_param_reaches_every_problem(config, name):
+    """one cost weight, one plant parameter and a target, against handles"""
+    B = 3
+    batch, handles, plant = make(config, B, True)
+    rng = np.random.default_rng(3)
+    s = first_states(rng, B, batch.S)
+    u0 = batch.step(s)
+    np.testing.assert_array_equal(u0, np.stack([handles[q].step(s[q]) for q in range(B)]))
+    value = 0.3
+    batch.set_param(name, value)
+    assert batch.get_param(name) == np.float32(value)
+    for h in handles:
+        h.set_param(name, value)
+    # the same draws before and after: what moves the costs is the parameter
+    for q in range(B):
+        batch.set_rng_position(q, 0)
+        handles[q].set_rng_position(0)
+        st = handles[q].get_state()
+        st[:] = 0.0
+        st[batch.H * batch.C:2 * batch.H * batch.C] = 0.5
+        batch.set_state(q, st)
+        handles[q].set_state(st)
+    u = batch.step(s)
+    np.testing.assert_array_equal(u, np.stack([handles[q].step(s[q]) for q in range(B)]))
+    compare(batch, handles, range(B), True, f"{name} = {value}")
+    fresh = CtkCemBatch(B, seeds=[7 + q for q in range(B)], **common_kw(config, True))
+    fresh.step(s)
+    assert not np.array_equal(fresh.read_all("J"), batch.read_all("J"))          # the parameter is in the rollouts' costs
+    fresh.close()
+    close_all(batch, handles)
+
+
+# ---- 6. kernel names -----------------------------------------------------------------------------------------------------------------------------
+def test_dominant_kernel_names():
+    b = CtkCemBatch(2, **common_kw("four_workgroups", False))
+    assert b.dominant_kernel() == "ctk_cem_batch<0, false>"
+    b.close()
+    b = CtkCemBatch(2, **common_kw("quad2d", True))
+    assert b.dominant_kernel() == "ctk_cem_batch<1, true>"
+    b.close()
+    e = CtkEngine("cem", "ODE", **common_kw("four_workgroups", False))           # the single handle's name is what it was
+    assert e.dominant_kernel() == "ctk_cem_fused<0, false>"
+    e.step(np.array([0.0, 0.0, 2.6, 0.0], np.float32))
+    assert e.dominant_kernel() == "ctk_cem_fused<0, false>"
+    e.close()
