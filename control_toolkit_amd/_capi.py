@@ -161,6 +161,9 @@ SYMBOLS = {
     "ctk_cem_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
     "ctk_cem_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
     "ctk_cem_batch_dominant_kernel": (C.c_char_p, [_H]),
+    "ctk_cem_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ctk_cem_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
+    "ctk_cem_problem_params_differ": (C.c_int, [_H]),
 }
 
 
@@ -689,7 +692,7 @@ _F32_MAX = float(np.finfo(np.float32).max)
 
 
 def batch_param_args(param_names, num_problems: int, name, values, ids=None):
-    """Checks the arguments of CtkMppiBatch.set_problem_params without touching a device: the parameter name against the environment's
+    """Checks the arguments of CtkMppiBatch.set_problem_params / CtkCemBatch.set_problem_params without touching a device: the parameter name against the environment's
     names, ids (batch_ids), values a finite scalar (every listed problem) or one finite value per listed problem ([n]).  Returns
     (parameter id, ids, n, values as fp32 [n])."""
     if name not in param_names:
@@ -888,7 +891,8 @@ class CtkMppiBatch:
 class CtkCemBatch:
     """Owns one ctk_cem_batch: num_problems independent plain-CEM controllers of ONE configuration (the CEM keywords of CtkEngine),
     stepped together by launches of one kernel.  Problem p behaves bit for bit like CtkEngine("cem", "ODE", seed=seeds[p], ...) given the
-    same calls.  seeds: one per problem (default seed + p).  The parameter table is shared: set_param reaches every problem."""
+    same calls, set_param among them: set_problem_params gives every problem its own plant, cost weights and targets, set_param the same
+    value to all.  seeds: one per problem (default seed + p)."""
 
     def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "cem", predictor: str = "ODE",
                  num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
@@ -1030,9 +1034,33 @@ class CtkCemBatch:
         self._check(self._lib.ctk_cem_batch_set_param(self._h, self.param_names.index(name), float(value)))
 
     def get_param(self, name: str) -> float:
+        """the last value set_param gave the whole batch (the default before that); a problem's own value: get_problem_param"""
         v = C.c_float()
         self._check(self._lib.ctk_cem_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
         return v.value
+
+    def set_problem_params(self, name: str, values, ids=None):
+        """parameter `name` of the problems in ids (None: all): values a scalar or [n], one per listed problem in the order of ids.  The
+        next step re-derives the constants of the problems touched; from the first call on the batch runs the per-problem form of its
+        kernel (params_differ, dominant_kernel)."""
+        pid, idv, n, vals = batch_param_args(self.param_names, self.B, name, values, ids)
+        self._check(self._lib.ctk_cem_problem_set_param(self._h, n, _ptr(idv), pid, _ptr(vals)))
+
+    def get_problem_param(self, name: str, problem: int) -> float:
+        if name not in self.param_names:
+            raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(self.param_names)})")
+        v = C.c_float()
+        if self._lib.ctk_cem_problem_get_param(self._h, self._problem(problem), self.param_names.index(name), C.byref(v)) != 0:
+            raise CtkError(f"ctk_cem_problem_get_param({problem}, {name!r}) failed")
+        return v.value
+
+    def get_problem_params(self, name: str) -> np.ndarray:
+        """[B] parameter `name` of every problem"""
+        return np.array([self.get_problem_param(name, p) for p in range(self.B)], np.float32)
+
+    def params_differ(self) -> int:
+        """1 once a set_problem_params has succeeded on this batch (sticky), else 0"""
+        return int(self._lib.ctk_cem_problem_params_differ(self._h))
 
     def rng_position(self, problem: int) -> int:
         v = C.c_uint32()

@@ -2799,12 +2799,20 @@ int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) {
 // Batched CEM (include/ctk_hip.h: ctk_cem_batch_*): B independent CEM problems of one configuration, stepped by launches of
 // ctk_cem_batch<ENV, TRAJ> (ctk_cem_fused.hip).  One allocation per buffer kind with a problem stride — no handles inside.  Per-problem
 // host state is what a CEM handle keeps: the sequence number of its next step, its Philox position, its step count (which decides the
-// outer iterations of its next step: cem_iterations), the next hand-off tag, and whether BEST_IDX has to be rebuilt from J.
+// outer iterations of its next step: cem_iterations), the next hand-off tag, whether BEST_IDX has to be rebuilt from J, and its parameter
+// table.  While no ctk_cem_problem_set_param has succeeded the launches take the constants of the shared table by value; from then on
+// (`differ`, sticky) every step writes the constants of the problems it steps BEHIND their step records, in the records' order, so they
+// travel in the records' transfer (no constants array in device memory, no second transfer).
 // =============================================================================================
 struct ctk_cem_batch {
     ctk_config cfg{};
     int B = 0, N = 0, H = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, K = 0, nblk = 0;
-    float params[CTK_MAX_PARAMS]{};         // one table for all problems (ctk_cem_batch_set_param)
+    float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (ctk_cem_batch_set_param / get_param)
+    std::vector<float> pparams;             // [B][CTK_MAX_PARAMS] every problem's own table
+    std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived into kcache
+    bool differ = false;                    // a ctk_cem_problem_set_param has succeeded: the per-problem form of the kernel from now on
+    size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes per problem in kcache and behind the step records
+    std::vector<unsigned char> kcache;      // [B][kstride] derived constants by problem id (host only; the step copies them into h_steps)
     hipStream_t stream = nullptr;
     int max_per_launch = 1;                 // problems per launch: max(1, CUs / nblk) (ctk_cem_batch_create), a diagnostic switch may lower it
     size_t llw = 0;                         // ctk_cem_fused_ll_words(N, HC): hand-off words per problem
@@ -2819,8 +2827,8 @@ struct ctk_cem_batch {
     float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
     float* h_u_dev = nullptr;
     CtkCemBatchDesc* d_desc = nullptr;      // [B]
-    CtkCemBatchStep* h_steps = nullptr;     // pinned [B]: the step records of the step being issued
-    CtkCemBatchStep* d_steps = nullptr;     // [B]
+    CtkCemBatchStep* h_steps = nullptr;     // pinned, B * (sizeof(CtkCemBatchStep) + kstride) bytes: the n step records of the step being
+    CtkCemBatchStep* d_steps = nullptr;     // issued and, in the per-problem form, the constants of those n problems right behind them
     float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
     std::vector<uint32_t> seq, call, cem_tag;
     std::vector<int> count;
@@ -2830,6 +2838,8 @@ struct ctk_cem_batch {
     float* sd(int p) const { return d_sd + (size_t)p * HC; }
     float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
     float* slot(int p) const { return h_u + (size_t)p * 16; }
+    float* table(int p) { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
+    const float* table(int p) const { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
     int its(int p) const { return (cfg.warmup && count[(size_t)p] == 0) ? cfg.warmup_iterations : cfg.cem_outer_it; }   // cem_iterations
 };
 
@@ -2940,6 +2950,11 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
     b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = HC;
     b->llw = ctk_cem_fused_ll_words(N, HC);
     default_params(b->env, b->params);
+    b->pparams.resize((size_t)n_problems * CTK_MAX_PARAMS);
+    for (int p = 0; p < n_problems; ++p) std::memcpy(b->table(p), b->params, sizeof(b->params));
+    b->dirty.assign((size_t)n_problems, 1);            // nothing derived yet: the first step of the per-problem form derives what it steps
+    b->kstride = ctk_mppi_batch_k_stride(b->env);
+    b->kcache.assign((size_t)n_problems * b->kstride, 0);
     // Progress (the proof stands above ctk_cem_batch, ctk_cem_fused.hip): every workgroup of a problem waits for all workgroups of that
     // problem, so a launch holds at most max(1, CUs / nblk) problems — problems * nblk <= CUs, every CU admits at least one workgroup of
     // this kernel (LDS <= 128 KiB), so all workgroups of a launch are co-resident whatever the dispatch order or placement.  One problem
@@ -2971,12 +2986,13 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
     CHIP_CREATE(dev_zero((void**)&b->d_idx, Bz * N * sizeof(int)));
     CHIP_CREATE(dev_zero((void**)&b->d_u, Bz * CTK_MAX_INPUTS * sizeof(float)));
     CHIP_CREATE(dev_zero((void**)&b->d_desc, Bz * sizeof(CtkCemBatchDesc)));
-    CHIP_CREATE(dev_zero((void**)&b->d_steps, Bz * sizeof(CtkCemBatchStep)));
+    const size_t steps_bytes = Bz * (sizeof(CtkCemBatchStep) + b->kstride);   // the records, then room for as many elements of constants
+    CHIP_CREATE(dev_zero((void**)&b->d_steps, steps_bytes));
     CHIP_CREATE(hipHostMalloc((void**)&b->h_u, Bz * 64, hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(b->h_u, 0, Bz * 64);
     CHIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
-    CHIP_CREATE(hipHostMalloc((void**)&b->h_steps, Bz * sizeof(CtkCemBatchStep), hipHostMallocDefault));
-    std::memset(b->h_steps, 0, Bz * sizeof(CtkCemBatchStep));
+    CHIP_CREATE(hipHostMalloc((void**)&b->h_steps, steps_bytes, hipHostMallocDefault));
+    std::memset(b->h_steps, 0, steps_bytes);
 
     std::vector<CtkCemBatchDesc> desc(Bz);
     std::vector<float> mu(Bz * HC), sd(Bz * HC);                   // optimizer_reset() of every problem
@@ -3054,7 +3070,27 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
         for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
         for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
     }
-    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkCemBatchStep), hipMemcpyHostToDevice, b->stream);
+    // The per-problem form: the constants of the n problems of this step right behind the n records, in the records' order, so that ONE
+    // transfer carries both.  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses
+    // (ctk_set_param -> derive_constants / Env<>::derive at its launch); the cache is by problem id, the block behind the records by launch order.
+    size_t step_bytes = (size_t)n * sizeof(CtkCemBatchStep);
+    const unsigned char* d_ksteps = nullptr;
+    if (b->differ) {
+        unsigned char* h_k = reinterpret_cast<unsigned char*>(b->h_steps) + step_bytes;
+        for (int j = 0; j < n; ++j) {
+            const size_t z = (size_t)b->h_steps[j].id;
+            if (b->dirty[z]) {
+                ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, b->kcache.data() + z * b->kstride);
+                b->dirty[z] = 0;
+            }
+            std::memcpy(h_k + (size_t)j * b->kstride, b->kcache.data() + z * b->kstride, b->kstride);
+        }
+        d_ksteps = reinterpret_cast<const unsigned char*>(b->d_steps) + step_bytes;
+        step_bytes += (size_t)n * b->kstride;
+    }
+    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, step_bytes, hipMemcpyHostToDevice, b->stream);
+    if (le != hipSuccess && b->differ)                 // nothing reached the device: derive and copy again at the next step
+        for (int j = 0; j < n; ++j) b->dirty[(size_t)b->h_steps[j].id] = 1;
     const RolloutArgs a = cem_batch_args(b);
     const bool log = b->cfg.materialize_trajectories != 0;
     const CemFusedLaunch cl{0, b->K, nullptr, 0u, b->cfg.cem_stdev_min, 1.0e8f, b->cfg.cem_initial_action_stdev,
@@ -3062,7 +3098,8 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
     int launched = 0;                                  // consecutive launches of at most max_per_launch problems; a problem never spans launches
     while (le == hipSuccess && launched < n) {
         const int cnt = std::min(b->max_per_launch, n - launched);
-        le = ctk_launch_cem_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, cl, b->d_desc, b->d_steps + launched, cnt, log);
+        le = ctk_launch_cem_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, cl, b->d_desc, b->d_steps + launched, cnt, log,
+                                  d_ksteps ? d_ksteps + (size_t)launched * b->kstride : nullptr);
         if (le == hipSuccess) launched += cnt;
     }
     // completion: every launched problem's {u, seq} store landing in its pinned slot (finish_step's bounded spin, one budget for all)
@@ -3182,7 +3219,8 @@ int ctk_cem_batch_set_state(ctk_cem_batch* b, int problem, const float* src, siz
 int ctk_cem_batch_set_param(ctk_cem_batch* b, int id, float value) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     if (id < 0 || id >= env_info(b->env)->n_params) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_set_param: unknown parameter id for this environment");
-    b->params[id] = value;                             // every launch derives its constants from the table (Env<>::derive, as a handle's launch does)
+    b->params[id] = value;                             // the shared table: the shared form derives its constants from it at each launch
+    for (int p = 0; p < b->B; ++p) { b->table(p)[id] = value; b->dirty[(size_t)p] = 1; }   // column id of every problem; the other ids stay
     return CTK_OK;
 }
 
@@ -3191,6 +3229,32 @@ int ctk_cem_batch_get_param(const ctk_cem_batch* b, int id, float* value) {
     *value = b->params[id];
     return CTK_OK;
 }
+
+int ctk_cem_problem_set_param(ctk_cem_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = cem_batch_ids(b, "ctk_cem_problem_set_param", n_ids, ids, &n)) return rc;
+    if (id < 0 || id >= env_info(b->env)->n_params) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_problem_set_param: unknown parameter id for this environment");
+    if (!values) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_problem_set_param: NULL values (one value per listed problem)");
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        b->table(p)[id] = values[j];
+        b->dirty[(size_t)p] = 1;                       // derived when the problem is next stepped: no cost until then
+    }
+    if (!b->differ) {                                  // sticky: the tables are never compared again
+        b->differ = true;
+        b->dominant = ctk_cem_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    }
+    return CTK_OK;
+}
+
+int ctk_cem_problem_get_param(const ctk_cem_batch* b, int problem, int id, float* value) {
+    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->table(problem)[id];
+    return CTK_OK;
+}
+
+int ctk_cem_problem_params_differ(const ctk_cem_batch* b) { return b && b->differ ? 1 : 0; }
 
 int ctk_cem_batch_rng_get_position(const ctk_cem_batch* b, int problem, uint32_t* call) {
     if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;

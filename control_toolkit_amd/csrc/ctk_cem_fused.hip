@@ -236,25 +236,26 @@ __global__ __launch_bounds__(CF_BLOCK) void ctk_cem_batch(const CtkCemBatchDesc*
     using E = Env<ENV>;
     constexpr int C = E::C, S = E::S;
     extern __shared__ float lds[];
-    const CtkCemBatchStep& q = steps[blockIdx.y];
-    const CtkCemBatchDesc& d = desc[q.id];
-    RolloutArgs a = a_tpl;                         // limits, inv_Hp1, global_row0 (launcher)
-    a.N = N_; a.H = H_; a.P = P_; a.p_magic = pmagic_;
-#pragma unroll
-    for (int i = 0; i < S; ++i) a.s0[i] = q.s[i];
-#pragma unroll
-    for (int c = 0; c < C; ++c) a.u_prev[c] = q.u_prev[c];
-    a.u_prev_dev = q.dev_uprev ? d.u_dev : nullptr;
-    a.J = d.J; a.Q_out = d.Q_out; a.traj_out = d.traj_out;
-    a.seed_lo = d.seed_lo; a.seed_hi = d.seed_hi; a.call = q.call;
-    const float* samples = q.samples;
-    CemFusedK cf = cf_tpl;                         // per_it, std_min / std_max / init_std, mid[], timeout_ticks (launcher)
-    cf.nblk = nblk_; cf.K = K_;
-    cf.its = q.its; cf.tag0 = q.tag0; cf.seq = q.seq;
-    cf.llJ = d.ll; cf.llS = d.ll + N_;
-    cf.mu = d.mu; cf.sd = d.sd; cf.u_dev = d.u_dev; cf.u_host = d.u_host; cf.idx_out = d.idx_out;
-    const float* mid = cf_tpl.mid;                 // shared by value: read where the kernel argument lies
-    const uint32_t bx = blockIdx.x;                // unsigned, as blockIdx.x is: the body's index arithmetic keeps its types
+#include "ctk_cem_batch_pro.inc"
+#include "ctk_cem_body.inc"
+}
+
+// The PER-PROBLEM-PARAMETER form of the batch kernel (ctk_cem_problem_set_param): the same prologue and the same body, but the derived
+// constants `k` of the problem come from device memory instead of the by-value argument.  The host writes them BEHIND the step records, in
+// the records' order (stride CtkBatchKStride<ENV>, derived with Env<ENV>::derive, as a handle's are), so they arrive with the records'
+// transfer and element blockIdx.y of ksteps belongs to record blockIdx.y of steps — indexed by launch order, not by problem id.  The
+// address depends on blockIdx.y alone: uniform, so the constants arrive by scalar loads like the record; they are copied into a local K
+// here, ahead of the body's first global store, and stay in SGPRs as the kernarg copy does.  ksteps stands among the leading (preloaded)
+// arguments: the load depends on it.
+template <int ENV, bool WTRAJ>
+__global__ __launch_bounds__(CF_BLOCK) void ctk_cem_batch_pp(const CtkCemBatchDesc* __restrict__ desc, const CtkCemBatchStep* __restrict__ steps,
+                                                             int N_, int H_, int P_, uint32_t pmagic_, int nblk_, int K_,
+                                                             const unsigned char* __restrict__ ksteps, RolloutArgs a_tpl, CemFusedK cf_tpl) {
+    using E = Env<ENV>;
+    constexpr int C = E::C, S = E::S;
+    extern __shared__ float lds[];
+#include "ctk_cem_batch_pro.inc"
+    const typename E::K k = *reinterpret_cast<const typename E::K*>(ksteps + (size_t)blockIdx.y * CtkBatchKStride<ENV>::value);
 #include "ctk_cem_body.inc"
 }
 
@@ -293,14 +294,14 @@ hipError_t ctk_launch_cem_fused(hipStream_t st, int env, const float* params, fl
     return hipGetLastError();
 }
 
-const char* ctk_cem_batch_name(int env, bool log) {
-    return ctk_kernel_name("ctk_cem_batch<%d, %4$s>", env, 0, 0, log ? "true" : "false");
+const char* ctk_cem_batch_name(int env, bool log, bool per_problem) {
+    return ctk_kernel_name(per_problem ? "ctk_cem_batch_pp<%d, %4$s>" : "ctk_cem_batch<%d, %4$s>", env, 0, 0, log ? "true" : "false");
 }
 
 // n_problems step records from steps_dev on, as ONE launch of grid (workgroups per problem, n_problems); the caller keeps
 // n_problems * workgroups per problem within the device's CU count (the progress argument above the kernel)
 hipError_t ctk_launch_cem_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a_in, const CemFusedLaunch& c,
-                                const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* steps_dev, int n_problems, bool log) {
+                                const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* steps_dev, int n_problems, bool log, const void* k_steps_dev) {
     const int nblk = ctk_cem_fused_blocks(a_in.N);
     if (n_problems < 1 || nblk > CTK_CEM_FUSED_MAX_BLOCKS) return hipErrorInvalidValue;
     const dim3 grid(nblk, n_problems), block(CF_BLOCK);
@@ -308,7 +309,6 @@ hipError_t ctk_launch_cem_batch(hipStream_t st, int env, const float* params, fl
         using E = Env<EV>;
         const int HC = a_in.H * E::C;
         const RolloutArgs a = ctk_rollout_args(a_in, E::C, HC);
-        const typename E::K k = E::derive(params, dt, isteps);
         CemFusedK cf{};                                // its, tag0, seq and every pointer come from the records and descriptors
         cf.K = c.K; cf.nblk = nblk; cf.per_it = (unsigned long long)a.N * HC;
         cf.std_min = c.std_min; cf.std_max = c.std_max; cf.init_std = c.init_std;
@@ -316,10 +316,18 @@ hipError_t ctk_launch_cem_batch(hipStream_t st, int env, const float* params, fl
         cf.timeout_ticks = (unsigned long long)(c.timeout_s * 1.0e8);
         const size_t lds = ctk_cem_fused_lds(a.N, HC);
         if (lds > 128 * 1024) return hipErrorInvalidValue;
-        ctk_with_bool(log, [&](auto log_c) {
-            hipLaunchKernelGGL((ctk_cem_batch<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.N, a.H, a.P, a.p_magic, nblk,
-                               c.K, a, k, cf);
-        });
+        if (k_steps_dev) {                             // per-problem constants: element j belongs to record j (ctk_mppi_batch_derive_k)
+            ctk_with_bool(log, [&](auto log_c) {
+                hipLaunchKernelGGL((ctk_cem_batch_pp<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.N, a.H, a.P, a.p_magic,
+                                   nblk, c.K, static_cast<const unsigned char*>(k_steps_dev), a, cf);
+            });
+        } else {
+            const typename E::K k = E::derive(params, dt, isteps);
+            ctk_with_bool(log, [&](auto log_c) {
+                hipLaunchKernelGGL((ctk_cem_batch<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.N, a.H, a.P, a.p_magic, nblk,
+                                   c.K, a, k, cf);
+            });
+        }
     });
     return hipGetLastError();
 }

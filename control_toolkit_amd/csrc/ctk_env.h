@@ -676,3 +676,12 @@ struct Env<CTK_ENV_USER> : EnvFromModel<CtkUserEnv> {};
         CTK_FOR_ENV_USER_BRANCH(id, ENVV, __VA_ARGS__)                          \
         else { constexpr int ENVV = CTK_ENV_HOVER; __VA_ARGS__; }             \
     } while (0)
+
+// stride of an array of per-problem constants (ctk_mppi.hip: ctk_mppi_batch_pp, ctk_cem_fused.hip: ctk_cem_batch_pp): sizeof(K) rounded up
+// to 16, which also keeps every element aligned
+template <int ENV>
+struct CtkBatchKStride {
+    using K = typename Env<ENV>::K;
+    static_assert(std::is_trivially_copyable<K>::value && alignof(K) <= 16, "the derived constants travel as bytes");
+    static constexpr size_t value = (sizeof(K) + 15) & ~(size_t)15;
+};

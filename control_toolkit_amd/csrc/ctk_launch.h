@@ -309,10 +309,15 @@ struct CtkCemBatchStep {
     float s[CTK_MAX_STATES];
     float u_prev[CTK_MAX_INPUTS];
 };
-const char* ctk_cem_batch_name(int env, bool log);
-// c: K, the std constants and timeout_s only (its / tag0 / seq and the pointers are the records' and descriptors'); a: the shared template
+static_assert(sizeof(CtkCemBatchStep) % 16 == 0, "the per-problem constants lie behind the step records, 16-aligned");
+// per_problem: the form whose constants come from device memory (ctk_cem_batch_pp<ENV, TRAJ>), one element per step record
+const char* ctk_cem_batch_name(int env, bool log, bool per_problem = false);
+// c: K, the std constants and timeout_s only (its / tag0 / seq and the pointers are the records' and descriptors'); a: the shared template.
+// k_steps_dev == nullptr: ctk_cem_batch, every problem with the constants of `params`; else ctk_cem_batch_pp, record j of steps_dev with
+// element j of k_steps_dev (stride ctk_mppi_batch_k_stride(env), filled by ctk_mppi_batch_derive_k; `params` unused)
 hipError_t ctk_launch_cem_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const CemFusedLaunch& c,
-                                const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* steps_dev, int n_problems, bool log);
+                                const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* steps_dev, int n_problems, bool log,
+                                const void* k_steps_dev = nullptr);
 int ctk_cem_fused_blocks(int N);        // workgroups of a problem (64 rollouts each)
 size_t ctk_cem_fused_lds(int N, int H); // dynamic LDS of a launch, bytes
 

@@ -412,14 +412,6 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_resident(const ResidentAr
     }
 }
 
-// stride of the per-problem constants array (ctk_mppi_batch_pp): sizeof(K) rounded up to 16, which also keeps every element aligned
-template <int ENV>
-struct CtkBatchKStride {
-    using K = typename Env<ENV>::K;
-    static_assert(std::is_trivially_copyable<K>::value && alignof(K) <= 16, "the derived constants travel as bytes");
-    static constexpr size_t value = (sizeof(K) + 15) & ~(size_t)15;
-};
-
 // ---------------------------------------------------------------------------------------------
 // The BATCH form (include/ctk_hip.h: ctk_batch_*): B independent problems of one configuration in ONE launch — the same step, the same
 // statements (ctk_mppi_body.inc, unchanged, FORM 0), around per-problem inputs.  Grid (workgroups per problem, problems of this launch):

@@ -523,12 +523,15 @@ int ctk_problem_params_differ(const ctk_batch* b);                              
  * CTK_OPT_CEM; a family of its own, added without an ABI bump).  A handle's one-launch CEM step occupies 64 of the chip's 256 CUs at
  * the BASELINE size (N 4096) and 8 at N 512; B handles step one after another.  A batch steps them in launches of the kernel
  * ctk_cem_batch<ENV, TRAJ>, grid (workgroups per problem, problems of the launch).
- *  - shared by all problems: everything in ctk_config and the parameter table (ctk_cem_batch_set_param writes it for all);
- *    per problem: state, previous input, mean and stdev, last output, Philox seed and position, step count, draws, readable buffers;
+ *  - shared by all problems: everything in ctk_config (environment, N, H, limits, CEM constants);
+ *    per problem: state, previous input, mean and stdev, last output, Philox seed and position, step count, draws, readable buffers and
+ *    the parameter table (plant, cost weights, targets: ctk_cem_problem_set_param below);
  *  - CONTRACT: problem p behaves bit for bit like a ctk_handle created from the same ctk_config (optimizer = CTK_OPT_CEM, ODE predictor)
  *    with seed = seeds[p] that received the same calls: u, CTK_BUF_U_NOM (the mean), STD, J, Q, TRAJ, BEST_IDX, the Philox position and
  *    the ctk_get_state vector (mu[H,C] | std[H,C] | u[C] | count), for every sample source, u_prev given or NULL, and any interleaving
- *    of whole-batch steps, subset steps, per-problem resets and ctk_cem_batch_set_state;
+ *    of whole-batch steps, subset steps, per-problem resets, ctk_cem_batch_set_state and parameter changes (ctk_set_param is one of
+ *    those calls: ctk_cem_problem_set_param on problem p, or ctk_cem_batch_set_param on all of them), also where a problem's warm-up
+ *    step shares a launch with other problems' short steps;
  *  - plain CEM with the analytic (ODE) predictor at the sizes of the one-launch step (at most 128 workgroups of 64 rollouts and 128 KiB
  *    of LDS per problem) and cem_best_k <= num_rollouts; everything else is CTK_ERR_UNSUPPORTED with the sizes in
  *    ctk_cem_batch_last_error(NULL), as is n_problems < 1.  The variants (naive-grad, Bharadhwaj, GMM) run as single handles.
@@ -545,6 +548,19 @@ int ctk_problem_params_differ(const ctk_batch* b);                              
  *    nothing is launched and nothing is consumed (step them in separate calls);
  *  - ctk_cem_batch_step is synchronous.  CTK_ERR_STATE = a bounded device-side wait ran out for the problems the message names; the
  *    other problems' outputs are valid and written.  A batch is NOT thread-safe.
+ *  - parameters: every problem has its own table [CTK_MAX_PARAMS], initialised with the environment's defaults.
+ *    ctk_cem_batch_set_param(id, v) writes column id of EVERY problem's table (the other ids stay per problem) and of the shared table
+ *    that ctk_cem_batch_get_param reads, so ctk_cem_batch_get_param returns the last whole-batch value of id, NOT what a problem holds
+ *    after a ctk_cem_problem_set_param (ctk_cem_problem_get_param reads that).  ctk_cem_problem_set_param sets parameter id of the listed
+ *    problems (ids as above; values[n], one per listed problem, in the order of ids), legal only between steps; a bad id list, a bad
+ *    parameter id, NULL values or a NULL batch is CTK_ERR_INVALID_ARGUMENT and nothing is written.  The kernel constants of a problem
+ *    whose table changed are re-derived when that problem is next stepped (as ctk_set_param derives a handle's) and travel behind the
+ *    step records, in the records' one transfer: new values before every step cost no transfer of their own.  Once a
+ *    ctk_cem_problem_set_param has succeeded, ctk_cem_problem_params_differ is 1 for the rest of the batch's life (0 before, and for a
+ *    NULL batch) and the steps launch the per-problem form of the kernel, ctk_cem_batch_pp<ENV, TRAJ> (ctk_cem_batch_dominant_kernel
+ *    names the form the next step launches); a batch that never calls it runs the shared form.  ctk_cem_batch_reset and
+ *    ctk_cem_batch_set_state leave the tables alone, as ctk_reset and ctk_set_state leave a handle's: they are not part of the state
+ *    vector.
  * Each entry corresponds to the single-handle call named beside it.
  * ----------------------------------------------------------------------------------------- */
 typedef struct ctk_cem_batch ctk_cem_batch;
@@ -564,6 +580,9 @@ int ctk_cem_batch_get_param(const ctk_cem_batch* b, int id, float* value);      
 int ctk_cem_batch_rng_get_position(const ctk_cem_batch* b, int problem, uint32_t* call);        /* ctk_rng_get_position */
 int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call);               /* ctk_rng_set_position */
 const char* ctk_cem_batch_dominant_kernel(const ctk_cem_batch* b);                              /* ctk_dominant_kernel */
+int ctk_cem_problem_set_param(ctk_cem_batch* b, int n_ids, const int32_t* ids, int id, const float* values);   /* ctk_set_param of every listed problem */
+int ctk_cem_problem_get_param(const ctk_cem_batch* b, int problem, int id, float* value);       /* ctk_get_param of one problem */
+int ctk_cem_problem_params_differ(const ctk_cem_batch* b);                                      /* 1 once a ctk_cem_problem_set_param has succeeded */
 
 #ifdef __cplusplus
 }
