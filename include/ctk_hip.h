@@ -348,6 +348,8 @@ int ctk_mppi_step_end(ctk_handle* h, const float* parts_dev, int n_parts, float*
  *   ctk_shard_finish(h, u_out)                                          CEM :99-102 / random :68
  * samples_it: this iteration's draws only ([N,H,C]); cand_dev / cands_all_dev are device pointers
  * and cands_all_dev must stay valid until ctk_shard_finish.  K = cem_best_k (CEM) or 1.
+ * K is GLOBAL while num_rollouts is the shard's own N: every shard contributes K candidates, so a CEM shard needs
+ * cem_best_k <= num_rollouts (ctk_create refuses it otherwise) — the documented limit of CEM sharding.
  * ----------------------------------------------------------------------------------------- */
 size_t ctk_shard_candidates_size(const ctk_handle* h);
 int ctk_shard_iterations(const ctk_handle* h);

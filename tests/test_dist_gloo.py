@@ -1,7 +1,7 @@
-"""CPU, world_size = 2, gloo: the sharded-MPPI collective plumbing (control_toolkit_amd/dist.py).
+"""CPU, world_size = 2, 3 and 4, gloo: the sharded-MPPI collective plumbing (control_toolkit_amd/dist.py).
 The engine is replaced by a tiny stand-in built on the oracle (test infrastructure) that writes
 the same (2+P)-float record libctk_hip.so writes; the test checks that one all-gather + replicated
-merge reproduces the single-process result on both ranks."""
+merge reproduces the single-process result on every rank."""
 import os
 import sys
 
@@ -74,10 +74,11 @@ def _worker(rank, world, port, N, H, p, noise, s, out_q):
 
 
 @pytest.mark.timeout(120)
-def test_sharded_mppi_two_ranks_gloo():
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_sharded_mppi_two_ranks_gloo(world):
     sys.path.insert(0, ROOT)
     from oracle import ctk_oracle as O
-    N, H, p, steps = 128, 20, 5, 3
+    N, H, p, steps = 132, 20, 5, 3                                # 132 rollouts: equal shards at every world size
     rng = np.random.default_rng(0)
     P = O.num_inducing_points(H, p)
     noise = rng.standard_normal((steps, N, P, 1)).astype(np.float32)
@@ -87,8 +88,8 @@ def test_sharded_mppi_two_ranks_gloo():
     ref = [float(full.step(s, noise[t])) for t in range(steps)]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29500 + (os.getpid() % 2000)
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, N, H, p, noise, s, q)) for r in range(2)]
+    port = 29500 + ((os.getpid() + 97 * world) % 2000)
+    procs = [ctx.Process(target=_worker, args=(r, world, port, N, H, p, noise, s, q)) for r in range(world)]
     for pr in procs:
         pr.start()
     res = [q.get(timeout=100) for _ in procs]
@@ -96,7 +97,8 @@ def test_sharded_mppi_two_ranks_gloo():
         pr.join(timeout=30)
         assert pr.exitcode == 0
     res.sort(key=lambda r: r[0])
-    np.testing.assert_array_equal(res[0][1], res[1][1])             # identical on both ranks, no 2nd collective
+    for r in res[1:]:
+        np.testing.assert_array_equal(res[0][1], r[1])              # identical on every rank, no 2nd collective
     np.testing.assert_allclose(res[0][1], ref, rtol=1e-4, atol=2e-5)
     np.testing.assert_allclose(res[0][2], full.u_nom, rtol=1e-4, atol=2e-5)
 
@@ -259,7 +261,8 @@ def _topk_worker(rank, world, port, kind, N, H, K, noise, s, out_q):
 
 @pytest.mark.timeout(180)
 @pytest.mark.parametrize("kind", ["cem", "random_action"])
-def test_sharded_topk_two_ranks_gloo(kind):
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_sharded_topk_two_ranks_gloo(kind, world):
     sys.path.insert(0, ROOT)
     from oracle import ctk_oracle as O
     N, H, K, steps, its = 96, 12, 10, 3, (3 if kind == "cem" else 1)
@@ -275,16 +278,19 @@ def test_sharded_topk_two_ranks_gloo(kind):
         ref = [float(full.step(s, noise[t, 0])) for t in range(steps)]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29500 + ((os.getpid() + (313 if kind == "cem" else 717)) % 2000)
-    procs = [ctx.Process(target=_topk_worker, args=(r, 2, port, kind, N, H, K, noise, s, q)) for r in range(2)]
+    port = 29500 + ((os.getpid() + (313 if kind == "cem" else 717) + 97 * world) % 2000)
+    procs = [ctx.Process(target=_topk_worker, args=(r, world, port, kind, N, H, K, noise, s, q)) for r in range(world)]
     for pr in procs:
         pr.start()
     res = sorted([q.get(timeout=150) for _ in procs], key=lambda r: r[0])
     for pr in procs:
         pr.join(timeout=30)
         assert pr.exitcode == 0
-    np.testing.assert_array_equal(res[0][1], res[1][1])          # replicated selection: identical on both ranks
-    np.testing.assert_array_equal(res[0][4], res[1][4])
+    for r in res[1:]:
+        np.testing.assert_array_equal(res[0][1], r[1])           # replicated selection: identical on every rank
+        np.testing.assert_array_equal(res[0][4], r[4])
+        np.testing.assert_array_equal(res[0][2], r[2])
+        np.testing.assert_array_equal(res[0][3], r[3])
     np.testing.assert_allclose(res[0][1], ref, rtol=1e-6, atol=1e-7)
     if kind == "cem":
         np.testing.assert_allclose(res[0][2], full.dist_mue, rtol=1e-6, atol=1e-7)
@@ -394,10 +400,11 @@ def _rpgd_worker(rank, world, port, N, H, p, k, outer_its, resamp_per, reset_dra
 
 
 @pytest.mark.timeout(240)
-def test_sharded_rpgd_two_ranks_gloo():
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_sharded_rpgd_two_ranks_gloo(world):
     sys.path.insert(0, ROOT)
     from oracle import ctk_oracle as O
-    N, H, p, k, outer_its, resamp_per, steps = 32, 12, 4, 6, 2, 2, 4
+    N, H, p, k, outer_its, resamp_per, steps = 36, 12, 4, 10, 2, 2, 4      # 36 rollouts: equal shards at every world size; k 10 > N_local 9 at world 4
     rng = np.random.default_rng(11)
     P = O.num_inducing_points(H, p)
     reset_draws = rng.random((N, P, 1), dtype=np.float32)
@@ -411,18 +418,19 @@ def test_sharded_rpgd_two_ranks_gloo():
     ref = [float(full.step(s_seq[t], fresh[t])) for t in range(steps)]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29500 + ((os.getpid() + 1201) % 2000)
-    procs = [ctx.Process(target=_rpgd_worker, args=(r, 2, port, N, H, p, k, outer_its, resamp_per, reset_draws, fresh, s_seq, q))
-             for r in range(2)]
+    port = 29500 + ((os.getpid() + 1201 + 97 * world) % 2000)
+    procs = [ctx.Process(target=_rpgd_worker, args=(r, world, port, N, H, p, k, outer_its, resamp_per, reset_draws, fresh, s_seq, q))
+             for r in range(world)]
     for pr in procs:
         pr.start()
     res = sorted([q.get(timeout=200) for _ in procs], key=lambda r: r[0])
     for pr in procs:
         pr.join(timeout=30)
         assert pr.exitcode == 0
-    np.testing.assert_array_equal(res[0][1], res[1][1])
+    for r in res[1:]:
+        np.testing.assert_array_equal(res[0][1], r[1])
     np.testing.assert_allclose(res[0][1], ref, rtol=1e-6, atol=1e-7)
     for j, ref_arr in ((2, full.Q), (3, full.opt.m), (4, full.opt.v)):
-        got = np.concatenate([res[0][j], res[1][j]], 0)        # the two shards ARE the global population, row for row
+        got = np.concatenate([r[j] for r in res], 0)           # the shards ARE the global population, row for row
         np.testing.assert_allclose(got, ref_arr, rtol=1e-6, atol=1e-7)
-    np.testing.assert_array_equal(np.concatenate([res[0][5], res[1][5]]), full.trajectory_ages)
+    np.testing.assert_array_equal(np.concatenate([r[5] for r in res]), full.trajectory_ages)
