@@ -164,6 +164,23 @@ SYMBOLS = {
     "ctk_cem_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "ctk_cem_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
     "ctk_cem_problem_params_differ": (C.c_int, [_H]),
+    # batched RPGD (ctk_rpgd_batch_*): _H is the ctk_rpgd_batch* there
+    "ctk_rpgd_batch_create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
+    "ctk_rpgd_batch_destroy": (None, [_H]),
+    "ctk_rpgd_batch_last_error": (C.c_char_p, [_H]),
+    "ctk_rpgd_batch_size": (C.c_int, [_H]),
+    "ctk_rpgd_batch_samples_needed": (C.c_size_t, [_H, C.c_int]),
+    "ctk_rpgd_batch_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "ctk_rpgd_batch_reset": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "ctk_rpgd_batch_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_rpgd_batch_get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_rpgd_batch_set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_rpgd_batch_set_param": (C.c_int, [_H, C.c_int, C.c_float]),
+    "ctk_rpgd_batch_get_param": (C.c_int, [_H, C.c_int, _FP]),
+    "ctk_rpgd_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
+    "ctk_rpgd_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
+    "ctk_rpgd_batch_dominant_kernel": (C.c_char_p, [_H]),
+    "ctk_rpgd_template_descent_lds": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
 }
 
 
@@ -1072,3 +1089,196 @@ class CtkCemBatch:
 
     def dominant_kernel(self) -> str:
         return self._lib.ctk_cem_batch_dominant_kernel(self._h).decode()
+
+
+# ---- batched RPGD (include/ctk_hip.h: ctk_rpgd_batch_*) -------------------------------------------------------------------------------
+class CtkRpgdBatch:
+    """Owns one ctk_rpgd_batch: num_problems independent RPGD controllers of ONE configuration (the RPGD keywords of CtkEngine) with at
+    most 64 plans each, any subset of them stepped by ONE kernel launch: descent, keep-k selection and warm start of every listed problem.
+    Problem p behaves bit for bit like CtkEngine("rpgd", "ODE", seed=seeds[p], generic_kernels=True, ...) given the same calls (reset,
+    step, set_state, set_param, set_rng_position).  seeds: one per problem (default seed + p).
+    generic_kernels: None means True for this class — the batch kernel is the template descent; CartPole's tuned descent (what
+    CtkEngine runs with generic_kernels=False) has no batch form, and generic_kernels=False for CartPole is refused rather than
+    silently differing from such an engine.  The other environments have template kernels only."""
+
+    def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "rpgd", predictor: str = "ODE",
+                 num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
+                 period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
+                 materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
+                 num_control_inputs: int = None, generic_kernels: bool = None, **kw):
+        # what needs no device is checked before the library is asked for one
+        if int(num_problems) < 1:
+            raise ValueError(f"a batch holds at least one problem (num_problems == {num_problems})")
+        B = int(num_problems)
+        if optimizer != "rpgd":
+            raise NotImplementedError(f"an RPGD batch steps RPGD controllers only (optimizer {optimizer!r}); MPPI has CtkMppiBatch, plain CEM "
+                                      "CtkCemBatch, the gradient variant and the other optimizers run as CtkEngine")
+        if predictor != "ODE":
+            raise NotImplementedError(f"the batch kernel descends through the analytic (ODE) predictor only (predictor {predictor!r}); "
+                                      "network predictors run as CtkEngine")
+        if seeds is not None:
+            seeds = np.ascontiguousarray(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in np.asarray(seeds, dtype=object).reshape(-1)], np.uint64))
+            if seeds.size != B:
+                raise ValueError(f"seeds must have one entry per problem ({B}), got {seeds.size}")
+        unknown = set(kw) - set(_CONFIG_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown engine arguments: {sorted(unknown)}")
+        lib, env_id = environment_library(environment)
+        S, Cn, self.param_names = environment_info(environment)
+        self.environment, self.S, self.C, self.B = environment, S, Cn, B
+        cfg = _make_config("rpgd", "ODE", env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                           action_low=action_low, action_high=action_high,
+                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                           global_rollout_offset=global_rollout_offset, num_states=S if num_states is None else num_states,
+                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs,
+                           generic_kernels=True if generic_kernels is None else generic_kernels, **kw)
+        self._lib, self.cfg = lib, cfg
+        self.N, self.H, self.K = int(num_rollouts), int(mpc_horizon), int(cfg.opt_keep_k)
+        self._h = _H()
+        rc = lib.ctk_rpgd_batch_create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
+        if rc != 0:
+            msg = lib.ctk_rpgd_batch_last_error(None).decode()
+            self._h = _H()
+            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(msg)
+        # preallocated argument buffers, as CtkEngine.step's: rows 0 .. n-1 are the stepped problems'
+        self._s = np.zeros((B, S), np.float32)
+        self._up = np.zeros((B, Cn), np.float32)
+        self._u = np.zeros((B, Cn), np.float32)
+        self._ids = np.zeros(B, np.int32)
+        self._s_p, self._up_p, self._u_p, self._ids_p = (a.ctypes.data for a in (self._s, self._up, self._u, self._ids))
+        self._step_fn = lib.ctk_rpgd_batch_step
+        self._need_fn = lib.ctk_rpgd_batch_samples_needed
+
+    def _check(self, rc: int):
+        if rc != 0:
+            msg = self._lib.ctk_rpgd_batch_last_error(self._h).decode()
+            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(f"[ctk {rc}] {msg}")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.ctk_rpgd_batch_destroy(self._h)
+            self._h = _H()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.B
+
+    def _problem(self, problem: int) -> int:
+        if not 0 <= int(problem) < self.B:
+            raise ValueError(f"problem index {problem} is outside 0 .. {self.B - 1}")
+        return int(problem)
+
+    def samples_needed(self, problem: int = 0) -> int:
+        """draws the NEXT step of `problem` consumes: (N - opt_keep_k) * P * C when it resamples (count % resamp_per == 0), else 0"""
+        return int(self._need_fn(self._h, self._problem(problem)))
+
+    def samples_needed_reset(self) -> int:
+        """draws the reset of ONE problem consumes (N * P * C)"""
+        P = -(-(self.H - 1) // int(self.cfg.period_interpolation_inducing_points)) + 1
+        return self.N * P * self.C
+
+    def step(self, S, samples=None, u_prev=None, ids=None) -> np.ndarray:
+        """S [n, num_states], one row per stepped problem in the order of ids (None: all problems).  samples: None (device Philox), or a
+        host array (any shape) / an int device pointer holding the concatenation, in id order, of one [N - opt_keep_k, P, C] block for
+        exactly those listed problems whose samples_needed is non-zero; a host array of another total size is a ValueError with both
+        numbers and changes nothing.  u_prev [n, C] or None (every problem's own last output).  Returns u [n, C].  A listed problem that
+        was never reset: CtkError naming it, nothing is launched."""
+        idv, n, _ = batch_step_args(self.B, self.S, self.C, 0, S, None, u_prev, ids)       # ids, states, u_prev
+        self._s[:n] = np.asarray(S).reshape(n, self.S)
+        up_p = None
+        if u_prev is not None:
+            self._up[:n] = np.asarray(u_prev).reshape(n, self.C)
+            up_p = self._up_p
+        ids_p = None
+        if idv is not None:
+            self._ids[:n] = idv
+            ids_p = self._ids_p
+        if samples is None:
+            sp, cnt, loc = None, 0, LOC_NONE
+        elif type(samples) is int:     # a device buffer has no size of its own: what the listed problems draw
+            sp, loc = samples, LOC_DEVICE
+            cnt = sum(self.samples_needed(p) for p in (range(self.B) if idv is None else idv.tolist()))
+        else:
+            samples = _f32(samples)
+            sp, cnt, loc = samples.ctypes.data, samples.size, LOC_HOST
+        rc = self._step_fn(self._h, n, ids_p, self._s_p, up_p, sp, cnt, loc, self._u_p)
+        if rc:
+            self._check(rc)
+        self.last_u = self._u[:n].copy()
+        return self.last_u
+
+    def reset(self, draws=None, ids=None):
+        """optimizer_reset of the listed problems (None: all) in one launch.  draws: None (device Philox, every problem at its own
+        position), a host array [n, N, P, C] or an int device pointer to one, one block per listed problem in id order."""
+        idv = batch_ids(self.B, ids)
+        n = self.B if idv is None else int(idv.size)
+        if draws is None:
+            dp, loc = None, LOC_NONE
+        elif type(draws) is int:
+            dp, loc = draws, LOC_DEVICE
+        else:
+            draws = _f32(draws)
+            if draws.size != n * self.samples_needed_reset():
+                raise ValueError(f"reset of {n} problems consumes {n} x {self.samples_needed_reset()} draws ([n, N, P, C]), got shape {tuple(draws.shape)}")
+            dp, loc = draws.ctypes.data, LOC_HOST
+        self._check(self._lib.ctk_rpgd_batch_reset(self._h, 0 if idv is None else idv.size, _ptr(idv), dp, loc))
+
+    def read(self, name: str, problem: int) -> np.ndarray:
+        N, H, Cn = self.N, self.H, self.C
+        shapes = {"Q": (N, H, Cn), "J": (N,), "U_NOM": (1, H, Cn), "PLAN": (N, H, Cn), "ADAM_M": (N, H, Cn), "ADAM_V": (N, H, Cn),
+                  "AGES": (N,), "AGES_LOGGED": (N,), "BEST_IDX": (self.K,)}
+        if name not in shapes:
+            raise ValueError(f"an RPGD batch has the buffers {sorted(shapes)}, not {name!r}")
+        out = np.empty(shapes[name], np.float32)
+        self._check(self._lib.ctk_rpgd_batch_read(self._h, self._problem(problem), BUFFERS[name], _ptr(out), out.size))
+        return out.astype(np.int64) if name == "BEST_IDX" else out
+
+    def read_all(self, name: str) -> np.ndarray:
+        return np.stack([self.read(name, p) for p in range(self.B)])
+
+    def state_size(self) -> int:
+        return 3 * self.N * self.H * self.C + self.N + self.C + 2
+
+    @staticmethod
+    def descent_lds(environment: str, mpc_horizon: int):
+        """(dynamic LDS bytes of a problem's workgroup, whether the state tape is part of it) — ctk_rpgd_template_descent_lds; when the
+        tape does not fit it lives in device memory, one slice per problem.  Needs no device."""
+        lib, env_id = environment_library(environment)
+        fits = C.c_int()
+        return int(lib.ctk_rpgd_template_descent_lds(env_id, int(mpc_horizon), C.byref(fits))), bool(fits.value)
+
+    def get_state(self, problem: int) -> np.ndarray:
+        """population, Adam m, Adam v [N,H,C] | ages [N] | u [C] | adam_step | count of one problem (CtkEngine.get_state of an RPGD engine)"""
+        buf = np.empty(self.state_size(), np.float32)
+        self._check(self._lib.ctk_rpgd_batch_get_state(self._h, self._problem(problem), _ptr(buf), buf.size))
+        return buf
+
+    def set_state(self, problem: int, state):
+        st = _f32(state).ravel()
+        self._check(self._lib.ctk_rpgd_batch_set_state(self._h, self._problem(problem), _ptr(st), st.size))
+
+    def set_param(self, name: str, value: float):
+        """parameter `name` of every problem (one table for the batch)"""
+        self._check(self._lib.ctk_rpgd_batch_set_param(self._h, self.param_names.index(name), float(value)))
+
+    def get_param(self, name: str) -> float:
+        v = C.c_float()
+        self._check(self._lib.ctk_rpgd_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
+        return v.value
+
+    def rng_position(self, problem: int) -> int:
+        v = C.c_uint32()
+        self._check(self._lib.ctk_rpgd_batch_rng_get_position(self._h, self._problem(problem), C.byref(v)))
+        return int(v.value)
+
+    def set_rng_position(self, problem: int, call: int):
+        self._check(self._lib.ctk_rpgd_batch_rng_set_position(self._h, self._problem(problem), int(call) & 0xFFFFFFFF))
+
+    def dominant_kernel(self) -> str:
+        return self._lib.ctk_rpgd_batch_dominant_kernel(self._h).decode()

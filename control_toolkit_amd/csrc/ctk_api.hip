@@ -3270,3 +3270,490 @@ int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call)
 }
 
 }  // extern "C"
+
+// =============================================================================================
+// Batched RPGD (include/ctk_hip.h: ctk_rpgd_batch_*): B independent RPGD problems of one configuration with at most
+// CTK_RPGD_FUSED_MAX_N plans each, stepped by launches of ctk_g_rpgd_batch<ENV> (ctk_generic.hip) — one workgroup per problem runs the
+// descent, the keep-k selection and the warm start that a template handle runs as three launches.  One allocation per buffer kind with a
+// problem stride — no handles inside.  Per-problem host state is what an RPGD handle keeps: the sequence number of its next step, its
+// Philox position, its step count (which decides the iterations of its next step and whether it resamples), its Adam step number, which
+// buffer holds its population, and whether it has been reset.  No workgroup of the kernel waits for another, so a call is split into
+// launches only at the grid's y limit.
+// =============================================================================================
+struct ctk_rpgd_batch {
+    ctk_config cfg{};
+    int B = 0, N = 0, H = 0, P = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, PC = 0, K = 0;
+    float params[CTK_MAX_PARAMS]{};         // one table for all problems (ctk_rpgd_batch_set_param); the launcher derives the constants from it
+    hipStream_t stream = nullptr;
+    InterpEntry* d_interp = nullptr;        // [H] shared
+    float* d_bc = nullptr; int bc_len = 0;  // shared bias-correction table
+    float* d_pop[2] = {nullptr, nullptr};   // [B][N,H,C] each
+    float* d_m[2] = {nullptr, nullptr};
+    float* d_v[2] = {nullptr, nullptr};
+    float* d_ages[2] = {nullptr, nullptr};  // [B][N] each
+    float* d_J = nullptr;                   // [B][N]
+    int* d_idx = nullptr;                   // [B][N]
+    float* d_unom = nullptr;                // [B][H,C]
+    float* d_u = nullptr;                   // [B][CTK_MAX_INPUTS]
+    float* d_scratch = nullptr; size_t scratch_stride = 0;   // [B][H * NT * 64] state tapes that do not fit in LDS
+    float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
+    float* h_u_dev = nullptr;
+    CtkRpgdBatchDesc* d_desc = nullptr;     // [B]
+    CtkRpgdBatchStep* h_steps = nullptr;    // pinned [B]: the records of the step (or reset) being issued
+    CtkRpgdBatchStep* d_steps = nullptr;
+    float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
+    std::vector<uint32_t> seq, call;
+    std::vector<int> count, adam_step;
+    std::vector<unsigned char> cur, ready;
+    std::string err, dominant;
+    size_t NHC() const { return (size_t)N * HC; }
+    float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
+    float* slot(int p) const { return h_u + (size_t)p * 16; }
+    size_t state_size() const { return 3 * NHC() + (size_t)N + C + 2; }   // ctk_state_size of an RPGD handle
+    int its(int p) const {                  // rpgd_iterations
+        const int first = cfg.warmup ? cfg.warmup_iterations : cfg.outer_its;
+        return count[(size_t)p] == 0 ? first : cfg.outer_its;
+    }
+    bool resamples(int p) const { return count[(size_t)p] % cfg.resamp_per == 0; }   // optimizer_rpgd.py:449
+    size_t needs(int p) const { return (resamples(p) && K < N) ? (size_t)(N - K) * PC : 0; }   // samples_needed of an RPGD handle
+};
+
+namespace {
+
+int rfail(ctk_rpgd_batch* b, int code, const std::string& msg) {
+    if (b) b->err = msg; else g_create_error = msg;
+    return code;
+}
+#define RHIP_TRY(b, expr)                                                                       \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess)                                                                   \
+            return rfail((b), CTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
+    } while (0)
+
+// the problems a call addresses (batch_ids of the MPPI family): ids[0..n) strictly ascending, or all of them (ids == NULL)
+int rpgd_batch_ids(ctk_rpgd_batch* b, const char* who, int n_ids, const int32_t* ids, int* n_out) {
+    if (!ids) { *n_out = b->B; return CTK_OK; }
+    if (n_ids < 1 || n_ids > b->B) return rfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": n_ids must be 1 .. " + std::to_string(b->B) + " (the batch size)");
+    for (int j = 0; j < n_ids; ++j) {
+        if (ids[j] < 0 || ids[j] >= b->B)
+            return rfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(ids[j]) + " is outside 0 .. " + std::to_string(b->B - 1));
+        if (j > 0 && ids[j] <= ids[j - 1]) return rfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": ids must be strictly ascending");
+    }
+    *n_out = n_ids;
+    return CTK_OK;
+}
+int rpgd_batch_problem(ctk_rpgd_batch* b, const char* who, int p) {
+    if (p < 0 || p >= b->B) return rfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(p) + " is outside 0 .. " + std::to_string(b->B - 1));
+    return CTK_OK;
+}
+
+// the shared template of a launch's RolloutArgs (make_args of an RPGD handle's descent without what the step records and descriptors supply)
+RolloutArgs rpgd_batch_args(const ctk_rpgd_batch* b) {
+    RolloutArgs a{};
+    for (int c = 0; c < b->C; ++c) { a.lo[c] = b->cfg.action_low[c]; a.hi[c] = b->cfg.action_high[c]; }
+    a.C = b->C;
+    a.N = b->N; a.H = b->H; a.P = b->H;
+    a.p_magic = ctk_magic_of(b->H);
+    a.identity_interp = b->cfg.period_interpolation_inducing_points == 1 ? 1 : 0;
+    a.inv_Hp1 = 1.0f / (float)(b->H + 1);
+    a.interp = b->d_interp;
+    a.stream_id = 0;
+    a.global_row0 = b->cfg.global_rollout_offset;
+    return a;
+}
+// what the launches take of the warm start's description: keep_k, P, the sampling constants, the interpolation table
+RpgdFusedWarm rpgd_batch_warm(const ctk_rpgd_batch* b) {
+    const ctk_config& c = b->cfg;
+    return RpgdFusedWarm{b->K, nullptr, b->P, 0, 0, c.shift_previous, c.sampling_distribution, 0, c.sample_whole_control_space, c.sample_stdev,
+                         c.sample_mean, c.sample_min, c.sample_max, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b->d_interp,
+                         nullptr, nullptr, nullptr, 0u};
+}
+
+// host-supplied draws into the staging buffer (resolve_samples of a handle): n floats
+int rpgd_batch_stage(ctk_rpgd_batch* b, const float* src, size_t n) {
+    if (n > b->samples_cap) {
+        if (b->d_samples) RHIP_TRY(b, hipFree(b->d_samples));
+        b->d_samples = nullptr; b->samples_cap = 0;
+        RHIP_TRY(b, hipMalloc((void**)&b->d_samples, n * sizeof(float)));
+        b->samples_cap = n;
+    }
+    RHIP_TRY(b, hipMemcpyAsync(b->d_samples, src, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    return CTK_OK;
+}
+
+constexpr int RPGD_BATCH_MAX_GRID_Y = 65535;   // problems of one launch: the grid's y limit, nothing else bounds it
+
+}  // namespace
+
+extern "C" {
+
+size_t ctk_rpgd_template_descent_lds(int environment, int mpc_horizon, int* tape_in_lds) {
+    if (tape_in_lds) *tape_in_lds = 0;
+    if (!env_info(environment) || mpc_horizon < 1) return 0;
+    bool fits = false;
+    const size_t lds = ctk_g_rpgd_descent_lds(environment, mpc_horizon, &fits);
+    if (tape_in_lds) *tape_in_lds = fits ? 1 : 0;
+    return lds;
+}
+
+const char* ctk_rpgd_batch_last_error(const ctk_rpgd_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+int ctk_rpgd_batch_size(const ctk_rpgd_batch* b) { return b ? b->B : 0; }
+size_t ctk_rpgd_batch_samples_needed(const ctk_rpgd_batch* b, int problem) { return (b && problem >= 0 && problem < b->B) ? b->needs(problem) : 0; }
+const char* ctk_rpgd_batch_dominant_kernel(const ctk_rpgd_batch* b) { return b ? b->dominant.c_str() : ""; }
+
+void ctk_rpgd_batch_destroy(ctk_rpgd_batch* b) {
+    if (!b) return;
+    hipSetDevice(b->cfg.device);
+    if (b->stream) hipStreamSynchronize(b->stream);
+    void* bufs[] = {b->d_interp, b->d_bc, b->d_pop[0], b->d_pop[1], b->d_m[0], b->d_m[1], b->d_v[0], b->d_v[1], b->d_ages[0], b->d_ages[1],
+                    b->d_J, b->d_idx, b->d_unom, b->d_u, b->d_scratch, b->d_desc, b->d_steps, b->d_samples};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (b->h_u) hipHostFree(b->h_u);
+    if (b->h_steps) hipHostFree(b->h_steps);
+    if (b->stream) hipStreamDestroy(b->stream);
+    delete b;
+}
+
+int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_rpgd_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return rfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: NULL argument");
+    if (n_problems < 1) return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    const EnvInfo* einfo = nullptr;
+    if (int rc = check_config("ctk_rpgd_batch_create", cfg, &einfo)) return rc;
+    const int N = cfg->num_rollouts, H = cfg->mpc_horizon, HC = H * einfo->C;
+    if (cfg->optimizer != CTK_OPT_RPGD)
+        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: an RPGD batch steps RPGD controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+                     ", num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + "); MPPI has ctk_batch_create, plain CEM ctk_cem_batch_create, the "
+                     "gradient variant (CTK_OPT_GRADIENT) and the other optimizers run as single handles (ctk_create)");
+    if (cfg->predictor != CTK_PRED_ODE)
+        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: the batch kernel descends through the analytic (ODE) predictor only (cfg.predictor == " +
+                     std::to_string(cfg->predictor) + ", num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) +
+                     "); network predictors run as single handles (ctk_create)");
+    if (cfg->environment == CTK_ENV_CARTPOLE && cfg->generic_kernels == 0)
+        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: CartPole's tuned descent (ctk_rpgd_descent, what a handle with generic_kernels == 0 runs) has no "
+                     "batch form; the template kernels do: set cfg.generic_kernels = 1, and compare with handles created the same way (num_rollouts " +
+                     std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ")");
+    if (N > CTK_RPGD_FUSED_MAX_N)
+        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: num_rollouts " + std::to_string(N) + " exceeds " + std::to_string(CTK_RPGD_FUSED_MAX_N) +
+                     ", the population one workgroup holds (a problem's whole step runs in one workgroup); such a controller runs as a single handle (ctk_create)");
+    if (cfg->opt_keep_k > N)
+        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: opt_keep_k " + std::to_string(cfg->opt_keep_k) + " exceeds num_rollouts " + std::to_string(N) +
+                     ": the plans a problem keeps are part of its population");
+    if (cfg->materialize_trajectories)
+        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: materialize_trajectories is not built for a batch (num_rollouts " + std::to_string(N) +
+                     ", mpc_horizon " + std::to_string(H) + "): the logging rollout sits between descent and warm start, and the one launch has no seam for it; "
+                     "such a controller runs as a single handle (ctk_create)");
+    bool tape_in_lds = false;
+    const size_t lds = ctk_g_rpgd_descent_lds(cfg->environment, H, &tape_in_lds);
+    if (lds > 160 * 1024)
+        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: mpc_horizon " + std::to_string(H) + " x " + std::to_string(einfo->C) + " inputs = " +
+                     std::to_string(HC) + " columns need " + std::to_string(lds) + " bytes of LDS without the state tape; a workgroup has 163840 (160 KiB)");
+    if (cfg->opt_keep_k < 1 || cfg->outer_its < 0 || cfg->resamp_per < 1 || cfg->shift_previous < 0 || (cfg->warmup && cfg->warmup_iterations < 0) ||
+        (cfg->sampling_distribution != 0 && cfg->sampling_distribution != 1))
+        return rfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: RPGD needs opt_keep_k >= 1, outer_its >= 0, resamp_per >= 1, shift_previous >= 0, "
+                     "warmup_iterations >= 0, sampling_distribution in {0,1}");
+    if (cfg->intermediate_steps != 1)
+        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: the RPGD adjoint is built for intermediate_steps == 1 (given " + std::to_string(cfg->intermediate_steps) + ")");
+    if (cfg->adam_rule != 0 && cfg->adam_rule != 1)
+        return rfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: adam_rule must be 0 (the reference's torch ADAM) or 1 (tf.keras.optimizers.Adam)");
+
+    hipDeviceProp_t prop;
+    if (int rc = probe_device("ctk_rpgd_batch_create", cfg->device, &prop)) return rc;
+
+    ctk_rpgd_batch* b = new ctk_rpgd_batch();
+    b->cfg = *cfg;
+    b->B = n_problems; b->N = N; b->H = H; b->K = cfg->opt_keep_k;
+    b->P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
+    b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = HC; b->PC = b->P * einfo->C;
+    default_params(b->env, b->params);
+    b->scratch_stride = tape_in_lds ? 0 : ctk_g_rpgd_scratch_floats(b->env, N, H);
+    b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u);
+    b->count.assign((size_t)n_problems, 0); b->adam_step.assign((size_t)n_problems, 0);
+    b->cur.assign((size_t)n_problems, 0); b->ready.assign((size_t)n_problems, 0);
+    b->dominant = ctk_g_rpgd_batch_name(b->env);
+
+    auto bail = [&](int rc) { g_create_error = b->err; ctk_rpgd_batch_destroy(b); return rc; };
+#define RHIP_CREATE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { b->err = std::string(#expr) + ": " + hipGetErrorString(_e); return bail(CTK_ERR_HIP); } } while (0)
+    RHIP_CREATE(hipSetDevice(cfg->device));
+    RHIP_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    const size_t Bz = (size_t)n_problems, NHC = b->NHC();
+    auto dev_zero = [&](void** p, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+        return e != hipSuccess ? e : hipMemsetAsync(*p, 0, bytes ? bytes : 1, b->stream);
+    };
+    for (int i = 0; i < 2; ++i) {
+        RHIP_CREATE(dev_zero((void**)&b->d_pop[i], Bz * NHC * sizeof(float)));
+        RHIP_CREATE(dev_zero((void**)&b->d_m[i], Bz * NHC * sizeof(float)));
+        RHIP_CREATE(dev_zero((void**)&b->d_v[i], Bz * NHC * sizeof(float)));
+        RHIP_CREATE(dev_zero((void**)&b->d_ages[i], Bz * N * sizeof(float)));
+    }
+    RHIP_CREATE(dev_zero((void**)&b->d_J, Bz * N * sizeof(float)));
+    RHIP_CREATE(dev_zero((void**)&b->d_idx, Bz * N * sizeof(int)));
+    RHIP_CREATE(dev_zero((void**)&b->d_unom, Bz * HC * sizeof(float)));
+    RHIP_CREATE(dev_zero((void**)&b->d_u, Bz * CTK_MAX_INPUTS * sizeof(float)));
+    RHIP_CREATE(dev_zero((void**)&b->d_scratch, Bz * b->scratch_stride * sizeof(float)));
+    RHIP_CREATE(dev_zero((void**)&b->d_desc, Bz * sizeof(CtkRpgdBatchDesc)));
+    RHIP_CREATE(dev_zero((void**)&b->d_steps, Bz * sizeof(CtkRpgdBatchStep)));
+    RHIP_CREATE(hipHostMalloc((void**)&b->h_u, Bz * 64, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(b->h_u, 0, Bz * 64);
+    RHIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
+    RHIP_CREATE(hipHostMalloc((void**)&b->h_steps, Bz * sizeof(CtkRpgdBatchStep), hipHostMallocDefault));
+    std::memset(b->h_steps, 0, Bz * sizeof(CtkRpgdBatchStep));
+
+    std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, b->P);
+    RHIP_CREATE(dev_zero((void**)&b->d_interp, (size_t)H * sizeof(InterpEntry)));
+    RHIP_CREATE(hipMemcpyAsync(b->d_interp, tab.data(), (size_t)H * sizeof(InterpEntry), hipMemcpyHostToDevice, b->stream));
+    // bias corrections 1 - beta^t in double, rounded to fp32: the table of a handle (ctk_create)
+    b->bc_len = 32768;
+    std::vector<float> bc((size_t)2 * b->bc_len);
+    for (int tt = 1; tt <= b->bc_len; ++tt) {
+        bc[2 * (tt - 1)] = (float)(1.0 - std::pow((double)cfg->adam_beta_1, (double)tt));
+        bc[2 * (tt - 1) + 1] = (float)(1.0 - std::pow((double)cfg->adam_beta_2, (double)tt));
+    }
+    RHIP_CREATE(dev_zero((void**)&b->d_bc, bc.size() * sizeof(float)));
+    RHIP_CREATE(hipMemcpyAsync(b->d_bc, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+
+    std::vector<CtkRpgdBatchDesc> desc(Bz);
+    for (int p = 0; p < n_problems; ++p) {
+        const size_t z = (size_t)p;
+        const uint64_t seed = seeds ? seeds[p] : cfg->seed + (uint64_t)p;
+        CtkRpgdBatchDesc& d = desc[z];
+        for (int i = 0; i < 2; ++i) {
+            d.pop[i] = b->d_pop[i] + z * NHC; d.m[i] = b->d_m[i] + z * NHC; d.v[i] = b->d_v[i] + z * NHC;
+            d.ages[i] = b->d_ages[i] + z * N;
+        }
+        d.J = b->d_J + z * N; d.idx = b->d_idx + z * N; d.u_nom = b->d_unom + z * HC;
+        d.u_dev = b->u(p); d.u_host = b->h_u_dev + z * 16;
+        d.scratch = b->d_scratch + z * b->scratch_stride;
+        d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
+    }
+    RHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkRpgdBatchDesc), hipMemcpyHostToDevice, b->stream));
+    RHIP_CREATE(hipStreamSynchronize(b->stream));                  // the host vectors go out of scope below
+#undef RHIP_CREATE
+    *out = b;
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_reset(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* draws, int draws_loc) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = rpgd_batch_ids(b, "ctk_rpgd_batch_reset", n_ids, ids, &n)) return rc;
+    const size_t per = (size_t)b->N * b->PC;           // sample_actions of a whole population: [N,P,C] per problem
+    const float* d_draws = nullptr;
+    if (draws_loc != CTK_LOC_NONE) {
+        if (draws == nullptr) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "draws pointer is NULL but draws_loc != CTK_LOC_NONE");
+        if (draws_loc != CTK_LOC_DEVICE && draws_loc != CTK_LOC_HOST) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "bad draws_loc");
+    }
+    RHIP_TRY(b, hipSetDevice(b->cfg.device));
+    if (draws_loc == CTK_LOC_DEVICE) d_draws = draws;
+    else if (draws_loc == CTK_LOC_HOST) {
+        if (int rc = rpgd_batch_stage(b, draws, (size_t)n * per)) return rc;
+        d_draws = b->d_samples;
+    }
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        CtkRpgdBatchStep& q = b->h_steps[j];
+        q = CtkRpgdBatchStep{};
+        q.id = p; q.call = b->call[(size_t)p]; q.cur = b->cur[(size_t)p];
+        q.draws = d_draws ? d_draws + (size_t)j * per : nullptr;
+    }
+    RHIP_TRY(b, hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkRpgdBatchStep), hipMemcpyHostToDevice, b->stream));
+    const RolloutArgs a = rpgd_batch_args(b);
+    const RpgdFusedWarm f = rpgd_batch_warm(b);
+    for (int done = 0; done < n;) {                    // ONE launch for the call (more only past the grid's y limit)
+        const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - done);
+        RHIP_TRY(b, ctk_launch_rpgd_batch_reset(b->stream, a, f, b->d_desc, b->d_steps + done, cnt));
+        done += cnt;
+    }
+    RHIP_TRY(b, hipStreamSynchronize(b->stream));
+    for (int j = 0; j < n; ++j) {                      // rpgd_reset of a handle: parameters, the sequence number and the buffer index stay
+        const size_t z = (size_t)(ids ? ids[j] : j);
+        b->count[z] = 0; b->adam_step[z] = 0; b->ready[z] = 1;
+        ++b->call[z];
+    }
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples,
+                        size_t n_samples, int samples_loc, float* u_out) {
+    if (!b || !s) return b ? rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = rpgd_batch_ids(b, "ctk_rpgd_batch_step", n_ids, ids, &n)) return rc;
+    size_t need = 0;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        if (!b->ready[(size_t)p])
+            return rfail(b, CTK_ERR_STATE, "ctk_rpgd_batch_step: problem " + std::to_string(p) + " was never reset: call ctk_rpgd_batch_reset (optimizer_reset) "
+                         "before its first step; nothing was launched");
+        need += b->needs(p);
+    }
+    if (samples_loc != CTK_LOC_NONE) {
+        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+        if (n_samples != need)                          // refused before a sample is read
+            return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: " + std::to_string(n_samples) + " samples given, the listed problems need " +
+                         std::to_string(need) + " (one [num_rollouts - opt_keep_k, P, C] block for every listed problem whose ctk_rpgd_batch_samples_needed is "
+                         "non-zero, in id order); nothing was launched");
+        if (need != 0 && samples == nullptr) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+    }
+    RHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const float* d_s = nullptr;                        // the first block; the blocks follow one another in the order of the listed problems that draw
+    if (samples_loc == CTK_LOC_DEVICE && need) d_s = samples;
+    else if (samples_loc == CTK_LOC_HOST && need) {
+        if (int rc = rpgd_batch_stage(b, samples, need)) return rc;
+        d_s = b->d_samples;
+    }
+    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es)
+    size_t off = 0;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        const size_t z = (size_t)p;
+        CtkRpgdBatchStep& q = b->h_steps[j];
+        q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.cur = b->cur[z];
+        q.iters = b->its(p); q.t0 = b->adam_step[z]; q.resample = b->resamples(p) ? 1 : 0;
+        q.dev_uprev = u_prev ? 0u : 1u;
+        const size_t cnt = b->needs(p);
+        q.draws = (d_s && cnt) ? d_s + off : nullptr;
+        off += d_s ? cnt : 0;
+        q.pad = 0;
+        for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
+        for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
+    }
+    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkRpgdBatchStep), hipMemcpyHostToDevice, b->stream);
+    const RolloutArgs a = rpgd_batch_args(b);
+    const RpgdFusedWarm f = rpgd_batch_warm(b);
+    const ctk_config& c = b->cfg;
+    int launched = 0;                                  // consecutive launches only past the grid's y limit; a problem never spans launches
+    while (le == hipSuccess && launched < n) {
+        const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - launched);
+        le = ctk_launch_g_rpgd_batch(b->stream, b->env, a, b->params, c.dt, c.intermediate_steps, c.learning_rate, c.adam_beta_1, c.adam_beta_2,
+                                     c.adam_epsilon, c.gradmax_clip, c.adam_rule == 1 ? 1 : 0, b->d_bc, b->bc_len, f, b->d_desc, b->d_steps + launched, cnt);
+        if (le == hipSuccess) launched += cnt;
+    }
+    // completion: every launched problem's {u, seq} store landing in its pinned slot (finish_step's bounded spin, one budget for all).
+    // h_steps is both the source of the transfer above and, below, the host's memory of id / seq / iters for the bookkeeping: that holds
+    // because the call is synchronous (nothing refills h_steps before it returns); an asynchronous step would need its own copy.
+    bool synced = false;
+    int spins = 0;
+    std::string late;
+    for (int j = 0; j < launched; ++j) {
+        const int p = b->h_steps[j].id;
+        const uint32_t want = b->seq[(size_t)p];
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 1;
+        while (*slot != want) {
+            if (!synced && ++spins < 4000000) { __builtin_ia32_pause(); continue; }
+            if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
+            break;
+        }
+        if (*slot != want) late += (late.empty() ? "" : ", ") + std::to_string(p);
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int j = 0; j < n; ++j) {
+        const int p = b->h_steps[j].id;
+        const size_t z = (size_t)p;
+        if (j >= launched) continue;                   // never issued: nothing on the device carries its numbers, nothing advances
+        ++b->seq[z];
+        b->adam_step[z] += b->h_steps[j].iters;        // as rpgd_descent / rpgd_step: with the launch
+        b->cur[z] ^= 1; ++b->count[z];
+        if (reinterpret_cast<volatile uint32_t*>(b->slot(p))[1] != b->h_steps[j].seq) continue;   // never published (a device fault): finish_step
+        ++b->call[z];                                  // returns before it advances the Philox position or reads u
+        volatile float* sl = reinterpret_cast<volatile float*>(b->slot(p));
+        if (u_out) {
+            u_out[(size_t)j * b->C] = sl[0];
+            for (int cc = 1; cc < b->C; ++cc) u_out[(size_t)j * b->C + cc] = sl[4 + cc];   // publish_u_vec
+        }
+    }
+    if (le != hipSuccess) return rfail(b, CTK_ERR_HIP, std::string("ctk_rpgd_batch_step: ") + hipGetErrorString(le));
+    if (!late.empty()) return rfail(b, CTK_ERR_HIP, "ctk_rpgd_batch_step: the step finished without publishing the result of problem(s) " + late);
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_read(ctk_rpgd_batch* b, int problem, int buffer, float* dst, size_t cap) {
+    if (!b || !dst) return b ? rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: NULL destination") : CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = rpgd_batch_problem(b, "ctk_rpgd_batch_read", problem)) return rc;
+    const size_t z = (size_t)problem, N = (size_t)b->N, NHC = b->NHC();
+    const int cur = b->cur[z];
+    const float* src = nullptr; size_t n = 0; bool is_int = false;
+    switch (buffer) {                                  // locate_buffer of an RPGD handle
+        case CTK_BUF_Q: src = b->d_pop[cur ^ 1] + z * NHC; n = NHC; break;
+        case CTK_BUF_PLAN: src = b->d_pop[cur] + z * NHC; n = NHC; break;
+        case CTK_BUF_ADAM_M: src = b->d_m[cur] + z * NHC; n = NHC; break;
+        case CTK_BUF_ADAM_V: src = b->d_v[cur] + z * NHC; n = NHC; break;
+        case CTK_BUF_AGES: src = b->d_ages[cur] + z * N; n = N; break;
+        case CTK_BUF_AGES_LOGGED: src = b->d_ages[cur ^ 1] + z * N; n = N; break;
+        case CTK_BUF_J: src = b->d_J + z * N; n = N; break;
+        case CTK_BUF_U_NOM: src = b->d_unom + z * b->HC; n = (size_t)b->HC; break;
+        case CTK_BUF_BEST_IDX: src = reinterpret_cast<const float*>(b->d_idx + z * N); n = (size_t)b->K; is_int = true; break;
+        default: return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: an RPGD batch has Q, J, U_NOM, PLAN, ADAM_M, ADAM_V, AGES, AGES_LOGGED and BEST_IDX");
+    }
+    if (cap < n) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: destination too small (" + std::to_string(n) + " floats)");
+    RHIP_TRY(b, hipSetDevice(b->cfg.device));
+    RHIP_TRY(b, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    RHIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (is_int) for (size_t i = 0; i < n; ++i) { int v; std::memcpy(&v, &dst[i], 4); dst[i] = (float)v; }
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_get_state(ctk_rpgd_batch* b, int problem, float* dst, size_t cap) {
+    if (!b || !dst) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = rpgd_batch_problem(b, "ctk_rpgd_batch_get_state", problem)) return rc;
+    if (cap < b->state_size()) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_get_state: destination too small (" + std::to_string(b->state_size()) + " floats)");
+    const size_t z = (size_t)problem, N = (size_t)b->N, NHC = b->NHC();
+    const int cur = b->cur[z];
+    RHIP_TRY(b, hipSetDevice(b->cfg.device));
+    RHIP_TRY(b, hipMemcpyAsync(dst, b->d_pop[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    RHIP_TRY(b, hipMemcpyAsync(dst + NHC, b->d_m[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    RHIP_TRY(b, hipMemcpyAsync(dst + 2 * NHC, b->d_v[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    RHIP_TRY(b, hipMemcpyAsync(dst + 3 * NHC, b->d_ages[cur] + z * N, N * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    RHIP_TRY(b, hipMemcpyAsync(dst + 3 * NHC + N, b->u(problem), (size_t)b->C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    RHIP_TRY(b, hipStreamSynchronize(b->stream));
+    dst[3 * NHC + N + b->C] = (float)b->adam_step[z];
+    dst[3 * NHC + N + b->C + 1] = (float)b->count[z];
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_set_state(ctk_rpgd_batch* b, int problem, const float* src, size_t n) {
+    if (!b || !src) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = rpgd_batch_problem(b, "ctk_rpgd_batch_set_state", problem)) return rc;
+    if (n != b->state_size()) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_set_state: wrong state size (" + std::to_string(b->state_size()) + " floats)");
+    const size_t z = (size_t)problem, N = (size_t)b->N, NHC = b->NHC();
+    const int cur = b->cur[z];
+    RHIP_TRY(b, hipSetDevice(b->cfg.device));
+    RHIP_TRY(b, hipMemcpyAsync(b->d_pop[cur] + z * NHC, src, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    RHIP_TRY(b, hipMemcpyAsync(b->d_m[cur] + z * NHC, src + NHC, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    RHIP_TRY(b, hipMemcpyAsync(b->d_v[cur] + z * NHC, src + 2 * NHC, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    RHIP_TRY(b, hipMemcpyAsync(b->d_ages[cur] + z * N, src + 3 * NHC, N * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    RHIP_TRY(b, hipMemcpyAsync(b->u(problem), src + 3 * NHC + N, (size_t)b->C * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    b->adam_step[z] = (int)src[3 * NHC + N + b->C]; b->count[z] = (int)src[3 * NHC + N + b->C + 1];
+    b->ready[z] = 1;
+    RHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_set_param(ctk_rpgd_batch* b, int id, float value) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (id < 0 || id >= env_info(b->env)->n_params) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_set_param: unknown parameter id for this environment");
+    b->params[id] = value;                             // every launch derives its constants from the table, as a template handle's does
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_get_param(const ctk_rpgd_batch* b, int id, float* value) {
+    if (!b || !value || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->params[id];
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32_t* call) {
+    if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *call = b->call[(size_t)problem];
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_rng_set_position(ctk_rpgd_batch* b, int problem, uint32_t call) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = rpgd_batch_problem(b, "ctk_rpgd_batch_rng_set_position", problem)) return rc;
+    b->call[(size_t)problem] = call;
+    return CTK_OK;
+}
+
+}  // extern "C"

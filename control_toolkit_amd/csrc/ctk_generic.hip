@@ -15,12 +15,15 @@
 //   ctk_g_rpgd_descent<ENV>         all Adam iterations of one MPC step in one launch: forward with a state tape,
 //        reverse sweep through Env::step_vjp + cost gradients, per-plan clip_by_norm, Adam, clip, final cost pass
 //        (optimizer_rpgd.py:306-338, :342)
+//   ctk_g_rpgd_batch<ENV>           B independent RPGD problems of at most 64 plans, one workgroup each: the descent above (the same
+//        text, ctk_g_rpgd_body.inc), then keep-k selection and warm start in the same launch (ctk_rpgd_warm.h)
 // The block-record merge (ctk_mppi_merge<false>), the selection (ctk_select_topk), the refit (ctk_cem_refit) and the
 // RPGD warm start are shared with the CartPole kernels: they only ever see P*C / H*C columns.
 #include <type_traits>
 #include "ctk_rollout.h"
 #include "ctk_env.h"
 #include "ctk_adam.h"
+#include "ctk_rpgd_warm.h"
 #include "ctk_launch.h"
 
 constexpr int G_TRAJ = 64;
@@ -237,150 +240,49 @@ __global__ __launch_bounds__(GR_BLOCK) void ctk_g_rpgd_descent(RolloutArgs a, ty
                                                               float* __restrict__ m, float* __restrict__ v,
                                                               const float* __restrict__ bc_table, int bc_len, int t0, int iters,
                                                               float* __restrict__ scratch, int tape_in_lds) {
-    using E = Env<ENV>;
-    constexpr int S = E::S, C = E::C;
-    extern __shared__ float lds[];
-    const int H = a.H, HC = H * C;
-    float* q_s = lds;                        // [HC][65]
-    float* g_s = q_s + HC * GR_LD;           // [HC][65]
-    float* sc_s = g_s + HC * GR_LD;          // [64]
-    float* tape_l = sc_s + G_TRAJ;           // [H][NT][64]
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int row0 = blockIdx.x * G_TRAJ;
-    const int rows = min(G_TRAJ, a.N - row0);
-    const int total = rows * HC;
-    const size_t gbase = (size_t)row0 * HC;
-    constexpr int NT = E::NT;                // taped values per step (Env::fwd_tape / bwd_tape: the sweep recomputes nothing)
-    float* tape = tape_in_lds ? tape_l : scratch + (size_t)blockIdx.x * H * NT * 64;
+    const RolloutArgs& lim = a;
+#include "ctk_g_rpgd_body.inc"
+}
 
-    for (int i = t; i < G_TRAJ * HC; i += GR_BLOCK) {      // a.p_magic = ceil(2^32 / HC)
-        const int r = HC >= 2 ? (int)__umulhi((uint32_t)i, a.p_magic) : i, hc = i - r * HC;
-        q_s[hc * GR_LD + r] = i < total ? Q[gbase + i] : 0.0f;
-    }
-    __syncthreads();
+// The batch form (include/ctk_hip.h: ctk_rpgd_batch_*): grid (1, problems of this launch), a problem's whole population in ONE workgroup
+// (N <= 64, host-checked).  The prologue rebuilds ctk_g_rpgd_descent's arguments from the step record of blockIdx.y and the descriptor it
+// names (both read-only, wave-uniform); the descent is the handle kernel's text; behind it comes what a template handle runs as two more
+// launches, ctk_select_topk and ctk_rpgd_warmstart (rpgd_fused_tail: the fence and barrier make this launch's Q, m, v, J visible first).
+// No workgroup waits for another.
+static_assert(GR_BLOCK == RPGD_TAIL_BLOCK, "rpgd_fused_tail strides by the workgroup size");
 
-    float up0[C];
+template <int ENV>
+__global__ __launch_bounds__(GR_BLOCK) void ctk_g_rpgd_batch(RolloutArgs a_tpl, typename Env<ENV>::K k, AdamK ad,
+                                                            const float* __restrict__ bc_table, int bc_len, int tape_in_lds, FusedWarm fw_tpl,
+                                                            const CtkRpgdBatchDesc* __restrict__ desc,
+                                                            const CtkRpgdBatchStep* __restrict__ steps) {
+    const CtkRpgdBatchStep& rec = steps[blockIdx.y];
+    const CtkRpgdBatchDesc& d = desc[rec.id];
+    const RolloutArgs& lim = a_tpl;                // the limits are read where the kernel argument lies (ctk_g_rpgd_body.inc)
+    RolloutArgs a = a_tpl;                         // sizes, p_magic, inv_Hp1, global_row0 (launcher)
 #pragma unroll
-    for (int c = 0; c < C; ++c) up0[c] = a.u_prev_dev ? a.u_prev_dev[c] : a.u_prev[c];
-    const float inv = a.inv_Hp1;
-
-    // forward pass of a gradient iteration: no cost, NT taped values per step; the final state in sF
-    auto forward_tape = [&](float (&sF)[S]) {
-        float s[S];
+    for (int i = 0; i < Env<ENV>::S; ++i) a.s0[i] = rec.s[i];
 #pragma unroll
-        for (int i = 0; i < S; ++i) s[i] = a.s0[i];
-        float un[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) un[c] = q_s[c * GR_LD + lane];
-        for (int h = 0; h < H; ++h) {
-            float u[C], tp[NT];
-#pragma unroll
-            for (int c = 0; c < C; ++c) u[c] = un[c];
-            if (h + 1 < H) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) un[c] = q_s[((h + 1) * C + c) * GR_LD + lane];
-            }
-            E::fwd_tape(k, s, u, tp);
-#pragma unroll
-            for (int i = 0; i < NT; ++i) tape[((size_t)h * NT + i) * 64 + lane] = tp[i];
-        }
-#pragma unroll
-        for (int i = 0; i < S; ++i) sF[i] = s[i];
-    };
-    // get_action's cost pass (:342): the recurrence of the sampling kernels (Env::cost_step, checked fallback) + the input-only terms
-    auto final_cost = [&]() {
-        float u[C], up[C], cin = 0.0f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) up[c] = up0[c];
-        for (int h = 0; h < H; ++h) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) u[c] = q_s[(h * C + c) * GR_LD + lane];
-            cin += E::input_cost(k, u, up);
-#pragma unroll
-            for (int c = 0; c < C; ++c) up[c] = u[c];
-        }
-        auto run = [&](auto fast) {
-            constexpr bool FAST = decltype(fast)::value;
-            float s[S], csum = 0.0f, amax = 0.0f;
-#pragma unroll
-            for (int i = 0; i < S; ++i) s[i] = a.s0[i];
-            float un[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) un[c] = q_s[c * GR_LD + lane];
-            for (int h = 0; h < H; ++h) {
-                float f[C];
-#pragma unroll
-                for (int c = 0; c < C; ++c) f[c] = E::prep_input(k, un[c], c);
-                if (h + 1 < H) {
-#pragma unroll
-                    for (int c = 0; c < C; ++c) un[c] = q_s[((h + 1) * C + c) * GR_LD + lane];
-                }
-                E::template cost_step<FAST>(k, s, f, csum, amax);
-            }
-            const float J = csum + E::terminal_cost(k, s);
-            return __builtin_amdgcn_ballot_w64(FAST && E::out_of_range(amax)) != 0 ? __builtin_nanf("") : J;
-        };
-        float J = E::fast_ok(k) ? run(std::true_type{}) : __builtin_nanf("");
-        if (__builtin_amdgcn_ballot_w64(J != J) != 0) J = run(std::false_type{});   // wave-uniform: Euler sub-steps or an angle out of range
-        return (J + cin) * inv;
-    };
-
-    for (int it = 0; it < iters; ++it) {
-        if (wave == 0) {
-            float sH[S], lam[S];
-            forward_tape(sH);
-            E::terminal_grad(k, sH, lam);
-#pragma unroll
-            for (int i = 0; i < S; ++i) lam[i] *= inv;
-            float nrm2 = 0.0f;
-            float gp_next[C];                 // d stage_{h+1} / d u_h (through u_prev of the next step)
-#pragma unroll
-            for (int c = 0; c < C; ++c) gp_next[c] = 0.0f;
-            for (int h = H - 1; h >= 0; --h) {
-                float tp[NT], u[C], upv[C];
-#pragma unroll
-                for (int i = 0; i < NT; ++i) tp[i] = tape[((size_t)h * NT + i) * 64 + lane];
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    u[c] = q_s[(h * C + c) * GR_LD + lane];
-                    upv[c] = h > 0 ? q_s[((h - 1) * C + c) * GR_LD + lane] : up0[c];
-                }
-                float du[C], gu[C], gp[C];
-                E::bwd_tape(k, tp, u, lam, du, inv);
-                E::input_grad(k, u, upv, gu, gp);
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float g = (gu[c] + gp_next[c]) * inv + du[c];
-                    g_s[(h * C + c) * GR_LD + lane] = g;
-                    nrm2 += g * g;
-                    gp_next[c] = gp[c];
-                }
-            }
-            sc_s[lane] = ad.clip / fmaxf(sqrtf(nrm2), ad.clip);       // clip_by_norm over [H,C] (:315,:334)
-        }
-        __syncthreads();
-        const int ti = t0 + it + 1;
-        const float bc1 = ti <= bc_len ? bc_table[2 * (ti - 1)] : 1.0f;
-        const float bc2 = ti <= bc_len ? bc_table[2 * (ti - 1) + 1] : 1.0f;
-        for (int i = t; i < total; i += GR_BLOCK) {
-            const int r = HC >= 2 ? (int)__umulhi((uint32_t)i, a.p_magic) : i, hc = i - r * HC, c = hc % C;
-            float mm = 0.0f, vv = 0.0f;
-            if (ad.rule != 2) { mm = m[gbase + i]; vv = v[gbase + i]; }
-            const float g = g_s[hc * GR_LD + r] * sc_s[r];
-            q_s[hc * GR_LD + r] = adam_update(ad, q_s[hc * GR_LD + r], g, mm, vv, bc1, bc2, a.lo[c], a.hi[c]);
-            if (ad.rule != 2) { m[gbase + i] = mm; v[gbase + i] = vv; }
-        }
-        __syncthreads();
-    }
-    if (wave == 0) {                          // get_action's forward pass (:342)
-        const float J = final_cost();
-        if (row0 + lane < a.N) a.J[row0 + lane] = J;
-    }
-    __syncthreads();
-    for (int i = t; i < total; i += GR_BLOCK) {
-        const int r = HC >= 2 ? (int)__umulhi((uint32_t)i, a.p_magic) : i, hc = i - r * HC;
-        Q[gbase + i] = q_s[hc * GR_LD + r];
-    }
+    for (int c = 0; c < Env<ENV>::C; ++c) a.u_prev[c] = rec.u_prev[c];
+    a.u_prev_dev = rec.dev_uprev ? d.u_dev : nullptr;
+    a.J = d.J;
+    a.seed_lo = d.seed_lo; a.seed_hi = d.seed_hi; a.call = rec.call;
+    const uint32_t cur = rec.cur & 1u;
+    float* __restrict__ Q = d.pop[cur];
+    float* __restrict__ m = d.m[cur];
+    float* __restrict__ v = d.v[cur];
+    const int t0 = rec.t0, iters = rec.iters;
+    float* __restrict__ scratch = d.scratch;       // blockIdx.x == 0: the problem's own slice
+#include "ctk_g_rpgd_body.inc"
+    FusedWarm fw = fw_tpl;                         // K, P, shift_previous, the sampling constants, interp (launcher)
+    fw.idx_out = d.idx;
+    fw.w.n_new = rec.resample ? a.N - fw.K : 0;
+    fw.w.gather = rec.resample ? 1 : 0;
+    fw.p.draws = rec.draws;
+    fw.p.Q_old = Q; fw.p.m_old = m; fw.p.v_old = v; fw.p.ages_old = d.ages[cur];
+    fw.p.Q_new = d.pop[cur ^ 1u]; fw.p.m_new = d.m[cur ^ 1u]; fw.p.v_new = d.v[cur ^ 1u]; fw.p.ages_new = d.ages[cur ^ 1u];
+    fw.p.u_nom = d.u_nom; fw.p.u_dev = d.u_dev; fw.p.u_host = d.u_host; fw.p.seq = rec.seq;
+    rpgd_fused_tail(a, lim, fw, g_s, t, HC);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -473,6 +375,30 @@ hipError_t ctk_launch_g_rpgd_descent(hipStream_t st, int env, const RolloutArgs&
         const dim3 grid((a.N + G_TRAJ - 1) / G_TRAJ), block(GR_BLOCK);
         CTK_LAUNCH((ctk_g_rpgd_descent<EV>), grid, block, lds, st, e0, e1, a, k, ad, Q, m, v, bc_table, bc_len, t0, iters, scratch,
                    tape_in_lds ? 1 : 0);
+    });
+    return hipGetLastError();
+}
+
+
+const char* ctk_g_rpgd_batch_name(int env) { return ctk_kernel_name("ctk_g_rpgd_batch<%d>", env); }
+
+hipError_t ctk_launch_g_rpgd_batch(hipStream_t st, int env, const RolloutArgs& a_in, const float* params, float dt, int isteps, float lr,
+                                   float b1, float b2, float eps, float clip, int rule, const float* bc_table, int bc_len,
+                                   const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems) {
+    AdamK ad{lr, b1, b2, (float)(1.0 - (double)b1), (float)(1.0 - (double)b2), eps, clip, rule};
+    CTK_FOR_ENV(env, EV, {
+        using E = Env<EV>;
+        const RolloutArgs a = ctk_descent_args(a_in, E::C);
+        const typename E::K k = E::derive(params, dt, isteps);
+        bool tape_in_lds = false;
+        const size_t lds = ctk_g_rpgd_descent_lds(env, a.H, &tape_in_lds);
+        FusedWarm fw{};
+        fw.enabled = 1; fw.K = f.K;
+        fw.w = WarmArgs{a.N, a.H, f.P, 0, 0, f.shift_previous, f.sampling_distribution, 0, f.sample_stdev, f.sample_mean, f.sample_min,
+                        f.sample_max, f.whole_space, nullptr, 0, 0, 0};
+        fw.p.interp = f.interp;
+        const dim3 grid(1, n_problems), block(GR_BLOCK);
+        hipLaunchKernelGGL((ctk_g_rpgd_batch<EV>), grid, block, lds, st, a, k, ad, bc_table, bc_len, tape_in_lds ? 1 : 0, fw, desc_dev, steps_dev);
     });
     return hipGetLastError();
 }

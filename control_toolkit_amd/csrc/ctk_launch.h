@@ -358,6 +358,41 @@ hipError_t ctk_launch_rpgd_warmstart(hipStream_t st, const RolloutArgs& a, int N
                                      float* Q_new, float* m_new, float* v_new, float* ages_new, const InterpEntry* interp,
                                      float* u_nom, float* u_dev, float* u_host, uint32_t seq, const float* recs = nullptr,
                                      int rs = 0, int keeper_base = 0, int fresh_tail = 0);
+// the BATCH form of the RPGD step (ctk_generic.hip: ctk_g_rpgd_batch<ENV>; include/ctk_hip.h: ctk_rpgd_batch_*): B independent problems of ONE
+// configuration with at most CTK_RPGD_FUSED_MAX_N plans each, one workgroup per problem, grid (1, problems of this launch).  As for
+// ctk_mppi_batch and ctk_cem_batch, what differs per problem reaches the kernel through two arrays in device memory, both read-only to
+// it: the descriptor [B] (the problem's buffers; written once, at creation) and the step records [problems of this step] (written by
+// the host into pinned memory, ONE transfer ahead of the launches).  blockIdx.y picks the step record, its id the descriptor.
+struct CtkRpgdBatchDesc {
+    float* pop[2]; float* m[2]; float* v[2];   // [N,H,C] population and Adam moments, ping-pong
+    float* ages[2];                     // [N]
+    float* J;                           // [N]
+    int* idx;                           // [N] idx[0 .. keep_k) = the keepers, ascending cost (BEST_IDX)
+    float* u_nom;                       // [H,C] the best plan before the warm start
+    float* u_dev;                       // [C] the problem's own last output
+    float* u_host;                      // pinned {u, seq} slot (16 floats)
+    float* scratch;                     // [H * NT * 64] the state tape when it does not fit in LDS
+    uint32_t seed_lo, seed_hi;          // Philox key
+};
+struct CtkRpgdBatchStep {
+    int32_t id;                         // problem index = descriptor index
+    uint32_t seq;                       // published with u
+    uint32_t call;                      // Philox position
+    uint32_t cur;                       // which buffer holds the current population (the warm start writes the other one; a reset this one)
+    int32_t iters;                      // Adam iterations of THIS problem's step (warm-up or outer_its)
+    int32_t t0;                         // Adam steps the problem has taken (bias correction)
+    int32_t resample;                   // 1: keep the best keep_k plans and draw N - keep_k fresh ones (count % resamp_per == 0)
+    uint32_t dev_uprev;                 // 1: the previous input is the problem's own last output (u_prev == NULL at the API)
+    const float* draws;                 // this problem's draws [N - keep_k, P, C] (reset: [N, P, C]; device pointer) or nullptr: Philox
+    uint64_t pad;
+    float s[CTK_MAX_STATES];
+    float u_prev[CTK_MAX_INPUTS];
+};
+static_assert(sizeof(CtkRpgdBatchStep) % 16 == 0, "step records are copied and indexed as an array");
+// ctk_rpgd.hip: the warm start with reset = 1 (sample_actions of every plan, moments and ages 0) of n_problems records in ONE launch,
+// grid (blocks, problems); f: P, the sampling constants and interp only; the records' id / call / cur / draws are read
+hipError_t ctk_launch_rpgd_batch_reset(hipStream_t st, const RolloutArgs& a, const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev,
+                                       const CtkRpgdBatchStep* steps_dev, int n_problems);
 hipError_t ctk_launch_rpgd_pack_keepers(hipStream_t st, const float* J, const float* Q, const float* m, const float* v,
                                         const float* ages, const int* idx, int K, int H, int global_offset, float* out);
 
@@ -390,6 +425,13 @@ hipError_t ctk_launch_g_rpgd_descent(hipStream_t st, int env, const RolloutArgs&
                                      float b1, float b2, float eps, float clip, float* Q, float* m, float* v, const float* bc_table,
                                      int bc_len, int t0, int iters, float* scratch, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
                                      int rule = 0);
+// n_problems step records from `steps_dev` on as ONE launch of ctk_g_rpgd_batch<env>: descent, keep-k selection and warm start of every
+// problem.  a: the shared template (limits, sizes; s0 / u_prev / J / seed / call come from the records and descriptors); f: keep_k, P,
+// shift_previous, the sampling constants and interp (its pointers, n_new and gather are the records' and descriptors')
+const char* ctk_g_rpgd_batch_name(int env);
+hipError_t ctk_launch_g_rpgd_batch(hipStream_t st, int env, const RolloutArgs& a, const float* params, float dt, int isteps, float lr,
+                                   float b1, float b2, float eps, float clip, int rule, const float* bc_table, int bc_len,
+                                   const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems);
 
 // ---- ctk_generic_net.hip : the template kernels with a network predictor (net = CTK_PRED_MLP | CTK_PRED_GRU; ctk_net.h) -----
 // wperm: the policy's per-lane operand tables (forward | reverse), followed by the GRU's carried hidden state [64]

@@ -586,6 +586,64 @@ int ctk_cem_problem_set_param(ctk_cem_batch* b, int n_ids, const int32_t* ids, i
 int ctk_cem_problem_get_param(const ctk_cem_batch* b, int problem, int id, float* value);       /* ctk_get_param of one problem */
 int ctk_cem_problem_params_differ(const ctk_cem_batch* b);                                      /* 1 once a ctk_cem_problem_set_param has succeeded */
 
+/* -----------------------------------------------------------------------------------------
+ * batched RPGD: B independent RPGD controllers of ONE configuration stepped together (the counterpart of ctk_batch_* and
+ * ctk_cem_batch_* for CTK_OPT_RPGD; a family of its own, added without an ABI bump).  The reference's RPGD populations are 16 - 64
+ * plans: a whole step of such a controller is ONE workgroup, one CU of 256, and a template handle pays three launches for it (descent,
+ * selection, warm start).  A batch steps any subset of its problems with one launch of ctk_g_rpgd_batch<ENV>, grid (1, problems of
+ * the launch): descent, keep-k selection and warm start of every listed problem.
+ *  - shared by all problems: everything in ctk_config and the parameter table (ctk_rpgd_batch_set_param);
+ *    per problem: state, previous input, population, Adam moments and step number, ages, last output, Philox seed and position, step
+ *    count, draws and the readable buffers;
+ *  - CONTRACT: problem p behaves bit for bit like a ctk_handle created from the same ctk_config (optimizer = CTK_OPT_RPGD, ODE
+ *    predictor; for CartPole generic_kernels = 1, the template kernels) with seed = seeds[p] that received the same calls (ctk_reset,
+ *    ctk_step, ctk_set_state, ctk_set_param, ctk_rng_set_position): u, CTK_BUF_Q, J, U_NOM, PLAN, ADAM_M, ADAM_V, AGES, AGES_LOGGED,
+ *    BEST_IDX, the Philox position and the ctk_get_state vector (population, both moments [N,H,C] | ages [N] | u [C] | adam_step |
+ *    count), for every sample source, u_prev given or NULL, and any interleaving of whole-batch steps, subset steps, per-problem resets,
+ *    ctk_rpgd_batch_set_state and ctk_rpgd_batch_set_param — also where the problems of one launch differ in iteration count (the
+ *    first step after a reset runs warmup_iterations or outer_its), Adam step number or resampling (count % resamp_per);
+ *  - refused with CTK_ERR_UNSUPPORTED and the sizes in ctk_rpgd_batch_last_error(NULL), from the configuration alone (no device is
+ *    touched): an optimizer other than CTK_OPT_RPGD (CTK_OPT_GRADIENT included), a predictor other than ODE, num_rollouts > 64 (the
+ *    population one workgroup holds), opt_keep_k > num_rollouts, materialize_trajectories, a horizon whose plans and gradients alone
+ *    exceed 160 KiB of LDS, n_problems < 1, and CartPole with generic_kernels == 0: CartPole's tuned descent has no batch form, the
+ *    template kernels do — a batch never silently differs from the handle it is compared with;
+ *  - no workgroup of the kernel waits for another: a call is one launch whatever B is (consecutive launches only beyond 65535
+ *    problems, the grid's y limit; a problem never spans launches);
+ *  - ids: as for ctk_batch_step.  Rows of s [n,S], u_prev [n,C] (NULL: every problem's own last output) and u_out [n,C] follow the
+ *    order of ids.  A problem must have been reset (or had its state set) before its first step: else CTK_ERR_STATE names it and nothing
+ *    is launched, as for a handle;
+ *  - samples: ctk_rpgd_batch_samples_needed(b, p) is what p's NEXT step draws: (num_rollouts - opt_keep_k) * P * C when it resamples
+ *    (count % resamp_per == 0), else 0.  With samples_loc != CTK_LOC_NONE, `samples` is the concatenation, in id order, of one
+ *    [num_rollouts - opt_keep_k, P, C] block for exactly those listed problems whose number is non-zero, n_samples floats in all; a
+ *    wrong total is CTK_ERR_INVALID_ARGUMENT with both numbers, refused before a sample is read, and nothing changes;
+ *  - ctk_rpgd_batch_reset draws the initial populations (RPGD's reset does): draws [n,N,P,C] in id order, or NULL with
+ *    draws_loc = CTK_LOC_NONE for the in-kernel sampler; ONE launch for the call;
+ *  - ctk_rpgd_batch_step is synchronous.  A batch is NOT thread-safe.
+ * Each entry corresponds to the single-handle call named beside it.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct ctk_rpgd_batch ctk_rpgd_batch;
+/* Dynamic LDS (bytes) of one workgroup of the template RPGD descent (ctk_g_rpgd_descent<ENV>, ctk_g_rpgd_batch<ENV>) for `environment`
+ * at horizon mpc_horizon; *tape_in_lds (may be NULL) = 1 when the state tape of the reverse sweep is part of it, 0 when plans and
+ * gradients leave no room within 160 KiB and the tape lives in device memory (a batch: one slice per problem).  0 for an unknown
+ * environment or mpc_horizon < 1.  Needs no device. */
+size_t ctk_rpgd_template_descent_lds(int environment, int mpc_horizon, int* tape_in_lds);
+int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds /* NULL: cfg->seed + p */, ctk_rpgd_batch** out); /* ctk_create */
+void ctk_rpgd_batch_destroy(ctk_rpgd_batch* b);                                                 /* ctk_destroy */
+const char* ctk_rpgd_batch_last_error(const ctk_rpgd_batch* b);                                 /* ctk_last_error; b may be NULL */
+int ctk_rpgd_batch_size(const ctk_rpgd_batch* b);                                               /* B */
+size_t ctk_rpgd_batch_samples_needed(const ctk_rpgd_batch* b, int problem);                     /* ctk_samples_needed of one problem's next step */
+int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev,
+                        const float* samples, size_t n_samples, int samples_loc, float* u_out); /* ctk_step of every listed problem */
+int ctk_rpgd_batch_reset(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* draws, int draws_loc);   /* ctk_reset of every listed problem */
+int ctk_rpgd_batch_read(ctk_rpgd_batch* b, int problem, int buffer, float* dst, size_t cap);    /* ctk_read: CTK_BUF_Q, J, U_NOM, PLAN, ADAM_M, ADAM_V, AGES, AGES_LOGGED, BEST_IDX */
+int ctk_rpgd_batch_get_state(ctk_rpgd_batch* b, int problem, float* dst, size_t cap);           /* ctk_get_state: 3 N H C + N + C + 2 floats */
+int ctk_rpgd_batch_set_state(ctk_rpgd_batch* b, int problem, const float* src, size_t n);       /* ctk_set_state */
+int ctk_rpgd_batch_set_param(ctk_rpgd_batch* b, int id, float value);                           /* ctk_set_param, all problems */
+int ctk_rpgd_batch_get_param(const ctk_rpgd_batch* b, int id, float* value);                    /* ctk_get_param */
+int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32_t* call);      /* ctk_rng_get_position */
+int ctk_rpgd_batch_rng_set_position(ctk_rpgd_batch* b, int problem, uint32_t call);             /* ctk_rng_set_position */
+const char* ctk_rpgd_batch_dominant_kernel(const ctk_rpgd_batch* b);                            /* ctk_dominant_kernel */
+
 #ifdef __cplusplus
 }
 #endif
