@@ -620,7 +620,9 @@ int finish_step(ctk_handle* h, float* u_out) {
     // error word behind {u, seq}: a bounded device-side wait ran out (1: a peer's record never arrived,
     // ctk_mppi.hip:p2p_exchange_and_update; 2: a block record of the in-launch hand-off never arrived; 3: an RPGD Jacobian record never
     // arrived / non-finite gradient, ctk_net_split.hip: rpgd_jac_worker + the update's tile_bad) — the published
-    // result is NaN or built from a stale record, never silently wrong
+    // result is NaN or built from a stale record, never silently wrong.  (2, MPPI with u published ahead of the plan update: the launch
+    // may still be polling the whole records when this runs; if THAT poll runs out, the word is raised after the host has left and the
+    // NEXT step's finish_step finds it — the plan it stepped from held NaN.  The word is therefore cleared only where it is found.)
     volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(h->h_u) + 2;
     const uint32_t dev_err = errw[0], bad_tile = errw[1];              // (word 3: a tile of the RPGD update saw a non-finite gradient norm)
     if (dev_err || bad_tile) {

@@ -76,7 +76,16 @@ inline bool ctk_ll_records_ok(int blocks, int cols) {
 //              batch and one thread per column — what a launch within those sizes runs in either form, so the results do not depend on it
 //   OLD_RECUR  the recurrence without sin / cos one step ahead (ctk_env.h: recur_env_range): diagnostic switch CTK_MPPI_OLD_RECUR,
 //              bit for bit the same results (tests/test_gpu_mppi_pipelined.py)
-constexpr int CTK_MPPI_FORM_WIDE_TAIL = 1, CTK_MPPI_FORM_OLD_RECUR = 2;
+//   LATE_U     u = u_nom_new[0] is published by the final update, behind the plan update of all H entries — the order before FORM 0
+//              published it ahead of them (ctk_mppi_body_5_post.inc: EARLY_U): diagnostic switch CTK_MPPI_LATE_U, bit for bit the same
+//              results (tests/test_gpu_mppi_early_u.py).  Raised only where FORM 0 would take the early order: the late order is
+//              what every other launch runs anyway (ctk_mppi_early_u_ok), under the name it had
+constexpr int CTK_MPPI_FORM_WIDE_TAIL = 1, CTK_MPPI_FORM_OLD_RECUR = 2, CTK_MPPI_FORM_LATE_U = 4;
+// does a launched 4-wave kernel of this form compile the early order?  (pred: the kernel variant, 0 = the analytic predictor; C control
+// inputs; at run time it also takes a merge + update launch with the {value, seq} tail: fuse mode 1)
+constexpr bool ctk_mppi_early_u_ok(int form, int pred, int C, bool p2p) {
+    return (form & (CTK_MPPI_FORM_LATE_U | CTK_MPPI_FORM_WIDE_TAIL)) == 0 && pred == 0 && C == 1 && !p2p;
+}
 constexpr int CTK_MPPI_LL_NARROW_WORDS = 8 * 256;   // one 8-deep poll batch of the 256-thread merging workgroup
 inline bool ctk_ll_tail_wide(int blocks, int cols) {
     return blocks > CTK_MPPI_FUSE_MAX_BLOCKS_LL || blocks * (2 + cols) > CTK_MPPI_LL_NARROW_WORDS;

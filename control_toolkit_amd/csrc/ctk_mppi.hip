@@ -155,7 +155,10 @@ struct FuseArgs {
 // P_ = inducing points; pmagic_ = magic of the P_*C sample columns of a row.
 // FORM (ctk_launch.h: CTK_MPPI_FORM_*): the four-argument kernel is FORM 0 — the tail of at most CTK_MPPI_FUSE_MAX_BLOCKS_LL records and
 // CTK_MPPI_LL_NARROW_WORDS words (one 8-deep poll batch, one thread per column in the merge), the pipelined recurrence; the launcher
-// takes the five-argument overload for the other forms (many records; the previous recurrence, a diagnostic switch).  One body text.
+// takes the five-argument overload for the other forms (many records; the previous recurrence and the late publish of u, diagnostic
+// switches).  One body text.  FORM 0 publishes u AHEAD of the plan update (part 5: EARLY_U) in a merge + update launch of the analytic
+// predictor with one control input; every other launch, and the resident and batch kernels, publish it from the final update.
+#define CTK_BODY_EARLY_U   // the launched kernel: u ahead of the plan update where the form allows it (ctk_launch.h: ctk_mppi_early_u_ok)
 template <int ENV, int PRED, bool LOG, bool P2P = false>
 __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_rollout(const float* __restrict__ samples,
                                                                const float* __restrict__ u_nom,
@@ -178,6 +181,7 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_rollout(const float* __re
     extern __shared__ float lds[];
 #include "ctk_mppi_body.inc"
 }
+#undef CTK_BODY_EARLY_U
 
 // ---------------------------------------------------------------------------------------------
 // The RESIDENT form (opt-in: ctk_resident_enable): the same step — the same statements, ctk_mppi_body.inc — served
@@ -731,6 +735,11 @@ static bool mppi_old_recur() {
     static const bool on = getenv("CTK_MPPI_OLD_RECUR") != nullptr;
     return on;
 }
+// the late publish of u (ctk_launch.h: CTK_MPPI_FORM_LATE_U) — diagnostic switch: A/B and the bit-identity test
+static bool mppi_late_u() {
+    static const bool on = getenv("CTK_MPPI_LATE_U") != nullptr;
+    return on;
+}
 // the form of a 4-wave launch of `blocks` records of `cols` columns (fz.ll: the {value, seq} tail); the old recurrence is the
 // analytic predictor's only
 static int mppi_form(int kp, int blocks, int cols, bool ll) {
@@ -792,15 +801,18 @@ static FuseArgs mppi_fuse_args(const MppiFuse& fuse, int stage_ok, const Rollout
 }
 
 // a launch's CTK_MPPI_FORM_* bits as a constant: f(integral_constant<int, form>).  OLD: the instantiations with the previous recurrence
-// exist (the analytic predictor of a pipelined environment: mppi_form / mppi_env_form raise that bit nowhere else)
-template <bool OLD, class F>
+// exist (the analytic predictor of a pipelined environment: mppi_form / mppi_env_form raise that bit nowhere else).  LATE: those with the
+// late publish of u exist (launch_mppi_4wave raises that bit, never together with WIDE_TAIL)
+template <bool OLD, bool LATE = false, class F>
 static void with_mppi_form(int form, F&& f) {
     using std::integral_constant;
-    constexpr int W = CTK_MPPI_FORM_WIDE_TAIL, O = CTK_MPPI_FORM_OLD_RECUR;
+    constexpr int W = CTK_MPPI_FORM_WIDE_TAIL, O = CTK_MPPI_FORM_OLD_RECUR, L = CTK_MPPI_FORM_LATE_U;
     if (form == 0) f(integral_constant<int, 0>{});
     else if (form == W) f(integral_constant<int, W>{});
+    else if (LATE && form == L) { if constexpr (LATE) f(integral_constant<int, L>{}); }
     else if constexpr (OLD) {
         if (form == O) f(integral_constant<int, O>{});
+        else if (LATE && form == (L | O)) { if constexpr (LATE) f(integral_constant<int, L | O>{}); }
         else f(integral_constant<int, W | O>{});
     }
 }
@@ -825,13 +837,17 @@ static int launch_mppi_4wave(hipStream_t st, const RolloutArgs& a, const typenam
     int form;
     if constexpr (ODE) form = mppi_env_form<ENV>((int)grid.x, PC, fz.ll != nullptr);
     else form = mppi_form(PRED, (int)grid.x, PC, fz.ll != nullptr);
+    // the late publish of u, on request: only where FORM 0 would publish early, so that the switch changes no other launch
+    constexpr bool LATE = ctk_mppi_early_u_ok(0, PRED, C, false);
+    if (LATE && mppi_late_u() && fz.mode == 1 && fz.ll != nullptr && ctk_mppi_early_u_ok(form, PRED, C, p2p)) form |= CTK_MPPI_FORM_LATE_U;
     auto go = [&](auto kernel) { CTK_LAUNCH(kernel, grid, block, lds, st, e0, e1, samples, u_nom, a.interp, wperm, parts, a.N, a.H, a.P, pmagic, a, k, m, fz); };
-    with_mppi_form<ODE && env_pipelined<ENV>::value>(form, [&](auto form_c) {
+    with_mppi_form<ODE && env_pipelined<ENV>::value, LATE>(form, [&](auto form_c) {
         ctk_with_bool(log, [&](auto log_c) {
             ctk_with_bool(p2p, [&](auto p2p_c) {
                 constexpr int FV = decltype(form_c)::value;
                 constexpr bool LV = decltype(log_c)::value, XV = ENV == CTK_ENV_CARTPOLE && decltype(p2p_c)::value;
                 if constexpr (FV == 0) go(ctk_mppi_rollout<ENV, PRED, LV, XV>);      // (FORM 0 is the four-argument kernel)
+                else if constexpr ((FV & CTK_MPPI_FORM_LATE_U) != 0 && XV) (void)0;   // (never launched: LATE_U is raised without the peer-to-peer tail only)
                 else go(ctk_mppi_rollout<ENV, PRED, LV, XV, FV>);
             });
         });

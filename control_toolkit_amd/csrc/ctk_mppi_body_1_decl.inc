@@ -31,5 +31,11 @@
     const bool use_ll = fz.mode != 0 && fz.ll != nullptr;   // kernel-argument uniform
     constexpr bool WIDE_TAIL = (FORM & CTK_MPPI_FORM_WIDE_TAIL) != 0;   // the 16-deep poll and the sliced merge of many narrow records
     constexpr bool PIPE = (FORM & CTK_MPPI_FORM_OLD_RECUR) == 0 && env_pipelined<ENV>::value;   // recurrence: sin / cos one step ahead
+    // u ahead of the plan update (part 5): the launched kernel's order unless LATE_U; the resident and batch forms keep the late order
+#ifdef CTK_BODY_EARLY_U
+    constexpr bool EARLY_U = ctk_mppi_early_u_ok(FORM, PRED, C, P2P);
+#else
+    constexpr bool EARLY_U = false;
+#endif
 
     const uint32_t ka_sink = kernarg_prefetch<sizeof(RolloutArgs) + sizeof(typename E::K) + sizeof(MppiK) + 5 * sizeof(void*) + 16 + sizeof(FuseArgs)>();

@@ -108,17 +108,41 @@
                 st_rec(rec, rho); st_rec(rec + 1, asum);
             }
         }
+        // ---- u ahead of the plan update (EARLY_U, ctk_mppi_body_1_decl.inc): the caller waits for u = u_nom_new[0] alone, and entry 0
+        //      of the update reads, of every block's record, only rho_b, a_b and the columns c0 = i0(0) and c0 + 1.  Wave 0 of every block
+        //      forms those two column sums here, ahead of the workgroup's barrier and full pass, and publishes them in their slots of the
+        //      block's record (the full pass stores the same values under the same sequence number again); wave 0 of block 0 then polls
+        //      the four words of every block, merges them in registers and publishes {u, seq}.  Everything below — the barrier, the full
+        //      column sums, the full poll, the merge, the update of all H entries — is as in the late order, minus the publish.
+        if constexpr (EARLY_U) {
+            if (fz.mode == 1 && use_ll) {
+                const int c0 = i0_s[0];
+                float cs = 0.0f;
+                if (lane < 8) cs = mppi_col_partial<RPW>(e_s, tile, ts, lane & 3, c0 + (lane >> 2));   // (column P: the tile's zero pad)
+                cs += dpp_mov<DPP_QUAD_XOR1>(cs);                     // lanes 4c .. 4c+3: (s0 + s1) + (s2 + s3), the full pass's order
+                cs += dpp_mov<DPP_QUAD_XOR2>(cs);
+                if ((lane == 0 || lane == 4) && c0 + (lane >> 2) < P)
+                    ll_store(fz.ll + (size_t)blockIdx.x * (2 + P) + 2 + c0 + (lane >> 2), cs, fz.up.seq);
+                if (blockIdx.x == 0) {
+                    bool late = false;                // the bounded poll ran out: error word 2, as in the tail
+                    const float o = mppi_early_u<CTK_MPPI_FUSE_MAX_BLOCKS_LL / 64>(fz.ll, (int)gridDim.x, P, c0, w0_s[0], w1_s[0], un_s[0], m.neg_inv_lbd,
+                                                                                  fz.up.lo, fz.up.hi, fz.up.seq, &late);
+                    if (lane == 0) {
+                        // ctk_api.hip:finish_step turns a non-zero error word (the dword behind {u, seq}) into CTK_ERR_STATE
+                        if (late && fz.up.u_host)
+                            __hip_atomic_store(reinterpret_cast<uint32_t*>(fz.up.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        publish_u(fz.up.u_dev, fz.up.u_host, o, fz.up.seq);   // optimizer_mppi.py:191 u = u_nom[0,0,:]
+                    }
+                    STAMP(7);
+                }
+            }
+        }
     }
     __syncthreads();
     STAMP(4);
 
     // ---- epilogue (256 threads): b_b[p] = sum_r e_r * tile[r][p]; wave w sums rows RPW*w..RPW*w+RPW-1 ----
-    for (int p = lane; p < P; p += 64) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int r = 0; r < RPW; ++r) acc += e_s[wave * RPW + r] * tile[(wave * RPW + r) * ts + p];
-        col_s[wave * P + p] = acc;
-    }
+    for (int p = lane; p < P; p += 64) col_s[wave * P + p] = mppi_col_partial<RPW>(e_s, tile, ts, wave, p);
     __syncthreads();
     float* rec = parts + (size_t)blockIdx.x * (2 + P);
     for (int p = t; p < P; p += MPPI_BLOCK) {
@@ -138,33 +162,14 @@
             const int nb = (int)gridDim.x, tot = nb * (2 + P);
             float* st = merge_stage_ptr(lds, nb, P);
             bool expired = false;                 // a bounded poll ran out: surfaced to the host through the error word
-            // LLW words in flight per thread: the first pass over a thread's words is one pipelined batch of loads, not LLW round trips.
+            // LLW words in flight per thread: the first pass over a thread's words is one pipelined batch of loads, not LLW round trips
+            // (ctk_mppi_merge.h: ll_poll_stage; every later pass re-reads what has not arrived, then sleeps once).
             // A SECOND batch starts only when the first has arrived, i.e. after the slowest workgroup's record — a whole extra round trip
             // (~2 us) behind the launch's critical path: up to 16 words per thread go out as ONE batch (a configs[4] shard: 13 per thread).
             // Only the WIDE_TAIL form carries the 16-deep batch: the launcher takes it exactly when the records exceed one 8-deep batch.
             auto poll = [&](auto llw_tag) {
                 constexpr int LLW = decltype(llw_tag)::value;
-                for (int i0 = t; i0 < tot; i0 += MPPI_BLOCK * LLW) {
-                    unsigned long long w[LLW];
-#pragma unroll
-                    for (int j = 0; j < LLW; ++j) {
-                        const int i = i0 + j * MPPI_BLOCK;
-                        if (i < tot) w[j] = __hip_atomic_load(fz.ll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-#pragma unroll
-                    for (int j = 0; j < LLW; ++j) {
-                        const int i = i0 + j * MPPI_BLOCK;
-                        if (i < tot) {
-                            for (int spin = 0; (uint32_t)(w[j] >> 32) != fz.up.seq && spin < (1 << 22); ++spin) {
-                                __builtin_amdgcn_s_sleep(1);
-                                w[j] = __hip_atomic_load(fz.ll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            }
-                            const bool got = (uint32_t)(w[j] >> 32) == fz.up.seq;
-                            expired |= !got;
-                            st[i] = got ? __builtin_bit_cast(float, (uint32_t)w[j]) : __builtin_nanf("");
-                        }
-                    }
-                }
+                for (int i0 = t; i0 < tot; i0 += MPPI_BLOCK * LLW) expired |= ll_poll_stage_call<LLW, MPPI_BLOCK>(fz.ll, st, i0, tot, fz.up.seq);
             };
             if constexpr (WIDE_TAIL) {
                 if (tot > MPPI_BLOCK * 8 && tot <= MPPI_BLOCK * 16) poll(std::integral_constant<int, 16>{});
@@ -178,7 +183,7 @@
             __syncthreads();
             const size_t scratch_floats = 8 + P + 1 + min(nb, MERGE_CHUNK) + (size_t)tot + MERGE_BLOCK;   // (+ the column slices of many narrow records)
             if (scratch_floats <= (size_t)(w0_s - lds)) { fz.up.w0_l = w0_s; fz.up.w1_l = w1_s; fz.up.un_l = un_s; fz.up.i0_l = i0_s; }
-            if (fz.mode == 1) mppi_merge_block<true, 0, C, WIDE_TAIL>(lds, nullptr, nb, P, m.neg_inv_lbd, nullptr, fz.up, 2);
+            if (fz.mode == 1) mppi_merge_block<true, 0, C, WIDE_TAIL, !EARLY_U>(lds, nullptr, nb, P, m.neg_inv_lbd, nullptr, fz.up, 2);   // (EARLY_U: u is out already)
             else mppi_merge_block<false, 0, C, WIDE_TAIL>(lds, nullptr, nb, P, m.neg_inv_lbd, fz.out_rec, fz.up, 2);
             if constexpr (P2P) {
                 // sharded step over peer-to-peer stores, all in this launch: the shard's record (just written to

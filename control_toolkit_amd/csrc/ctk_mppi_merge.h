@@ -49,11 +49,29 @@ inline MppiUpdateArgs mppi_update_args(const RolloutArgs& a, int C, const float*
     return up;
 }
 
+// entry h of the MPPI update, C == 1: u_nom[h] <- clip(shift(u_nom)[h] + interp(b)[h] / a) (optimizer_mppi.py:184, :190).  ONE function
+// for the final update and for the early form of entry 0 (mppi_early_u), so that both are the same operations
+CTK_DEV float mppi_update_entry(float b0, float b1, float w0, float w1, float a_tot, float un, float lo, float hi) {
+    const float w = (b0 * w0 + b1 * w1) / a_tot;
+    return fminf(fmaxf(un + w, lo), hi);   // optimizer_mppi.py:190
+}
+
+// rows w*RPW .. w*RPW+RPW-1 of column p of a block record's numerator, b_b[p] = sum_r e_r * tile[r][p]: ONE function for the epilogue's
+// full pass and for the two columns that wave 0 forms ahead of it, so that both sum in the same order with the same contraction
+template <int RPW>
+CTK_DEV float mppi_col_partial(const float* e_s, const float* tile, int ts, int w, int p) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) acc += e_s[w * RPW + r] * tile[(w * RPW + r) * ts + p];
+    return acc;
+}
+
 // scratch: >= 8 + (P + 1) + min(cnt, MERGE_CHUNK) floats of LDS, plus cnt*(2+P) more when `stage`
 // (all records fetched into LDS by ONE wide pass: one memory round trip instead of one per record).
 // CH: control inputs of the FINAL update (compile time: the C == 1 instantiations are CartPole's statement sequence, unchanged)
 // MANY: the sliced column sums of many narrow records are compiled in (a caller that never merges more than 128 records leaves them out)
-template <bool FINAL, int SC1, int CH = 1, bool MANY = true>
+// PUB: the FINAL update publishes u (false: entry 0 went out ahead of the plan update, mppi_early_u; C == 1 only)
+template <bool FINAL, int SC1, int CH = 1, bool MANY = true, bool PUB = true>
 CTK_DEV void mppi_merge_block(float* scratch, const float* base, int cnt, int P, float neg_inv_lbd, float* out_rec,
                               const MppiUpdateArgs& up, int stage) {
     float* red = scratch;             // [4] cross-wave scratch
@@ -154,12 +172,14 @@ CTK_DEV void mppi_merge_block(float* scratch, const float* base, int cnt, int P,
                 InterpEntry e; float un;
                 if (up.w0_l) { e = InterpEntry{up.i0_l[h], up.w0_l[h], up.w1_l[h]}; un = up.un_l[h]; }
                 else { e = up.interp[h]; un = up.u_nom_in[min(h + 1, up.H - 1)]; }
-                const float w = (b_s[e.i0] * e.w0 + b_s[e.i0 + 1] * e.w1) / a_tot;
-                const float o = fminf(fmaxf(un + w, up.lo), up.hi);   // optimizer_mppi.py:190
+                const float o = mppi_update_entry(b_s[e.i0], b_s[e.i0 + 1], e.w0, e.w1, a_tot, un, up.lo, up.hi);
                 up.u_nom_out[h] = o;
-                if (h == 0) publish_u(up.u_dev, up.u_host, o, up.seq);   // :191 u = u_nom[0,0,:]
+                if constexpr (PUB) {
+                    if (h == 0) publish_u(up.u_dev, up.u_host, o, up.seq);   // :191 u = u_nom[0,0,:]
+                }
             }
         } else {
+            static_assert(PUB, "the early form of entry 0 is the C == 1 update's");
             // P here = P*C record columns; inducing point i of channel c is column i*C + c
             constexpr int C = CH;
             const int Pp = P / C;
@@ -192,6 +212,111 @@ CTK_DEV void ll_store(unsigned long long* p, float v, uint32_t seq) {
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// One batch of a thread's {value, seq} words, i0 + j*STRIDE < tot (j < LLW), polled until each carries `seq`, then staged as floats in
+// st[]: ONE bounded loop whose every pass (re)loads the words that have not arrived — the first pass is one pipelined batch of LLW loads —
+// checks them and sleeps once.  Returns true when the bound ran out with a word missing (staged as NaN).
+constexpr int LL_POLL_SPINS = 1 << 22;
+template <int LLW, int STRIDE>
+CTK_DEV bool ll_poll_stage(const unsigned long long* ll, float* st, int i0, int tot, uint32_t seq) {
+    unsigned long long w[LLW];
+    unsigned pend = 0;
+#pragma unroll
+    for (int j = 0; j < LLW; ++j) pend |= (i0 + j * STRIDE < tot ? 1u : 0u) << j;
+    for (int spin = 0;; ++spin) {
+#pragma unroll
+        for (int j = 0; j < LLW; ++j)
+            if ((pend >> j) & 1u) w[j] = __hip_atomic_load(ll + i0 + j * STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int j = 0; j < LLW; ++j)
+            if (((pend >> j) & 1u) && (uint32_t)(w[j] >> 32) == seq) pend &= ~(1u << j);
+        if (pend == 0 || spin >= LL_POLL_SPINS) break;
+        __builtin_amdgcn_s_sleep(1);
+    }
+#pragma unroll
+    for (int j = 0; j < LLW; ++j) {
+        const int i = i0 + j * STRIDE;
+        if (i < tot) st[i] = ((pend >> j) & 1u) ? __builtin_nanf("") : __builtin_bit_cast(float, (uint32_t)w[j]);
+    }
+    return pend != 0;
+}
+// ... as a function of its own, for the 4-wave rollout kernel (ctk_mppi_body_5_post.inc).  Only block 0 runs the poll, once, at the very
+// end of the launch, but inlined its divergent loop takes part in the scheduling and register allocation of the whole kernel: with it
+// the cold (checked sin / cos) recurrence loop of ctk_mppi_rollout<0, 0, false, false> came out in another block layout and four more
+// SGPRs were spilled.  One call (no stack: the callee keeps to registers) costs the tail nothing that can be measured.
+template <int LLW, int STRIDE>
+__device__ __attribute__((noinline)) bool ll_poll_stage_call(const unsigned long long* ll, float* st, int i0, int tot, uint32_t seq) {
+    return ll_poll_stage<LLW, STRIDE>(ll, st, i0, tot, seq);
+}
+
+// Entry 0 of the MPPI update AHEAD of the plan update (C == 1, at most 64*NB block records): ONE wave (all 64 lanes) of the merging
+// workgroup polls, of every block's record, only the four words that entry needs — rho_b, a_b and the columns c0 = i0(0) and c0 + 1
+// (c0 + 1 == P: the zero pad, no word) — and merges them in registers: lane i % 64 holds block i.  No LDS, no barrier.  The association
+// is mppi_merge_block's for cnt <= 128 (thread t = record t there): rho the min over all blocks, sc_i = expf(neg_inv_lbd*(rho_i - rho)),
+// a_tot = red[0] + red[1] + red[2] + red[3] with red[k] the wave_sum of lanes' a_i*sc_i of batch k (zero for an absent batch), the two
+// columns as acc += rec_i * sc_i over i = 0 .. nb-1 from zero; then mppi_update_entry.  The value is therefore bit for bit the
+// u_nom_out[0] that the final update stores later.  *expired: the bounded poll ran out (the missing words enter as NaN, as in the tail).
+template <int NB>
+CTK_DEV float mppi_early_u(const unsigned long long* ll, int nb, int P, int c0, float w0, float w1, float un, float neg_inv_lbd,
+                           float lo, float hi, uint32_t seq, bool* expired) {
+    const int lane = threadIdx.x & 63, rs = 2 + P;
+    const bool has1 = c0 + 1 < P;
+    unsigned long long w[NB][4];
+    unsigned pend = 0;
+#pragma unroll
+    for (int k = 0; k < NB; ++k)
+        if (k * 64 + lane < nb) pend |= (has1 ? 0xFu : 0x7u) << (4 * k);
+    for (int spin = 0;; ++spin) {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const unsigned long long* rl = ll + (size_t)(k * 64 + lane) * rs;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((pend >> (4 * k + j)) & 1u) w[k][j] = __hip_atomic_load(rl + (j < 2 ? j : c0 + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (((pend >> (4 * k + j)) & 1u) && (uint32_t)(w[k][j] >> 32) == seq) pend &= ~(1u << (4 * k + j));
+        if (pend == 0 || spin >= LL_POLL_SPINS) break;
+        __builtin_amdgcn_s_sleep(1);
+    }
+    *expired = __builtin_amdgcn_ballot_w64(pend != 0) != 0;
+    auto val = [&](int k, int j) { return ((pend >> (4 * k + j)) & 1u) ? __builtin_nanf("") : __builtin_bit_cast(float, (uint32_t)w[k][j]); };
+
+    float red[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
+#pragma unroll
+    for (int k = 0; k < NB; ++k) red[k] = wave_min(k * 64 + lane < nb ? val(k, 0) : INFINITY);
+    const float rho = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+
+    float sc[NB];
+    float asum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        float a_acc = 0.0f;
+        sc[k] = 0.0f;
+        if (k * 64 + lane < nb) {
+            sc[k] = expf(neg_inv_lbd * (val(k, 0) - rho));   // e^{-(rho_r - rho)/lambda}
+            a_acc += val(k, 1) * sc[k];
+        }
+        asum[k] = wave_sum(a_acc);
+    }
+    const float a_tot = asum[0] + asum[1] + asum[2] + asum[3];
+
+    float b0 = 0.0f, b1 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        const int v0 = __builtin_bit_cast(int, val(k, 2)), v1 = __builtin_bit_cast(int, has1 ? val(k, 3) : 0.0f), vs = __builtin_bit_cast(int, sc[k]);
+        const int cn = min(64, nb - k * 64);
+        for (int i = 0; i < cn; ++i) {
+            const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vs, i));
+            b0 += __builtin_bit_cast(float, __builtin_amdgcn_readlane(v0, i)) * s;
+            b1 += __builtin_bit_cast(float, __builtin_amdgcn_readlane(v1, i)) * s;
+        }
+    }
+    return mppi_update_entry(b0, b1, w0, w1, a_tot, un, lo, hi);
+}
+
 // The fused tail of an MPPI rollout launch of 256-thread workgroups whose blocks have published their records as {value, seq} words
 // (ll_store): called by block 0 (all threads, after a barrier that retires its own use of `lds`), which polls every word until it
 // carries this launch's sequence number — the words ARE the data — stages them in LDS, merges, and either applies the update and
@@ -203,28 +328,7 @@ CTK_DEV void mppi_ll_tail(float* lds, const unsigned long long* ll, int nb, int 
     const int t = threadIdx.x, tot = nb * (2 + P);
     float* st = merge_stage_ptr(lds, nb, P);
     bool expired = false;
-    constexpr int LLW = 8;                // words in flight per thread
-    for (int i0 = t; i0 < tot; i0 += MERGE_BLOCK * LLW) {
-        unsigned long long w[LLW];
-#pragma unroll
-        for (int j = 0; j < LLW; ++j) {
-            const int i = i0 + j * MERGE_BLOCK;
-            if (i < tot) w[j] = __hip_atomic_load(ll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int j = 0; j < LLW; ++j) {
-            const int i = i0 + j * MERGE_BLOCK;
-            if (i < tot) {
-                for (int spin = 0; (uint32_t)(w[j] >> 32) != up.seq && spin < (1 << 22); ++spin) {
-                    __builtin_amdgcn_s_sleep(1);
-                    w[j] = __hip_atomic_load(ll + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                const bool got = (uint32_t)(w[j] >> 32) == up.seq;
-                expired |= !got;
-                st[i] = got ? __builtin_bit_cast(float, (uint32_t)w[j]) : __builtin_nanf("");
-            }
-        }
-    }
+    for (int i0 = t; i0 < tot; i0 += MERGE_BLOCK * 8) expired |= ll_poll_stage<8, MERGE_BLOCK>(ll, st, i0, tot, up.seq);   // 8 words in flight per thread
     if (expired && up.u_host)
         __hip_atomic_store(reinterpret_cast<uint32_t*>(up.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __syncthreads();

@@ -300,11 +300,23 @@ int ctk_predictor_set_hidden(ctk_handle* h, const float* src, size_t n); /* src 
  * s: host [S].  u_prev: host [C] previous applied input (cost `previous_input`); NULL = the
  * optimizer's own last output, as the reference passes self.u.  u_out: host [C].
  * Synchronous: returns when u_out is valid.
+ * Completion of a step.  When ctk_step returns,
+ *   - u_out is FINAL;
+ *   - the handle's other results of the step (the new plan U_NOM above all) are final for EVERY LATER API CALL on the handle: the MPPI
+ *     kernel publishes u = u_nom_new[0] ahead of the update of the rest of the plan, so its launch may still be finishing that update
+ *     for a few microseconds; every API entry that reads or writes the handle's buffers is ordered behind the launch on the handle's
+ *     stream (or synchronises that stream first), and the next step's launch is ordered behind it likewise;
+ *   - a caller that touches the handle's device buffers from a stream of its OWN orders that stream behind ctk_get_stream, as before;
+ *   - the step no longer reads caller-owned device memory (a CTK_LOC_DEVICE sample buffer): it may be refilled at once.
  * CTK_ERR_STATE from a step = a bounded device-side wait ran out (ctk_last_error says which): a peer's record (sharded MPPI over
  * p2p), a workgroup's record of an in-launch hand-off (MPPI / CEM), or — RPGD with a network predictor — a step Jacobian of the
  * in-launch hand-off / a non-finite gradient.  In the RPGD case the affected 16-plan tile SKIPPED that iteration's update: plans and
  * Adam moments are finite and as they were before it, u_out comes from a population that missed an update, the handle stays usable
  * and the next ctk_step is a normal step (ctk_reset / ctk_set_state re-pin it if the caller wants a defined population).
+ * MPPI, u published ahead of the plan update: the launch waits for the workgroups' records twice.  If the FIRST wait (the four words
+ * per record that u needs) runs out, this step returns CTK_ERR_STATE and u_out is NaN, as ever.  If only the SECOND (the whole records,
+ * for the plan update) runs out, the host has left with a valid u_out by then: the plan holds NaN, and it is the NEXT ctk_step that
+ * finds the error word and returns CTK_ERR_STATE.
  * ----------------------------------------------------------------------------------------- */
 int ctk_step(ctk_handle* h, const float* s, const float* u_prev,
              const float* samples, int samples_loc, float* u_out);

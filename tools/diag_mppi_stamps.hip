@@ -59,5 +59,19 @@ int main(int argc, char** argv) {
     unsigned long long mn = ~0ull, mx = 0;
     for (int b = 0; b < nb; ++b) { mn = std::min(mn, st[b * 16]); mx = std::max(mx, st[b * 16 + 6]); }
     printf("  first block start -> last block end: %llu cycles\n", mx - mn);
+    {   // u ahead of the plan update (FORM 0; stamp 7, block 0 only): "J ready -> early publish -> kernel end" in block 0's own clock
+        // (s_memtime counts per XCD: stamps of different blocks are not compared).  CTK_MPPI_LATE_U set: no stamp 7, the publish is the
+        // final update's, just before block 0's end.  Block 0 publishes once the slowest block's four fast words are there, so "J ready ->
+        // publish" holds that block's lag behind block 0 as well.
+        std::vector<double> a_step;           // every block: J ready -> its barrier (the soft-min partial + its two fast column sums)
+        for (int b = 0; b < nb; ++b) a_step.push_back((double)(st[b * 16 + 4] - st[b * 16 + 3]));
+        std::sort(a_step.begin(), a_step.end());
+        if (st[7] != 0)
+            printf("  early publish of u, block 0: J ready -> publish %lld cycles; publish -> kernel end %lld cycles  (J ready -> barrier, blocks 1..: median %.0f)\n",
+                   (long long)(st[7] - st[3]), (long long)(st[6] - st[7]), a_step[a_step.size() / 2]);
+        else
+            printf("  late publish of u, block 0: J ready -> kernel end (the publish) %lld cycles  (J ready -> barrier, every block: median %.0f)\n",
+                   (long long)(st[6] - st[3]), a_step[a_step.size() / 2]);
+    }
     return 0;
 }
