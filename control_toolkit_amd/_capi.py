@@ -180,6 +180,9 @@ SYMBOLS = {
     "ctk_rpgd_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
     "ctk_rpgd_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
     "ctk_rpgd_batch_dominant_kernel": (C.c_char_p, [_H]),
+    "ctk_rpgd_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ctk_rpgd_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
+    "ctk_rpgd_problem_params_differ": (C.c_int, [_H]),
     "ctk_rpgd_template_descent_lds": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
 }
 
@@ -709,7 +712,7 @@ _F32_MAX = float(np.finfo(np.float32).max)
 
 
 def batch_param_args(param_names, num_problems: int, name, values, ids=None):
-    """Checks the arguments of CtkMppiBatch.set_problem_params / CtkCemBatch.set_problem_params without touching a device: the parameter name against the environment's
+    """Checks the arguments of CtkMppiBatch.set_problem_params / CtkCemBatch.set_problem_params / CtkRpgdBatch.set_problem_params without touching a device: the parameter name against the environment's
     names, ids (batch_ids), values a finite scalar (every listed problem) or one finite value per listed problem ([n]).  Returns
     (parameter id, ids, n, values as fp32 [n])."""
     if name not in param_names:
@@ -1096,7 +1099,8 @@ class CtkRpgdBatch:
     """Owns one ctk_rpgd_batch: num_problems independent RPGD controllers of ONE configuration (the RPGD keywords of CtkEngine) with at
     most 64 plans each, any subset of them stepped by ONE kernel launch: descent, keep-k selection and warm start of every listed problem.
     Problem p behaves bit for bit like CtkEngine("rpgd", "ODE", seed=seeds[p], generic_kernels=True, ...) given the same calls (reset,
-    step, set_state, set_param, set_rng_position).  seeds: one per problem (default seed + p).
+    step, set_state, set_param, set_rng_position): set_problem_params gives every problem its own plant, cost weights and targets,
+    set_param the same value to all.  seeds: one per problem (default seed + p).
     generic_kernels: None means True for this class — the batch kernel is the template descent; CartPole's tuned descent (what
     CtkEngine runs with generic_kernels=False) has no batch form, and generic_kernels=False for CartPole is refused rather than
     silently differing from such an engine.  The other environments have template kernels only."""
@@ -1264,13 +1268,37 @@ class CtkRpgdBatch:
         self._check(self._lib.ctk_rpgd_batch_set_state(self._h, self._problem(problem), _ptr(st), st.size))
 
     def set_param(self, name: str, value: float):
-        """parameter `name` of every problem (one table for the batch)"""
+        """parameter `name` of every problem (that column of every problem's table; the other parameters stay per problem)"""
         self._check(self._lib.ctk_rpgd_batch_set_param(self._h, self.param_names.index(name), float(value)))
 
     def get_param(self, name: str) -> float:
+        """the last value set_param gave the whole batch (the default before that); a problem's own value: get_problem_param"""
         v = C.c_float()
         self._check(self._lib.ctk_rpgd_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
         return v.value
+
+    def set_problem_params(self, name: str, values, ids=None):
+        """parameter `name` of the problems in ids (None: all): values a scalar or [n], one per listed problem in the order of ids.  The
+        next step re-derives the constants of the problems touched; from the first call on the batch runs the per-problem form of its
+        kernel (params_differ, dominant_kernel)."""
+        pid, idv, n, vals = batch_param_args(self.param_names, self.B, name, values, ids)
+        self._check(self._lib.ctk_rpgd_problem_set_param(self._h, n, _ptr(idv), pid, _ptr(vals)))
+
+    def get_problem_param(self, name: str, problem: int) -> float:
+        if name not in self.param_names:
+            raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(self.param_names)})")
+        v = C.c_float()
+        if self._lib.ctk_rpgd_problem_get_param(self._h, self._problem(problem), self.param_names.index(name), C.byref(v)) != 0:
+            raise CtkError(f"ctk_rpgd_problem_get_param({problem}, {name!r}) failed")
+        return v.value
+
+    def get_problem_params(self, name: str) -> np.ndarray:
+        """[B] parameter `name` of every problem"""
+        return np.array([self.get_problem_param(name, p) for p in range(self.B)], np.float32)
+
+    def params_differ(self) -> int:
+        """1 once a set_problem_params has succeeded on this batch (sticky), else 0"""
+        return int(self._lib.ctk_rpgd_problem_params_differ(self._h))
 
     def rng_position(self, problem: int) -> int:
         v = C.c_uint32()

@@ -3279,13 +3279,21 @@ int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call)
 // descent, the keep-k selection and the warm start that a template handle runs as three launches.  One allocation per buffer kind with a
 // problem stride — no handles inside.  Per-problem host state is what an RPGD handle keeps: the sequence number of its next step, its
 // Philox position, its step count (which decides the iterations of its next step and whether it resamples), its Adam step number, which
-// buffer holds its population, and whether it has been reset.  No workgroup of the kernel waits for another, so a call is split into
-// launches only at the grid's y limit.
+// buffer holds its population, whether it has been reset, and its parameter table.  No workgroup of the kernel waits for another, so a
+// call is split into launches only at the grid's y limit.  While no ctk_rpgd_problem_set_param has succeeded the launches take the
+// constants of the shared table by value; from then on (`differ`, sticky) every step writes the constants of the problems it steps
+// BEHIND their step records, in the records' order, so they travel in the records' transfer (no constants array in device memory, no
+// second transfer).
 // =============================================================================================
 struct ctk_rpgd_batch {
     ctk_config cfg{};
     int B = 0, N = 0, H = 0, P = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, PC = 0, K = 0;
-    float params[CTK_MAX_PARAMS]{};         // one table for all problems (ctk_rpgd_batch_set_param); the launcher derives the constants from it
+    float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (ctk_rpgd_batch_set_param / get_param)
+    std::vector<float> pparams;             // [B][CTK_MAX_PARAMS] every problem's own table
+    std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived into kcache
+    bool differ = false;                    // a ctk_rpgd_problem_set_param has succeeded: the per-problem form of the kernel from now on
+    size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes per problem in kcache and behind the step records
+    std::vector<unsigned char> kcache;      // [B][kstride] derived constants by problem id (host only; the step copies them into h_steps)
     hipStream_t stream = nullptr;
     InterpEntry* d_interp = nullptr;        // [H] shared
     float* d_bc = nullptr; int bc_len = 0;  // shared bias-correction table
@@ -3301,8 +3309,8 @@ struct ctk_rpgd_batch {
     float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
     float* h_u_dev = nullptr;
     CtkRpgdBatchDesc* d_desc = nullptr;     // [B]
-    CtkRpgdBatchStep* h_steps = nullptr;    // pinned [B]: the records of the step (or reset) being issued
-    CtkRpgdBatchStep* d_steps = nullptr;
+    CtkRpgdBatchStep* h_steps = nullptr;    // pinned, B * (sizeof(CtkRpgdBatchStep) + kstride) bytes: the n records of the step (or reset) being
+    CtkRpgdBatchStep* d_steps = nullptr;    // issued and, in the per-problem form of a step, the constants of those n problems right behind them
     float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
     std::vector<uint32_t> seq, call;
     std::vector<int> count, adam_step;
@@ -3311,6 +3319,8 @@ struct ctk_rpgd_batch {
     size_t NHC() const { return (size_t)N * HC; }
     float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
     float* slot(int p) const { return h_u + (size_t)p * 16; }
+    float* table(int p) { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
+    const float* table(int p) const { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
     size_t state_size() const { return 3 * NHC() + (size_t)N + C + 2; }   // ctk_state_size of an RPGD handle
     int its(int p) const {                  // rpgd_iterations
         const int first = cfg.warmup ? cfg.warmup_iterations : cfg.outer_its;
@@ -3469,6 +3479,11 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
     b->P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
     b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = HC; b->PC = b->P * einfo->C;
     default_params(b->env, b->params);
+    b->pparams.resize((size_t)n_problems * CTK_MAX_PARAMS);
+    for (int p = 0; p < n_problems; ++p) std::memcpy(b->table(p), b->params, sizeof(b->params));
+    b->dirty.assign((size_t)n_problems, 1);            // nothing derived yet: the first step of the per-problem form derives what it steps
+    b->kstride = ctk_mppi_batch_k_stride(b->env);
+    b->kcache.assign((size_t)n_problems * b->kstride, 0);
     b->scratch_stride = tape_in_lds ? 0 : ctk_g_rpgd_scratch_floats(b->env, N, H);
     b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u);
     b->count.assign((size_t)n_problems, 0); b->adam_step.assign((size_t)n_problems, 0);
@@ -3496,12 +3511,13 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
     RHIP_CREATE(dev_zero((void**)&b->d_u, Bz * CTK_MAX_INPUTS * sizeof(float)));
     RHIP_CREATE(dev_zero((void**)&b->d_scratch, Bz * b->scratch_stride * sizeof(float)));
     RHIP_CREATE(dev_zero((void**)&b->d_desc, Bz * sizeof(CtkRpgdBatchDesc)));
-    RHIP_CREATE(dev_zero((void**)&b->d_steps, Bz * sizeof(CtkRpgdBatchStep)));
+    const size_t steps_bytes = Bz * (sizeof(CtkRpgdBatchStep) + b->kstride);   // the records, then room for as many elements of constants
+    RHIP_CREATE(dev_zero((void**)&b->d_steps, steps_bytes));
     RHIP_CREATE(hipHostMalloc((void**)&b->h_u, Bz * 64, hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(b->h_u, 0, Bz * 64);
     RHIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
-    RHIP_CREATE(hipHostMalloc((void**)&b->h_steps, Bz * sizeof(CtkRpgdBatchStep), hipHostMallocDefault));
-    std::memset(b->h_steps, 0, Bz * sizeof(CtkRpgdBatchStep));
+    RHIP_CREATE(hipHostMalloc((void**)&b->h_steps, steps_bytes, hipHostMallocDefault));
+    std::memset(b->h_steps, 0, steps_bytes);
 
     std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, b->P);
     RHIP_CREATE(dev_zero((void**)&b->d_interp, (size_t)H * sizeof(InterpEntry)));
@@ -3621,7 +3637,27 @@ int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const 
         for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
         for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
     }
-    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkRpgdBatchStep), hipMemcpyHostToDevice, b->stream);
+    // The per-problem form: the constants of the n problems of this step right behind the n records, in the records' order, so that ONE
+    // transfer carries both.  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses
+    // (Env<>::derive at its launch); the cache is by problem id, the block behind the records by launch order.
+    size_t step_bytes = (size_t)n * sizeof(CtkRpgdBatchStep);
+    const unsigned char* d_ksteps = nullptr;
+    if (b->differ) {
+        unsigned char* h_k = reinterpret_cast<unsigned char*>(b->h_steps) + step_bytes;
+        for (int j = 0; j < n; ++j) {
+            const size_t z = (size_t)b->h_steps[j].id;
+            if (b->dirty[z]) {
+                ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, b->kcache.data() + z * b->kstride);
+                b->dirty[z] = 0;
+            }
+            std::memcpy(h_k + (size_t)j * b->kstride, b->kcache.data() + z * b->kstride, b->kstride);
+        }
+        d_ksteps = reinterpret_cast<const unsigned char*>(b->d_steps) + step_bytes;
+        step_bytes += (size_t)n * b->kstride;
+    }
+    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, step_bytes, hipMemcpyHostToDevice, b->stream);
+    if (le != hipSuccess && b->differ)                 // nothing reached the device: derive and copy again at the next step
+        for (int j = 0; j < n; ++j) b->dirty[(size_t)b->h_steps[j].id] = 1;
     const RolloutArgs a = rpgd_batch_args(b);
     const RpgdFusedWarm f = rpgd_batch_warm(b);
     const ctk_config& c = b->cfg;
@@ -3629,7 +3665,8 @@ int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const 
     while (le == hipSuccess && launched < n) {
         const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - launched);
         le = ctk_launch_g_rpgd_batch(b->stream, b->env, a, b->params, c.dt, c.intermediate_steps, c.learning_rate, c.adam_beta_1, c.adam_beta_2,
-                                     c.adam_epsilon, c.gradmax_clip, c.adam_rule == 1 ? 1 : 0, b->d_bc, b->bc_len, f, b->d_desc, b->d_steps + launched, cnt);
+                                     c.adam_epsilon, c.gradmax_clip, c.adam_rule == 1 ? 1 : 0, b->d_bc, b->bc_len, f, b->d_desc, b->d_steps + launched, cnt,
+                                     d_ksteps ? d_ksteps + (size_t)launched * b->kstride : nullptr);
         if (le == hipSuccess) launched += cnt;
     }
     // completion: every launched problem's {u, seq} store landing in its pinned slot (finish_step's bounded spin, one budget for all).
@@ -3735,7 +3772,8 @@ int ctk_rpgd_batch_set_state(ctk_rpgd_batch* b, int problem, const float* src, s
 int ctk_rpgd_batch_set_param(ctk_rpgd_batch* b, int id, float value) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     if (id < 0 || id >= env_info(b->env)->n_params) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_set_param: unknown parameter id for this environment");
-    b->params[id] = value;                             // every launch derives its constants from the table, as a template handle's does
+    b->params[id] = value;                             // the shared table: the shared form derives its constants from it at each launch
+    for (int p = 0; p < b->B; ++p) { b->table(p)[id] = value; b->dirty[(size_t)p] = 1; }   // column id of every problem; the other ids stay
     return CTK_OK;
 }
 
@@ -3744,6 +3782,32 @@ int ctk_rpgd_batch_get_param(const ctk_rpgd_batch* b, int id, float* value) {
     *value = b->params[id];
     return CTK_OK;
 }
+
+int ctk_rpgd_problem_set_param(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = rpgd_batch_ids(b, "ctk_rpgd_problem_set_param", n_ids, ids, &n)) return rc;
+    if (id < 0 || id >= env_info(b->env)->n_params) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_problem_set_param: unknown parameter id for this environment");
+    if (!values) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_problem_set_param: NULL values (one value per listed problem)");
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        b->table(p)[id] = values[j];
+        b->dirty[(size_t)p] = 1;                       // derived when the problem is next stepped: no cost until then
+    }
+    if (!b->differ) {                                  // sticky: the tables are never compared again
+        b->differ = true;
+        b->dominant = ctk_g_rpgd_batch_name(b->env, true);
+    }
+    return CTK_OK;
+}
+
+int ctk_rpgd_problem_get_param(const ctk_rpgd_batch* b, int problem, int id, float* value) {
+    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->table(problem)[id];
+    return CTK_OK;
+}
+
+int ctk_rpgd_problem_params_differ(const ctk_rpgd_batch* b) { return b && b->differ ? 1 : 0; }
 
 int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32_t* call) {
     if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;

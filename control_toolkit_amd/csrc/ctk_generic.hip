@@ -17,6 +17,7 @@
 //        (optimizer_rpgd.py:306-338, :342)
 //   ctk_g_rpgd_batch<ENV>           B independent RPGD problems of at most 64 plans, one workgroup each: the descent above (the same
 //        text, ctk_g_rpgd_body.inc), then keep-k selection and warm start in the same launch (ctk_rpgd_warm.h)
+//   ctk_g_rpgd_batch_pp<ENV>        the same with every problem's own derived constants, read from device memory behind the step records
 // The block-record merge (ctk_mppi_merge<false>), the selection (ctk_select_topk), the refit (ctk_cem_refit) and the
 // RPGD warm start are shared with the CartPole kernels: they only ever see P*C / H*C columns.
 #include <type_traits>
@@ -256,33 +257,27 @@ __global__ __launch_bounds__(GR_BLOCK) void ctk_g_rpgd_batch(RolloutArgs a_tpl, 
                                                             const float* __restrict__ bc_table, int bc_len, int tape_in_lds, FusedWarm fw_tpl,
                                                             const CtkRpgdBatchDesc* __restrict__ desc,
                                                             const CtkRpgdBatchStep* __restrict__ steps) {
-    const CtkRpgdBatchStep& rec = steps[blockIdx.y];
-    const CtkRpgdBatchDesc& d = desc[rec.id];
-    const RolloutArgs& lim = a_tpl;                // the limits are read where the kernel argument lies (ctk_g_rpgd_body.inc)
-    RolloutArgs a = a_tpl;                         // sizes, p_magic, inv_Hp1, global_row0 (launcher)
-#pragma unroll
-    for (int i = 0; i < Env<ENV>::S; ++i) a.s0[i] = rec.s[i];
-#pragma unroll
-    for (int c = 0; c < Env<ENV>::C; ++c) a.u_prev[c] = rec.u_prev[c];
-    a.u_prev_dev = rec.dev_uprev ? d.u_dev : nullptr;
-    a.J = d.J;
-    a.seed_lo = d.seed_lo; a.seed_hi = d.seed_hi; a.call = rec.call;
-    const uint32_t cur = rec.cur & 1u;
-    float* __restrict__ Q = d.pop[cur];
-    float* __restrict__ m = d.m[cur];
-    float* __restrict__ v = d.v[cur];
-    const int t0 = rec.t0, iters = rec.iters;
-    float* __restrict__ scratch = d.scratch;       // blockIdx.x == 0: the problem's own slice
+#include "ctk_g_rpgd_batch_pro.inc"
 #include "ctk_g_rpgd_body.inc"
-    FusedWarm fw = fw_tpl;                         // K, P, shift_previous, the sampling constants, interp (launcher)
-    fw.idx_out = d.idx;
-    fw.w.n_new = rec.resample ? a.N - fw.K : 0;
-    fw.w.gather = rec.resample ? 1 : 0;
-    fw.p.draws = rec.draws;
-    fw.p.Q_old = Q; fw.p.m_old = m; fw.p.v_old = v; fw.p.ages_old = d.ages[cur];
-    fw.p.Q_new = d.pop[cur ^ 1u]; fw.p.m_new = d.m[cur ^ 1u]; fw.p.v_new = d.v[cur ^ 1u]; fw.p.ages_new = d.ages[cur ^ 1u];
-    fw.p.u_nom = d.u_nom; fw.p.u_dev = d.u_dev; fw.p.u_host = d.u_host; fw.p.seq = rec.seq;
-    rpgd_fused_tail(a, lim, fw, g_s, t, HC);
+#include "ctk_g_rpgd_batch_epi.inc"
+}
+
+// The PER-PROBLEM-PARAMETER form of the batch kernel (ctk_rpgd_problem_set_param): the same prologue, body and tail, but the derived
+// constants `k` of the problem come from device memory instead of the by-value argument.  The host writes them BEHIND the step records, in
+// the records' order (stride CtkBatchKStride<ENV>, derived with Env<ENV>::derive, as a handle's are), so they arrive with the records'
+// transfer and element blockIdx.y of ksteps belongs to record blockIdx.y of steps — indexed by launch order, not by problem id.  The
+// address depends on blockIdx.y alone: uniform, so the constants arrive by scalar loads like the record.  They are copied into a local K
+// here, once, ahead of the body: the descent stores to Q / m / v through all its iterations, and nothing is left to be read again behind
+// those stores.  No workgroup waits for another in this form either.
+template <int ENV>
+__global__ __launch_bounds__(GR_BLOCK) void ctk_g_rpgd_batch_pp(RolloutArgs a_tpl, const unsigned char* __restrict__ ksteps, AdamK ad,
+                                                               const float* __restrict__ bc_table, int bc_len, int tape_in_lds, FusedWarm fw_tpl,
+                                                               const CtkRpgdBatchDesc* __restrict__ desc,
+                                                               const CtkRpgdBatchStep* __restrict__ steps) {
+#include "ctk_g_rpgd_batch_pro.inc"
+    const typename Env<ENV>::K k = *reinterpret_cast<const typename Env<ENV>::K*>(ksteps + (size_t)blockIdx.y * CtkBatchKStride<ENV>::value);
+#include "ctk_g_rpgd_body.inc"
+#include "ctk_g_rpgd_batch_epi.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -380,16 +375,18 @@ hipError_t ctk_launch_g_rpgd_descent(hipStream_t st, int env, const RolloutArgs&
 }
 
 
-const char* ctk_g_rpgd_batch_name(int env) { return ctk_kernel_name("ctk_g_rpgd_batch<%d>", env); }
+const char* ctk_g_rpgd_batch_name(int env, bool per_problem) {
+    return ctk_kernel_name(per_problem ? "ctk_g_rpgd_batch_pp<%d>" : "ctk_g_rpgd_batch<%d>", env);
+}
 
 hipError_t ctk_launch_g_rpgd_batch(hipStream_t st, int env, const RolloutArgs& a_in, const float* params, float dt, int isteps, float lr,
                                    float b1, float b2, float eps, float clip, int rule, const float* bc_table, int bc_len,
-                                   const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems) {
+                                   const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems,
+                                   const void* k_steps_dev) {
     AdamK ad{lr, b1, b2, (float)(1.0 - (double)b1), (float)(1.0 - (double)b2), eps, clip, rule};
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
         const RolloutArgs a = ctk_descent_args(a_in, E::C);
-        const typename E::K k = E::derive(params, dt, isteps);
         bool tape_in_lds = false;
         const size_t lds = ctk_g_rpgd_descent_lds(env, a.H, &tape_in_lds);
         FusedWarm fw{};
@@ -398,7 +395,13 @@ hipError_t ctk_launch_g_rpgd_batch(hipStream_t st, int env, const RolloutArgs& a
                         f.sample_max, f.whole_space, nullptr, 0, 0, 0};
         fw.p.interp = f.interp;
         const dim3 grid(1, n_problems), block(GR_BLOCK);
-        hipLaunchKernelGGL((ctk_g_rpgd_batch<EV>), grid, block, lds, st, a, k, ad, bc_table, bc_len, tape_in_lds ? 1 : 0, fw, desc_dev, steps_dev);
+        if (k_steps_dev) {                             // per-problem constants: element j belongs to record j (ctk_mppi_batch_derive_k)
+            hipLaunchKernelGGL((ctk_g_rpgd_batch_pp<EV>), grid, block, lds, st, a, static_cast<const unsigned char*>(k_steps_dev), ad, bc_table, bc_len,
+                               tape_in_lds ? 1 : 0, fw, desc_dev, steps_dev);
+        } else {
+            const typename E::K k = E::derive(params, dt, isteps);
+            hipLaunchKernelGGL((ctk_g_rpgd_batch<EV>), grid, block, lds, st, a, k, ad, bc_table, bc_len, tape_in_lds ? 1 : 0, fw, desc_dev, steps_dev);
+        }
     });
     return hipGetLastError();
 }

@@ -397,7 +397,7 @@ struct CtkRpgdBatchStep {
     float s[CTK_MAX_STATES];
     float u_prev[CTK_MAX_INPUTS];
 };
-static_assert(sizeof(CtkRpgdBatchStep) % 16 == 0, "step records are copied and indexed as an array");
+static_assert(sizeof(CtkRpgdBatchStep) % 16 == 0, "step records are copied and indexed as an array; the per-problem constants lie behind them, 16-aligned");
 // ctk_rpgd.hip: the warm start with reset = 1 (sample_actions of every plan, moments and ages 0) of n_problems records in ONE launch,
 // grid (blocks, problems); f: P, the sampling constants and interp only; the records' id / call / cur / draws are read
 hipError_t ctk_launch_rpgd_batch_reset(hipStream_t st, const RolloutArgs& a, const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev,
@@ -436,11 +436,14 @@ hipError_t ctk_launch_g_rpgd_descent(hipStream_t st, int env, const RolloutArgs&
                                      int rule = 0);
 // n_problems step records from `steps_dev` on as ONE launch of ctk_g_rpgd_batch<env>: descent, keep-k selection and warm start of every
 // problem.  a: the shared template (limits, sizes; s0 / u_prev / J / seed / call come from the records and descriptors); f: keep_k, P,
-// shift_previous, the sampling constants and interp (its pointers, n_new and gather are the records' and descriptors')
-const char* ctk_g_rpgd_batch_name(int env);
+// shift_previous, the sampling constants and interp (its pointers, n_new and gather are the records' and descriptors').
+// k_steps_dev == nullptr: ctk_g_rpgd_batch, every problem with the constants of `params`; else the per-problem form ctk_g_rpgd_batch_pp<env>,
+// record j of steps_dev with element j of k_steps_dev (stride ctk_mppi_batch_k_stride(env), filled by ctk_mppi_batch_derive_k; `params` unused)
+const char* ctk_g_rpgd_batch_name(int env, bool per_problem = false);
 hipError_t ctk_launch_g_rpgd_batch(hipStream_t st, int env, const RolloutArgs& a, const float* params, float dt, int isteps, float lr,
                                    float b1, float b2, float eps, float clip, int rule, const float* bc_table, int bc_len,
-                                   const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems);
+                                   const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems,
+                                   const void* k_steps_dev = nullptr);
 
 // ---- ctk_generic_net.hip : the template kernels with a network predictor (net = CTK_PRED_MLP | CTK_PRED_GRU; ctk_net.h) -----
 // wperm: the policy's per-lane operand tables (forward | reverse), followed by the GRU's carried hidden state [64]

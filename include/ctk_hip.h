@@ -604,16 +604,17 @@ int ctk_cem_problem_params_differ(const ctk_cem_batch* b);                      
  * plans: a whole step of such a controller is ONE workgroup, one CU of 256, and a template handle pays three launches for it (descent,
  * selection, warm start).  A batch steps any subset of its problems with one launch of ctk_g_rpgd_batch<ENV>, grid (1, problems of
  * the launch): descent, keep-k selection and warm start of every listed problem.
- *  - shared by all problems: everything in ctk_config and the parameter table (ctk_rpgd_batch_set_param);
+ *  - shared by all problems: everything in ctk_config (environment, N, H, limits, Adam and sampling constants);
  *    per problem: state, previous input, population, Adam moments and step number, ages, last output, Philox seed and position, step
- *    count, draws and the readable buffers;
+ *    count, draws, the readable buffers and the parameter table (plant, cost weights, targets: ctk_rpgd_problem_set_param below);
  *  - CONTRACT: problem p behaves bit for bit like a ctk_handle created from the same ctk_config (optimizer = CTK_OPT_RPGD, ODE
  *    predictor; for CartPole generic_kernels = 1, the template kernels) with seed = seeds[p] that received the same calls (ctk_reset,
  *    ctk_step, ctk_set_state, ctk_set_param, ctk_rng_set_position): u, CTK_BUF_Q, J, U_NOM, PLAN, ADAM_M, ADAM_V, AGES, AGES_LOGGED,
  *    BEST_IDX, the Philox position and the ctk_get_state vector (population, both moments [N,H,C] | ages [N] | u [C] | adam_step |
  *    count), for every sample source, u_prev given or NULL, and any interleaving of whole-batch steps, subset steps, per-problem resets,
- *    ctk_rpgd_batch_set_state and ctk_rpgd_batch_set_param — also where the problems of one launch differ in iteration count (the
- *    first step after a reset runs warmup_iterations or outer_its), Adam step number or resampling (count % resamp_per);
+ *    ctk_rpgd_batch_set_state and parameter changes (ctk_set_param is one of those calls: ctk_rpgd_problem_set_param on problem p, or
+ *    ctk_rpgd_batch_set_param on all of them) — also where the problems of one launch differ in iteration count (the first step after a
+ *    reset runs warmup_iterations or outer_its), Adam step number or resampling (count % resamp_per);
  *  - refused with CTK_ERR_UNSUPPORTED and the sizes in ctk_rpgd_batch_last_error(NULL), from the configuration alone (no device is
  *    touched): an optimizer other than CTK_OPT_RPGD (CTK_OPT_GRADIENT included), a predictor other than ODE, num_rollouts > 64 (the
  *    population one workgroup holds), opt_keep_k > num_rollouts, materialize_trajectories, a horizon whose plans and gradients alone
@@ -631,6 +632,19 @@ int ctk_cem_problem_params_differ(const ctk_cem_batch* b);                      
  *  - ctk_rpgd_batch_reset draws the initial populations (RPGD's reset does): draws [n,N,P,C] in id order, or NULL with
  *    draws_loc = CTK_LOC_NONE for the in-kernel sampler; ONE launch for the call;
  *  - ctk_rpgd_batch_step is synchronous.  A batch is NOT thread-safe.
+ *  - parameters: every problem has its own table [CTK_MAX_PARAMS], initialised with the environment's defaults.
+ *    ctk_rpgd_batch_set_param(id, v) writes column id of EVERY problem's table (the other ids stay per problem) and of the shared table
+ *    that ctk_rpgd_batch_get_param reads, so ctk_rpgd_batch_get_param returns the last whole-batch value of id, NOT what a problem holds
+ *    after a ctk_rpgd_problem_set_param (ctk_rpgd_problem_get_param reads that).  ctk_rpgd_problem_set_param sets parameter id of the
+ *    listed problems (ids as above; values[n], one per listed problem, in the order of ids), legal only between steps; a bad id list, a
+ *    bad parameter id, NULL values or a NULL batch is CTK_ERR_INVALID_ARGUMENT and nothing is written.  The kernel constants of a problem
+ *    whose table changed are re-derived when that problem is next stepped (as ctk_set_param derives a handle's) and travel behind the
+ *    step records, in the records' one transfer: new values before every step cost no transfer of their own.  Once a
+ *    ctk_rpgd_problem_set_param has succeeded, ctk_rpgd_problem_params_differ is 1 for the rest of the batch's life (0 before, and for a
+ *    NULL batch) and the steps launch the per-problem form of the kernel, ctk_g_rpgd_batch_pp<ENV> (ctk_rpgd_batch_dominant_kernel
+ *    names the form the next step launches); a batch that never calls it runs the shared form.  ctk_rpgd_batch_reset and
+ *    ctk_rpgd_batch_set_state leave the tables alone, as ctk_reset and ctk_set_state leave a handle's: they are not part of the state
+ *    vector.
  * Each entry corresponds to the single-handle call named beside it.
  * ----------------------------------------------------------------------------------------- */
 typedef struct ctk_rpgd_batch ctk_rpgd_batch;
@@ -655,6 +669,9 @@ int ctk_rpgd_batch_get_param(const ctk_rpgd_batch* b, int id, float* value);    
 int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32_t* call);      /* ctk_rng_get_position */
 int ctk_rpgd_batch_rng_set_position(ctk_rpgd_batch* b, int problem, uint32_t call);             /* ctk_rng_set_position */
 const char* ctk_rpgd_batch_dominant_kernel(const ctk_rpgd_batch* b);                            /* ctk_dominant_kernel */
+int ctk_rpgd_problem_set_param(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, int id, const float* values);   /* ctk_set_param of every listed problem */
+int ctk_rpgd_problem_get_param(const ctk_rpgd_batch* b, int problem, int id, float* value);     /* ctk_get_param of one problem */
+int ctk_rpgd_problem_params_differ(const ctk_rpgd_batch* b);                                    /* 1 once a ctk_rpgd_problem_set_param has succeeded */
 
 #ifdef __cplusplus
 }
