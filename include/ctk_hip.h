@@ -324,8 +324,11 @@ int ctk_step(ctk_handle* h, const float* s, const float* u_prev,
 /* Number of raw draws (floats) the NEXT ctk_step consumes from `samples` (0 if none).        */
 size_t ctk_samples_needed(const ctk_handle* h);
 
-/* Position of the on-device Philox stream = the number of completed steps/resets that drew (the `call` word of
- * the counter).  Together with ctk_get_state (and ctk_predictor_get_hidden for a recurrent predictor) it makes a
+/* Position of the on-device Philox stream = the `call` word of the counter the NEXT call's draws take.  0 on a new handle; +1 after
+ * every COMPLETED ctk_step, whether or not it drew (an RPGD step that does not resample counts, and so does a step fed from a caller's
+ * buffer), and +1 after a ctk_reset that draws (RPGD and gradient; the other optimizers' resets draw nothing and leave it).  A refused
+ * call leaves it alone.  ctk_rng_set_position(k) makes the next call's draws those of call = k (tests/test_gpu_device_rng.py pins all of
+ * this against oracle/ctk_oracle.py: device_noise).  Together with ctk_get_state (and ctk_predictor_get_hidden for a recurrent predictor) it makes a
  * handle resumable bit-for-bit: reference create_rng(seed) returns a generator object whose state the caller can
  * save and restore (others/globals_and_utils.py:86-99).                                                          */
 int ctk_rng_get_position(const ctk_handle* h, uint32_t* call);

@@ -1151,7 +1151,7 @@ class RPGD:
 
 # ----------------------------------------------------------------------------------------------
 # Counter-based RNG of the performance mode (Philox4x32-10 + Box-Muller); the device code in
-# csrc/ctk_rng.h follows the same published algorithm (Salmon et al., SC'11).  The integer stream
+# csrc/ctk_device.h follows the same published algorithm (Salmon et al., SC'11).  The integer stream
 # is bit-exact; the normal transform differs by fp32 rounding of log/sin/cos only.
 # ----------------------------------------------------------------------------------------------
 _PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)

@@ -177,15 +177,11 @@ def test_random_action_matches_oracle(N, H):
     e.close()
 
 
-def test_device_rng_cem_and_random_run():
-    e = CtkEngine("cem", "ODE", num_rollouts=512, mpc_horizon=20, dt=0.02, cem_outer_it=2, cem_best_k=50, seed=3)
+def test_device_rng_cem_and_random_run(monkeypatch):
+    # CEM: Q, J, BEST_IDX, U_NOM, STD and u of the device-draw step against the oracle fed device_noise (stream `it` per outer iteration)
+    from test_gpu_device_rng import cem_compare
+    cem_compare(monkeypatch, "one_launch", "ODE", "CartPole", 512, 20, 50, 2, steps=1, seed=3, mat=False)
     s = np.array([0.0, 0.0, 3.0, 0.0], np.float32)
-    u = e.step(s)
-    Q = e.read("Q")
-    assert np.isfinite(u).all() and abs(Q.mean()) < 0.1 and 0.2 < Q.std() < 0.7
-    noise_like = O.device_noise(seed=3, stream=1, call=0, first_row=0, rows=512, cols=20, kind="normal")
-    assert noise_like.shape == (512, 20)
-    e.close()
     r = CtkEngine("random_action", "ODE", num_rollouts=256, mpc_horizon=10, dt=0.02, seed=4)
     u = r.step(s)
     Q = r.read("Q")
