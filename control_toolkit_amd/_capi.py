@@ -184,6 +184,29 @@ SYMBOLS = {
     "ctk_rpgd_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
     "ctk_rpgd_problem_params_differ": (C.c_int, [_H]),
     "ctk_rpgd_template_descent_lds": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    # batched MPPI with the MLP predictor (ctk_mlp_batch_* / ctk_mlp_problem_*): _H is the ctk_mlp_batch* there; the signatures of ctk_batch_*
+    "ctk_mlp_batch_create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
+    "ctk_mlp_batch_destroy": (None, [_H]),
+    "ctk_mlp_batch_last_error": (C.c_char_p, [_H]),
+    "ctk_mlp_batch_size": (C.c_int, [_H]),
+    "ctk_mlp_batch_samples_needed": (C.c_size_t, [_H]),
+    "ctk_mlp_batch_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ctk_mlp_batch_reset": (C.c_int, [_H, C.c_int, C.c_void_p]),
+    "ctk_mlp_batch_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_mlp_batch_get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_mlp_batch_set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "ctk_mlp_batch_set_param": (C.c_int, [_H, C.c_int, C.c_float]),
+    "ctk_mlp_batch_get_param": (C.c_int, [_H, C.c_int, _FP]),
+    "ctk_mlp_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
+    "ctk_mlp_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
+    "ctk_mlp_batch_dominant_kernel": (C.c_char_p, [_H]),
+    "ctk_mlp_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ctk_mlp_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
+    "ctk_mlp_problem_params_differ": (C.c_int, [_H]),
+    "ctk_mlp_batch_weight_count": (C.c_size_t, [_H]),
+    "ctk_mlp_batch_set_weights": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
+    "ctk_mlp_problem_set_weights": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ctk_mlp_problem_have_weights": (C.c_int, [_H, C.c_int]),
 }
 
 
@@ -905,6 +928,115 @@ class CtkMppiBatch:
 
     def dominant_kernel(self) -> str:
         return self._lib.ctk_batch_dominant_kernel(self._h).decode()
+
+
+# ---- batched MPPI with the MLP predictor (include/ctk_hip.h: ctk_mlp_batch_* / ctk_mlp_problem_*) --------------------------------------
+def mlp_weight_count(num_states: int, num_control_inputs: int, hidden=(32, 32)) -> int:
+    """floats of one (S+C)-h1-h2-S MLP in the layout of ctk_set_predictor_weights: W1, b1, W2, b2, W3, b3 (ctk_mlp_batch_weight_count)"""
+    i, s, (h1, h2) = int(num_states) + int(num_control_inputs), int(num_states), (int(hidden[0]), int(hidden[1]))
+    return i * h1 + h1 + h1 * h2 + h2 + h2 * s + s
+
+
+class _MlpBatchEntries:
+    """the library as CtkMppiBatch's methods name it, answering with the MLP family's entry of the same signature"""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        if name.startswith("ctk_batch_"):
+            name = "ctk_mlp_batch_" + name[len("ctk_batch_"):]
+        elif name.startswith("ctk_problem_"):
+            name = "ctk_mlp_problem_" + name[len("ctk_problem_"):]
+        return getattr(self._lib, name)
+
+
+class CtkMppiMlpBatch(CtkMppiBatch):
+    """Owns one ctk_mlp_batch: num_problems independent MPPI controllers of ONE configuration whose plant model is a learned MLP, stepped
+    by one kernel launch per step.  Problem p behaves bit for bit like CtkEngine("mppi", "MLP", seed=seeds[p], predictor_hidden=...) given
+    the same calls, set_predictor_weights and set_param among them.  The methods are CtkMppiBatch's; the network is the plant here, so
+    every problem has its own: set_weights gives all problems one network, set_problem_weights the listed problems one each.  A problem
+    steps only once it has weights.  predictor_hidden = (h1, h2): the hidden widths of all the batch's networks (default 32 / 32, at most
+    32; narrower ones are embedded exactly).  CartPole only."""
+
+    def __init__(self, num_problems: int, *, seeds=None, predictor_hidden=None, environment: str = "CartPole", optimizer: str = "mppi",
+                 predictor: str = "MLP", num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
+                 period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
+                 materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
+                 num_control_inputs: int = None, generic_kernels: bool = False, **kw):
+        # what needs no device is checked before the library is asked for one
+        if int(num_problems) < 1:
+            raise ValueError(f"a batch holds at least one problem (num_problems == {num_problems})")
+        B = int(num_problems)
+        if optimizer != "mppi":
+            raise NotImplementedError(f"a batch steps MPPI controllers only (optimizer {optimizer!r}); the other optimizers run as CtkEngine")
+        if predictor != "MLP":
+            raise NotImplementedError(f"this batch rolls out the MLP predictor only (predictor {predictor!r}): the analytic one is CtkMppiBatch, "
+                                      "the GRU's carried hidden state has no batch form (CtkEngine)")
+        if environment != "CartPole" or generic_kernels:
+            raise NotImplementedError(f"the MLP batch kernel is CartPole's matrix-core kernel (environment {environment!r}, generic_kernels "
+                                      f"{bool(generic_kernels)}); the template network kernels run as CtkEngine")
+        hidden = (32, 32) if predictor_hidden is None else tuple(int(x) for x in np.asarray(predictor_hidden).reshape(-1))
+        if len(hidden) != 2 or min(hidden) < 1:
+            raise ValueError(f"predictor_hidden must be two widths >= 1 (h1, h2), got {predictor_hidden!r}")
+        if max(hidden) > 32:
+            raise NotImplementedError(f"the MLP batch kernel holds 32 units per hidden layer (predictor_hidden {hidden}); wider networks run as CtkEngine")
+        if seeds is not None:
+            seeds = np.ascontiguousarray(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in np.asarray(seeds, dtype=object).reshape(-1)], np.uint64))
+            if seeds.size != B:
+                raise ValueError(f"seeds must have one entry per problem ({B}), got {seeds.size}")
+        lib, env_id = environment_library(environment)
+        lib = _MlpBatchEntries(lib)
+        S, Cn, self.param_names = environment_info(environment)
+        self.environment, self.S, self.C, self.B = environment, S, Cn, B
+        self.predictor_hidden = hidden
+        self._wn = mlp_weight_count(S, Cn, hidden)
+        if predictor_hidden is not None:
+            kw = dict(kw, predictor_hidden1=hidden[0], predictor_hidden2=hidden[1])
+        cfg = _make_config("mppi", "MLP", env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                           action_low=action_low, action_high=action_high,
+                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                           global_rollout_offset=global_rollout_offset, num_states=S if num_states is None else num_states,
+                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs, generic_kernels=generic_kernels, **kw)
+        self._lib, self.cfg = lib, cfg
+        self.N, self.H = int(num_rollouts), int(mpc_horizon)
+        self._h = _H()
+        rc = lib.ctk_batch_create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
+        if rc != 0:
+            msg = lib.ctk_batch_last_error(None).decode()
+            self._h = _H()
+            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(msg)
+        self._per = int(lib.ctk_batch_samples_needed(self._h))
+        self._s = np.zeros((B, S), np.float32)
+        self._up = np.zeros((B, Cn), np.float32)
+        self._u = np.zeros((B, Cn), np.float32)
+        self._ids = np.zeros(B, np.int32)
+        self._s_p, self._up_p, self._u_p, self._ids_p = (a.ctypes.data for a in (self._s, self._up, self._u, self._ids))
+        self._step_fn = lib.ctk_batch_step
+
+    def weight_count(self) -> int:
+        """floats of one problem's network (predictor_hidden's widths)"""
+        return int(self._lib.ctk_mlp_batch_weight_count(self._h))
+
+    def set_weights(self, w):
+        """one network [weight_count()] for every problem"""
+        w = _f32(w).ravel()
+        if w.size != self._wn:
+            raise ValueError(f"a network of hidden widths {self.predictor_hidden} has {self._wn} weights, got {w.size}")
+        self._check(self._lib.ctk_mlp_batch_set_weights(self._h, _ptr(w), w.size))
+
+    def set_problem_weights(self, W, ids=None):
+        """W [n, weight_count()]: one network per problem in ids (None: all problems), in the order of ids; one transfer for the call"""
+        idv = batch_ids(self.B, ids)
+        n = self.B if idv is None else int(idv.size)
+        W = _f32(W)
+        if W.shape != (n, self._wn) and not (n == 1 and W.shape == (self._wn,)):
+            raise ValueError(f"weights must have shape ({n}, {self._wn}): one network per listed problem, got {tuple(W.shape)}")
+        self._check(self._lib.ctk_mlp_problem_set_weights(self._h, n, _ptr(idv), _ptr(W), self._wn))
+
+    def have_weights(self, problem: int) -> bool:
+        return bool(self._lib.ctk_mlp_problem_have_weights(self._h, self._problem(problem)))
 
 
 # ---- batched CEM (include/ctk_hip.h: ctk_cem_batch_*) ---------------------------------------------------------------------------------

@@ -1616,6 +1616,19 @@ static size_t shaped_weight_count(int predictor, int S, int C, int h1, int h2) {
     if (predictor == CTK_PRED_GRU) return (3 * a * I + 3 * a * a + 6 * a) + (3 * b * a + 3 * b * b + 6 * b) + (b * (size_t)S + S);
     return 0;
 }
+// an I-h1-h2-S MLP's raw weights into the zero-initialised raw layout of an I-W-W-S one (h1, h2 <= W): every matrix into the top-left of
+// its wider one (ctk_set_predictor_weights_shaped; the MLP batch's weight calls)
+static void embed_mlp_rows(const float* w, int S, int I, int h1, int h2, int W, float* full) {
+    const float* p = w;
+    float* q = full;
+    auto rows = [&](int r_src, int c_src, int r_dst, int c_dst) {
+        for (int r = 0; r < r_src; ++r) std::memcpy(q + (size_t)r * c_dst, p + (size_t)r * c_src, (size_t)c_src * sizeof(float));
+        p += (size_t)r_src * c_src; q += (size_t)r_dst * c_dst;
+    };
+    rows(h1, I, W, I); rows(1, h1, 1, W);          // W1, b1
+    rows(h2, h1, W, W); rows(1, h2, 1, W);         // W2, b2
+    rows(S, h2, S, W); rows(1, S, 1, S);           // W3, b3
+}
 size_t ctk_predictor_weight_count_shaped(const ctk_handle* h, int h1, int h2) {
     return (h && h1 >= 1 && h2 >= 1) ? shaped_weight_count(h->cfg.predictor, h->S, h->C, h1, h2) : 0;
 }
@@ -1641,9 +1654,7 @@ int ctk_set_predictor_weights_shaped(ctk_handle* h, const float* w, size_t n, in
         p += (size_t)r_src * c_src; q += (size_t)r_dst * c_dst;
     };
     if (h->cfg.predictor == CTK_PRED_MLP) {
-        rows(h1, I, W, I); rows(1, h1, 1, W);          // W1, b1
-        rows(h2, h1, W, W); rows(1, h2, 1, W);         // W2, b2
-        rows(S, h2, S, W); rows(1, S, 1, S);           // W3, b3
+        embed_mlp_rows(w, S, I, h1, h2, W, full.data());
     } else {
         auto gates = [&](int hs, int c_src, int c_dst) {               // [3 hs, c_src] (rows r|z|n) -> [96, c_dst]
             for (int gte = 0; gte < 3; ++gte) {
@@ -2402,6 +2413,13 @@ struct ctk_batch {
     std::vector<uint32_t> seq, call;
     std::vector<int> cur;
     std::string err, dominant;
+    // the MLP family (include/ctk_hip.h: ctk_mlp_batch_*): the same struct with a predictor field and per-problem weight tables
+    int pred = CTK_PRED_ODE;                // CTK_PRED_MLP: ctk_mppi_batch_mlp<LOG> / ctk_mppi_batch_mlp_pp<LOG>
+    int hid1 = 32, hid2 = 32;               // the network's hidden widths (cfg.predictor_hidden1/2, 0 = 32): narrower ones are embedded
+    size_t wtab = 0;                        // floats of one per-lane weight table (ctk_mppi_batch_mlp_table_floats)
+    float* d_w = nullptr;                   // [B][wtab] problem p's table, in the layout of a handle's d_wperm
+    float* h_w = nullptr;                   // pinned [B][wtab]: the staging of ONE transfer per weight call
+    std::vector<unsigned char> have_w;      // [B] the problem has received weights
     size_t unom_stride() const { return (size_t)2 * HC; }
     float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
     float* slot(int p) const { return h_u + (size_t)p * 16; }
@@ -2411,8 +2429,17 @@ struct ctk_batch {
 
 namespace {
 
+// the MLP family runs the code of this one; its messages carry its own entry points' names (ctk_batch_x -> ctk_mlp_batch_x,
+// ctk_problem_x -> ctk_mlp_problem_x), substituted here where a message is stored, so that this family's texts are the literals below
+std::string mlp_family_names(std::string msg) {
+    for (const char* from : {"ctk_batch_", "ctk_problem_"}) {
+        const std::string to = std::string("ctk_mlp_") + (from + 4);
+        for (size_t at = msg.find(from); at != std::string::npos; at = msg.find(from, at + to.size())) msg.replace(at, std::strlen(from), to);
+    }
+    return msg;
+}
 int bfail(ctk_batch* b, int code, const std::string& msg) {
-    if (b) b->err = msg; else g_create_error = msg;
+    if (b) b->err = b->pred == CTK_PRED_MLP ? mlp_family_names(msg) : msg; else g_create_error = msg;
     return code;
 }
 #define BHIP_TRY(b, expr)                                                                       \
@@ -2492,50 +2519,78 @@ int ctk_batch_size(const ctk_batch* b) { return b ? b->B : 0; }
 size_t ctk_batch_samples_needed(const ctk_batch* b) { return b ? (size_t)b->N * b->PC : 0; }
 const char* ctk_batch_dominant_kernel(const ctk_batch* b) { return b ? b->dominant.c_str() : ""; }
 
-void ctk_batch_destroy(ctk_batch* b) {
-    if (!b) return;
+}  // extern "C"
+
+namespace {
+
+// everything a batch owns on the device and in pinned memory (both families' destroy; a failed creation)
+void batch_release(ctk_batch* b) {
     hipSetDevice(b->cfg.device);
     if (b->stream) hipStreamSynchronize(b->stream);
-    void* bufs[] = {b->d_interp, b->d_J, b->d_Q, b->d_traj, b->d_parts, b->d_ll, b->d_unom, b->d_u, b->d_desc, b->d_steps, b->d_samples, b->d_k};
+    void* bufs[] = {b->d_interp, b->d_J, b->d_Q, b->d_traj, b->d_parts, b->d_ll, b->d_unom, b->d_u, b->d_desc, b->d_steps, b->d_samples, b->d_k, b->d_w};
     for (void* p : bufs) if (p) hipFree(p);
     if (b->h_u) hipHostFree(b->h_u);
     if (b->h_steps) hipHostFree(b->h_steps);
     if (b->h_k) hipHostFree(b->h_k);
+    if (b->h_w) hipHostFree(b->h_w);
     if (b->stream) hipStreamDestroy(b->stream);
-    delete b;
 }
 
-int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_batch** out) {
-    if (out) *out = nullptr;
-    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: NULL argument");
-    if (n_problems < 1) return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+// ctk_batch_create (pred == CTK_PRED_ODE) and ctk_mlp_batch_create (CTK_PRED_MLP) into the caller's fresh struct: the refusals that need
+// only the configuration, the device probe, the buffers.  On failure everything is released and the message is in g_create_error.
+int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problems, const uint64_t* seeds) {
+    const bool mlp = pred == CTK_PRED_MLP;
+    const char* who = mlp ? "ctk_mlp_batch_create" : "ctk_batch_create";
+    auto refuse = [&](int code, const std::string& msg) { return bfail(nullptr, code, mlp ? mlp_family_names(msg) : msg); };
+    if (n_problems < 1) return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
     const EnvInfo* einfo = nullptr;
-    if (int rc = check_config("ctk_batch_create", cfg, &einfo)) return rc;
-    if (cfg->optimizer != CTK_OPT_MPPI)
-        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch steps MPPI controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
-                     "); the other optimizers run as single handles (ctk_create)");
-    if (cfg->predictor != CTK_PRED_ODE)
-        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
-                     std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
-    if (!(cfg->LBD > 0.0f && cfg->NU != 0.0f)) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: MPPI needs LBD > 0 and NU != 0");
+    if (int rc = check_config(who, cfg, &einfo)) return rc;
     const int N = cfg->num_rollouts, H = cfg->mpc_horizon, P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
+    const int hw1 = cfg->predictor_hidden1 ? cfg->predictor_hidden1 : 32, hw2 = cfg->predictor_hidden2 ? cfg->predictor_hidden2 : 32;
+    // the MLP family's refusals name the sizes refused: population, horizon, inducing points and the network as the reference names it
+    const std::string sizes = !mlp ? std::string()
+        : " (num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ", " + std::to_string(P) + " inducing points, network " +
+          std::to_string(einfo->S + einfo->C) + "IN-" + std::to_string(hw1) + "H1-" + std::to_string(hw2) + "H2-" + std::to_string(einfo->S) + "OUT)";
+    if (cfg->optimizer != CTK_OPT_MPPI)
+        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch steps MPPI controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+                      "); the other optimizers run as single handles (ctk_create)" + sizes);
+    if (!mlp && cfg->predictor != CTK_PRED_ODE)
+        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
+                      std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
+    if (mlp) {
+        if (cfg->predictor == CTK_PRED_ODE)
+            return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: this family rolls out the MLP predictor (cfg.predictor == " + std::to_string(cfg->predictor) +
+                         " is the analytic one: use ctk_batch_create)" + sizes);
+        if (cfg->predictor != CTK_PRED_MLP)
+            return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: this family rolls out the MLP predictor only (cfg.predictor == " + std::to_string(cfg->predictor) +
+                         "); the GRU's carried hidden state has no batch form, such a controller runs as a single handle (ctk_create)" + sizes);
+        if (cfg->environment != CTK_ENV_CARTPOLE || cfg->generic_kernels != 0)
+            return bfail(nullptr, CTK_ERR_UNSUPPORTED, std::string("ctk_mlp_batch_create: the batch kernel is CartPole's matrix-core MLP kernel (environment ") + einfo->name +
+                         ", generic_kernels == " + std::to_string(cfg->generic_kernels) + "): such handles run the one-wave template network kernels, which have no batch form (ctk_create)" + sizes);
+        if (hw1 < 1 || hw2 < 1) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_create: predictor_hidden1 / predictor_hidden2 must be >= 1 (0 = 32)");
+        if (std::max(hw1, hw2) > 32)
+            return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: the batch kernel holds 32 units per hidden layer (narrower layers are embedded exactly); wider "
+                         "networks run the 64-unit template kernels, which have no batch form (ctk_create)" + sizes);
+    }
+    if (!(cfg->LBD > 0.0f && cfg->NU != 0.0f)) return refuse(CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: MPPI needs LBD > 0 and NU != 0");
     size_t lds = 0;
     int blocks = 0;
-    if (const int why = ctk_mppi_batch_fit(cfg->environment, N, H, P, &lds, &blocks)) {
+    if (const int why = mlp ? ctk_mppi_batch_mlp_fit(N, H, P, &lds, &blocks) : ctk_mppi_batch_fit(cfg->environment, N, H, P, &lds, &blocks)) {
         const std::string sizes = "num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ", " + std::to_string(P) + " inducing points x " +
                                   std::to_string(einfo->C) + " inputs = " + std::to_string(blocks) + " block records of " + std::to_string(2 + P * einfo->C) + " words";
-        const char* reason = why == 1 ? ": populations from 32768 rollouts on run the throughput kernels, which a batch does not have"
+        const char* reason = why == 1 ? (mlp ? ": a handle of this size does not run the pair form of the MLP kernel (more than 8192 rollouts, or CTK_MPPI_NO_PAIR is set), the only one a batch has"
+                                             : ": populations from 32768 rollouts on run the throughput kernels, which a batch does not have")
                            : why == 2 ? ": the batch kernel has the narrow in-launch hand-off only (at most 128 records and 2048 record words per problem)"
                            : why == 3 ? ": the block records do not fit the hand-off's LDS staging"
                                       : ": the rollout tiles need more than 160 KiB of LDS";
-        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_batch_create: per-problem population outside the batch kernel's sizes (" + sizes + ")" + reason +
-                     (why == 4 ? " (" + std::to_string(lds) + " bytes)" : std::string()) + "; such a controller runs as a single handle (ctk_create)");
+        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: per-problem population outside the batch kernel's sizes (" + sizes + ")" + reason +
+                      (why == 4 ? " (" + std::to_string(lds) + " bytes)" : std::string()) + "; such a controller runs as a single handle (ctk_create)");
     }
 
     hipDeviceProp_t prop;
-    if (int rc = probe_device("ctk_batch_create", cfg->device, &prop)) return rc;
+    if (int rc = probe_device(who, cfg->device, &prop)) return rc;
 
-    ctk_batch* b = new ctk_batch();
+    b->pred = pred; b->hid1 = hw1; b->hid2 = hw2;
     b->cfg = *cfg;
     b->B = n_problems; b->N = N; b->H = H; b->P = P; b->blocks = blocks;
     b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = H * b->C; b->PC = P * b->C;
@@ -2554,9 +2609,10 @@ int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seed
         if (v >= 1 && v < b->max_per_launch) b->max_per_launch = v;
     }
     b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u); b->cur.assign((size_t)n_problems, 0);
-    b->dominant = ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
+    b->dominant = mlp ? ctk_mppi_batch_mlp_name(cfg->materialize_trajectories != 0) : ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
+    if (mlp) { b->wtab = ctk_mppi_batch_mlp_table_floats(); b->have_w.assign((size_t)n_problems, 0); }
 
-    auto bail = [&](int rc) { g_create_error = b->err; ctk_batch_destroy(b); return rc; };
+    auto bail = [&](int rc) { g_create_error = b->err; batch_release(b); return rc; };
 #define BHIP_CREATE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { b->err = std::string(#expr) + ": " + hipGetErrorString(_e); return bail(CTK_ERR_HIP); } } while (0)
     BHIP_CREATE(hipSetDevice(cfg->device));
     BHIP_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
@@ -2583,6 +2639,10 @@ int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seed
     BHIP_CREATE(dev_zero((void**)&b->d_k, Bz * b->kstride));
     BHIP_CREATE(hipHostMalloc((void**)&b->h_k, Bz * b->kstride, hipHostMallocDefault));
     std::memset(b->h_k, 0, Bz * b->kstride);
+    if (mlp) {
+        BHIP_CREATE(dev_zero((void**)&b->d_w, Bz * b->wtab * sizeof(float)));
+        BHIP_CREATE(hipHostMalloc((void**)&b->h_w, Bz * b->wtab * sizeof(float), hipHostMallocDefault));
+    }
 
     const std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, P);
     std::vector<CtkBatchDesc> desc(Bz);
@@ -2604,6 +2664,24 @@ int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seed
     BHIP_CREATE(hipMemcpyAsync(b->d_unom, plan.data(), plan.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
     BHIP_CREATE(hipStreamSynchronize(b->stream));                  // the host vectors go out of scope below
 #undef BHIP_CREATE
+    return CTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void ctk_batch_destroy(ctk_batch* b) {
+    if (!b) return;
+    batch_release(b);
+    delete b;
+}
+
+int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: NULL argument");
+    ctk_batch* b = new ctk_batch();
+    if (int rc = batch_create_in(b, CTK_PRED_ODE, cfg, n_problems, seeds)) { delete b; return rc; }
     *out = b;
     return CTK_OK;
 }
@@ -2647,8 +2725,12 @@ int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, 
     int launched = 0;                                  // consecutive launches of at most max_per_launch problems: the results do not depend on the split
     while (le == hipSuccess && launched < n) {
         const int cnt = std::min(b->max_per_launch, n - launched);
-        le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, b->d_steps + launched, cnt, log,
-                                   b->differ ? b->d_k : nullptr);
+        if (b->pred == CTK_PRED_MLP)
+            le = ctk_launch_mppi_batch_mlp(b->stream, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, b->d_steps + launched, cnt, log,
+                                           b->d_w, b->differ ? b->d_k : nullptr);
+        else
+            le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, b->d_steps + launched, cnt, log,
+                                       b->differ ? b->d_k : nullptr);
         if (le == hipSuccess) launched += cnt;
     }
     for (int j = 0; j < launched; ++j) b->cur[(size_t)b->h_steps[j].id] ^= 1;
@@ -2769,7 +2851,8 @@ int ctk_problem_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, c
     }
     if (!b->differ) {                                  // sticky: the tables are never compared again
         b->differ = true;
-        b->dominant = ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+        b->dominant = b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
+                                              : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
     }
     return CTK_OK;
 }
@@ -2794,6 +2877,139 @@ int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) {
     b->call[(size_t)problem] = call;
     return CTK_OK;
 }
+
+}  // extern "C"
+
+// =============================================================================================
+// Batched MPPI with the MLP predictor (include/ctk_hip.h: ctk_mlp_batch_* / ctk_mlp_problem_*): the ctk_batch above with pred == CTK_PRED_MLP
+// — the same struct, step records, completion poll, constants flush, reset and read paths — launched as ctk_mppi_batch_mlp<LOG> /
+// ctk_mppi_batch_mlp_pp<LOG>, plus what a learned plant adds: one per-lane weight table per problem (d_w [B][wtab], permute_mlp_weights as
+// for a handle's d_wperm), written by ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights through ONE transfer per call, and
+// `have_w`, without which a problem is not stepped.
+// =============================================================================================
+struct ctk_mlp_batch { ctk_batch b; };
+
+namespace {
+
+ctk_batch* core(ctk_mlp_batch* m) { return m ? &m->b : nullptr; }
+const ctk_batch* core(const ctk_mlp_batch* m) { return m ? &m->b : nullptr; }
+
+size_t mlp_batch_weight_count(const ctk_batch* b) { return shaped_weight_count(CTK_PRED_MLP, b->S, b->C, b->hid1, b->hid2); }
+
+// tables of the n listed problems (ids == NULL: problems 0 .. n-1) from w [n][cnt] (each_own) or from the one network w [cnt]: permuted
+// into the pinned staging at the problems' places, then the span from the first to the last listed problem in ONE transfer.  The staging
+// mirrors d_w (both start as zeros and change only here), so what lies between two listed problems is rewritten with what it holds.
+int mlp_batch_put_weights(ctk_batch* b, int n, const int32_t* ids, const float* w, size_t cnt, bool each_own) {
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    std::vector<float> full(weight_count(CTK_PRED_MLP, b->S, b->C, 32));
+    std::vector<float> perm;
+    for (int j = 0; j < n; ++j) {
+        if (j == 0 || each_own) {
+            const float* src = w + (each_own ? (size_t)j * cnt : 0);
+            if (b->hid1 == 32 && b->hid2 == 32) perm = permute_mlp_weights(src, b->S, b->C);
+            else {
+                std::fill(full.begin(), full.end(), 0.0f);
+                embed_mlp_rows(src, b->S, b->S + b->C, b->hid1, b->hid2, 32, full.data());
+                perm = permute_mlp_weights(full.data(), b->S, b->C);
+            }
+        }
+        std::memcpy(b->h_w + (size_t)(ids ? ids[j] : j) * b->wtab, perm.data(), b->wtab * sizeof(float));
+    }
+    const int lo = ids ? ids[0] : 0, hi = ids ? ids[n - 1] : n - 1;         // (ids are ascending: batch_ids)
+    BHIP_TRY(b, hipMemcpyAsync(b->d_w + (size_t)lo * b->wtab, b->h_w + (size_t)lo * b->wtab, (size_t)(hi - lo + 1) * b->wtab * sizeof(float),
+                               hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    for (int j = 0; j < n; ++j) b->have_w[(size_t)(ids ? ids[j] : j)] = 1;
+    return CTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* ctk_mlp_batch_last_error(const ctk_mlp_batch* m) { return ctk_batch_last_error(core(m)); }
+int ctk_mlp_batch_size(const ctk_mlp_batch* m) { return ctk_batch_size(core(m)); }
+size_t ctk_mlp_batch_samples_needed(const ctk_mlp_batch* m) { return ctk_batch_samples_needed(core(m)); }
+const char* ctk_mlp_batch_dominant_kernel(const ctk_mlp_batch* m) { return ctk_batch_dominant_kernel(core(m)); }
+
+void ctk_mlp_batch_destroy(ctk_mlp_batch* m) {
+    if (!m) return;
+    batch_release(&m->b);
+    delete m;
+}
+
+int ctk_mlp_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_mlp_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_create: NULL argument");
+    ctk_mlp_batch* m = new ctk_mlp_batch();
+    if (int rc = batch_create_in(&m->b, CTK_PRED_MLP, cfg, n_problems, seeds)) { delete m; return rc; }
+    *out = m;
+    return CTK_OK;
+}
+
+size_t ctk_mlp_batch_weight_count(const ctk_mlp_batch* m) { return m ? mlp_batch_weight_count(&m->b) : 0; }
+
+int ctk_mlp_batch_set_weights(ctk_mlp_batch* m, const float* w, size_t n) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    if (!w) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_set_weights: NULL weights");
+    if (n != mlp_batch_weight_count(b))
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_set_weights: expected " + std::to_string(mlp_batch_weight_count(b)) + " floats for the " +
+                     std::to_string(b->S + b->C) + "IN-" + std::to_string(b->hid1) + "H1-" + std::to_string(b->hid2) + "H2-" + std::to_string(b->S) +
+                     "OUT network (ctk_mlp_batch_weight_count), got " + std::to_string(n));
+    return mlp_batch_put_weights(b, b->B, nullptr, w, n, false);
+}
+
+int ctk_mlp_problem_set_weights(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* w, size_t n) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    int cnt = 0;
+    if (int rc = batch_ids(b, "ctk_mlp_problem_set_weights", n_ids, ids, &cnt)) return rc;
+    if (!w) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_problem_set_weights: NULL weights (one network per listed problem)");
+    if (n != mlp_batch_weight_count(b))
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_problem_set_weights: expected " + std::to_string(mlp_batch_weight_count(b)) + " floats per problem for the " +
+                     std::to_string(b->S + b->C) + "IN-" + std::to_string(b->hid1) + "H1-" + std::to_string(b->hid2) + "H2-" + std::to_string(b->S) +
+                     "OUT network (ctk_mlp_batch_weight_count), got " + std::to_string(n));
+    return mlp_batch_put_weights(b, cnt, ids, w, n, true);
+}
+
+int ctk_mlp_problem_have_weights(const ctk_mlp_batch* m, int problem) {
+    return (m && problem >= 0 && problem < m->b.B && m->b.have_w[(size_t)problem]) ? 1 : 0;
+}
+
+int ctk_mlp_batch_step(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
+                       float* u_out) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    if (!s) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_step: NULL state");
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_mlp_batch_step", n_ids, ids, &n)) return rc;
+    // a problem without a network is not stepped, and then none of the listed ones is: nothing is launched, no plan, output or Philox
+    // position moves (a handle's ctk_step fails the same way: check_predictor)
+    std::string missing;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        if (!b->have_w[(size_t)p]) missing += (missing.empty() ? "" : ", ") + std::to_string(p);
+    }
+    if (!missing.empty())
+        return bfail(b, CTK_ERR_STATE, "ctk_mlp_batch_step: no network weights for problem(s) " + missing +
+                     " (ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights before stepping); nothing was launched");
+    return ctk_batch_step(b, n_ids, ids, s, u_prev, samples, samples_loc, u_out);
+}
+
+int ctk_mlp_batch_reset(ctk_mlp_batch* m, int n_ids, const int32_t* ids) { return ctk_batch_reset(core(m), n_ids, ids); }
+int ctk_mlp_batch_read(ctk_mlp_batch* m, int problem, int buffer, float* dst, size_t cap) { return ctk_batch_read(core(m), problem, buffer, dst, cap); }
+int ctk_mlp_batch_get_state(ctk_mlp_batch* m, int problem, float* dst, size_t cap) { return ctk_batch_get_state(core(m), problem, dst, cap); }
+int ctk_mlp_batch_set_state(ctk_mlp_batch* m, int problem, const float* src, size_t n) { return ctk_batch_set_state(core(m), problem, src, n); }
+int ctk_mlp_batch_set_param(ctk_mlp_batch* m, int id, float value) { return ctk_batch_set_param(core(m), id, value); }
+int ctk_mlp_batch_get_param(const ctk_mlp_batch* m, int id, float* value) { return ctk_batch_get_param(core(m), id, value); }
+int ctk_mlp_problem_set_param(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int id, const float* values) {
+    return ctk_problem_set_param(core(m), n_ids, ids, id, values);
+}
+int ctk_mlp_problem_get_param(const ctk_mlp_batch* m, int problem, int id, float* value) { return ctk_problem_get_param(core(m), problem, id, value); }
+int ctk_mlp_problem_params_differ(const ctk_mlp_batch* m) { return ctk_problem_params_differ(core(m)); }
+int ctk_mlp_batch_rng_get_position(const ctk_mlp_batch* m, int problem, uint32_t* call) { return ctk_batch_rng_get_position(core(m), problem, call); }
+int ctk_mlp_batch_rng_set_position(ctk_mlp_batch* m, int problem, uint32_t call) { return ctk_batch_rng_set_position(core(m), problem, call); }
 
 }  // extern "C"
 

@@ -196,6 +196,17 @@ void ctk_mppi_batch_derive_k(int env, const float* params, float dt, int isteps,
 hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                  const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
                                  const void* k_dev = nullptr);
+// the MLP forms of the batch kernel (ctk_mppi.hip: ctk_mppi_batch_mlp<LOG> / ctk_mppi_batch_mlp_pp<LOG>; include/ctk_hip.h: ctk_mlp_batch_*):
+// CartPole's MLP predictor in the pair form (32 trajectories per workgroup), the same descriptors and step records, plus per-problem
+// weight tables w_dev [B][ctk_mppi_batch_mlp_table_floats()] in the per-lane layout of a handle's launch (ctk_api.hip: permute_mlp_weights).
+// fit: 0, or why not — 1 a handle of this N does not run the pair form (N > CTK_MPPI_PAIR_MAX_N, or the diagnostic switch
+// CTK_MPPI_NO_PAIR), 2 / 3 / 4 as ctk_mppi_batch_fit
+int ctk_mppi_batch_mlp_fit(int N, int H, int P, size_t* lds_out, int* blocks_out);
+const char* ctk_mppi_batch_mlp_name(bool log, bool per_problem = false);
+size_t ctk_mppi_batch_mlp_table_floats();
+hipError_t ctk_launch_mppi_batch_mlp(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
+                                     const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
+                                     const float* w_dev, const void* k_dev = nullptr);
 hipError_t ctk_launch_mppi_merge_partial(hipStream_t st, const float* parts, int n_parts, int per_block, int P,
                                          float neg_inv_lbd, float* out_rec);
 // direct peer-to-peer record exchange + merge + update (ctk_mppi.hip: ctk_mppi_p2p_exchange)

@@ -458,6 +458,42 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_pp(const CtkBatchDe
 #include "ctk_mppi_body.inc"
 }
 
+// The MLP forms of the batch kernel (include/ctk_hip.h: ctk_mlp_batch_*): the same prologue around the body of
+// ctk_mppi_rollout<0, CTK_PRED_MLP_PAIR, LOG, false> — 32 trajectories per workgroup, two waves per 16-trajectory tile, grid
+// (ceil(N / 32), problems of this launch).  The network is the plant here, so it is per problem: wbase is the base of the per-problem
+// weight tables ([B][wstride] floats, each table in the per-lane layout of a handle's d_wperm), wstride rides behind the preloaded
+// dwords.  q.id is uniform, so the table's address is scalar arithmetic; the weights themselves are fetched per lane by the body's
+// mlp_load_fwd_thin(wperm), as in a handle's launch.  The descriptor is read where the body reads fz / a (the tail's d.ll and u slots
+// are scalar loads the compiler places; the instantiations carry no scratch: DESIGN 2.1d).
+template <bool LOG>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_mlp(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                 const InterpEntry* __restrict__ interp, const float* __restrict__ wbase,
+                                                                 const void* spare, int N_, int H_, int P_, uint32_t pmagic_, uint32_t wstride,
+                                                                 RolloutArgs a_tpl, EnvK k, MppiK m, FuseArgs fz_tpl) {
+    constexpr int ENV = CTK_ENV_CARTPOLE, PRED = CTK_PRED_MLP_PAIR, FORM = 0;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+#include "ctk_mppi_batch_pro.inc"
+    (void)spare;
+    const float* wperm = wbase + (size_t)q.id * wstride;
+#include "ctk_mppi_body.inc"
+}
+
+// ... with per-problem cost constants (ctk_mlp_problem_set_param): k from kdev [B], exactly as ctk_mppi_batch_pp takes it
+template <bool LOG>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_mlp_pp(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                    const InterpEntry* __restrict__ interp, const float* __restrict__ wbase,
+                                                                    const unsigned char* __restrict__ kdev, int N_, int H_, int P_, uint32_t pmagic_,
+                                                                    uint32_t wstride, RolloutArgs a_tpl, MppiK m, FuseArgs fz_tpl) {
+    constexpr int ENV = CTK_ENV_CARTPOLE, PRED = CTK_PRED_MLP_PAIR, FORM = 0;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+#include "ctk_mppi_batch_pro.inc"
+    const EnvK k = *reinterpret_cast<const EnvK*>(kdev + (size_t)q.id * CtkBatchKStride<CTK_ENV_CARTPOLE>::value);
+    const float* wperm = wbase + (size_t)q.id * wstride;
+#include "ctk_mppi_body.inc"
+}
+
 // ---------------------------------------------------------------------------------------------
 // Throughput variant (ODE, N >= CTK_MPPI_THROUGHPUT_MIN_N): one wave per block, 64 trajectories, the
 // inputs formed inline in the recurrence instead of through an LDS input buffer.  LDS per block is the
@@ -1000,6 +1036,51 @@ hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, f
             });
         }
     });
+    return hipGetLastError();
+}
+
+// ---- the MLP batch form (ctk_mppi_batch_mlp): the pair form of the 4-wave kernel with the narrow {value, seq} tail, nothing else.  The
+// blocks, the LDS and the form come from the functions a handle's launch takes them from, so the two can never disagree.
+int ctk_mppi_batch_mlp_fit(int N, int H, int P, size_t* lds_out, int* blocks_out) {
+    const int blocks = ctk_mppi_num_blocks(N, CTK_PRED_MLP);
+    if (blocks_out) *blocks_out = blocks;
+    if (kernel_pred(CTK_PRED_MLP, N) != CTK_PRED_MLP_PAIR) return 1;
+    if (!ctk_ll_records_ok(blocks, P) || ctk_ll_tail_wide(blocks, P)) return 2;
+    int stage_ok;
+    const size_t lds = rollout_launch_lds(P, H, CTK_PRED_MLP, N, blocks, &stage_ok);
+    if (lds_out) *lds_out = lds;
+    if (!stage_ok) return 3;
+    if (lds > 160 * 1024) return 4;
+    return 0;
+}
+const char* ctk_mppi_batch_mlp_name(bool log, bool per_problem) {
+    return per_problem ? (log ? "ctk_mppi_batch_mlp_pp<true>" : "ctk_mppi_batch_mlp_pp<false>") : (log ? "ctk_mppi_batch_mlp<true>" : "ctk_mppi_batch_mlp<false>");
+}
+size_t ctk_mppi_batch_mlp_table_floats() { return (size_t)64 * (MLP_FWD_PER_LANE + MLP_BWD_PER_LANE); }
+
+hipError_t ctk_launch_mppi_batch_mlp(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
+                                     const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
+                                     const float* w_dev, const void* k_dev) {
+    size_t lds;
+    int blocks;
+    if (n_problems < 1 || w_dev == nullptr || ctk_mppi_batch_mlp_fit(a.N, a.H, a.P, &lds, &blocks) != 0) return hipErrorInvalidValue;
+    const dim3 grid(blocks, n_problems), block(MPPI_BLOCK);
+    FuseArgs fz{};                                     // as ctk_launch_mppi_batch: merge + update by block 0 of every problem
+    fz.mode = 1; fz.stage_ok = 1;
+    fz.up = mppi_update_args(a, CTK_C, nullptr, nullptr, nullptr, nullptr, 0u);
+    const uint32_t pmagic = ctk_magic_of(a.P), wstride = (uint32_t)ctk_mppi_batch_mlp_table_floats();
+    if (k_dev) {
+        ctk_with_bool(log, [&](auto log_c) {
+            hipLaunchKernelGGL((ctk_mppi_batch_mlp_pp<decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp, w_dev,
+                               static_cast<const unsigned char*>(k_dev), a.N, a.H, a.P, pmagic, wstride, a, m, fz);
+        });
+    } else {
+        const EnvK k = Env<CTK_ENV_CARTPOLE>::derive(params, dt, isteps);
+        ctk_with_bool(log, [&](auto log_c) {
+            hipLaunchKernelGGL((ctk_mppi_batch_mlp<decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp, w_dev,
+                               static_cast<const void*>(nullptr), a.N, a.H, a.P, pmagic, wstride, a, k, m, fz);
+        });
+    }
     return hipGetLastError();
 }
 

@@ -676,6 +676,59 @@ int ctk_rpgd_problem_set_param(ctk_rpgd_batch* b, int n_ids, const int32_t* ids,
 int ctk_rpgd_problem_get_param(const ctk_rpgd_batch* b, int problem, int id, float* value);     /* ctk_get_param of one problem */
 int ctk_rpgd_problem_params_differ(const ctk_rpgd_batch* b);                                    /* 1 once a ctk_rpgd_problem_set_param has succeeded */
 
+/* -------------------------------------------------------------------------------------------
+ * batched MPPI with the MLP predictor: B independent MPPI controllers of ONE configuration whose plant model is a learned network
+ * (BASELINE configs 4 and 5; the reference's `Dense-5IN-32H1-32H2-4OUT-0`), stepped by one kernel launch per step.  The counterpart of
+ * ctk_batch_* above for cfg.predictor == CTK_PRED_MLP, a family of its own, added without an ABI bump as the CEM and RPGD batches were.
+ * Everything said of ctk_batch_* holds (what is shared and what is per problem, ids, the launch cap and its switch, the synchronous
+ * step and its CTK_ERR_STATE, parameters and the per-problem form of the kernel), with ctk_mlp_batch_* / ctk_mlp_problem_* for
+ * ctk_batch_* / ctk_problem_*.  What differs:
+ *  - CONTRACT: problem p behaves bit for bit like ctk_create(cfg with predictor = CTK_PRED_MLP, seed = seeds[p]) that received the same
+ *    calls — ctk_set_predictor_weights[_shaped], ctk_set_param, ctk_step, ctk_reset, ctk_set_state, ctk_rng_set_position — (u, U_NOM, J,
+ *    Q, TRAJ, the Philox position, the ctk_get_state vector), for every sample source, u_prev given or NULL, and any interleaving of
+ *    whole-batch steps, subset steps, per-problem resets, and weight and parameter changes;
+ *  - the network is the plant, so every problem has its own: cfg.predictor_hidden1/2 (0 = 32, at most 32) are the widths of ALL the
+ *    batch's networks, ctk_mlp_batch_weight_count the floats of one (ctk_predictor_weight_count_shaped for those widths; the layout of
+ *    ctk_set_predictor_weights: W1, b1, W2, b2, W3, b3, row-major).  ctk_mlp_batch_set_weights gives every problem the same network,
+ *    ctk_mlp_problem_set_weights the listed problems one each (w [n_ids][n], in the order of ids; ids NULL: all problems).  Widths
+ *    below 32 are embedded exactly, by the row embedding of ctk_set_predictor_weights_shaped.  Weights are legal only between steps and
+ *    travel in ONE transfer per call; a wrong n, bad ids or NULL w is CTK_ERR_INVALID_ARGUMENT and nothing is written.  They are not
+ *    part of the ctk_mlp_batch_get_state vector; ctk_mlp_batch_reset and ctk_mlp_batch_set_state leave them alone, as a handle's;
+ *  - a step that lists a problem without weights is CTK_ERR_STATE naming the problems; nothing is launched, and every listed problem's
+ *    state vector and Philox position are what they were (a handle's ctk_step without weights fails the same way);
+ *  - refused at creation from the configuration alone (CTK_ERR_UNSUPPORTED, the sizes in ctk_mlp_batch_last_error(NULL)): an optimizer
+ *    other than MPPI; a predictor other than MLP (ODE: ctk_batch_create; the GRU's carried hidden state has no batch form); an
+ *    environment other than CartPole, or generic_kernels != 0 (those handles run the one-wave template network kernels); hidden widths
+ *    above 32 (the 64-unit kernels are template kernels); per-problem sizes whose handle would not run the pair form of the MLP kernel
+ *    (more than 8192 rollouts) or outside the narrow in-launch hand-off (at most 128 block records — 32 rollouts each — and 2048
+ *    record words per problem); n_problems < 1.
+ * Each entry corresponds to the single-handle call named beside it.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct ctk_mlp_batch ctk_mlp_batch;
+int ctk_mlp_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds /* NULL: cfg->seed + p */, ctk_mlp_batch** out); /* ctk_create */
+void ctk_mlp_batch_destroy(ctk_mlp_batch* b);                                                   /* ctk_destroy */
+const char* ctk_mlp_batch_last_error(const ctk_mlp_batch* b);                                   /* ctk_last_error; b may be NULL */
+int ctk_mlp_batch_size(const ctk_mlp_batch* b);                                                 /* B */
+size_t ctk_mlp_batch_samples_needed(const ctk_mlp_batch* b);                                    /* ctk_samples_needed, per problem: N*P*C */
+int ctk_mlp_batch_step(ctk_mlp_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev,
+                       const float* samples, int samples_loc, float* u_out);                    /* ctk_step of every listed problem */
+int ctk_mlp_batch_reset(ctk_mlp_batch* b, int n_ids, const int32_t* ids);                       /* ctk_reset of every listed problem */
+int ctk_mlp_batch_read(ctk_mlp_batch* b, int problem, int buffer, float* dst, size_t cap);      /* ctk_read: CTK_BUF_Q, J, TRAJ, U_NOM */
+int ctk_mlp_batch_get_state(ctk_mlp_batch* b, int problem, float* dst, size_t cap);             /* ctk_get_state: u_nom [H,C], u [C] */
+int ctk_mlp_batch_set_state(ctk_mlp_batch* b, int problem, const float* src, size_t n);         /* ctk_set_state */
+int ctk_mlp_batch_set_param(ctk_mlp_batch* b, int id, float value);                             /* ctk_set_param, all problems */
+int ctk_mlp_batch_get_param(const ctk_mlp_batch* b, int id, float* value);                      /* ctk_get_param */
+int ctk_mlp_batch_rng_get_position(const ctk_mlp_batch* b, int problem, uint32_t* call);        /* ctk_rng_get_position */
+int ctk_mlp_batch_rng_set_position(ctk_mlp_batch* b, int problem, uint32_t call);               /* ctk_rng_set_position */
+const char* ctk_mlp_batch_dominant_kernel(const ctk_mlp_batch* b);                              /* ctk_dominant_kernel */
+int ctk_mlp_problem_set_param(ctk_mlp_batch* b, int n_ids, const int32_t* ids, int id, const float* values);   /* ctk_set_param of every listed problem */
+int ctk_mlp_problem_get_param(const ctk_mlp_batch* b, int problem, int id, float* value);       /* ctk_get_param of one problem */
+int ctk_mlp_problem_params_differ(const ctk_mlp_batch* b);                                      /* 1 once a ctk_mlp_problem_set_param has succeeded */
+size_t ctk_mlp_batch_weight_count(const ctk_mlp_batch* b);                                      /* ctk_predictor_weight_count_shaped for cfg.predictor_hidden1/2 */
+int ctk_mlp_batch_set_weights(ctk_mlp_batch* b, const float* w, size_t n);                      /* ctk_set_predictor_weights[_shaped] of every problem, one network */
+int ctk_mlp_problem_set_weights(ctk_mlp_batch* b, int n_ids, const int32_t* ids, const float* w, size_t n);   /* ... of every listed problem, w [n_ids][n] */
+int ctk_mlp_problem_have_weights(const ctk_mlp_batch* b, int problem);                          /* 1 once the problem has received weights */
+
 #ifdef __cplusplus
 }
 #endif

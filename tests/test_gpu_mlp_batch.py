@@ -1,0 +1,405 @@
+"""-m gpu: CtkMppiMlpBatch (ctk_mlp_batch_* / ctk_mlp_problem_*, kernels ctk_mppi_batch_mlp<LOG> / ctk_mppi_batch_mlp_pp<LOG>) — B independent
+MPPI problems whose plant model is a learned MLP, stepped by one launch, every problem with a network of its own.
+
+The contract under test: problem p of a batch behaves BIT FOR BIT like a CtkEngine("mppi", "MLP", seed=seeds[p]) created from the same
+configuration that received the same calls, set_predictor_weights and set_param among them.  Every comparison against single handles is
+assert_array_equal; the only tolerances in this file are the existing ones of the reference-recorded fixture
+(tests/test_gpu_mlp.py::test_mppi_mlp_matches_reference_golden: J rtol J_RTOL / atol 1e-3, u / u_nom GOLDEN_U_TOL, u_run 1e-6 / 1e-6,
+traj rtol 1e-4 / atol 2e-5), applied to a problem that replays that fixture INSIDE a batch."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from oracle import ctk_oracle as O
+from control_toolkit_amd import CtkEngine, CtkMppiMlpBatch, CtkError
+from helpers import load, env_from
+from gpu_helpers import ENV_NAMES
+from test_gpu_mppi import GOLDEN_U_TOL, J_RTOL
+from margins import close
+
+pytestmark = pytest.mark.gpu
+
+# (N, H, period): one workgroup with a half-filled tile | three workgroups, the last one partial | interpolated | cfg2: 32 records, 1 664
+# words | 128 records x 16 = 2 048 words, the fit's boundary
+SIZES = [(16, 5, 2), (70, 12, 5), (1000, 35, 10), (1024, 50, 1), (4096, 14, 1)]
+SOURCES = [("philox", True), ("host", False), ("devptr", True), ("philox", False), ("host", True), ("devptr", False)]   # (draws, u_prev given)
+STEPS = 5
+PLANT = O.Predictor("ODE", dt=0.02, env=O.EnvParams())
+_W = {}
+
+
+def weights(seed, hidden=(32, 32)):
+    """O.mlp_default_weights(seed), computed once"""
+    key = (seed, hidden)
+    if key not in _W:
+        _W[key] = O.mlp_default_weights(seed, hidden=hidden)
+        _W[key].setflags(write=False)
+    return _W[key]
+
+
+def make(size, B, materialize, weight_seeds="own", hidden=None, **kw):
+    """(batch, B single handles with seeds[p]); weight_seeds: "own" = seed 100 + p per problem, None = no weights yet"""
+    N, H, p = size
+    seeds = [7 + q for q in range(B)]
+    common = dict(num_rollouts=N, mpc_horizon=H, dt=0.02, period_interpolation_inducing_points=p, materialize_trajectories=materialize, **kw)
+    if hidden is not None:
+        common["predictor_hidden"] = hidden
+    batch = CtkMppiMlpBatch(B, seeds=seeds, **common)
+    handles = [CtkEngine("mppi", "MLP", seed=seeds[q], **common) for q in range(B)]
+    if weight_seeds == "own":
+        hid = (32, 32) if hidden is None else hidden
+        batch.set_problem_weights(np.stack([weights(100 + q, hid) for q in range(B)]))
+        for q in range(B):
+            handles[q].set_predictor_weights(weights(100 + q, hid))
+    return batch, handles
+
+
+def first_states(rng, B):
+    s = rng.uniform(-0.4, 0.4, (B, 4)).astype(np.float32)
+    s[:, 2] += 2.6          # the pendulum hangs away from the target
+    return s
+
+
+def draws_for(source, rng, n, batch):
+    """(what the batch is given, what handle row j is given, keep-alive)"""
+    if source == "philox":
+        return None, [None] * n, None
+    arr = rng.standard_normal((n, batch.N, batch.samples_needed() // batch.N, 1)).astype(np.float32)
+    if source == "host":
+        return arr, [arr[j] for j in range(n)], None
+    import torch
+    t = torch.from_numpy(arr).to("cuda")
+    torch.cuda.synchronize()
+    return t.data_ptr(), [t.data_ptr() + 4 * j * arr[0].size for j in range(n)], t
+
+
+def compare(batch, handles, problems, materialize, tag):
+    for q in problems:
+        h = handles[q]
+        np.testing.assert_array_equal(batch.read("U_NOM", q), h.read("U_NOM"), err_msg=f"{tag}: U_NOM of problem {q}")
+        np.testing.assert_array_equal(batch.read("J", q), h.read("J"), err_msg=f"{tag}: J of problem {q}")
+        np.testing.assert_array_equal(batch.get_state(q), h.get_state(), err_msg=f"{tag}: state vector of problem {q}")
+        assert batch.rng_position(q) == h.rng_position(), f"{tag}: Philox position of problem {q}"
+        if materialize:
+            np.testing.assert_array_equal(batch.read("Q", q), h.read("Q"), err_msg=f"{tag}: Q of problem {q}")
+            np.testing.assert_array_equal(batch.read("TRAJ", q), h.read("TRAJ"), err_msg=f"{tag}: TRAJ of problem {q}")
+
+
+def step_both(batch, handles, s, ids=None, samples=None, hs=None, up=None):
+    """one step of the listed problems on both sides; asserts u bit for bit and returns it"""
+    idl = list(range(len(handles))) if ids is None else list(ids)
+    u = batch.step(s[idl] if ids is not None else s, samples, u_prev=up, ids=ids)
+    uh = np.stack([handles[q].step(s[q], None if hs is None else hs[j], u_prev=None if up is None else up[j]) for j, q in enumerate(idl)])
+    np.testing.assert_array_equal(u, uh)
+    return u
+
+
+def close_all(batch, handles):
+    batch.close()
+    for h in handles:
+        h.close()
+
+
+def snapshot(batch, q):
+    return dict(U_NOM=batch.read("U_NOM", q), J=batch.read("J", q), Q=batch.read("Q", q), TRAJ=batch.read("TRAJ", q),
+                state=batch.get_state(q), rng=batch.rng_position(q))
+
+
+def assert_unchanged(batch, q, snap, tag):
+    now = snapshot(batch, q)
+    for k, v in snap.items():
+        np.testing.assert_array_equal(now[k], v, err_msg=f"{tag}: {k} of untouched problem {q} changed")
+
+
+# ---- 1. batch == single handles, bit for bit, every problem with its own network ----------------------------------------------------------
+CASES = [(B, size) for size in SIZES for B in (1, 3, 16)] + [(40, (70, 12, 5))]
+
+
+@pytest.mark.parametrize("materialize", [False, True])
+@pytest.mark.parametrize("B,size", CASES)
+def test_batch_equals_single_handles(B, size, materialize):
+    """every sample source with u_prev given and None, one after another on the SAME objects: STEPS closed-loop steps each on the oracle's
+    plant with every problem's own output fed back"""
+    batch, handles = make(size, B, materialize)
+    assert batch.weight_count() == O.mlp_num_weights() and all(batch.have_weights(q) for q in range(B))
+    assert batch.dominant_kernel() == f"ctk_mppi_batch_mlp<{'true' if materialize else 'false'}>"
+    rng = np.random.default_rng(B * 131 + size[0])
+    s = first_states(rng, B)
+    for source, given in SOURCES:
+        for t in range(STEPS):
+            up = rng.uniform(-1.0, 1.0, (B, 1)).astype(np.float32) if given else None
+            bs, hs, keep = draws_for(source, rng, B, batch)
+            u = batch.step(s, bs, u_prev=up)
+            uh = np.stack([handles[q].step(s[q], hs[q], u_prev=None if up is None else up[q]) for q in range(B)])
+            np.testing.assert_array_equal(u, uh, err_msg=f"{size} B={B} {source} u_prev={'given' if given else 'None'} step {t}: u")
+            s = PLANT.step(s, u).astype(np.float32)
+            del keep
+        compare(batch, handles, range(B), materialize, f"{size} B={B} after {source}/{'given' if given else 'None'}")
+    assert handles[0].dominant_kernel() == f"ctk_mppi_rollout<0, 3, {'true' if materialize else 'false'}, false>"   # the form compared with
+    close_all(batch, handles)
+
+
+# ---- 2. one network for all ----------------------------------------------------------------------------------------------------------------
+def test_shared_weights():
+    B = 4
+    batch, handles = make((70, 12, 5), B, True, weight_seeds=None)
+    assert not any(batch.have_weights(q) for q in range(B))
+    batch.set_weights(weights(5))
+    assert all(batch.have_weights(q) for q in range(B))
+    for h in handles:
+        h.set_predictor_weights(weights(5))
+    s = first_states(np.random.default_rng(2), B)
+    for t in range(3):
+        s = PLANT.step(s, step_both(batch, handles, s)).astype(np.float32)
+    compare(batch, handles, range(B), True, "shared network")
+    close_all(batch, handles)
+
+
+# ---- 3. networks adapted between steps -----------------------------------------------------------------------------------------------------
+def test_weights_changed_between_steps():
+    B = 6
+    batch, handles = make((1000, 35, 10), B, True)
+    s = first_states(np.random.default_rng(3), B)
+    for t in range(2):
+        s = PLANT.step(s, step_both(batch, handles, s)).astype(np.float32)
+    ids = [1, 4]
+    snaps = {q: snapshot(batch, q) for q in range(B)}
+    batch.set_problem_weights(np.stack([weights(200 + q) for q in ids]), ids=ids)
+    for q in ids:
+        handles[q].set_predictor_weights(weights(200 + q))
+    for q in range(B):                                   # the call itself moves nobody's buffers, listed or not
+        assert_unchanged(batch, q, snaps[q], "set_problem_weights([1, 4])")
+    J_before = batch.read_all("J")
+    for t in range(3):
+        s = PLANT.step(s, step_both(batch, handles, s)).astype(np.float32)
+    compare(batch, handles, range(B), True, "after new networks for problems 1 and 4")
+    assert not np.array_equal(batch.read_all("J")[ids], J_before[ids])
+    batch.reset([4]); handles[4].reset()                 # reset and set_state leave the network alone, as a handle's
+    batch.set_state(1, snaps[1]["state"]); handles[1].set_state(snaps[1]["state"])
+    for t in range(2):
+        s = PLANT.step(s, step_both(batch, handles, s)).astype(np.float32)
+    compare(batch, handles, range(B), True, "after reset / set_state")
+    close_all(batch, handles)
+
+
+# ---- 4. narrow networks --------------------------------------------------------------------------------------------------------------------
+def test_narrow_networks():
+    B, hid = 3, (8, 12)
+    batch, handles = make((70, 12, 5), B, True, hidden=hid)
+    assert batch.weight_count() == O.mlp_num_weights(hidden=hid) == handles[0].predictor_weight_count(hid)
+    s = first_states(np.random.default_rng(4), B)
+    for t in range(3):
+        s = PLANT.step(s, step_both(batch, handles, s)).astype(np.float32)
+    compare(batch, handles, range(B), True, "8-12 networks")
+    with pytest.raises(ValueError, match="weights"):
+        batch.set_weights(weights(1))                   # a 32-32 network into a batch of 8-12 ones
+    close_all(batch, handles)
+
+
+# ---- 5. split into launches ----------------------------------------------------------------------------------------------------------------
+def test_split_into_launches_gives_the_same_bits(monkeypatch):
+    """B = 40 with CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH = 16 runs as three launches (16 + 16 + 8) and gives the bits of one launch"""
+    B, size = 40, (70, 12, 5)
+    one, handles = make(size, B, True)
+    monkeypatch.setenv("CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH", "16")
+    split = CtkMppiMlpBatch(B, seeds=[7 + q for q in range(B)], num_rollouts=size[0], mpc_horizon=size[1], dt=0.02, materialize_trajectories=True,
+                            period_interpolation_inducing_points=size[2])
+    monkeypatch.delenv("CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH")
+    split.set_problem_weights(np.stack([weights(100 + q) for q in range(B)]))
+    s = first_states(np.random.default_rng(40), B)
+    for t in range(STEPS):
+        u1 = step_both(one, handles, s)
+        np.testing.assert_array_equal(split.step(s), u1)
+        s = PLANT.step(s, u1).astype(np.float32)
+    compare(one, handles, range(B), True, "one launch")
+    compare(split, handles, range(B), True, "three launches")
+    ids = list(range(1, 40, 2))                          # an id list longer than the cap is split as well
+    u2 = split.step(s[ids], ids=ids)
+    np.testing.assert_array_equal(u2, np.stack([handles[q].step(s[q]) for q in ids]))
+    compare(split, handles, ids, True, "subset over two launches")
+    split.close()
+    close_all(one, handles)
+
+
+# ---- 6. subset steps, resets, state round trip ---------------------------------------------------------------------------------------------
+def test_subset_steps_and_resets():
+    B, size = 8, (1000, 35, 10)
+    batch, handles = make(size, B, True)
+    rng = np.random.default_rng(8)
+    s = first_states(rng, B)
+    for t in range(2):
+        s = PLANT.step(s, step_both(batch, handles, s)).astype(np.float32)
+    ids = [1, 4, 5]
+    rest = [q for q in range(B) if q not in ids]
+    snaps = {q: snapshot(batch, q) for q in rest}
+    for t in range(3):
+        u = step_both(batch, handles, s, ids=ids)
+        s[ids] = PLANT.step(s[ids], u).astype(np.float32)
+    for q in rest:
+        assert_unchanged(batch, q, snaps[q], "subset step")
+    compare(batch, handles, range(B), True, "after subset steps")
+    snaps = {q: snapshot(batch, q) for q in range(B) if q != 4}
+    batch.reset([4])
+    handles[4].reset()
+    for q in snaps:
+        assert_unchanged(batch, q, snaps[q], "reset([4])")
+    compare(batch, handles, [4], True, "after reset([4])")
+    for t in range(2):
+        up = rng.uniform(-1.0, 1.0, (B, 1)).astype(np.float32)
+        s = PLANT.step(s, step_both(batch, handles, s, up=up)).astype(np.float32)
+    compare(batch, handles, range(B), True, "after the reset and two more steps")
+    # get_state / set_state / set_rng_position: a batch restored into a FRESH batch (which gets the networks anew: they are not state)
+    fresh = CtkMppiMlpBatch(B, seeds=[7 + q for q in range(B)], num_rollouts=size[0], mpc_horizon=size[1], dt=0.02,
+                            period_interpolation_inducing_points=size[2], materialize_trajectories=True)
+    fresh.set_problem_weights(np.stack([weights(100 + q) for q in range(B)]))
+    for q in range(B):
+        fresh.set_state(q, batch.get_state(q))
+        fresh.set_rng_position(q, batch.rng_position(q))
+        np.testing.assert_array_equal(fresh.get_state(q), batch.get_state(q))
+    for t in range(3):
+        u = batch.step(s)
+        np.testing.assert_array_equal(fresh.step(s), u)
+        s = PLANT.step(s, u).astype(np.float32)
+    for q in range(B):
+        for k, v in snapshot(batch, q).items():
+            np.testing.assert_array_equal(snapshot(fresh, q)[k], v, err_msg=f"restored batch: {k} of problem {q}")
+    fresh.close()
+    close_all(batch, handles)
+
+
+# ---- 7. parameters -------------------------------------------------------------------------------------------------------------------------
+def test_parameters_shared_and_per_problem():
+    B = 5
+    batch, handles = make((1000, 35, 10), B, True)
+    s = first_states(np.random.default_rng(7), B)
+    step_both(batch, handles, s)
+    batch.set_param("target_position", 0.3)
+    assert batch.get_param("target_position") == np.float32(0.3) and batch.params_differ() == 0
+    for h in handles:
+        h.set_param("target_position", 0.3)
+    J0 = batch.read_all("J")
+    for t in range(2):
+        step_both(batch, handles, s)
+    compare(batch, handles, range(B), True, "target_position = 0.3 everywhere")
+    J1 = batch.read_all("J")
+    assert not np.array_equal(J1, J0)                    # the parameter is in the cost
+    ids, vals = [0, 3], [-0.4, 0.7]
+    batch.set_problem_params("target_position", vals, ids=ids)
+    for q, v in zip(ids, vals):
+        handles[q].set_param("target_position", v)
+    assert batch.params_differ() == 1 and batch.dominant_kernel() == "ctk_mppi_batch_mlp_pp<true>"
+    np.testing.assert_array_equal(batch.get_problem_params("target_position"), np.array([-0.4, 0.3, 0.3, 0.7, 0.3], np.float32))
+    for t in range(2):
+        s = PLANT.step(s, step_both(batch, handles, s)).astype(np.float32)
+    compare(batch, handles, range(B), True, "target_position per problem")
+    assert not np.array_equal(batch.read_all("J")[ids], J1[ids])
+    close_all(batch, handles)
+
+
+# ---- 8. the reference-recorded fixture inside a batch --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("materialize", [True, False])
+def test_reference_fixture_inside_a_batch(materialize):
+    """B = 3; problem 1 replays mppi_mlp (the loop of test_mppi_mlp_matches_reference_golden, re-pinned with set_state) while problems 0
+    and 2 run other networks, states and draws in the same launches"""
+    d = load("mppi_mlp.npz")
+    B, me = 3, 1
+    N, H = int(d["num_rollouts"]), int(d["mpc_horizon"])
+    batch = CtkMppiMlpBatch(B, seeds=[11, 12, 13], num_rollouts=N, mpc_horizon=H, dt=float(d["dt"]),
+                            action_low=float(d["low"][0]), action_high=float(d["high"][0]),
+                            period_interpolation_inducing_points=int(d["period_interpolation_inducing_points"]),
+                            materialize_trajectories=materialize, cc_weight=float(d["cc_weight"]), R=float(d["R"]), LBD=float(d["LBD"]),
+                            NU=float(d["NU"]), SQRTRHOINV=float(d["SQRTRHOINV"]))
+    env = env_from(d)
+    for n in ENV_NAMES:
+        batch.set_param(n, float(getattr(env, n)))
+    batch.set_problem_weights(np.stack([weights(100), np.asarray(d["mlp_weights"], np.float32).ravel(), weights(102)]))
+    rng = np.random.default_rng(52)
+    P = batch.samples_needed() // N
+    for t in range(int(d["steps"])):
+        s = first_states(rng, B)
+        s[me] = d[f"s_{t}"]
+        noise = rng.standard_normal((B, N, P, 1)).astype(np.float32)
+        noise[me] = np.asarray(d[f"noise_{t}"], np.float32).reshape(N, P, 1)
+        up = rng.uniform(-1.0, 1.0, (B, 1)).astype(np.float32)
+        up[me, 0] = d[f"u_prev_{t}"]
+        u = batch.step(s, noise, u_prev=up)
+        tag = f"batch3[1]=mppi_mlp[materialize={materialize}] step {t}"
+        if materialize:
+            close(tag, "q", batch.read("Q", me), d[f"u_run_{t}"], rtol=1e-6, atol=1e-6)
+            close(tag, "traj", batch.read("TRAJ", me), d[f"traj_{t}"], rtol=1e-4, atol=2e-5)
+        close(tag, "j", batch.read("J", me), d[f"J_{t}"], rtol=J_RTOL, atol=1e-3)
+        close(tag, "u_nom", batch.read("U_NOM", me), d[f"u_nom_{t}"], **GOLDEN_U_TOL)
+        close(tag, "u", u[me], d[f"u_{t}"], **GOLDEN_U_TOL)
+        assert np.all(np.isfinite(u))
+        batch.set_state(me, np.concatenate([d[f"u_nom_{t}"].reshape(H), d[f"u_{t}"].reshape(1)]))
+    batch.close()
+
+
+# ---- 9. refusals ---------------------------------------------------------------------------------------------------------------------------
+def test_step_without_weights_moves_nothing():
+    B = 4
+    batch, handles = make((70, 12, 5), B, True, weight_seeds=None)
+    s = first_states(np.random.default_rng(9), B)
+    # what a weightless handle's failed step leaves: its state vector and Philox position as they were
+    h = handles[2]
+    before = (h.get_state(), h.rng_position())
+    with pytest.raises(CtkError, match="set_predictor_weights before stepping"):
+        h.step(s[2])
+    np.testing.assert_array_equal(h.get_state(), before[0])
+    assert h.rng_position() == before[1]
+    # the batch: problems 0 and 1 have networks, 2 and 3 do not
+    batch.set_problem_weights(np.stack([weights(100), weights(101)]), ids=[0, 1])
+    for q in (0, 1):
+        handles[q].set_predictor_weights(weights(100 + q))
+    assert [batch.have_weights(q) for q in range(B)] == [True, True, False, False]
+    step_both(batch, handles, s, ids=[0, 1])
+    snaps = {q: snapshot(batch, q) for q in range(B)}
+    with pytest.raises(CtkError, match=r"\[ctk 5\] ctk_mlp_batch_step: no network weights for problem\(s\) 2, 3 "):
+        batch.step(s)
+    with pytest.raises(CtkError, match=r"problem\(s\) 2 "):
+        batch.step(s[[1, 2]], ids=[1, 2])
+    for q in range(B):
+        assert_unchanged(batch, q, snaps[q], "refused step")
+    step_both(batch, handles, s, ids=[0, 1])            # the refusals left the batch usable, and in step with the handles
+    compare(batch, handles, [0, 1], True, "after the refused steps")
+    close_all(batch, handles)
+
+
+def test_weight_and_id_refusals():
+    from control_toolkit_amd import _capi
+    B = 4
+    batch, handles = make((16, 5, 2), B, True, weight_seeds=None)
+    n = batch.weight_count()
+    with pytest.raises(ValueError, match=rf"\({B}, {n}\)"):
+        batch.set_problem_weights(np.zeros((B, n - 1), np.float32))
+    with pytest.raises(ValueError, match=rf"\(2, {n}\)"):
+        batch.set_problem_weights(np.zeros((3, n), np.float32), ids=[0, 1])
+    with pytest.raises(ValueError, match="strictly ascending"):
+        batch.set_problem_weights(np.zeros((2, n), np.float32), ids=[2, 1])
+    with pytest.raises(ValueError, match=f"{n} weights"):
+        batch.set_weights(np.zeros(n + 1, np.float32))
+    # ... and the C ABI refuses them itself, writing nothing
+    lib = _capi.load_library()
+    w = np.ones((B, n), np.float32)
+    assert lib.ctk_mlp_batch_set_weights(batch._h, w.ctypes.data, n - 1) == 1
+    assert f"expected {n} floats".encode() in lib.ctk_mlp_batch_last_error(batch._h)
+    assert lib.ctk_mlp_batch_set_weights(batch._h, None, n) == 1
+    ids = (ctypes.c_int32 * 2)(2, 1)
+    assert lib.ctk_mlp_problem_set_weights(batch._h, 2, ids, w.ctypes.data, n) == 1
+    assert b"ctk_mlp_problem_set_weights: ids must be strictly ascending" in lib.ctk_mlp_batch_last_error(batch._h)
+    ids = (ctypes.c_int32 * 1)(B)
+    assert lib.ctk_mlp_problem_set_weights(batch._h, 1, ids, w.ctypes.data, n) == 1
+    ids = (ctypes.c_int32 * 2)(0, 1)
+    assert lib.ctk_mlp_problem_set_weights(batch._h, 2, ids, w.ctypes.data, n + 1) == 1
+    assert lib.ctk_mlp_problem_set_weights(batch._h, 2, ids, None, n) == 1
+    assert not any(batch.have_weights(q) for q in range(B))
+    s = np.zeros((B, 4), np.float32)
+    ids = (ctypes.c_int32 * 2)(2, 1)
+    assert lib.ctk_mlp_batch_step(batch._h, 2, ids, s.ctypes.data, None, None, 0, None) == 1
+    assert b"ctk_mlp_batch_step: ids must be strictly ascending" in lib.ctk_mlp_batch_last_error(batch._h)
+    close_all(batch, handles)
+    b2 = CtkMppiMlpBatch(1, num_rollouts=16, mpc_horizon=5, dt=0.02)         # the shared code's messages carry this family's names
+    with pytest.raises(CtkError, match="ctk_mlp_batch_read: trajectories not materialised"):
+        b2.read("TRAJ", 0)
+    b2.close()
