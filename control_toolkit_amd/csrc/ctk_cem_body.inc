@@ -305,9 +305,9 @@
             const int gbest = (int)red_min(0);
             if (t == 0 && gbest >= row0 && gbest < row0 + CF_TRAJ) {
                 cf.idx_out[0] = gbest;
-                if (expired) __hip_atomic_store(reinterpret_cast<uint32_t*>(cf.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if constexpr (C == 1) publish_u(cf.u_dev, cf.u_host, ubuf[(gbest - row0) * us], cf.seq);
-                else publish_u_vec(cf.u_dev, cf.u_host, ubuf + (gbest - row0) * us, C, cf.seq);
+                if (expired) host_word_store(cf.u_host, 2, 2u);    // (drained: the flag below must not overtake it)
+                if constexpr (C == 1) publish_u_launched(cf.u_dev, cf.u_host, ubuf[(gbest - row0) * us], cf.seq);
+                else publish_u_vec_launched(cf.u_dev, cf.u_host, ubuf + (gbest - row0) * us, C, cf.seq);
             }
             // :99-102 clip the std, shift both by one step, refill the tail — the handle's distribution for the next MPC step
             if (bx == 0) {

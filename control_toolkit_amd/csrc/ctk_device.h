@@ -269,6 +269,48 @@ CTK_DEV void publish_u_vec(float* u_dev, float* u_host, const float* u, int C, u
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(u_host), v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---- the publish of a kernel that is LAUNCHED once per step and whose end orders everything else -------------------------------
+// When a step returns, the host has read the 8-byte word {u, seq}, the error words behind it and (C > 1) the vector at floats 4.. —
+// nothing else (ctk_api.hip: finish_step and the batch steps' completion loops).  Every other reader of a handle's buffers is an API
+// entry ordered behind the launch on the handle's stream, and the kernel's END writes the caches back for those.  So the word the host
+// spins on needs no release: publish_u's system-scope release is a write-back of the whole L2 plus a drain of the wave's stores
+// (buffer_wbl2 sc0 sc1; s_waitcnt vmcnt(0)) on the path between u and the host.  Here every word the host reads is a RELAXED
+// system-scope store (write-through to the pinned slot); a lane that has stored one of the other words drains its own stores
+// (host_words_drain) before it stores {u, seq}, so the flag cannot overtake them; the common path has neither a wait nor a write-back.
+// Callers, and what the host reads behind each (all: {u, seq} + the error words; nothing else needs the release because the launch ends):
+//   ctk_mppi_body_5_post.inc  early u of FORM 0 (word 2 drained in the `late` branch); the merge tails' word 2 is drained by the
+//                             threads that raised it, ahead of the barrier in front of the merge
+//   mppi_merge_block          PUB of the launched forms: ctk_mppi_rollout's tails, ctk_mppi_merge<true>, mppi_ll_tail (network kernels),
+//                             the batch kernels (one slot per problem, read by the same loop as finish_step's); C > 1: the vector
+//   ctk_generic.hip           ctk_g_mppi_update, ctk_g_cem_finish, ctk_g_pick_best_first: the vector
+//   ctk_cem_body.inc          CEM finish of the one-launch step and its batch forms (word 2 drained where `expired`)
+//   ctk_gmm.hip               CEM-GMM finish: the vector
+//   ctk_sampled.hip           pick-best (word 2 drained by the lanes that raised it: the same wave as the winner)
+//   ctk_rpgd_warm.h           RPGD warm start: words 3 and 6..9 come from an EARLIER launch, or (one-workgroup step) from this workgroup
+//                             ahead of rpgd_fused_tail's fence and barrier; C > 1: the vector
+// NOT for a kernel that goes on after the publish and hands data to other workgroups or peers with it: the resident kernel and the
+// peer-to-peer exchange keep publish_u (mppi_merge_block<..., REL = true>).
+CTK_DEV void host_words_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+CTK_DEV void host_word_store(float* u_host, int word, uint32_t v) {
+    __hip_atomic_store(reinterpret_cast<uint32_t*>(u_host) + word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    host_words_drain();
+}
+CTK_DEV void publish_u_launched(float* u_dev, float* u_host, float u, uint32_t seq) {
+    *u_dev = u;
+    const unsigned long long v = ((unsigned long long)seq << 32) | (unsigned long long)__builtin_bit_cast(unsigned, u);
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(u_host), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// ... its vector form (single thread): the host reads floats 5.. only when C > 1, and only then are they drained
+CTK_DEV void publish_u_vec_launched(float* u_dev, float* u_host, const float* u, int C, uint32_t seq) {
+    for (int c = 0; c < C; ++c) {
+        u_dev[c] = u[c];
+        __hip_atomic_store(u_host + 4 + c, u[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (C > 1) host_words_drain();
+    const unsigned long long v = ((unsigned long long)seq << 32) | (unsigned long long)__builtin_bit_cast(unsigned, u[0]);
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(u_host), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Kernel-argument prefetch.  Arguments are read with scalar loads at their points of use; the scalar
 // cache is cold at every launch and each first touch of a 64-B line of the kernarg segment is a
 // full memory round trip (~1-2 k cycles), paid serially wherever the compiler sank the load

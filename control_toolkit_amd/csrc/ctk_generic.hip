@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void ctk_g_mppi_update(const float* __restrict
         if (h == 0) u_s[c] = o;
     }
     __syncthreads();
-    if (t == 0) publish_u_vec(u_dev, u_host, u_s, C, seq);
+    if (t == 0) publish_u_vec_launched(u_dev, u_host, u_s, C, seq);
 }
 
 // optimizer_cem_tf.py:99-102 with C channels: clip std, shift mean and std by one STEP (C floats), refill the tail with
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void ctk_g_cem_finish(const float* __restrict_
     if (t == 0) {
         float u[CTK_MAX_INPUTS];
         for (int c = 0; c < C; ++c) u[c] = u_from_mu ? m_s[c] : Q[(size_t)idx[0] * ldq + c];
-        publish_u_vec(u_dev, u_host, u, C, seq);
+        publish_u_vec_launched(u_dev, u_host, u, C, seq);
     }
 }
 
@@ -224,7 +224,7 @@ __global__ void ctk_g_pick_best_first(const float* __restrict__ Q, int ldq, cons
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         float u[CTK_MAX_INPUTS];
         for (int c = 0; c < C; ++c) u[c] = Q[(size_t)idx[0] * ldq + c];
-        publish_u_vec(u_dev, u_host, u, C, seq);
+        publish_u_vec_launched(u_dev, u_host, u, C, seq);
     }
 }
 

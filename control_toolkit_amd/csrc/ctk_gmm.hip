@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void ctk_gmm_finish(const float* __restrict__ 
     if (t == 0) {
         float u[CTK_MAX_INPUTS];
         for (int c = 0; c < C; ++c) u[c] = Q[(size_t)idx[0] * ldq + c];
-        publish_u_vec(u_dev, u_host, u, C, seq);
+        publish_u_vec_launched(u_dev, u_host, u, C, seq);
     }
 }
 

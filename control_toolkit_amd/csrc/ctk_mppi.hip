@@ -94,7 +94,7 @@ CTK_DEV void p2p_exchange_and_update(float* lds, int* bad, const P2PArgs& x, int
         }
         return;
     }
-    mppi_merge_block<true, 2>(lds, mine + (size_t)par * W * rs, W, P, neg_inv_lbd, nullptr, up, stage_ok != 0 ? 1 : 0);
+    mppi_merge_block<true, 2, 1, true, true, true>(lds, mine + (size_t)par * W * rs, W, P, neg_inv_lbd, nullptr, up, stage_ok != 0 ? 1 : 0);
 }
 
 __global__ __launch_bounds__(MERGE_BLOCK) void ctk_mppi_p2p_exchange(P2PArgs x, int P, float neg_inv_lbd, MppiUpdateArgs up, int stage_ok) {
@@ -252,6 +252,7 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_resident(const ResidentAr
 #undef STAMP
 #define STAMP(i) do { if ((blockIdx.x == 0 || blockIdx.x == 5) && threadIdx.x == 0 && (i) >= 3) __hip_atomic_store(&stat->stamps[(blockIdx.x ? 6 : 0) + (i) - 2], (uint32_t)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } while (0)
 #endif
+#define CTK_BODY_RESIDENT                             // the kernel goes on behind the publish: its release stays (part 1: PUB_REL)
 #define CTK_BODY_S1 16                                // as the launched kernel: the same split of the steps over the waves = the same sums, bit for bit
 #include "ctk_mppi_body_1_decl.inc"
 #include "ctk_mppi_body_3_defs.inc"
@@ -275,6 +276,7 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_resident(const ResidentAr
 #ifdef CTK_RES_STAMPS
 #pragma pop_macro("STAMP")
 #endif
+#undef CTK_BODY_RESIDENT
     uint32_t served = first_req - 1u;                 // request number of the last step this workgroup has taken
     unsigned long long t_seen = 0, t_relayed = 0;
     bool pre_ok = false;                              // the inputs of the NEXT step are already in LDS, formed for ...

@@ -37,5 +37,12 @@
 #else
     constexpr bool EARLY_U = false;
 #endif
+    // the publish of u: a launched kernel's end orders everything the step leaves, so {u, seq} goes out relaxed (ctk_device.h:
+    // publish_u_launched); the resident kernel stays on the device and keeps publish_u's release
+#ifdef CTK_BODY_RESIDENT
+    constexpr bool PUB_REL = true;
+#else
+    constexpr bool PUB_REL = false;
+#endif
 
     const uint32_t ka_sink = kernarg_prefetch<sizeof(RolloutArgs) + sizeof(typename E::K) + sizeof(MppiK) + 5 * sizeof(void*) + 16 + sizeof(FuseArgs)>();

@@ -84,13 +84,31 @@
         J = rollout_gru<LOG, false>(a, k, wperm, wperm + GRU_TABLE_FLOATS, gru_ex, row0, [&](int h) { return myu[h]; });
     }
     if (wave == 0) {
+        // EARLY_U, off the chain between J and the publish: what the early form reads that does not depend on J.  Entry 0 of the tables
+        // (c0 = i0(0), w0, w1, un) is read here, beside the correction partials below (one wait for both); the 16 tile values of the column
+        // partial of lanes 0..7 follow, behind J and ahead of wave_min, and arrive under the soft-min partial.  (The grid size and the
+        // limits stay where they are used: scalar loads share the LDS counter, and fetched here they put a full wait for the table
+        // reads in front of the correction partials in EVERY block.)
+        [[maybe_unused]] int eu_c0 = 0;
+        [[maybe_unused]] float eu_w0 = 0.0f, eu_w1 = 0.0f, eu_un = 0.0f;
+        [[maybe_unused]] float eu_tile[RPW];
+        [[maybe_unused]] bool eu_on = false;
         if constexpr (TRAJ == MPPI_TRAJ) {
-            J += (corr_s[lane] + corr_s[TRAJ + lane]) + (corr_s[2 * TRAJ + lane] + corr_s[3 * TRAJ + lane]);
+            const float cr0 = corr_s[lane], cr1 = corr_s[TRAJ + lane], cr2 = corr_s[2 * TRAJ + lane], cr3 = corr_s[3 * TRAJ + lane];
+            if constexpr (EARLY_U) {
+                eu_on = fz.mode == 1 && use_ll;
+                if (eu_on) { eu_c0 = i0_s[0]; eu_w0 = w0_s[0]; eu_w1 = w1_s[0]; eu_un = un_s[0]; }   // (behind the partials' reads: one wait)
+            }
+            J += (cr0 + cr1) + (cr2 + cr3);
         } else {
             float cs = 0.0f;
 #pragma unroll
             for (int cnk = 0; cnk < CHUNKS; ++cnk) cs += corr_s[cnk * TRAJ + (lane & (TRAJ - 1))];
             J += cs;
+        }
+        if constexpr (EARLY_U) {
+            asm volatile("" : "+v"(J));       // J is formed HERE, ahead of the tile reads' issue (they are waited for behind the soft-min)
+            if (eu_on && lane < 8) mppi_col_tile_regs<RPW>(eu_tile, tile, ts, lane & 3, eu_c0 + (lane >> 2));   // (column P: the tile's zero pad)
         }
         STAMP(3);
         if (valid) a.J[n] = J;
@@ -115,23 +133,23 @@
         //      the four words of every block, merges them in registers and publishes {u, seq}.  Everything below — the barrier, the full
         //      column sums, the full poll, the merge, the update of all H entries — is as in the late order, minus the publish.
         if constexpr (EARLY_U) {
-            if (fz.mode == 1 && use_ll) {
-                const int c0 = i0_s[0];
+            if (eu_on) {
+                const int c0 = eu_c0;
                 float cs = 0.0f;
-                if (lane < 8) cs = mppi_col_partial<RPW>(e_s, tile, ts, lane & 3, c0 + (lane >> 2));   // (column P: the tile's zero pad)
+                if (lane < 8) cs = mppi_col_partial_regs<RPW>(e_s, eu_tile, lane & 3);   // mppi_col_partial's sum, its operands fetched above
                 cs += dpp_mov<DPP_QUAD_XOR1>(cs);                     // lanes 4c .. 4c+3: (s0 + s1) + (s2 + s3), the full pass's order
                 cs += dpp_mov<DPP_QUAD_XOR2>(cs);
                 if ((lane == 0 || lane == 4) && c0 + (lane >> 2) < P)
                     ll_store(fz.ll + (size_t)blockIdx.x * (2 + P) + 2 + c0 + (lane >> 2), cs, fz.up.seq);
                 if (blockIdx.x == 0) {
                     bool late = false;                // the bounded poll ran out: error word 2, as in the tail
-                    const float o = mppi_early_u<CTK_MPPI_FUSE_MAX_BLOCKS_LL / 64>(fz.ll, (int)gridDim.x, P, c0, w0_s[0], w1_s[0], un_s[0], m.neg_inv_lbd,
+                    const float o = mppi_early_u<CTK_MPPI_FUSE_MAX_BLOCKS_LL / 64>(fz.ll, (int)gridDim.x, P, c0, eu_w0, eu_w1, eu_un, m.neg_inv_lbd,
                                                                                   fz.up.lo, fz.up.hi, fz.up.seq, &late);
+                    STAMP(11);                        // u formed (stamp 7 below: published)
                     if (lane == 0) {
                         // ctk_api.hip:finish_step turns a non-zero error word (the dword behind {u, seq}) into CTK_ERR_STATE
-                        if (late && fz.up.u_host)
-                            __hip_atomic_store(reinterpret_cast<uint32_t*>(fz.up.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        publish_u(fz.up.u_dev, fz.up.u_host, o, fz.up.seq);   // optimizer_mppi.py:191 u = u_nom[0,0,:]
+                        if (late && fz.up.u_host) host_word_store(fz.up.u_host, 2, 2u);   // (drained here only: the flag must not overtake it)
+                        publish_u_launched(fz.up.u_dev, fz.up.u_host, o, fz.up.seq);   // optimizer_mppi.py:191 u = u_nom[0,0,:]  (EARLY_U: a launched form)
                     }
                     STAMP(7);
                 }
@@ -178,12 +196,11 @@
                 poll(std::integral_constant<int, 8>{});
             }
             // ctk_api.hip:finish_step turns a non-zero error word (the dword behind {u, seq}) into CTK_ERR_STATE
-            if (expired && fz.up.u_host)
-                __hip_atomic_store(reinterpret_cast<uint32_t*>(fz.up.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (expired && fz.up.u_host) host_word_store(fz.up.u_host, 2, 2u);   // (drained ahead of the barrier: the merge's publish cannot overtake it)
             __syncthreads();
             const size_t scratch_floats = 8 + P + 1 + min(nb, MERGE_CHUNK) + (size_t)tot + MERGE_BLOCK;   // (+ the column slices of many narrow records)
             if (scratch_floats <= (size_t)(w0_s - lds)) { fz.up.w0_l = w0_s; fz.up.w1_l = w1_s; fz.up.un_l = un_s; fz.up.i0_l = i0_s; }
-            if (fz.mode == 1) mppi_merge_block<true, 0, C, WIDE_TAIL, !EARLY_U>(lds, nullptr, nb, P, m.neg_inv_lbd, nullptr, fz.up, 2);   // (EARLY_U: u is out already)
+            if (fz.mode == 1) mppi_merge_block<true, 0, C, WIDE_TAIL, !EARLY_U, PUB_REL>(lds, nullptr, nb, P, m.neg_inv_lbd, nullptr, fz.up, 2);   // (EARLY_U: u is out already)
             else mppi_merge_block<false, 0, C, WIDE_TAIL>(lds, nullptr, nb, P, m.neg_inv_lbd, fz.out_rec, fz.up, 2);
             if constexpr (P2P) {
                 // sharded step over peer-to-peer stores, all in this launch: the shard's record (just written to
@@ -224,7 +241,7 @@
             // whenever the scratch ends below them
             const size_t scratch_floats = 8 + P + 1 + min((int)gridDim.x, MERGE_CHUNK) + (fz.stage_ok ? (size_t)gridDim.x * (2 + P) + MERGE_BLOCK : 0);
             if (scratch_floats <= (size_t)(w0_s - lds)) { fz.up.w0_l = w0_s; fz.up.w1_l = w1_s; fz.up.un_l = un_s; fz.up.i0_l = i0_s; }
-            if (fz.mode == 1) mppi_merge_block<true, 1, C, WIDE_TAIL>(lds, parts, (int)gridDim.x, P, m.neg_inv_lbd, nullptr, fz.up, fz.stage_ok != 0 ? 1 : 0);
+            if (fz.mode == 1) mppi_merge_block<true, 1, C, WIDE_TAIL, true, PUB_REL>(lds, parts, (int)gridDim.x, P, m.neg_inv_lbd, nullptr, fz.up, fz.stage_ok != 0 ? 1 : 0);
             else mppi_merge_block<false, 1, C, WIDE_TAIL>(lds, parts, (int)gridDim.x, P, m.neg_inv_lbd, fz.out_rec, fz.up, fz.stage_ok != 0 ? 1 : 0);
             if (t == 0) __hip_atomic_store(fz.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }

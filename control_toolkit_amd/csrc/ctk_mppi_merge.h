@@ -58,12 +58,35 @@ CTK_DEV float mppi_update_entry(float b0, float b1, float w0, float w1, float a_
 
 // rows w*RPW .. w*RPW+RPW-1 of column p of a block record's numerator, b_b[p] = sum_r e_r * tile[r][p]: ONE function for the epilogue's
 // full pass and for the two columns that wave 0 forms ahead of it, so that both sum in the same order with the same contraction
-template <int RPW>
-CTK_DEV float mppi_col_partial(const float* e_s, const float* tile, int ts, int w, int p) {
+// (mppi_col_sum: the arithmetic — acc = e_r * tile_r + acc from zero over r = 0 .. RPW-1 — whatever the operands come from)
+template <int RPW, class FE, class FT>
+CTK_DEV float mppi_col_sum(FE e_at, FT tile_at) {
     float acc = 0.0f;
 #pragma unroll
-    for (int r = 0; r < RPW; ++r) acc += e_s[w * RPW + r] * tile[(w * RPW + r) * ts + p];
+    for (int r = 0; r < RPW; ++r) acc += e_at(r) * tile_at(r);
     return acc;
+}
+template <int RPW>
+CTK_DEV float mppi_col_partial(const float* e_s, const float* tile, int ts, int w, int p) {
+    return mppi_col_sum<RPW>([&](int r) { return e_s[w * RPW + r]; }, [&](int r) { return tile[(w * RPW + r) * ts + p]; });
+}
+// ... the early form's operands: the column's RPW tile values are in registers already (read under the soft-min partial, they do not
+// depend on J), the row group's RPW weights come out of e_s in 16-byte reads (contiguous, 64-byte aligned: ONE wait in front of the sum)
+template <int RPW>
+CTK_DEV void mppi_col_tile_regs(float (&tv)[RPW], const float* tile, int ts, int w, int p) {
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) tv[r] = tile[(w * RPW + r) * ts + p];
+}
+template <int RPW>
+CTK_DEV float mppi_col_partial_regs(const float* e_s, const float (&tv)[RPW], int w) {
+    static_assert(RPW % 4 == 0, "the weights of a row group are read as float4");
+    float ev[RPW];
+#pragma unroll
+    for (int q = 0; q < RPW / 4; ++q) {
+        const float4 e4 = reinterpret_cast<const float4*>(e_s + w * RPW)[q];
+        ev[4 * q] = e4.x; ev[4 * q + 1] = e4.y; ev[4 * q + 2] = e4.z; ev[4 * q + 3] = e4.w;
+    }
+    return mppi_col_sum<RPW>([&](int r) { return ev[r]; }, [&](int r) { return tv[r]; });
 }
 
 // scratch: >= 8 + (P + 1) + min(cnt, MERGE_CHUNK) floats of LDS, plus cnt*(2+P) more when `stage`
@@ -71,7 +94,9 @@ CTK_DEV float mppi_col_partial(const float* e_s, const float* tile, int ts, int 
 // CH: control inputs of the FINAL update (compile time: the C == 1 instantiations are CartPole's statement sequence, unchanged)
 // MANY: the sliced column sums of many narrow records are compiled in (a caller that never merges more than 128 records leaves them out)
 // PUB: the FINAL update publishes u (false: entry 0 went out ahead of the plan update, mppi_early_u; C == 1 only)
-template <bool FINAL, int SC1, int CH = 1, bool MANY = true, bool PUB = true>
+// REL: ... with publish_u's system-scope release — the callers whose kernel does NOT end behind the publish (the resident kernel, the
+//      peer-to-peer exchange); every launched form takes the relaxed publish (ctk_device.h: publish_u_launched)
+template <bool FINAL, int SC1, int CH = 1, bool MANY = true, bool PUB = true, bool REL = false>
 CTK_DEV void mppi_merge_block(float* scratch, const float* base, int cnt, int P, float neg_inv_lbd, float* out_rec,
                               const MppiUpdateArgs& up, int stage) {
     float* red = scratch;             // [4] cross-wave scratch
@@ -175,7 +200,10 @@ CTK_DEV void mppi_merge_block(float* scratch, const float* base, int cnt, int P,
                 const float o = mppi_update_entry(b_s[e.i0], b_s[e.i0 + 1], e.w0, e.w1, a_tot, un, up.lo, up.hi);
                 up.u_nom_out[h] = o;
                 if constexpr (PUB) {
-                    if (h == 0) publish_u(up.u_dev, up.u_host, o, up.seq);   // :191 u = u_nom[0,0,:]
+                    if (h == 0) {                            // :191 u = u_nom[0,0,:]
+                        if constexpr (REL) publish_u(up.u_dev, up.u_host, o, up.seq);
+                        else publish_u_launched(up.u_dev, up.u_host, o, up.seq);
+                    }
                 }
             }
         } else {
@@ -196,7 +224,10 @@ CTK_DEV void mppi_merge_block(float* scratch, const float* base, int cnt, int P,
                 if (h == 0) u_s[c] = o;
             }
             __syncthreads();
-            if (t == 0) publish_u_vec(up.u_dev, up.u_host, u_s, C, up.seq);   // :191 u = u_nom[0,0,:]
+            if (t == 0) {                                    // :191 u = u_nom[0,0,:]
+                if constexpr (REL) publish_u_vec(up.u_dev, up.u_host, u_s, C, up.seq);
+                else publish_u_vec_launched(up.u_dev, up.u_host, u_s, C, up.seq);
+            }
         }
     }
 }
@@ -307,12 +338,22 @@ CTK_DEV float mppi_early_u(const unsigned long long* ll, int nb, int P, int c0, 
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
         const int v0 = __builtin_bit_cast(int, val(k, 2)), v1 = __builtin_bit_cast(int, has1 ? val(k, 3) : 0.0f), vs = __builtin_bit_cast(int, sc[k]);
-        const int cn = min(64, nb - k * 64);
-        for (int i = 0; i < cn; ++i) {
+        const int cn = max(0, min(64, nb - k * 64));   // (an absent batch: none)
+        auto add = [&](int i) {               // record k*64 + i: i ascending from zero, the same two accumulators
             const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vs, i));
             b0 += __builtin_bit_cast(float, __builtin_amdgcn_readlane(v0, i)) * s;
             b1 += __builtin_bit_cast(float, __builtin_amdgcn_readlane(v1, i)) * s;
+        };
+        // whole chunks of 16 records with constant lane numbers (straight-line: no compare and branch per record; 16 blocks = one
+        // chunk), then a rolled remainder
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (cn >= 16 * (q + 1)) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) add(16 * q + j);
+            }
         }
+        for (int i = cn & ~15; i < cn; ++i) add(i);
     }
     return mppi_update_entry(b0, b1, w0, w1, a_tot, un, lo, hi);
 }
@@ -329,8 +370,7 @@ CTK_DEV void mppi_ll_tail(float* lds, const unsigned long long* ll, int nb, int 
     float* st = merge_stage_ptr(lds, nb, P);
     bool expired = false;
     for (int i0 = t; i0 < tot; i0 += MERGE_BLOCK * 8) expired |= ll_poll_stage<8, MERGE_BLOCK>(ll, st, i0, tot, up.seq);   // 8 words in flight per thread
-    if (expired && up.u_host)
-        __hip_atomic_store(reinterpret_cast<uint32_t*>(up.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (expired && up.u_host) host_word_store(up.u_host, 2, 2u);   // (drained ahead of the barrier: the merge's publish cannot overtake it)
     __syncthreads();
     if (mode == 1) mppi_merge_block<true, 0, CH>(lds, nullptr, nb, P, neg_inv_lbd, nullptr, up, 2);
     else mppi_merge_block<false, 0, CH>(lds, nullptr, nb, P, neg_inv_lbd, out_rec, up, 2);

@@ -108,7 +108,7 @@ CTK_DEV void rpgd_warm_element(const WarmArgs& w, const RolloutArgs& a, const Ro
         const float q = w.recs ? w.recs[(size_t)idx[0] * w.rs + 3 + gid] : Q_old[(size_t)idx[0] * HC + gid];
         u_nom[gid] = q;
         if (C == 1) {
-            if (gid == 0) publish_u(u_dev, u_host, q, seq);   // :523
+            if (gid == 0) publish_u_launched(u_dev, u_host, q, seq);   // :523
         } else if (gid == 0) {
             // one thread publishes the whole input vector: u[c] first (floats 4..), then the {u[0], seq} word the host polls
             for (int cc = 0; cc < C; ++cc) {
@@ -116,8 +116,9 @@ CTK_DEV void rpgd_warm_element(const WarmArgs& w, const RolloutArgs& a, const Ro
                 u_dev[cc] = uc;
                 __hip_atomic_store(u_host + 4 + cc, uc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
+            host_words_drain();                      // the vector lands before the flag (ctk_device.h: publish_u_launched)
             const unsigned long long pv = ((unsigned long long)seq << 32) | (unsigned long long)__builtin_bit_cast(unsigned, q);
-            __hip_atomic_store(reinterpret_cast<unsigned long long*>(u_host), pv, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(reinterpret_cast<unsigned long long*>(u_host), pv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }

@@ -209,17 +209,17 @@ CTK_DEV void affine_rollout_body(const float* __restrict__ samples, const float*
                         }
                     }
                     // a stale record may have won or lost wrongly: tell the host (ctk_api.hip:finish_step -> CTK_ERR_STATE)
-                    if (expired) __hip_atomic_store(reinterpret_cast<uint32_t*>(best.u_host) + 2, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    if (expired) host_word_store(best.u_host, 2, 2u);   // (drained by this wave, whose winner lane stores the flag below)
                     const uint32_t gk = wave_min_u32(bk);
                     const uint32_t gi = wave_min_u32(bk == gk ? bi : 0x7FFFFFFFu);
                     if (bk == gk && bi == gi) {     // exactly one lane holds the winner
                         best.idx_out[0] = (int)gi;
-                        if constexpr (C == 1) publish_u(best.u_dev, best.u_host, __builtin_bit_cast(float, bu[0]), best.seq);
+                        if constexpr (C == 1) publish_u_launched(best.u_dev, best.u_host, __builtin_bit_cast(float, bu[0]), best.seq);
                         else {
                             float uo[C];
 #pragma unroll
                             for (int c = 0; c < C; ++c) uo[c] = __builtin_bit_cast(float, bu[c]);
-                            publish_u_vec(best.u_dev, best.u_host, uo, C, best.seq);
+                            publish_u_vec_launched(best.u_dev, best.u_host, uo, C, best.seq);
                         }
                     }
                 }

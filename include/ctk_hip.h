@@ -302,6 +302,9 @@ int ctk_predictor_set_hidden(ctk_handle* h, const float* src, size_t n); /* src 
  * Synchronous: returns when u_out is valid.
  * Completion of a step.  When ctk_step returns,
  *   - u_out is FINAL;
+ *   - ONLY u_out and the step's error words are guaranteed visible at that moment: the publishing kernel stores them — and nothing else —
+ *     through to the host (relaxed system-scope stores, no write-back of the device's caches in front of them); everything else the step
+ *     leaves is reached through API entries, which are ordered behind the launch on the handle's stream (next item);
  *   - the handle's other results of the step (the new plan U_NOM above all) are final for EVERY LATER API CALL on the handle: the MPPI
  *     kernel publishes u = u_nom_new[0] ahead of the update of the rest of the plan, so its launch may still be finishing that update
  *     for a few microseconds; every API entry that reads or writes the handle's buffers is ordered behind the launch on the handle's

@@ -66,6 +66,9 @@ int main(int argc, char** argv) {
         std::vector<double> a_step;           // every block: J ready -> its barrier (the soft-min partial + its two fast column sums)
         for (int b = 0; b < nb; ++b) a_step.push_back((double)(st[b * 16 + 4] - st[b * 16 + 3]));
         std::sort(a_step.begin(), a_step.end());
+        if (st[7] != 0 && st[11] != 0)        // stamp 11: u formed, ahead of the publish's stores (what the publish itself costs the path)
+            printf("  early publish of u, block 0: J ready -> u formed %lld cycles; u formed -> published %lld cycles\n",
+                   (long long)(st[11] - st[3]), (long long)(st[7] - st[11]));
         if (st[7] != 0)
             printf("  early publish of u, block 0: J ready -> publish %lld cycles; publish -> kernel end %lld cycles  (J ready -> barrier, blocks 1..: median %.0f)\n",
                    (long long)(st[7] - st[3]), (long long)(st[6] - st[7]), a_step[a_step.size() / 2]);
