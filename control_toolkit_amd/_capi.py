@@ -292,6 +292,24 @@ def environment_defaults(name: str) -> dict:
     return out
 
 
+# the pre-bound step call (csrc/ctk_pystep.cpp -> _ctk_pystep): an optional accelerator of CtkEngine.step.  Not built, built for
+# another interpreter, or CTK_PYSTEP=0 in the environment: the engine keeps its ctypes path.  Looked up once per process.
+_pystep = None
+
+
+def _pystep_module():
+    global _pystep
+    if _pystep is None:
+        _pystep = False
+        if os.environ.get("CTK_PYSTEP", "1") != "0":
+            try:
+                from . import _ctk_pystep
+                _pystep = _ctk_pystep
+            except ImportError:
+                pass
+    return _pystep or None
+
+
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -350,11 +368,12 @@ class CtkEngine:
                  action_low: float = -1.0, action_high: float = 1.0, period_interpolation_inducing_points: int = 1,
                  seed: int = 0, device: int = 0, intermediate_steps: int = 1, materialize_trajectories: bool = False,
                  global_rollout_offset: int = 0, num_states: int = None, num_control_inputs: int = None,
-                 environment: str = "CartPole", generic_kernels: bool = False, predictor_hidden=None, **kw):
+                 environment: str = "CartPole", generic_kernels: bool = False, predictor_hidden=None, pystep: bool = None, **kw):
         """action_low / action_high: scalars (every input) or one value per control input.  environment: the plant +
         cost the kernels implement ("CartPole", "Quad2D", "Hover"); num_states / num_control_inputs default to its dimensions and
         are checked against them.  generic_kernels: run the environment-agnostic template kernels even where a hand-tuned
-        one exists."""
+        one exists.  pystep: False keeps step() on the ctypes call even where the pre-bound call (_ctk_pystep) is available;
+        None / True use it where it is (see step_path)."""
         lib, env_id = environment_library(environment)
         S, Cn, self.param_names = environment_info(environment)
         self.environment, self.S, self.C = environment, S, Cn
@@ -391,14 +410,32 @@ class CtkEngine:
         self._up = np.zeros(Cn, np.float32)
         self._u_p, self._s_p, self._up_p = self._u.ctypes.data, self._s.ctypes.data, self._up.ctypes.data
         self._step_fn = lib.ctk_step
+        self._bound = None
+        if pystep is None or pystep:
+            self._bind_step()
 
     # ---- plumbing ------------------------------------------------------------------------------
+    def _bind_step(self):
+        """step() through the pre-bound call where the module is there: ctk_step's address in the library this engine loaded, the
+        handle, the sizes and self._u's memory are fixed once (ctk_pystep.cpp)"""
+        mod = _pystep_module()
+        if mod is not None:
+            self._bound = mod.bind(C.cast(self._step_fn, C.c_void_p).value, self._h.value, self.S, self.C, self._u)
+
+    @property
+    def step_path(self) -> str:
+        """which call step() makes: "bound" (_ctk_pystep) or "ctypes" """
+        return "bound" if self._bound is not None else "ctypes"
+
     def _check(self, rc: int):
         if rc != 0:
             msg = self._lib.ctk_last_error(self._h).decode()
             raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(f"[ctk {rc}] {msg}")
 
     def close(self):
+        if getattr(self, "_bound", None) is not None:   # before ctk_destroy: the bound call must never see a freed handle
+            self._bound.invalidate()
+            self._bound = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.ctk_destroy(self._h)
             self._h = _H()
@@ -489,6 +526,21 @@ class CtkEngine:
 
     def step(self, s, samples=None, loc: int = None, u_prev=None) -> np.ndarray:
         """samples: None (device Philox), a host ndarray (parity mode) or an int device pointer."""
+        bound = self._bound
+        if bound is not None:
+            # the pre-bound call takes float32 buffers of the right sizes as they are; NotImplemented = an argument that needs
+            # the conversions (or the error texts) below, and ctk_step has not been called
+            if samples is None:
+                rc = bound(s, u_prev, None, LOC_NONE)
+            elif type(samples) is int:
+                rc = bound(s, u_prev, samples, LOC_DEVICE)
+            else:
+                arr = _f32(samples)
+                rc = bound(s, u_prev, arr.ctypes.data, LOC_HOST) if arr.size == self.samples_needed() else NotImplemented
+            if rc is not NotImplemented:
+                if rc:
+                    self._check(rc)
+                return self._u.copy()
         try:
             self._s[:] = np.asarray(s).reshape(-1)
         except ValueError:

@@ -64,7 +64,8 @@ def build_environment(header_path: str, jobs: int = 8, verbose: bool = False):
                 with open(copy, "wb") as f:
                     f.write(open(header_path, "rb").read())
                 cmd = ["make", "-C", _CSRC, f"-j{max(1, min(jobs, os.cpu_count() or 1))}", f"BUILD={os.path.join(out_dir, 'obj')}", f"LIB={lib}",
-                       f"EXTRA=-DCTK_USER_ENV_HEADER='\"{copy}\"'", f"USER_ENV_DEP={copy}"]
+                       f"EXTRA=-DCTK_USER_ENV_HEADER='\"{copy}\"'", f"USER_ENV_DEP={copy}",
+                       lib]   # the library alone: `all` also builds the engine's optional _ctk_pystep module, which is not this build's business
                 r = subprocess.run(cmd, capture_output=True, text=True)
                 if r.returncode != 0 or not os.path.exists(lib):
                     tail = "\n".join((r.stdout + "\n" + r.stderr).splitlines()[-40:])

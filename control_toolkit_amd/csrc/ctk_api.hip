@@ -28,7 +28,21 @@ struct EventPair {
 
 }  // namespace
 
+// -DCTK_HOST_STAMPS (diagnostic build, tools/host_split.py; never the product library): where ctk_step's own host time goes in the
+// one-launch MPPI step.  Stamps in the handle: 0 ctk_step entered, 1 before the launch call, 2 the launch call returned, 3 {u, seq}
+// seen by finish_step; the three intervals are summed per handle and read through ctk_diag_host_split (exported by that build alone).
+#ifdef CTK_HOST_STAMPS
+#define CTK_HSTAMP(h, i) ((h)->hstamp[i] = std::chrono::steady_clock::now())
+#else
+#define CTK_HSTAMP(h, i) ((void)0)
+#endif
+
 struct ctk_handle {
+#ifdef CTK_HOST_STAMPS
+    std::chrono::steady_clock::time_point hstamp[4]{};
+    double hsplit_ns[3] = {0.0, 0.0, 0.0};
+    uint64_t hsplit_n = 0;
+#endif
     ctk_config cfg{};
     int N = 0, H = 0, P = 0;
     int env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C;   // the environment and its dimensions
@@ -611,6 +625,14 @@ int finish_step(ctk_handle* h, float* u_out) {
         if (*slot != want) return fail(h, CTK_ERR_HIP, "step finished without publishing its result");
     }
     std::atomic_thread_fence(std::memory_order_acquire);
+#ifdef CTK_HOST_STAMPS
+    CTK_HSTAMP(h, 3);
+    if (h->hstamp[1] >= h->hstamp[0] && h->hstamp[2] >= h->hstamp[1]) {   // a ctk_step that went through the stamped launch
+        for (int i = 0; i < 3; ++i) h->hsplit_ns[i] += std::chrono::duration<double, std::nano>(h->hstamp[i + 1] - h->hstamp[i]).count();
+        ++h->hsplit_n;
+        h->hstamp[1] = {};
+    }
+#endif
     if (u_out) {
         u_out[0] = *reinterpret_cast<volatile float*>(h->h_u);
         for (int c = 1; c < h->C; ++c) u_out[c] = reinterpret_cast<volatile float*>(h->h_u)[4 + c];   // publish_u_vec
@@ -816,8 +838,10 @@ int mppi_rollout(ctk_handle* h, const float* s, const float* u_prev, const float
         return CTK_OK;
     }
     const char* ran = nullptr;
+    CTK_HSTAMP(h, 1);
     HIP_TRY(h, ctk_launch_mppi_rollout(h->stream, h->cfg.predictor, a, h->k, h->mk, d_s, h->d_unom[h->cur], h->d_wperm,
                                        h->d_parts, log, fz, ps.a, ps.b, &ran));
+    CTK_HSTAMP(h, 2);
     if (ran != h->dominant_ran) { h->dominant_ran = ran; h->dominant = ran; }   // string literals: pointer compare
     return CTK_OK;
 }
@@ -1721,6 +1745,7 @@ int ctk_rng_set_position(ctk_handle* h, uint32_t call) {
 
 int ctk_step(ctk_handle* h, const float* s, const float* u_prev, const float* samples, int samples_loc, float* u_out) {
     if (!h || !s) return h ? fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    CTK_HSTAMP(h, 0);
     return guarded(h, [&]() -> int {
     if (h->mppi_pending) return fail(h, CTK_ERR_STATE, "ctk_step: a sharded step is pending (call ctk_mppi_step_end)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -4039,3 +4064,15 @@ int ctk_rpgd_batch_rng_set_position(ctk_rpgd_batch* b, int problem, uint32_t cal
 }
 
 }  // extern "C"
+
+#ifdef CTK_HOST_STAMPS
+// diagnostic build only (tools/host_split.py): out = {steps counted, ns entry -> launch call, ns inside the launch call,
+// ns launch return -> {u, seq} seen}, summed since the last read; the sums are cleared
+extern "C" int ctk_diag_host_split(ctk_handle* h, double* out4) {
+    if (!h || !out4) return CTK_ERR_INVALID_ARGUMENT;
+    out4[0] = (double)h->hsplit_n;
+    for (int i = 0; i < 3; ++i) { out4[1 + i] = h->hsplit_ns[i]; h->hsplit_ns[i] = 0.0; }
+    h->hsplit_n = 0;
+    return CTK_OK;
+}
+#endif
