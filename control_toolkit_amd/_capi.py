@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -787,9 +788,9 @@ _F32_MAX = float(np.finfo(np.float32).max)
 
 
 def batch_param_args(param_names, num_problems: int, name, values, ids=None):
-    """Checks the arguments of CtkMppiBatch.set_problem_params / CtkCemBatch.set_problem_params / CtkRpgdBatch.set_problem_params without touching a device: the parameter name against the environment's
-    names, ids (batch_ids), values a finite scalar (every listed problem) or one finite value per listed problem ([n]).  Returns
-    (parameter id, ids, n, values as fp32 [n])."""
+    """Checks the arguments of CtkMppiBatch.set_problem_params / CtkCemBatch.set_problem_params / CtkRpgdBatch.set_problem_params
+    without touching a device: the parameter name against the environment's names, ids (batch_ids), values a finite scalar (every
+    listed problem) or one finite value per listed problem ([n]).  Returns (parameter id, ids, n, values as fp32 [n])."""
     if name not in param_names:
         raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(param_names)})")
     idv = batch_ids(num_problems, ids)
@@ -809,64 +810,70 @@ def batch_param_args(param_names, num_problems: int, name, values, ids=None):
     return param_names.index(name), idv, n, out
 
 
-class CtkMppiBatch:
-    """Owns one ctk_batch: num_problems independent MPPI controllers of ONE configuration (the MPPI keywords of CtkEngine), stepped by
-    one kernel launch per step.  Problem p behaves bit for bit like CtkEngine("mppi", "ODE", seed=seeds[p], ...) given the same calls,
-    set_param among them: set_problem_params gives every problem its own plant, cost weights and targets, set_param the same value to all.
-    seeds: one per problem (default seed + p)."""
+class _CtkBatch:
+    """What the batch classes share: the handle, the argument buffers, the error mapping, the parameter tables and the Philox positions.
+    A family is its two entry-point prefixes (_BATCH: the calls on a batch, _PROBLEM: the per-problem parameter calls); its entries are
+    looked up by name once, when the batch is created (_open)."""
 
-    def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "mppi", predictor: str = "ODE",
-                 num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
-                 period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
-                 materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
-                 num_control_inputs: int = None, generic_kernels: bool = False, **kw):
-        # what needs no device is checked before the library is asked for one
+    _BATCH = _PROBLEM = None
+    _BATCH_ENTRIES = ("create", "destroy", "last_error", "samples_needed", "step", "reset", "read", "get_state", "set_state", "set_param",
+                      "get_param", "rng_get_position", "rng_set_position", "dominant_kernel")
+    _PROBLEM_ENTRIES = ("set_param", "get_param", "params_differ")
+
+    # what needs no device is checked before the library is asked for one: _count, _seeds, _known and the class's own refusals
+    @staticmethod
+    def _count(num_problems) -> int:
         if int(num_problems) < 1:
             raise ValueError(f"a batch holds at least one problem (num_problems == {num_problems})")
-        B = int(num_problems)
-        if optimizer != "mppi":
-            raise NotImplementedError(f"a batch steps MPPI controllers only (optimizer {optimizer!r}); the other optimizers run as CtkEngine")
-        if predictor != "ODE":
-            raise NotImplementedError(f"the batch kernel rolls out the analytic (ODE) predictor only (predictor {predictor!r}); "
-                                      "network predictors run as CtkEngine")
+        return int(num_problems)
+
+    @staticmethod
+    def _seeds(B: int, seeds):
         if seeds is not None:
             seeds = np.ascontiguousarray(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in np.asarray(seeds, dtype=object).reshape(-1)], np.uint64))
             if seeds.size != B:
                 raise ValueError(f"seeds must have one entry per problem ({B}), got {seeds.size}")
+        return seeds
+
+    @staticmethod
+    def _known(kw):
+        unknown = set(kw) - set(_CONFIG_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown engine arguments: {sorted(unknown)}")
+
+    def _open(self, B: int, seeds, optimizer: str, predictor: str, environment: str, *, num_states, num_control_inputs, **cfg_kw):
+        """the library of `environment`, the configuration, the family's entries, the handle and the argument buffers"""
         lib, env_id = environment_library(environment)
         S, Cn, self.param_names = environment_info(environment)
         self.environment, self.S, self.C, self.B = environment, S, Cn, B
-        cfg = _make_config("mppi", "ODE", env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
-                           action_low=action_low, action_high=action_high,
-                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
-                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
-                           global_rollout_offset=global_rollout_offset, num_states=S if num_states is None else num_states,
-                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs, generic_kernels=generic_kernels, **kw)
+        cfg = _make_config(optimizer, predictor, env_id, environment, Cn, num_states=S if num_states is None else num_states,
+                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs, **cfg_kw)
         self._lib, self.cfg = lib, cfg
-        self.N, self.H = int(num_rollouts), int(mpc_horizon)
+        self.N, self.H = int(cfg.num_rollouts), int(cfg.mpc_horizon)
+        self._b = SimpleNamespace(**{e: getattr(lib, f"{self._BATCH}_{e}") for e in self._BATCH_ENTRIES})
+        self._p = SimpleNamespace(**{e: getattr(lib, f"{self._PROBLEM}_{e}") for e in self._PROBLEM_ENTRIES})
         self._h = _H()
-        rc = lib.ctk_batch_create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
+        rc = self._b.create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
         if rc != 0:
-            msg = lib.ctk_batch_last_error(None).decode()
+            msg = self._b.last_error(None).decode()
             self._h = _H()
             raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(msg)
-        self._per = int(lib.ctk_batch_samples_needed(self._h))
         # preallocated argument buffers, as CtkEngine.step's: rows 0 .. n-1 are the stepped problems'
         self._s = np.zeros((B, S), np.float32)
         self._up = np.zeros((B, Cn), np.float32)
         self._u = np.zeros((B, Cn), np.float32)
         self._ids = np.zeros(B, np.int32)
         self._s_p, self._up_p, self._u_p, self._ids_p = (a.ctypes.data for a in (self._s, self._up, self._u, self._ids))
-        self._step_fn = lib.ctk_batch_step
+        self._step_fn = self._b.step
 
     def _check(self, rc: int):
         if rc != 0:
-            msg = self._lib.ctk_batch_last_error(self._h).decode()
+            msg = self._b.last_error(self._h).decode()
             raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(f"[ctk {rc}] {msg}")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.ctk_batch_destroy(self._h)
+            self._b.destroy(self._h)
             self._h = _H()
 
     def __del__(self):
@@ -878,16 +885,15 @@ class CtkMppiBatch:
     def __len__(self):
         return self.B
 
-    def samples_needed(self) -> int:
-        """draws one problem's step consumes (N * P * C)"""
-        return self._per
+    def _problem(self, problem: int) -> int:
+        if not 0 <= int(problem) < self.B:
+            raise ValueError(f"problem index {problem} is outside 0 .. {self.B - 1}")
+        return int(problem)
 
-    def step(self, S, samples=None, u_prev=None, ids=None) -> np.ndarray:
-        """S [n, num_states], one row per stepped problem in the order of ids (None: all problems).  samples: None (device Philox), a
-        host array [n, N, P, C] or an int device pointer to such an array.  u_prev [n, C] or None (every problem's own last output).
-        Returns u [n, C].  CtkError naming the problems whose in-launch hand-off timed out: the other problems' rows are valid (`last_u`)."""
-        idv, n, samples = batch_step_args(self.B, self.S, self.C, self._per, S, samples, u_prev, ids)
-        self._s[:n] = np.asarray(S).reshape(n, self.S)
+    def _step_args(self, n: int, idv, S, u_prev, samples):
+        """the front of a step, after its arguments were checked (batch_step_args): states, u_prev and ids into rows 0 .. n-1 of the
+        buffers.  Returns the pointers (ids, u_prev, samples) and where the samples are (LOC_*)."""
+        self._s[:n] = S                # checked to be [n, S] (or [S] for one problem, which broadcasts): the assignment converts
         up_p = None
         if u_prev is not None:
             self._up[:n] = np.asarray(u_prev).reshape(n, self.C)
@@ -902,49 +908,35 @@ class CtkMppiBatch:
             sp, loc = samples, LOC_DEVICE
         else:
             sp, loc = samples.ctypes.data, LOC_HOST
-        rc = self._step_fn(self._h, n, ids_p, self._s_p, up_p, sp, loc, self._u_p)
-        self.last_u = self._u[:n].copy()
-        if rc:
-            self._check(rc)
-        return self.last_u
+        return ids_p, up_p, sp, loc
 
-    def reset(self, ids=None):
-        idv = batch_ids(self.B, ids)
-        self._check(self._lib.ctk_batch_reset(self._h, 0 if idv is None else idv.size, _ptr(idv)))
-
-    def _problem(self, problem: int) -> int:
-        if not 0 <= int(problem) < self.B:
-            raise ValueError(f"problem index {problem} is outside 0 .. {self.B - 1}")
-        return int(problem)
-
-    def read(self, name: str, problem: int) -> np.ndarray:
-        N, H, S, Cn = self.N, self.H, self.S, self.C
-        shapes = {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn)}
+    def _read(self, what: str, shapes: dict, name: str, problem: int) -> np.ndarray:
         if name not in shapes:
-            raise ValueError(f"a batch has the buffers {sorted(shapes)}, not {name!r}")
+            raise ValueError(f"{what} has the buffers {sorted(shapes)}, not {name!r}")
         out = np.empty(shapes[name], np.float32)
-        self._check(self._lib.ctk_batch_read(self._h, self._problem(problem), BUFFERS[name], _ptr(out), out.size))
-        return out
+        self._check(self._b.read(self._h, self._problem(problem), BUFFERS[name], _ptr(out), out.size))
+        return out.astype(np.int64) if name == "BEST_IDX" else out
 
     def read_all(self, name: str) -> np.ndarray:
         return np.stack([self.read(name, p) for p in range(self.B)])
 
-    def get_state(self, problem: int) -> np.ndarray:
-        buf = np.empty(self.H * self.C + self.C, np.float32)
-        self._check(self._lib.ctk_batch_get_state(self._h, self._problem(problem), _ptr(buf), buf.size))
+    def _get_state(self, problem: int, size: int) -> np.ndarray:
+        buf = np.empty(size, np.float32)
+        self._check(self._b.get_state(self._h, self._problem(problem), _ptr(buf), buf.size))
         return buf
 
     def set_state(self, problem: int, state):
         st = _f32(state).ravel()
-        self._check(self._lib.ctk_batch_set_state(self._h, self._problem(problem), _ptr(st), st.size))
+        self._check(self._b.set_state(self._h, self._problem(problem), _ptr(st), st.size))
 
     def set_param(self, name: str, value: float):
-        self._check(self._lib.ctk_batch_set_param(self._h, self.param_names.index(name), float(value)))
+        """parameter `name` of every problem (that column of every problem's table; the other parameters stay per problem)"""
+        self._check(self._b.set_param(self._h, self.param_names.index(name), float(value)))
 
     def get_param(self, name: str) -> float:
         """the last value set_param gave the whole batch (the default before that); a problem's own value: get_problem_param"""
         v = C.c_float()
-        self._check(self._lib.ctk_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
+        self._check(self._b.get_param(self._h, self.param_names.index(name), C.byref(v)))
         return v.value
 
     def set_problem_params(self, name: str, values, ids=None):
@@ -952,14 +944,14 @@ class CtkMppiBatch:
         next step re-derives the constants of the problems touched; from the first call on the batch runs the per-problem form of its
         kernel (params_differ, dominant_kernel)."""
         pid, idv, n, vals = batch_param_args(self.param_names, self.B, name, values, ids)
-        self._check(self._lib.ctk_problem_set_param(self._h, n, _ptr(idv), pid, _ptr(vals)))
+        self._check(self._p.set_param(self._h, n, _ptr(idv), pid, _ptr(vals)))
 
     def get_problem_param(self, name: str, problem: int) -> float:
         if name not in self.param_names:
             raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(self.param_names)})")
         v = C.c_float()
-        if self._lib.ctk_problem_get_param(self._h, self._problem(problem), self.param_names.index(name), C.byref(v)) != 0:
-            raise CtkError(f"ctk_problem_get_param({problem}, {name!r}) failed")
+        if self._p.get_param(self._h, self._problem(problem), self.param_names.index(name), C.byref(v)) != 0:
+            raise CtkError(f"{self._PROBLEM}_get_param({problem}, {name!r}) failed")
         return v.value
 
     def get_problem_params(self, name: str) -> np.ndarray:
@@ -968,18 +960,73 @@ class CtkMppiBatch:
 
     def params_differ(self) -> int:
         """1 once a set_problem_params has succeeded on this batch (sticky), else 0"""
-        return int(self._lib.ctk_problem_params_differ(self._h))
+        return int(self._p.params_differ(self._h))
 
     def rng_position(self, problem: int) -> int:
         v = C.c_uint32()
-        self._check(self._lib.ctk_batch_rng_get_position(self._h, self._problem(problem), C.byref(v)))
+        self._check(self._b.rng_get_position(self._h, self._problem(problem), C.byref(v)))
         return int(v.value)
 
     def set_rng_position(self, problem: int, call: int):
-        self._check(self._lib.ctk_batch_rng_set_position(self._h, self._problem(problem), int(call) & 0xFFFFFFFF))
+        self._check(self._b.rng_set_position(self._h, self._problem(problem), int(call) & 0xFFFFFFFF))
 
     def dominant_kernel(self) -> str:
-        return self._lib.ctk_batch_dominant_kernel(self._h).decode()
+        return self._b.dominant_kernel(self._h).decode()
+
+
+class CtkMppiBatch(_CtkBatch):
+    """Owns one ctk_batch: num_problems independent MPPI controllers of ONE configuration (the MPPI keywords of CtkEngine), stepped by
+    one kernel launch per step.  Problem p behaves bit for bit like CtkEngine("mppi", "ODE", seed=seeds[p], ...) given the same calls,
+    set_param among them: set_problem_params gives every problem its own plant, cost weights and targets, set_param the same value to all.
+    seeds: one per problem (default seed + p)."""
+
+    _BATCH, _PROBLEM = "ctk_batch", "ctk_problem"
+
+    def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "mppi", predictor: str = "ODE",
+                 num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
+                 period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
+                 materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
+                 num_control_inputs: int = None, generic_kernels: bool = False, **kw):
+        B = self._count(num_problems)
+        if optimizer != "mppi":
+            raise NotImplementedError(f"a batch steps MPPI controllers only (optimizer {optimizer!r}); the other optimizers run as CtkEngine")
+        if predictor != "ODE":
+            raise NotImplementedError(f"the batch kernel rolls out the analytic (ODE) predictor only (predictor {predictor!r}); "
+                                      "network predictors run as CtkEngine")
+        self._open(B, self._seeds(B, seeds), "mppi", "ODE", environment, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                   action_low=action_low, action_high=action_high,
+                   period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                   intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                   global_rollout_offset=global_rollout_offset, num_states=num_states, num_control_inputs=num_control_inputs,
+                   generic_kernels=generic_kernels, **kw)
+        self._per = int(self._b.samples_needed(self._h))
+
+    def samples_needed(self) -> int:
+        """draws one problem's step consumes (N * P * C)"""
+        return self._per
+
+    def step(self, S, samples=None, u_prev=None, ids=None) -> np.ndarray:
+        """S [n, num_states], one row per stepped problem in the order of ids (None: all problems).  samples: None (device Philox), a
+        host array [n, N, P, C] or an int device pointer to such an array.  u_prev [n, C] or None (every problem's own last output).
+        Returns u [n, C].  CtkError naming the problems whose in-launch hand-off timed out: the other problems' rows are valid (`last_u`)."""
+        idv, n, samples = batch_step_args(self.B, self.S, self.C, self._per, S, samples, u_prev, ids)
+        ids_p, up_p, sp, loc = self._step_args(n, idv, S, u_prev, samples)
+        rc = self._step_fn(self._h, n, ids_p, self._s_p, up_p, sp, loc, self._u_p)
+        self.last_u = self._u[:n].copy()
+        if rc:
+            self._check(rc)
+        return self.last_u
+
+    def reset(self, ids=None):
+        idv = batch_ids(self.B, ids)
+        self._check(self._b.reset(self._h, 0 if idv is None else idv.size, _ptr(idv)))
+
+    def read(self, name: str, problem: int) -> np.ndarray:
+        N, H, S, Cn = self.N, self.H, self.S, self.C
+        return self._read("a batch", {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn)}, name, problem)
+
+    def get_state(self, problem: int) -> np.ndarray:
+        return self._get_state(problem, self.H * self.C + self.C)
 
 
 # ---- batched MPPI with the MLP predictor (include/ctk_hip.h: ctk_mlp_batch_* / ctk_mlp_problem_*) --------------------------------------
@@ -987,20 +1034,6 @@ def mlp_weight_count(num_states: int, num_control_inputs: int, hidden=(32, 32)) 
     """floats of one (S+C)-h1-h2-S MLP in the layout of ctk_set_predictor_weights: W1, b1, W2, b2, W3, b3 (ctk_mlp_batch_weight_count)"""
     i, s, (h1, h2) = int(num_states) + int(num_control_inputs), int(num_states), (int(hidden[0]), int(hidden[1]))
     return i * h1 + h1 + h1 * h2 + h2 + h2 * s + s
-
-
-class _MlpBatchEntries:
-    """the library as CtkMppiBatch's methods name it, answering with the MLP family's entry of the same signature"""
-
-    def __init__(self, lib):
-        self._lib = lib
-
-    def __getattr__(self, name):
-        if name.startswith("ctk_batch_"):
-            name = "ctk_mlp_batch_" + name[len("ctk_batch_"):]
-        elif name.startswith("ctk_problem_"):
-            name = "ctk_mlp_problem_" + name[len("ctk_problem_"):]
-        return getattr(self._lib, name)
 
 
 class CtkMppiMlpBatch(CtkMppiBatch):
@@ -1011,15 +1044,14 @@ class CtkMppiMlpBatch(CtkMppiBatch):
     steps only once it has weights.  predictor_hidden = (h1, h2): the hidden widths of all the batch's networks (default 32 / 32, at most
     32; narrower ones are embedded exactly).  CartPole only."""
 
+    _BATCH, _PROBLEM = "ctk_mlp_batch", "ctk_mlp_problem"
+
     def __init__(self, num_problems: int, *, seeds=None, predictor_hidden=None, environment: str = "CartPole", optimizer: str = "mppi",
                  predictor: str = "MLP", num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
                  period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
                  materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
                  num_control_inputs: int = None, generic_kernels: bool = False, **kw):
-        # what needs no device is checked before the library is asked for one
-        if int(num_problems) < 1:
-            raise ValueError(f"a batch holds at least one problem (num_problems == {num_problems})")
-        B = int(num_problems)
+        B = self._count(num_problems)
         if optimizer != "mppi":
             raise NotImplementedError(f"a batch steps MPPI controllers only (optimizer {optimizer!r}); the other optimizers run as CtkEngine")
         if predictor != "MLP":
@@ -1033,39 +1065,17 @@ class CtkMppiMlpBatch(CtkMppiBatch):
             raise ValueError(f"predictor_hidden must be two widths >= 1 (h1, h2), got {predictor_hidden!r}")
         if max(hidden) > 32:
             raise NotImplementedError(f"the MLP batch kernel holds 32 units per hidden layer (predictor_hidden {hidden}); wider networks run as CtkEngine")
-        if seeds is not None:
-            seeds = np.ascontiguousarray(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in np.asarray(seeds, dtype=object).reshape(-1)], np.uint64))
-            if seeds.size != B:
-                raise ValueError(f"seeds must have one entry per problem ({B}), got {seeds.size}")
-        lib, env_id = environment_library(environment)
-        lib = _MlpBatchEntries(lib)
-        S, Cn, self.param_names = environment_info(environment)
-        self.environment, self.S, self.C, self.B = environment, S, Cn, B
         self.predictor_hidden = hidden
-        self._wn = mlp_weight_count(S, Cn, hidden)
         if predictor_hidden is not None:
             kw = dict(kw, predictor_hidden1=hidden[0], predictor_hidden2=hidden[1])
-        cfg = _make_config("mppi", "MLP", env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
-                           action_low=action_low, action_high=action_high,
-                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
-                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
-                           global_rollout_offset=global_rollout_offset, num_states=S if num_states is None else num_states,
-                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs, generic_kernels=generic_kernels, **kw)
-        self._lib, self.cfg = lib, cfg
-        self.N, self.H = int(num_rollouts), int(mpc_horizon)
-        self._h = _H()
-        rc = lib.ctk_batch_create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
-        if rc != 0:
-            msg = lib.ctk_batch_last_error(None).decode()
-            self._h = _H()
-            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(msg)
-        self._per = int(lib.ctk_batch_samples_needed(self._h))
-        self._s = np.zeros((B, S), np.float32)
-        self._up = np.zeros((B, Cn), np.float32)
-        self._u = np.zeros((B, Cn), np.float32)
-        self._ids = np.zeros(B, np.int32)
-        self._s_p, self._up_p, self._u_p, self._ids_p = (a.ctypes.data for a in (self._s, self._up, self._u, self._ids))
-        self._step_fn = lib.ctk_batch_step
+        self._open(B, self._seeds(B, seeds), "mppi", "MLP", environment, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                   action_low=action_low, action_high=action_high,
+                   period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                   intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                   global_rollout_offset=global_rollout_offset, num_states=num_states, num_control_inputs=num_control_inputs,
+                   generic_kernels=generic_kernels, **kw)
+        self._per = int(self._b.samples_needed(self._h))
+        self._wn = mlp_weight_count(self.S, self.C, hidden)
 
     def weight_count(self) -> int:
         """floats of one problem's network (predictor_hidden's widths)"""
@@ -1092,86 +1102,39 @@ class CtkMppiMlpBatch(CtkMppiBatch):
 
 
 # ---- batched CEM (include/ctk_hip.h: ctk_cem_batch_*) ---------------------------------------------------------------------------------
-class CtkCemBatch:
+class CtkCemBatch(_CtkBatch):
     """Owns one ctk_cem_batch: num_problems independent plain-CEM controllers of ONE configuration (the CEM keywords of CtkEngine),
     stepped together by launches of one kernel.  Problem p behaves bit for bit like CtkEngine("cem", "ODE", seed=seeds[p], ...) given the
     same calls, set_param among them: set_problem_params gives every problem its own plant, cost weights and targets, set_param the same
     value to all.  seeds: one per problem (default seed + p)."""
+
+    _BATCH, _PROBLEM = "ctk_cem_batch", "ctk_cem_problem"
 
     def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "cem", predictor: str = "ODE",
                  num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
                  period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
                  materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
                  num_control_inputs: int = None, generic_kernels: bool = False, **kw):
-        # what needs no device is checked before the library is asked for one
-        if int(num_problems) < 1:
-            raise ValueError(f"a batch holds at least one problem (num_problems == {num_problems})")
-        B = int(num_problems)
+        B = self._count(num_problems)
         if optimizer != "cem":
             raise NotImplementedError(f"a CEM batch steps plain CEM controllers only (optimizer {optimizer!r}); MPPI has CtkMppiBatch, the CEM "
                                       "variants and the other optimizers run as CtkEngine")
         if predictor != "ODE":
             raise NotImplementedError(f"the batch kernel rolls out the analytic (ODE) predictor only (predictor {predictor!r}); "
                                       "network predictors run as CtkEngine")
-        if seeds is not None:
-            seeds = np.ascontiguousarray(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in np.asarray(seeds, dtype=object).reshape(-1)], np.uint64))
-            if seeds.size != B:
-                raise ValueError(f"seeds must have one entry per problem ({B}), got {seeds.size}")
-        unknown = set(kw) - set(_CONFIG_DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown engine arguments: {sorted(unknown)}")
-        lib, env_id = environment_library(environment)
-        S, Cn, self.param_names = environment_info(environment)
-        self.environment, self.S, self.C, self.B = environment, S, Cn, B
-        cfg = _make_config("cem", "ODE", env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
-                           action_low=action_low, action_high=action_high,
-                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
-                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
-                           global_rollout_offset=global_rollout_offset, num_states=S if num_states is None else num_states,
-                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs, generic_kernels=generic_kernels, **kw)
-        self._lib, self.cfg = lib, cfg
-        self.N, self.H, self.K = int(num_rollouts), int(mpc_horizon), int(cfg.cem_best_k)
-        self._h = _H()
-        rc = lib.ctk_cem_batch_create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
-        if rc != 0:
-            msg = lib.ctk_cem_batch_last_error(None).decode()
-            self._h = _H()
-            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(msg)
-        # preallocated argument buffers, as CtkEngine.step's: rows 0 .. n-1 are the stepped problems'
-        self._s = np.zeros((B, S), np.float32)
-        self._up = np.zeros((B, Cn), np.float32)
-        self._u = np.zeros((B, Cn), np.float32)
-        self._ids = np.zeros(B, np.int32)
-        self._s_p, self._up_p, self._u_p, self._ids_p = (a.ctypes.data for a in (self._s, self._up, self._u, self._ids))
-        self._step_fn = lib.ctk_cem_batch_step
-
-    def _check(self, rc: int):
-        if rc != 0:
-            msg = self._lib.ctk_cem_batch_last_error(self._h).decode()
-            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(f"[ctk {rc}] {msg}")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.ctk_cem_batch_destroy(self._h)
-            self._h = _H()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self):
-        return self.B
-
-    def _problem(self, problem: int) -> int:
-        if not 0 <= int(problem) < self.B:
-            raise ValueError(f"problem index {problem} is outside 0 .. {self.B - 1}")
-        return int(problem)
+        seeds = self._seeds(B, seeds)
+        self._known(kw)
+        self._open(B, seeds, "cem", "ODE", environment, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                   action_low=action_low, action_high=action_high,
+                   period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                   intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                   global_rollout_offset=global_rollout_offset, num_states=num_states, num_control_inputs=num_control_inputs,
+                   generic_kernels=generic_kernels, **kw)
+        self.K = int(self.cfg.cem_best_k)
 
     def samples_needed(self, problem: int = 0) -> int:
         """draws the NEXT step of `problem` consumes (its * N * H * C: a warm-up step after creation or reset is longer)"""
-        return int(self._lib.ctk_cem_batch_samples_needed(self._h, self._problem(problem)))
+        return int(self._b.samples_needed(self._h, self._problem(problem)))
 
     def step(self, S, samples=None, u_prev=None, ids=None) -> np.ndarray:
         """S [n, num_states], one row per stepped problem in the order of ids (None: all problems).  samples: None (device Philox), a
@@ -1187,21 +1150,7 @@ class CtkCemBatch:
             per = needs.pop()
             if not needs and (samples.size != n * per or (samples.ndim > 1 and samples.shape[0] != n)):
                 raise ValueError(f"step of {n} problems consumes {n} x {per} draws ([n, its, N, H, C]), got shape {tuple(samples.shape)}")
-        self._s[:n] = np.asarray(S).reshape(n, self.S)
-        up_p = None
-        if u_prev is not None:
-            self._up[:n] = np.asarray(u_prev).reshape(n, self.C)
-            up_p = self._up_p
-        ids_p = None
-        if idv is not None:
-            self._ids[:n] = idv
-            ids_p = self._ids_p
-        if samples is None:
-            sp, loc = None, LOC_NONE
-        elif type(samples) is int:
-            sp, loc = samples, LOC_DEVICE
-        else:
-            sp, loc = samples.ctypes.data, LOC_HOST
+        ids_p, up_p, sp, loc = self._step_args(n, idv, S, u_prev, samples)
         rc = self._step_fn(self._h, n, ids_p, self._s_p, up_p, sp, loc, self._u_p)
         self.last_u = self._u[:n].copy()
         if rc:
@@ -1210,76 +1159,20 @@ class CtkCemBatch:
 
     def reset(self, ids=None):
         idv = batch_ids(self.B, ids)
-        self._check(self._lib.ctk_cem_batch_reset(self._h, 0 if idv is None else idv.size, _ptr(idv)))
+        self._check(self._b.reset(self._h, 0 if idv is None else idv.size, _ptr(idv)))
 
     def read(self, name: str, problem: int) -> np.ndarray:
         N, H, S, Cn = self.N, self.H, self.S, self.C
-        shapes = {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn), "STD": (1, H, Cn), "BEST_IDX": (self.K,)}
-        if name not in shapes:
-            raise ValueError(f"a CEM batch has the buffers {sorted(shapes)}, not {name!r}")
-        out = np.empty(shapes[name], np.float32)
-        self._check(self._lib.ctk_cem_batch_read(self._h, self._problem(problem), BUFFERS[name], _ptr(out), out.size))
-        return out.astype(np.int64) if name == "BEST_IDX" else out
-
-    def read_all(self, name: str) -> np.ndarray:
-        return np.stack([self.read(name, p) for p in range(self.B)])
+        return self._read("a CEM batch", {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn), "STD": (1, H, Cn),
+                                          "BEST_IDX": (self.K,)}, name, problem)
 
     def get_state(self, problem: int) -> np.ndarray:
         """mu[H,C] | std[H,C] | u[C] | count of one problem (CtkEngine.get_state of a CEM engine)"""
-        buf = np.empty(2 * self.H * self.C + self.C + 1, np.float32)
-        self._check(self._lib.ctk_cem_batch_get_state(self._h, self._problem(problem), _ptr(buf), buf.size))
-        return buf
-
-    def set_state(self, problem: int, state):
-        st = _f32(state).ravel()
-        self._check(self._lib.ctk_cem_batch_set_state(self._h, self._problem(problem), _ptr(st), st.size))
-
-    def set_param(self, name: str, value: float):
-        self._check(self._lib.ctk_cem_batch_set_param(self._h, self.param_names.index(name), float(value)))
-
-    def get_param(self, name: str) -> float:
-        """the last value set_param gave the whole batch (the default before that); a problem's own value: get_problem_param"""
-        v = C.c_float()
-        self._check(self._lib.ctk_cem_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
-        return v.value
-
-    def set_problem_params(self, name: str, values, ids=None):
-        """parameter `name` of the problems in ids (None: all): values a scalar or [n], one per listed problem in the order of ids.  The
-        next step re-derives the constants of the problems touched; from the first call on the batch runs the per-problem form of its
-        kernel (params_differ, dominant_kernel)."""
-        pid, idv, n, vals = batch_param_args(self.param_names, self.B, name, values, ids)
-        self._check(self._lib.ctk_cem_problem_set_param(self._h, n, _ptr(idv), pid, _ptr(vals)))
-
-    def get_problem_param(self, name: str, problem: int) -> float:
-        if name not in self.param_names:
-            raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(self.param_names)})")
-        v = C.c_float()
-        if self._lib.ctk_cem_problem_get_param(self._h, self._problem(problem), self.param_names.index(name), C.byref(v)) != 0:
-            raise CtkError(f"ctk_cem_problem_get_param({problem}, {name!r}) failed")
-        return v.value
-
-    def get_problem_params(self, name: str) -> np.ndarray:
-        """[B] parameter `name` of every problem"""
-        return np.array([self.get_problem_param(name, p) for p in range(self.B)], np.float32)
-
-    def params_differ(self) -> int:
-        """1 once a set_problem_params has succeeded on this batch (sticky), else 0"""
-        return int(self._lib.ctk_cem_problem_params_differ(self._h))
-
-    def rng_position(self, problem: int) -> int:
-        v = C.c_uint32()
-        self._check(self._lib.ctk_cem_batch_rng_get_position(self._h, self._problem(problem), C.byref(v)))
-        return int(v.value)
-
-    def set_rng_position(self, problem: int, call: int):
-        self._check(self._lib.ctk_cem_batch_rng_set_position(self._h, self._problem(problem), int(call) & 0xFFFFFFFF))
-
-    def dominant_kernel(self) -> str:
-        return self._lib.ctk_cem_batch_dominant_kernel(self._h).decode()
+        return self._get_state(problem, 2 * self.H * self.C + self.C + 1)
 
 
 # ---- batched RPGD (include/ctk_hip.h: ctk_rpgd_batch_*) -------------------------------------------------------------------------------
-class CtkRpgdBatch:
+class CtkRpgdBatch(_CtkBatch):
     """Owns one ctk_rpgd_batch: num_problems independent RPGD controllers of ONE configuration (the RPGD keywords of CtkEngine) with at
     most 64 plans each, any subset of them stepped by ONE kernel launch: descent, keep-k selection and warm start of every listed problem.
     Problem p behaves bit for bit like CtkEngine("rpgd", "ODE", seed=seeds[p], generic_kernels=True, ...) given the same calls (reset,
@@ -1289,78 +1182,30 @@ class CtkRpgdBatch:
     CtkEngine runs with generic_kernels=False) has no batch form, and generic_kernels=False for CartPole is refused rather than
     silently differing from such an engine.  The other environments have template kernels only."""
 
+    _BATCH, _PROBLEM = "ctk_rpgd_batch", "ctk_rpgd_problem"
+
     def __init__(self, num_problems: int, *, environment: str = "CartPole", seeds=None, optimizer: str = "rpgd", predictor: str = "ODE",
                  num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
                  period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
                  materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
                  num_control_inputs: int = None, generic_kernels: bool = None, **kw):
-        # what needs no device is checked before the library is asked for one
-        if int(num_problems) < 1:
-            raise ValueError(f"a batch holds at least one problem (num_problems == {num_problems})")
-        B = int(num_problems)
+        B = self._count(num_problems)
         if optimizer != "rpgd":
             raise NotImplementedError(f"an RPGD batch steps RPGD controllers only (optimizer {optimizer!r}); MPPI has CtkMppiBatch, plain CEM "
                                       "CtkCemBatch, the gradient variant and the other optimizers run as CtkEngine")
         if predictor != "ODE":
             raise NotImplementedError(f"the batch kernel descends through the analytic (ODE) predictor only (predictor {predictor!r}); "
                                       "network predictors run as CtkEngine")
-        if seeds is not None:
-            seeds = np.ascontiguousarray(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in np.asarray(seeds, dtype=object).reshape(-1)], np.uint64))
-            if seeds.size != B:
-                raise ValueError(f"seeds must have one entry per problem ({B}), got {seeds.size}")
-        unknown = set(kw) - set(_CONFIG_DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown engine arguments: {sorted(unknown)}")
-        lib, env_id = environment_library(environment)
-        S, Cn, self.param_names = environment_info(environment)
-        self.environment, self.S, self.C, self.B = environment, S, Cn, B
-        cfg = _make_config("rpgd", "ODE", env_id, environment, Cn, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
-                           action_low=action_low, action_high=action_high,
-                           period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
-                           intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
-                           global_rollout_offset=global_rollout_offset, num_states=S if num_states is None else num_states,
-                           num_control_inputs=Cn if num_control_inputs is None else num_control_inputs,
-                           generic_kernels=True if generic_kernels is None else generic_kernels, **kw)
-        self._lib, self.cfg = lib, cfg
-        self.N, self.H, self.K = int(num_rollouts), int(mpc_horizon), int(cfg.opt_keep_k)
-        self._h = _H()
-        rc = lib.ctk_rpgd_batch_create(C.byref(cfg), B, _ptr(seeds), C.byref(self._h))
-        if rc != 0:
-            msg = lib.ctk_rpgd_batch_last_error(None).decode()
-            self._h = _H()
-            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(msg)
-        # preallocated argument buffers, as CtkEngine.step's: rows 0 .. n-1 are the stepped problems'
-        self._s = np.zeros((B, S), np.float32)
-        self._up = np.zeros((B, Cn), np.float32)
-        self._u = np.zeros((B, Cn), np.float32)
-        self._ids = np.zeros(B, np.int32)
-        self._s_p, self._up_p, self._u_p, self._ids_p = (a.ctypes.data for a in (self._s, self._up, self._u, self._ids))
-        self._step_fn = lib.ctk_rpgd_batch_step
-        self._need_fn = lib.ctk_rpgd_batch_samples_needed
-
-    def _check(self, rc: int):
-        if rc != 0:
-            msg = self._lib.ctk_rpgd_batch_last_error(self._h).decode()
-            raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(f"[ctk {rc}] {msg}")
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.ctk_rpgd_batch_destroy(self._h)
-            self._h = _H()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self):
-        return self.B
-
-    def _problem(self, problem: int) -> int:
-        if not 0 <= int(problem) < self.B:
-            raise ValueError(f"problem index {problem} is outside 0 .. {self.B - 1}")
-        return int(problem)
+        seeds = self._seeds(B, seeds)
+        self._known(kw)
+        self._open(B, seeds, "rpgd", "ODE", environment, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                   action_low=action_low, action_high=action_high,
+                   period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                   intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                   global_rollout_offset=global_rollout_offset, num_states=num_states, num_control_inputs=num_control_inputs,
+                   generic_kernels=True if generic_kernels is None else generic_kernels, **kw)
+        self.K = int(self.cfg.opt_keep_k)
+        self._need_fn = self._b.samples_needed
 
     def samples_needed(self, problem: int = 0) -> int:
         """draws the NEXT step of `problem` consumes: (N - opt_keep_k) * P * C when it resamples (count % resamp_per == 0), else 0"""
@@ -1378,23 +1223,15 @@ class CtkRpgdBatch:
         numbers and changes nothing.  u_prev [n, C] or None (every problem's own last output).  Returns u [n, C].  A listed problem that
         was never reset: CtkError naming it, nothing is launched."""
         idv, n, _ = batch_step_args(self.B, self.S, self.C, 0, S, None, u_prev, ids)       # ids, states, u_prev
-        self._s[:n] = np.asarray(S).reshape(n, self.S)
-        up_p = None
-        if u_prev is not None:
-            self._up[:n] = np.asarray(u_prev).reshape(n, self.C)
-            up_p = self._up_p
-        ids_p = None
-        if idv is not None:
-            self._ids[:n] = idv
-            ids_p = self._ids_p
-        if samples is None:
-            sp, cnt, loc = None, 0, LOC_NONE
-        elif type(samples) is int:     # a device buffer has no size of its own: what the listed problems draw
-            sp, loc = samples, LOC_DEVICE
-            cnt = sum(self.samples_needed(p) for p in (range(self.B) if idv is None else idv.tolist()))
-        else:
+        if samples is not None and type(samples) is not int:
             samples = _f32(samples)
-            sp, cnt, loc = samples.ctypes.data, samples.size, LOC_HOST
+        ids_p, up_p, sp, loc = self._step_args(n, idv, S, u_prev, samples)
+        if sp is None:
+            cnt = 0
+        elif loc == LOC_HOST:
+            cnt = samples.size
+        else:                          # a device buffer has no size of its own: what the listed problems draw
+            cnt = sum(self.samples_needed(p) for p in (range(self.B) if idv is None else idv.tolist()))
         rc = self._step_fn(self._h, n, ids_p, self._s_p, up_p, sp, cnt, loc, self._u_p)
         if rc:
             self._check(rc)
@@ -1415,20 +1252,12 @@ class CtkRpgdBatch:
             if draws.size != n * self.samples_needed_reset():
                 raise ValueError(f"reset of {n} problems consumes {n} x {self.samples_needed_reset()} draws ([n, N, P, C]), got shape {tuple(draws.shape)}")
             dp, loc = draws.ctypes.data, LOC_HOST
-        self._check(self._lib.ctk_rpgd_batch_reset(self._h, 0 if idv is None else idv.size, _ptr(idv), dp, loc))
+        self._check(self._b.reset(self._h, 0 if idv is None else idv.size, _ptr(idv), dp, loc))
 
     def read(self, name: str, problem: int) -> np.ndarray:
         N, H, Cn = self.N, self.H, self.C
-        shapes = {"Q": (N, H, Cn), "J": (N,), "U_NOM": (1, H, Cn), "PLAN": (N, H, Cn), "ADAM_M": (N, H, Cn), "ADAM_V": (N, H, Cn),
-                  "AGES": (N,), "AGES_LOGGED": (N,), "BEST_IDX": (self.K,)}
-        if name not in shapes:
-            raise ValueError(f"an RPGD batch has the buffers {sorted(shapes)}, not {name!r}")
-        out = np.empty(shapes[name], np.float32)
-        self._check(self._lib.ctk_rpgd_batch_read(self._h, self._problem(problem), BUFFERS[name], _ptr(out), out.size))
-        return out.astype(np.int64) if name == "BEST_IDX" else out
-
-    def read_all(self, name: str) -> np.ndarray:
-        return np.stack([self.read(name, p) for p in range(self.B)])
+        return self._read("an RPGD batch", {"Q": (N, H, Cn), "J": (N,), "U_NOM": (1, H, Cn), "PLAN": (N, H, Cn), "ADAM_M": (N, H, Cn),
+                                            "ADAM_V": (N, H, Cn), "AGES": (N,), "AGES_LOGGED": (N,), "BEST_IDX": (self.K,)}, name, problem)
 
     def state_size(self) -> int:
         return 3 * self.N * self.H * self.C + self.N + self.C + 2
@@ -1443,54 +1272,5 @@ class CtkRpgdBatch:
 
     def get_state(self, problem: int) -> np.ndarray:
         """population, Adam m, Adam v [N,H,C] | ages [N] | u [C] | adam_step | count of one problem (CtkEngine.get_state of an RPGD engine)"""
-        buf = np.empty(self.state_size(), np.float32)
-        self._check(self._lib.ctk_rpgd_batch_get_state(self._h, self._problem(problem), _ptr(buf), buf.size))
-        return buf
+        return self._get_state(problem, self.state_size())
 
-    def set_state(self, problem: int, state):
-        st = _f32(state).ravel()
-        self._check(self._lib.ctk_rpgd_batch_set_state(self._h, self._problem(problem), _ptr(st), st.size))
-
-    def set_param(self, name: str, value: float):
-        """parameter `name` of every problem (that column of every problem's table; the other parameters stay per problem)"""
-        self._check(self._lib.ctk_rpgd_batch_set_param(self._h, self.param_names.index(name), float(value)))
-
-    def get_param(self, name: str) -> float:
-        """the last value set_param gave the whole batch (the default before that); a problem's own value: get_problem_param"""
-        v = C.c_float()
-        self._check(self._lib.ctk_rpgd_batch_get_param(self._h, self.param_names.index(name), C.byref(v)))
-        return v.value
-
-    def set_problem_params(self, name: str, values, ids=None):
-        """parameter `name` of the problems in ids (None: all): values a scalar or [n], one per listed problem in the order of ids.  The
-        next step re-derives the constants of the problems touched; from the first call on the batch runs the per-problem form of its
-        kernel (params_differ, dominant_kernel)."""
-        pid, idv, n, vals = batch_param_args(self.param_names, self.B, name, values, ids)
-        self._check(self._lib.ctk_rpgd_problem_set_param(self._h, n, _ptr(idv), pid, _ptr(vals)))
-
-    def get_problem_param(self, name: str, problem: int) -> float:
-        if name not in self.param_names:
-            raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(self.param_names)})")
-        v = C.c_float()
-        if self._lib.ctk_rpgd_problem_get_param(self._h, self._problem(problem), self.param_names.index(name), C.byref(v)) != 0:
-            raise CtkError(f"ctk_rpgd_problem_get_param({problem}, {name!r}) failed")
-        return v.value
-
-    def get_problem_params(self, name: str) -> np.ndarray:
-        """[B] parameter `name` of every problem"""
-        return np.array([self.get_problem_param(name, p) for p in range(self.B)], np.float32)
-
-    def params_differ(self) -> int:
-        """1 once a set_problem_params has succeeded on this batch (sticky), else 0"""
-        return int(self._lib.ctk_rpgd_problem_params_differ(self._h))
-
-    def rng_position(self, problem: int) -> int:
-        v = C.c_uint32()
-        self._check(self._lib.ctk_rpgd_batch_rng_get_position(self._h, self._problem(problem), C.byref(v)))
-        return int(v.value)
-
-    def set_rng_position(self, problem: int, call: int):
-        self._check(self._lib.ctk_rpgd_batch_rng_set_position(self._h, self._problem(problem), int(call) & 0xFFFFFFFF))
-
-    def dominant_kernel(self) -> str:
-        return self._lib.ctk_rpgd_batch_dominant_kernel(self._h).decode()

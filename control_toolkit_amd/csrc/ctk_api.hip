@@ -2402,60 +2402,37 @@ int ctk_log_read(ctk_handle* h, int which, size_t first_step, size_t n_steps, fl
 }  // extern "C"
 
 // =============================================================================================
-// Batched MPPI (include/ctk_hip.h: ctk_batch_*): B independent problems of one configuration, stepped by ONE launch of
-// ctk_mppi_batch<ENV, LOG> per step (ctk_mppi.hip).  One allocation per buffer kind with a problem stride — no handles inside.
-// Per-problem host state is what a handle keeps: the sequence number of its next step, its Philox position, which u_nom buffer is current,
-// its parameter table.  While no ctk_problem_set_param has succeeded the launches take the constants of the shared table by value; from
-// then on (`differ`, sticky) they read every problem's constants from d_k, which ctk_batch_step refreshes for the problems marked dirty.
+// The host core of the batch families (ctk_batch, ctk_cem_batch, ctk_rpgd_batch derive from it; ctk_mlp_batch holds a ctk_batch): what
+// every family keeps per batch and per problem, and the one copy of what they all do with it — the id checks, the staging of host draws,
+// the step records' common fields, the completion poll, the read-out of u, the parameter tables and the Philox positions.  Plain data and
+// free functions, private to this file: a family's own entry points pass their name (`who`) for the messages.
 // =============================================================================================
-struct ctk_batch {
+namespace {
+
+struct BatchCore {
     ctk_config cfg{};
-    int B = 0, N = 0, H = 0, P = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, PC = 0, blocks = 0;
-    float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (ctk_batch_set_param / get_param)
+    int B = 0, N = 0, H = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0;
+    float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (*_batch_set_param / get_param)
     std::vector<float> pparams;             // [B][CTK_MAX_PARAMS] every problem's own table
-    std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived into h_k / copied to d_k
-    bool differ = false;                    // a ctk_problem_set_param has succeeded: the per-problem form of the kernel from now on
-    size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes per problem in h_k / d_k
-    unsigned char* h_k = nullptr;           // pinned [B][kstride] derived constants, the staging of the copy to d_k
-    unsigned char* d_k = nullptr;           // [B][kstride]
-    MppiK mk{};
+    std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived (MPPI: and copied to d_k)
+    bool differ = false;                    // a *_problem_set_param has succeeded: the per-problem form of the kernel from now on
+    size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes of one problem's derived constants
     hipStream_t stream = nullptr;
-    int max_per_launch = 1;                 // problems per launch: half the device's CUs (ctk_batch_create), a diagnostic switch may lower it
-    InterpEntry* d_interp = nullptr;
-    float* d_J = nullptr;                   // [B][N]
-    float* d_Q = nullptr;                   // [B][N,H,C]
-    float* d_traj = nullptr;                // [B][N,H+1,S] (materialize_trajectories)
-    float* d_parts = nullptr;               // [B][blocks][2+PC]
-    unsigned long long* d_ll = nullptr;     // [B][blocks][2+PC] {value, seq} words
-    float* d_unom = nullptr;                // [B][2][H,C]
     float* d_u = nullptr;                   // [B][CTK_MAX_INPUTS]
     float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
     float* h_u_dev = nullptr;
-    CtkBatchDesc* d_desc = nullptr;         // [B]
-    CtkBatchStep* h_steps = nullptr;        // pinned [B]: the step records of the step being issued
-    CtkBatchStep* d_steps = nullptr;        // [B]
     float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
-    std::vector<uint32_t> seq, call;
-    std::vector<int> cur;
+    std::vector<uint32_t> seq, call;        // [B] the sequence number of the problem's next step, its Philox position
     std::string err, dominant;
-    // the MLP family (include/ctk_hip.h: ctk_mlp_batch_*): the same struct with a predictor field and per-problem weight tables
-    int pred = CTK_PRED_ODE;                // CTK_PRED_MLP: ctk_mppi_batch_mlp<LOG> / ctk_mppi_batch_mlp_pp<LOG>
-    int hid1 = 32, hid2 = 32;               // the network's hidden widths (cfg.predictor_hidden1/2, 0 = 32): narrower ones are embedded
-    size_t wtab = 0;                        // floats of one per-lane weight table (ctk_mppi_batch_mlp_table_floats)
-    float* d_w = nullptr;                   // [B][wtab] problem p's table, in the layout of a handle's d_wperm
-    float* h_w = nullptr;                   // pinned [B][wtab]: the staging of ONE transfer per weight call
-    std::vector<unsigned char> have_w;      // [B] the problem has received weights
-    size_t unom_stride() const { return (size_t)2 * HC; }
-    float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
+    bool mlp_names = false;                 // the MLP family: its messages carry its own entry points' names (bfail)
+    float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
     float* slot(int p) const { return h_u + (size_t)p * 16; }
     float* table(int p) { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
     const float* table(int p) const { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
 };
 
-namespace {
-
-// the MLP family runs the code of this one; its messages carry its own entry points' names (ctk_batch_x -> ctk_mlp_batch_x,
-// ctk_problem_x -> ctk_mlp_problem_x), substituted here where a message is stored, so that this family's texts are the literals below
+// the MLP family runs the MPPI family's code; its messages carry its own entry points' names (ctk_batch_x -> ctk_mlp_batch_x,
+// ctk_problem_x -> ctk_mlp_problem_x), substituted here where a message is stored, so that the MPPI family's texts are the literals
 std::string mlp_family_names(std::string msg) {
     for (const char* from : {"ctk_batch_", "ctk_problem_"}) {
         const std::string to = std::string("ctk_mlp_") + (from + 4);
@@ -2463,8 +2440,8 @@ std::string mlp_family_names(std::string msg) {
     }
     return msg;
 }
-int bfail(ctk_batch* b, int code, const std::string& msg) {
-    if (b) b->err = b->pred == CTK_PRED_MLP ? mlp_family_names(msg) : msg; else g_create_error = msg;
+int bfail(BatchCore* b, int code, const std::string& msg) {
+    if (b) b->err = b->mlp_names ? mlp_family_names(msg) : msg; else g_create_error = msg;
     return code;
 }
 #define BHIP_TRY(b, expr)                                                                       \
@@ -2474,8 +2451,21 @@ int bfail(ctk_batch* b, int code, const std::string& msg) {
             return bfail((b), CTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
     } while (0)
 
-// the problems a call addresses: ids[0..n) strictly ascending, or all of them (ids == NULL)
-int batch_ids(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, int* n_out) {
+// the fields of the core that depend on the configuration alone (every family's create, after its refusals)
+void batch_core_init(BatchCore* b, const ctk_config* cfg, const EnvInfo* einfo, int n_problems) {
+    b->cfg = *cfg;
+    b->B = n_problems; b->N = cfg->num_rollouts; b->H = cfg->mpc_horizon;
+    b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = b->H * b->C;
+    default_params(b->env, b->params);
+    b->pparams.resize((size_t)n_problems * CTK_MAX_PARAMS);
+    for (int p = 0; p < n_problems; ++p) std::memcpy(b->table(p), b->params, sizeof(b->params));
+    b->dirty.assign((size_t)n_problems, 1);            // nothing derived yet: the per-problem form derives what it steps (MPPI: all of them)
+    b->kstride = ctk_mppi_batch_k_stride(b->env);
+    b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u);
+}
+
+// the problems a call addresses: ids[0..n) ascending without repeats, or all of them (ids == NULL)
+int batch_ids(BatchCore* b, const char* who, int n_ids, const int32_t* ids, int* n_out) {
     if (!ids) { *n_out = b->B; return CTK_OK; }
     if (n_ids < 1 || n_ids > b->B) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": n_ids must be 1 .. " + std::to_string(b->B) + " (the batch size)");
     for (int j = 0; j < n_ids; ++j) {
@@ -2486,23 +2476,198 @@ int batch_ids(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, int*
     *n_out = n_ids;
     return CTK_OK;
 }
-int batch_problem(ctk_batch* b, const char* who, int p) {
+int batch_problem(BatchCore* b, const char* who, int p) {
     if (p < 0 || p >= b->B) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(p) + " is outside 0 .. " + std::to_string(b->B - 1));
     return CTK_OK;
 }
 
-// the shared template of a launch's RolloutArgs (make_args without what the step records and descriptors supply)
-RolloutArgs batch_args(const ctk_batch* b) {
+// what every family's launches share of RolloutArgs (make_args of a handle without what the step records and descriptors supply); P,
+// p_magic, interp and identity_interp are the family's
+RolloutArgs batch_common_args(const BatchCore* b) {
     RolloutArgs a{};
     for (int c = 0; c < b->C; ++c) { a.lo[c] = b->cfg.action_low[c]; a.hi[c] = b->cfg.action_high[c]; }
     a.C = b->C;
-    a.N = b->N; a.H = b->H; a.P = b->P;
-    a.p_magic = ctk_magic_of(b->P);
-    a.identity_interp = (b->cfg.period_interpolation_inducing_points == 1 && b->P == b->H) ? 1 : 0;
+    a.N = b->N; a.H = b->H;
     a.inv_Hp1 = 1.0f / (float)(b->H + 1);
-    a.interp = b->d_interp;
     a.stream_id = 0;
     a.global_row0 = b->cfg.global_rollout_offset;
+    return a;
+}
+
+// host-supplied draws into the staging buffer (resolve_samples of a handle): n floats
+int batch_stage(BatchCore* b, const float* src, size_t n) {
+    if (n > b->samples_cap) {
+        if (b->d_samples) BHIP_TRY(b, hipFree(b->d_samples));
+        b->d_samples = nullptr; b->samples_cap = 0;
+        BHIP_TRY(b, hipMalloc((void**)&b->d_samples, n * sizeof(float)));
+        b->samples_cap = n;
+    }
+    BHIP_TRY(b, hipMemcpyAsync(b->d_samples, src, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    return CTK_OK;
+}
+
+// row j of the call's states and previous inputs into a step record: they travel with the records
+template <class Rec>
+void batch_record_io(const BatchCore* b, Rec& q, int j, const float* s, const float* u_prev) {
+    q.dev_uprev = u_prev ? 0u : 1u;
+    for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
+    for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
+}
+
+// The step records of the CEM and RPGD steps to the device, n of `rec` bytes each.  In the per-problem form the constants of the n
+// problems lie right behind the n records, in the records' order, so that ONE transfer carries both (*d_ksteps: where they land, else
+// NULL).  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses (ctk_set_param ->
+// derive_constants / Env<>::derive at its launch); kcache is by problem id, the block behind the records by launch order.
+hipError_t batch_send_records(BatchCore* b, unsigned char* kcache, const int32_t* ids, int n, size_t rec, void* h_steps, void* d_steps,
+                              const unsigned char** d_ksteps) {
+    size_t bytes = (size_t)n * rec;
+    *d_ksteps = nullptr;
+    if (b->differ) {
+        unsigned char* h_k = static_cast<unsigned char*>(h_steps) + bytes;
+        for (int j = 0; j < n; ++j) {
+            const size_t z = (size_t)(ids ? ids[j] : j);
+            if (b->dirty[z]) {
+                ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, kcache + z * b->kstride);
+                b->dirty[z] = 0;
+            }
+            std::memcpy(h_k + (size_t)j * b->kstride, kcache + z * b->kstride, b->kstride);
+        }
+        *d_ksteps = static_cast<const unsigned char*>(d_steps) + bytes;
+        bytes += (size_t)n * b->kstride;
+    }
+    const hipError_t e = hipMemcpyAsync(d_steps, h_steps, bytes, hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess && b->differ)                  // nothing reached the device: derive and copy again at the next step
+        for (int j = 0; j < n; ++j) b->dirty[(size_t)(ids ? ids[j] : j)] = 1;
+    return e;
+}
+
+// completion of a step: the {u, seq} store of each of the first `launched` listed problems landing in its pinned slot (finish_step's
+// bounded spin: one budget of pauses for the whole call, then one synchronise, then give up).  Returns the problems that never published.
+std::string batch_poll(BatchCore* b, const int32_t* ids, int launched) {
+    bool synced = false;
+    int spins = 0;
+    std::string late;
+    for (int j = 0; j < launched; ++j) {
+        const int p = ids ? ids[j] : j;
+        const uint32_t want = b->seq[(size_t)p];
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 1;
+        while (*slot != want) {
+            if (!synced && ++spins < 4000000) { __builtin_ia32_pause(); continue; }
+            if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
+            break;
+        }
+        if (*slot != want) late += (late.empty() ? "" : ", ") + std::to_string(p);
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return late;
+}
+
+// u of problem p from its slot into row j of u_out (publish_u_vec: u[0] beside seq, the other inputs behind the error words)
+void batch_read_u(const BatchCore* b, int p, int j, float* u_out) {
+    if (!u_out) return;
+    volatile float* sl = reinterpret_cast<volatile float*>(b->slot(p));
+    u_out[(size_t)j * b->C] = sl[0];
+    for (int c = 1; c < b->C; ++c) u_out[(size_t)j * b->C + c] = sl[4 + c];
+}
+
+// ---- the parameter tables and Philox positions: the bodies of every family's *_set_param ... *_rng_set_position ----
+int batch_param_id(BatchCore* b, const char* who, int id) {
+    if (id < 0 || id >= env_info(b->env)->n_params) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown parameter id for this environment");
+    return CTK_OK;
+}
+int batch_set_param(BatchCore* b, const char* who, int id, float value) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_param_id(b, who, id)) return rc;
+    b->params[id] = value;                             // the shared table: the shared form derives its constants from it at each launch
+    for (int p = 0; p < b->B; ++p) { b->table(p)[id] = value; b->dirty[(size_t)p] = 1; }   // column id of every problem; the other ids stay
+    return CTK_OK;
+}
+int batch_get_param(const BatchCore* b, int id, float* value) {
+    if (!b || !value || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->params[id];
+    return CTK_OK;
+}
+// *flipped: this call turned `differ` on, the family names its per-problem kernel in `dominant`
+int batch_problem_set_param(BatchCore* b, const char* who, int n_ids, const int32_t* ids, int id, const float* values, bool* flipped) {
+    *flipped = false;
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (int rc = batch_param_id(b, who, id)) return rc;
+    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL values (one value per listed problem)");
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        b->table(p)[id] = values[j];
+        b->dirty[(size_t)p] = 1;                       // derived at a later step (MPPI: the next one, CEM and RPGD: the problem's next one)
+    }
+    *flipped = !b->differ;
+    b->differ = true;                                  // sticky: the tables are never compared again
+    return CTK_OK;
+}
+int batch_problem_get_param(const BatchCore* b, int problem, int id, float* value) {
+    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->table(problem)[id];
+    return CTK_OK;
+}
+int batch_params_differ(const BatchCore* b) { return b && b->differ ? 1 : 0; }
+int batch_rng_get_position(const BatchCore* b, int problem, uint32_t* call) {
+    if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *call = b->call[(size_t)problem];
+    return CTK_OK;
+}
+int batch_rng_set_position(BatchCore* b, const char* who, int problem, uint32_t call) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, who, problem)) return rc;
+    b->call[(size_t)problem] = call;
+    return CTK_OK;
+}
+
+}  // namespace
+
+// =============================================================================================
+// Batched MPPI (include/ctk_hip.h: ctk_batch_*): B independent problems of one configuration, stepped by ONE launch of
+// ctk_mppi_batch<ENV, LOG> per step (ctk_mppi.hip).  One allocation per buffer kind with a problem stride — no handles inside.
+// Per-problem host state is what a handle keeps: the sequence number of its next step, its Philox position, which u_nom buffer is current,
+// its parameter table.  While no ctk_problem_set_param has succeeded the launches take the constants of the shared table by value; from
+// then on (`differ`, sticky) they read every problem's constants from d_k, which ctk_batch_step refreshes for the problems marked dirty.
+// =============================================================================================
+struct ctk_batch : BatchCore {
+    int P = 0, PC = 0, blocks = 0;
+    unsigned char* h_k = nullptr;           // pinned [B][kstride] derived constants, the staging of the copy to d_k
+    unsigned char* d_k = nullptr;           // [B][kstride]
+    MppiK mk{};
+    int max_per_launch = 1;                 // problems per launch: half the device's CUs (ctk_batch_create), a diagnostic switch may lower it
+    InterpEntry* d_interp = nullptr;
+    float* d_J = nullptr;                   // [B][N]
+    float* d_Q = nullptr;                   // [B][N,H,C]
+    float* d_traj = nullptr;                // [B][N,H+1,S] (materialize_trajectories)
+    float* d_parts = nullptr;               // [B][blocks][2+PC]
+    unsigned long long* d_ll = nullptr;     // [B][blocks][2+PC] {value, seq} words
+    float* d_unom = nullptr;                // [B][2][H,C]
+    CtkBatchDesc* d_desc = nullptr;         // [B]
+    CtkBatchStep* h_steps = nullptr;        // pinned [B]: the step records of the step being issued
+    CtkBatchStep* d_steps = nullptr;        // [B]
+    std::vector<int> cur;
+    // the MLP family (include/ctk_hip.h: ctk_mlp_batch_*): the same struct with a predictor field and per-problem weight tables
+    int pred = CTK_PRED_ODE;                // CTK_PRED_MLP: ctk_mppi_batch_mlp<LOG> / ctk_mppi_batch_mlp_pp<LOG>
+    int hid1 = 32, hid2 = 32;               // the network's hidden widths (cfg.predictor_hidden1/2, 0 = 32): narrower ones are embedded
+    size_t wtab = 0;                        // floats of one per-lane weight table (ctk_mppi_batch_mlp_table_floats)
+    float* d_w = nullptr;                   // [B][wtab] problem p's table, in the layout of a handle's d_wperm
+    float* h_w = nullptr;                   // pinned [B][wtab]: the staging of ONE transfer per weight call
+    std::vector<unsigned char> have_w;      // [B] the problem has received weights
+    size_t unom_stride() const { return (size_t)2 * HC; }
+    float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
+};
+
+namespace {
+
+// the shared template of a launch's RolloutArgs (make_args without what the step records and descriptors supply)
+RolloutArgs batch_args(const ctk_batch* b) {
+    RolloutArgs a = batch_common_args(b);
+    a.P = b->P;
+    a.p_magic = ctk_magic_of(b->P);
+    a.identity_interp = (b->cfg.period_interpolation_inducing_points == 1 && b->P == b->H) ? 1 : 0;
+    a.interp = b->d_interp;
     return a;
 }
 
@@ -2615,15 +2780,10 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
     hipDeviceProp_t prop;
     if (int rc = probe_device(who, cfg->device, &prop)) return rc;
 
+    batch_core_init(b, cfg, einfo, n_problems);        // dirty: no constants in d_k yet, the first step of the per-problem form derives them all
+    b->mlp_names = mlp;
     b->pred = pred; b->hid1 = hw1; b->hid2 = hw2;
-    b->cfg = *cfg;
-    b->B = n_problems; b->N = N; b->H = H; b->P = P; b->blocks = blocks;
-    b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = H * b->C; b->PC = P * b->C;
-    default_params(b->env, b->params);
-    b->pparams.resize((size_t)n_problems * CTK_MAX_PARAMS);
-    for (int p = 0; p < n_problems; ++p) std::memcpy(b->table(p), b->params, sizeof(b->params));
-    b->dirty.assign((size_t)n_problems, 1);            // no constants in d_k yet: the first step of the per-problem form derives them all
-    b->kstride = ctk_mppi_batch_k_stride(b->env);
+    b->P = P; b->PC = P * b->C; b->blocks = blocks;
     b->mk = mppi_constants(b->cfg);
     // Progress: the only workgroup of a launch that ever waits is block 0 of a problem, for workgroups of its own problem.  With at most
     // CUs / 2 problems in a launch the waiting workgroups cannot fill the machine (every CU holds at least one workgroup of this kernel),
@@ -2633,7 +2793,7 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
         const int v = std::atoi(e);
         if (v >= 1 && v < b->max_per_launch) b->max_per_launch = v;
     }
-    b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u); b->cur.assign((size_t)n_problems, 0);
+    b->cur.assign((size_t)n_problems, 0);
     b->dominant = mlp ? ctk_mppi_batch_mlp_name(cfg->materialize_trajectories != 0) : ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
     if (mlp) { b->wtab = ctk_mppi_batch_mlp_table_floats(); b->have_w.assign((size_t)n_problems, 0); }
 
@@ -2716,20 +2876,14 @@ int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, 
     if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
     int n = 0;
     if (int rc = batch_ids(b, "ctk_batch_step", n_ids, ids, &n)) return rc;
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // by history: ahead of the check of `samples` here, behind it in the CEM and RPGD steps
     const size_t per = (size_t)b->N * b->PC;
     const float* d_s = nullptr;                        // draws of the step's first problem; row j follows at j * per
     if (samples_loc != CTK_LOC_NONE) {
         if (samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
         if (samples_loc == CTK_LOC_DEVICE) d_s = samples;
         else if (samples_loc == CTK_LOC_HOST) {
-            if ((size_t)n * per > b->samples_cap) {
-                if (b->d_samples) BHIP_TRY(b, hipFree(b->d_samples));
-                b->d_samples = nullptr; b->samples_cap = 0;
-                BHIP_TRY(b, hipMalloc((void**)&b->d_samples, (size_t)n * per * sizeof(float)));
-                b->samples_cap = (size_t)n * per;
-            }
-            BHIP_TRY(b, hipMemcpyAsync(b->d_samples, samples, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice, b->stream));
+            if (int rc = batch_stage(b, samples, (size_t)n * per)) return rc;
             d_s = b->d_samples;
         } else return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
     }
@@ -2738,10 +2892,9 @@ int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, 
         const int p = ids ? ids[j] : j;
         CtkBatchStep& q = b->h_steps[j];
         q.id = p; q.seq = b->seq[(size_t)p]; q.call = b->call[(size_t)p]; q.cur = (uint32_t)b->cur[(size_t)p];
-        q.dev_uprev = u_prev ? 0u : 1u; q.pad = 0u;
+        q.pad = 0u;
         q.samples = d_s ? d_s + (size_t)j * per : nullptr;
-        for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
-        for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
+        batch_record_io(b, q, j, s, u_prev);
     }
     hipError_t le = b->differ ? batch_flush_constants(b) : hipSuccess;          // the constants' transfer goes ahead of the step records'
     if (le == hipSuccess) le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkBatchStep), hipMemcpyHostToDevice, b->stream);
@@ -2759,38 +2912,20 @@ int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, 
         if (le == hipSuccess) launched += cnt;
     }
     for (int j = 0; j < launched; ++j) b->cur[(size_t)b->h_steps[j].id] ^= 1;
-    // completion: every launched problem's {u, seq} store landing in its pinned slot (finish_step's bounded spin, one budget for all)
-    bool synced = false;
-    int spins = 0;
-    std::string late, timed_out;
-    for (int j = 0; j < launched; ++j) {
-        const int p = b->h_steps[j].id;
-        const uint32_t want = b->seq[(size_t)p];
-        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 1;
-        while (*slot != want) {
-            if (!synced && ++spins < 4000000) { __builtin_ia32_pause(); continue; }
-            if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
-            break;
-        }
-        if (*slot != want) late += (late.empty() ? "" : ", ") + std::to_string(p);
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    const std::string late = batch_poll(b, ids, launched);
+    std::string timed_out;
     for (int j = 0; j < n; ++j) {
         const int p = b->h_steps[j].id;
-        ++b->seq[(size_t)p];                           // every launch attempt consumes its sequence number (guarded())
+        ++b->seq[(size_t)p];                           // every listed problem, launched or not, consumes its sequence number (guarded()); as CEM, RPGD differs on purpose
         if (j >= launched) continue;
-        ++b->call[(size_t)p];
-        volatile float* sl = reinterpret_cast<volatile float*>(b->slot(p));
-        if (u_out) {
-            u_out[(size_t)j * b->C] = sl[0];
-            for (int c = 1; c < b->C; ++c) u_out[(size_t)j * b->C + c] = sl[4 + c];   // publish_u_vec
-        }
-        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;
+        ++b->call[(size_t)p];                          // by history: for every launched problem, published or not (CEM and RPGD: only if its slot shows the step's seq)
+        batch_read_u(b, p, j, u_out);
+        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;   // the hand-off's error word (MPPI and CEM; RPGD has none)
         if (errw[0]) { errw[0] = 0; timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(p); }
     }
     if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_step: ") + hipGetErrorString(le));
     if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_step: the step finished without publishing the result of problem(s) " + late);
-    if (!timed_out.empty())
+    if (!timed_out.empty())                            // this family's text alone says "their outputs are NaN"
         return bfail(b, CTK_ERR_STATE, "ctk_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
                      "; their outputs are NaN, the other problems' outputs are valid and written");
     return CTK_OK;
@@ -2849,59 +2984,19 @@ int ctk_batch_set_state(ctk_batch* b, int problem, const float* src, size_t n) {
     return CTK_OK;
 }
 
-int ctk_batch_set_param(ctk_batch* b, int id, float value) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (id < 0 || id >= env_info(b->env)->n_params) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_set_param: unknown parameter id for this environment");
-    b->params[id] = value;                             // the shared table: the shared form derives its constants from it at each launch
-    for (int p = 0; p < b->B; ++p) { b->table(p)[id] = value; b->dirty[(size_t)p] = 1; }   // column id of every problem; the other ids stay
-    return CTK_OK;
-}
-
-int ctk_batch_get_param(const ctk_batch* b, int id, float* value) {
-    if (!b || !value || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
-    *value = b->params[id];
-    return CTK_OK;
-}
-
+int ctk_batch_set_param(ctk_batch* b, int id, float value) { return batch_set_param(b, "ctk_batch_set_param", id, value); }
+int ctk_batch_get_param(const ctk_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
 int ctk_problem_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = batch_ids(b, "ctk_problem_set_param", n_ids, ids, &n)) return rc;
-    if (id < 0 || id >= env_info(b->env)->n_params) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_problem_set_param: unknown parameter id for this environment");
-    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_problem_set_param: NULL values (one value per listed problem)");
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        b->table(p)[id] = values[j];
-        b->dirty[(size_t)p] = 1;
-    }
-    if (!b->differ) {                                  // sticky: the tables are never compared again
-        b->differ = true;
-        b->dominant = b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
-                                              : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
-    }
-    return CTK_OK;
+    bool flipped = false;
+    const int rc = batch_problem_set_param(b, "ctk_problem_set_param", n_ids, ids, id, values, &flipped);
+    if (flipped) b->dominant = b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
+                                                       : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    return rc;
 }
-
-int ctk_problem_get_param(const ctk_batch* b, int problem, int id, float* value) {
-    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
-    *value = b->table(problem)[id];
-    return CTK_OK;
-}
-
-int ctk_problem_params_differ(const ctk_batch* b) { return b && b->differ ? 1 : 0; }
-
-int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call) {
-    if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
-    *call = b->call[(size_t)problem];
-    return CTK_OK;
-}
-
-int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = batch_problem(b, "ctk_batch_rng_set_position", problem)) return rc;
-    b->call[(size_t)problem] = call;
-    return CTK_OK;
-}
+int ctk_problem_get_param(const ctk_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
+int ctk_problem_params_differ(const ctk_batch* b) { return batch_params_differ(b); }
+int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
+int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) { return batch_rng_set_position(b, "ctk_batch_rng_set_position", problem, call); }
 
 }  // extern "C"
 
@@ -3047,16 +3142,9 @@ int ctk_mlp_batch_rng_set_position(ctk_mlp_batch* m, int problem, uint32_t call)
 // (`differ`, sticky) every step writes the constants of the problems it steps BEHIND their step records, in the records' order, so they
 // travel in the records' transfer (no constants array in device memory, no second transfer).
 // =============================================================================================
-struct ctk_cem_batch {
-    ctk_config cfg{};
-    int B = 0, N = 0, H = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, K = 0, nblk = 0;
-    float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (ctk_cem_batch_set_param / get_param)
-    std::vector<float> pparams;             // [B][CTK_MAX_PARAMS] every problem's own table
-    std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived into kcache
-    bool differ = false;                    // a ctk_cem_problem_set_param has succeeded: the per-problem form of the kernel from now on
-    size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes per problem in kcache and behind the step records
+struct ctk_cem_batch : BatchCore {
+    int K = 0, nblk = 0;
     std::vector<unsigned char> kcache;      // [B][kstride] derived constants by problem id (host only; the step copies them into h_steps)
-    hipStream_t stream = nullptr;
     int max_per_launch = 1;                 // problems per launch: max(1, CUs / nblk) (ctk_cem_batch_create), a diagnostic switch may lower it
     size_t llw = 0;                         // ctk_cem_fused_ll_words(N, HC): hand-off words per problem
     unsigned long long* d_ll = nullptr;     // [B][llw], zero at allocation
@@ -3066,66 +3154,24 @@ struct ctk_cem_batch {
     float* d_Q = nullptr;                   // [B][N,H,C]
     float* d_traj = nullptr;                // [B][N,H+1,S] (materialize_trajectories)
     int* d_idx = nullptr;                   // [B][N]
-    float* d_u = nullptr;                   // [B][CTK_MAX_INPUTS]
-    float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
-    float* h_u_dev = nullptr;
     CtkCemBatchDesc* d_desc = nullptr;      // [B]
     CtkCemBatchStep* h_steps = nullptr;     // pinned, B * (sizeof(CtkCemBatchStep) + kstride) bytes: the n step records of the step being
     CtkCemBatchStep* d_steps = nullptr;     // issued and, in the per-problem form, the constants of those n problems right behind them
-    float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
-    std::vector<uint32_t> seq, call, cem_tag;
+    std::vector<uint32_t> cem_tag;
     std::vector<int> count;
     std::vector<unsigned char> idx_stale;
-    std::string err, dominant;
     float* mu(int p) const { return d_mu + (size_t)p * HC; }
     float* sd(int p) const { return d_sd + (size_t)p * HC; }
-    float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
-    float* slot(int p) const { return h_u + (size_t)p * 16; }
-    float* table(int p) { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
-    const float* table(int p) const { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
     int its(int p) const { return (cfg.warmup && count[(size_t)p] == 0) ? cfg.warmup_iterations : cfg.cem_outer_it; }   // cem_iterations
 };
 
 namespace {
 
-int cfail(ctk_cem_batch* b, int code, const std::string& msg) {
-    if (b) b->err = msg; else g_create_error = msg;
-    return code;
-}
-#define CHIP_TRY(b, expr)                                                                       \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess)                                                                   \
-            return cfail((b), CTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-    } while (0)
-
-// the problems a call addresses (batch_ids of the MPPI family): ids[0..n) strictly ascending, or all of them (ids == NULL)
-int cem_batch_ids(ctk_cem_batch* b, const char* who, int n_ids, const int32_t* ids, int* n_out) {
-    if (!ids) { *n_out = b->B; return CTK_OK; }
-    if (n_ids < 1 || n_ids > b->B) return cfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": n_ids must be 1 .. " + std::to_string(b->B) + " (the batch size)");
-    for (int j = 0; j < n_ids; ++j) {
-        if (ids[j] < 0 || ids[j] >= b->B)
-            return cfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(ids[j]) + " is outside 0 .. " + std::to_string(b->B - 1));
-        if (j > 0 && ids[j] <= ids[j - 1]) return cfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": ids must be strictly ascending");
-    }
-    *n_out = n_ids;
-    return CTK_OK;
-}
-int cem_batch_problem(ctk_cem_batch* b, const char* who, int p) {
-    if (p < 0 || p >= b->B) return cfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(p) + " is outside 0 .. " + std::to_string(b->B - 1));
-    return CTK_OK;
-}
-
 // the shared template of a launch's RolloutArgs (make_args of a CEM handle without what the step records and descriptors supply)
 RolloutArgs cem_batch_args(const ctk_cem_batch* b) {
-    RolloutArgs a{};
-    for (int c = 0; c < b->C; ++c) { a.lo[c] = b->cfg.action_low[c]; a.hi[c] = b->cfg.action_high[c]; }
-    a.C = b->C;
-    a.N = b->N; a.H = b->H; a.P = b->H;
+    RolloutArgs a = batch_common_args(b);
+    a.P = b->H;
     a.p_magic = ctk_magic_of(b->H);
-    a.inv_Hp1 = 1.0f / (float)(b->H + 1);
-    a.stream_id = 0;
-    a.global_row0 = b->cfg.global_rollout_offset;
     return a;
 }
 
@@ -3162,41 +3208,35 @@ void ctk_cem_batch_destroy(ctk_cem_batch* b) {
 
 int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_cem_batch** out) {
     if (out) *out = nullptr;
-    if (!cfg || !out) return cfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_create: NULL argument");
-    if (n_problems < 1) return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_create: NULL argument");
+    if (n_problems < 1) return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
     const EnvInfo* einfo = nullptr;
     if (int rc = check_config("ctk_cem_batch_create", cfg, &einfo)) return rc;
     if (cfg->optimizer != CTK_OPT_CEM)
-        return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: a CEM batch steps plain CEM controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: a CEM batch steps plain CEM controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
                      "); MPPI has ctk_batch_create, the CEM variants (naive-grad, Bharadhwaj, GMM) and the other optimizers run as single handles (ctk_create)");
     if (cfg->predictor != CTK_PRED_ODE)
-        return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
                      std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
     const int N = cfg->num_rollouts, H = cfg->mpc_horizon, HC = H * einfo->C, nblk = ctk_cem_fused_blocks(N);
     if (!ctk_cem_fusable(cfg->predictor, N, HC))
-        return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: per-problem population outside the one-launch CEM step's sizes (num_rollouts " + std::to_string(N) +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: per-problem population outside the one-launch CEM step's sizes (num_rollouts " + std::to_string(N) +
                      " = " + std::to_string(nblk) + " workgroups of 64 rollouts, mpc_horizon " + std::to_string(H) + " x " + std::to_string(einfo->C) + " inputs = " +
                      std::to_string(HC) + " columns, " + std::to_string(ctk_cem_fused_lds(N, HC)) + " bytes of LDS): the batch kernel takes at most " +
                      std::to_string(CTK_CEM_FUSED_MAX_BLOCKS) + " workgroups per problem and 131072 bytes (128 KiB) of LDS; such a controller runs as a single handle (ctk_create)");
     if (cfg->cem_best_k > N)
-        return cfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: cem_best_k " + std::to_string(cfg->cem_best_k) + " exceeds num_rollouts " + std::to_string(N) +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: cem_best_k " + std::to_string(cfg->cem_best_k) + " exceeds num_rollouts " + std::to_string(N) +
                      ": the elite set of a problem is part of its population");
     if (cfg->cem_best_k < 1 || cfg->cem_outer_it < 1 || (cfg->warmup && cfg->warmup_iterations < 1))
-        return cfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_create: need cem_best_k >= 1, cem_outer_it >= 1 and, with warmup, warmup_iterations >= 1");
+        return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_create: need cem_best_k >= 1, cem_outer_it >= 1 and, with warmup, warmup_iterations >= 1");
 
     hipDeviceProp_t prop;
     if (int rc = probe_device("ctk_cem_batch_create", cfg->device, &prop)) return rc;
 
     ctk_cem_batch* b = new ctk_cem_batch();
-    b->cfg = *cfg;
-    b->B = n_problems; b->N = N; b->H = H; b->K = cfg->cem_best_k; b->nblk = nblk;
-    b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = HC;
+    batch_core_init(b, cfg, einfo, n_problems);
+    b->K = cfg->cem_best_k; b->nblk = nblk;
     b->llw = ctk_cem_fused_ll_words(N, HC);
-    default_params(b->env, b->params);
-    b->pparams.resize((size_t)n_problems * CTK_MAX_PARAMS);
-    for (int p = 0; p < n_problems; ++p) std::memcpy(b->table(p), b->params, sizeof(b->params));
-    b->dirty.assign((size_t)n_problems, 1);            // nothing derived yet: the first step of the per-problem form derives what it steps
-    b->kstride = ctk_mppi_batch_k_stride(b->env);
     b->kcache.assign((size_t)n_problems * b->kstride, 0);
     // Progress (the proof stands above ctk_cem_batch, ctk_cem_fused.hip): every workgroup of a problem waits for all workgroups of that
     // problem, so a launch holds at most max(1, CUs / nblk) problems — problems * nblk <= CUs, every CU admits at least one workgroup of
@@ -3207,7 +3247,7 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
         const int v = std::atoi(e);
         if (v >= 1 && v < b->max_per_launch) b->max_per_launch = v;
     }
-    b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u); b->cem_tag.assign((size_t)n_problems, 1u);
+    b->cem_tag.assign((size_t)n_problems, 1u);
     b->count.assign((size_t)n_problems, 0); b->idx_stale.assign((size_t)n_problems, 0);
     b->dominant = ctk_cem_batch_name(b->env, cfg->materialize_trajectories != 0);
 
@@ -3262,14 +3302,14 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
 
 int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
                        float* u_out) {
-    if (!b || !s) return b ? cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
     int n = 0;
-    if (int rc = cem_batch_ids(b, "ctk_cem_batch_step", n_ids, ids, &n)) return rc;
+    if (int rc = batch_ids(b, "ctk_cem_batch_step", n_ids, ids, &n)) return rc;
     const size_t per_it = (size_t)b->N * b->HC;
     const int its0 = b->its(ids ? ids[0] : 0);
     if (samples_loc != CTK_LOC_NONE) {
-        if (samples == nullptr) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
-        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+        if (samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
         // the rows of a caller's buffer have ONE length: refused before anything is launched or consumed
         bool mixed = false;
         for (int j = 1; j < n; ++j) mixed |= b->its(ids ? ids[j] : j) != its0;
@@ -3279,23 +3319,17 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
                 const int p = ids ? ids[j] : j;
                 who += (j ? ", " : "") + std::to_string(p) + ": " + std::to_string(b->its(p));
             }
-            return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: with caller-supplied samples every listed problem must run the same number of outer "
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: with caller-supplied samples every listed problem must run the same number of outer "
                          "iterations, but (problem: iterations) " + who + " — the warm-up step of a problem after its creation or reset is longer; step them in "
                          "separate calls (the in-kernel sampler has no such restriction)");
         }
     }
-    CHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // behind the checks of `samples`, as in the RPGD step (the MPPI step: ahead of them, by history)
     const size_t per = per_it * (size_t)its0;          // draws per problem (caller-supplied samples: the same for all listed problems)
     const float* d_s = nullptr;                        // draws of the step's first problem; row j follows at j * per
     if (samples_loc == CTK_LOC_DEVICE) d_s = samples;
     else if (samples_loc == CTK_LOC_HOST) {
-        if ((size_t)n * per > b->samples_cap) {
-            if (b->d_samples) CHIP_TRY(b, hipFree(b->d_samples));
-            b->d_samples = nullptr; b->samples_cap = 0;
-            CHIP_TRY(b, hipMalloc((void**)&b->d_samples, (size_t)n * per * sizeof(float)));
-            b->samples_cap = (size_t)n * per;
-        }
-        CHIP_TRY(b, hipMemcpyAsync(b->d_samples, samples, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        if (int rc = batch_stage(b, samples, (size_t)n * per)) return rc;
         d_s = b->d_samples;
     }
     // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es).  Every launch attempt
@@ -3308,32 +3342,11 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
         if ((uint32_t)(b->cem_tag[z] + (uint32_t)its) < b->cem_tag[z]) b->cem_tag[z] = 1;
         q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.tag0 = b->cem_tag[z]; q.its = its;
         b->cem_tag[z] += (uint32_t)its;
-        q.dev_uprev = u_prev ? 0u : 1u;
         q.samples = d_s ? d_s + (size_t)j * per : nullptr;
-        for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
-        for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
+        batch_record_io(b, q, j, s, u_prev);
     }
-    // The per-problem form: the constants of the n problems of this step right behind the n records, in the records' order, so that ONE
-    // transfer carries both.  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses
-    // (ctk_set_param -> derive_constants / Env<>::derive at its launch); the cache is by problem id, the block behind the records by launch order.
-    size_t step_bytes = (size_t)n * sizeof(CtkCemBatchStep);
-    const unsigned char* d_ksteps = nullptr;
-    if (b->differ) {
-        unsigned char* h_k = reinterpret_cast<unsigned char*>(b->h_steps) + step_bytes;
-        for (int j = 0; j < n; ++j) {
-            const size_t z = (size_t)b->h_steps[j].id;
-            if (b->dirty[z]) {
-                ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, b->kcache.data() + z * b->kstride);
-                b->dirty[z] = 0;
-            }
-            std::memcpy(h_k + (size_t)j * b->kstride, b->kcache.data() + z * b->kstride, b->kstride);
-        }
-        d_ksteps = reinterpret_cast<const unsigned char*>(b->d_steps) + step_bytes;
-        step_bytes += (size_t)n * b->kstride;
-    }
-    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, step_bytes, hipMemcpyHostToDevice, b->stream);
-    if (le != hipSuccess && b->differ)                 // nothing reached the device: derive and copy again at the next step
-        for (int j = 0; j < n; ++j) b->dirty[(size_t)b->h_steps[j].id] = 1;
+    const unsigned char* d_ksteps = nullptr;           // the per-problem form: the constants behind the records, in the same transfer
+    hipError_t le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(CtkCemBatchStep), b->h_steps, b->d_steps, &d_ksteps);
     const RolloutArgs a = cem_batch_args(b);
     const bool log = b->cfg.materialize_trajectories != 0;
     const CemFusedLaunch cl{0, b->K, nullptr, 0u, b->cfg.cem_stdev_min, 1.0e8f, b->cfg.cem_initial_action_stdev,
@@ -3345,42 +3358,24 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
                                   d_ksteps ? d_ksteps + (size_t)launched * b->kstride : nullptr);
         if (le == hipSuccess) launched += cnt;
     }
-    // completion: every launched problem's {u, seq} store landing in its pinned slot (finish_step's bounded spin, one budget for all)
-    bool synced = false;
-    int spins = 0;
-    std::string late, timed_out;
-    for (int j = 0; j < launched; ++j) {
-        const int p = b->h_steps[j].id;
-        const uint32_t want = b->seq[(size_t)p];
-        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 1;
-        while (*slot != want) {
-            if (!synced && ++spins < 4000000) { __builtin_ia32_pause(); continue; }
-            if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
-            break;
-        }
-        if (*slot != want) late += (late.empty() ? "" : ", ") + std::to_string(p);
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    const std::string late = batch_poll(b, ids, launched);
+    std::string timed_out;
     for (int j = 0; j < n; ++j) {
         const int p = b->h_steps[j].id;
         const size_t z = (size_t)p;
-        ++b->seq[z];                                   // every launch attempt consumes its sequence number (guarded())
+        ++b->seq[z];                                   // every listed problem, launched or not, consumes its sequence number (guarded()); as MPPI, RPGD differs on purpose
         if (j >= launched) continue;
         ++b->count[z]; b->idx_stale[z] = 1;            // as cem_step: with the launch
         if (reinterpret_cast<volatile uint32_t*>(b->slot(p))[1] != b->h_steps[j].seq) continue;   // never published (a device fault): finish_step
-        ++b->call[z];                                  // returns before it advances the Philox position or reads u
-        volatile float* sl = reinterpret_cast<volatile float*>(b->slot(p));
-        if (u_out) {
-            u_out[(size_t)j * b->C] = sl[0];
-            for (int c = 1; c < b->C; ++c) u_out[(size_t)j * b->C + c] = sl[4 + c];   // publish_u_vec
-        }
-        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;
+        ++b->call[z];                                  // returns before it advances the Philox position or reads u (as RPGD; MPPI advances it regardless, by history)
+        batch_read_u(b, p, j, u_out);
+        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;   // the hand-off's error word (MPPI and CEM; RPGD has none)
         if (errw[0]) { errw[0] = 0; timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(p); }
     }
-    if (le != hipSuccess) return cfail(b, CTK_ERR_HIP, std::string("ctk_cem_batch_step: ") + hipGetErrorString(le));
-    if (!late.empty()) return cfail(b, CTK_ERR_HIP, "ctk_cem_batch_step: the step finished without publishing the result of problem(s) " + late);
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_cem_batch_step: ") + hipGetErrorString(le));
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_cem_batch_step: the step finished without publishing the result of problem(s) " + late);
     if (!timed_out.empty())
-        return cfail(b, CTK_ERR_STATE, "ctk_cem_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+        return bfail(b, CTK_ERR_STATE, "ctk_cem_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
                      "; the other problems' outputs are valid and written");
     return CTK_OK;
 }
@@ -3388,128 +3383,90 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
 int ctk_cem_batch_reset(ctk_cem_batch* b, int n_ids, const int32_t* ids) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     int n = 0;
-    if (int rc = cem_batch_ids(b, "ctk_cem_batch_reset", n_ids, ids, &n)) return rc;
-    CHIP_TRY(b, hipSetDevice(b->cfg.device));
+    if (int rc = batch_ids(b, "ctk_cem_batch_reset", n_ids, ids, &n)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
     std::vector<float> mu((size_t)b->HC), sd((size_t)b->HC), zero((size_t)b->C, 0.0f);
     cem_batch_initial(b, mu.data(), sd.data());
     for (int j = 0; j < n; ++j) {                      // ctk_reset of a CEM handle: parameters, tags and the Philox position stay
         const int p = ids ? ids[j] : j;
         b->count[(size_t)p] = 0;
-        CHIP_TRY(b, hipMemcpyAsync(b->mu(p), mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
-        CHIP_TRY(b, hipMemcpyAsync(b->sd(p), sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
-        CHIP_TRY(b, hipMemcpyAsync(b->u(p), zero.data(), zero.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        BHIP_TRY(b, hipMemcpyAsync(b->mu(p), mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        BHIP_TRY(b, hipMemcpyAsync(b->sd(p), sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        BHIP_TRY(b, hipMemcpyAsync(b->u(p), zero.data(), zero.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
     }
-    CHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
     return CTK_OK;
 }
 
 int ctk_cem_batch_read(ctk_cem_batch* b, int problem, int buffer, float* dst, size_t cap) {
-    if (!b || !dst) return b ? cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: NULL destination") : CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = cem_batch_problem(b, "ctk_cem_batch_read", problem)) return rc;
+    if (!b || !dst) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: NULL destination") : CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, "ctk_cem_batch_read", problem)) return rc;
     const size_t z = (size_t)problem, N = (size_t)b->N;
     const float* src = nullptr; size_t n = 0; bool is_int = false;
     switch (buffer) {
         case CTK_BUF_Q: src = b->d_Q + z * N * b->HC; n = N * b->HC; break;
         case CTK_BUF_J: src = b->d_J + z * N; n = N; break;
         case CTK_BUF_TRAJ:
-            if (!b->d_traj) return cfail(b, CTK_ERR_STATE, "ctk_cem_batch_read: trajectories not materialised (cfg.materialize_trajectories == 0)");
+            if (!b->d_traj) return bfail(b, CTK_ERR_STATE, "ctk_cem_batch_read: trajectories not materialised (cfg.materialize_trajectories == 0)");
             n = N * ((size_t)b->H + 1) * b->S; src = b->d_traj + z * n; break;
         case CTK_BUF_U_NOM: src = b->mu(problem); n = (size_t)b->HC; break;
         case CTK_BUF_STD: src = b->sd(problem); n = (size_t)b->HC; break;
         case CTK_BUF_BEST_IDX: src = reinterpret_cast<const float*>(b->d_idx + z * N); n = (size_t)b->K; is_int = true; break;
-        default: return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: a CEM batch has Q, J, TRAJ, U_NOM, STD and BEST_IDX");
+        default: return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: a CEM batch has Q, J, TRAJ, U_NOM, STD and BEST_IDX");
     }
-    if (cap < n) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: destination too small (" + std::to_string(n) + " floats)");
-    CHIP_TRY(b, hipSetDevice(b->cfg.device));
+    if (cap < n) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: destination too small (" + std::to_string(n) + " floats)");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
     if (is_int && b->idx_stale[z]) {   // the sorted elite indices are materialised from the last iteration's costs (locate_buffer)
-        CHIP_TRY(b, ctk_launch_select_topk(b->stream, b->d_J + z * N, b->N, b->K, b->d_idx + z * N));
+        BHIP_TRY(b, ctk_launch_select_topk(b->stream, b->d_J + z * N, b->N, b->K, b->d_idx + z * N));
         b->idx_stale[z] = 0;
     }
-    CHIP_TRY(b, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    CHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
     if (is_int) for (size_t i = 0; i < n; ++i) { int v; std::memcpy(&v, &dst[i], 4); dst[i] = (float)v; }
     return CTK_OK;
 }
 
 int ctk_cem_batch_get_state(ctk_cem_batch* b, int problem, float* dst, size_t cap) {
     if (!b || !dst) return CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = cem_batch_problem(b, "ctk_cem_batch_get_state", problem)) return rc;
+    if (int rc = batch_problem(b, "ctk_cem_batch_get_state", problem)) return rc;
     const size_t HC = (size_t)b->HC;
-    if (cap < 2 * HC + b->C + 1) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_get_state: destination too small");
-    CHIP_TRY(b, hipSetDevice(b->cfg.device));
-    CHIP_TRY(b, hipMemcpyAsync(dst, b->mu(problem), HC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    CHIP_TRY(b, hipMemcpyAsync(dst + HC, b->sd(problem), HC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    CHIP_TRY(b, hipMemcpyAsync(dst + 2 * HC, b->u(problem), (size_t)b->C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    CHIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (cap < 2 * HC + b->C + 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_get_state: destination too small");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipMemcpyAsync(dst, b->mu(problem), HC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(dst + HC, b->sd(problem), HC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(dst + 2 * HC, b->u(problem), (size_t)b->C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
     dst[2 * HC + b->C] = (float)b->count[(size_t)problem];
     return CTK_OK;
 }
 
 int ctk_cem_batch_set_state(ctk_cem_batch* b, int problem, const float* src, size_t n) {
     if (!b || !src) return CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = cem_batch_problem(b, "ctk_cem_batch_set_state", problem)) return rc;
+    if (int rc = batch_problem(b, "ctk_cem_batch_set_state", problem)) return rc;
     const size_t HC = (size_t)b->HC;
-    if (n != 2 * HC + b->C + 1) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_set_state: wrong state size");
-    CHIP_TRY(b, hipSetDevice(b->cfg.device));
-    CHIP_TRY(b, hipMemcpyAsync(b->mu(problem), src, HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    CHIP_TRY(b, hipMemcpyAsync(b->sd(problem), src + HC, HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    CHIP_TRY(b, hipMemcpyAsync(b->u(problem), src + 2 * HC, (size_t)b->C * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    if (n != 2 * HC + b->C + 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_set_state: wrong state size");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipMemcpyAsync(b->mu(problem), src, HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(b->sd(problem), src + HC, HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(b->u(problem), src + 2 * HC, (size_t)b->C * sizeof(float), hipMemcpyHostToDevice, b->stream));
     b->count[(size_t)problem] = (int)src[2 * HC + b->C];
-    CHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
     return CTK_OK;
 }
 
-int ctk_cem_batch_set_param(ctk_cem_batch* b, int id, float value) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (id < 0 || id >= env_info(b->env)->n_params) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_set_param: unknown parameter id for this environment");
-    b->params[id] = value;                             // the shared table: the shared form derives its constants from it at each launch
-    for (int p = 0; p < b->B; ++p) { b->table(p)[id] = value; b->dirty[(size_t)p] = 1; }   // column id of every problem; the other ids stay
-    return CTK_OK;
-}
-
-int ctk_cem_batch_get_param(const ctk_cem_batch* b, int id, float* value) {
-    if (!b || !value || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
-    *value = b->params[id];
-    return CTK_OK;
-}
-
+int ctk_cem_batch_set_param(ctk_cem_batch* b, int id, float value) { return batch_set_param(b, "ctk_cem_batch_set_param", id, value); }
+int ctk_cem_batch_get_param(const ctk_cem_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
 int ctk_cem_problem_set_param(ctk_cem_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = cem_batch_ids(b, "ctk_cem_problem_set_param", n_ids, ids, &n)) return rc;
-    if (id < 0 || id >= env_info(b->env)->n_params) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_problem_set_param: unknown parameter id for this environment");
-    if (!values) return cfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_problem_set_param: NULL values (one value per listed problem)");
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        b->table(p)[id] = values[j];
-        b->dirty[(size_t)p] = 1;                       // derived when the problem is next stepped: no cost until then
-    }
-    if (!b->differ) {                                  // sticky: the tables are never compared again
-        b->differ = true;
-        b->dominant = ctk_cem_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
-    }
-    return CTK_OK;
+    bool flipped = false;
+    const int rc = batch_problem_set_param(b, "ctk_cem_problem_set_param", n_ids, ids, id, values, &flipped);
+    if (flipped) b->dominant = ctk_cem_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    return rc;
 }
-
-int ctk_cem_problem_get_param(const ctk_cem_batch* b, int problem, int id, float* value) {
-    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
-    *value = b->table(problem)[id];
-    return CTK_OK;
-}
-
-int ctk_cem_problem_params_differ(const ctk_cem_batch* b) { return b && b->differ ? 1 : 0; }
-
-int ctk_cem_batch_rng_get_position(const ctk_cem_batch* b, int problem, uint32_t* call) {
-    if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
-    *call = b->call[(size_t)problem];
-    return CTK_OK;
-}
-
+int ctk_cem_problem_get_param(const ctk_cem_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
+int ctk_cem_problem_params_differ(const ctk_cem_batch* b) { return batch_params_differ(b); }
+int ctk_cem_batch_rng_get_position(const ctk_cem_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
 int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = cem_batch_problem(b, "ctk_cem_batch_rng_set_position", problem)) return rc;
-    b->call[(size_t)problem] = call;
-    return CTK_OK;
+    return batch_rng_set_position(b, "ctk_cem_batch_rng_set_position", problem, call);
 }
 
 }  // extern "C"
@@ -3526,16 +3483,9 @@ int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call)
 // BEHIND their step records, in the records' order, so they travel in the records' transfer (no constants array in device memory, no
 // second transfer).
 // =============================================================================================
-struct ctk_rpgd_batch {
-    ctk_config cfg{};
-    int B = 0, N = 0, H = 0, P = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0, PC = 0, K = 0;
-    float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (ctk_rpgd_batch_set_param / get_param)
-    std::vector<float> pparams;             // [B][CTK_MAX_PARAMS] every problem's own table
-    std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived into kcache
-    bool differ = false;                    // a ctk_rpgd_problem_set_param has succeeded: the per-problem form of the kernel from now on
-    size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes per problem in kcache and behind the step records
+struct ctk_rpgd_batch : BatchCore {
+    int P = 0, PC = 0, K = 0;
     std::vector<unsigned char> kcache;      // [B][kstride] derived constants by problem id (host only; the step copies them into h_steps)
-    hipStream_t stream = nullptr;
     InterpEntry* d_interp = nullptr;        // [H] shared
     float* d_bc = nullptr; int bc_len = 0;  // shared bias-correction table
     float* d_pop[2] = {nullptr, nullptr};   // [B][N,H,C] each
@@ -3545,23 +3495,13 @@ struct ctk_rpgd_batch {
     float* d_J = nullptr;                   // [B][N]
     int* d_idx = nullptr;                   // [B][N]
     float* d_unom = nullptr;                // [B][H,C]
-    float* d_u = nullptr;                   // [B][CTK_MAX_INPUTS]
     float* d_scratch = nullptr; size_t scratch_stride = 0;   // [B][H * NT * 64] state tapes that do not fit in LDS
-    float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
-    float* h_u_dev = nullptr;
     CtkRpgdBatchDesc* d_desc = nullptr;     // [B]
     CtkRpgdBatchStep* h_steps = nullptr;    // pinned, B * (sizeof(CtkRpgdBatchStep) + kstride) bytes: the n records of the step (or reset) being
     CtkRpgdBatchStep* d_steps = nullptr;    // issued and, in the per-problem form of a step, the constants of those n problems right behind them
-    float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
-    std::vector<uint32_t> seq, call;
     std::vector<int> count, adam_step;
     std::vector<unsigned char> cur, ready;
-    std::string err, dominant;
     size_t NHC() const { return (size_t)N * HC; }
-    float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
-    float* slot(int p) const { return h_u + (size_t)p * 16; }
-    float* table(int p) { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
-    const float* table(int p) const { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
     size_t state_size() const { return 3 * NHC() + (size_t)N + C + 2; }   // ctk_state_size of an RPGD handle
     int its(int p) const {                  // rpgd_iterations
         const int first = cfg.warmup ? cfg.warmup_iterations : cfg.outer_its;
@@ -3573,46 +3513,13 @@ struct ctk_rpgd_batch {
 
 namespace {
 
-int rfail(ctk_rpgd_batch* b, int code, const std::string& msg) {
-    if (b) b->err = msg; else g_create_error = msg;
-    return code;
-}
-#define RHIP_TRY(b, expr)                                                                       \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess)                                                                   \
-            return rfail((b), CTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-    } while (0)
-
-// the problems a call addresses (batch_ids of the MPPI family): ids[0..n) strictly ascending, or all of them (ids == NULL)
-int rpgd_batch_ids(ctk_rpgd_batch* b, const char* who, int n_ids, const int32_t* ids, int* n_out) {
-    if (!ids) { *n_out = b->B; return CTK_OK; }
-    if (n_ids < 1 || n_ids > b->B) return rfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": n_ids must be 1 .. " + std::to_string(b->B) + " (the batch size)");
-    for (int j = 0; j < n_ids; ++j) {
-        if (ids[j] < 0 || ids[j] >= b->B)
-            return rfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(ids[j]) + " is outside 0 .. " + std::to_string(b->B - 1));
-        if (j > 0 && ids[j] <= ids[j - 1]) return rfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": ids must be strictly ascending");
-    }
-    *n_out = n_ids;
-    return CTK_OK;
-}
-int rpgd_batch_problem(ctk_rpgd_batch* b, const char* who, int p) {
-    if (p < 0 || p >= b->B) return rfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(p) + " is outside 0 .. " + std::to_string(b->B - 1));
-    return CTK_OK;
-}
-
 // the shared template of a launch's RolloutArgs (make_args of an RPGD handle's descent without what the step records and descriptors supply)
 RolloutArgs rpgd_batch_args(const ctk_rpgd_batch* b) {
-    RolloutArgs a{};
-    for (int c = 0; c < b->C; ++c) { a.lo[c] = b->cfg.action_low[c]; a.hi[c] = b->cfg.action_high[c]; }
-    a.C = b->C;
-    a.N = b->N; a.H = b->H; a.P = b->H;
+    RolloutArgs a = batch_common_args(b);
+    a.P = b->H;
     a.p_magic = ctk_magic_of(b->H);
     a.identity_interp = b->cfg.period_interpolation_inducing_points == 1 ? 1 : 0;
-    a.inv_Hp1 = 1.0f / (float)(b->H + 1);
     a.interp = b->d_interp;
-    a.stream_id = 0;
-    a.global_row0 = b->cfg.global_rollout_offset;
     return a;
 }
 // what the launches take of the warm start's description: keep_k, P, the sampling constants, the interpolation table
@@ -3621,18 +3528,6 @@ RpgdFusedWarm rpgd_batch_warm(const ctk_rpgd_batch* b) {
     return RpgdFusedWarm{b->K, nullptr, b->P, 0, 0, c.shift_previous, c.sampling_distribution, 0, c.sample_whole_control_space, c.sample_stdev,
                          c.sample_mean, c.sample_min, c.sample_max, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b->d_interp,
                          nullptr, nullptr, nullptr, 0u};
-}
-
-// host-supplied draws into the staging buffer (resolve_samples of a handle): n floats
-int rpgd_batch_stage(ctk_rpgd_batch* b, const float* src, size_t n) {
-    if (n > b->samples_cap) {
-        if (b->d_samples) RHIP_TRY(b, hipFree(b->d_samples));
-        b->d_samples = nullptr; b->samples_cap = 0;
-        RHIP_TRY(b, hipMalloc((void**)&b->d_samples, n * sizeof(float)));
-        b->samples_cap = n;
-    }
-    RHIP_TRY(b, hipMemcpyAsync(b->d_samples, src, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    return CTK_OK;
 }
 
 constexpr int RPGD_BATCH_MAX_GRID_Y = 65535;   // problems of one launch: the grid's y limit, nothing else bounds it
@@ -3670,63 +3565,57 @@ void ctk_rpgd_batch_destroy(ctk_rpgd_batch* b) {
 
 int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_rpgd_batch** out) {
     if (out) *out = nullptr;
-    if (!cfg || !out) return rfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: NULL argument");
-    if (n_problems < 1) return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: NULL argument");
+    if (n_problems < 1) return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
     const EnvInfo* einfo = nullptr;
     if (int rc = check_config("ctk_rpgd_batch_create", cfg, &einfo)) return rc;
     const int N = cfg->num_rollouts, H = cfg->mpc_horizon, HC = H * einfo->C;
     if (cfg->optimizer != CTK_OPT_RPGD)
-        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: an RPGD batch steps RPGD controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: an RPGD batch steps RPGD controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
                      ", num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + "); MPPI has ctk_batch_create, plain CEM ctk_cem_batch_create, the "
                      "gradient variant (CTK_OPT_GRADIENT) and the other optimizers run as single handles (ctk_create)");
     if (cfg->predictor != CTK_PRED_ODE)
-        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: the batch kernel descends through the analytic (ODE) predictor only (cfg.predictor == " +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: the batch kernel descends through the analytic (ODE) predictor only (cfg.predictor == " +
                      std::to_string(cfg->predictor) + ", num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) +
                      "); network predictors run as single handles (ctk_create)");
     if (cfg->environment == CTK_ENV_CARTPOLE && cfg->generic_kernels == 0)
-        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: CartPole's tuned descent (ctk_rpgd_descent, what a handle with generic_kernels == 0 runs) has no "
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: CartPole's tuned descent (ctk_rpgd_descent, what a handle with generic_kernels == 0 runs) has no "
                      "batch form; the template kernels do: set cfg.generic_kernels = 1, and compare with handles created the same way (num_rollouts " +
                      std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ")");
     if (N > CTK_RPGD_FUSED_MAX_N)
-        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: num_rollouts " + std::to_string(N) + " exceeds " + std::to_string(CTK_RPGD_FUSED_MAX_N) +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: num_rollouts " + std::to_string(N) + " exceeds " + std::to_string(CTK_RPGD_FUSED_MAX_N) +
                      ", the population one workgroup holds (a problem's whole step runs in one workgroup); such a controller runs as a single handle (ctk_create)");
     if (cfg->opt_keep_k > N)
-        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: opt_keep_k " + std::to_string(cfg->opt_keep_k) + " exceeds num_rollouts " + std::to_string(N) +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: opt_keep_k " + std::to_string(cfg->opt_keep_k) + " exceeds num_rollouts " + std::to_string(N) +
                      ": the plans a problem keeps are part of its population");
     if (cfg->materialize_trajectories)
-        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: materialize_trajectories is not built for a batch (num_rollouts " + std::to_string(N) +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: materialize_trajectories is not built for a batch (num_rollouts " + std::to_string(N) +
                      ", mpc_horizon " + std::to_string(H) + "): the logging rollout sits between descent and warm start, and the one launch has no seam for it; "
                      "such a controller runs as a single handle (ctk_create)");
     bool tape_in_lds = false;
     const size_t lds = ctk_g_rpgd_descent_lds(cfg->environment, H, &tape_in_lds);
     if (lds > 160 * 1024)
-        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: mpc_horizon " + std::to_string(H) + " x " + std::to_string(einfo->C) + " inputs = " +
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: mpc_horizon " + std::to_string(H) + " x " + std::to_string(einfo->C) + " inputs = " +
                      std::to_string(HC) + " columns need " + std::to_string(lds) + " bytes of LDS without the state tape; a workgroup has 163840 (160 KiB)");
     if (cfg->opt_keep_k < 1 || cfg->outer_its < 0 || cfg->resamp_per < 1 || cfg->shift_previous < 0 || (cfg->warmup && cfg->warmup_iterations < 0) ||
         (cfg->sampling_distribution != 0 && cfg->sampling_distribution != 1))
-        return rfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: RPGD needs opt_keep_k >= 1, outer_its >= 0, resamp_per >= 1, shift_previous >= 0, "
+        return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: RPGD needs opt_keep_k >= 1, outer_its >= 0, resamp_per >= 1, shift_previous >= 0, "
                      "warmup_iterations >= 0, sampling_distribution in {0,1}");
     if (cfg->intermediate_steps != 1)
-        return rfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: the RPGD adjoint is built for intermediate_steps == 1 (given " + std::to_string(cfg->intermediate_steps) + ")");
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: the RPGD adjoint is built for intermediate_steps == 1 (given " + std::to_string(cfg->intermediate_steps) + ")");
     if (cfg->adam_rule != 0 && cfg->adam_rule != 1)
-        return rfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: adam_rule must be 0 (the reference's torch ADAM) or 1 (tf.keras.optimizers.Adam)");
+        return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: adam_rule must be 0 (the reference's torch ADAM) or 1 (tf.keras.optimizers.Adam)");
 
     hipDeviceProp_t prop;
     if (int rc = probe_device("ctk_rpgd_batch_create", cfg->device, &prop)) return rc;
 
     ctk_rpgd_batch* b = new ctk_rpgd_batch();
-    b->cfg = *cfg;
-    b->B = n_problems; b->N = N; b->H = H; b->K = cfg->opt_keep_k;
+    batch_core_init(b, cfg, einfo, n_problems);
+    b->K = cfg->opt_keep_k;
     b->P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
-    b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = HC; b->PC = b->P * einfo->C;
-    default_params(b->env, b->params);
-    b->pparams.resize((size_t)n_problems * CTK_MAX_PARAMS);
-    for (int p = 0; p < n_problems; ++p) std::memcpy(b->table(p), b->params, sizeof(b->params));
-    b->dirty.assign((size_t)n_problems, 1);            // nothing derived yet: the first step of the per-problem form derives what it steps
-    b->kstride = ctk_mppi_batch_k_stride(b->env);
+    b->PC = b->P * einfo->C;
     b->kcache.assign((size_t)n_problems * b->kstride, 0);
     b->scratch_stride = tape_in_lds ? 0 : ctk_g_rpgd_scratch_floats(b->env, N, H);
-    b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u);
     b->count.assign((size_t)n_problems, 0); b->adam_step.assign((size_t)n_problems, 0);
     b->cur.assign((size_t)n_problems, 0); b->ready.assign((size_t)n_problems, 0);
     b->dominant = ctk_g_rpgd_batch_name(b->env);
@@ -3797,17 +3686,17 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
 int ctk_rpgd_batch_reset(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* draws, int draws_loc) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     int n = 0;
-    if (int rc = rpgd_batch_ids(b, "ctk_rpgd_batch_reset", n_ids, ids, &n)) return rc;
+    if (int rc = batch_ids(b, "ctk_rpgd_batch_reset", n_ids, ids, &n)) return rc;
     const size_t per = (size_t)b->N * b->PC;           // sample_actions of a whole population: [N,P,C] per problem
     const float* d_draws = nullptr;
     if (draws_loc != CTK_LOC_NONE) {
-        if (draws == nullptr) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "draws pointer is NULL but draws_loc != CTK_LOC_NONE");
-        if (draws_loc != CTK_LOC_DEVICE && draws_loc != CTK_LOC_HOST) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "bad draws_loc");
+        if (draws == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "draws pointer is NULL but draws_loc != CTK_LOC_NONE");
+        if (draws_loc != CTK_LOC_DEVICE && draws_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad draws_loc");
     }
-    RHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
     if (draws_loc == CTK_LOC_DEVICE) d_draws = draws;
     else if (draws_loc == CTK_LOC_HOST) {
-        if (int rc = rpgd_batch_stage(b, draws, (size_t)n * per)) return rc;
+        if (int rc = batch_stage(b, draws, (size_t)n * per)) return rc;
         d_draws = b->d_samples;
     }
     for (int j = 0; j < n; ++j) {
@@ -3817,15 +3706,15 @@ int ctk_rpgd_batch_reset(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const
         q.id = p; q.call = b->call[(size_t)p]; q.cur = b->cur[(size_t)p];
         q.draws = d_draws ? d_draws + (size_t)j * per : nullptr;
     }
-    RHIP_TRY(b, hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkRpgdBatchStep), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkRpgdBatchStep), hipMemcpyHostToDevice, b->stream));
     const RolloutArgs a = rpgd_batch_args(b);
     const RpgdFusedWarm f = rpgd_batch_warm(b);
     for (int done = 0; done < n;) {                    // ONE launch for the call (more only past the grid's y limit)
         const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - done);
-        RHIP_TRY(b, ctk_launch_rpgd_batch_reset(b->stream, a, f, b->d_desc, b->d_steps + done, cnt));
+        BHIP_TRY(b, ctk_launch_rpgd_batch_reset(b->stream, a, f, b->d_desc, b->d_steps + done, cnt));
         done += cnt;
     }
-    RHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
     for (int j = 0; j < n; ++j) {                      // rpgd_reset of a handle: parameters, the sequence number and the buffer index stay
         const size_t z = (size_t)(ids ? ids[j] : j);
         b->count[z] = 0; b->adam_step[z] = 0; b->ready[z] = 1;
@@ -3836,30 +3725,30 @@ int ctk_rpgd_batch_reset(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const
 
 int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples,
                         size_t n_samples, int samples_loc, float* u_out) {
-    if (!b || !s) return b ? rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
     int n = 0;
-    if (int rc = rpgd_batch_ids(b, "ctk_rpgd_batch_step", n_ids, ids, &n)) return rc;
+    if (int rc = batch_ids(b, "ctk_rpgd_batch_step", n_ids, ids, &n)) return rc;
     size_t need = 0;
     for (int j = 0; j < n; ++j) {
         const int p = ids ? ids[j] : j;
         if (!b->ready[(size_t)p])
-            return rfail(b, CTK_ERR_STATE, "ctk_rpgd_batch_step: problem " + std::to_string(p) + " was never reset: call ctk_rpgd_batch_reset (optimizer_reset) "
+            return bfail(b, CTK_ERR_STATE, "ctk_rpgd_batch_step: problem " + std::to_string(p) + " was never reset: call ctk_rpgd_batch_reset (optimizer_reset) "
                          "before its first step; nothing was launched");
         need += b->needs(p);
     }
     if (samples_loc != CTK_LOC_NONE) {
-        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
         if (n_samples != need)                          // refused before a sample is read
-            return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: " + std::to_string(n_samples) + " samples given, the listed problems need " +
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: " + std::to_string(n_samples) + " samples given, the listed problems need " +
                          std::to_string(need) + " (one [num_rollouts - opt_keep_k, P, C] block for every listed problem whose ctk_rpgd_batch_samples_needed is "
                          "non-zero, in id order); nothing was launched");
-        if (need != 0 && samples == nullptr) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+        if (need != 0 && samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
     }
-    RHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // behind the checks of `samples`, as in the CEM step (the MPPI step: ahead of them, by history)
     const float* d_s = nullptr;                        // the first block; the blocks follow one another in the order of the listed problems that draw
     if (samples_loc == CTK_LOC_DEVICE && need) d_s = samples;
     else if (samples_loc == CTK_LOC_HOST && need) {
-        if (int rc = rpgd_batch_stage(b, samples, need)) return rc;
+        if (int rc = batch_stage(b, samples, need)) return rc;
         d_s = b->d_samples;
     }
     // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es)
@@ -3870,35 +3759,14 @@ int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const 
         CtkRpgdBatchStep& q = b->h_steps[j];
         q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.cur = b->cur[z];
         q.iters = b->its(p); q.t0 = b->adam_step[z]; q.resample = b->resamples(p) ? 1 : 0;
-        q.dev_uprev = u_prev ? 0u : 1u;
         const size_t cnt = b->needs(p);
         q.draws = (d_s && cnt) ? d_s + off : nullptr;
         off += d_s ? cnt : 0;
         q.pad = 0;
-        for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
-        for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
+        batch_record_io(b, q, j, s, u_prev);
     }
-    // The per-problem form: the constants of the n problems of this step right behind the n records, in the records' order, so that ONE
-    // transfer carries both.  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses
-    // (Env<>::derive at its launch); the cache is by problem id, the block behind the records by launch order.
-    size_t step_bytes = (size_t)n * sizeof(CtkRpgdBatchStep);
-    const unsigned char* d_ksteps = nullptr;
-    if (b->differ) {
-        unsigned char* h_k = reinterpret_cast<unsigned char*>(b->h_steps) + step_bytes;
-        for (int j = 0; j < n; ++j) {
-            const size_t z = (size_t)b->h_steps[j].id;
-            if (b->dirty[z]) {
-                ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, b->kcache.data() + z * b->kstride);
-                b->dirty[z] = 0;
-            }
-            std::memcpy(h_k + (size_t)j * b->kstride, b->kcache.data() + z * b->kstride, b->kstride);
-        }
-        d_ksteps = reinterpret_cast<const unsigned char*>(b->d_steps) + step_bytes;
-        step_bytes += (size_t)n * b->kstride;
-    }
-    hipError_t le = hipMemcpyAsync(b->d_steps, b->h_steps, step_bytes, hipMemcpyHostToDevice, b->stream);
-    if (le != hipSuccess && b->differ)                 // nothing reached the device: derive and copy again at the next step
-        for (int j = 0; j < n; ++j) b->dirty[(size_t)b->h_steps[j].id] = 1;
+    const unsigned char* d_ksteps = nullptr;           // the per-problem form: the constants behind the records, in the same transfer
+    hipError_t le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(CtkRpgdBatchStep), b->h_steps, b->d_steps, &d_ksteps);
     const RolloutArgs a = rpgd_batch_args(b);
     const RpgdFusedWarm f = rpgd_batch_warm(b);
     const ctk_config& c = b->cfg;
@@ -3910,47 +3778,27 @@ int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const 
                                      d_ksteps ? d_ksteps + (size_t)launched * b->kstride : nullptr);
         if (le == hipSuccess) launched += cnt;
     }
-    // completion: every launched problem's {u, seq} store landing in its pinned slot (finish_step's bounded spin, one budget for all).
     // h_steps is both the source of the transfer above and, below, the host's memory of id / seq / iters for the bookkeeping: that holds
     // because the call is synchronous (nothing refills h_steps before it returns); an asynchronous step would need its own copy.
-    bool synced = false;
-    int spins = 0;
-    std::string late;
-    for (int j = 0; j < launched; ++j) {
-        const int p = b->h_steps[j].id;
-        const uint32_t want = b->seq[(size_t)p];
-        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 1;
-        while (*slot != want) {
-            if (!synced && ++spins < 4000000) { __builtin_ia32_pause(); continue; }
-            if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
-            break;
-        }
-        if (*slot != want) late += (late.empty() ? "" : ", ") + std::to_string(p);
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    for (int j = 0; j < n; ++j) {
-        const int p = b->h_steps[j].id;
+    const std::string late = batch_poll(b, ids, launched);
+    for (int j = 0; j < launched; ++j) {               // on purpose: a problem never issued consumes no sequence number, nothing of it advances
+        const int p = b->h_steps[j].id;                // (the MPPI and CEM steps consume seq for every listed problem)
         const size_t z = (size_t)p;
-        if (j >= launched) continue;                   // never issued: nothing on the device carries its numbers, nothing advances
         ++b->seq[z];
         b->adam_step[z] += b->h_steps[j].iters;        // as rpgd_descent / rpgd_step: with the launch
         b->cur[z] ^= 1; ++b->count[z];
         if (reinterpret_cast<volatile uint32_t*>(b->slot(p))[1] != b->h_steps[j].seq) continue;   // never published (a device fault): finish_step
-        ++b->call[z];                                  // returns before it advances the Philox position or reads u
-        volatile float* sl = reinterpret_cast<volatile float*>(b->slot(p));
-        if (u_out) {
-            u_out[(size_t)j * b->C] = sl[0];
-            for (int cc = 1; cc < b->C; ++cc) u_out[(size_t)j * b->C + cc] = sl[4 + cc];   // publish_u_vec
-        }
+        ++b->call[z];                                  // returns before it advances the Philox position or reads u (as CEM; MPPI advances it regardless, by history)
+        batch_read_u(b, p, j, u_out);                  // no error word to read here: this kernel has no in-launch hand-off (MPPI and CEM have)
     }
-    if (le != hipSuccess) return rfail(b, CTK_ERR_HIP, std::string("ctk_rpgd_batch_step: ") + hipGetErrorString(le));
-    if (!late.empty()) return rfail(b, CTK_ERR_HIP, "ctk_rpgd_batch_step: the step finished without publishing the result of problem(s) " + late);
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_rpgd_batch_step: ") + hipGetErrorString(le));
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_rpgd_batch_step: the step finished without publishing the result of problem(s) " + late);
     return CTK_OK;
 }
 
 int ctk_rpgd_batch_read(ctk_rpgd_batch* b, int problem, int buffer, float* dst, size_t cap) {
-    if (!b || !dst) return b ? rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: NULL destination") : CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = rpgd_batch_problem(b, "ctk_rpgd_batch_read", problem)) return rc;
+    if (!b || !dst) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: NULL destination") : CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, "ctk_rpgd_batch_read", problem)) return rc;
     const size_t z = (size_t)problem, N = (size_t)b->N, NHC = b->NHC();
     const int cur = b->cur[z];
     const float* src = nullptr; size_t n = 0; bool is_int = false;
@@ -3964,29 +3812,29 @@ int ctk_rpgd_batch_read(ctk_rpgd_batch* b, int problem, int buffer, float* dst, 
         case CTK_BUF_J: src = b->d_J + z * N; n = N; break;
         case CTK_BUF_U_NOM: src = b->d_unom + z * b->HC; n = (size_t)b->HC; break;
         case CTK_BUF_BEST_IDX: src = reinterpret_cast<const float*>(b->d_idx + z * N); n = (size_t)b->K; is_int = true; break;
-        default: return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: an RPGD batch has Q, J, U_NOM, PLAN, ADAM_M, ADAM_V, AGES, AGES_LOGGED and BEST_IDX");
+        default: return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: an RPGD batch has Q, J, U_NOM, PLAN, ADAM_M, ADAM_V, AGES, AGES_LOGGED and BEST_IDX");
     }
-    if (cap < n) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: destination too small (" + std::to_string(n) + " floats)");
-    RHIP_TRY(b, hipSetDevice(b->cfg.device));
-    RHIP_TRY(b, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    RHIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (cap < n) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: destination too small (" + std::to_string(n) + " floats)");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
     if (is_int) for (size_t i = 0; i < n; ++i) { int v; std::memcpy(&v, &dst[i], 4); dst[i] = (float)v; }
     return CTK_OK;
 }
 
 int ctk_rpgd_batch_get_state(ctk_rpgd_batch* b, int problem, float* dst, size_t cap) {
     if (!b || !dst) return CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = rpgd_batch_problem(b, "ctk_rpgd_batch_get_state", problem)) return rc;
-    if (cap < b->state_size()) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_get_state: destination too small (" + std::to_string(b->state_size()) + " floats)");
+    if (int rc = batch_problem(b, "ctk_rpgd_batch_get_state", problem)) return rc;
+    if (cap < b->state_size()) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_get_state: destination too small (" + std::to_string(b->state_size()) + " floats)");
     const size_t z = (size_t)problem, N = (size_t)b->N, NHC = b->NHC();
     const int cur = b->cur[z];
-    RHIP_TRY(b, hipSetDevice(b->cfg.device));
-    RHIP_TRY(b, hipMemcpyAsync(dst, b->d_pop[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    RHIP_TRY(b, hipMemcpyAsync(dst + NHC, b->d_m[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    RHIP_TRY(b, hipMemcpyAsync(dst + 2 * NHC, b->d_v[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    RHIP_TRY(b, hipMemcpyAsync(dst + 3 * NHC, b->d_ages[cur] + z * N, N * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    RHIP_TRY(b, hipMemcpyAsync(dst + 3 * NHC + N, b->u(problem), (size_t)b->C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    RHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipMemcpyAsync(dst, b->d_pop[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(dst + NHC, b->d_m[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(dst + 2 * NHC, b->d_v[cur] + z * NHC, NHC * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(dst + 3 * NHC, b->d_ages[cur] + z * N, N * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(dst + 3 * NHC + N, b->u(problem), (size_t)b->C * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
     dst[3 * NHC + N + b->C] = (float)b->adam_step[z];
     dst[3 * NHC + N + b->C + 1] = (float)b->count[z];
     return CTK_OK;
@@ -3994,73 +3842,35 @@ int ctk_rpgd_batch_get_state(ctk_rpgd_batch* b, int problem, float* dst, size_t 
 
 int ctk_rpgd_batch_set_state(ctk_rpgd_batch* b, int problem, const float* src, size_t n) {
     if (!b || !src) return CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = rpgd_batch_problem(b, "ctk_rpgd_batch_set_state", problem)) return rc;
-    if (n != b->state_size()) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_set_state: wrong state size (" + std::to_string(b->state_size()) + " floats)");
+    if (int rc = batch_problem(b, "ctk_rpgd_batch_set_state", problem)) return rc;
+    if (n != b->state_size()) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_set_state: wrong state size (" + std::to_string(b->state_size()) + " floats)");
     const size_t z = (size_t)problem, N = (size_t)b->N, NHC = b->NHC();
     const int cur = b->cur[z];
-    RHIP_TRY(b, hipSetDevice(b->cfg.device));
-    RHIP_TRY(b, hipMemcpyAsync(b->d_pop[cur] + z * NHC, src, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    RHIP_TRY(b, hipMemcpyAsync(b->d_m[cur] + z * NHC, src + NHC, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    RHIP_TRY(b, hipMemcpyAsync(b->d_v[cur] + z * NHC, src + 2 * NHC, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    RHIP_TRY(b, hipMemcpyAsync(b->d_ages[cur] + z * N, src + 3 * NHC, N * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    RHIP_TRY(b, hipMemcpyAsync(b->u(problem), src + 3 * NHC + N, (size_t)b->C * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    BHIP_TRY(b, hipMemcpyAsync(b->d_pop[cur] + z * NHC, src, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(b->d_m[cur] + z * NHC, src + NHC, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(b->d_v[cur] + z * NHC, src + 2 * NHC, NHC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(b->d_ages[cur] + z * N, src + 3 * NHC, N * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(b->u(problem), src + 3 * NHC + N, (size_t)b->C * sizeof(float), hipMemcpyHostToDevice, b->stream));
     b->adam_step[z] = (int)src[3 * NHC + N + b->C]; b->count[z] = (int)src[3 * NHC + N + b->C + 1];
     b->ready[z] = 1;
-    RHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
     return CTK_OK;
 }
 
-int ctk_rpgd_batch_set_param(ctk_rpgd_batch* b, int id, float value) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (id < 0 || id >= env_info(b->env)->n_params) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_set_param: unknown parameter id for this environment");
-    b->params[id] = value;                             // the shared table: the shared form derives its constants from it at each launch
-    for (int p = 0; p < b->B; ++p) { b->table(p)[id] = value; b->dirty[(size_t)p] = 1; }   // column id of every problem; the other ids stay
-    return CTK_OK;
-}
-
-int ctk_rpgd_batch_get_param(const ctk_rpgd_batch* b, int id, float* value) {
-    if (!b || !value || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
-    *value = b->params[id];
-    return CTK_OK;
-}
-
+int ctk_rpgd_batch_set_param(ctk_rpgd_batch* b, int id, float value) { return batch_set_param(b, "ctk_rpgd_batch_set_param", id, value); }
+int ctk_rpgd_batch_get_param(const ctk_rpgd_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
 int ctk_rpgd_problem_set_param(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = rpgd_batch_ids(b, "ctk_rpgd_problem_set_param", n_ids, ids, &n)) return rc;
-    if (id < 0 || id >= env_info(b->env)->n_params) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_problem_set_param: unknown parameter id for this environment");
-    if (!values) return rfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_problem_set_param: NULL values (one value per listed problem)");
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        b->table(p)[id] = values[j];
-        b->dirty[(size_t)p] = 1;                       // derived when the problem is next stepped: no cost until then
-    }
-    if (!b->differ) {                                  // sticky: the tables are never compared again
-        b->differ = true;
-        b->dominant = ctk_g_rpgd_batch_name(b->env, true);
-    }
-    return CTK_OK;
+    bool flipped = false;
+    const int rc = batch_problem_set_param(b, "ctk_rpgd_problem_set_param", n_ids, ids, id, values, &flipped);
+    if (flipped) b->dominant = ctk_g_rpgd_batch_name(b->env, true);
+    return rc;
 }
-
-int ctk_rpgd_problem_get_param(const ctk_rpgd_batch* b, int problem, int id, float* value) {
-    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
-    *value = b->table(problem)[id];
-    return CTK_OK;
-}
-
-int ctk_rpgd_problem_params_differ(const ctk_rpgd_batch* b) { return b && b->differ ? 1 : 0; }
-
-int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32_t* call) {
-    if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
-    *call = b->call[(size_t)problem];
-    return CTK_OK;
-}
-
+int ctk_rpgd_problem_get_param(const ctk_rpgd_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
+int ctk_rpgd_problem_params_differ(const ctk_rpgd_batch* b) { return batch_params_differ(b); }
+int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
 int ctk_rpgd_batch_rng_set_position(ctk_rpgd_batch* b, int problem, uint32_t call) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = rpgd_batch_problem(b, "ctk_rpgd_batch_rng_set_position", problem)) return rc;
-    b->call[(size_t)problem] = call;
-    return CTK_OK;
+    return batch_rng_set_position(b, "ctk_rpgd_batch_rng_set_position", problem, call);
 }
 
 }  // extern "C"

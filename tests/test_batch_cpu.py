@@ -151,3 +151,60 @@ def test_valid_batch_without_a_gpu_fails_loudly():
         CtkMppiBatch(3, seeds=[5, 6, 2 ** 63 + 1], environment="Quad2D", num_rollouts=64, mpc_horizon=10, dt=0.02)
     with pytest.raises(TypeError, match="unknown engine arguments"):
         CtkMppiBatch(3, nonsense=1, **KW)
+
+
+# The public interface of the four batch classes, as it stood before they were given one base class: every public method of each class
+# with str(inspect.signature(...)), the constructor among them.  A method that moves into the base keeps its name and signature here.
+_CTOR_TAIL = ("num_rollouts: 'int', mpc_horizon: 'int', dt: 'float', action_low: 'float' = -1.0, action_high: 'float' = 1.0, "
+              "period_interpolation_inducing_points: 'int' = 1, seed: 'int' = 0, device: 'int' = 0, intermediate_steps: 'int' = 1, "
+              "materialize_trajectories: 'bool' = False, global_rollout_offset: 'int' = 0, num_states: 'int' = None, "
+              "num_control_inputs: 'int' = None, generic_kernels: 'bool' = %s, **kw)")
+_COMMON = {
+    "close": "(self)",
+    "dominant_kernel": "(self) -> 'str'",
+    "get_param": "(self, name: 'str') -> 'float'",
+    "get_problem_param": "(self, name: 'str', problem: 'int') -> 'float'",
+    "get_problem_params": "(self, name: 'str') -> 'np.ndarray'",
+    "get_state": "(self, problem: 'int') -> 'np.ndarray'",
+    "params_differ": "(self) -> 'int'",
+    "read": "(self, name: 'str', problem: 'int') -> 'np.ndarray'",
+    "read_all": "(self, name: 'str') -> 'np.ndarray'",
+    "rng_position": "(self, problem: 'int') -> 'int'",
+    "set_param": "(self, name: 'str', value: 'float')",
+    "set_problem_params": "(self, name: 'str', values, ids=None)",
+    "set_rng_position": "(self, problem: 'int', call: 'int')",
+    "set_state": "(self, problem: 'int', state)",
+    "step": "(self, S, samples=None, u_prev=None, ids=None) -> 'np.ndarray'",
+}
+INTERFACE = {
+    "CtkMppiBatch": dict(
+        _COMMON, reset="(self, ids=None)", samples_needed="(self) -> 'int'",
+        __init__="(self, num_problems: 'int', *, environment: 'str' = 'CartPole', seeds=None, optimizer: 'str' = 'mppi', "
+                 "predictor: 'str' = 'ODE', " + _CTOR_TAIL % "False"),
+    "CtkMppiMlpBatch": dict(
+        _COMMON, reset="(self, ids=None)", samples_needed="(self) -> 'int'", have_weights="(self, problem: 'int') -> 'bool'",
+        set_problem_weights="(self, W, ids=None)", set_weights="(self, w)", weight_count="(self) -> 'int'",
+        __init__="(self, num_problems: 'int', *, seeds=None, predictor_hidden=None, environment: 'str' = 'CartPole', "
+                 "optimizer: 'str' = 'mppi', predictor: 'str' = 'MLP', " + _CTOR_TAIL % "False"),
+    "CtkCemBatch": dict(
+        _COMMON, reset="(self, ids=None)", samples_needed="(self, problem: 'int' = 0) -> 'int'",
+        __init__="(self, num_problems: 'int', *, environment: 'str' = 'CartPole', seeds=None, optimizer: 'str' = 'cem', "
+                 "predictor: 'str' = 'ODE', " + _CTOR_TAIL % "False"),
+    "CtkRpgdBatch": dict(
+        _COMMON, reset="(self, draws=None, ids=None)", samples_needed="(self, problem: 'int' = 0) -> 'int'",
+        samples_needed_reset="(self) -> 'int'", state_size="(self) -> 'int'", descent_lds="(environment: 'str', mpc_horizon: 'int')",
+        __init__="(self, num_problems: 'int', *, environment: 'str' = 'CartPole', seeds=None, optimizer: 'str' = 'rpgd', "
+                 "predictor: 'str' = 'ODE', " + _CTOR_TAIL % "None"),
+}
+
+
+@pytest.mark.parametrize("cname", sorted(INTERFACE))
+def test_public_interface_of_the_batch_classes_is_pinned(cname):
+    import inspect
+    from control_toolkit_amd import _capi
+    cls = getattr(_capi, cname)
+    have = {n: str(inspect.signature(getattr(cls, n))) for n in dir(cls) if (not n.startswith("_") or n == "__init__") and callable(getattr(cls, n))}
+    assert set(have) == set(INTERFACE[cname]), sorted(set(have) ^ set(INTERFACE[cname]))
+    for n, sig in INTERFACE[cname].items():
+        assert have[n] == sig, f"{cname}.{n}: {have[n]}"
+    assert issubclass(_capi.CtkMppiMlpBatch, _capi.CtkMppiBatch)
