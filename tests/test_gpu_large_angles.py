@@ -209,7 +209,8 @@ TP_STATES = L.TP_STATES
 def test_mppi_throughput_kernels(kernel, p, generic, isteps):
     """the smallest N that selects them, H = 6 as in test_mppi_throughput_variants_match_oracle: the streaming kernel (period 1, draws in a
     buffer; its second pass re-reads the draws from global memory and rebuilds the four input sums another way), the whole-tile kernel
-    (P < H) and the template's one-wave kernel; intermediate_steps = 2 always takes the checked recurrence"""
+    (P < H) and the template's one-wave kernel; intermediate_steps = 2 always takes the checked recurrence (true of CartPole, the only
+    environment these kernels are run for here: Quad2D and Hover keep their sub-step loop inside the fast path, test_gpu_substeps.py)"""
     env = "CartPole"
     engines = [engine("mppi", env, num_rollouts=TP_N, mpc_horizon=TP_H, period_interpolation_inducing_points=p, intermediate_steps=isteps,
                       materialize_trajectories=log, generic_kernels=generic) for log in (True, False)]

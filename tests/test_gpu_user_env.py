@@ -172,6 +172,41 @@ def test_user_env_cem_random_and_plain_rollouts_match_oracle(pendulum):
     er.close()
 
 
+def test_user_env_with_euler_substeps_matches_oracle(pendulum):
+    """intermediate_steps = 2: the sub-step loop of the model header (CtkUserEnv::step) under one MPPI step and one CEM step, at the bounds of
+    the two tests above; the library is the one the fixture built"""
+    env = PendulumParams(terminal_weight=0.5, target_angle=0.1)
+    pred, cost = PendulumPredictor("ODE", dt=0.02, env=env, intermediate_steps=2), PendulumCost(env)
+    rng = np.random.default_rng(12)
+    s = np.array([2.6, -0.4], f32)
+    one = PendulumPredictor("ODE", dt=0.02, env=env).step(s.reshape(1, 2), np.array([[0.5]], f32))
+    assert np.abs(pred.step(s.reshape(1, 2), np.array([[0.5]], f32)) - one).max() > 1e-5        # the restatement's sub-steps do something
+    N, H, p = 200, 30, 10
+    o = O.MPPI(pred, cost, num_rollouts=N, mpc_horizon=H, period_interpolation_inducing_points=p)
+    e = engine(pendulum, "mppi", env, num_rollouts=N, mpc_horizon=H, period_interpolation_inducing_points=p, materialize_trajectories=True,
+               intermediate_steps=2)
+    noise = rng.standard_normal((N, o.P, 1)).astype(f32)
+    uo, ug = o.step(s, noise), e.step(s, noise)
+    np.testing.assert_allclose(e.read("TRAJ"), o.rollout_trajectories, rtol=1e-4, atol=3e-5)
+    np.testing.assert_allclose(e.read("J"), o.J, rtol=3e-5)
+    np.testing.assert_allclose(e.read("U_NOM"), o.u_nom, **U_TOL)
+    np.testing.assert_allclose(ug[0], uo, **U_TOL)
+    assert "<3," in e.dominant_kernel(), e.dominant_kernel()
+    e.close()
+    N, H, K, its = 512, 25, 50, 3
+    o = O.CEM(pred, cost, num_rollouts=N, mpc_horizon=H, cem_outer_it=its, cem_best_k=K)
+    e = engine(pendulum, "cem", env, num_rollouts=N, mpc_horizon=H, cem_outer_it=its, cem_best_k=K, materialize_trajectories=True, intermediate_steps=2)
+    noise = rng.standard_normal((its, N, H, 1)).astype(f32)
+    uo, ug = o.step(s, noise), e.step(s, noise)
+    np.testing.assert_allclose(e.read("Q"), o.Q, rtol=1e-5, atol=2e-6)
+    np.testing.assert_allclose(e.read("J"), o.J, rtol=3e-5)
+    np.testing.assert_allclose(e.read("U_NOM"), o.dist_mue, rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(e.read("STD"), o.stdev, rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(ug[0], uo, rtol=1e-5, atol=2e-6)
+    assert e.dominant_kernel().startswith("ctk_cem_fused<3"), e.dominant_kernel()
+    e.close()
+
+
 @pytest.mark.parametrize("N,H,p,its", [(64, 20, 5, 5), (256, 50, 10, 3)])
 def test_user_env_rpgd_matches_oracle(pendulum, N, H, p, its):
     """reverse mode through the user model: step_vjp, stage / terminal / input gradients"""
