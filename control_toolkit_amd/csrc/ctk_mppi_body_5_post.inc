@@ -144,7 +144,11 @@
                 if (blockIdx.x == 0) {
                     bool late = false;                // the bounded poll ran out: error word 2, as in the tail
                     const float o = mppi_early_u<CTK_MPPI_FUSE_MAX_BLOCKS_LL / 64>(fz.ll, (int)gridDim.x, P, c0, eu_w0, eu_w1, eu_un, m.neg_inv_lbd,
-                                                                                  fz.up.lo, fz.up.hi, fz.up.seq, &late);
+                                                                                  fz.up.lo, fz.up.hi, fz.up.seq, &late
+#ifdef CTK_STAMPS
+                                                                                  , a.stamps
+#endif
+                                                                                  );
                     STAMP(11);                        // u formed (stamp 7 below: published)
                     if (lane == 0) {
                         // ctk_api.hip:finish_step turns a non-zero error word (the dword behind {u, seq}) into CTK_ERR_STATE

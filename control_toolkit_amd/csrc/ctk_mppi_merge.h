@@ -286,34 +286,100 @@ __device__ __attribute__((noinline)) bool ll_poll_stage_call(const unsigned long
 // a_tot = red[0] + red[1] + red[2] + red[3] with red[k] the wave_sum of lanes' a_i*sc_i of batch k (zero for an absent batch), the two
 // columns as acc += rec_i * sc_i over i = 0 .. nb-1 from zero; then mppi_update_entry.  The value is therefore bit for bit the
 // u_nom_out[0] that the final update stores later.  *expired: the bounded poll ran out (the missing words enter as NaN, as in the tail).
-template <int NB>
+//
+// The poll is a software pipeline of LL_EARLY_DEPTH passes: a ring of LL_EARLY_DEPTH x NB x 4 words in registers, statically unrolled.
+// A pass loads every lane's eight words into its slot; while it is outstanding the next pass goes out into the next slot, one sleep
+// behind it, and the OLDEST pass is checked behind a partial wait (loads return in order: vmcnt(loads of the younger passes)).  A word
+// seen keeps the value of the pass that saw it (v[][]); a slot whose pass missed a word is issued again.  The loop ends on the first
+// pass after which every word is there; a younger pass still in flight is not used and not waited for (its registers are dead).  A
+// single-pass poll pays one full memory round trip per look, so a block that lags block 0 by a few hundred cycles costs u a second
+// round trip; here the second look follows the first by the sleep.  The slots start with a sequence number that cannot match, so
+// the first LL_EARLY_DEPTH - 1 checks are of nothing and the loop needs no prologue of loads (the kernel body keeps to 4 x NB x
+// LL_EARLY_DEPTH polling loads: tests/test_mppi_recurrence_isa.py).  Bound: LL_POLL_SPINS passes, as before.
+// stamps (diagnostic builds, tools/diag_mppi_stamps.hip): [12] first pass issued, [13] the pass that completed returned, [14] passes issued.
+#ifdef CTK_STAMPS
+CTK_DEV unsigned long long ll_stamp_time() {          // (kept in a register: a store inside the poll would join its loads' counter)
+    __builtin_amdgcn_sched_barrier(0);
+    unsigned long long t;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#endif
+constexpr int LL_EARLY_DEPTH = 2;
+#ifndef CTK_EARLY_POLL_SLEEP
+#define CTK_EARLY_POLL_SLEEP 1          // s_sleep argument between two issues (0: none)
+#endif
+template <int NB, int D = LL_EARLY_DEPTH>
 CTK_DEV float mppi_early_u(const unsigned long long* ll, int nb, int P, int c0, float w0, float w1, float un, float neg_inv_lbd,
-                           float lo, float hi, uint32_t seq, bool* expired) {
+                           float lo, float hi, uint32_t seq, bool* expired, [[maybe_unused]] unsigned long long* stamps = nullptr) {
     const int lane = threadIdx.x & 63, rs = 2 + P;
     const bool has1 = c0 + 1 < P;
-    unsigned long long w[NB][4];
+    unsigned long long w[D][NB][4];
+    float v[NB][4];
     unsigned pend = 0;
 #pragma unroll
-    for (int k = 0; k < NB; ++k)
+    for (int k = 0; k < NB; ++k) {
         if (k * 64 + lane < nb) pend |= (has1 ? 0xFu : 0x7u) << (4 * k);
-    for (int spin = 0;; ++spin) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[k][j] = __builtin_nanf("");
+#pragma unroll
+            for (int d = 0; d < D; ++d) w[d][k][j] = (unsigned long long)~seq << 32;
+        }
+    }
+    int spin = 0;                             // passes issued
+#ifdef CTK_STAMPS
+    unsigned long long t_first = 0;
+#endif
+    // Every lane loads its eight words in every pass, from addresses that are in bounds for every lane (an absent block: the last
+    // one; the absent fourth word: the third again), and the loop's exit is the wave's: there is NO branch around a load, which is
+    // what lets the compiler count the younger pass (behind a branch it waits vmcnt(0) at the join).  What a pass may TAKE is still
+    // only a word not yet seen: `pend` guards the check.
+    const unsigned long long* rl[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) rl[k] = ll + (size_t)min(k * 64 + lane, nb - 1) * rs;
+    const int o2 = c0 + 2, o3 = has1 ? c0 + 3 : c0 + 2;
+    auto issue = [&](int d) {
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
-            const unsigned long long* rl = ll + (size_t)(k * 64 + lane) * rs;
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if ((pend >> (4 * k + j)) & 1u) w[k][j] = __hip_atomic_load(rl + (j < 2 ? j : c0 + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                w[d][k][j] = __hip_atomic_load(rl[k] + (j < 2 ? j : j == 2 ? o2 : o3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+        ++spin;
+    };
+    auto check = [&](int d) {
 #pragma unroll
         for (int k = 0; k < NB; ++k)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (((pend >> (4 * k + j)) & 1u) && (uint32_t)(w[k][j] >> 32) == seq) pend &= ~(1u << (4 * k + j));
-        if (pend == 0 || spin >= LL_POLL_SPINS) break;
-        __builtin_amdgcn_s_sleep(1);
-    }
+                if (((pend >> (4 * k + j)) & 1u) && (uint32_t)(w[d][k][j] >> 32) == seq) {
+                    v[k][j] = __builtin_bit_cast(float, (uint32_t)w[d][k][j]);
+                    pend &= ~(1u << (4 * k + j));
+                }
+    };
+    [&] {
+#pragma nounroll
+        for (;;) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                issue((d + D - 1) % D);       // the youngest pass goes out ...
+#ifdef CTK_STAMPS
+                if (spin == 1) t_first = ll_stamp_time();
+#endif
+                check(d);                     // ... and the oldest is looked at: D - 1 passes stay in flight
+                if (__builtin_amdgcn_ballot_w64(pend != 0) == 0 || spin >= LL_POLL_SPINS + D - 1) return;
+                if constexpr (CTK_EARLY_POLL_SLEEP > 0) __builtin_amdgcn_s_sleep(CTK_EARLY_POLL_SLEEP);
+            }
+        }
+    }();
+#ifdef CTK_STAMPS
+    const unsigned long long t_done = ll_stamp_time();
+    if (threadIdx.x == 0 && stamps) { stamps[12] = t_first; stamps[13] = t_done; stamps[14] = (unsigned long long)spin; }   // block 0's row
+#endif
     *expired = __builtin_amdgcn_ballot_w64(pend != 0) != 0;
-    auto val = [&](int k, int j) { return ((pend >> (4 * k + j)) & 1u) ? __builtin_nanf("") : __builtin_bit_cast(float, (uint32_t)w[k][j]); };
+    auto val = [&](int k, int j) { return v[k][j]; };      // (a word never seen: NaN)
 
     float red[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
 #pragma unroll

@@ -30,11 +30,18 @@ int main(int argc, char** argv) {
     MppiFuse fz; fz.mode = argc > 3 ? atoi(argv[3]) : 1; fz.counter = d_cnt; fz.ll = (argc > 4 && atoi(argv[4]) == 0) ? nullptr : d_ll; fz.u_nom_out = d_unom2; fz.u_dev = d_u; fz.u_host = h_u;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     float ms = 0;
+    std::vector<long long> hop, rtt, slack; std::vector<unsigned long long> passes;   // block 0's early poll, launches 4..19
     for (int it = 0; it < 20; ++it) {
         CK(hipEventRecord(e0, 0));
         fz.seq = (uint32_t)(it + 1);
         CK(ctk_launch_mppi_rollout(0, CTK_PRED_ODE, a, k, m, d_noise, d_unom, nullptr, d_parts, false, fz));
         CK(hipEventRecord(e1, 0)); CK(hipDeviceSynchronize()); CK(hipEventElapsedTime(&ms, e0, e1));
+        unsigned long long b0[16];
+        CK(hipMemcpy(b0, d_st, sizeof(b0), hipMemcpyDeviceToHost));
+        if (it >= 4 && b0[11] != 0 && b0[12] != 0) {
+            hop.push_back((long long)(b0[11] - b0[3])); rtt.push_back((long long)(b0[13] - b0[12])); slack.push_back((long long)(b0[12] - b0[3]));
+            passes.push_back(b0[14]);
+        }
     }
     std::vector<unsigned long long> st(nb * 16);
     CK(hipMemcpy(st.data(), d_st, st.size() * 8, hipMemcpyDeviceToHost));
@@ -69,6 +76,20 @@ int main(int argc, char** argv) {
         if (st[7] != 0 && st[11] != 0)        // stamp 11: u formed, ahead of the publish's stores (what the publish itself costs the path)
             printf("  early publish of u, block 0: J ready -> u formed %lld cycles; u formed -> published %lld cycles\n",
                    (long long)(st[11] - st[3]), (long long)(st[7] - st[11]));
+        if (st[12] != 0) {
+            // inside the early poll (stamps 12, 13, word 14; ctk_mppi_merge.h: mppi_early_u).  With `passes` = 2 the first pass found every
+            // word: "first pass issued -> returned" is then one memory round trip plus the spacing of the second issue
+            printf("  early poll, block 0: J ready -> first pass issued %lld cycles; first pass issued -> completing pass returned %lld; returned -> u formed %lld; passes issued %llu\n",
+                   (long long)(st[12] - st[3]), (long long)(st[13] - st[12]), (long long)(st[11] - st[13]), st[14]);
+            auto line = [](const char* nm, std::vector<long long> d) {
+                std::sort(d.begin(), d.end());
+                printf("    %-44s min %6lld  median %6lld  max %6lld   (launches 4..19)\n", nm, d.front(), d[d.size() / 2], d.back());
+            };
+            line("J ready -> u formed", hop); line("J ready -> first pass issued", slack); line("first pass issued -> completing pass returned", rtt);
+            printf("    passes issued per launch:");
+            for (auto p : passes) printf(" %llu", p);
+            printf("\n");
+        }
         if (st[7] != 0)
             printf("  early publish of u, block 0: J ready -> publish %lld cycles; publish -> kernel end %lld cycles  (J ready -> barrier, blocks 1..: median %.0f)\n",
                    (long long)(st[7] - st[3]), (long long)(st[6] - st[7]), a_step[a_step.size() / 2]);
