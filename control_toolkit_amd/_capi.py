@@ -210,6 +210,17 @@ SYMBOLS = {
     "ctk_mlp_problem_have_weights": (C.c_int, [_H, C.c_int]),
 }
 
+# closed-loop episodes of the MPPI batches on the device (include/ctk_hip_run.h, which ctk_hip.h includes): the same table for the entry
+# points declared there; _bind_library binds both
+_PLANT_RUN = {
+    "plant_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "plant_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
+    "plant_clear_params": (C.c_int, [_H]),
+    "plant_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "run": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+RUN_SYMBOLS = {f"{family}_{name}": sig for family in ("ctk_batch", "ctk_mlp_batch") for name, sig in _PLANT_RUN.items()}
+
 
 # user environments (include/ctk_user_env.h): name -> path of the library that was compiled with that model (control_toolkit_amd/build_env.py:
 # register_environment); their environment id inside that library is CTK_ENV_USER
@@ -253,7 +264,7 @@ def _bind_library(path: str):
         lib = C.CDLL(path)
     except OSError as e:
         raise CtkError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctk_abi_version() != 6:
@@ -784,6 +795,29 @@ def batch_step_args(num_problems: int, S: int, Cn: int, per_problem: int, states
     return idv, n, samples
 
 
+def batch_run_args(num_problems: int, S: int, Cn: int, states, steps, u_prev=None, ids=None, plant_substeps=None, samples=None,
+                   what=None):
+    """Checks the arguments of CtkMppiBatch.run / plant_step without touching a device, the way batch_step_args checks a step's: ids,
+    start states [n, S], u_prev None or [n, C] (what: the names a plant step's messages give the two), steps >= 1, plant_substeps None or >= 1, and samples, which must be None (a run draws
+    from the device Philox only).  Returns (ids, n, the sub-step count as the library takes it: 0 = the controller's)."""
+    if samples is not None:
+        raise NotImplementedError("a run draws from the device Philox only: it has no place for per-step host or device sample buffers "
+                                  "(samples must be None; step() takes them)")
+    try:
+        idv, n, _ = batch_step_args(num_problems, S, Cn, 0, states, None, u_prev, ids)
+    except ValueError as e:
+        if what is None:
+            raise
+        raise ValueError(str(e).replace("states must", f"{what[0]} must").replace("u_prev must", f"{what[1]} must")) from None
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+        raise ValueError(f"a run has at least one step (steps == {steps!r})")
+    if plant_substeps is None:
+        return idv, n, 0
+    if isinstance(plant_substeps, bool) or not isinstance(plant_substeps, (int, np.integer)) or plant_substeps < 1:
+        raise ValueError(f"plant_substeps must be an integer >= 1 or None (the controller's intermediate_steps), got {plant_substeps!r}")
+    return idv, n, int(plant_substeps)
+
+
 _F32_MAX = float(np.finfo(np.float32).max)
 
 
@@ -1025,9 +1059,91 @@ class CtkMppiBatch(_CtkBatch):
         N, H, S, Cn = self.N, self.H, self.S, self.C
         return self._read("a batch", {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn)}, name, problem)
 
+    @property
+    def closed_loop(self) -> "BatchClosedLoop":
+        """closed-loop episodes on the device, plant step included: closed_loop.run(S0, steps), .plant_step(S, U), .set_plant_params,
+        .get_plant_params, .clear_plant_params (BatchClosedLoop).  A view of this batch: it owns nothing."""
+        return BatchClosedLoop(self)
+
     def get_state(self, problem: int) -> np.ndarray:
         return self._get_state(problem, self.H * self.C + self.C)
 
+
+# ---- closed-loop episodes of an MPPI batch on the device (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_*) ---------------------------
+class BatchClosedLoop:
+    """CtkMppiBatch.closed_loop / CtkMppiMlpBatch.closed_loop: the batch's closed loops run on the device (kernel ctk_batch_plant<ENV>
+    between the controller launches), and the plants they run against.  Problem p's plant has, for every parameter, the value set here
+    (set_plant_params), else the problem's own current controller value: a batch that sets none controls exactly the plant it models.
+    For the MLP batch the learned network plans and the plant is the analytic CartPole."""
+
+    def __init__(self, batch):
+        self._batch = batch
+
+    def _entry(self, name: str):
+        return getattr(self._batch._lib, f"{self._batch._BATCH}_{name}")
+
+    @property
+    def last_run_first_bad(self):
+        """[n] per problem of the last run: the first step whose input is not finite, or -1 (None before the first run)"""
+        return getattr(self._batch, "last_run_first_bad", None)
+
+    def run(self, S0, steps: int, u_prev=None, ids=None, plant_substeps=None, samples=None):
+        """`steps` closed-loop MPC steps of the problems in ids (None: all) from the states S0 [n, num_states], the plant integrated on
+        the device between the controller launches: bit for bit the loop `u = batch.step(S); S = plant_step(S, u)`.  u_prev [n, C] is the
+        first step's previous input (None: every problem's own last output).  plant_substeps: the plant's Euler sub-steps per dt (None:
+        the controller's intermediate_steps).  The draws are the device Philox's: a run has no place for per-step sample buffers
+        (samples must stay None).  Returns (states [n, steps + 1, S], inputs [n, steps, C]); last_run_first_bad [n] (here and on the
+        batch) is, per problem, the first step whose input is not finite, or -1.  CtkError naming the problems whose in-launch hand-off
+        timed out in some step: the traces are then in batch.last_run, valid for the other problems."""
+        b = self._batch
+        idv, n, sub = batch_run_args(b.B, b.S, b.C, S0, steps, u_prev, ids, plant_substeps, samples)
+        ids_p, up_p, _, _ = b._step_args(n, idv, S0, u_prev, None)
+        states = np.empty((n, int(steps) + 1, b.S), np.float32)
+        inputs = np.empty((n, int(steps), b.C), np.float32)
+        bad = np.full(n, -1, np.int32)
+        rc = self._entry("run")(b._h, n, ids_p, b._s_p, up_p, int(steps), sub, _ptr(states), _ptr(inputs), _ptr(bad))
+        b.last_run_first_bad = bad
+        if rc:
+            b.last_run = (states, inputs)
+            b._check(rc)
+        return states, inputs
+
+    def plant_step(self, S, U, ids=None, plant_substeps=None) -> np.ndarray:
+        """one step of the plants of the problems in ids (None: all) on the device: S [n, num_states], U [n, C] in the units step()
+        returns.  Returns the next states [n, num_states].  No controller state, sequence number or Philox position changes."""
+        b = self._batch
+        idv, n, sub = batch_run_args(b.B, b.S, b.C, S, 1, U, ids, plant_substeps, None, what=("S", "U"))
+        if U is None:
+            raise ValueError(f"U must have shape ({n}, {b.C}): one row per listed problem, got None")
+        s = _f32(np.asarray(S).reshape(n, b.S))
+        u = _f32(np.asarray(U).reshape(n, b.C))
+        out = np.empty((n, b.S), np.float32)
+        b._check(self._entry("plant_step")(b._h, n, _ptr(idv), _ptr(s), _ptr(u), sub, _ptr(out)))
+        return out
+
+    def set_plant_params(self, name: str, values, ids=None):
+        """parameter `name` of the PLANTS of the problems in ids (None: all): values a scalar or [n].  The controllers keep planning with
+        their own values (set_param / set_problem_params); a plant parameter that was never set here follows its problem's controller."""
+        b = self._batch
+        pid, idv, n, vals = batch_param_args(b.param_names, b.B, name, values, ids)
+        b._check(self._entry("plant_set_param")(b._h, n, _ptr(idv), pid, _ptr(vals)))
+
+    def get_plant_params(self, name: str) -> np.ndarray:
+        """[B] parameter `name` of every problem's plant: the override, else the problem's own controller value"""
+        b = self._batch
+        if name not in b.param_names:
+            raise ValueError(f"unknown parameter {name!r} for this environment (it has {', '.join(b.param_names)})")
+        v, out = C.c_float(), np.empty(b.B, np.float32)
+        for p in range(b.B):
+            if self._entry("plant_get_param")(b._h, p, b.param_names.index(name), C.byref(v)) != 0:
+                raise CtkError(f"{b._BATCH}_plant_get_param({p}, {name!r}) failed")
+            out[p] = v.value
+        return out
+
+    def clear_plant_params(self):
+        """drop every plant override: each plant is again the one its controller models"""
+        b = self._batch
+        b._check(self._entry("plant_clear_params")(b._h))
 
 # ---- batched MPPI with the MLP predictor (include/ctk_hip.h: ctk_mlp_batch_* / ctk_mlp_problem_*) --------------------------------------
 def mlp_weight_count(num_states: int, num_control_inputs: int, hidden=(32, 32)) -> int:

@@ -2655,6 +2655,18 @@ struct ctk_batch : BatchCore {
     float* d_w = nullptr;                   // [B][wtab] problem p's table, in the layout of a handle's d_wperm
     float* h_w = nullptr;                   // pinned [B][wtab]: the staging of ONE transfer per weight call
     std::vector<unsigned char> have_w;      // [B] the problem has received weights
+    // the closed loop on the device (ctk_batch_run / ctk_batch_plant_step; kernel ctk_batch_plant<ENV>, ctk_plant.hip).  Problem p's PLANT
+    // has, for parameter id, the override if one was set (ctk_batch_plant_set_param), else the problem's own controller value table(p)[id]
+    std::vector<float> plant_over;          // [B][CTK_MAX_PARAMS] the overrides
+    std::vector<unsigned char> plant_has;   // [B][CTK_MAX_PARAMS] an override was set
+    std::vector<float> plant_tab;           // [B][CTK_MAX_PARAMS] the effective table the constants in h_kplant were derived from
+    std::vector<int> plant_sub;             // [B] ... and their Euler sub-step count (0: nothing derived yet)
+    unsigned char* h_kplant = nullptr;      // pinned [B][kstride] the plants' derived constants, the staging of the copy to d_kplant
+    unsigned char* d_kplant = nullptr;      // [B][kstride]
+    unsigned char* h_run = nullptr;         // pinned: step records [L][n] | inputs of a plant step [n][C] | state trace [n][L][S] | input trace [n][L][C]
+    unsigned char* d_run = nullptr;         // the same on the device; both grow on demand (batch_run_buffers)
+    size_t run_cap = 0;
+    int run_segment = 256;                  // steps per segment of a run: a diagnostic switch may lower it (ctk_batch_create)
     size_t unom_stride() const { return (size_t)2 * HC; }
     float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
 };
@@ -2690,6 +2702,25 @@ hipError_t batch_flush_constants(ctk_batch* b) {
     return e;
 }
 
+// The controller launches of n step records from steps_dev on (ctk_batch_step; every step of ctk_batch_run): consecutive launches of at
+// most max_per_launch problems — the results do not depend on the split.  *launched: the records that were launched.
+hipError_t batch_launch_records(ctk_batch* b, const RolloutArgs& a, const CtkBatchStep* steps_dev, int n, int* launched) {
+    const bool log = b->cfg.materialize_trajectories != 0;
+    hipError_t le = hipSuccess;
+    *launched = 0;
+    while (le == hipSuccess && *launched < n) {
+        const int cnt = std::min(b->max_per_launch, n - *launched);
+        if (b->pred == CTK_PRED_MLP)
+            le = ctk_launch_mppi_batch_mlp(b->stream, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
+                                           b->d_w, b->differ ? b->d_k : nullptr);
+        else
+            le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
+                                       b->differ ? b->d_k : nullptr);
+        if (le == hipSuccess) *launched += cnt;
+    }
+    return le;
+}
+
 // optimizer_reset() of problem p (ctk_reset of an MPPI handle): the plan at mid-range in buffer 0; u, the Philox position stay
 int batch_reset_one(ctk_batch* b, int p) {
     std::vector<float> tmp((size_t)b->HC);
@@ -2697,6 +2728,62 @@ int batch_reset_one(ctk_batch* b, int p) {
     b->cur[(size_t)p] = 0;
     BHIP_TRY(b, hipMemcpyAsync(b->unom(p, 0), tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
     BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+// ---- the closed loop on the device: the plants' constants and the run buffer (ctk_batch_run / ctk_batch_plant_step) ----
+
+// The plants' constants ahead of a run or a plant step: problem p's effective table (override, else its own controller value) and the
+// sub-step count against what h_kplant was derived from; those that changed are re-derived with the function the controller's
+// constants come from, and the span from the first to the last of them travels in ONE transfer on the batch's stream (none when
+// nothing changed).  The caller synchronises before it returns, so the staging is free again at the next call.
+hipError_t batch_plant_flush(ctk_batch* b, int substeps) {
+    int lo = b->B, hi = -1;
+    float eff[CTK_MAX_PARAMS];
+    for (int p = 0; p < b->B; ++p) {
+        const size_t z = (size_t)p * CTK_MAX_PARAMS;
+        for (int i = 0; i < CTK_MAX_PARAMS; ++i) eff[i] = b->plant_has[z + i] ? b->plant_over[z + i] : b->table(p)[i];
+        if (b->plant_sub[(size_t)p] == substeps && std::memcmp(eff, &b->plant_tab[z], sizeof(eff)) == 0) continue;
+        ctk_mppi_batch_derive_k(b->env, eff, b->cfg.dt, substeps, b->h_kplant + (size_t)p * b->kstride);
+        std::memcpy(&b->plant_tab[z], eff, sizeof(eff));
+        b->plant_sub[(size_t)p] = substeps;
+        lo = std::min(lo, p); hi = p;
+    }
+    if (hi < 0) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(b->d_kplant + (size_t)lo * b->kstride, b->h_kplant + (size_t)lo * b->kstride, (size_t)(hi - lo + 1) * b->kstride,
+                                        hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess) for (int p = lo; p <= hi; ++p) b->plant_sub[(size_t)p] = 0;      // nothing reached the device: derive and copy again
+    return e;
+}
+
+// where the parts of the run buffer lie for n problems and L steps (bytes from its start; every part 16-aligned)
+struct RunLayout {
+    size_t u_in, states, inputs, total;
+    RunLayout(const ctk_batch* b, int n, int L) {
+        auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        u_in = (size_t)L * n * sizeof(CtkBatchStep);
+        states = u_in + up((size_t)n * b->C * sizeof(float));
+        inputs = states + up((size_t)n * L * b->S * sizeof(float));
+        total = inputs + up((size_t)n * L * b->C * sizeof(float));
+    }
+};
+static_assert(sizeof(CtkBatchStep) % 16 == 0, "the parts of the run buffer lie behind the step records, 16-aligned");
+
+int batch_run_buffers(ctk_batch* b, const RunLayout& lay) {
+    if (lay.total <= b->run_cap) return CTK_OK;
+    if (b->d_run) BHIP_TRY(b, hipFree(b->d_run));
+    b->d_run = nullptr; b->run_cap = 0;
+    if (b->h_run) BHIP_TRY(b, hipHostFree(b->h_run));
+    b->h_run = nullptr;
+    BHIP_TRY(b, hipMalloc((void**)&b->d_run, lay.total));
+    BHIP_TRY(b, hipHostMalloc((void**)&b->h_run, lay.total, hipHostMallocDefault));
+    b->run_cap = lay.total;
+    return CTK_OK;
+}
+
+int batch_substeps(ctk_batch* b, const char* who, int substeps, int* out) {
+    if (substeps < 0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": the plant's sub-step count must be >= 1, or 0 for cfg.intermediate_steps (" + std::to_string(substeps) + ")");
+    *out = substeps ? substeps : b->cfg.intermediate_steps;
     return CTK_OK;
 }
 
@@ -2717,8 +2804,11 @@ namespace {
 void batch_release(ctk_batch* b) {
     hipSetDevice(b->cfg.device);
     if (b->stream) hipStreamSynchronize(b->stream);
-    void* bufs[] = {b->d_interp, b->d_J, b->d_Q, b->d_traj, b->d_parts, b->d_ll, b->d_unom, b->d_u, b->d_desc, b->d_steps, b->d_samples, b->d_k, b->d_w};
+    void* bufs[] = {b->d_interp, b->d_J, b->d_Q, b->d_traj, b->d_parts, b->d_ll, b->d_unom, b->d_u, b->d_desc, b->d_steps, b->d_samples, b->d_k, b->d_w,
+                    b->d_kplant, b->d_run};
     for (void* p : bufs) if (p) hipFree(p);
+    if (b->h_kplant) hipHostFree(b->h_kplant);
+    if (b->h_run) hipHostFree(b->h_run);
     if (b->h_u) hipHostFree(b->h_u);
     if (b->h_steps) hipHostFree(b->h_steps);
     if (b->h_k) hipHostFree(b->h_k);
@@ -2793,6 +2883,16 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
         const int v = std::atoi(e);
         if (v >= 1 && v < b->max_per_launch) b->max_per_launch = v;
     }
+    // A long run goes in segments of this many steps, so that its record buffer stays bounded (256 steps of 128 problems: 2.5 MiB of
+    // records).  CTK_BATCH_RUN_SEGMENT_STEPS (diagnostic) only lowers it; the results do not depend on it.
+    if (const char* e = std::getenv("CTK_BATCH_RUN_SEGMENT_STEPS")) {
+        const int v = std::atoi(e);
+        if (v >= 1 && v < b->run_segment) b->run_segment = v;
+    }
+    b->plant_over.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
+    b->plant_has.assign((size_t)n_problems * CTK_MAX_PARAMS, 0);
+    b->plant_tab.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
+    b->plant_sub.assign((size_t)n_problems, 0);
     b->cur.assign((size_t)n_problems, 0);
     b->dominant = mlp ? ctk_mppi_batch_mlp_name(cfg->materialize_trajectories != 0) : ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
     if (mlp) { b->wtab = ctk_mppi_batch_mlp_table_floats(); b->have_w.assign((size_t)n_problems, 0); }
@@ -2824,6 +2924,9 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
     BHIP_CREATE(dev_zero((void**)&b->d_k, Bz * b->kstride));
     BHIP_CREATE(hipHostMalloc((void**)&b->h_k, Bz * b->kstride, hipHostMallocDefault));
     std::memset(b->h_k, 0, Bz * b->kstride);
+    BHIP_CREATE(dev_zero((void**)&b->d_kplant, Bz * b->kstride));
+    BHIP_CREATE(hipHostMalloc((void**)&b->h_kplant, Bz * b->kstride, hipHostMallocDefault));
+    std::memset(b->h_kplant, 0, Bz * b->kstride);
     if (mlp) {
         BHIP_CREATE(dev_zero((void**)&b->d_w, Bz * b->wtab * sizeof(float)));
         BHIP_CREATE(hipHostMalloc((void**)&b->h_w, Bz * b->wtab * sizeof(float), hipHostMallocDefault));
@@ -2899,18 +3002,8 @@ int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, 
     hipError_t le = b->differ ? batch_flush_constants(b) : hipSuccess;          // the constants' transfer goes ahead of the step records'
     if (le == hipSuccess) le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkBatchStep), hipMemcpyHostToDevice, b->stream);
     const RolloutArgs a = batch_args(b);
-    const bool log = b->cfg.materialize_trajectories != 0;
-    int launched = 0;                                  // consecutive launches of at most max_per_launch problems: the results do not depend on the split
-    while (le == hipSuccess && launched < n) {
-        const int cnt = std::min(b->max_per_launch, n - launched);
-        if (b->pred == CTK_PRED_MLP)
-            le = ctk_launch_mppi_batch_mlp(b->stream, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, b->d_steps + launched, cnt, log,
-                                           b->d_w, b->differ ? b->d_k : nullptr);
-        else
-            le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, b->d_steps + launched, cnt, log,
-                                       b->differ ? b->d_k : nullptr);
-        if (le == hipSuccess) launched += cnt;
-    }
+    int launched = 0;
+    if (le == hipSuccess) le = batch_launch_records(b, a, b->d_steps, n, &launched);
     for (int j = 0; j < launched; ++j) b->cur[(size_t)b->h_steps[j].id] ^= 1;
     const std::string late = batch_poll(b, ids, launched);
     std::string timed_out;
@@ -2998,6 +3091,158 @@ int ctk_problem_params_differ(const ctk_batch* b) { return batch_params_differ(b
 int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
 int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) { return batch_rng_set_position(b, "ctk_batch_rng_set_position", problem, call); }
 
+// ---- the closed loop on the device (include/ctk_hip_run.h: ctk_batch_plant_* / ctk_batch_run) ----
+int ctk_batch_plant_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_plant_set_param", n_ids, ids, &n)) return rc;
+    if (int rc = batch_param_id(b, "ctk_batch_plant_set_param", id)) return rc;
+    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_param: NULL values (one value per listed problem)");
+    for (int j = 0; j < n; ++j) {
+        const size_t z = (size_t)(ids ? ids[j] : j) * CTK_MAX_PARAMS + (size_t)id;
+        b->plant_over[z] = values[j];                  // derived at the next run or plant step (batch_plant_flush compares the tables)
+        b->plant_has[z] = 1;
+    }
+    return CTK_OK;
+}
+
+int ctk_batch_plant_get_param(const ctk_batch* b, int problem, int id, float* value) {
+    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    const size_t z = (size_t)problem * CTK_MAX_PARAMS + (size_t)id;
+    *value = b->plant_has[z] ? b->plant_over[z] : b->table(problem)[id];
+    return CTK_OK;
+}
+
+int ctk_batch_plant_clear_params(ctk_batch* b) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    std::fill(b->plant_has.begin(), b->plant_has.end(), (unsigned char)0);
+    return CTK_OK;
+}
+
+int ctk_batch_plant_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u, int substeps, float* s_next) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!s || !u || !s_next) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_step: NULL state, input or destination");
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, "ctk_batch_plant_step", n_ids, ids, &n)) return rc;
+    if (int rc = batch_substeps(b, "ctk_batch_plant_step", substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const RunLayout lay(b, n, 1);
+    if (int rc = batch_run_buffers(b, lay)) return rc;
+    // the records carry the problem and its state only; they and the inputs behind them travel in ONE transfer
+    CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
+    for (int j = 0; j < n; ++j) {
+        std::memset(&rec[j], 0, sizeof(CtkBatchStep));
+        rec[j].id = ids ? ids[j] : j;
+        for (int i = 0; i < b->S; ++i) rec[j].s[i] = s[(size_t)j * b->S + i];
+    }
+    std::memcpy(b->h_run + lay.u_in, u, (size_t)n * b->C * sizeof(float));
+    const size_t out_bytes = (size_t)n * b->S * sizeof(float);
+    hipError_t le = batch_plant_flush(b, sub);
+    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
+    if (le == hipSuccess)
+        le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, reinterpret_cast<const CtkBatchStep*>(b->d_run), nullptr, b->d_kplant,
+                                    reinterpret_cast<const float*>(b->d_run + lay.u_in), reinterpret_cast<float*>(b->d_run + lay.states), nullptr, n,
+                                    (size_t)b->S, 0);
+    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, out_bytes, hipMemcpyDeviceToHost, b->stream);
+    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
+    if (le == hipSuccess) le = se;
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_plant_step: ") + hipGetErrorString(le));
+    std::memcpy(s_next, b->h_run + lay.states, out_bytes);
+    return CTK_OK;
+}
+
+int ctk_batch_run(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, const float* u_prev, int n_steps, int plant_substeps,
+                  float* states_out, float* inputs_out, int32_t* first_bad) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!s0 || !states_out || !inputs_out) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_run: NULL start states or trace destination");
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, "ctk_batch_run", n_ids, ids, &n)) return rc;
+    if (n_steps < 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_run: a run has at least one step (n_steps == " + std::to_string(n_steps) + ")");
+    if (int rc = batch_substeps(b, "ctk_batch_run", plant_substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const size_t srow = ((size_t)n_steps + 1) * S, urow = (size_t)n_steps * C;       // one problem's rows of the two traces
+    for (int j = 0; j < n; ++j) {
+        std::memcpy(states_out + (size_t)j * srow, s0 + (size_t)j * S, (size_t)S * sizeof(float));
+        if (first_bad) first_bad[j] = -1;
+    }
+    std::vector<unsigned char> timed((size_t)n, 0);
+    std::string late;
+    const RolloutArgs a = batch_args(b);
+    hipError_t le = batch_plant_flush(b, sub);
+    for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
+        const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
+        const RunLayout lay(b, n, L);
+        if (int rc = batch_run_buffers(b, lay)) { hipStreamSynchronize(b->stream); return rc; }
+        // every record of the segment: all but the state is known in advance.  The state of the segment's first step is the host's (the
+        // start state, or the previous segment's last one from the copied trace); the later ones the plant launches write on the device.
+        CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
+        for (int t = 0; t < L; ++t) {
+            const bool given = k0 + t == 0 && u_prev;                          // from the second step on: the problem's own last output
+            for (int j = 0; j < n; ++j) {
+                const int p = ids ? ids[j] : j;
+                CtkBatchStep& q = rec[(size_t)t * n + j];
+                q.id = p; q.seq = b->seq[(size_t)p] + (uint32_t)t; q.call = b->call[(size_t)p] + (uint32_t)t;
+                q.cur = (uint32_t)(b->cur[(size_t)p] ^ (t & 1));
+                q.dev_uprev = given ? 0u : 1u; q.pad = 0u; q.samples = nullptr;
+                for (int i = 0; i < CTK_MAX_STATES; ++i) q.s[i] = (t == 0 && i < S) ? states_out[(size_t)j * srow + (size_t)k0 * S + i] : 0.0f;
+                for (int c = 0; c < CTK_MAX_INPUTS; ++c) q.u_prev[c] = (given && c < C) ? u_prev[(size_t)j * C + c] : 0.0f;
+            }
+        }
+        CtkBatchStep* d_rec = reinterpret_cast<CtkBatchStep*>(b->d_run);
+        float* d_st = reinterpret_cast<float*>(b->d_run + lay.states);
+        float* d_in = reinterpret_cast<float*>(b->d_run + lay.inputs);
+        if (b->differ) le = batch_flush_constants(b);                          // the constants' transfer goes ahead of the step records'
+        if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.u_in, hipMemcpyHostToDevice, b->stream);
+        int ctrl = 0, part = -1;                       // steps whose controllers were all launched; of the step whose launches failed, how many were
+        for (int t = 0; le == hipSuccess && t < L; ++t) {
+            int launched = 0;
+            le = batch_launch_records(b, a, d_rec + (size_t)t * n, n, &launched);
+            if (le != hipSuccess) { part = launched; break; }
+            ++ctrl;
+            le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, t + 1 < L ? d_rec + (size_t)(t + 1) * n : nullptr, b->d_kplant,
+                                        nullptr, d_st + (size_t)t * S, d_in + (size_t)t * C, n, (size_t)L * S, (size_t)L * C);
+        }
+        if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
+        const hipError_t se = hipStreamSynchronize(b->stream);                 // ONE synchronisation per segment
+        if (le == hipSuccess) le = se;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        // the counters reflect what was launched (ctk_batch_step: a listed problem consumes its sequence number launched or not)
+        for (int j = 0; j < n; ++j) {
+            const int p = ids ? ids[j] : j;
+            volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
+            if (le == hipSuccess && slot[1] != b->seq[(size_t)p] + (uint32_t)(L - 1)) late += (late.empty() ? "" : ", ") + std::to_string(p);
+            if (slot[2]) { slot[2] = 0; timed[(size_t)j] = 1; }               // the hand-off's error word, read and cleared
+            b->seq[(size_t)p] += (uint32_t)ctrl; b->call[(size_t)p] += (uint32_t)ctrl; b->cur[(size_t)p] ^= ctrl & 1;
+            if (part >= 0) {
+                ++b->seq[(size_t)p];
+                if (j < part) { ++b->call[(size_t)p]; b->cur[(size_t)p] ^= 1; }
+            }
+        }
+        if (le != hipSuccess) break;
+        const float* h_st = reinterpret_cast<const float*>(b->h_run + lay.states);
+        const float* h_in = reinterpret_cast<const float*>(b->h_run + lay.inputs);
+        for (int j = 0; j < n; ++j) {
+            std::memcpy(states_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_st + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+            std::memcpy(inputs_out + (size_t)j * urow + (size_t)k0 * C, h_in + (size_t)j * L * C, (size_t)L * C * sizeof(float));
+            if (first_bad && first_bad[j] < 0)
+                for (int i = 0; i < L * C; ++i)
+                    if (!std::isfinite(h_in[(size_t)j * L * C + i])) { first_bad[j] = k0 + i / C; break; }
+        }
+        k0 += L;
+    }
+    if (le != hipSuccess)
+        return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_run: ") + hipGetErrorString(le) + " (the counters reflect the steps that were launched; the traces are not valid)");
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_run: a segment finished without publishing the last result of problem(s) " + late);
+    std::string timed_out;
+    for (int j = 0; j < n; ++j)
+        if (timed[(size_t)j]) timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(ids ? ids[j] : j);
+    if (!timed_out.empty())
+        return bfail(b, CTK_ERR_STATE, "ctk_batch_run: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; such a step publishes NaN and the plant propagates it: their traces show where (first_bad), the other problems' traces are valid");
+    return CTK_OK;
+}
+
 }  // extern "C"
 
 // =============================================================================================
@@ -3040,6 +3285,22 @@ int mlp_batch_put_weights(ctk_batch* b, int n, const int32_t* ids, const float* 
                                hipMemcpyHostToDevice, b->stream));
     BHIP_TRY(b, hipStreamSynchronize(b->stream));
     for (int j = 0; j < n; ++j) b->have_w[(size_t)(ids ? ids[j] : j)] = 1;
+    return CTK_OK;
+}
+
+// a problem without a network is not stepped, and then none of the listed ones is: nothing is launched, no plan, output or Philox
+// position moves (a handle's ctk_step fails the same way: check_predictor)
+int mlp_batch_have_weights(ctk_batch* b, const char* who, int n_ids, const int32_t* ids) {
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    std::string missing;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        if (!b->have_w[(size_t)p]) missing += (missing.empty() ? "" : ", ") + std::to_string(p);
+    }
+    if (!missing.empty())
+        return bfail(b, CTK_ERR_STATE, std::string(who) + ": no network weights for problem(s) " + missing +
+                     " (ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights before stepping); nothing was launched");
     return CTK_OK;
 }
 
@@ -3102,19 +3363,27 @@ int ctk_mlp_batch_step(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const fl
     if (!m) return CTK_ERR_INVALID_ARGUMENT;
     ctk_batch* b = &m->b;
     if (!s) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_step: NULL state");
-    int n = 0;
-    if (int rc = batch_ids(b, "ctk_mlp_batch_step", n_ids, ids, &n)) return rc;
-    // a problem without a network is not stepped, and then none of the listed ones is: nothing is launched, no plan, output or Philox
-    // position moves (a handle's ctk_step fails the same way: check_predictor)
-    std::string missing;
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        if (!b->have_w[(size_t)p]) missing += (missing.empty() ? "" : ", ") + std::to_string(p);
-    }
-    if (!missing.empty())
-        return bfail(b, CTK_ERR_STATE, "ctk_mlp_batch_step: no network weights for problem(s) " + missing +
-                     " (ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights before stepping); nothing was launched");
+    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_step", n_ids, ids)) return rc;
     return ctk_batch_step(b, n_ids, ids, s, u_prev, samples, samples_loc, u_out);
+}
+
+// the closed loop on the device: ctk_batch_plant_* / ctk_batch_run under this family's names.  The network plans, the plant is the
+// analytic CartPole with the problem's parameter table (and the overrides set here)
+int ctk_mlp_batch_plant_set_param(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int id, const float* values) {
+    return ctk_batch_plant_set_param(core(m), n_ids, ids, id, values);
+}
+int ctk_mlp_batch_plant_get_param(const ctk_mlp_batch* m, int problem, int id, float* value) { return ctk_batch_plant_get_param(core(m), problem, id, value); }
+int ctk_mlp_batch_plant_clear_params(ctk_mlp_batch* m) { return ctk_batch_plant_clear_params(core(m)); }
+int ctk_mlp_batch_plant_step(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u, int substeps, float* s_next) {
+    return ctk_batch_plant_step(core(m), n_ids, ids, s, u, substeps, s_next);
+}
+int ctk_mlp_batch_run(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s0, const float* u_prev, int n_steps, int plant_substeps,
+                      float* states_out, float* inputs_out, int32_t* first_bad) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    if (!s0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_run: NULL start states or trace destination");
+    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_run", n_ids, ids)) return rc;
+    return ctk_batch_run(b, n_ids, ids, s0, u_prev, n_steps, plant_substeps, states_out, inputs_out, first_bad);
 }
 
 int ctk_mlp_batch_reset(ctk_mlp_batch* m, int n_ids, const int32_t* ids) { return ctk_batch_reset(core(m), n_ids, ids); }

@@ -207,6 +207,16 @@ size_t ctk_mppi_batch_mlp_table_floats();
 hipError_t ctk_launch_mppi_batch_mlp(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                      const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
                                      const float* w_dev, const void* k_dev = nullptr);
+// ---- ctk_plant.hip : the plant of a batch's closed loop (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_step) ----
+// ONE launch of ctk_batch_plant<env>, one lane per record: record j of cur_dev (its id = the problem, its s = the state) advanced by
+// Env<env>::step with element id of kplant_dev (stride ctk_mppi_batch_k_stride(env), filled by ctk_mppi_batch_derive_k from the PLANT's
+// table and sub-step count) and the input u_in_dev [n][C], or, where that is NULL, the problem's own last output (its descriptor's
+// u_dev).  The new state goes to states_out + j * state_stride, the input to inputs_out + j * input_stride (NULL: not kept) and, where
+// next_dev is given, into next_dev[j].s — the record the next controller launch reads.
+const char* ctk_batch_plant_name(int env);
+hipError_t ctk_launch_batch_plant(hipStream_t st, int env, const CtkBatchDesc* desc_dev, const CtkBatchStep* cur_dev, CtkBatchStep* next_dev,
+                                  const void* kplant_dev, const float* u_in_dev, float* states_out, float* inputs_out, int n_records,
+                                  size_t state_stride, size_t input_stride);
 hipError_t ctk_launch_mppi_merge_partial(hipStream_t st, const float* parts, int n_parts, int per_block, int P,
                                          float neg_inv_lbd, float* out_rec);
 // direct peer-to-peer record exchange + merge + update (ctk_mppi.hip: ctk_mppi_p2p_exchange)
