@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from types import SimpleNamespace
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -221,6 +221,22 @@ _PLANT_RUN = {
 }
 RUN_SYMBOLS = {f"{family}_{name}": sig for family in ("ctk_batch", "ctk_mlp_batch") for name, sig in _PLANT_RUN.items()}
 
+# stochastic closed-loop episodes with the realised cost (include/ctk_hip_episode.h, which ctk_hip.h includes): a third table, bound with
+# the other two
+_PLANT_EPISODE = {
+    "plant_set_noise": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "plant_get_noise": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "plant_clear_noise": (C.c_int, [_H]),
+    "plant_set_noise_seed": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
+    "plant_get_noise_seed": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint64)]),
+    "plant_noise_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
+    "plant_noise_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
+    "plant_step_noisy": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "episodes": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.c_void_p]),
+}
+EPISODE_SYMBOLS = {f"{family}_{name}": sig for family in ("ctk_batch", "ctk_mlp_batch") for name, sig in _PLANT_EPISODE.items()}
+
 
 # user environments (include/ctk_user_env.h): name -> path of the library that was compiled with that model (control_toolkit_amd/build_env.py:
 # register_environment); their environment id inside that library is CTK_ENV_USER
@@ -264,7 +280,7 @@ def _bind_library(path: str):
         lib = C.CDLL(path)
     except OSError as e:
         raise CtkError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctk_abi_version() != 6:
@@ -821,6 +837,46 @@ def batch_run_args(num_problems: int, S: int, Cn: int, states, steps, u_prev=Non
 _F32_MAX = float(np.finfo(np.float32).max)
 
 
+def batch_noise_args(num_problems: int, S: int, sigma, ids=None, what: str = "process"):
+    """Checks one noise argument of BatchClosedLoop.set_noise without touching a device: ids (batch_ids), sigma a scalar, [S] or [n, S]
+    of finite standard deviations >= 0 that fit float32.  Returns (ids, n, sigma as fp32 [n, S])."""
+    idv = batch_ids(num_problems, ids)
+    n = num_problems if idv is None else int(idv.size)
+    try:
+        sg = np.asarray(sigma, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} noise must be a number or an array of numbers, got {sigma!r}") from None
+    if sg.ndim == 0 or sg.shape == (S,):
+        sg = np.broadcast_to(sg, (n, S))
+    if sg.shape != (n, S):
+        raise ValueError(f"{what} noise must be a scalar, ({S},) or ({n}, {S}): one row per listed problem, got shape {tuple(sg.shape)}")
+    ok = (sg >= 0.0) & (sg <= _F32_MAX)                            # NaN compares false
+    if not ok.all():
+        j, i = (int(x[0]) for x in np.nonzero(~ok))
+        raise ValueError(f"{what} noise: a standard deviation is finite and >= 0, got {float(sg[j, i])!r} for problem {j if idv is None else int(idv[j])}, state {i}")
+    return idv, n, np.ascontiguousarray(sg, dtype=np.float32)
+
+
+def batch_episode_args(num_problems: int, S: int, Cn: int, states, steps, u_prev=None, ids=None, plant_substeps=None, observations=None):
+    """Checks the arguments of BatchClosedLoop.episodes without touching a device: those of a run (batch_run_args) and Y0, None or [n, S]
+    like the start states.  Returns (ids, n, the sub-step count as the library takes it)."""
+    idv, n, sub = batch_run_args(num_problems, S, Cn, states, steps, u_prev, ids, plant_substeps, None)
+    if observations is not None:
+        y = np.asarray(observations)
+        if y.shape != (n, S) and not (n == 1 and y.shape == (S,)):
+            raise ValueError(f"Y0 must have shape ({n}, {S}): one row per listed problem, like S0, got {tuple(y.shape)}")
+    return idv, n, sub
+
+
+class Episodes(NamedTuple):
+    """what BatchClosedLoop.episodes returns: the true states [n, steps + 1, S], what the controllers were given [n, steps + 1, S], the
+    inputs [n, steps, C] and the realised stage costs [n, steps]"""
+    states: np.ndarray
+    observations: np.ndarray
+    inputs: np.ndarray
+    costs: np.ndarray
+
+
 def batch_param_args(param_names, num_problems: int, name, values, ids=None):
     """Checks the arguments of CtkMppiBatch.set_problem_params / CtkCemBatch.set_problem_params / CtkRpgdBatch.set_problem_params
     without touching a device: the parameter name against the environment's names, ids (batch_ids), values a finite scalar (every
@@ -1144,6 +1200,107 @@ class BatchClosedLoop:
         """drop every plant override: each plant is again the one its controller models"""
         b = self._batch
         b._check(self._entry("plant_clear_params")(b._h))
+
+    # ---- the stochastic plant and the realised cost (include/ctk_hip_episode.h; kernel ctk_batch_plant_noisy<ENV>) ----
+    def set_noise(self, process=None, measurement=None, ids=None):
+        """per-step standard deviations, in state units, of the process noise (added to the true next state) and the measurement noise
+        (added to what the controller is given) of the problems in ids (None: all).  Each: None (leave as is), a scalar, [S] or [n, S].
+        A component at 0 gets no noise.  run() and plant_step() ignore both."""
+        b = self._batch
+        checked = [(kind, batch_noise_args(b.B, b.S, sigma, ids, what)) for kind, what, sigma in ((0, "process", process), (1, "measurement", measurement))
+                   if sigma is not None]
+        for kind, (idv, n, sg) in checked:
+            b._check(self._entry("plant_set_noise")(b._h, n, _ptr(idv), kind, _ptr(sg)))
+
+    def get_noise(self):
+        """(process [B, S], measurement [B, S]): every problem's standard deviations"""
+        b = self._batch
+        out = np.zeros((2, b.B, b.S), np.float32)
+        for kind in (0, 1):
+            for p in range(b.B):
+                row = np.zeros(b.S, np.float32)
+                if self._entry("plant_get_noise")(b._h, p, kind, _ptr(row)) != 0:
+                    raise CtkError(f"{b._BATCH}_plant_get_noise({p}, {kind}) failed")
+                out[kind, p] = row
+        return out[0], out[1]
+
+    def clear_noise(self):
+        """every standard deviation back to 0; the noise seeds and positions stay"""
+        b = self._batch
+        b._check(self._entry("plant_clear_noise")(b._h))
+
+    def set_noise_seeds(self, seeds, ids=None):
+        """the Philox key of the noise of the problems in ids (None: all), one uint64 per listed problem (at creation: the controller's seed)"""
+        b = self._batch
+        idv = batch_ids(b.B, ids)
+        n = b.B if idv is None else int(idv.size)
+        sd = _CtkBatch._seeds(n, seeds)
+        if sd is None:
+            raise ValueError(f"seeds must have one entry per listed problem ({n}), got None")
+        b._check(self._entry("plant_set_noise_seed")(b._h, n, _ptr(idv), _ptr(sd)))
+
+    def get_noise_seeds(self) -> np.ndarray:
+        """[B] uint64: every problem's noise seed"""
+        b = self._batch
+        v, out = C.c_uint64(), np.zeros(b.B, np.uint64)
+        for p in range(b.B):
+            if self._entry("plant_get_noise_seed")(b._h, p, C.byref(v)) != 0:
+                raise CtkError(f"{b._BATCH}_plant_get_noise_seed({p}) failed")
+            out[p] = v.value
+        return out
+
+    def noise_position(self, problem: int) -> int:
+        """the problem's noise position: one per transition of the noisy plant (episodes, plant_step_noisy), 0 at creation"""
+        b = self._batch
+        v = C.c_uint32()
+        b._check(self._entry("plant_noise_get_position")(b._h, b._problem(problem), C.byref(v)))
+        return int(v.value)
+
+    def set_noise_position(self, problem: int, pos: int):
+        b = self._batch
+        b._check(self._entry("plant_noise_set_position")(b._h, b._problem(problem), int(pos) & 0xFFFFFFFF))
+
+    def plant_step_noisy(self, S, U, U_prev, ids=None, plant_substeps=None):
+        """one transition of the noisy plants of the problems in ids (None: all): true states S [n, num_states], inputs U [n, C] and the
+        inputs before them U_prev [n, C] (required: the cost's input-change term).  Returns (S_next, Y_next, cost): the true next states,
+        what the controllers are given, and the realised stage cost of (S, U, U_prev) [n].  Advances the listed problems' noise
+        positions; no controller state, sequence number or Philox position changes."""
+        b = self._batch
+        idv, n, sub = batch_run_args(b.B, b.S, b.C, S, 1, U, ids, plant_substeps, None, what=("S", "U"))
+        if U is None:
+            raise ValueError(f"U must have shape ({n}, {b.C}): one row per listed problem, got None")
+        if U_prev is None:
+            raise ValueError(f"U_prev must have shape ({n}, {b.C}): one row per listed problem, got None")
+        batch_run_args(b.B, b.S, b.C, S, 1, U_prev, ids, None, None, what=("S", "U_prev"))
+        s = _f32(np.asarray(S).reshape(n, b.S))
+        u = _f32(np.asarray(U).reshape(n, b.C))
+        up = _f32(np.asarray(U_prev).reshape(n, b.C))
+        s_next, y_next, cost = np.empty((n, b.S), np.float32), np.empty((n, b.S), np.float32), np.empty(n, np.float32)
+        b._check(self._entry("plant_step_noisy")(b._h, n, _ptr(idv), _ptr(s), _ptr(u), _ptr(up), sub, _ptr(s_next), _ptr(y_next), _ptr(cost)))
+        return s_next, y_next, cost
+
+    def episodes(self, S0, steps: int, u_prev=None, ids=None, plant_substeps=None, Y0=None) -> Episodes:
+        """run() against the noisy plant, with the realised cost: `steps` closed-loop MPC steps of the problems in ids (None: all) from
+        the TRUE states S0 [n, num_states]; the controllers are given the observations (Y0 [n, num_states] at the first step, None: S0).
+        Bit for bit the loop `U = batch.step(Y); S, Y, c = plant_step_noisy(S, U, U_prev)`.  u_prev [n, C] is the input before the first
+        one, for the controller and for the first cost (None: every problem's own last output, what set_state restored included).  Returns
+        Episodes(states [n, steps + 1, S], observations [n, steps + 1, S], inputs [n, steps, C], costs [n, steps]); an episode continues
+        from (states[:, -1], observations[:, -1]).  last_run_first_bad and the CtkError of a timed-out hand-off are run()'s (the traces
+        are then in batch.last_run)."""
+        b = self._batch
+        idv, n, sub = batch_episode_args(b.B, b.S, b.C, S0, steps, u_prev, ids, plant_substeps, Y0)
+        ids_p, up_p, _, _ = b._step_args(n, idv, S0, u_prev, None)
+        y0 = None if Y0 is None else _f32(np.asarray(Y0).reshape(n, b.S))
+        out = Episodes(np.empty((n, int(steps) + 1, b.S), np.float32), np.empty((n, int(steps) + 1, b.S), np.float32),
+                       np.empty((n, int(steps), b.C), np.float32), np.empty((n, int(steps)), np.float32))
+        bad = np.full(n, -1, np.int32)
+        rc = self._entry("episodes")(b._h, n, ids_p, b._s_p, _ptr(y0), up_p, int(steps), sub, _ptr(out.states), _ptr(out.observations),
+                                     _ptr(out.inputs), _ptr(out.costs), _ptr(bad))
+        b.last_run_first_bad = bad
+        if rc:
+            b.last_run = out
+            b._check(rc)
+        return out
 
 # ---- batched MPPI with the MLP predictor (include/ctk_hip.h: ctk_mlp_batch_* / ctk_mlp_problem_*) --------------------------------------
 def mlp_weight_count(num_states: int, num_control_inputs: int, hidden=(32, 32)) -> int:

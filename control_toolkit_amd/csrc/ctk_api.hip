@@ -2667,6 +2667,10 @@ struct ctk_batch : BatchCore {
     unsigned char* d_run = nullptr;         // the same on the device; both grow on demand (batch_run_buffers)
     size_t run_cap = 0;
     int run_segment = 256;                  // steps per segment of a run: a diagnostic switch may lower it (ctk_batch_create)
+    // the stochastic plant (include/ctk_hip_episode.h: ctk_batch_episodes / ctk_batch_plant_step_noisy; kernel ctk_batch_plant_noisy<ENV>)
+    std::vector<float> noise_sigma;         // [B][2][CTK_MAX_STATES] process | measurement standard deviations (0: none)
+    std::vector<uint64_t> noise_seed;       // [B] Philox key of the problem's noise (at creation: its controller seed)
+    std::vector<uint32_t> noise_pos;        // [B] noise position: one per transition of the noisy plant
     size_t unom_stride() const { return (size_t)2 * HC; }
     float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
 };
@@ -2769,16 +2773,52 @@ struct RunLayout {
 };
 static_assert(sizeof(CtkBatchStep) % 16 == 0, "the parts of the run buffer lie behind the step records, 16-aligned");
 
-int batch_run_buffers(ctk_batch* b, const RunLayout& lay) {
-    if (lay.total <= b->run_cap) return CTK_OK;
+// the run buffer (device and pinned), grown to `total` bytes on demand
+int batch_run_buffers(ctk_batch* b, size_t total) {
+    if (total <= b->run_cap) return CTK_OK;
     if (b->d_run) BHIP_TRY(b, hipFree(b->d_run));
     b->d_run = nullptr; b->run_cap = 0;
     if (b->h_run) BHIP_TRY(b, hipHostFree(b->h_run));
     b->h_run = nullptr;
-    BHIP_TRY(b, hipMalloc((void**)&b->d_run, lay.total));
-    BHIP_TRY(b, hipHostMalloc((void**)&b->h_run, lay.total, hipHostMallocDefault));
-    b->run_cap = lay.total;
+    BHIP_TRY(b, hipMalloc((void**)&b->d_run, total));
+    BHIP_TRY(b, hipHostMalloc((void**)&b->h_run, total, hipHostMallocDefault));
+    b->run_cap = total;
     return CTK_OK;
+}
+int batch_run_buffers(ctk_batch* b, const RunLayout& lay) { return batch_run_buffers(b, lay.total); }
+
+// where the parts of the run buffer lie for an episode segment of n problems and L steps (ctk_batch_episodes / ctk_batch_plant_step_noisy).
+// What travels to the device in ONE transfer lies in front (up to `states`), what comes back in ONE copy behind it:
+//   step records [L][n] | inputs of a noisy plant step [n][C] | true start states [n][S] | previous inputs of the first step [n][C] |
+//   noise records [n] || state trace [n][L][S] | observation trace [n][L][S] | input trace [n][L][C] | realised costs [n][L]
+struct EpisodeLayout {
+    size_t u_in, s_start, u_start, noise, states, obs, inputs, costs, total;
+    EpisodeLayout(const ctk_batch* b, int n, int L) {
+        auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        u_in = (size_t)L * n * sizeof(CtkBatchStep);
+        s_start = u_in + up((size_t)n * b->C * sizeof(float));
+        u_start = s_start + up((size_t)n * b->S * sizeof(float));
+        noise = u_start + up((size_t)n * b->C * sizeof(float));
+        states = noise + (size_t)n * sizeof(CtkPlantNoise);
+        obs = states + up((size_t)n * L * b->S * sizeof(float));
+        inputs = obs + up((size_t)n * L * b->S * sizeof(float));
+        costs = inputs + up((size_t)n * L * b->C * sizeof(float));
+        total = costs + up((size_t)n * L * sizeof(float));
+    }
+};
+static_assert(sizeof(CtkPlantNoise) % 16 == 0, "the traces lie behind the noise records, 16-aligned");
+
+// problem p's noise record at its current position
+void batch_noise_record(const ctk_batch* b, int p, CtkPlantNoise* q) {
+    const float* sg = &b->noise_sigma[(size_t)p * 2 * CTK_MAX_STATES];
+    q->any = 0u;
+    for (int i = 0; i < CTK_MAX_STATES; ++i) {
+        q->sigma_w[i] = i < b->S ? sg[i] : 0.0f;
+        q->sigma_v[i] = i < b->S ? sg[CTK_MAX_STATES + i] : 0.0f;
+        if (q->sigma_w[i] != 0.0f || q->sigma_v[i] != 0.0f) q->any = 1u;
+    }
+    q->seed_lo = (uint32_t)(b->noise_seed[(size_t)p] & 0xFFFFFFFFull); q->seed_hi = (uint32_t)(b->noise_seed[(size_t)p] >> 32);
+    q->pos = b->noise_pos[(size_t)p];
 }
 
 int batch_substeps(ctk_batch* b, const char* who, int substeps, int* out) {
@@ -2893,6 +2933,10 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
     b->plant_has.assign((size_t)n_problems * CTK_MAX_PARAMS, 0);
     b->plant_tab.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
     b->plant_sub.assign((size_t)n_problems, 0);
+    b->noise_sigma.assign((size_t)n_problems * 2 * CTK_MAX_STATES, 0.0f);
+    b->noise_seed.resize((size_t)n_problems);
+    for (int p = 0; p < n_problems; ++p) b->noise_seed[(size_t)p] = seeds ? seeds[p] : cfg->seed + (uint64_t)p;   // the controller's (below)
+    b->noise_pos.assign((size_t)n_problems, 0u);
     b->cur.assign((size_t)n_problems, 0);
     b->dominant = mlp ? ctk_mppi_batch_mlp_name(cfg->materialize_trajectories != 0) : ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
     if (mlp) { b->wtab = ctk_mppi_batch_mlp_table_floats(); b->have_w.assign((size_t)n_problems, 0); }
@@ -3243,6 +3287,238 @@ int ctk_batch_run(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, 
     return CTK_OK;
 }
 
+// ---- the stochastic plant and the realised cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes) ----
+int ctk_batch_plant_set_noise(ctk_batch* b, int n_ids, const int32_t* ids, int kind, const float* sigma) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_plant_set_noise", n_ids, ids, &n)) return rc;
+    if (kind != 0 && kind != 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: kind is 0 (process noise) or 1 (measurement noise), not " + std::to_string(kind));
+    if (!sigma) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: NULL sigma (one row of num_states values per listed problem)");
+    for (int i = 0; i < n * b->S; ++i)
+        if (!(std::isfinite(sigma[i]) && sigma[i] >= 0.0f))
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: a standard deviation is finite and >= 0 (" + std::to_string(sigma[i]) + " for problem " +
+                         std::to_string(ids ? ids[i / b->S] : i / b->S) + ", state " + std::to_string(i % b->S) + "); nothing was written");
+    for (int j = 0; j < n; ++j) {
+        float* dst = &b->noise_sigma[((size_t)(ids ? ids[j] : j) * 2 + (size_t)kind) * CTK_MAX_STATES];
+        for (int i = 0; i < b->S; ++i) dst[i] = sigma[(size_t)j * b->S + i] == 0.0f ? 0.0f : sigma[(size_t)j * b->S + i];   // -0.0 is "none" too
+    }
+    return CTK_OK;
+}
+
+int ctk_batch_plant_get_noise(const ctk_batch* b, int problem, int kind, float* sigma) {
+    if (!b || !sigma || problem < 0 || problem >= b->B || (kind != 0 && kind != 1)) return CTK_ERR_INVALID_ARGUMENT;
+    std::memcpy(sigma, &b->noise_sigma[((size_t)problem * 2 + (size_t)kind) * CTK_MAX_STATES], (size_t)b->S * sizeof(float));
+    return CTK_OK;
+}
+
+int ctk_batch_plant_clear_noise(ctk_batch* b) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    std::fill(b->noise_sigma.begin(), b->noise_sigma.end(), 0.0f);
+    return CTK_OK;
+}
+
+int ctk_batch_plant_set_noise_seed(ctk_batch* b, int n_ids, const int32_t* ids, const uint64_t* seeds) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_plant_set_noise_seed", n_ids, ids, &n)) return rc;
+    if (!seeds) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise_seed: NULL seeds (one per listed problem)");
+    for (int j = 0; j < n; ++j) b->noise_seed[(size_t)(ids ? ids[j] : j)] = seeds[j];
+    return CTK_OK;
+}
+
+int ctk_batch_plant_get_noise_seed(const ctk_batch* b, int problem, uint64_t* seed) {
+    if (!b || !seed || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *seed = b->noise_seed[(size_t)problem];
+    return CTK_OK;
+}
+
+int ctk_batch_plant_noise_get_position(const ctk_batch* b, int problem, uint32_t* pos) {
+    if (!b || !pos || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *pos = b->noise_pos[(size_t)problem];
+    return CTK_OK;
+}
+
+int ctk_batch_plant_noise_set_position(ctk_batch* b, int problem, uint32_t pos) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, "ctk_batch_plant_noise_set_position", problem)) return rc;
+    b->noise_pos[(size_t)problem] = pos;
+    return CTK_OK;
+}
+
+int ctk_batch_plant_step_noisy(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev, int substeps,
+                               float* s_next, float* y_next, float* cost) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!s || !u || !u_prev || !s_next || !y_next || !cost)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_step_noisy: NULL state, input, previous input or destination");
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, "ctk_batch_plant_step_noisy", n_ids, ids, &n)) return rc;
+    if (int rc = batch_substeps(b, "ctk_batch_plant_step_noisy", substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const EpisodeLayout lay(b, n, 1);
+    if (int rc = batch_run_buffers(b, lay.total)) return rc;
+    // the records carry the problem only; they, the states, the two inputs and the noise records travel in ONE transfer
+    CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
+    CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
+    for (int j = 0; j < n; ++j) {
+        std::memset(&rec[j], 0, sizeof(CtkBatchStep));
+        rec[j].id = ids ? ids[j] : j;
+        batch_noise_record(b, rec[j].id, &nz[j]);
+    }
+    std::memcpy(b->h_run + lay.u_in, u, (size_t)n * C * sizeof(float));
+    std::memcpy(b->h_run + lay.s_start, s, (size_t)n * S * sizeof(float));
+    std::memcpy(b->h_run + lay.u_start, u_prev, (size_t)n * C * sizeof(float));
+    auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+    hipError_t le = batch_plant_flush(b, sub);
+    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
+    bool launched = false;
+    if (le == hipSuccess) {
+        le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, reinterpret_cast<const CtkBatchStep*>(b->d_run), nullptr, b->d_kplant,
+                                          reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise), dev(lay.u_in), dev(lay.s_start), (size_t)S,
+                                          dev(lay.u_start), (size_t)C, 0u, dev(lay.states), dev(lay.obs), nullptr, dev(lay.costs), n, (size_t)S, 0, 1);
+        launched = le == hipSuccess;
+    }
+    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
+    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
+    if (le == hipSuccess) le = se;
+    if (launched)
+        for (int j = 0; j < n; ++j) ++b->noise_pos[(size_t)rec[j].id];         // by the plant launch that was issued
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_plant_step_noisy: ") + hipGetErrorString(le));
+    std::memcpy(s_next, b->h_run + lay.states, (size_t)n * S * sizeof(float));
+    std::memcpy(y_next, b->h_run + lay.obs, (size_t)n * S * sizeof(float));
+    std::memcpy(cost, b->h_run + lay.costs, (size_t)n * sizeof(float));
+    return CTK_OK;
+}
+
+// ctk_batch_run with the noisy plant: the same records, launches, segments, counters and error words; what differs is where the plant
+// reads from (the true state and the previous input have their own rows, see ctk_plant.hip) and the two further traces.
+int ctk_batch_episodes(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, const float* y0, const float* u_prev, int n_steps,
+                       int plant_substeps, float* states_out, float* obs_out, float* inputs_out, float* costs_out, int32_t* first_bad) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!s0 || !states_out || !obs_out || !inputs_out || !costs_out)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_episodes: NULL start states or trace destination");
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, "ctk_batch_episodes", n_ids, ids, &n)) return rc;
+    if (n_steps < 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_episodes: an episode has at least one step (n_steps == " + std::to_string(n_steps) + ")");
+    if (int rc = batch_substeps(b, "ctk_batch_episodes", plant_substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const size_t srow = ((size_t)n_steps + 1) * S, urow = (size_t)n_steps * C;       // one problem's rows of the traces
+    for (int j = 0; j < n; ++j) {
+        std::memcpy(states_out + (size_t)j * srow, s0 + (size_t)j * S, (size_t)S * sizeof(float));
+        std::memcpy(obs_out + (size_t)j * srow, (y0 ? y0 : s0) + (size_t)j * S, (size_t)S * sizeof(float));
+        if (first_bad) first_bad[j] = -1;
+    }
+    // u_prev == NULL: c_0's previous input is what the first controller launch reads as its own — the problem's last output in d_u
+    // (ctk_batch_set_state writes it too, the pinned result slot only holds what a step published).  That launch overwrites it, so the
+    // span of the listed problems is read here, once per call, ahead of everything else.
+    const int p_lo = ids ? ids[0] : 0, p_hi = ids ? ids[n - 1] : n - 1;
+    std::vector<float> own_u;
+    if (!u_prev) {
+        own_u.resize((size_t)(p_hi - p_lo + 1) * CTK_MAX_INPUTS);
+        BHIP_TRY(b, hipMemcpyAsync(own_u.data(), b->d_u + (size_t)p_lo * CTK_MAX_INPUTS, own_u.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+        BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    }
+    std::vector<unsigned char> timed((size_t)n, 0);
+    std::string late;
+    const RolloutArgs a = batch_args(b);
+    hipError_t le = batch_plant_flush(b, sub);
+    for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
+        const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
+        const EpisodeLayout lay(b, n, L);
+        if (int rc = batch_run_buffers(b, lay.total)) { hipStreamSynchronize(b->stream); return rc; }
+        // every record of the segment, as in ctk_batch_run; the first step's record carries the OBSERVATION (the given one, or the
+        // previous segment's last from the copied trace), the later ones the plant launches write on the device
+        CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
+        float* h_s = reinterpret_cast<float*>(b->h_run + lay.s_start);
+        float* h_up = reinterpret_cast<float*>(b->h_run + lay.u_start);
+        CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
+        for (int t = 0; t < L; ++t) {
+            const bool given = k0 + t == 0 && u_prev;                          // from the second step on: the problem's own last output
+            for (int j = 0; j < n; ++j) {
+                const int p = ids ? ids[j] : j;
+                CtkBatchStep& q = rec[(size_t)t * n + j];
+                q.id = p; q.seq = b->seq[(size_t)p] + (uint32_t)t; q.call = b->call[(size_t)p] + (uint32_t)t;
+                q.cur = (uint32_t)(b->cur[(size_t)p] ^ (t & 1));
+                q.dev_uprev = given ? 0u : 1u; q.pad = 0u; q.samples = nullptr;
+                for (int i = 0; i < CTK_MAX_STATES; ++i) q.s[i] = (t == 0 && i < S) ? obs_out[(size_t)j * srow + (size_t)k0 * S + i] : 0.0f;
+                for (int c = 0; c < CTK_MAX_INPUTS; ++c) q.u_prev[c] = (given && c < C) ? u_prev[(size_t)j * C + c] : 0.0f;
+            }
+        }
+        // what the first plant launch of the segment reads in place of trace rows: the true state, and the input before the segment's
+        // first one — the given u_prev, the previous segment's last input, or the problem's own last output (read above)
+        for (int j = 0; j < n; ++j) {
+            const int p = ids ? ids[j] : j;
+            std::memcpy(h_s + (size_t)j * S, states_out + (size_t)j * srow + (size_t)k0 * S, (size_t)S * sizeof(float));
+            if (k0 > 0) std::memcpy(h_up + (size_t)j * C, inputs_out + (size_t)j * urow + ((size_t)k0 - 1) * C, (size_t)C * sizeof(float));
+            else if (u_prev) std::memcpy(h_up + (size_t)j * C, u_prev + (size_t)j * C, (size_t)C * sizeof(float));
+            else std::memcpy(h_up + (size_t)j * C, &own_u[(size_t)(p - p_lo) * CTK_MAX_INPUTS], (size_t)C * sizeof(float));
+            batch_noise_record(b, p, &nz[j]);
+        }
+        CtkBatchStep* d_rec = reinterpret_cast<CtkBatchStep*>(b->d_run);
+        auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+        const CtkPlantNoise* d_nz = reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise);
+        float *d_st = dev(lay.states), *d_ob = dev(lay.obs), *d_in = dev(lay.inputs), *d_co = dev(lay.costs);
+        if (b->differ) le = batch_flush_constants(b);                          // the constants' transfer goes ahead of the step records'
+        if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
+        int ctrl = 0, part = -1, plants = 0;           // as in ctk_batch_run; plants: the plant launches that were issued
+        for (int t = 0; le == hipSuccess && t < L; ++t) {
+            int launched = 0;
+            le = batch_launch_records(b, a, d_rec + (size_t)t * n, n, &launched);
+            if (le != hipSuccess) { part = launched; break; }
+            ++ctrl;
+            le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, t + 1 < L ? d_rec + (size_t)(t + 1) * n : nullptr,
+                                              b->d_kplant, d_nz, nullptr, t ? d_st + (size_t)(t - 1) * S : dev(lay.s_start), t ? (size_t)L * S : (size_t)S,
+                                              t ? d_in + (size_t)(t - 1) * C : dev(lay.u_start), t ? (size_t)L * C : (size_t)C, (uint32_t)t,
+                                              d_st + (size_t)t * S, d_ob + (size_t)t * S, d_in + (size_t)t * C, d_co + t, n, (size_t)L * S, (size_t)L * C,
+                                              (size_t)L);
+            if (le == hipSuccess) ++plants;
+        }
+        if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
+        const hipError_t se = hipStreamSynchronize(b->stream);                 // ONE synchronisation per segment
+        if (le == hipSuccess) le = se;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        // the counters reflect what was launched, as in ctk_batch_run; the noise positions the plant launches
+        for (int j = 0; j < n; ++j) {
+            const int p = ids ? ids[j] : j;
+            volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
+            if (le == hipSuccess && slot[1] != b->seq[(size_t)p] + (uint32_t)(L - 1)) late += (late.empty() ? "" : ", ") + std::to_string(p);
+            if (slot[2]) { slot[2] = 0; timed[(size_t)j] = 1; }               // the hand-off's error word, read and cleared
+            b->seq[(size_t)p] += (uint32_t)ctrl; b->call[(size_t)p] += (uint32_t)ctrl; b->cur[(size_t)p] ^= ctrl & 1;
+            if (part >= 0) {
+                ++b->seq[(size_t)p];
+                if (j < part) { ++b->call[(size_t)p]; b->cur[(size_t)p] ^= 1; }
+            }
+            b->noise_pos[(size_t)p] += (uint32_t)plants;
+        }
+        if (le != hipSuccess) break;
+        const float* h_st = reinterpret_cast<const float*>(b->h_run + lay.states);
+        const float* h_ob = reinterpret_cast<const float*>(b->h_run + lay.obs);
+        const float* h_in = reinterpret_cast<const float*>(b->h_run + lay.inputs);
+        const float* h_co = reinterpret_cast<const float*>(b->h_run + lay.costs);
+        for (int j = 0; j < n; ++j) {
+            std::memcpy(states_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_st + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+            std::memcpy(obs_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_ob + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+            std::memcpy(inputs_out + (size_t)j * urow + (size_t)k0 * C, h_in + (size_t)j * L * C, (size_t)L * C * sizeof(float));
+            std::memcpy(costs_out + (size_t)j * n_steps + (size_t)k0, h_co + (size_t)j * L, (size_t)L * sizeof(float));
+            if (first_bad && first_bad[j] < 0)
+                for (int i = 0; i < L * C; ++i)
+                    if (!std::isfinite(h_in[(size_t)j * L * C + i])) { first_bad[j] = k0 + i / C; break; }
+        }
+        k0 += L;
+    }
+    if (le != hipSuccess)
+        return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_episodes: ") + hipGetErrorString(le) + " (the counters reflect the steps that were launched; the traces are not valid)");
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_episodes: a segment finished without publishing the last result of problem(s) " + late);
+    std::string timed_out;
+    for (int j = 0; j < n; ++j)
+        if (timed[(size_t)j]) timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(ids ? ids[j] : j);
+    if (!timed_out.empty())
+        return bfail(b, CTK_ERR_STATE, "ctk_batch_episodes: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; such a step publishes NaN and the plant propagates it: their traces show where (first_bad), the other problems' traces are valid");
+    return CTK_OK;
+}
+
 }  // extern "C"
 
 // =============================================================================================
@@ -3384,6 +3660,30 @@ int ctk_mlp_batch_run(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const flo
     if (!s0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_run: NULL start states or trace destination");
     if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_run", n_ids, ids)) return rc;
     return ctk_batch_run(b, n_ids, ids, s0, u_prev, n_steps, plant_substeps, states_out, inputs_out, first_bad);
+}
+// the stochastic plant and the realised cost (include/ctk_hip_episode.h), under this family's names
+int ctk_mlp_batch_plant_set_noise(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int kind, const float* sigma) {
+    return ctk_batch_plant_set_noise(core(m), n_ids, ids, kind, sigma);
+}
+int ctk_mlp_batch_plant_get_noise(const ctk_mlp_batch* m, int problem, int kind, float* sigma) { return ctk_batch_plant_get_noise(core(m), problem, kind, sigma); }
+int ctk_mlp_batch_plant_clear_noise(ctk_mlp_batch* m) { return ctk_batch_plant_clear_noise(core(m)); }
+int ctk_mlp_batch_plant_set_noise_seed(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const uint64_t* seeds) {
+    return ctk_batch_plant_set_noise_seed(core(m), n_ids, ids, seeds);
+}
+int ctk_mlp_batch_plant_get_noise_seed(const ctk_mlp_batch* m, int problem, uint64_t* seed) { return ctk_batch_plant_get_noise_seed(core(m), problem, seed); }
+int ctk_mlp_batch_plant_noise_get_position(const ctk_mlp_batch* m, int problem, uint32_t* pos) { return ctk_batch_plant_noise_get_position(core(m), problem, pos); }
+int ctk_mlp_batch_plant_noise_set_position(ctk_mlp_batch* m, int problem, uint32_t pos) { return ctk_batch_plant_noise_set_position(core(m), problem, pos); }
+int ctk_mlp_batch_plant_step_noisy(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev, int substeps,
+                                   float* s_next, float* y_next, float* cost) {
+    return ctk_batch_plant_step_noisy(core(m), n_ids, ids, s, u, u_prev, substeps, s_next, y_next, cost);
+}
+int ctk_mlp_batch_episodes(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s0, const float* y0, const float* u_prev, int n_steps,
+                           int plant_substeps, float* states_out, float* obs_out, float* inputs_out, float* costs_out, int32_t* first_bad) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    if (!s0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_episodes: NULL start states or trace destination");
+    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_episodes", n_ids, ids)) return rc;
+    return ctk_batch_episodes(b, n_ids, ids, s0, y0, u_prev, n_steps, plant_substeps, states_out, obs_out, inputs_out, costs_out, first_bad);
 }
 
 int ctk_mlp_batch_reset(ctk_mlp_batch* m, int n_ids, const int32_t* ids) { return ctk_batch_reset(core(m), n_ids, ids); }

@@ -217,6 +217,28 @@ const char* ctk_batch_plant_name(int env);
 hipError_t ctk_launch_batch_plant(hipStream_t st, int env, const CtkBatchDesc* desc_dev, const CtkBatchStep* cur_dev, CtkBatchStep* next_dev,
                                   const void* kplant_dev, const float* u_in_dev, float* states_out, float* inputs_out, int n_records,
                                   size_t state_stride, size_t input_stride);
+// ---- ctk_plant.hip : the stochastic plant (include/ctk_hip_episode.h: ctk_batch_episodes / ctk_batch_plant_step_noisy) ----
+// The Philox stream of the plants' noise: far from the optimizers' stream ids, which are small iteration numbers ("PLNT").
+constexpr uint32_t CTK_PLANT_STREAM = 0x504C4E54u;
+// One per step record of a segment's FIRST step, behind the records and travelling with them: the problem's noise at the segment start.
+struct CtkPlantNoise {
+    float sigma_w[CTK_MAX_STATES];      // process noise, per-step standard deviation per state (0: none)
+    float sigma_v[CTK_MAX_STATES];      // measurement noise
+    uint32_t seed_lo, seed_hi;          // Philox key of the noise
+    uint32_t pos;                       // noise position at the segment start (the launch of step t draws at pos + t)
+    uint32_t any;                       // some sigma is not 0 (else the record draws nothing)
+};
+// ONE launch of ctk_batch_plant_noisy<env>, one lane per record: record j's problem advanced from its TRUE state
+// s_true_dev + j * s_true_stride with the input u_in_dev [n][C] (NULL: the problem's own last output) — the realised stage cost of
+// (true state, input, u_last_dev + j * u_last_stride) to costs_out + j * cost_stride, the new true state to states_out + j * state_stride,
+// the observation to obs_out + j * state_stride and, where next_dev is given, into next_dev[j].s; the input to inputs_out + j *
+// input_stride (NULL: not kept).  noise_dev [n]; t: this launch's step within the segment.
+const char* ctk_batch_plant_noisy_name(int env);
+hipError_t ctk_launch_batch_plant_noisy(hipStream_t st, int env, const CtkBatchDesc* desc_dev, const CtkBatchStep* cur_dev, CtkBatchStep* next_dev,
+                                        const void* kplant_dev, const CtkPlantNoise* noise_dev, const float* u_in_dev, const float* s_true_dev,
+                                        size_t s_true_stride, const float* u_last_dev, size_t u_last_stride, uint32_t t, float* states_out,
+                                        float* obs_out, float* inputs_out, float* costs_out, int n_records, size_t state_stride,
+                                        size_t input_stride, size_t cost_stride);
 hipError_t ctk_launch_mppi_merge_partial(hipStream_t st, const float* parts, int n_parts, int per_block, int P,
                                          float neg_inv_lbd, float* out_rec);
 // direct peer-to-peer record exchange + merge + update (ctk_mppi.hip: ctk_mppi_p2p_exchange)

@@ -59,3 +59,100 @@ hipError_t ctk_launch_batch_plant(hipStream_t st, int env, const CtkBatchDesc* d
     });
     return hipGetLastError();
 }
+
+// ---- the stochastic plant (include/ctk_hip_episode.h: ctk_batch_episodes / ctk_batch_plant_step_noisy) ----
+//   ctk_batch_plant_noisy<ENV>   one lane per step record, beside ctk_batch_plant<ENV>:
+//        n       = the normal draws [2 S] of (noise seed, stream CTK_PLANT_STREAM, call pos + t, row 0): draw4's arithmetic, column
+//                  blocks 0 .. ceil(2 S / 4) - 1; columns [0, S) process noise, [S, 2 S) measurement noise
+//        c_k     = Env<ENV>::stage_cost(k_plant, s_k, u_k, u_{k-1})           the realised cost, with the PLANT's constants
+//        s_{k+1} = Env<ENV>::step(k_plant, s_k, u_k) + sigma_w * n[0:S]       the true state: to the state trace
+//        y_{k+1} = s_{k+1} + sigma_v * n[S:2S]                                what the controller is given: to the observation trace
+//                                                                             and into the next step's record
+//        A component whose sigma is 0 is SELECTED, not added to (-0.0 survives); a record whose sigmas are all 0 draws nothing, and
+//        its transition is then the one of ctk_batch_plant<ENV>.
+//        Where the operands come from: the record's s holds y_k, not s_k, so the TRUE state is read from s_true (the state trace row
+//        the previous transition wrote, or what the host put there for a segment's first step); u_k from the problem's u_dev (what
+//        the controller launch ahead published) or the caller's array; u_{k-1} from u_last (the input trace row k - 1, or the host's
+//        row for a segment's first step), because u_dev no longer holds it.  The noise record of lane j lies behind the step records
+//        and travels with them; `t` is the step within the segment, added to the record's position.
+// Plain vector loads and stores, no LDS, no scratch; ordered by the stream like ctk_batch_plant.
+template <int ENV>
+__global__ __launch_bounds__(PLANT_BLOCK) void ctk_batch_plant_noisy(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ cur,
+                                                                    CtkBatchStep* __restrict__ next, const unsigned char* __restrict__ kplant,
+                                                                    const CtkPlantNoise* __restrict__ noise, const float* __restrict__ u_in,
+                                                                    const float* __restrict__ s_true, const float* __restrict__ u_last,
+                                                                    float* __restrict__ states_out, float* __restrict__ obs_out,
+                                                                    float* __restrict__ inputs_out, float* __restrict__ costs_out, int n,
+                                                                    uint32_t t, size_t s_true_stride, size_t u_last_stride, size_t state_stride,
+                                                                    size_t input_stride, size_t cost_stride) {
+    using E = Env<ENV>;
+    constexpr int S = E::S, C = E::C, NB = (2 * S + 3) / 4;
+    const int j = blockIdx.x * PLANT_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const int p = cur[j].id;
+    const typename E::K k = *reinterpret_cast<const typename E::K*>(kplant + (size_t)p * CtkBatchKStride<ENV>::value);
+    const CtkPlantNoise& nz = noise[j];
+    const float* up = u_in ? u_in + (size_t)j * C : desc[p].u_dev;
+    float s[S], s0[S], u[C], ul[C];
+#pragma unroll
+    for (int i = 0; i < S; ++i) s[i] = s0[i] = s_true[(size_t)j * s_true_stride + i];
+#pragma unroll
+    for (int c = 0; c < C; ++c) { u[c] = up[c]; ul[c] = u_last[(size_t)j * u_last_stride + c]; }
+    const float cost = E::stage_cost(k, s0, u, ul);
+    E::step(k, s, u);
+    float y[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) y[i] = s[i];
+    if (nz.any) {
+        float z[NB * 4];
+#pragma unroll
+        for (int cb = 0; cb < NB; ++cb) {
+            // draw4 (ctk_device.h), kind 0, with the counter (row 0, column block, position, stream)
+            const U4 r = philox4x32_10(U4{0u, (uint32_t)cb, nz.pos + t, CTK_PLANT_STREAM}, nz.seed_lo, nz.seed_hi);
+            const float ra = sqrtf(-2.0f * logf(u32_unit_open(r.x)));
+            const float rb = sqrtf(-2.0f * logf(u32_unit_open(r.z)));
+            float sa, ca, sb, cb2;
+            sincosf(6.28318530717958647692f * u32_unit_halfopen(r.y), &sa, &ca);
+            sincosf(6.28318530717958647692f * u32_unit_halfopen(r.w), &sb, &cb2);
+            z[4 * cb] = ra * ca; z[4 * cb + 1] = ra * sa; z[4 * cb + 2] = rb * cb2; z[4 * cb + 3] = rb * sb;
+        }
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            const float sw = nz.sigma_w[i], sv = nz.sigma_v[i];
+            s[i] = sw != 0.0f ? s[i] + sw * z[i] : s[i];
+            y[i] = sv != 0.0f ? s[i] + sv * z[S + i] : s[i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+        states_out[(size_t)j * state_stride + i] = s[i];
+        obs_out[(size_t)j * state_stride + i] = y[i];
+    }
+    costs_out[(size_t)j * cost_stride] = cost;
+    if (inputs_out) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) inputs_out[(size_t)j * input_stride + c] = u[c];
+    }
+    if (next) {
+#pragma unroll
+        for (int i = 0; i < S; ++i) next[j].s[i] = y[i];
+    }
+}
+
+const char* ctk_batch_plant_noisy_name(int env) { return ctk_kernel_name("ctk_batch_plant_noisy<%d>", env); }
+
+hipError_t ctk_launch_batch_plant_noisy(hipStream_t st, int env, const CtkBatchDesc* desc_dev, const CtkBatchStep* cur_dev, CtkBatchStep* next_dev,
+                                        const void* kplant_dev, const CtkPlantNoise* noise_dev, const float* u_in_dev, const float* s_true_dev,
+                                        size_t s_true_stride, const float* u_last_dev, size_t u_last_stride, uint32_t t, float* states_out,
+                                        float* obs_out, float* inputs_out, float* costs_out, int n_records, size_t state_stride,
+                                        size_t input_stride, size_t cost_stride) {
+    if (n_records < 1 || !desc_dev || !cur_dev || !kplant_dev || !noise_dev || !s_true_dev || !u_last_dev || !states_out || !obs_out || !costs_out)
+        return hipErrorInvalidValue;
+    const dim3 grid((n_records + PLANT_BLOCK - 1) / PLANT_BLOCK), block(PLANT_BLOCK);
+    CTK_FOR_ENV(env, EV, {
+        hipLaunchKernelGGL((ctk_batch_plant_noisy<EV>), grid, block, 0, st, desc_dev, cur_dev, next_dev, static_cast<const unsigned char*>(kplant_dev),
+                           noise_dev, u_in_dev, s_true_dev, u_last_dev, states_out, obs_out, inputs_out, costs_out, n_records, t, s_true_stride,
+                           u_last_stride, state_stride, input_stride, cost_stride);
+    });
+    return hipGetLastError();
+}

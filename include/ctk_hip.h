@@ -737,4 +737,5 @@ int ctk_mlp_problem_have_weights(const ctk_mlp_batch* b, int problem);          
 #endif
 /* closed-loop episodes of the MPPI batches on the device (a run with the plant step included): declared in a header of their own */
 #include "ctk_hip_run.h"
+#include "ctk_hip_episode.h"
 #endif /* CTK_HIP_H */
