@@ -2541,6 +2541,9 @@ hipError_t batch_send_records(BatchCore* b, unsigned char* kcache, const int32_t
     return e;
 }
 
+// problem p onto a message's list of problems ("3, 7, 12")
+void list_problem(std::string& list, int p) { list += (list.empty() ? "" : ", ") + std::to_string(p); }
+
 // completion of a step: the {u, seq} store of each of the first `launched` listed problems landing in its pinned slot (finish_step's
 // bounded spin: one budget of pauses for the whole call, then one synchronise, then give up).  Returns the problems that never published.
 std::string batch_poll(BatchCore* b, const int32_t* ids, int launched) {
@@ -2556,7 +2559,7 @@ std::string batch_poll(BatchCore* b, const int32_t* ids, int launched) {
             if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
             break;
         }
-        if (*slot != want) late += (late.empty() ? "" : ", ") + std::to_string(p);
+        if (*slot != want) list_problem(late, p);
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     return late;
@@ -2663,7 +2666,7 @@ struct ctk_batch : BatchCore {
     std::vector<int> plant_sub;             // [B] ... and their Euler sub-step count (0: nothing derived yet)
     unsigned char* h_kplant = nullptr;      // pinned [B][kstride] the plants' derived constants, the staging of the copy to d_kplant
     unsigned char* d_kplant = nullptr;      // [B][kstride]
-    unsigned char* h_run = nullptr;         // pinned: step records [L][n] | inputs of a plant step [n][C] | state trace [n][L][S] | input trace [n][L][C]
+    unsigned char* h_run = nullptr;         // pinned: the step records, plant operands and traces of one segment or plant step (LoopLayout)
     unsigned char* d_run = nullptr;         // the same on the device; both grow on demand (batch_run_buffers)
     size_t run_cap = 0;
     int run_segment = 256;                  // steps per segment of a run: a diagnostic switch may lower it (ctk_batch_create)
@@ -2760,53 +2763,43 @@ hipError_t batch_plant_flush(ctk_batch* b, int substeps) {
     return e;
 }
 
-// where the parts of the run buffer lie for n problems and L steps (bytes from its start; every part 16-aligned)
-struct RunLayout {
-    size_t u_in, states, inputs, total;
-    RunLayout(const ctk_batch* b, int n, int L) {
+// Where the parts of the run buffer lie for a segment of n problems and L steps (bytes from its start; every part 16-aligned).  What
+// travels to the device in ONE transfer lies in front (up to `states`), what comes back in ONE copy behind it:
+//   step records [L][n] | inputs of a plant step [n][C] | true start states [n][S] | previous inputs of the first step [n][C] |
+//   noise records [n] || state trace [n][L][S] | observation trace [n][L][S] | input trace [n][L][C] | realised costs [n][L]
+// The parts only the noisy plant has (s_start, u_start, noise, obs, costs) are empty without it (ctk_batch_run / ctk_batch_plant_step):
+// what then remains is  step records | inputs of a plant step || state trace | input trace.
+struct LoopLayout {
+    size_t u_in, s_start, u_start, noise, states, obs, inputs, costs, total;
+    LoopLayout(const ctk_batch* b, int n, int L, bool noisy) {
         auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        auto ep = [&](size_t x) { return noisy ? x : 0; };
         u_in = (size_t)L * n * sizeof(CtkBatchStep);
-        states = u_in + up((size_t)n * b->C * sizeof(float));
-        inputs = states + up((size_t)n * L * b->S * sizeof(float));
-        total = inputs + up((size_t)n * L * b->C * sizeof(float));
+        s_start = u_in + up((size_t)n * b->C * sizeof(float));
+        u_start = s_start + ep(up((size_t)n * b->S * sizeof(float)));
+        noise = u_start + ep(up((size_t)n * b->C * sizeof(float)));
+        states = noise + ep((size_t)n * sizeof(CtkPlantNoise));
+        obs = states + up((size_t)n * L * b->S * sizeof(float));
+        inputs = obs + ep(up((size_t)n * L * b->S * sizeof(float)));
+        costs = inputs + up((size_t)n * L * b->C * sizeof(float));
+        total = costs + ep(up((size_t)n * L * sizeof(float)));
     }
 };
 static_assert(sizeof(CtkBatchStep) % 16 == 0, "the parts of the run buffer lie behind the step records, 16-aligned");
+static_assert(sizeof(CtkPlantNoise) % 16 == 0, "the traces lie behind the noise records, 16-aligned");
 
-// the run buffer (device and pinned), grown to `total` bytes on demand
-int batch_run_buffers(ctk_batch* b, size_t total) {
-    if (total <= b->run_cap) return CTK_OK;
+// the run buffer (device and pinned), grown to the layout's bytes on demand
+int batch_run_buffers(ctk_batch* b, const LoopLayout& lay) {
+    if (lay.total <= b->run_cap) return CTK_OK;
     if (b->d_run) BHIP_TRY(b, hipFree(b->d_run));
     b->d_run = nullptr; b->run_cap = 0;
     if (b->h_run) BHIP_TRY(b, hipHostFree(b->h_run));
     b->h_run = nullptr;
-    BHIP_TRY(b, hipMalloc((void**)&b->d_run, total));
-    BHIP_TRY(b, hipHostMalloc((void**)&b->h_run, total, hipHostMallocDefault));
-    b->run_cap = total;
+    BHIP_TRY(b, hipMalloc((void**)&b->d_run, lay.total));
+    BHIP_TRY(b, hipHostMalloc((void**)&b->h_run, lay.total, hipHostMallocDefault));
+    b->run_cap = lay.total;
     return CTK_OK;
 }
-int batch_run_buffers(ctk_batch* b, const RunLayout& lay) { return batch_run_buffers(b, lay.total); }
-
-// where the parts of the run buffer lie for an episode segment of n problems and L steps (ctk_batch_episodes / ctk_batch_plant_step_noisy).
-// What travels to the device in ONE transfer lies in front (up to `states`), what comes back in ONE copy behind it:
-//   step records [L][n] | inputs of a noisy plant step [n][C] | true start states [n][S] | previous inputs of the first step [n][C] |
-//   noise records [n] || state trace [n][L][S] | observation trace [n][L][S] | input trace [n][L][C] | realised costs [n][L]
-struct EpisodeLayout {
-    size_t u_in, s_start, u_start, noise, states, obs, inputs, costs, total;
-    EpisodeLayout(const ctk_batch* b, int n, int L) {
-        auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-        u_in = (size_t)L * n * sizeof(CtkBatchStep);
-        s_start = u_in + up((size_t)n * b->C * sizeof(float));
-        u_start = s_start + up((size_t)n * b->S * sizeof(float));
-        noise = u_start + up((size_t)n * b->C * sizeof(float));
-        states = noise + (size_t)n * sizeof(CtkPlantNoise);
-        obs = states + up((size_t)n * L * b->S * sizeof(float));
-        inputs = obs + up((size_t)n * L * b->S * sizeof(float));
-        costs = inputs + up((size_t)n * L * b->C * sizeof(float));
-        total = costs + up((size_t)n * L * sizeof(float));
-    }
-};
-static_assert(sizeof(CtkPlantNoise) % 16 == 0, "the traces lie behind the noise records, 16-aligned");
 
 // problem p's noise record at its current position
 void batch_noise_record(const ctk_batch* b, int p, CtkPlantNoise* q) {
@@ -2824,6 +2817,233 @@ void batch_noise_record(const ctk_batch* b, int p, CtkPlantNoise* q) {
 int batch_substeps(ctk_batch* b, const char* who, int substeps, int* out) {
     if (substeps < 0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": the plant's sub-step count must be >= 1, or 0 for cfg.intermediate_steps (" + std::to_string(substeps) + ")");
     *out = substeps ? substeps : b->cfg.intermediate_steps;
+    return CTK_OK;
+}
+
+// what a step record says of the step that problem p takes t steps from now (ctk_batch_step: t == 0; a segment of the closed loop: t in
+// [0, L)): its counters, and no draws.  The state and the previous input are the caller's.
+void batch_fill_record(const ctk_batch* b, CtkBatchStep& q, int p, int t) {
+    q.id = p; q.seq = b->seq[(size_t)p] + (uint32_t)t; q.call = b->call[(size_t)p] + (uint32_t)t;
+    q.cur = (uint32_t)(b->cur[(size_t)p] ^ (t & 1));
+    q.pad = 0u; q.samples = nullptr;
+}
+
+// One plant step of the listed problems (ctk_batch_plant_step; with y_next, ctk_batch_plant_step_noisy): the records, the inputs and
+// what the noisy plant reads besides travel in ONE transfer, one launch, one copy back, one synchronisation.
+int batch_plant_step(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev,
+                     int substeps, float* s_next, float* y_next, float* cost) {
+    const bool noisy = y_next != nullptr;
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (int rc = batch_substeps(b, who, substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const LoopLayout lay(b, n, 1, noisy);
+    if (int rc = batch_run_buffers(b, lay)) return rc;
+    // the records carry the problem and, for the plain plant, its state; the noisy plant reads the state from a row of its own
+    CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
+    CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
+    for (int j = 0; j < n; ++j) {
+        std::memset(&rec[j], 0, sizeof(CtkBatchStep));
+        rec[j].id = ids ? ids[j] : j;
+        if (noisy) batch_noise_record(b, rec[j].id, &nz[j]);
+        else for (int i = 0; i < S; ++i) rec[j].s[i] = s[(size_t)j * S + i];
+    }
+    std::memcpy(b->h_run + lay.u_in, u, (size_t)n * C * sizeof(float));
+    if (noisy) {
+        std::memcpy(b->h_run + lay.s_start, s, (size_t)n * S * sizeof(float));
+        std::memcpy(b->h_run + lay.u_start, u_prev, (size_t)n * C * sizeof(float));
+    }
+    const CtkBatchStep* d_rec = reinterpret_cast<const CtkBatchStep*>(b->d_run);
+    auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+    const size_t back = noisy ? lay.total - lay.states : (size_t)n * S * sizeof(float);      // the plain plant wrote the next states alone
+    hipError_t le = batch_plant_flush(b, sub);
+    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
+    bool launched = false;
+    if (le == hipSuccess) {
+        if (noisy)
+            le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec, nullptr, b->d_kplant,
+                                              reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise), dev(lay.u_in), dev(lay.s_start), (size_t)S,
+                                              dev(lay.u_start), (size_t)C, 0u, dev(lay.states), dev(lay.obs), nullptr, dev(lay.costs), n, (size_t)S, 0, 1);
+        else
+            le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec, nullptr, b->d_kplant, dev(lay.u_in), dev(lay.states), nullptr, n,
+                                        (size_t)S, 0);
+        launched = le == hipSuccess;
+    }
+    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, back, hipMemcpyDeviceToHost, b->stream);
+    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
+    if (le == hipSuccess) le = se;
+    if (noisy && launched)
+        for (int j = 0; j < n; ++j) ++b->noise_pos[(size_t)rec[j].id];         // by the plant launch that was issued
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string(who) + ": " + hipGetErrorString(le));
+    std::memcpy(s_next, b->h_run + lay.states, (size_t)n * S * sizeof(float));
+    if (noisy) {
+        std::memcpy(y_next, b->h_run + lay.obs, (size_t)n * S * sizeof(float));
+        std::memcpy(cost, b->h_run + lay.costs, (size_t)n * sizeof(float));
+    }
+    return CTK_OK;
+}
+
+// The counters after a segment of L steps whose launches ended with `le`.  `ctrl` steps had the controllers of all n listed problems
+// launched; if the launches of the step after them failed (part >= 0), those of its first `part` problems were; `plants` launches of
+// the noisy plant were issued (a run: 0).  seq, call, cur and noise_pos are left as if exactly these had run, by the rule of
+// ctk_batch_step: a listed problem consumes its sequence number launched or not, its Philox position and plan buffer only if launched.
+// Only where nothing failed, a problem whose slot does not show the segment's last step is listed in `late`; the hand-off's error word
+// is read and cleared into timed[j] whatever happened.
+void batch_loop_account(ctk_batch* b, int n, const int32_t* ids, hipError_t le, int L, int ctrl, int part, int plants, std::string& late,
+                        std::vector<unsigned char>& timed) {
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
+        if (le == hipSuccess && slot[1] != b->seq[(size_t)p] + (uint32_t)(L - 1)) list_problem(late, p);
+        if (slot[2]) { slot[2] = 0; timed[(size_t)j] = 1; }                   // the hand-off's error word, read and cleared
+        b->seq[(size_t)p] += (uint32_t)ctrl; b->call[(size_t)p] += (uint32_t)ctrl; b->cur[(size_t)p] ^= ctrl & 1;
+        if (part >= 0) {
+            ++b->seq[(size_t)p];
+            if (j < part) { ++b->call[(size_t)p]; b->cur[(size_t)p] ^= 1; }
+        }
+        b->noise_pos[(size_t)p] += (uint32_t)plants;
+    }
+}
+
+// a closed-loop call: ctk_batch_run, or with obs_out (and costs_out) ctk_batch_episodes
+struct LoopCall {
+    const char* who;                        // the entry point, for the messages
+    const char* noun;                       // "a run" / "an episode"
+    int n_ids; const int32_t* ids;
+    const float *s0, *y0, *u_prev;
+    int n_steps, plant_substeps;
+    float *states_out, *obs_out, *inputs_out, *costs_out;
+    int32_t* first_bad;
+};
+
+// The closed loop on the device, in segments of at most run_segment steps.  A segment is ONE transfer of its step records (and what the
+// noisy plant reads at its first step), per step the controller launches and one plant launch, ONE copy of the traces back and ONE
+// synchronisation; the plant launch of step t writes the state (the noisy plant: the observation) into the records of step t + 1 on the
+// device.  The noisy plant differs in where it reads from (the true state and the previous input have rows of their own, see
+// ctk_plant.hip), in its noise positions and in the two further traces.
+int batch_closed_loop(ctk_batch* b, const LoopCall& c) {
+    const bool noisy = c.obs_out != nullptr;
+    const int32_t* ids = c.ids;
+    const float* u_prev = c.u_prev;
+    const int n_steps = c.n_steps;
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, c.who, c.n_ids, ids, &n)) return rc;
+    if (n_steps < 1)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(c.who) + ": " + c.noun + " has at least one step (n_steps == " + std::to_string(n_steps) + ")");
+    if (int rc = batch_substeps(b, c.who, c.plant_substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const size_t srow = ((size_t)n_steps + 1) * S, urow = (size_t)n_steps * C;       // one problem's rows of the traces
+    for (int j = 0; j < n; ++j) {
+        std::memcpy(c.states_out + (size_t)j * srow, c.s0 + (size_t)j * S, (size_t)S * sizeof(float));
+        if (noisy) std::memcpy(c.obs_out + (size_t)j * srow, (c.y0 ? c.y0 : c.s0) + (size_t)j * S, (size_t)S * sizeof(float));
+        if (c.first_bad) c.first_bad[j] = -1;
+    }
+    // The noisy plant without u_prev: the first step's previous input is what the first controller launch reads as its own — the problem's
+    // last output in d_u (ctk_batch_set_state writes it too, the pinned result slot only holds what a step published).  That launch
+    // overwrites it, so the span of the listed problems is read here, once per call, ahead of everything else.  A run has no use for it.
+    const int p_lo = ids ? ids[0] : 0, p_hi = ids ? ids[n - 1] : n - 1;
+    std::vector<float> own_u;
+    if (noisy && !u_prev) {
+        own_u.resize((size_t)(p_hi - p_lo + 1) * CTK_MAX_INPUTS);
+        BHIP_TRY(b, hipMemcpyAsync(own_u.data(), b->d_u + (size_t)p_lo * CTK_MAX_INPUTS, own_u.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+        BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    }
+    const float* first_s = noisy ? c.obs_out : c.states_out;                   // what the controllers see: of a run the state itself
+    std::vector<unsigned char> timed((size_t)n, 0);
+    std::string late;
+    const RolloutArgs a = batch_args(b);
+    hipError_t le = batch_plant_flush(b, sub);
+    for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
+        const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
+        const LoopLayout lay(b, n, L, noisy);
+        if (int rc = batch_run_buffers(b, lay)) { hipStreamSynchronize(b->stream); return rc; }
+        // every record of the segment: all but the state is known in advance.  The state of the segment's first step is the host's (the
+        // start state or observation, or the previous segment's last one from the copied trace); the later ones the plant launches write
+        // on the device.
+        CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
+        for (int t = 0; t < L; ++t) {
+            const bool given = k0 + t == 0 && u_prev;                          // from the second step on: the problem's own last output
+            for (int j = 0; j < n; ++j) {
+                CtkBatchStep& q = rec[(size_t)t * n + j];
+                batch_fill_record(b, q, ids ? ids[j] : j, t);
+                q.dev_uprev = given ? 0u : 1u;
+                for (int i = 0; i < CTK_MAX_STATES; ++i) q.s[i] = (t == 0 && i < S) ? first_s[(size_t)j * srow + (size_t)k0 * S + i] : 0.0f;
+                for (int i = 0; i < CTK_MAX_INPUTS; ++i) q.u_prev[i] = (given && i < C) ? u_prev[(size_t)j * C + i] : 0.0f;
+            }
+        }
+        // what the first noisy plant launch of the segment reads in place of trace rows: the true state, and the input before the
+        // segment's first one — the given u_prev, the previous segment's last input, or the problem's own last output (read above)
+        if (noisy) {
+            float* h_s = reinterpret_cast<float*>(b->h_run + lay.s_start);
+            float* h_up = reinterpret_cast<float*>(b->h_run + lay.u_start);
+            CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
+            for (int j = 0; j < n; ++j) {
+                const int p = ids ? ids[j] : j;
+                std::memcpy(h_s + (size_t)j * S, c.states_out + (size_t)j * srow + (size_t)k0 * S, (size_t)S * sizeof(float));
+                if (k0 > 0) std::memcpy(h_up + (size_t)j * C, c.inputs_out + (size_t)j * urow + ((size_t)k0 - 1) * C, (size_t)C * sizeof(float));
+                else if (u_prev) std::memcpy(h_up + (size_t)j * C, u_prev + (size_t)j * C, (size_t)C * sizeof(float));
+                else std::memcpy(h_up + (size_t)j * C, &own_u[(size_t)(p - p_lo) * CTK_MAX_INPUTS], (size_t)C * sizeof(float));
+                batch_noise_record(b, p, &nz[j]);
+            }
+        }
+        CtkBatchStep* d_rec = reinterpret_cast<CtkBatchStep*>(b->d_run);
+        auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+        const CtkPlantNoise* d_nz = reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise);
+        float *d_st = dev(lay.states), *d_ob = dev(lay.obs), *d_in = dev(lay.inputs), *d_co = dev(lay.costs);
+        if (b->differ) le = batch_flush_constants(b);                          // the constants' transfer goes ahead of the step records'
+        if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, noisy ? lay.states : lay.u_in, hipMemcpyHostToDevice, b->stream);
+        int ctrl = 0, part = -1, plants = 0;           // steps whose controllers were all launched; of the step whose launches failed, how
+                                                       // many were; the noisy plant launches that were issued
+        for (int t = 0; le == hipSuccess && t < L; ++t) {
+            int launched = 0;
+            le = batch_launch_records(b, a, d_rec + (size_t)t * n, n, &launched);
+            if (le != hipSuccess) { part = launched; break; }
+            ++ctrl;
+            CtkBatchStep* next = t + 1 < L ? d_rec + (size_t)(t + 1) * n : nullptr;
+            if (noisy) {
+                le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, next, b->d_kplant, d_nz, nullptr,
+                                                  t ? d_st + (size_t)(t - 1) * S : dev(lay.s_start), t ? (size_t)L * S : (size_t)S,
+                                                  t ? d_in + (size_t)(t - 1) * C : dev(lay.u_start), t ? (size_t)L * C : (size_t)C, (uint32_t)t,
+                                                  d_st + (size_t)t * S, d_ob + (size_t)t * S, d_in + (size_t)t * C, d_co + t, n, (size_t)L * S, (size_t)L * C,
+                                                  (size_t)L);
+                if (le == hipSuccess) ++plants;
+            } else {
+                le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, next, b->d_kplant, nullptr, d_st + (size_t)t * S,
+                                            d_in + (size_t)t * C, n, (size_t)L * S, (size_t)L * C);
+            }
+        }
+        if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
+        const hipError_t se = hipStreamSynchronize(b->stream);                 // ONE synchronisation per segment, whatever happened
+        if (le == hipSuccess) le = se;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        batch_loop_account(b, n, ids, le, L, ctrl, part, plants, late, timed);  // the counters reflect what was launched
+        if (le != hipSuccess) break;
+        auto host = [&](size_t at) { return reinterpret_cast<const float*>(b->h_run + at); };
+        const float *h_st = host(lay.states), *h_ob = host(lay.obs), *h_in = host(lay.inputs), *h_co = host(lay.costs);
+        for (int j = 0; j < n; ++j) {
+            std::memcpy(c.states_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_st + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+            std::memcpy(c.inputs_out + (size_t)j * urow + (size_t)k0 * C, h_in + (size_t)j * L * C, (size_t)L * C * sizeof(float));
+            if (noisy) {
+                std::memcpy(c.obs_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_ob + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+                std::memcpy(c.costs_out + (size_t)j * n_steps + (size_t)k0, h_co + (size_t)j * L, (size_t)L * sizeof(float));
+            }
+            if (c.first_bad && c.first_bad[j] < 0)
+                for (int i = 0; i < L * C; ++i)
+                    if (!std::isfinite(h_in[(size_t)j * L * C + i])) { c.first_bad[j] = k0 + i / C; break; }
+        }
+        k0 += L;
+    }
+    if (le != hipSuccess)
+        return bfail(b, CTK_ERR_HIP, std::string(c.who) + ": " + hipGetErrorString(le) + " (the counters reflect the steps that were launched; the traces are not valid)");
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, std::string(c.who) + ": a segment finished without publishing the last result of problem(s) " + late);
+    std::string timed_out;
+    for (int j = 0; j < n; ++j)
+        if (timed[(size_t)j]) list_problem(timed_out, ids ? ids[j] : j);
+    if (!timed_out.empty())
+        return bfail(b, CTK_ERR_STATE, std::string(c.who) + ": in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; such a step publishes NaN and the plant propagates it: their traces show where (first_bad), the other problems' traces are valid");
     return CTK_OK;
 }
 
@@ -3036,11 +3256,9 @@ int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, 
     }
     // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es)
     for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
         CtkBatchStep& q = b->h_steps[j];
-        q.id = p; q.seq = b->seq[(size_t)p]; q.call = b->call[(size_t)p]; q.cur = (uint32_t)b->cur[(size_t)p];
-        q.pad = 0u;
-        q.samples = d_s ? d_s + (size_t)j * per : nullptr;
+        batch_fill_record(b, q, ids ? ids[j] : j, 0);
+        if (d_s) q.samples = d_s + (size_t)j * per;
         batch_record_io(b, q, j, s, u_prev);
     }
     hipError_t le = b->differ ? batch_flush_constants(b) : hipSuccess;          // the constants' transfer goes ahead of the step records'
@@ -3058,7 +3276,7 @@ int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, 
         ++b->call[(size_t)p];                          // by history: for every launched problem, published or not (CEM and RPGD: only if its slot shows the step's seq)
         batch_read_u(b, p, j, u_out);
         volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;   // the hand-off's error word (MPPI and CEM; RPGD has none)
-        if (errw[0]) { errw[0] = 0; timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(p); }
+        if (errw[0]) { errw[0] = 0; list_problem(timed_out, p); }
     }
     if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_step: ") + hipGetErrorString(le));
     if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_step: the step finished without publishing the result of problem(s) " + late);
@@ -3166,125 +3384,15 @@ int ctk_batch_plant_clear_params(ctk_batch* b) {
 int ctk_batch_plant_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u, int substeps, float* s_next) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     if (!s || !u || !s_next) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_step: NULL state, input or destination");
-    int n = 0, sub = 0;
-    if (int rc = batch_ids(b, "ctk_batch_plant_step", n_ids, ids, &n)) return rc;
-    if (int rc = batch_substeps(b, "ctk_batch_plant_step", substeps, &sub)) return rc;
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));
-    const RunLayout lay(b, n, 1);
-    if (int rc = batch_run_buffers(b, lay)) return rc;
-    // the records carry the problem and its state only; they and the inputs behind them travel in ONE transfer
-    CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
-    for (int j = 0; j < n; ++j) {
-        std::memset(&rec[j], 0, sizeof(CtkBatchStep));
-        rec[j].id = ids ? ids[j] : j;
-        for (int i = 0; i < b->S; ++i) rec[j].s[i] = s[(size_t)j * b->S + i];
-    }
-    std::memcpy(b->h_run + lay.u_in, u, (size_t)n * b->C * sizeof(float));
-    const size_t out_bytes = (size_t)n * b->S * sizeof(float);
-    hipError_t le = batch_plant_flush(b, sub);
-    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
-    if (le == hipSuccess)
-        le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, reinterpret_cast<const CtkBatchStep*>(b->d_run), nullptr, b->d_kplant,
-                                    reinterpret_cast<const float*>(b->d_run + lay.u_in), reinterpret_cast<float*>(b->d_run + lay.states), nullptr, n,
-                                    (size_t)b->S, 0);
-    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, out_bytes, hipMemcpyDeviceToHost, b->stream);
-    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
-    if (le == hipSuccess) le = se;
-    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_plant_step: ") + hipGetErrorString(le));
-    std::memcpy(s_next, b->h_run + lay.states, out_bytes);
-    return CTK_OK;
+    return batch_plant_step(b, "ctk_batch_plant_step", n_ids, ids, s, u, nullptr, substeps, s_next, nullptr, nullptr);
 }
 
 int ctk_batch_run(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, const float* u_prev, int n_steps, int plant_substeps,
                   float* states_out, float* inputs_out, int32_t* first_bad) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     if (!s0 || !states_out || !inputs_out) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_run: NULL start states or trace destination");
-    int n = 0, sub = 0;
-    if (int rc = batch_ids(b, "ctk_batch_run", n_ids, ids, &n)) return rc;
-    if (n_steps < 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_run: a run has at least one step (n_steps == " + std::to_string(n_steps) + ")");
-    if (int rc = batch_substeps(b, "ctk_batch_run", plant_substeps, &sub)) return rc;
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));
-    const int S = b->S, C = b->C;
-    const size_t srow = ((size_t)n_steps + 1) * S, urow = (size_t)n_steps * C;       // one problem's rows of the two traces
-    for (int j = 0; j < n; ++j) {
-        std::memcpy(states_out + (size_t)j * srow, s0 + (size_t)j * S, (size_t)S * sizeof(float));
-        if (first_bad) first_bad[j] = -1;
-    }
-    std::vector<unsigned char> timed((size_t)n, 0);
-    std::string late;
-    const RolloutArgs a = batch_args(b);
-    hipError_t le = batch_plant_flush(b, sub);
-    for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
-        const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
-        const RunLayout lay(b, n, L);
-        if (int rc = batch_run_buffers(b, lay)) { hipStreamSynchronize(b->stream); return rc; }
-        // every record of the segment: all but the state is known in advance.  The state of the segment's first step is the host's (the
-        // start state, or the previous segment's last one from the copied trace); the later ones the plant launches write on the device.
-        CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
-        for (int t = 0; t < L; ++t) {
-            const bool given = k0 + t == 0 && u_prev;                          // from the second step on: the problem's own last output
-            for (int j = 0; j < n; ++j) {
-                const int p = ids ? ids[j] : j;
-                CtkBatchStep& q = rec[(size_t)t * n + j];
-                q.id = p; q.seq = b->seq[(size_t)p] + (uint32_t)t; q.call = b->call[(size_t)p] + (uint32_t)t;
-                q.cur = (uint32_t)(b->cur[(size_t)p] ^ (t & 1));
-                q.dev_uprev = given ? 0u : 1u; q.pad = 0u; q.samples = nullptr;
-                for (int i = 0; i < CTK_MAX_STATES; ++i) q.s[i] = (t == 0 && i < S) ? states_out[(size_t)j * srow + (size_t)k0 * S + i] : 0.0f;
-                for (int c = 0; c < CTK_MAX_INPUTS; ++c) q.u_prev[c] = (given && c < C) ? u_prev[(size_t)j * C + c] : 0.0f;
-            }
-        }
-        CtkBatchStep* d_rec = reinterpret_cast<CtkBatchStep*>(b->d_run);
-        float* d_st = reinterpret_cast<float*>(b->d_run + lay.states);
-        float* d_in = reinterpret_cast<float*>(b->d_run + lay.inputs);
-        if (b->differ) le = batch_flush_constants(b);                          // the constants' transfer goes ahead of the step records'
-        if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.u_in, hipMemcpyHostToDevice, b->stream);
-        int ctrl = 0, part = -1;                       // steps whose controllers were all launched; of the step whose launches failed, how many were
-        for (int t = 0; le == hipSuccess && t < L; ++t) {
-            int launched = 0;
-            le = batch_launch_records(b, a, d_rec + (size_t)t * n, n, &launched);
-            if (le != hipSuccess) { part = launched; break; }
-            ++ctrl;
-            le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, t + 1 < L ? d_rec + (size_t)(t + 1) * n : nullptr, b->d_kplant,
-                                        nullptr, d_st + (size_t)t * S, d_in + (size_t)t * C, n, (size_t)L * S, (size_t)L * C);
-        }
-        if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
-        const hipError_t se = hipStreamSynchronize(b->stream);                 // ONE synchronisation per segment
-        if (le == hipSuccess) le = se;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        // the counters reflect what was launched (ctk_batch_step: a listed problem consumes its sequence number launched or not)
-        for (int j = 0; j < n; ++j) {
-            const int p = ids ? ids[j] : j;
-            volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
-            if (le == hipSuccess && slot[1] != b->seq[(size_t)p] + (uint32_t)(L - 1)) late += (late.empty() ? "" : ", ") + std::to_string(p);
-            if (slot[2]) { slot[2] = 0; timed[(size_t)j] = 1; }               // the hand-off's error word, read and cleared
-            b->seq[(size_t)p] += (uint32_t)ctrl; b->call[(size_t)p] += (uint32_t)ctrl; b->cur[(size_t)p] ^= ctrl & 1;
-            if (part >= 0) {
-                ++b->seq[(size_t)p];
-                if (j < part) { ++b->call[(size_t)p]; b->cur[(size_t)p] ^= 1; }
-            }
-        }
-        if (le != hipSuccess) break;
-        const float* h_st = reinterpret_cast<const float*>(b->h_run + lay.states);
-        const float* h_in = reinterpret_cast<const float*>(b->h_run + lay.inputs);
-        for (int j = 0; j < n; ++j) {
-            std::memcpy(states_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_st + (size_t)j * L * S, (size_t)L * S * sizeof(float));
-            std::memcpy(inputs_out + (size_t)j * urow + (size_t)k0 * C, h_in + (size_t)j * L * C, (size_t)L * C * sizeof(float));
-            if (first_bad && first_bad[j] < 0)
-                for (int i = 0; i < L * C; ++i)
-                    if (!std::isfinite(h_in[(size_t)j * L * C + i])) { first_bad[j] = k0 + i / C; break; }
-        }
-        k0 += L;
-    }
-    if (le != hipSuccess)
-        return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_run: ") + hipGetErrorString(le) + " (the counters reflect the steps that were launched; the traces are not valid)");
-    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_run: a segment finished without publishing the last result of problem(s) " + late);
-    std::string timed_out;
-    for (int j = 0; j < n; ++j)
-        if (timed[(size_t)j]) timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(ids ? ids[j] : j);
-    if (!timed_out.empty())
-        return bfail(b, CTK_ERR_STATE, "ctk_batch_run: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
-                     "; such a step publishes NaN and the plant propagates it: their traces show where (first_bad), the other problems' traces are valid");
-    return CTK_OK;
+    return batch_closed_loop(b, LoopCall{"ctk_batch_run", "a run", n_ids, ids, s0, nullptr, u_prev, n_steps, plant_substeps, states_out, nullptr, inputs_out,
+                                         nullptr, first_bad});
 }
 
 // ---- the stochastic plant and the realised cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes) ----
@@ -3350,173 +3458,16 @@ int ctk_batch_plant_step_noisy(ctk_batch* b, int n_ids, const int32_t* ids, cons
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     if (!s || !u || !u_prev || !s_next || !y_next || !cost)
         return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_step_noisy: NULL state, input, previous input or destination");
-    int n = 0, sub = 0;
-    if (int rc = batch_ids(b, "ctk_batch_plant_step_noisy", n_ids, ids, &n)) return rc;
-    if (int rc = batch_substeps(b, "ctk_batch_plant_step_noisy", substeps, &sub)) return rc;
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));
-    const int S = b->S, C = b->C;
-    const EpisodeLayout lay(b, n, 1);
-    if (int rc = batch_run_buffers(b, lay.total)) return rc;
-    // the records carry the problem only; they, the states, the two inputs and the noise records travel in ONE transfer
-    CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
-    CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
-    for (int j = 0; j < n; ++j) {
-        std::memset(&rec[j], 0, sizeof(CtkBatchStep));
-        rec[j].id = ids ? ids[j] : j;
-        batch_noise_record(b, rec[j].id, &nz[j]);
-    }
-    std::memcpy(b->h_run + lay.u_in, u, (size_t)n * C * sizeof(float));
-    std::memcpy(b->h_run + lay.s_start, s, (size_t)n * S * sizeof(float));
-    std::memcpy(b->h_run + lay.u_start, u_prev, (size_t)n * C * sizeof(float));
-    auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
-    hipError_t le = batch_plant_flush(b, sub);
-    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
-    bool launched = false;
-    if (le == hipSuccess) {
-        le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, reinterpret_cast<const CtkBatchStep*>(b->d_run), nullptr, b->d_kplant,
-                                          reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise), dev(lay.u_in), dev(lay.s_start), (size_t)S,
-                                          dev(lay.u_start), (size_t)C, 0u, dev(lay.states), dev(lay.obs), nullptr, dev(lay.costs), n, (size_t)S, 0, 1);
-        launched = le == hipSuccess;
-    }
-    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
-    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
-    if (le == hipSuccess) le = se;
-    if (launched)
-        for (int j = 0; j < n; ++j) ++b->noise_pos[(size_t)rec[j].id];         // by the plant launch that was issued
-    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_plant_step_noisy: ") + hipGetErrorString(le));
-    std::memcpy(s_next, b->h_run + lay.states, (size_t)n * S * sizeof(float));
-    std::memcpy(y_next, b->h_run + lay.obs, (size_t)n * S * sizeof(float));
-    std::memcpy(cost, b->h_run + lay.costs, (size_t)n * sizeof(float));
-    return CTK_OK;
+    return batch_plant_step(b, "ctk_batch_plant_step_noisy", n_ids, ids, s, u, u_prev, substeps, s_next, y_next, cost);
 }
 
-// ctk_batch_run with the noisy plant: the same records, launches, segments, counters and error words; what differs is where the plant
-// reads from (the true state and the previous input have their own rows, see ctk_plant.hip) and the two further traces.
 int ctk_batch_episodes(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, const float* y0, const float* u_prev, int n_steps,
                        int plant_substeps, float* states_out, float* obs_out, float* inputs_out, float* costs_out, int32_t* first_bad) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     if (!s0 || !states_out || !obs_out || !inputs_out || !costs_out)
         return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_episodes: NULL start states or trace destination");
-    int n = 0, sub = 0;
-    if (int rc = batch_ids(b, "ctk_batch_episodes", n_ids, ids, &n)) return rc;
-    if (n_steps < 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_episodes: an episode has at least one step (n_steps == " + std::to_string(n_steps) + ")");
-    if (int rc = batch_substeps(b, "ctk_batch_episodes", plant_substeps, &sub)) return rc;
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));
-    const int S = b->S, C = b->C;
-    const size_t srow = ((size_t)n_steps + 1) * S, urow = (size_t)n_steps * C;       // one problem's rows of the traces
-    for (int j = 0; j < n; ++j) {
-        std::memcpy(states_out + (size_t)j * srow, s0 + (size_t)j * S, (size_t)S * sizeof(float));
-        std::memcpy(obs_out + (size_t)j * srow, (y0 ? y0 : s0) + (size_t)j * S, (size_t)S * sizeof(float));
-        if (first_bad) first_bad[j] = -1;
-    }
-    // u_prev == NULL: c_0's previous input is what the first controller launch reads as its own — the problem's last output in d_u
-    // (ctk_batch_set_state writes it too, the pinned result slot only holds what a step published).  That launch overwrites it, so the
-    // span of the listed problems is read here, once per call, ahead of everything else.
-    const int p_lo = ids ? ids[0] : 0, p_hi = ids ? ids[n - 1] : n - 1;
-    std::vector<float> own_u;
-    if (!u_prev) {
-        own_u.resize((size_t)(p_hi - p_lo + 1) * CTK_MAX_INPUTS);
-        BHIP_TRY(b, hipMemcpyAsync(own_u.data(), b->d_u + (size_t)p_lo * CTK_MAX_INPUTS, own_u.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-        BHIP_TRY(b, hipStreamSynchronize(b->stream));
-    }
-    std::vector<unsigned char> timed((size_t)n, 0);
-    std::string late;
-    const RolloutArgs a = batch_args(b);
-    hipError_t le = batch_plant_flush(b, sub);
-    for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
-        const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
-        const EpisodeLayout lay(b, n, L);
-        if (int rc = batch_run_buffers(b, lay.total)) { hipStreamSynchronize(b->stream); return rc; }
-        // every record of the segment, as in ctk_batch_run; the first step's record carries the OBSERVATION (the given one, or the
-        // previous segment's last from the copied trace), the later ones the plant launches write on the device
-        CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
-        float* h_s = reinterpret_cast<float*>(b->h_run + lay.s_start);
-        float* h_up = reinterpret_cast<float*>(b->h_run + lay.u_start);
-        CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
-        for (int t = 0; t < L; ++t) {
-            const bool given = k0 + t == 0 && u_prev;                          // from the second step on: the problem's own last output
-            for (int j = 0; j < n; ++j) {
-                const int p = ids ? ids[j] : j;
-                CtkBatchStep& q = rec[(size_t)t * n + j];
-                q.id = p; q.seq = b->seq[(size_t)p] + (uint32_t)t; q.call = b->call[(size_t)p] + (uint32_t)t;
-                q.cur = (uint32_t)(b->cur[(size_t)p] ^ (t & 1));
-                q.dev_uprev = given ? 0u : 1u; q.pad = 0u; q.samples = nullptr;
-                for (int i = 0; i < CTK_MAX_STATES; ++i) q.s[i] = (t == 0 && i < S) ? obs_out[(size_t)j * srow + (size_t)k0 * S + i] : 0.0f;
-                for (int c = 0; c < CTK_MAX_INPUTS; ++c) q.u_prev[c] = (given && c < C) ? u_prev[(size_t)j * C + c] : 0.0f;
-            }
-        }
-        // what the first plant launch of the segment reads in place of trace rows: the true state, and the input before the segment's
-        // first one — the given u_prev, the previous segment's last input, or the problem's own last output (read above)
-        for (int j = 0; j < n; ++j) {
-            const int p = ids ? ids[j] : j;
-            std::memcpy(h_s + (size_t)j * S, states_out + (size_t)j * srow + (size_t)k0 * S, (size_t)S * sizeof(float));
-            if (k0 > 0) std::memcpy(h_up + (size_t)j * C, inputs_out + (size_t)j * urow + ((size_t)k0 - 1) * C, (size_t)C * sizeof(float));
-            else if (u_prev) std::memcpy(h_up + (size_t)j * C, u_prev + (size_t)j * C, (size_t)C * sizeof(float));
-            else std::memcpy(h_up + (size_t)j * C, &own_u[(size_t)(p - p_lo) * CTK_MAX_INPUTS], (size_t)C * sizeof(float));
-            batch_noise_record(b, p, &nz[j]);
-        }
-        CtkBatchStep* d_rec = reinterpret_cast<CtkBatchStep*>(b->d_run);
-        auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
-        const CtkPlantNoise* d_nz = reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise);
-        float *d_st = dev(lay.states), *d_ob = dev(lay.obs), *d_in = dev(lay.inputs), *d_co = dev(lay.costs);
-        if (b->differ) le = batch_flush_constants(b);                          // the constants' transfer goes ahead of the step records'
-        if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
-        int ctrl = 0, part = -1, plants = 0;           // as in ctk_batch_run; plants: the plant launches that were issued
-        for (int t = 0; le == hipSuccess && t < L; ++t) {
-            int launched = 0;
-            le = batch_launch_records(b, a, d_rec + (size_t)t * n, n, &launched);
-            if (le != hipSuccess) { part = launched; break; }
-            ++ctrl;
-            le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, t + 1 < L ? d_rec + (size_t)(t + 1) * n : nullptr,
-                                              b->d_kplant, d_nz, nullptr, t ? d_st + (size_t)(t - 1) * S : dev(lay.s_start), t ? (size_t)L * S : (size_t)S,
-                                              t ? d_in + (size_t)(t - 1) * C : dev(lay.u_start), t ? (size_t)L * C : (size_t)C, (uint32_t)t,
-                                              d_st + (size_t)t * S, d_ob + (size_t)t * S, d_in + (size_t)t * C, d_co + t, n, (size_t)L * S, (size_t)L * C,
-                                              (size_t)L);
-            if (le == hipSuccess) ++plants;
-        }
-        if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
-        const hipError_t se = hipStreamSynchronize(b->stream);                 // ONE synchronisation per segment
-        if (le == hipSuccess) le = se;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        // the counters reflect what was launched, as in ctk_batch_run; the noise positions the plant launches
-        for (int j = 0; j < n; ++j) {
-            const int p = ids ? ids[j] : j;
-            volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
-            if (le == hipSuccess && slot[1] != b->seq[(size_t)p] + (uint32_t)(L - 1)) late += (late.empty() ? "" : ", ") + std::to_string(p);
-            if (slot[2]) { slot[2] = 0; timed[(size_t)j] = 1; }               // the hand-off's error word, read and cleared
-            b->seq[(size_t)p] += (uint32_t)ctrl; b->call[(size_t)p] += (uint32_t)ctrl; b->cur[(size_t)p] ^= ctrl & 1;
-            if (part >= 0) {
-                ++b->seq[(size_t)p];
-                if (j < part) { ++b->call[(size_t)p]; b->cur[(size_t)p] ^= 1; }
-            }
-            b->noise_pos[(size_t)p] += (uint32_t)plants;
-        }
-        if (le != hipSuccess) break;
-        const float* h_st = reinterpret_cast<const float*>(b->h_run + lay.states);
-        const float* h_ob = reinterpret_cast<const float*>(b->h_run + lay.obs);
-        const float* h_in = reinterpret_cast<const float*>(b->h_run + lay.inputs);
-        const float* h_co = reinterpret_cast<const float*>(b->h_run + lay.costs);
-        for (int j = 0; j < n; ++j) {
-            std::memcpy(states_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_st + (size_t)j * L * S, (size_t)L * S * sizeof(float));
-            std::memcpy(obs_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_ob + (size_t)j * L * S, (size_t)L * S * sizeof(float));
-            std::memcpy(inputs_out + (size_t)j * urow + (size_t)k0 * C, h_in + (size_t)j * L * C, (size_t)L * C * sizeof(float));
-            std::memcpy(costs_out + (size_t)j * n_steps + (size_t)k0, h_co + (size_t)j * L, (size_t)L * sizeof(float));
-            if (first_bad && first_bad[j] < 0)
-                for (int i = 0; i < L * C; ++i)
-                    if (!std::isfinite(h_in[(size_t)j * L * C + i])) { first_bad[j] = k0 + i / C; break; }
-        }
-        k0 += L;
-    }
-    if (le != hipSuccess)
-        return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_episodes: ") + hipGetErrorString(le) + " (the counters reflect the steps that were launched; the traces are not valid)");
-    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_episodes: a segment finished without publishing the last result of problem(s) " + late);
-    std::string timed_out;
-    for (int j = 0; j < n; ++j)
-        if (timed[(size_t)j]) timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(ids ? ids[j] : j);
-    if (!timed_out.empty())
-        return bfail(b, CTK_ERR_STATE, "ctk_batch_episodes: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
-                     "; such a step publishes NaN and the plant propagates it: their traces show where (first_bad), the other problems' traces are valid");
-    return CTK_OK;
+    return batch_closed_loop(b, LoopCall{"ctk_batch_episodes", "an episode", n_ids, ids, s0, y0, u_prev, n_steps, plant_substeps, states_out, obs_out,
+                                         inputs_out, costs_out, first_bad});
 }
 
 }  // extern "C"
@@ -3572,7 +3523,7 @@ int mlp_batch_have_weights(ctk_batch* b, const char* who, int n_ids, const int32
     std::string missing;
     for (int j = 0; j < n; ++j) {
         const int p = ids ? ids[j] : j;
-        if (!b->have_w[(size_t)p]) missing += (missing.empty() ? "" : ", ") + std::to_string(p);
+        if (!b->have_w[(size_t)p]) list_problem(missing, p);
     }
     if (!missing.empty())
         return bfail(b, CTK_ERR_STATE, std::string(who) + ": no network weights for problem(s) " + missing +
@@ -3939,7 +3890,7 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
         ++b->call[z];                                  // returns before it advances the Philox position or reads u (as RPGD; MPPI advances it regardless, by history)
         batch_read_u(b, p, j, u_out);
         volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;   // the hand-off's error word (MPPI and CEM; RPGD has none)
-        if (errw[0]) { errw[0] = 0; timed_out += (timed_out.empty() ? "" : ", ") + std::to_string(p); }
+        if (errw[0]) { errw[0] = 0; list_problem(timed_out, p); }
     }
     if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_cem_batch_step: ") + hipGetErrorString(le));
     if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_cem_batch_step: the step finished without publishing the result of problem(s) " + late);

@@ -324,6 +324,55 @@ def test_splits_segments_and_continuation_give_the_same_bits(env, monkeypatch):
         x.close()
 
 
+# ---- 6b. one batch, one run buffer, both layouts in turn ------------------------------------------------------------------------------------
+def same_bits(got, want, tag):
+    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32)), tag
+
+
+@pytest.mark.parametrize("env", ["CartPole", "Hover"])
+def test_mixed_calls_share_one_buffer(env, monkeypatch):
+    """run, episodes, plant_step, plant_step_noisy and run again on ONE batch, in segments of 2 steps: the grown-on-demand run buffer
+    serves the layout with and the layout without the noisy plant's parts in turn.  Against a twin stepped as the host loop, whose buffer
+    only ever holds single plant steps.  Host sequencing alone: bit for bit, no tolerance."""
+    monkeypatch.setenv("CTK_BATCH_RUN_SEGMENT_STEPS", "2")
+    a, b = make(env), make(env)                               # the switch is read at creation
+    la, lb = a.closed_loop, b.closed_loop
+    S0 = K.start_states(env, K.B)
+    # A: the device loops
+    st1, in1 = la.run(S0, 3)
+    ep = la.episodes(st1[:, -1], 3)
+    s3 = la.plant_step(ep.states[:, -1], ep.inputs[:, -1])
+    s4, y4, c4 = la.plant_step_noisy(s3, ep.inputs[:, -1], ep.inputs[:, -2])
+    st2, in2 = la.run(s4, 2)
+    # B: the same 8 controller steps and 2 single plant steps, every step a round trip
+    def run_loop(S, steps):
+        states, inputs = np.empty((K.B, steps + 1, b.S), np.float32), np.empty((K.B, steps, b.C), np.float32)
+        states[:, 0] = S
+        for k in range(steps):
+            inputs[:, k] = b.step(states[:, k])
+            states[:, k + 1] = lb.plant_step(states[:, k], inputs[:, k])
+        return states, inputs
+    wst1, win1 = run_loop(S0, 3)
+    wep = loop(b, wst1[:, -1], 3)
+    w3 = lb.plant_step(wep.states[:, -1], wep.inputs[:, -1])
+    w4, wy4, wc4 = lb.plant_step_noisy(w3, wep.inputs[:, -1], wep.inputs[:, -2])
+    wst2, win2 = run_loop(w4, 2)
+    tag = f"{env} mixed calls"
+    for name, got, want in (("first run's states", st1, wst1), ("first run's inputs", in1, win1), ("plant_step", s3, w3),
+                            ("plant_step_noisy's states", s4, w4), ("plant_step_noisy's observations", y4, wy4),
+                            ("plant_step_noisy's costs", c4, wc4), ("second run's states", st2, wst2), ("second run's inputs", in2, win2)):
+        same_bits(got, want, f"{tag}: {name}")
+    for name in Episodes._fields:
+        same_bits(getattr(ep, name), getattr(wep, name), f"{tag}: the episode's {name}")
+    assert not np.array_equal(ep.observations[2], ep.states[2])                # problem 2 has measurement noise
+    for q in range(K.B):
+        same_bits(a.get_state(q), b.get_state(q), f"{tag}: state vector of problem {q}")
+        assert a.rng_position(q) == b.rng_position(q) == 8, f"{tag}: Philox position of problem {q}"
+    assert positions(a) == positions(b) == [4] * K.B and 4 < E.MAX_POS, f"{tag}: noise positions"
+    a.close(); b.close()
+
+
 # ---- 7. the existing paths are blind to the noise -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("env", K.ENVS)
 def test_run_and_plant_step_ignore_the_noise(env):
