@@ -1,0 +1,1943 @@
+// ctk_batch.hip — the batch families of the C ABI (include/ctk_hip.h, ctk_hip_run.h, ctk_hip_episode.h): ctk_batch_*, ctk_mlp_batch_*,
+// ctk_cem_batch_*, ctk_rpgd_batch_*.  The single handle is in ctk_api.hip; what the two files share is declared in ctk_host.h.
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+
+#include "ctk_launch.h"
+#include "ctk_host.h"
+
+using namespace ctk_host;
+
+// =============================================================================================
+// The host core of the batch families (ctk_batch, ctk_cem_batch, ctk_rpgd_batch derive from it; ctk_mlp_batch holds a ctk_batch): what
+// every family keeps per batch and per problem, and the one copy of what they all do with it — the id checks, the owner of every device
+// and pinned allocation, the staging of host draws, the step records' common fields, the completion poll, the read-out of u, the
+// transfers of read / get_state / set_state, the parameter tables and the Philox positions.  Plain data and free functions, private to
+// this file (ctk_batch.hip): a family's own entry points pass their name (`who`) for the messages.
+// =============================================================================================
+namespace {
+
+struct BatchCore {
+    ctk_config cfg{};
+    int B = 0, N = 0, H = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0;
+    float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (*_batch_set_param / get_param)
+    std::vector<float> pparams;             // [B][CTK_MAX_PARAMS] every problem's own table
+    std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived (MPPI: and copied to d_k)
+    bool differ = false;                    // a *_problem_set_param has succeeded: the per-problem form of the kernel from now on
+    size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes of one problem's derived constants
+    hipStream_t stream = nullptr;
+    float* d_u = nullptr;                   // [B][CTK_MAX_INPUTS]
+    float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
+    float* h_u_dev = nullptr;
+    float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
+    float *d_J = nullptr, *d_Q = nullptr, *d_traj = nullptr;   // [B][N] | [B][N,H,C] | [B][N,H+1,S] (materialize_trajectories); RPGD has J alone
+    std::vector<void*> dev_owned, pin_owned;   // every device / pinned allocation of the batch, entered where it is made (batch_core_release)
+    std::vector<uint32_t> seq, call;        // [B] the sequence number of the problem's next step, its Philox position
+    std::string err, dominant;
+    bool mlp_names = false;                 // the MLP family: its messages carry its own entry points' names (bfail)
+    float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
+    float* slot(int p) const { return h_u + (size_t)p * 16; }
+    float* table(int p) { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
+    const float* table(int p) const { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
+    ~BatchCore();                           // batch_core_release: `delete` is every family's destroy and the end of a failed creation
+};
+
+// the MLP family runs the MPPI family's code; its messages carry its own entry points' names (ctk_batch_x -> ctk_mlp_batch_x,
+// ctk_problem_x -> ctk_mlp_problem_x), substituted here where a message is stored, so that the MPPI family's texts are the literals
+std::string mlp_family_names(std::string msg) {
+    for (const char* from : {"ctk_batch_", "ctk_problem_"}) {
+        const std::string to = std::string("ctk_mlp_") + (from + 4);
+        for (size_t at = msg.find(from); at != std::string::npos; at = msg.find(from, at + to.size())) msg.replace(at, std::strlen(from), to);
+    }
+    return msg;
+}
+int bfail(BatchCore* b, int code, const std::string& msg) {
+    if (b) b->err = b->mlp_names ? mlp_family_names(msg) : msg; else g_create_error = msg;
+    return code;
+}
+#define BHIP_TRY(b, expr)                                                                       \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess)                                                                   \
+            return bfail((b), CTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
+    } while (0)
+
+// the fields of the core that depend on the configuration alone (every family's create, after its refusals)
+void batch_core_init(BatchCore* b, const ctk_config* cfg, const EnvInfo* einfo, int n_problems) {
+    b->cfg = *cfg;
+    b->B = n_problems; b->N = cfg->num_rollouts; b->H = cfg->mpc_horizon;
+    b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = b->H * b->C;
+    default_params(b->env, b->params);
+    b->pparams.resize((size_t)n_problems * CTK_MAX_PARAMS);
+    for (int p = 0; p < n_problems; ++p) std::memcpy(b->table(p), b->params, sizeof(b->params));
+    b->dirty.assign((size_t)n_problems, 1);            // nothing derived yet: the per-problem form derives what it steps (MPPI: all of them)
+    b->kstride = ctk_mppi_batch_k_stride(b->env);
+    b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u);
+}
+
+// a diagnostic switch of the environment that only lowers a limit (values from 1 up to the limit)
+void batch_env_lowers(const char* name, int* limit) {
+    const char* e = std::getenv(name);
+    if (e && std::atoi(e) >= 1 && std::atoi(e) < *limit) *limit = std::atoi(e);
+}
+// the seed of problem p: the caller's, or consecutive ones from the configuration's
+uint64_t batch_seed(const ctk_config* cfg, const uint64_t* seeds, int p) { return seeds ? seeds[p] : cfg->seed + (uint64_t)p; }
+
+// ---- the owner: every allocation of a batch is entered in dev_owned / pin_owned where it is made; batch_core_release frees them ----
+// a zeroed device allocation of at least one byte (the memset on the batch's stream); a zeroed pinned allocation with the caller's flags
+template <class T>
+hipError_t batch_dev_zero(BatchCore* b, T** p, size_t bytes) {
+    const hipError_t e = hipMalloc((void**)p, bytes ? bytes : 1);
+    if (e == hipSuccess) b->dev_owned.push_back(*p);
+    return e != hipSuccess ? e : hipMemsetAsync(*p, 0, bytes ? bytes : 1, b->stream);
+}
+template <class T>
+hipError_t batch_pinned_zero(BatchCore* b, T** p, size_t bytes, unsigned flags = hipHostMallocDefault) {
+    const hipError_t e = hipHostMalloc((void**)p, bytes, flags);
+    if (e == hipSuccess) { b->pin_owned.push_back(*p); std::memset(*p, 0, bytes); }
+    return e;
+}
+// A buffer that grows on demand (d_samples; d_run / h_run) is freed and allocated where it grows, by the calls and in the order it always
+// was; the old pointer leaves the owner there and the new one is entered, so nothing is freed twice or kept twice.
+void batch_disown(std::vector<void*>& owned, void* p) { owned.erase(std::remove(owned.begin(), owned.end(), p), owned.end()); }
+
+// everything a batch owns on the device and in pinned memory; no HIP call for a batch that was refused before it opened anything
+void batch_core_release(BatchCore* b) {
+    if (!b->stream && b->dev_owned.empty() && b->pin_owned.empty()) return;
+    hipSetDevice(b->cfg.device);
+    if (b->stream) hipStreamSynchronize(b->stream);
+    for (void* p : b->dev_owned) hipFree(p);
+    for (void* p : b->pin_owned) hipHostFree(p);
+    if (b->stream) hipStreamDestroy(b->stream);
+}
+BatchCore::~BatchCore() { batch_core_release(this); }
+
+// a HIP call of a creation, from batch_core_open on: a failure stores a text that names the call, and the caller deletes the batch
+// (BatchMade: a batch under creation, deleted on every return but the one that hands it over)
+#define BHIP_CREATE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(_e); return CTK_ERR_HIP; } } while (0)
+template <class B>
+struct BatchMade { B* b = new B(); ~BatchMade() { delete b; } B* release() { B* r = b; b = nullptr; return r; } };
+
+// what every family's creation starts its device state with: the stream, u of every problem, the mapped result slots
+int batch_core_open(BatchCore* b) {
+    BHIP_CREATE(hipSetDevice(b->cfg.device));
+    BHIP_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_u, (size_t)b->B * CTK_MAX_INPUTS * sizeof(float)));
+    BHIP_CREATE(batch_pinned_zero(b, &b->h_u, (size_t)b->B * 64, hipHostMallocMapped | hipHostMallocCoherent));
+    BHIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
+    return CTK_OK;
+}
+
+// the problems a call addresses: ids[0..n) ascending without repeats, or all of them (ids == NULL)
+int batch_ids(BatchCore* b, const char* who, int n_ids, const int32_t* ids, int* n_out) {
+    if (!ids) { *n_out = b->B; return CTK_OK; }
+    if (n_ids < 1 || n_ids > b->B) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": n_ids must be 1 .. " + std::to_string(b->B) + " (the batch size)");
+    for (int j = 0; j < n_ids; ++j) {
+        if (ids[j] < 0 || ids[j] >= b->B)
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(ids[j]) + " is outside 0 .. " + std::to_string(b->B - 1));
+        if (j > 0 && ids[j] <= ids[j - 1]) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": ids must be strictly ascending");
+    }
+    *n_out = n_ids;
+    return CTK_OK;
+}
+int batch_problem(BatchCore* b, const char* who, int p) {
+    if (p < 0 || p >= b->B) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": problem index " + std::to_string(p) + " is outside 0 .. " + std::to_string(b->B - 1));
+    return CTK_OK;
+}
+
+// what every family's launches share of RolloutArgs (ctk_api.hip: make_args of a handle without what the step records and descriptors supply); P,
+// p_magic, interp and identity_interp are the family's
+RolloutArgs batch_common_args(const BatchCore* b) {
+    RolloutArgs a{};
+    for (int c = 0; c < b->C; ++c) { a.lo[c] = b->cfg.action_low[c]; a.hi[c] = b->cfg.action_high[c]; }
+    a.C = b->C;
+    a.N = b->N; a.H = b->H;
+    a.inv_Hp1 = 1.0f / (float)(b->H + 1);
+    a.stream_id = 0;
+    a.global_row0 = b->cfg.global_rollout_offset;
+    return a;
+}
+
+// host-supplied draws into the staging buffer (ctk_api.hip: resolve_samples of a handle): n floats
+int batch_stage(BatchCore* b, const float* src, size_t n) {
+    if (n > b->samples_cap) {
+        batch_disown(b->dev_owned, b->d_samples);
+        if (b->d_samples) BHIP_TRY(b, hipFree(b->d_samples));
+        b->d_samples = nullptr; b->samples_cap = 0;
+        BHIP_TRY(b, hipMalloc((void**)&b->d_samples, n * sizeof(float)));
+        b->dev_owned.push_back(b->d_samples);
+        b->samples_cap = n;
+    }
+    BHIP_TRY(b, hipMemcpyAsync(b->d_samples, src, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    return CTK_OK;
+}
+
+// row j of the call's states and previous inputs into a step record: they travel with the records
+template <class Rec>
+void batch_record_io(const BatchCore* b, Rec& q, int j, const float* s, const float* u_prev) {
+    q.dev_uprev = u_prev ? 0u : 1u;
+    for (int i = 0; i < b->S; ++i) q.s[i] = s[(size_t)j * b->S + i];
+    for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
+}
+
+// The step records of the CEM and RPGD steps to the device, n of `rec` bytes each.  In the per-problem form the constants of the n
+// problems lie right behind the n records, in the records' order, so that ONE transfer carries both (*d_ksteps: where they land, else
+// NULL).  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses (ctk_set_param ->
+// derive_constants / Env<>::derive at its launch); kcache is by problem id, the block behind the records by launch order.
+hipError_t batch_send_records(BatchCore* b, unsigned char* kcache, const int32_t* ids, int n, size_t rec, void* h_steps, void* d_steps,
+                              const unsigned char** d_ksteps) {
+    size_t bytes = (size_t)n * rec;
+    *d_ksteps = nullptr;
+    if (b->differ) {
+        unsigned char* h_k = static_cast<unsigned char*>(h_steps) + bytes;
+        for (int j = 0; j < n; ++j) {
+            const size_t z = (size_t)(ids ? ids[j] : j);
+            if (b->dirty[z]) {
+                ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, kcache + z * b->kstride);
+                b->dirty[z] = 0;
+            }
+            std::memcpy(h_k + (size_t)j * b->kstride, kcache + z * b->kstride, b->kstride);
+        }
+        *d_ksteps = static_cast<const unsigned char*>(d_steps) + bytes;
+        bytes += (size_t)n * b->kstride;
+    }
+    const hipError_t e = hipMemcpyAsync(d_steps, h_steps, bytes, hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess && b->differ)                  // nothing reached the device: derive and copy again at the next step
+        for (int j = 0; j < n; ++j) b->dirty[(size_t)(ids ? ids[j] : j)] = 1;
+    return e;
+}
+
+// problem p onto a message's list of problems ("3, 7, 12")
+void list_problem(std::string& list, int p) { list += (list.empty() ? "" : ", ") + std::to_string(p); }
+
+// completion of a step: the {u, seq} store of each of the first `launched` listed problems landing in its pinned slot (ctk_api.hip: finish_step's
+// bounded spin: one budget of pauses for the whole call, then one synchronise, then give up).  Returns the problems that never published.
+std::string batch_poll(BatchCore* b, const int32_t* ids, int launched) {
+    bool synced = false;
+    int spins = 0;
+    std::string late;
+    for (int j = 0; j < launched; ++j) {
+        const int p = ids ? ids[j] : j;
+        const uint32_t want = b->seq[(size_t)p];
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 1;
+        while (*slot != want) {
+            if (!synced && ++spins < 4000000) { __builtin_ia32_pause(); continue; }
+            if (!synced) { synced = true; if (hipStreamSynchronize(b->stream) != hipSuccess) break; continue; }
+            break;
+        }
+        if (*slot != want) list_problem(late, p);
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return late;
+}
+
+// u of problem p from its slot into row j of u_out (publish_u_vec: u[0] beside seq, the other inputs behind the error words)
+void batch_read_u(const BatchCore* b, int p, int j, float* u_out) {
+    if (!u_out) return;
+    volatile float* sl = reinterpret_cast<volatile float*>(b->slot(p));
+    u_out[(size_t)j * b->C] = sl[0];
+    for (int c = 1; c < b->C; ++c) u_out[(size_t)j * b->C + c] = sl[4 + c];
+}
+
+// ---- the parameter tables and Philox positions: the bodies of every family's *_set_param ... *_rng_set_position ----
+int batch_param_id(BatchCore* b, const char* who, int id) {
+    if (id < 0 || id >= env_info(b->env)->n_params) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown parameter id for this environment");
+    return CTK_OK;
+}
+int batch_set_param(BatchCore* b, const char* who, int id, float value) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_param_id(b, who, id)) return rc;
+    b->params[id] = value;                             // the shared table: the shared form derives its constants from it at each launch
+    for (int p = 0; p < b->B; ++p) { b->table(p)[id] = value; b->dirty[(size_t)p] = 1; }   // column id of every problem; the other ids stay
+    return CTK_OK;
+}
+int batch_get_param(const BatchCore* b, int id, float* value) {
+    if (!b || !value || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->params[id];
+    return CTK_OK;
+}
+// *flipped: this call turned `differ` on, the family names its per-problem kernel in `dominant`
+int batch_problem_set_param(BatchCore* b, const char* who, int n_ids, const int32_t* ids, int id, const float* values, bool* flipped) {
+    *flipped = false;
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (int rc = batch_param_id(b, who, id)) return rc;
+    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL values (one value per listed problem)");
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        b->table(p)[id] = values[j];
+        b->dirty[(size_t)p] = 1;                       // derived at a later step (MPPI: the next one, CEM and RPGD: the problem's next one)
+    }
+    *flipped = !b->differ;
+    b->differ = true;                                  // sticky: the tables are never compared again
+    return CTK_OK;
+}
+int batch_problem_get_param(const BatchCore* b, int problem, int id, float* value) {
+    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    *value = b->table(problem)[id];
+    return CTK_OK;
+}
+int batch_params_differ(const BatchCore* b) { return b && b->differ ? 1 : 0; }
+int batch_rng_get_position(const BatchCore* b, int problem, uint32_t* call) {
+    if (!b || !call || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *call = b->call[(size_t)problem];
+    return CTK_OK;
+}
+int batch_rng_set_position(BatchCore* b, const char* who, int problem, uint32_t call) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, who, problem)) return rc;
+    b->call[(size_t)problem] = call;
+    return CTK_OK;
+}
+
+// ---- the transfers of every family's *_get_state / *_set_state and *_read ----
+// A problem's state as a family describes it: segments on the device in the order of the state's layout, then its host-side counters,
+// one float each.  `mark`: a flag that set_state raises (RPGD: the problem counts as reset).
+struct StateSeg { float* dev; size_t n; };
+struct BatchState { std::vector<StateSeg> segs; std::vector<int*> counters; unsigned char* mark = nullptr; };
+
+// get (device to host) or set (host to device) of a problem's state through host[n]: the checks, the copies in the list's order, ONE
+// synchronisation; set writes the counters ahead of it, get reads them behind it.  name_size: the size messages name the size (RPGD's do)
+template <class B>
+int batch_state_io(B* b, const char* who, int problem, float* host, size_t n, bool get, bool name_size, BatchState (*describe)(B*, int)) {
+    if (!b || !host) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, who, problem)) return rc;
+    const BatchState st = describe(b, problem);
+    size_t size = st.counters.size();
+    for (const StateSeg& g : st.segs) size += g.n;
+    if (get ? n < size : n != size)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + (get ? ": destination too small" : ": wrong state size") +
+                     (name_size ? " (" + std::to_string(size) + " floats)" : std::string()));
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    float* at = host;
+    for (const StateSeg& g : st.segs) {
+        BHIP_TRY(b, hipMemcpyAsync(get ? at : g.dev, get ? g.dev : at, g.n * sizeof(float), get ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, b->stream));
+        at += g.n;
+    }
+    for (size_t i = 0; !get && i < st.counters.size(); ++i) *st.counters[i] = (int)at[i];
+    if (!get && st.mark) *st.mark = 1;
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    for (size_t i = 0; get && i < st.counters.size(); ++i) at[i] = (float)*st.counters[i];
+    return CTK_OK;
+}
+
+// what every *_read checks before the family resolves the buffer
+int batch_read_check(BatchCore* b, const char* who, int problem, const float* dst) {
+    if (!b || !dst) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL destination") : CTK_ERR_INVALID_ARGUMENT;
+    return batch_problem(b, who, problem);
+}
+// the Q / J / TRAJ cases of the MPPI and CEM families' reads; *src stays NULL for every other buffer
+int batch_locate_rollouts(BatchCore* b, const char* who, int problem, int buffer, const float** src, size_t* n) {
+    const size_t z = (size_t)problem, N = (size_t)b->N;
+    switch (buffer) {
+        case CTK_BUF_Q: *src = b->d_Q + z * N * b->HC; *n = N * b->HC; break;
+        case CTK_BUF_J: *src = b->d_J + z * N; *n = N; break;
+        case CTK_BUF_TRAJ:
+            if (!b->d_traj) return bfail(b, CTK_ERR_STATE, std::string(who) + ": trajectories not materialised (cfg.materialize_trajectories == 0)");
+            *n = N * ((size_t)b->H + 1) * b->S; *src = b->d_traj + z * *n; break;
+        default: break;
+    }
+    return CTK_OK;
+}
+// the n floats (is_int: 32-bit indices, converted) at src into dst[cap]; `before_copy` runs between hipSetDevice and the copy
+int batch_read_out(BatchCore* b, const char* who, const float* src, size_t n, bool is_int, float* dst, size_t cap,
+                   const std::function<int()>& before_copy = nullptr) {
+    if (cap < n) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": destination too small (" + std::to_string(n) + " floats)");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    if (before_copy) if (int rc = before_copy()) return rc;
+    BHIP_TRY(b, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (is_int) for (size_t i = 0; i < n; ++i) { int v; std::memcpy(&v, &dst[i], 4); dst[i] = (float)v; }
+    return CTK_OK;
+}
+
+}  // namespace
+
+// =============================================================================================
+// Batched MPPI (include/ctk_hip.h: ctk_batch_*): B independent problems of one configuration, stepped by ONE launch of
+// ctk_mppi_batch<ENV, LOG> per step (ctk_mppi.hip).  One allocation per buffer kind with a problem stride — no handles inside.
+// Per-problem host state is what a handle keeps: the sequence number of its next step, its Philox position, which u_nom buffer is current,
+// its parameter table.  While no ctk_problem_set_param has succeeded the launches take the constants of the shared table by value; from
+// then on (`differ`, sticky) they read every problem's constants from d_k, which ctk_batch_step refreshes for the problems marked dirty.
+// =============================================================================================
+struct ctk_batch : BatchCore {
+    int P = 0, PC = 0, blocks = 0;
+    unsigned char* h_k = nullptr;           // pinned [B][kstride] derived constants, the staging of the copy to d_k
+    unsigned char* d_k = nullptr;           // [B][kstride]
+    MppiK mk{};
+    int max_per_launch = 1;                 // problems per launch: half the device's CUs (ctk_batch_create), a diagnostic switch may lower it
+    InterpEntry* d_interp = nullptr;
+    float* d_parts = nullptr;               // [B][blocks][2+PC]
+    unsigned long long* d_ll = nullptr;     // [B][blocks][2+PC] {value, seq} words
+    float* d_unom = nullptr;                // [B][2][H,C]
+    CtkBatchDesc* d_desc = nullptr;         // [B]
+    CtkBatchStep* h_steps = nullptr;        // pinned [B]: the step records of the step being issued
+    CtkBatchStep* d_steps = nullptr;        // [B]
+    std::vector<int> cur;
+    // the MLP family (include/ctk_hip.h: ctk_mlp_batch_*): the same struct with a predictor field and per-problem weight tables
+    int pred = CTK_PRED_ODE;                // CTK_PRED_MLP: ctk_mppi_batch_mlp<LOG> / ctk_mppi_batch_mlp_pp<LOG>
+    int hid1 = 32, hid2 = 32;               // the network's hidden widths (cfg.predictor_hidden1/2, 0 = 32): narrower ones are embedded
+    size_t wtab = 0;                        // floats of one per-lane weight table (ctk_mppi_batch_mlp_table_floats)
+    float* d_w = nullptr;                   // [B][wtab] problem p's table, in the layout of a handle's d_wperm
+    float* h_w = nullptr;                   // pinned [B][wtab]: the staging of ONE transfer per weight call
+    std::vector<unsigned char> have_w;      // [B] the problem has received weights
+    // the closed loop on the device (ctk_batch_run / ctk_batch_plant_step; kernel ctk_batch_plant<ENV>, ctk_plant.hip).  Problem p's PLANT
+    // has, for parameter id, the override if one was set (ctk_batch_plant_set_param), else the problem's own controller value table(p)[id]
+    std::vector<float> plant_over;          // [B][CTK_MAX_PARAMS] the overrides
+    std::vector<unsigned char> plant_has;   // [B][CTK_MAX_PARAMS] an override was set
+    std::vector<float> plant_tab;           // [B][CTK_MAX_PARAMS] the effective table the constants in h_kplant were derived from
+    std::vector<int> plant_sub;             // [B] ... and their Euler sub-step count (0: nothing derived yet)
+    unsigned char* h_kplant = nullptr;      // pinned [B][kstride] the plants' derived constants, the staging of the copy to d_kplant
+    unsigned char* d_kplant = nullptr;      // [B][kstride]
+    unsigned char* h_run = nullptr;         // pinned: the step records, plant operands and traces of one segment or plant step (LoopLayout)
+    unsigned char* d_run = nullptr;         // the same on the device; both grow on demand (batch_run_buffers)
+    size_t run_cap = 0;
+    int run_segment = 256;                  // steps per segment of a run: a diagnostic switch may lower it (ctk_batch_create)
+    // the stochastic plant (include/ctk_hip_episode.h: ctk_batch_episodes / ctk_batch_plant_step_noisy; kernel ctk_batch_plant_noisy<ENV>)
+    std::vector<float> noise_sigma;         // [B][2][CTK_MAX_STATES] process | measurement standard deviations (0: none)
+    std::vector<uint64_t> noise_seed;       // [B] Philox key of the problem's noise (at creation: its controller seed)
+    std::vector<uint32_t> noise_pos;        // [B] noise position: one per transition of the noisy plant
+    size_t unom_stride() const { return (size_t)2 * HC; }
+    float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
+};
+
+namespace {
+
+// the shared template of a launch's RolloutArgs (ctk_api.hip: make_args without what the step records and descriptors supply)
+RolloutArgs batch_args(const ctk_batch* b) {
+    RolloutArgs a = batch_common_args(b);
+    a.P = b->P;
+    a.p_magic = ctk_magic_of(b->P);
+    a.identity_interp = (b->cfg.period_interpolation_inducing_points == 1 && b->P == b->H) ? 1 : 0;
+    a.interp = b->d_interp;
+    return a;
+}
+
+// The per-problem form's constants: re-derive those of every dirty problem (stepped now or not) with the function a handle uses
+// (ctk_set_param -> derive_constants / Env<>::derive at its launch), and copy the span from the first to the last dirty problem in ONE
+// transfer on the batch's stream; no transfer when nothing is dirty.  h_k mirrors d_k, so what lies between two dirty problems is current.
+// The caller synchronises before it returns (ctk_batch_step), so the staging is free again at the next call.
+hipError_t batch_flush_constants(ctk_batch* b) {
+    int lo = b->B, hi = -1;
+    for (int p = 0; p < b->B; ++p) {
+        if (!b->dirty[(size_t)p]) continue;
+        ctk_mppi_batch_derive_k(b->env, b->table(p), b->cfg.dt, b->cfg.intermediate_steps, b->h_k + (size_t)p * b->kstride);
+        b->dirty[(size_t)p] = 0;
+        lo = std::min(lo, p); hi = p;
+    }
+    if (hi < 0) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(b->d_k + (size_t)lo * b->kstride, b->h_k + (size_t)lo * b->kstride, (size_t)(hi - lo + 1) * b->kstride,
+                                        hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess) for (int p = lo; p <= hi; ++p) b->dirty[(size_t)p] = 1;       // nothing reached the device: derive and copy again
+    return e;
+}
+
+// The controller launches of n step records from steps_dev on (ctk_batch_step; every step of ctk_batch_run): consecutive launches of at
+// most max_per_launch problems — the results do not depend on the split.  *launched: the records that were launched.
+hipError_t batch_launch_records(ctk_batch* b, const RolloutArgs& a, const CtkBatchStep* steps_dev, int n, int* launched) {
+    const bool log = b->cfg.materialize_trajectories != 0;
+    hipError_t le = hipSuccess;
+    *launched = 0;
+    while (le == hipSuccess && *launched < n) {
+        const int cnt = std::min(b->max_per_launch, n - *launched);
+        if (b->pred == CTK_PRED_MLP)
+            le = ctk_launch_mppi_batch_mlp(b->stream, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
+                                           b->d_w, b->differ ? b->d_k : nullptr);
+        else
+            le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
+                                       b->differ ? b->d_k : nullptr);
+        if (le == hipSuccess) *launched += cnt;
+    }
+    return le;
+}
+
+// optimizer_reset() of problem p (ctk_reset of an MPPI handle): the plan at mid-range in buffer 0; u, the Philox position stay
+int batch_reset_one(ctk_batch* b, int p) {
+    std::vector<float> tmp((size_t)b->HC);
+    for (int i = 0; i < b->HC; ++i) tmp[(size_t)i] = 0.5f * (b->cfg.action_low[i % b->C] + b->cfg.action_high[i % b->C]);
+    b->cur[(size_t)p] = 0;
+    BHIP_TRY(b, hipMemcpyAsync(b->unom(p, 0), tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+// ---- the closed loop on the device: the plants' constants and the run buffer (ctk_batch_run / ctk_batch_plant_step) ----
+
+// The plants' constants ahead of a run or a plant step: problem p's effective table (override, else its own controller value) and the
+// sub-step count against what h_kplant was derived from; those that changed are re-derived with the function the controller's
+// constants come from, and the span from the first to the last of them travels in ONE transfer on the batch's stream (none when
+// nothing changed).  The caller synchronises before it returns, so the staging is free again at the next call.
+hipError_t batch_plant_flush(ctk_batch* b, int substeps) {
+    int lo = b->B, hi = -1;
+    float eff[CTK_MAX_PARAMS];
+    for (int p = 0; p < b->B; ++p) {
+        const size_t z = (size_t)p * CTK_MAX_PARAMS;
+        for (int i = 0; i < CTK_MAX_PARAMS; ++i) eff[i] = b->plant_has[z + i] ? b->plant_over[z + i] : b->table(p)[i];
+        if (b->plant_sub[(size_t)p] == substeps && std::memcmp(eff, &b->plant_tab[z], sizeof(eff)) == 0) continue;
+        ctk_mppi_batch_derive_k(b->env, eff, b->cfg.dt, substeps, b->h_kplant + (size_t)p * b->kstride);
+        std::memcpy(&b->plant_tab[z], eff, sizeof(eff));
+        b->plant_sub[(size_t)p] = substeps;
+        lo = std::min(lo, p); hi = p;
+    }
+    if (hi < 0) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(b->d_kplant + (size_t)lo * b->kstride, b->h_kplant + (size_t)lo * b->kstride, (size_t)(hi - lo + 1) * b->kstride,
+                                        hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess) for (int p = lo; p <= hi; ++p) b->plant_sub[(size_t)p] = 0;      // nothing reached the device: derive and copy again
+    return e;
+}
+
+// Where the parts of the run buffer lie for a segment of n problems and L steps (bytes from its start; every part 16-aligned).  What
+// travels to the device in ONE transfer lies in front (up to `states`), what comes back in ONE copy behind it:
+//   step records [L][n] | inputs of a plant step [n][C] | true start states [n][S] | previous inputs of the first step [n][C] |
+//   noise records [n] || state trace [n][L][S] | observation trace [n][L][S] | input trace [n][L][C] | realised costs [n][L]
+// The parts only the noisy plant has (s_start, u_start, noise, obs, costs) are empty without it (ctk_batch_run / ctk_batch_plant_step):
+// what then remains is  step records | inputs of a plant step || state trace | input trace.
+struct LoopLayout {
+    size_t u_in, s_start, u_start, noise, states, obs, inputs, costs, total;
+    LoopLayout(const ctk_batch* b, int n, int L, bool noisy) {
+        auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        auto ep = [&](size_t x) { return noisy ? x : 0; };
+        u_in = (size_t)L * n * sizeof(CtkBatchStep);
+        s_start = u_in + up((size_t)n * b->C * sizeof(float));
+        u_start = s_start + ep(up((size_t)n * b->S * sizeof(float)));
+        noise = u_start + ep(up((size_t)n * b->C * sizeof(float)));
+        states = noise + ep((size_t)n * sizeof(CtkPlantNoise));
+        obs = states + up((size_t)n * L * b->S * sizeof(float));
+        inputs = obs + ep(up((size_t)n * L * b->S * sizeof(float)));
+        costs = inputs + up((size_t)n * L * b->C * sizeof(float));
+        total = costs + ep(up((size_t)n * L * sizeof(float)));
+    }
+};
+static_assert(sizeof(CtkBatchStep) % 16 == 0, "the parts of the run buffer lie behind the step records, 16-aligned");
+static_assert(sizeof(CtkPlantNoise) % 16 == 0, "the traces lie behind the noise records, 16-aligned");
+
+// the run buffer (device and pinned), grown to the layout's bytes on demand
+int batch_run_buffers(ctk_batch* b, const LoopLayout& lay) {
+    if (lay.total <= b->run_cap) return CTK_OK;
+    batch_disown(b->dev_owned, b->d_run);
+    if (b->d_run) BHIP_TRY(b, hipFree(b->d_run));
+    b->d_run = nullptr; b->run_cap = 0;
+    batch_disown(b->pin_owned, b->h_run);
+    if (b->h_run) BHIP_TRY(b, hipHostFree(b->h_run));
+    b->h_run = nullptr;
+    BHIP_TRY(b, hipMalloc((void**)&b->d_run, lay.total));
+    b->dev_owned.push_back(b->d_run);
+    BHIP_TRY(b, hipHostMalloc((void**)&b->h_run, lay.total, hipHostMallocDefault));
+    b->pin_owned.push_back(b->h_run);
+    b->run_cap = lay.total;
+    return CTK_OK;
+}
+
+// problem p's noise record at its current position
+void batch_noise_record(const ctk_batch* b, int p, CtkPlantNoise* q) {
+    const float* sg = &b->noise_sigma[(size_t)p * 2 * CTK_MAX_STATES];
+    q->any = 0u;
+    for (int i = 0; i < CTK_MAX_STATES; ++i) {
+        q->sigma_w[i] = i < b->S ? sg[i] : 0.0f;
+        q->sigma_v[i] = i < b->S ? sg[CTK_MAX_STATES + i] : 0.0f;
+        if (q->sigma_w[i] != 0.0f || q->sigma_v[i] != 0.0f) q->any = 1u;
+    }
+    q->seed_lo = (uint32_t)(b->noise_seed[(size_t)p] & 0xFFFFFFFFull); q->seed_hi = (uint32_t)(b->noise_seed[(size_t)p] >> 32);
+    q->pos = b->noise_pos[(size_t)p];
+}
+
+int batch_substeps(ctk_batch* b, const char* who, int substeps, int* out) {
+    if (substeps < 0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": the plant's sub-step count must be >= 1, or 0 for cfg.intermediate_steps (" + std::to_string(substeps) + ")");
+    *out = substeps ? substeps : b->cfg.intermediate_steps;
+    return CTK_OK;
+}
+
+// what a step record says of the step that problem p takes t steps from now (ctk_batch_step: t == 0; a segment of the closed loop: t in
+// [0, L)): its counters, and no draws.  The state and the previous input are the caller's.
+void batch_fill_record(const ctk_batch* b, CtkBatchStep& q, int p, int t) {
+    q.id = p; q.seq = b->seq[(size_t)p] + (uint32_t)t; q.call = b->call[(size_t)p] + (uint32_t)t;
+    q.cur = (uint32_t)(b->cur[(size_t)p] ^ (t & 1));
+    q.pad = 0u; q.samples = nullptr;
+}
+
+// One plant step of the listed problems (ctk_batch_plant_step; with y_next, ctk_batch_plant_step_noisy): the records, the inputs and
+// what the noisy plant reads besides travel in ONE transfer, one launch, one copy back, one synchronisation.
+int batch_plant_step(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev,
+                     int substeps, float* s_next, float* y_next, float* cost) {
+    const bool noisy = y_next != nullptr;
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (int rc = batch_substeps(b, who, substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const LoopLayout lay(b, n, 1, noisy);
+    if (int rc = batch_run_buffers(b, lay)) return rc;
+    // the records carry the problem and, for the plain plant, its state; the noisy plant reads the state from a row of its own
+    CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
+    CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
+    for (int j = 0; j < n; ++j) {
+        std::memset(&rec[j], 0, sizeof(CtkBatchStep));
+        rec[j].id = ids ? ids[j] : j;
+        if (noisy) batch_noise_record(b, rec[j].id, &nz[j]);
+        else for (int i = 0; i < S; ++i) rec[j].s[i] = s[(size_t)j * S + i];
+    }
+    std::memcpy(b->h_run + lay.u_in, u, (size_t)n * C * sizeof(float));
+    if (noisy) {
+        std::memcpy(b->h_run + lay.s_start, s, (size_t)n * S * sizeof(float));
+        std::memcpy(b->h_run + lay.u_start, u_prev, (size_t)n * C * sizeof(float));
+    }
+    const CtkBatchStep* d_rec = reinterpret_cast<const CtkBatchStep*>(b->d_run);
+    auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+    const size_t back = noisy ? lay.total - lay.states : (size_t)n * S * sizeof(float);      // the plain plant wrote the next states alone
+    hipError_t le = batch_plant_flush(b, sub);
+    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
+    bool launched = false;
+    if (le == hipSuccess) {
+        if (noisy)
+            le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec, nullptr, b->d_kplant,
+                                              reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise), dev(lay.u_in), dev(lay.s_start), (size_t)S,
+                                              dev(lay.u_start), (size_t)C, 0u, dev(lay.states), dev(lay.obs), nullptr, dev(lay.costs), n, (size_t)S, 0, 1);
+        else
+            le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec, nullptr, b->d_kplant, dev(lay.u_in), dev(lay.states), nullptr, n,
+                                        (size_t)S, 0);
+        launched = le == hipSuccess;
+    }
+    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, back, hipMemcpyDeviceToHost, b->stream);
+    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
+    if (le == hipSuccess) le = se;
+    if (noisy && launched)
+        for (int j = 0; j < n; ++j) ++b->noise_pos[(size_t)rec[j].id];         // by the plant launch that was issued
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string(who) + ": " + hipGetErrorString(le));
+    std::memcpy(s_next, b->h_run + lay.states, (size_t)n * S * sizeof(float));
+    if (noisy) {
+        std::memcpy(y_next, b->h_run + lay.obs, (size_t)n * S * sizeof(float));
+        std::memcpy(cost, b->h_run + lay.costs, (size_t)n * sizeof(float));
+    }
+    return CTK_OK;
+}
+
+// The counters after a segment of L steps whose launches ended with `le`.  `ctrl` steps had the controllers of all n listed problems
+// launched; if the launches of the step after them failed (part >= 0), those of its first `part` problems were; `plants` launches of
+// the noisy plant were issued (a run: 0).  seq, call, cur and noise_pos are left as if exactly these had run, by the rule of
+// ctk_batch_step: a listed problem consumes its sequence number launched or not, its Philox position and plan buffer only if launched.
+// Only where nothing failed, a problem whose slot does not show the segment's last step is listed in `late`; the hand-off's error word
+// is read and cleared into timed[j] whatever happened.
+void batch_loop_account(ctk_batch* b, int n, const int32_t* ids, hipError_t le, int L, int ctrl, int part, int plants, std::string& late,
+                        std::vector<unsigned char>& timed) {
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
+        if (le == hipSuccess && slot[1] != b->seq[(size_t)p] + (uint32_t)(L - 1)) list_problem(late, p);
+        if (slot[2]) { slot[2] = 0; timed[(size_t)j] = 1; }                   // the hand-off's error word, read and cleared
+        b->seq[(size_t)p] += (uint32_t)ctrl; b->call[(size_t)p] += (uint32_t)ctrl; b->cur[(size_t)p] ^= ctrl & 1;
+        if (part >= 0) {
+            ++b->seq[(size_t)p];
+            if (j < part) { ++b->call[(size_t)p]; b->cur[(size_t)p] ^= 1; }
+        }
+        b->noise_pos[(size_t)p] += (uint32_t)plants;
+    }
+}
+
+// a closed-loop call: ctk_batch_run, or with obs_out (and costs_out) ctk_batch_episodes
+struct LoopCall {
+    const char* who;                        // the entry point, for the messages
+    const char* noun;                       // "a run" / "an episode"
+    int n_ids; const int32_t* ids;
+    const float *s0, *y0, *u_prev;
+    int n_steps, plant_substeps;
+    float *states_out, *obs_out, *inputs_out, *costs_out;
+    int32_t* first_bad;
+};
+
+// The closed loop on the device, in segments of at most run_segment steps.  A segment is ONE transfer of its step records (and what the
+// noisy plant reads at its first step), per step the controller launches and one plant launch, ONE copy of the traces back and ONE
+// synchronisation; the plant launch of step t writes the state (the noisy plant: the observation) into the records of step t + 1 on the
+// device.  The noisy plant differs in where it reads from (the true state and the previous input have rows of their own, see
+// ctk_plant.hip), in its noise positions and in the two further traces.
+int batch_closed_loop(ctk_batch* b, const LoopCall& c) {
+    const bool noisy = c.obs_out != nullptr;
+    const int32_t* ids = c.ids;
+    const float* u_prev = c.u_prev;
+    const int n_steps = c.n_steps;
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, c.who, c.n_ids, ids, &n)) return rc;
+    if (n_steps < 1)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(c.who) + ": " + c.noun + " has at least one step (n_steps == " + std::to_string(n_steps) + ")");
+    if (int rc = batch_substeps(b, c.who, c.plant_substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const size_t srow = ((size_t)n_steps + 1) * S, urow = (size_t)n_steps * C;       // one problem's rows of the traces
+    for (int j = 0; j < n; ++j) {
+        std::memcpy(c.states_out + (size_t)j * srow, c.s0 + (size_t)j * S, (size_t)S * sizeof(float));
+        if (noisy) std::memcpy(c.obs_out + (size_t)j * srow, (c.y0 ? c.y0 : c.s0) + (size_t)j * S, (size_t)S * sizeof(float));
+        if (c.first_bad) c.first_bad[j] = -1;
+    }
+    // The noisy plant without u_prev: the first step's previous input is what the first controller launch reads as its own — the problem's
+    // last output in d_u (ctk_batch_set_state writes it too, the pinned result slot only holds what a step published).  That launch
+    // overwrites it, so the span of the listed problems is read here, once per call, ahead of everything else.  A run has no use for it.
+    const int p_lo = ids ? ids[0] : 0, p_hi = ids ? ids[n - 1] : n - 1;
+    std::vector<float> own_u;
+    if (noisy && !u_prev) {
+        own_u.resize((size_t)(p_hi - p_lo + 1) * CTK_MAX_INPUTS);
+        BHIP_TRY(b, hipMemcpyAsync(own_u.data(), b->d_u + (size_t)p_lo * CTK_MAX_INPUTS, own_u.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+        BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    }
+    const float* first_s = noisy ? c.obs_out : c.states_out;                   // what the controllers see: of a run the state itself
+    std::vector<unsigned char> timed((size_t)n, 0);
+    std::string late;
+    const RolloutArgs a = batch_args(b);
+    hipError_t le = batch_plant_flush(b, sub);
+    for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
+        const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
+        const LoopLayout lay(b, n, L, noisy);
+        if (int rc = batch_run_buffers(b, lay)) { hipStreamSynchronize(b->stream); return rc; }
+        // every record of the segment: all but the state is known in advance.  The state of the segment's first step is the host's (the
+        // start state or observation, or the previous segment's last one from the copied trace); the later ones the plant launches write
+        // on the device.
+        CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
+        for (int t = 0; t < L; ++t) {
+            const bool given = k0 + t == 0 && u_prev;                          // from the second step on: the problem's own last output
+            for (int j = 0; j < n; ++j) {
+                CtkBatchStep& q = rec[(size_t)t * n + j];
+                batch_fill_record(b, q, ids ? ids[j] : j, t);
+                q.dev_uprev = given ? 0u : 1u;
+                for (int i = 0; i < CTK_MAX_STATES; ++i) q.s[i] = (t == 0 && i < S) ? first_s[(size_t)j * srow + (size_t)k0 * S + i] : 0.0f;
+                for (int i = 0; i < CTK_MAX_INPUTS; ++i) q.u_prev[i] = (given && i < C) ? u_prev[(size_t)j * C + i] : 0.0f;
+            }
+        }
+        // what the first noisy plant launch of the segment reads in place of trace rows: the true state, and the input before the
+        // segment's first one — the given u_prev, the previous segment's last input, or the problem's own last output (read above)
+        if (noisy) {
+            float* h_s = reinterpret_cast<float*>(b->h_run + lay.s_start);
+            float* h_up = reinterpret_cast<float*>(b->h_run + lay.u_start);
+            CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
+            for (int j = 0; j < n; ++j) {
+                const int p = ids ? ids[j] : j;
+                std::memcpy(h_s + (size_t)j * S, c.states_out + (size_t)j * srow + (size_t)k0 * S, (size_t)S * sizeof(float));
+                if (k0 > 0) std::memcpy(h_up + (size_t)j * C, c.inputs_out + (size_t)j * urow + ((size_t)k0 - 1) * C, (size_t)C * sizeof(float));
+                else if (u_prev) std::memcpy(h_up + (size_t)j * C, u_prev + (size_t)j * C, (size_t)C * sizeof(float));
+                else std::memcpy(h_up + (size_t)j * C, &own_u[(size_t)(p - p_lo) * CTK_MAX_INPUTS], (size_t)C * sizeof(float));
+                batch_noise_record(b, p, &nz[j]);
+            }
+        }
+        CtkBatchStep* d_rec = reinterpret_cast<CtkBatchStep*>(b->d_run);
+        auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+        const CtkPlantNoise* d_nz = reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise);
+        float *d_st = dev(lay.states), *d_ob = dev(lay.obs), *d_in = dev(lay.inputs), *d_co = dev(lay.costs);
+        if (b->differ) le = batch_flush_constants(b);                          // the constants' transfer goes ahead of the step records'
+        if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, noisy ? lay.states : lay.u_in, hipMemcpyHostToDevice, b->stream);
+        int ctrl = 0, part = -1, plants = 0;           // steps whose controllers were all launched; of the step whose launches failed, how
+                                                       // many were; the noisy plant launches that were issued
+        for (int t = 0; le == hipSuccess && t < L; ++t) {
+            int launched = 0;
+            le = batch_launch_records(b, a, d_rec + (size_t)t * n, n, &launched);
+            if (le != hipSuccess) { part = launched; break; }
+            ++ctrl;
+            CtkBatchStep* next = t + 1 < L ? d_rec + (size_t)(t + 1) * n : nullptr;
+            if (noisy) {
+                le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, next, b->d_kplant, d_nz, nullptr,
+                                                  t ? d_st + (size_t)(t - 1) * S : dev(lay.s_start), t ? (size_t)L * S : (size_t)S,
+                                                  t ? d_in + (size_t)(t - 1) * C : dev(lay.u_start), t ? (size_t)L * C : (size_t)C, (uint32_t)t,
+                                                  d_st + (size_t)t * S, d_ob + (size_t)t * S, d_in + (size_t)t * C, d_co + t, n, (size_t)L * S, (size_t)L * C,
+                                                  (size_t)L);
+                if (le == hipSuccess) ++plants;
+            } else {
+                le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, next, b->d_kplant, nullptr, d_st + (size_t)t * S,
+                                            d_in + (size_t)t * C, n, (size_t)L * S, (size_t)L * C);
+            }
+        }
+        if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
+        const hipError_t se = hipStreamSynchronize(b->stream);                 // ONE synchronisation per segment, whatever happened
+        if (le == hipSuccess) le = se;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        batch_loop_account(b, n, ids, le, L, ctrl, part, plants, late, timed);  // the counters reflect what was launched
+        if (le != hipSuccess) break;
+        auto host = [&](size_t at) { return reinterpret_cast<const float*>(b->h_run + at); };
+        const float *h_st = host(lay.states), *h_ob = host(lay.obs), *h_in = host(lay.inputs), *h_co = host(lay.costs);
+        for (int j = 0; j < n; ++j) {
+            std::memcpy(c.states_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_st + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+            std::memcpy(c.inputs_out + (size_t)j * urow + (size_t)k0 * C, h_in + (size_t)j * L * C, (size_t)L * C * sizeof(float));
+            if (noisy) {
+                std::memcpy(c.obs_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_ob + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+                std::memcpy(c.costs_out + (size_t)j * n_steps + (size_t)k0, h_co + (size_t)j * L, (size_t)L * sizeof(float));
+            }
+            if (c.first_bad && c.first_bad[j] < 0)
+                for (int i = 0; i < L * C; ++i)
+                    if (!std::isfinite(h_in[(size_t)j * L * C + i])) { c.first_bad[j] = k0 + i / C; break; }
+        }
+        k0 += L;
+    }
+    if (le != hipSuccess)
+        return bfail(b, CTK_ERR_HIP, std::string(c.who) + ": " + hipGetErrorString(le) + " (the counters reflect the steps that were launched; the traces are not valid)");
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, std::string(c.who) + ": a segment finished without publishing the last result of problem(s) " + late);
+    std::string timed_out;
+    for (int j = 0; j < n; ++j)
+        if (timed[(size_t)j]) list_problem(timed_out, ids ? ids[j] : j);
+    if (!timed_out.empty())
+        return bfail(b, CTK_ERR_STATE, std::string(c.who) + ": in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; such a step publishes NaN and the plant propagates it: their traces show where (first_bad), the other problems' traces are valid");
+    return CTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* ctk_batch_last_error(const ctk_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+int ctk_batch_size(const ctk_batch* b) { return b ? b->B : 0; }
+size_t ctk_batch_samples_needed(const ctk_batch* b) { return b ? (size_t)b->N * b->PC : 0; }
+const char* ctk_batch_dominant_kernel(const ctk_batch* b) { return b ? b->dominant.c_str() : ""; }
+
+}  // extern "C"
+
+namespace {
+
+// ctk_batch_create (pred == CTK_PRED_ODE) and ctk_mlp_batch_create (CTK_PRED_MLP) into the caller's fresh struct: the refusals that need
+// only the configuration, the device probe, the buffers.  On failure the message is in g_create_error and the caller deletes the struct.
+int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problems, const uint64_t* seeds) {
+    const bool mlp = pred == CTK_PRED_MLP;
+    const char* who = mlp ? "ctk_mlp_batch_create" : "ctk_batch_create";
+    auto refuse = [&](int code, const std::string& msg) { return bfail(nullptr, code, mlp ? mlp_family_names(msg) : msg); };
+    if (n_problems < 1) return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    const EnvInfo* einfo = nullptr;
+    if (int rc = check_config(who, cfg, &einfo)) return rc;
+    const int N = cfg->num_rollouts, H = cfg->mpc_horizon, P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
+    const int hw1 = cfg->predictor_hidden1 ? cfg->predictor_hidden1 : 32, hw2 = cfg->predictor_hidden2 ? cfg->predictor_hidden2 : 32;
+    // the MLP family's refusals name the sizes refused: population, horizon, inducing points and the network as the reference names it
+    const std::string sizes = !mlp ? std::string()
+        : " (num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ", " + std::to_string(P) + " inducing points, network " +
+          std::to_string(einfo->S + einfo->C) + "IN-" + std::to_string(hw1) + "H1-" + std::to_string(hw2) + "H2-" + std::to_string(einfo->S) + "OUT)";
+    if (cfg->optimizer != CTK_OPT_MPPI)
+        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch steps MPPI controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+                      "); the other optimizers run as single handles (ctk_create)" + sizes);
+    if (!mlp && cfg->predictor != CTK_PRED_ODE)
+        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
+                      std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
+    if (mlp) {
+        if (cfg->predictor == CTK_PRED_ODE)
+            return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: this family rolls out the MLP predictor (cfg.predictor == " + std::to_string(cfg->predictor) +
+                         " is the analytic one: use ctk_batch_create)" + sizes);
+        if (cfg->predictor != CTK_PRED_MLP)
+            return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: this family rolls out the MLP predictor only (cfg.predictor == " + std::to_string(cfg->predictor) +
+                         "); the GRU's carried hidden state has no batch form, such a controller runs as a single handle (ctk_create)" + sizes);
+        if (cfg->environment != CTK_ENV_CARTPOLE || cfg->generic_kernels != 0)
+            return bfail(nullptr, CTK_ERR_UNSUPPORTED, std::string("ctk_mlp_batch_create: the batch kernel is CartPole's matrix-core MLP kernel (environment ") + einfo->name +
+                         ", generic_kernels == " + std::to_string(cfg->generic_kernels) + "): such handles run the one-wave template network kernels, which have no batch form (ctk_create)" + sizes);
+        if (hw1 < 1 || hw2 < 1) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_create: predictor_hidden1 / predictor_hidden2 must be >= 1 (0 = 32)");
+        if (std::max(hw1, hw2) > 32)
+            return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: the batch kernel holds 32 units per hidden layer (narrower layers are embedded exactly); wider "
+                         "networks run the 64-unit template kernels, which have no batch form (ctk_create)" + sizes);
+    }
+    if (!(cfg->LBD > 0.0f && cfg->NU != 0.0f)) return refuse(CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: MPPI needs LBD > 0 and NU != 0");
+    size_t lds = 0;
+    int blocks = 0;
+    if (const int why = mlp ? ctk_mppi_batch_mlp_fit(N, H, P, &lds, &blocks) : ctk_mppi_batch_fit(cfg->environment, N, H, P, &lds, &blocks)) {
+        const std::string sizes = "num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ", " + std::to_string(P) + " inducing points x " +
+                                  std::to_string(einfo->C) + " inputs = " + std::to_string(blocks) + " block records of " + std::to_string(2 + P * einfo->C) + " words";
+        const char* reason = why == 1 ? (mlp ? ": a handle of this size does not run the pair form of the MLP kernel (more than 8192 rollouts, or CTK_MPPI_NO_PAIR is set), the only one a batch has"
+                                             : ": populations from 32768 rollouts on run the throughput kernels, which a batch does not have")
+                           : why == 2 ? ": the batch kernel has the narrow in-launch hand-off only (at most 128 records and 2048 record words per problem)"
+                           : why == 3 ? ": the block records do not fit the hand-off's LDS staging"
+                                      : ": the rollout tiles need more than 160 KiB of LDS";
+        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: per-problem population outside the batch kernel's sizes (" + sizes + ")" + reason +
+                      (why == 4 ? " (" + std::to_string(lds) + " bytes)" : std::string()) + "; such a controller runs as a single handle (ctk_create)");
+    }
+
+    hipDeviceProp_t prop;
+    if (int rc = probe_device(who, cfg->device, &prop)) return rc;
+
+    batch_core_init(b, cfg, einfo, n_problems);        // dirty: no constants in d_k yet, the first step of the per-problem form derives them all
+    b->mlp_names = mlp;
+    b->pred = pred; b->hid1 = hw1; b->hid2 = hw2;
+    b->P = P; b->PC = P * b->C; b->blocks = blocks;
+    b->mk = mppi_constants(b->cfg);
+    // Progress: the only workgroup of a launch that ever waits is block 0 of a problem, for workgroups of its own problem.  With at most
+    // CUs / 2 problems in a launch the waiting workgroups cannot fill the machine (every CU holds at least one workgroup of this kernel),
+    // so every other workgroup finds a place whatever the dispatch order.  CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH (diagnostic) only lowers it.
+    b->max_per_launch = std::max(1, prop.multiProcessorCount / 2);
+    batch_env_lowers("CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH", &b->max_per_launch);
+    // A long run goes in segments of this many steps, so that its record buffer stays bounded (256 steps of 128 problems: 2.5 MiB of
+    // records).  CTK_BATCH_RUN_SEGMENT_STEPS (diagnostic) only lowers it; the results do not depend on it.
+    batch_env_lowers("CTK_BATCH_RUN_SEGMENT_STEPS", &b->run_segment);
+    b->plant_over.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
+    b->plant_has.assign((size_t)n_problems * CTK_MAX_PARAMS, 0);
+    b->plant_tab.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
+    b->plant_sub.assign((size_t)n_problems, 0);
+    b->noise_sigma.assign((size_t)n_problems * 2 * CTK_MAX_STATES, 0.0f);
+    b->noise_seed.resize((size_t)n_problems);
+    for (int p = 0; p < n_problems; ++p) b->noise_seed[(size_t)p] = batch_seed(cfg, seeds, p);   // the controller's (below)
+    b->noise_pos.assign((size_t)n_problems, 0u);
+    b->cur.assign((size_t)n_problems, 0);
+    b->dominant = mlp ? ctk_mppi_batch_mlp_name(cfg->materialize_trajectories != 0) : ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
+    if (mlp) { b->wtab = ctk_mppi_batch_mlp_table_floats(); b->have_w.assign((size_t)n_problems, 0); }
+
+    if (int rc = batch_core_open(b)) return rc;
+    const size_t Bz = (size_t)n_problems, rec = (size_t)blocks * (2 + b->PC);
+    BHIP_CREATE(batch_dev_zero(b, &b->d_interp, (size_t)H * sizeof(InterpEntry)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_J, Bz * N * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_Q, Bz * N * b->HC * sizeof(float)));
+    if (cfg->materialize_trajectories) BHIP_CREATE(batch_dev_zero(b, &b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_parts, Bz * rec * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_ll, Bz * rec * sizeof(unsigned long long)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_unom, Bz * b->unom_stride() * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_desc, Bz * sizeof(CtkBatchDesc)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_steps, Bz * sizeof(CtkBatchStep)));
+    BHIP_CREATE(batch_pinned_zero(b, &b->h_steps, Bz * sizeof(CtkBatchStep)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_k, Bz * b->kstride));
+    BHIP_CREATE(batch_pinned_zero(b, &b->h_k, Bz * b->kstride));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_kplant, Bz * b->kstride));
+    BHIP_CREATE(batch_pinned_zero(b, &b->h_kplant, Bz * b->kstride));
+    if (mlp) {
+        BHIP_CREATE(batch_dev_zero(b, &b->d_w, Bz * b->wtab * sizeof(float)));
+        BHIP_CREATE(batch_pinned_zero(b, &b->h_w, Bz * b->wtab * sizeof(float)));
+    }
+
+    const std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, P);
+    std::vector<CtkBatchDesc> desc(Bz);
+    std::vector<float> plan(Bz * b->unom_stride(), 0.0f);          // optimizer_reset(): buffer 0 of every problem at mid-range
+    for (int p = 0; p < n_problems; ++p) {
+        const size_t z = (size_t)p;
+        const uint64_t seed = batch_seed(cfg, seeds, p);
+        CtkBatchDesc& d = desc[z];
+        d.parts = b->d_parts + z * rec; d.ll = b->d_ll + z * rec;
+        d.J = b->d_J + z * N; d.Q_out = b->d_Q + z * N * b->HC;
+        d.traj_out = b->d_traj ? b->d_traj + z * N * (H + 1) * b->S : nullptr;
+        d.unom[0] = b->unom(p, 0); d.unom[1] = b->unom(p, 1);
+        d.u_dev = b->d_u + z * CTK_MAX_INPUTS; d.u_host = b->h_u_dev + z * 16;
+        d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
+        for (int i = 0; i < b->HC; ++i) plan[z * b->unom_stride() + i] = 0.5f * (cfg->action_low[i % b->C] + cfg->action_high[i % b->C]);
+    }
+    BHIP_CREATE(hipMemcpyAsync(b->d_interp, tab.data(), (size_t)H * sizeof(InterpEntry), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkBatchDesc), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipMemcpyAsync(b->d_unom, plan.data(), plan.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
+    return CTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void ctk_batch_destroy(ctk_batch* b) { delete b; }
+
+int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: NULL argument");
+    ctk_batch* b = new ctk_batch();
+    if (int rc = batch_create_in(b, CTK_PRED_ODE, cfg, n_problems, seeds)) { delete b; return rc; }
+    *out = b;
+    return CTK_OK;
+}
+
+int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
+                   float* u_out) {
+    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_step", n_ids, ids, &n)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // by history: ahead of the check of `samples` here, behind it in the CEM and RPGD steps
+    const size_t per = (size_t)b->N * b->PC;
+    const float* d_s = nullptr;                        // draws of the step's first problem; row j follows at j * per
+    if (samples_loc != CTK_LOC_NONE) {
+        if (samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+        if (samples_loc == CTK_LOC_DEVICE) d_s = samples;
+        else if (samples_loc == CTK_LOC_HOST) {
+            if (int rc = batch_stage(b, samples, (size_t)n * per)) return rc;
+            d_s = b->d_samples;
+        } else return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+    }
+    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es)
+    for (int j = 0; j < n; ++j) {
+        CtkBatchStep& q = b->h_steps[j];
+        batch_fill_record(b, q, ids ? ids[j] : j, 0);
+        if (d_s) q.samples = d_s + (size_t)j * per;
+        batch_record_io(b, q, j, s, u_prev);
+    }
+    hipError_t le = b->differ ? batch_flush_constants(b) : hipSuccess;          // the constants' transfer goes ahead of the step records'
+    if (le == hipSuccess) le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkBatchStep), hipMemcpyHostToDevice, b->stream);
+    const RolloutArgs a = batch_args(b);
+    int launched = 0;
+    if (le == hipSuccess) le = batch_launch_records(b, a, b->d_steps, n, &launched);
+    for (int j = 0; j < launched; ++j) b->cur[(size_t)b->h_steps[j].id] ^= 1;
+    const std::string late = batch_poll(b, ids, launched);
+    std::string timed_out;
+    for (int j = 0; j < n; ++j) {
+        const int p = b->h_steps[j].id;
+        ++b->seq[(size_t)p];                           // every listed problem, launched or not, consumes its sequence number (ctk_api.hip: guarded()); as CEM, RPGD differs on purpose
+        if (j >= launched) continue;
+        ++b->call[(size_t)p];                          // by history: for every launched problem, published or not (CEM and RPGD: only if its slot shows the step's seq)
+        batch_read_u(b, p, j, u_out);
+        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;   // the hand-off's error word (MPPI and CEM; RPGD has none)
+        if (errw[0]) { errw[0] = 0; list_problem(timed_out, p); }
+    }
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_step: ") + hipGetErrorString(le));
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_step: the step finished without publishing the result of problem(s) " + late);
+    if (!timed_out.empty())                            // this family's text alone says "their outputs are NaN"
+        return bfail(b, CTK_ERR_STATE, "ctk_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; their outputs are NaN, the other problems' outputs are valid and written");
+    return CTK_OK;
+}
+
+int ctk_batch_reset(ctk_batch* b, int n_ids, const int32_t* ids) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_reset", n_ids, ids, &n)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    for (int j = 0; j < n; ++j)
+        if (int rc = batch_reset_one(b, ids ? ids[j] : j)) return rc;
+    return CTK_OK;
+}
+
+int ctk_batch_read(ctk_batch* b, int problem, int buffer, float* dst, size_t cap) {
+    if (int rc = batch_read_check(b, "ctk_batch_read", problem, dst)) return rc;
+    const float* src = nullptr; size_t n = 0;
+    if (int rc = batch_locate_rollouts(b, "ctk_batch_read", problem, buffer, &src, &n)) return rc;
+    if (!src) {
+        if (buffer != CTK_BUF_U_NOM) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_read: a batch has Q, J, TRAJ and U_NOM");
+        src = b->unom(problem, b->cur[(size_t)problem]); n = (size_t)b->HC;
+    }
+    return batch_read_out(b, "ctk_batch_read", src, n, false, dst, cap);
+}
+
+// the state of a problem: its current plan, its last output
+static BatchState batch_state(ctk_batch* b, int p) { return {{{b->unom(p, b->cur[(size_t)p]), (size_t)b->HC}, {b->u(p), (size_t)b->C}}, {}}; }
+int ctk_batch_get_state(ctk_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_batch_get_state", problem, dst, cap, true, false, batch_state); }
+int ctk_batch_set_state(ctk_batch* b, int problem, const float* src, size_t n) {
+    return batch_state_io(b, "ctk_batch_set_state", problem, const_cast<float*>(src), n, false, false, batch_state);
+}
+
+int ctk_batch_set_param(ctk_batch* b, int id, float value) { return batch_set_param(b, "ctk_batch_set_param", id, value); }
+int ctk_batch_get_param(const ctk_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
+int ctk_problem_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
+    bool flipped = false;
+    const int rc = batch_problem_set_param(b, "ctk_problem_set_param", n_ids, ids, id, values, &flipped);
+    if (flipped) b->dominant = b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
+                                                       : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    return rc;
+}
+int ctk_problem_get_param(const ctk_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
+int ctk_problem_params_differ(const ctk_batch* b) { return batch_params_differ(b); }
+int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
+int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) { return batch_rng_set_position(b, "ctk_batch_rng_set_position", problem, call); }
+
+// ---- the closed loop on the device (include/ctk_hip_run.h: ctk_batch_plant_* / ctk_batch_run) ----
+int ctk_batch_plant_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_plant_set_param", n_ids, ids, &n)) return rc;
+    if (int rc = batch_param_id(b, "ctk_batch_plant_set_param", id)) return rc;
+    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_param: NULL values (one value per listed problem)");
+    for (int j = 0; j < n; ++j) {
+        const size_t z = (size_t)(ids ? ids[j] : j) * CTK_MAX_PARAMS + (size_t)id;
+        b->plant_over[z] = values[j];                  // derived at the next run or plant step (batch_plant_flush compares the tables)
+        b->plant_has[z] = 1;
+    }
+    return CTK_OK;
+}
+
+int ctk_batch_plant_get_param(const ctk_batch* b, int problem, int id, float* value) {
+    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    const size_t z = (size_t)problem * CTK_MAX_PARAMS + (size_t)id;
+    *value = b->plant_has[z] ? b->plant_over[z] : b->table(problem)[id];
+    return CTK_OK;
+}
+
+int ctk_batch_plant_clear_params(ctk_batch* b) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    std::fill(b->plant_has.begin(), b->plant_has.end(), (unsigned char)0);
+    return CTK_OK;
+}
+
+int ctk_batch_plant_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u, int substeps, float* s_next) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!s || !u || !s_next) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_step: NULL state, input or destination");
+    return batch_plant_step(b, "ctk_batch_plant_step", n_ids, ids, s, u, nullptr, substeps, s_next, nullptr, nullptr);
+}
+
+int ctk_batch_run(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, const float* u_prev, int n_steps, int plant_substeps,
+                  float* states_out, float* inputs_out, int32_t* first_bad) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!s0 || !states_out || !inputs_out) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_run: NULL start states or trace destination");
+    return batch_closed_loop(b, LoopCall{"ctk_batch_run", "a run", n_ids, ids, s0, nullptr, u_prev, n_steps, plant_substeps, states_out, nullptr, inputs_out,
+                                         nullptr, first_bad});
+}
+
+// ---- the stochastic plant and the realised cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes) ----
+int ctk_batch_plant_set_noise(ctk_batch* b, int n_ids, const int32_t* ids, int kind, const float* sigma) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_plant_set_noise", n_ids, ids, &n)) return rc;
+    if (kind != 0 && kind != 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: kind is 0 (process noise) or 1 (measurement noise), not " + std::to_string(kind));
+    if (!sigma) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: NULL sigma (one row of num_states values per listed problem)");
+    for (int i = 0; i < n * b->S; ++i)
+        if (!(std::isfinite(sigma[i]) && sigma[i] >= 0.0f))
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: a standard deviation is finite and >= 0 (" + std::to_string(sigma[i]) + " for problem " +
+                         std::to_string(ids ? ids[i / b->S] : i / b->S) + ", state " + std::to_string(i % b->S) + "); nothing was written");
+    for (int j = 0; j < n; ++j) {
+        float* dst = &b->noise_sigma[((size_t)(ids ? ids[j] : j) * 2 + (size_t)kind) * CTK_MAX_STATES];
+        for (int i = 0; i < b->S; ++i) dst[i] = sigma[(size_t)j * b->S + i] == 0.0f ? 0.0f : sigma[(size_t)j * b->S + i];   // -0.0 is "none" too
+    }
+    return CTK_OK;
+}
+
+int ctk_batch_plant_get_noise(const ctk_batch* b, int problem, int kind, float* sigma) {
+    if (!b || !sigma || problem < 0 || problem >= b->B || (kind != 0 && kind != 1)) return CTK_ERR_INVALID_ARGUMENT;
+    std::memcpy(sigma, &b->noise_sigma[((size_t)problem * 2 + (size_t)kind) * CTK_MAX_STATES], (size_t)b->S * sizeof(float));
+    return CTK_OK;
+}
+
+int ctk_batch_plant_clear_noise(ctk_batch* b) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    std::fill(b->noise_sigma.begin(), b->noise_sigma.end(), 0.0f);
+    return CTK_OK;
+}
+
+int ctk_batch_plant_set_noise_seed(ctk_batch* b, int n_ids, const int32_t* ids, const uint64_t* seeds) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_batch_plant_set_noise_seed", n_ids, ids, &n)) return rc;
+    if (!seeds) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise_seed: NULL seeds (one per listed problem)");
+    for (int j = 0; j < n; ++j) b->noise_seed[(size_t)(ids ? ids[j] : j)] = seeds[j];
+    return CTK_OK;
+}
+
+int ctk_batch_plant_get_noise_seed(const ctk_batch* b, int problem, uint64_t* seed) {
+    if (!b || !seed || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *seed = b->noise_seed[(size_t)problem];
+    return CTK_OK;
+}
+
+int ctk_batch_plant_noise_get_position(const ctk_batch* b, int problem, uint32_t* pos) {
+    if (!b || !pos || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *pos = b->noise_pos[(size_t)problem];
+    return CTK_OK;
+}
+
+int ctk_batch_plant_noise_set_position(ctk_batch* b, int problem, uint32_t pos) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, "ctk_batch_plant_noise_set_position", problem)) return rc;
+    b->noise_pos[(size_t)problem] = pos;
+    return CTK_OK;
+}
+
+int ctk_batch_plant_step_noisy(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev, int substeps,
+                               float* s_next, float* y_next, float* cost) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!s || !u || !u_prev || !s_next || !y_next || !cost)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_step_noisy: NULL state, input, previous input or destination");
+    return batch_plant_step(b, "ctk_batch_plant_step_noisy", n_ids, ids, s, u, u_prev, substeps, s_next, y_next, cost);
+}
+
+int ctk_batch_episodes(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, const float* y0, const float* u_prev, int n_steps,
+                       int plant_substeps, float* states_out, float* obs_out, float* inputs_out, float* costs_out, int32_t* first_bad) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!s0 || !states_out || !obs_out || !inputs_out || !costs_out)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_episodes: NULL start states or trace destination");
+    return batch_closed_loop(b, LoopCall{"ctk_batch_episodes", "an episode", n_ids, ids, s0, y0, u_prev, n_steps, plant_substeps, states_out, obs_out,
+                                         inputs_out, costs_out, first_bad});
+}
+
+}  // extern "C"
+
+// =============================================================================================
+// Batched MPPI with the MLP predictor (include/ctk_hip.h: ctk_mlp_batch_* / ctk_mlp_problem_*): the ctk_batch above with pred == CTK_PRED_MLP
+// — the same struct, step records, completion poll, constants flush, reset and read paths — launched as ctk_mppi_batch_mlp<LOG> /
+// ctk_mppi_batch_mlp_pp<LOG>, plus what a learned plant adds: one per-lane weight table per problem (d_w [B][wtab], permute_mlp_weights as
+// for a handle's d_wperm), written by ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights through ONE transfer per call, and
+// `have_w`, without which a problem is not stepped.
+// =============================================================================================
+struct ctk_mlp_batch { ctk_batch b; };
+
+namespace {
+
+ctk_batch* core(ctk_mlp_batch* m) { return m ? &m->b : nullptr; }
+const ctk_batch* core(const ctk_mlp_batch* m) { return m ? &m->b : nullptr; }
+
+size_t mlp_batch_weight_count(const ctk_batch* b) { return shaped_weight_count(CTK_PRED_MLP, b->S, b->C, b->hid1, b->hid2); }
+
+// tables of the n listed problems (ids == NULL: problems 0 .. n-1) from w [n][cnt] (each_own) or from the one network w [cnt]: permuted
+// into the pinned staging at the problems' places, then the span from the first to the last listed problem in ONE transfer.  The staging
+// mirrors d_w (both start as zeros and change only here), so what lies between two listed problems is rewritten with what it holds.
+int mlp_batch_put_weights(ctk_batch* b, int n, const int32_t* ids, const float* w, size_t cnt, bool each_own) {
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    std::vector<float> full(weight_count(CTK_PRED_MLP, b->S, b->C, 32));
+    std::vector<float> perm;
+    for (int j = 0; j < n; ++j) {
+        if (j == 0 || each_own) {
+            const float* src = w + (each_own ? (size_t)j * cnt : 0);
+            if (b->hid1 == 32 && b->hid2 == 32) perm = permute_mlp_weights(src, b->S, b->C);
+            else {
+                std::fill(full.begin(), full.end(), 0.0f);
+                embed_mlp_rows(src, b->S, b->S + b->C, b->hid1, b->hid2, 32, full.data());
+                perm = permute_mlp_weights(full.data(), b->S, b->C);
+            }
+        }
+        std::memcpy(b->h_w + (size_t)(ids ? ids[j] : j) * b->wtab, perm.data(), b->wtab * sizeof(float));
+    }
+    const int lo = ids ? ids[0] : 0, hi = ids ? ids[n - 1] : n - 1;         // (ids are ascending: batch_ids)
+    BHIP_TRY(b, hipMemcpyAsync(b->d_w + (size_t)lo * b->wtab, b->h_w + (size_t)lo * b->wtab, (size_t)(hi - lo + 1) * b->wtab * sizeof(float),
+                               hipMemcpyHostToDevice, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    for (int j = 0; j < n; ++j) b->have_w[(size_t)(ids ? ids[j] : j)] = 1;
+    return CTK_OK;
+}
+
+// a problem without a network is not stepped, and then none of the listed ones is: nothing is launched, no plan, output or Philox
+// position moves (a handle's ctk_step fails the same way: check_predictor)
+int mlp_batch_have_weights(ctk_batch* b, const char* who, int n_ids, const int32_t* ids) {
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    std::string missing;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        if (!b->have_w[(size_t)p]) list_problem(missing, p);
+    }
+    if (!missing.empty())
+        return bfail(b, CTK_ERR_STATE, std::string(who) + ": no network weights for problem(s) " + missing +
+                     " (ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights before stepping); nothing was launched");
+    return CTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* ctk_mlp_batch_last_error(const ctk_mlp_batch* m) { return ctk_batch_last_error(core(m)); }
+int ctk_mlp_batch_size(const ctk_mlp_batch* m) { return ctk_batch_size(core(m)); }
+size_t ctk_mlp_batch_samples_needed(const ctk_mlp_batch* m) { return ctk_batch_samples_needed(core(m)); }
+const char* ctk_mlp_batch_dominant_kernel(const ctk_mlp_batch* m) { return ctk_batch_dominant_kernel(core(m)); }
+
+void ctk_mlp_batch_destroy(ctk_mlp_batch* m) { delete m; }
+
+int ctk_mlp_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_mlp_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_create: NULL argument");
+    ctk_mlp_batch* m = new ctk_mlp_batch();
+    if (int rc = batch_create_in(&m->b, CTK_PRED_MLP, cfg, n_problems, seeds)) { delete m; return rc; }
+    *out = m;
+    return CTK_OK;
+}
+
+size_t ctk_mlp_batch_weight_count(const ctk_mlp_batch* m) { return m ? mlp_batch_weight_count(&m->b) : 0; }
+
+int ctk_mlp_batch_set_weights(ctk_mlp_batch* m, const float* w, size_t n) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    if (!w) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_set_weights: NULL weights");
+    if (n != mlp_batch_weight_count(b))
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_set_weights: expected " + std::to_string(mlp_batch_weight_count(b)) + " floats for the " +
+                     std::to_string(b->S + b->C) + "IN-" + std::to_string(b->hid1) + "H1-" + std::to_string(b->hid2) + "H2-" + std::to_string(b->S) +
+                     "OUT network (ctk_mlp_batch_weight_count), got " + std::to_string(n));
+    return mlp_batch_put_weights(b, b->B, nullptr, w, n, false);
+}
+
+int ctk_mlp_problem_set_weights(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* w, size_t n) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    int cnt = 0;
+    if (int rc = batch_ids(b, "ctk_mlp_problem_set_weights", n_ids, ids, &cnt)) return rc;
+    if (!w) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_problem_set_weights: NULL weights (one network per listed problem)");
+    if (n != mlp_batch_weight_count(b))
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_problem_set_weights: expected " + std::to_string(mlp_batch_weight_count(b)) + " floats per problem for the " +
+                     std::to_string(b->S + b->C) + "IN-" + std::to_string(b->hid1) + "H1-" + std::to_string(b->hid2) + "H2-" + std::to_string(b->S) +
+                     "OUT network (ctk_mlp_batch_weight_count), got " + std::to_string(n));
+    return mlp_batch_put_weights(b, cnt, ids, w, n, true);
+}
+
+int ctk_mlp_problem_have_weights(const ctk_mlp_batch* m, int problem) {
+    return (m && problem >= 0 && problem < m->b.B && m->b.have_w[(size_t)problem]) ? 1 : 0;
+}
+
+int ctk_mlp_batch_step(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
+                       float* u_out) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    if (!s) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_step: NULL state");
+    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_step", n_ids, ids)) return rc;
+    return ctk_batch_step(b, n_ids, ids, s, u_prev, samples, samples_loc, u_out);
+}
+
+// the closed loop on the device: ctk_batch_plant_* / ctk_batch_run under this family's names.  The network plans, the plant is the
+// analytic CartPole with the problem's parameter table (and the overrides set here)
+int ctk_mlp_batch_plant_set_param(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int id, const float* values) {
+    return ctk_batch_plant_set_param(core(m), n_ids, ids, id, values);
+}
+int ctk_mlp_batch_plant_get_param(const ctk_mlp_batch* m, int problem, int id, float* value) { return ctk_batch_plant_get_param(core(m), problem, id, value); }
+int ctk_mlp_batch_plant_clear_params(ctk_mlp_batch* m) { return ctk_batch_plant_clear_params(core(m)); }
+int ctk_mlp_batch_plant_step(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u, int substeps, float* s_next) {
+    return ctk_batch_plant_step(core(m), n_ids, ids, s, u, substeps, s_next);
+}
+int ctk_mlp_batch_run(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s0, const float* u_prev, int n_steps, int plant_substeps,
+                      float* states_out, float* inputs_out, int32_t* first_bad) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    if (!s0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_run: NULL start states or trace destination");
+    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_run", n_ids, ids)) return rc;
+    return ctk_batch_run(b, n_ids, ids, s0, u_prev, n_steps, plant_substeps, states_out, inputs_out, first_bad);
+}
+// the stochastic plant and the realised cost (include/ctk_hip_episode.h), under this family's names
+int ctk_mlp_batch_plant_set_noise(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int kind, const float* sigma) {
+    return ctk_batch_plant_set_noise(core(m), n_ids, ids, kind, sigma);
+}
+int ctk_mlp_batch_plant_get_noise(const ctk_mlp_batch* m, int problem, int kind, float* sigma) { return ctk_batch_plant_get_noise(core(m), problem, kind, sigma); }
+int ctk_mlp_batch_plant_clear_noise(ctk_mlp_batch* m) { return ctk_batch_plant_clear_noise(core(m)); }
+int ctk_mlp_batch_plant_set_noise_seed(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const uint64_t* seeds) {
+    return ctk_batch_plant_set_noise_seed(core(m), n_ids, ids, seeds);
+}
+int ctk_mlp_batch_plant_get_noise_seed(const ctk_mlp_batch* m, int problem, uint64_t* seed) { return ctk_batch_plant_get_noise_seed(core(m), problem, seed); }
+int ctk_mlp_batch_plant_noise_get_position(const ctk_mlp_batch* m, int problem, uint32_t* pos) { return ctk_batch_plant_noise_get_position(core(m), problem, pos); }
+int ctk_mlp_batch_plant_noise_set_position(ctk_mlp_batch* m, int problem, uint32_t pos) { return ctk_batch_plant_noise_set_position(core(m), problem, pos); }
+int ctk_mlp_batch_plant_step_noisy(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev, int substeps,
+                                   float* s_next, float* y_next, float* cost) {
+    return ctk_batch_plant_step_noisy(core(m), n_ids, ids, s, u, u_prev, substeps, s_next, y_next, cost);
+}
+int ctk_mlp_batch_episodes(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s0, const float* y0, const float* u_prev, int n_steps,
+                           int plant_substeps, float* states_out, float* obs_out, float* inputs_out, float* costs_out, int32_t* first_bad) {
+    if (!m) return CTK_ERR_INVALID_ARGUMENT;
+    ctk_batch* b = &m->b;
+    if (!s0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_episodes: NULL start states or trace destination");
+    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_episodes", n_ids, ids)) return rc;
+    return ctk_batch_episodes(b, n_ids, ids, s0, y0, u_prev, n_steps, plant_substeps, states_out, obs_out, inputs_out, costs_out, first_bad);
+}
+
+int ctk_mlp_batch_reset(ctk_mlp_batch* m, int n_ids, const int32_t* ids) { return ctk_batch_reset(core(m), n_ids, ids); }
+int ctk_mlp_batch_read(ctk_mlp_batch* m, int problem, int buffer, float* dst, size_t cap) { return ctk_batch_read(core(m), problem, buffer, dst, cap); }
+int ctk_mlp_batch_get_state(ctk_mlp_batch* m, int problem, float* dst, size_t cap) { return ctk_batch_get_state(core(m), problem, dst, cap); }
+int ctk_mlp_batch_set_state(ctk_mlp_batch* m, int problem, const float* src, size_t n) { return ctk_batch_set_state(core(m), problem, src, n); }
+int ctk_mlp_batch_set_param(ctk_mlp_batch* m, int id, float value) { return ctk_batch_set_param(core(m), id, value); }
+int ctk_mlp_batch_get_param(const ctk_mlp_batch* m, int id, float* value) { return ctk_batch_get_param(core(m), id, value); }
+int ctk_mlp_problem_set_param(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int id, const float* values) {
+    return ctk_problem_set_param(core(m), n_ids, ids, id, values);
+}
+int ctk_mlp_problem_get_param(const ctk_mlp_batch* m, int problem, int id, float* value) { return ctk_problem_get_param(core(m), problem, id, value); }
+int ctk_mlp_problem_params_differ(const ctk_mlp_batch* m) { return ctk_problem_params_differ(core(m)); }
+int ctk_mlp_batch_rng_get_position(const ctk_mlp_batch* m, int problem, uint32_t* call) { return ctk_batch_rng_get_position(core(m), problem, call); }
+int ctk_mlp_batch_rng_set_position(ctk_mlp_batch* m, int problem, uint32_t call) { return ctk_batch_rng_set_position(core(m), problem, call); }
+
+}  // extern "C"
+
+// =============================================================================================
+// Batched CEM (include/ctk_hip.h: ctk_cem_batch_*): B independent CEM problems of one configuration, stepped by launches of
+// ctk_cem_batch<ENV, TRAJ> (ctk_cem_fused.hip).  One allocation per buffer kind with a problem stride — no handles inside.  Per-problem
+// host state is what a CEM handle keeps: the sequence number of its next step, its Philox position, its step count (which decides the
+// outer iterations of its next step: cem_iterations), the next hand-off tag, whether BEST_IDX has to be rebuilt from J, and its parameter
+// table.  While no ctk_cem_problem_set_param has succeeded the launches take the constants of the shared table by value; from then on
+// (`differ`, sticky) every step writes the constants of the problems it steps BEHIND their step records, in the records' order, so they
+// travel in the records' transfer (no constants array in device memory, no second transfer).
+// =============================================================================================
+struct ctk_cem_batch : BatchCore {
+    int K = 0, nblk = 0;
+    std::vector<unsigned char> kcache;      // [B][kstride] derived constants by problem id (host only; the step copies them into h_steps)
+    int max_per_launch = 1;                 // problems per launch: max(1, CUs / nblk) (ctk_cem_batch_create), a diagnostic switch may lower it
+    size_t llw = 0;                         // ctk_cem_fused_ll_words(N, HC): hand-off words per problem
+    unsigned long long* d_ll = nullptr;     // [B][llw], zero at allocation
+    float* d_mu = nullptr;                  // [B][H,C]
+    float* d_sd = nullptr;                  // [B][H,C]
+    int* d_idx = nullptr;                   // [B][N]
+    CtkCemBatchDesc* d_desc = nullptr;      // [B]
+    CtkCemBatchStep* h_steps = nullptr;     // pinned, B * (sizeof(CtkCemBatchStep) + kstride) bytes: the n step records of the step being
+    CtkCemBatchStep* d_steps = nullptr;     // issued and, in the per-problem form, the constants of those n problems right behind them
+    std::vector<uint32_t> cem_tag;
+    std::vector<int> count;
+    std::vector<unsigned char> idx_stale;
+    float* mu(int p) const { return d_mu + (size_t)p * HC; }
+    float* sd(int p) const { return d_sd + (size_t)p * HC; }
+    int its(int p) const { return (cfg.warmup && count[(size_t)p] == 0) ? cfg.warmup_iterations : cfg.cem_outer_it; }   // cem_iterations
+};
+
+namespace {
+
+// the shared template of a launch's RolloutArgs (ctk_api.hip: make_args of a CEM handle without what the step records and descriptors supply)
+RolloutArgs cem_batch_args(const ctk_cem_batch* b) {
+    RolloutArgs a = batch_common_args(b);
+    a.P = b->H;
+    a.p_magic = ctk_magic_of(b->H);
+    return a;
+}
+
+// mean at mid-range, std = cem_initial_action_stdev, u = 0 of problem p into the host images (ctk_reset of a CEM handle)
+void cem_batch_initial(const ctk_cem_batch* b, float* mu, float* sd) {
+    for (int i = 0; i < b->HC; ++i) {
+        mu[i] = 0.5f * (b->cfg.action_low[i % b->C] + b->cfg.action_high[i % b->C]);
+        sd[i] = b->cfg.cem_initial_action_stdev;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* ctk_cem_batch_last_error(const ctk_cem_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+int ctk_cem_batch_size(const ctk_cem_batch* b) { return b ? b->B : 0; }
+size_t ctk_cem_batch_samples_needed(const ctk_cem_batch* b, int problem) {
+    return (b && problem >= 0 && problem < b->B) ? (size_t)b->its(problem) * b->N * b->HC : 0;
+}
+const char* ctk_cem_batch_dominant_kernel(const ctk_cem_batch* b) { return b ? b->dominant.c_str() : ""; }
+
+void ctk_cem_batch_destroy(ctk_cem_batch* b) { delete b; }
+
+int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_cem_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_create: NULL argument");
+    if (n_problems < 1) return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    const EnvInfo* einfo = nullptr;
+    if (int rc = check_config("ctk_cem_batch_create", cfg, &einfo)) return rc;
+    if (cfg->optimizer != CTK_OPT_CEM)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: a CEM batch steps plain CEM controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+                     "); MPPI has ctk_batch_create, the CEM variants (naive-grad, Bharadhwaj, GMM) and the other optimizers run as single handles (ctk_create)");
+    if (cfg->predictor != CTK_PRED_ODE)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
+                     std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
+    const int N = cfg->num_rollouts, H = cfg->mpc_horizon, HC = H * einfo->C, nblk = ctk_cem_fused_blocks(N);
+    if (!ctk_cem_fusable(cfg->predictor, N, HC))
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: per-problem population outside the one-launch CEM step's sizes (num_rollouts " + std::to_string(N) +
+                     " = " + std::to_string(nblk) + " workgroups of 64 rollouts, mpc_horizon " + std::to_string(H) + " x " + std::to_string(einfo->C) + " inputs = " +
+                     std::to_string(HC) + " columns, " + std::to_string(ctk_cem_fused_lds(N, HC)) + " bytes of LDS): the batch kernel takes at most " +
+                     std::to_string(CTK_CEM_FUSED_MAX_BLOCKS) + " workgroups per problem and 131072 bytes (128 KiB) of LDS; such a controller runs as a single handle (ctk_create)");
+    if (cfg->cem_best_k > N)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_cem_batch_create: cem_best_k " + std::to_string(cfg->cem_best_k) + " exceeds num_rollouts " + std::to_string(N) +
+                     ": the elite set of a problem is part of its population");
+    if (cfg->cem_best_k < 1 || cfg->cem_outer_it < 1 || (cfg->warmup && cfg->warmup_iterations < 1))
+        return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_create: need cem_best_k >= 1, cem_outer_it >= 1 and, with warmup, warmup_iterations >= 1");
+
+    hipDeviceProp_t prop;
+    if (int rc = probe_device("ctk_cem_batch_create", cfg->device, &prop)) return rc;
+
+    BatchMade<ctk_cem_batch> made;
+    ctk_cem_batch* b = made.b;
+    batch_core_init(b, cfg, einfo, n_problems);
+    b->K = cfg->cem_best_k; b->nblk = nblk;
+    b->llw = ctk_cem_fused_ll_words(N, HC);
+    b->kcache.assign((size_t)n_problems * b->kstride, 0);
+    // Progress (the proof stands above ctk_cem_batch, ctk_cem_fused.hip): every workgroup of a problem waits for all workgroups of that
+    // problem, so a launch holds at most max(1, CUs / nblk) problems — problems * nblk <= CUs, every CU admits at least one workgroup of
+    // this kernel (LDS <= 128 KiB), so all workgroups of a launch are co-resident whatever the dispatch order or placement.  One problem
+    // alone is the single kernel's case (nblk <= CTK_CEM_FUSED_MAX_BLOCKS).  CTK_CEM_BATCH_MAX_PROBLEMS_PER_LAUNCH (diagnostic) only lowers it.
+    b->max_per_launch = std::max(1, prop.multiProcessorCount / nblk);
+    batch_env_lowers("CTK_CEM_BATCH_MAX_PROBLEMS_PER_LAUNCH", &b->max_per_launch);
+    b->cem_tag.assign((size_t)n_problems, 1u);
+    b->count.assign((size_t)n_problems, 0); b->idx_stale.assign((size_t)n_problems, 0);
+    b->dominant = ctk_cem_batch_name(b->env, cfg->materialize_trajectories != 0);
+
+    if (int rc = batch_core_open(b)) return rc;
+    const size_t Bz = (size_t)n_problems;
+    BHIP_CREATE(batch_dev_zero(b, &b->d_ll, Bz * b->llw * sizeof(unsigned long long)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_mu, Bz * HC * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_sd, Bz * HC * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_J, Bz * N * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_Q, Bz * N * HC * sizeof(float)));
+    if (cfg->materialize_trajectories) BHIP_CREATE(batch_dev_zero(b, &b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_idx, Bz * N * sizeof(int)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_desc, Bz * sizeof(CtkCemBatchDesc)));
+    const size_t steps_bytes = Bz * (sizeof(CtkCemBatchStep) + b->kstride);   // the records, then room for as many elements of constants
+    BHIP_CREATE(batch_dev_zero(b, &b->d_steps, steps_bytes));
+    BHIP_CREATE(batch_pinned_zero(b, &b->h_steps, steps_bytes));
+
+    std::vector<CtkCemBatchDesc> desc(Bz);
+    std::vector<float> mu(Bz * HC), sd(Bz * HC);                   // optimizer_reset() of every problem
+    for (int p = 0; p < n_problems; ++p) {
+        const size_t z = (size_t)p;
+        const uint64_t seed = batch_seed(cfg, seeds, p);
+        CtkCemBatchDesc& d = desc[z];
+        d.ll = b->d_ll + z * b->llw;
+        d.mu = b->mu(p); d.sd = b->sd(p);
+        d.J = b->d_J + z * N; d.Q_out = b->d_Q + z * N * HC;
+        d.traj_out = b->d_traj ? b->d_traj + z * N * (H + 1) * b->S : nullptr;
+        d.u_dev = b->u(p); d.u_host = b->h_u_dev + z * 16; d.idx_out = b->d_idx + z * N;
+        d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
+        cem_batch_initial(b, mu.data() + z * HC, sd.data() + z * HC);
+    }
+    BHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkCemBatchDesc), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipMemcpyAsync(b->d_mu, mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipMemcpyAsync(b->d_sd, sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
+    *out = made.release();
+    return CTK_OK;
+}
+
+int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
+                       float* u_out) {
+    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_cem_batch_step", n_ids, ids, &n)) return rc;
+    const size_t per_it = (size_t)b->N * b->HC;
+    const int its0 = b->its(ids ? ids[0] : 0);
+    if (samples_loc != CTK_LOC_NONE) {
+        if (samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+        // the rows of a caller's buffer have ONE length: refused before anything is launched or consumed
+        bool mixed = false;
+        for (int j = 1; j < n; ++j) mixed |= b->its(ids ? ids[j] : j) != its0;
+        if (mixed) {
+            std::string who;
+            for (int j = 0; j < n; ++j) {
+                const int p = ids ? ids[j] : j;
+                who += (j ? ", " : "") + std::to_string(p) + ": " + std::to_string(b->its(p));
+            }
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: with caller-supplied samples every listed problem must run the same number of outer "
+                         "iterations, but (problem: iterations) " + who + " — the warm-up step of a problem after its creation or reset is longer; step them in "
+                         "separate calls (the in-kernel sampler has no such restriction)");
+        }
+    }
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // behind the checks of `samples`, as in the RPGD step (the MPPI step: ahead of them, by history)
+    const size_t per = per_it * (size_t)its0;          // draws per problem (caller-supplied samples: the same for all listed problems)
+    const float* d_s = nullptr;                        // draws of the step's first problem; row j follows at j * per
+    if (samples_loc == CTK_LOC_DEVICE) d_s = samples;
+    else if (samples_loc == CTK_LOC_HOST) {
+        if (int rc = batch_stage(b, samples, (size_t)n * per)) return rc;
+        d_s = b->d_samples;
+    }
+    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es).  Every launch attempt
+    // consumes the problem's tags, as it consumes its sequence number (cem_step: the wrap rule keeps tag 0 the never-written value)
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        const size_t z = (size_t)p;
+        const int its = b->its(p);
+        CtkCemBatchStep& q = b->h_steps[j];
+        if ((uint32_t)(b->cem_tag[z] + (uint32_t)its) < b->cem_tag[z]) b->cem_tag[z] = 1;
+        q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.tag0 = b->cem_tag[z]; q.its = its;
+        b->cem_tag[z] += (uint32_t)its;
+        q.samples = d_s ? d_s + (size_t)j * per : nullptr;
+        batch_record_io(b, q, j, s, u_prev);
+    }
+    const unsigned char* d_ksteps = nullptr;           // the per-problem form: the constants behind the records, in the same transfer
+    hipError_t le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(CtkCemBatchStep), b->h_steps, b->d_steps, &d_ksteps);
+    const RolloutArgs a = cem_batch_args(b);
+    const bool log = b->cfg.materialize_trajectories != 0;
+    const CemFusedLaunch cl{0, b->K, nullptr, 0u, b->cfg.cem_stdev_min, 1.0e8f, b->cfg.cem_initial_action_stdev,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0.5};
+    int launched = 0;                                  // consecutive launches of at most max_per_launch problems; a problem never spans launches
+    while (le == hipSuccess && launched < n) {
+        const int cnt = std::min(b->max_per_launch, n - launched);
+        le = ctk_launch_cem_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, cl, b->d_desc, b->d_steps + launched, cnt, log,
+                                  d_ksteps ? d_ksteps + (size_t)launched * b->kstride : nullptr);
+        if (le == hipSuccess) launched += cnt;
+    }
+    const std::string late = batch_poll(b, ids, launched);
+    std::string timed_out;
+    for (int j = 0; j < n; ++j) {
+        const int p = b->h_steps[j].id;
+        const size_t z = (size_t)p;
+        ++b->seq[z];                                   // every listed problem, launched or not, consumes its sequence number (ctk_api.hip: guarded()); as MPPI, RPGD differs on purpose
+        if (j >= launched) continue;
+        ++b->count[z]; b->idx_stale[z] = 1;            // as cem_step: with the launch
+        if (reinterpret_cast<volatile uint32_t*>(b->slot(p))[1] != b->h_steps[j].seq) continue;   // never published (a device fault): ctk_api.hip's finish_step
+        ++b->call[z];                                  // returns before it advances the Philox position or reads u (as RPGD; MPPI advances it regardless, by history)
+        batch_read_u(b, p, j, u_out);
+        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;   // the hand-off's error word (MPPI and CEM; RPGD has none)
+        if (errw[0]) { errw[0] = 0; list_problem(timed_out, p); }
+    }
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_cem_batch_step: ") + hipGetErrorString(le));
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_cem_batch_step: the step finished without publishing the result of problem(s) " + late);
+    if (!timed_out.empty())
+        return bfail(b, CTK_ERR_STATE, "ctk_cem_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; the other problems' outputs are valid and written");
+    return CTK_OK;
+}
+
+int ctk_cem_batch_reset(ctk_cem_batch* b, int n_ids, const int32_t* ids) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_cem_batch_reset", n_ids, ids, &n)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    std::vector<float> mu((size_t)b->HC), sd((size_t)b->HC), zero((size_t)b->C, 0.0f);
+    cem_batch_initial(b, mu.data(), sd.data());
+    for (int j = 0; j < n; ++j) {                      // ctk_reset of a CEM handle: parameters, tags and the Philox position stay
+        const int p = ids ? ids[j] : j;
+        b->count[(size_t)p] = 0;
+        BHIP_TRY(b, hipMemcpyAsync(b->mu(p), mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        BHIP_TRY(b, hipMemcpyAsync(b->sd(p), sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        BHIP_TRY(b, hipMemcpyAsync(b->u(p), zero.data(), zero.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    }
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return CTK_OK;
+}
+
+int ctk_cem_batch_read(ctk_cem_batch* b, int problem, int buffer, float* dst, size_t cap) {
+    if (int rc = batch_read_check(b, "ctk_cem_batch_read", problem, dst)) return rc;
+    const size_t z = (size_t)problem, N = (size_t)b->N;
+    const float* src = nullptr; size_t n = 0; bool is_int = false;
+    if (int rc = batch_locate_rollouts(b, "ctk_cem_batch_read", problem, buffer, &src, &n)) return rc;
+    if (!src) switch (buffer) {
+        case CTK_BUF_U_NOM: src = b->mu(problem); n = (size_t)b->HC; break;
+        case CTK_BUF_STD: src = b->sd(problem); n = (size_t)b->HC; break;
+        case CTK_BUF_BEST_IDX: src = reinterpret_cast<const float*>(b->d_idx + z * N); n = (size_t)b->K; is_int = true; break;
+        default: return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: a CEM batch has Q, J, TRAJ, U_NOM, STD and BEST_IDX");
+    }
+    return batch_read_out(b, "ctk_cem_batch_read", src, n, is_int, dst, cap, [&]() -> int {
+        if (!is_int || !b->idx_stale[z]) return CTK_OK;
+        // the sorted elite indices are materialised from the last iteration's costs (ctk_api.hip: locate_buffer)
+        BHIP_TRY(b, ctk_launch_select_topk(b->stream, b->d_J + z * N, b->N, b->K, b->d_idx + z * N));
+        b->idx_stale[z] = 0;
+        return CTK_OK;
+    });
+}
+
+// the state of a problem: mean, standard deviation, last output; its step count
+static BatchState cem_batch_state(ctk_cem_batch* b, int p) {
+    return {{{b->mu(p), (size_t)b->HC}, {b->sd(p), (size_t)b->HC}, {b->u(p), (size_t)b->C}}, {&b->count[(size_t)p]}};
+}
+int ctk_cem_batch_get_state(ctk_cem_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_cem_batch_get_state", problem, dst, cap, true, false, cem_batch_state); }
+int ctk_cem_batch_set_state(ctk_cem_batch* b, int problem, const float* src, size_t n) {
+    return batch_state_io(b, "ctk_cem_batch_set_state", problem, const_cast<float*>(src), n, false, false, cem_batch_state);
+}
+
+int ctk_cem_batch_set_param(ctk_cem_batch* b, int id, float value) { return batch_set_param(b, "ctk_cem_batch_set_param", id, value); }
+int ctk_cem_batch_get_param(const ctk_cem_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
+int ctk_cem_problem_set_param(ctk_cem_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
+    bool flipped = false;
+    const int rc = batch_problem_set_param(b, "ctk_cem_problem_set_param", n_ids, ids, id, values, &flipped);
+    if (flipped) b->dominant = ctk_cem_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    return rc;
+}
+int ctk_cem_problem_get_param(const ctk_cem_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
+int ctk_cem_problem_params_differ(const ctk_cem_batch* b) { return batch_params_differ(b); }
+int ctk_cem_batch_rng_get_position(const ctk_cem_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
+int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call) {
+    return batch_rng_set_position(b, "ctk_cem_batch_rng_set_position", problem, call);
+}
+
+}  // extern "C"
+
+// =============================================================================================
+// Batched RPGD (include/ctk_hip.h: ctk_rpgd_batch_*): B independent RPGD problems of one configuration with at most
+// CTK_RPGD_FUSED_MAX_N plans each, stepped by launches of ctk_g_rpgd_batch<ENV> (ctk_generic.hip) — one workgroup per problem runs the
+// descent, the keep-k selection and the warm start that a template handle runs as three launches.  One allocation per buffer kind with a
+// problem stride — no handles inside.  Per-problem host state is what an RPGD handle keeps: the sequence number of its next step, its
+// Philox position, its step count (which decides the iterations of its next step and whether it resamples), its Adam step number, which
+// buffer holds its population, whether it has been reset, and its parameter table.  No workgroup of the kernel waits for another, so a
+// call is split into launches only at the grid's y limit.  While no ctk_rpgd_problem_set_param has succeeded the launches take the
+// constants of the shared table by value; from then on (`differ`, sticky) every step writes the constants of the problems it steps
+// BEHIND their step records, in the records' order, so they travel in the records' transfer (no constants array in device memory, no
+// second transfer).
+// =============================================================================================
+struct ctk_rpgd_batch : BatchCore {
+    int P = 0, PC = 0, K = 0;
+    std::vector<unsigned char> kcache;      // [B][kstride] derived constants by problem id (host only; the step copies them into h_steps)
+    InterpEntry* d_interp = nullptr;        // [H] shared
+    float* d_bc = nullptr; int bc_len = 0;  // shared bias-correction table
+    float* d_pop[2] = {nullptr, nullptr};   // [B][N,H,C] each
+    float* d_m[2] = {nullptr, nullptr};
+    float* d_v[2] = {nullptr, nullptr};
+    float* d_ages[2] = {nullptr, nullptr};  // [B][N] each
+    int* d_idx = nullptr;                   // [B][N]
+    float* d_unom = nullptr;                // [B][H,C]
+    float* d_scratch = nullptr; size_t scratch_stride = 0;   // [B][H * NT * 64] state tapes that do not fit in LDS
+    CtkRpgdBatchDesc* d_desc = nullptr;     // [B]
+    CtkRpgdBatchStep* h_steps = nullptr;    // pinned, B * (sizeof(CtkRpgdBatchStep) + kstride) bytes: the n records of the step (or reset) being
+    CtkRpgdBatchStep* d_steps = nullptr;    // issued and, in the per-problem form of a step, the constants of those n problems right behind them
+    std::vector<int> count, adam_step;
+    std::vector<unsigned char> cur, ready;
+    size_t NHC() const { return (size_t)N * HC; }
+    int its(int p) const {                  // rpgd_iterations
+        const int first = cfg.warmup ? cfg.warmup_iterations : cfg.outer_its;
+        return count[(size_t)p] == 0 ? first : cfg.outer_its;
+    }
+    bool resamples(int p) const { return count[(size_t)p] % cfg.resamp_per == 0; }   // optimizer_rpgd.py:449
+    size_t needs(int p) const { return (resamples(p) && K < N) ? (size_t)(N - K) * PC : 0; }   // samples_needed of an RPGD handle
+};
+
+namespace {
+
+// the shared template of a launch's RolloutArgs (ctk_api.hip: make_args of an RPGD handle's descent without what the step records and descriptors supply)
+RolloutArgs rpgd_batch_args(const ctk_rpgd_batch* b) {
+    RolloutArgs a = batch_common_args(b);
+    a.P = b->H;
+    a.p_magic = ctk_magic_of(b->H);
+    a.identity_interp = b->cfg.period_interpolation_inducing_points == 1 ? 1 : 0;
+    a.interp = b->d_interp;
+    return a;
+}
+// what the launches take of the warm start's description: keep_k, P, the sampling constants, the interpolation table
+RpgdFusedWarm rpgd_batch_warm(const ctk_rpgd_batch* b) {
+    const ctk_config& c = b->cfg;
+    return RpgdFusedWarm{b->K, nullptr, b->P, 0, 0, c.shift_previous, c.sampling_distribution, 0, c.sample_whole_control_space, c.sample_stdev,
+                         c.sample_mean, c.sample_min, c.sample_max, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b->d_interp,
+                         nullptr, nullptr, nullptr, 0u};
+}
+
+constexpr int RPGD_BATCH_MAX_GRID_Y = 65535;   // problems of one launch: the grid's y limit, nothing else bounds it
+
+}  // namespace
+
+extern "C" {
+
+size_t ctk_rpgd_template_descent_lds(int environment, int mpc_horizon, int* tape_in_lds) {
+    if (tape_in_lds) *tape_in_lds = 0;
+    if (!env_info(environment) || mpc_horizon < 1) return 0;
+    bool fits = false;
+    const size_t lds = ctk_g_rpgd_descent_lds(environment, mpc_horizon, &fits);
+    if (tape_in_lds) *tape_in_lds = fits ? 1 : 0;
+    return lds;
+}
+
+const char* ctk_rpgd_batch_last_error(const ctk_rpgd_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+int ctk_rpgd_batch_size(const ctk_rpgd_batch* b) { return b ? b->B : 0; }
+size_t ctk_rpgd_batch_samples_needed(const ctk_rpgd_batch* b, int problem) { return (b && problem >= 0 && problem < b->B) ? b->needs(problem) : 0; }
+const char* ctk_rpgd_batch_dominant_kernel(const ctk_rpgd_batch* b) { return b ? b->dominant.c_str() : ""; }
+
+void ctk_rpgd_batch_destroy(ctk_rpgd_batch* b) { delete b; }
+
+int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_rpgd_batch** out) {
+    if (out) *out = nullptr;
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: NULL argument");
+    if (n_problems < 1) return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    const EnvInfo* einfo = nullptr;
+    if (int rc = check_config("ctk_rpgd_batch_create", cfg, &einfo)) return rc;
+    const int N = cfg->num_rollouts, H = cfg->mpc_horizon, HC = H * einfo->C;
+    if (cfg->optimizer != CTK_OPT_RPGD)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: an RPGD batch steps RPGD controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+                     ", num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + "); MPPI has ctk_batch_create, plain CEM ctk_cem_batch_create, the "
+                     "gradient variant (CTK_OPT_GRADIENT) and the other optimizers run as single handles (ctk_create)");
+    if (cfg->predictor != CTK_PRED_ODE)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: the batch kernel descends through the analytic (ODE) predictor only (cfg.predictor == " +
+                     std::to_string(cfg->predictor) + ", num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) +
+                     "); network predictors run as single handles (ctk_create)");
+    if (cfg->environment == CTK_ENV_CARTPOLE && cfg->generic_kernels == 0)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: CartPole's tuned descent (ctk_rpgd_descent, what a handle with generic_kernels == 0 runs) has no "
+                     "batch form; the template kernels do: set cfg.generic_kernels = 1, and compare with handles created the same way (num_rollouts " +
+                     std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ")");
+    if (N > CTK_RPGD_FUSED_MAX_N)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: num_rollouts " + std::to_string(N) + " exceeds " + std::to_string(CTK_RPGD_FUSED_MAX_N) +
+                     ", the population one workgroup holds (a problem's whole step runs in one workgroup); such a controller runs as a single handle (ctk_create)");
+    if (cfg->opt_keep_k > N)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: opt_keep_k " + std::to_string(cfg->opt_keep_k) + " exceeds num_rollouts " + std::to_string(N) +
+                     ": the plans a problem keeps are part of its population");
+    if (cfg->materialize_trajectories)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: materialize_trajectories is not built for a batch (num_rollouts " + std::to_string(N) +
+                     ", mpc_horizon " + std::to_string(H) + "): the logging rollout sits between descent and warm start, and the one launch has no seam for it; "
+                     "such a controller runs as a single handle (ctk_create)");
+    bool tape_in_lds = false;
+    const size_t lds = ctk_g_rpgd_descent_lds(cfg->environment, H, &tape_in_lds);
+    if (lds > 160 * 1024)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: mpc_horizon " + std::to_string(H) + " x " + std::to_string(einfo->C) + " inputs = " +
+                     std::to_string(HC) + " columns need " + std::to_string(lds) + " bytes of LDS without the state tape; a workgroup has 163840 (160 KiB)");
+    if (cfg->opt_keep_k < 1 || cfg->outer_its < 0 || cfg->resamp_per < 1 || cfg->shift_previous < 0 || (cfg->warmup && cfg->warmup_iterations < 0) ||
+        (cfg->sampling_distribution != 0 && cfg->sampling_distribution != 1))
+        return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: RPGD needs opt_keep_k >= 1, outer_its >= 0, resamp_per >= 1, shift_previous >= 0, "
+                     "warmup_iterations >= 0, sampling_distribution in {0,1}");
+    if (cfg->intermediate_steps != 1)
+        return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_rpgd_batch_create: the RPGD adjoint is built for intermediate_steps == 1 (given " + std::to_string(cfg->intermediate_steps) + ")");
+    if (cfg->adam_rule != 0 && cfg->adam_rule != 1)
+        return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_create: adam_rule must be 0 (the reference's torch ADAM) or 1 (tf.keras.optimizers.Adam)");
+
+    hipDeviceProp_t prop;
+    if (int rc = probe_device("ctk_rpgd_batch_create", cfg->device, &prop)) return rc;
+
+    BatchMade<ctk_rpgd_batch> made;
+    ctk_rpgd_batch* b = made.b;
+    batch_core_init(b, cfg, einfo, n_problems);
+    b->K = cfg->opt_keep_k;
+    b->P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
+    b->PC = b->P * einfo->C;
+    b->kcache.assign((size_t)n_problems * b->kstride, 0);
+    b->scratch_stride = tape_in_lds ? 0 : ctk_g_rpgd_scratch_floats(b->env, N, H);
+    b->count.assign((size_t)n_problems, 0); b->adam_step.assign((size_t)n_problems, 0);
+    b->cur.assign((size_t)n_problems, 0); b->ready.assign((size_t)n_problems, 0);
+    b->dominant = ctk_g_rpgd_batch_name(b->env);
+
+    if (int rc = batch_core_open(b)) return rc;
+    const size_t Bz = (size_t)n_problems, NHC = b->NHC();
+    for (int i = 0; i < 2; ++i) {
+        BHIP_CREATE(batch_dev_zero(b, &b->d_pop[i], Bz * NHC * sizeof(float)));
+        BHIP_CREATE(batch_dev_zero(b, &b->d_m[i], Bz * NHC * sizeof(float)));
+        BHIP_CREATE(batch_dev_zero(b, &b->d_v[i], Bz * NHC * sizeof(float)));
+        BHIP_CREATE(batch_dev_zero(b, &b->d_ages[i], Bz * N * sizeof(float)));
+    }
+    BHIP_CREATE(batch_dev_zero(b, &b->d_J, Bz * N * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_idx, Bz * N * sizeof(int)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_unom, Bz * HC * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_scratch, Bz * b->scratch_stride * sizeof(float)));
+    BHIP_CREATE(batch_dev_zero(b, &b->d_desc, Bz * sizeof(CtkRpgdBatchDesc)));
+    const size_t steps_bytes = Bz * (sizeof(CtkRpgdBatchStep) + b->kstride);   // the records, then room for as many elements of constants
+    BHIP_CREATE(batch_dev_zero(b, &b->d_steps, steps_bytes));
+    BHIP_CREATE(batch_pinned_zero(b, &b->h_steps, steps_bytes));
+
+    std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, b->P);
+    BHIP_CREATE(batch_dev_zero(b, &b->d_interp, (size_t)H * sizeof(InterpEntry)));
+    BHIP_CREATE(hipMemcpyAsync(b->d_interp, tab.data(), (size_t)H * sizeof(InterpEntry), hipMemcpyHostToDevice, b->stream));
+    const std::vector<float> bc = adam_bias_corrections(cfg->adam_beta_1, cfg->adam_beta_2);   // the table of a handle (ctk_host.h)
+    b->bc_len = (int)(bc.size() / 2);
+    BHIP_CREATE(batch_dev_zero(b, &b->d_bc, bc.size() * sizeof(float)));
+    BHIP_CREATE(hipMemcpyAsync(b->d_bc, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+
+    std::vector<CtkRpgdBatchDesc> desc(Bz);
+    for (int p = 0; p < n_problems; ++p) {
+        const size_t z = (size_t)p;
+        const uint64_t seed = batch_seed(cfg, seeds, p);
+        CtkRpgdBatchDesc& d = desc[z];
+        for (int i = 0; i < 2; ++i) {
+            d.pop[i] = b->d_pop[i] + z * NHC; d.m[i] = b->d_m[i] + z * NHC; d.v[i] = b->d_v[i] + z * NHC;
+            d.ages[i] = b->d_ages[i] + z * N;
+        }
+        d.J = b->d_J + z * N; d.idx = b->d_idx + z * N; d.u_nom = b->d_unom + z * HC;
+        d.u_dev = b->u(p); d.u_host = b->h_u_dev + z * 16;
+        d.scratch = b->d_scratch + z * b->scratch_stride;
+        d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
+    }
+    BHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkRpgdBatchDesc), hipMemcpyHostToDevice, b->stream));
+    BHIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
+    *out = made.release();
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_reset(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* draws, int draws_loc) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_rpgd_batch_reset", n_ids, ids, &n)) return rc;
+    const size_t per = (size_t)b->N * b->PC;           // sample_actions of a whole population: [N,P,C] per problem
+    const float* d_draws = nullptr;
+    if (draws_loc != CTK_LOC_NONE) {
+        if (draws == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "draws pointer is NULL but draws_loc != CTK_LOC_NONE");
+        if (draws_loc != CTK_LOC_DEVICE && draws_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad draws_loc");
+    }
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    if (draws_loc == CTK_LOC_DEVICE) d_draws = draws;
+    else if (draws_loc == CTK_LOC_HOST) {
+        if (int rc = batch_stage(b, draws, (size_t)n * per)) return rc;
+        d_draws = b->d_samples;
+    }
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        CtkRpgdBatchStep& q = b->h_steps[j];
+        q = CtkRpgdBatchStep{};
+        q.id = p; q.call = b->call[(size_t)p]; q.cur = b->cur[(size_t)p];
+        q.draws = d_draws ? d_draws + (size_t)j * per : nullptr;
+    }
+    BHIP_TRY(b, hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkRpgdBatchStep), hipMemcpyHostToDevice, b->stream));
+    const RolloutArgs a = rpgd_batch_args(b);
+    const RpgdFusedWarm f = rpgd_batch_warm(b);
+    for (int done = 0; done < n;) {                    // ONE launch for the call (more only past the grid's y limit)
+        const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - done);
+        BHIP_TRY(b, ctk_launch_rpgd_batch_reset(b->stream, a, f, b->d_desc, b->d_steps + done, cnt));
+        done += cnt;
+    }
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    for (int j = 0; j < n; ++j) {                      // rpgd_reset of a handle: parameters, the sequence number and the buffer index stay
+        const size_t z = (size_t)(ids ? ids[j] : j);
+        b->count[z] = 0; b->adam_step[z] = 0; b->ready[z] = 1;
+        ++b->call[z];
+    }
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples,
+                        size_t n_samples, int samples_loc, float* u_out) {
+    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_rpgd_batch_step", n_ids, ids, &n)) return rc;
+    size_t need = 0;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        if (!b->ready[(size_t)p])
+            return bfail(b, CTK_ERR_STATE, "ctk_rpgd_batch_step: problem " + std::to_string(p) + " was never reset: call ctk_rpgd_batch_reset (optimizer_reset) "
+                         "before its first step; nothing was launched");
+        need += b->needs(p);
+    }
+    if (samples_loc != CTK_LOC_NONE) {
+        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+        if (n_samples != need)                          // refused before a sample is read
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: " + std::to_string(n_samples) + " samples given, the listed problems need " +
+                         std::to_string(need) + " (one [num_rollouts - opt_keep_k, P, C] block for every listed problem whose ctk_rpgd_batch_samples_needed is "
+                         "non-zero, in id order); nothing was launched");
+        if (need != 0 && samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+    }
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // behind the checks of `samples`, as in the CEM step (the MPPI step: ahead of them, by history)
+    const float* d_s = nullptr;                        // the first block; the blocks follow one another in the order of the listed problems that draw
+    if (samples_loc == CTK_LOC_DEVICE && need) d_s = samples;
+    else if (samples_loc == CTK_LOC_HOST && need) {
+        if (int rc = batch_stage(b, samples, need)) return rc;
+        d_s = b->d_samples;
+    }
+    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es)
+    size_t off = 0;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        const size_t z = (size_t)p;
+        CtkRpgdBatchStep& q = b->h_steps[j];
+        q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.cur = b->cur[z];
+        q.iters = b->its(p); q.t0 = b->adam_step[z]; q.resample = b->resamples(p) ? 1 : 0;
+        const size_t cnt = b->needs(p);
+        q.draws = (d_s && cnt) ? d_s + off : nullptr;
+        off += d_s ? cnt : 0;
+        q.pad = 0;
+        batch_record_io(b, q, j, s, u_prev);
+    }
+    const unsigned char* d_ksteps = nullptr;           // the per-problem form: the constants behind the records, in the same transfer
+    hipError_t le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(CtkRpgdBatchStep), b->h_steps, b->d_steps, &d_ksteps);
+    const RolloutArgs a = rpgd_batch_args(b);
+    const RpgdFusedWarm f = rpgd_batch_warm(b);
+    const ctk_config& c = b->cfg;
+    int launched = 0;                                  // consecutive launches only past the grid's y limit; a problem never spans launches
+    while (le == hipSuccess && launched < n) {
+        const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - launched);
+        le = ctk_launch_g_rpgd_batch(b->stream, b->env, a, b->params, c.dt, c.intermediate_steps, c.learning_rate, c.adam_beta_1, c.adam_beta_2,
+                                     c.adam_epsilon, c.gradmax_clip, c.adam_rule == 1 ? 1 : 0, b->d_bc, b->bc_len, f, b->d_desc, b->d_steps + launched, cnt,
+                                     d_ksteps ? d_ksteps + (size_t)launched * b->kstride : nullptr);
+        if (le == hipSuccess) launched += cnt;
+    }
+    // h_steps is both the source of the transfer above and, below, the host's memory of id / seq / iters for the bookkeeping: that holds
+    // because the call is synchronous (nothing refills h_steps before it returns); an asynchronous step would need its own copy.
+    const std::string late = batch_poll(b, ids, launched);
+    for (int j = 0; j < launched; ++j) {               // on purpose: a problem never issued consumes no sequence number, nothing of it advances
+        const int p = b->h_steps[j].id;                // (the MPPI and CEM steps consume seq for every listed problem)
+        const size_t z = (size_t)p;
+        ++b->seq[z];
+        b->adam_step[z] += b->h_steps[j].iters;        // as rpgd_descent / rpgd_step: with the launch
+        b->cur[z] ^= 1; ++b->count[z];
+        if (reinterpret_cast<volatile uint32_t*>(b->slot(p))[1] != b->h_steps[j].seq) continue;   // never published (a device fault): ctk_api.hip's finish_step
+        ++b->call[z];                                  // returns before it advances the Philox position or reads u (as CEM; MPPI advances it regardless, by history)
+        batch_read_u(b, p, j, u_out);                  // no error word to read here: this kernel has no in-launch hand-off (MPPI and CEM have)
+    }
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_rpgd_batch_step: ") + hipGetErrorString(le));
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_rpgd_batch_step: the step finished without publishing the result of problem(s) " + late);
+    return CTK_OK;
+}
+
+int ctk_rpgd_batch_read(ctk_rpgd_batch* b, int problem, int buffer, float* dst, size_t cap) {
+    if (int rc = batch_read_check(b, "ctk_rpgd_batch_read", problem, dst)) return rc;
+    const size_t z = (size_t)problem, N = (size_t)b->N, NHC = b->NHC();
+    const int cur = b->cur[z];
+    const float* src = nullptr; size_t n = 0; bool is_int = false;
+    switch (buffer) {                                  // ctk_api.hip: locate_buffer of an RPGD handle
+        case CTK_BUF_Q: src = b->d_pop[cur ^ 1] + z * NHC; n = NHC; break;
+        case CTK_BUF_PLAN: src = b->d_pop[cur] + z * NHC; n = NHC; break;
+        case CTK_BUF_ADAM_M: src = b->d_m[cur] + z * NHC; n = NHC; break;
+        case CTK_BUF_ADAM_V: src = b->d_v[cur] + z * NHC; n = NHC; break;
+        case CTK_BUF_AGES: src = b->d_ages[cur] + z * N; n = N; break;
+        case CTK_BUF_AGES_LOGGED: src = b->d_ages[cur ^ 1] + z * N; n = N; break;
+        case CTK_BUF_J: src = b->d_J + z * N; n = N; break;
+        case CTK_BUF_U_NOM: src = b->d_unom + z * b->HC; n = (size_t)b->HC; break;
+        case CTK_BUF_BEST_IDX: src = reinterpret_cast<const float*>(b->d_idx + z * N); n = (size_t)b->K; is_int = true; break;
+        default: return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_read: an RPGD batch has Q, J, U_NOM, PLAN, ADAM_M, ADAM_V, AGES, AGES_LOGGED and BEST_IDX");
+    }
+    return batch_read_out(b, "ctk_rpgd_batch_read", src, n, is_int, dst, cap);
+}
+
+// the state of a problem (ctk_state_size of an RPGD handle): population, Adam moments, ages, last output; Adam step and step count.
+// A problem whose state was set counts as reset.
+static BatchState rpgd_batch_state(ctk_rpgd_batch* b, int p) {
+    const size_t z = (size_t)p, N = (size_t)b->N, NHC = b->NHC();
+    const int cur = b->cur[z];
+    return {{{b->d_pop[cur] + z * NHC, NHC}, {b->d_m[cur] + z * NHC, NHC}, {b->d_v[cur] + z * NHC, NHC}, {b->d_ages[cur] + z * N, N}, {b->u(p), (size_t)b->C}},
+            {&b->adam_step[z], &b->count[z]}, &b->ready[z]};
+}
+int ctk_rpgd_batch_get_state(ctk_rpgd_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_rpgd_batch_get_state", problem, dst, cap, true, true, rpgd_batch_state); }
+int ctk_rpgd_batch_set_state(ctk_rpgd_batch* b, int problem, const float* src, size_t n) {
+    return batch_state_io(b, "ctk_rpgd_batch_set_state", problem, const_cast<float*>(src), n, false, true, rpgd_batch_state);
+}
+
+int ctk_rpgd_batch_set_param(ctk_rpgd_batch* b, int id, float value) { return batch_set_param(b, "ctk_rpgd_batch_set_param", id, value); }
+int ctk_rpgd_batch_get_param(const ctk_rpgd_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
+int ctk_rpgd_problem_set_param(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
+    bool flipped = false;
+    const int rc = batch_problem_set_param(b, "ctk_rpgd_problem_set_param", n_ids, ids, id, values, &flipped);
+    if (flipped) b->dominant = ctk_g_rpgd_batch_name(b->env, true);
+    return rc;
+}
+int ctk_rpgd_problem_get_param(const ctk_rpgd_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
+int ctk_rpgd_problem_params_differ(const ctk_rpgd_batch* b) { return batch_params_differ(b); }
+int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
+int ctk_rpgd_batch_rng_set_position(ctk_rpgd_batch* b, int problem, uint32_t call) {
+    return batch_rng_set_position(b, "ctk_rpgd_batch_rng_set_position", problem, call);
+}
+
+}  // extern "C"

@@ -26,7 +26,7 @@
 // include/ctk_hip.h gives the batch's opaque C type the name ctk_cem_batch; in C++ a type and a template cannot share a name in one scope,
 // and the kernel template below carries that name (it is what a kernel trace prints).  This translation unit never touches the C type, so
 // the header's declarations see it under another name here.  (A different struct TAG in the header would not help: the typedef name itself is
-// what collides.)  Whoever needs the C type in this file must move the code that does into ctk_api.hip; the guard below keeps a second
+// what collides.)  Whoever needs the C type in this file must move the code that does into ctk_batch.hip; the guard below keeps a second
 // definition of the name, from any header added here later, from passing silently.
 #ifdef ctk_cem_batch
 #error "ctk_cem_batch is already a macro: the renaming below would hide it"
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(CF_BLOCK) void ctk_cem_fused(const float* __restric
 // exactly when its nblk workgroups are resident at the same time.  ctk_cem_fused guarantees that by nblk <= CTK_CEM_FUSED_MAX_BLOCKS <=
 // CUs and LDS <= 128 KiB: a CU without a workgroup of this kernel admits one, so while a workgroup is still pending fewer than nblk are
 // resident, some CU holds none, and the pending one is placed.  The host keeps the same guarantee for a launch of this kernel
-// (ctk_api.hip: ctk_cem_batch_create): problems * nblk <= CUs.  While any workgroup of the launch is pending fewer than CUs workgroups are
+// (ctk_batch.hip: ctk_cem_batch_create): problems * nblk <= CUs.  While any workgroup of the launch is pending fewer than CUs workgroups are
 // resident, so some CU holds none and admits it — whatever the dispatch order or placement, all workgroups of the launch become
 // co-resident, and with them all workgroups of every problem.  Problems of one launch may loop a different number of times (its is per
 // record): a problem that finishes early only frees CUs.  Like the single kernel's, the argument assumes that the CUs are this launch's

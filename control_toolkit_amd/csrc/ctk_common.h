@@ -1,4 +1,4 @@
-// ctk_common.h — types shared by the host C-ABI (ctk_api.hip) and the device kernels.
+// ctk_common.h — types shared by the host C-ABI (ctk_api.hip, ctk_batch.hip) and the device kernels.
 // gfx950 only: wave = 64 lanes, no portability layer.
 #pragma once
 #include <hip/hip_runtime.h>

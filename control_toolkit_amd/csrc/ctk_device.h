@@ -271,7 +271,7 @@ CTK_DEV void publish_u_vec(float* u_dev, float* u_host, const float* u, int C, u
 
 // ---- the publish of a kernel that is LAUNCHED once per step and whose end orders everything else -------------------------------
 // When a step returns, the host has read the 8-byte word {u, seq}, the error words behind it and (C > 1) the vector at floats 4.. —
-// nothing else (ctk_api.hip: finish_step and the batch steps' completion loops).  Every other reader of a handle's buffers is an API
+// nothing else (ctk_api.hip: finish_step; ctk_batch.hip: the batch steps' completion loops).  Every other reader of a handle's buffers is an API
 // entry ordered behind the launch on the handle's stream, and the kernel's END writes the caches back for those.  So the word the host
 // spins on needs no release: publish_u's system-scope release is a write-back of the whole L2 plus a drain of the wave's stores
 // (buffer_wbl2 sc0 sc1; s_waitcnt vmcnt(0)) on the path between u and the host.  Here every word the host reads is a RELAXED

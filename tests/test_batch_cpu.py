@@ -137,6 +137,24 @@ def test_library_refuses_by_configuration_before_it_probes_the_device():
     assert rc == 1 and not made and "size mismatch" in msg
 
 
+def test_a_refused_creation_is_read_through_every_last_error():
+    """the text of a refused creation is ONE thread-local of the library, whichever source file the family's host code is in: after a
+    refused ctk_rpgd_batch_create every *_last_error(NULL) returns that text, and a refused ctk_create replaces it in all of them"""
+    from control_toolkit_amd._capi import load_library
+    lib, out = load_library(), ctypes.c_void_p()
+    readers = ("ctk_rpgd_batch_last_error", "ctk_cem_batch_last_error", "ctk_batch_last_error", "ctk_mlp_batch_last_error", "ctk_last_error")
+    cfg = make_cfg()
+    assert lib.ctk_rpgd_batch_create(ctypes.byref(cfg), 0, None, ctypes.byref(out)) == 2 and not out.value
+    texts = [getattr(lib, r)(None).decode() for r in readers]
+    assert texts[0].startswith("ctk_rpgd_batch_create: a batch holds at least one problem (n_problems == 0)")
+    assert texts == [texts[0]] * len(readers)
+    bad = make_cfg(struct_size=8)
+    assert lib.ctk_create(ctypes.byref(bad), ctypes.byref(out)) == 1 and not out.value
+    texts = [getattr(lib, r)(None).decode() for r in readers]
+    assert texts[0] == "ctk_create: ctk_config size mismatch (ABI)"
+    assert texts == [texts[0]] * len(readers)
+
+
 def test_valid_batch_without_a_gpu_fails_loudly():
     import torch
     from control_toolkit_amd import CtkMppiBatch, CtkError

@@ -370,3 +370,37 @@ def test_dominant_kernel_names():
     e.step(np.array([0.0, 0.0, 2.6, 0.0], np.float32))
     assert e.dominant_kernel() == "ctk_cem_fused<0, false>"
     e.close()
+
+
+# ---- what a batch allocates: a staging buffer that grows, destroy, create again ------------------------------------------------------------------
+def test_state_survives_destroy_and_create_after_buffers_grew():
+    """The staging buffer grows (host draws for one problem, then for all); then every problem's state is read, the batch destroyed,
+    created again from the same seeds and given the states and Philox positions back: its next step, by the in-kernel sampler, equals
+    bit for bit that of a batch that took the same steps and was never destroyed."""
+    kw = dict(seeds=[7, 8, 9], **common_kw("one_workgroup", False))
+    rng = np.random.default_rng(45)
+    s, s_next = first_states(rng, 3, 4), first_states(rng, 3, 4)
+
+    def used(batch):
+        its = batch.samples_needed(0) // (batch.N * batch.H * batch.C)
+        draws = np.random.default_rng(46).standard_normal((3, its, batch.N, batch.H, batch.C)).astype(np.float32)
+        batch.step(s[1:2], draws[:1], ids=[1])
+        batch.step(s, draws)
+        return batch
+
+    a, ref = used(CtkCemBatch(3, **kw)), used(CtkCemBatch(3, **kw))
+    saved = [(a.get_state(q), a.rng_position(q)) for q in range(3)]
+    a.close()
+    a = CtkCemBatch(3, **kw)
+    for q, (state, position) in enumerate(saved):
+        np.testing.assert_array_equal(state, ref.get_state(q))
+        a.set_state(q, state)
+        a.set_rng_position(q, position)
+    np.testing.assert_array_equal(a.step(s_next), ref.step(s_next))
+    for q in range(3):
+        for name in BUFFERS:
+            np.testing.assert_array_equal(a.read(name, q), ref.read(name, q), err_msg=f"{name} of problem {q}")
+        np.testing.assert_array_equal(a.get_state(q), ref.get_state(q), err_msg=f"state vector of problem {q}")
+        assert a.rng_position(q) == ref.rng_position(q)
+    a.close()
+    ref.close()

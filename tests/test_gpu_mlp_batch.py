@@ -403,3 +403,44 @@ def test_weight_and_id_refusals():
     with pytest.raises(CtkError, match="ctk_mlp_batch_read: trajectories not materialised"):
         b2.read("TRAJ", 0)
     b2.close()
+
+
+# ---- what a batch allocates: buffers that grow, destroy, create again --------------------------------------------------------------------------
+def test_state_survives_destroy_and_create_after_buffers_grew():
+    """The staging buffer grows (host draws for one problem, then for all), the run buffer grows (a run of 2 steps, of 5, episodes of 3);
+    then every problem's state is read, the batch destroyed, created again from the same seeds and given the weights, states and Philox
+    positions back: its next step, by the in-kernel sampler, equals bit for bit that of a batch that took the same steps and was never
+    destroyed."""
+    N, H, p = SIZES[0]
+    kw = dict(seeds=[7, 8, 9], num_rollouts=N, mpc_horizon=H, dt=0.02, period_interpolation_inducing_points=p)
+    w = np.stack([weights(100 + q) for q in range(3)])
+    rng = np.random.default_rng(43)
+    s, s_next = first_states(rng, 3), first_states(rng, 3)
+
+    def used(batch):
+        batch.set_problem_weights(w)
+        draws = np.random.default_rng(44).standard_normal((3, N, batch.samples_needed() // N, 1)).astype(np.float32)
+        batch.step(s[1:2], draws[:1], ids=[1])
+        batch.step(s, draws)
+        for steps in (2, 5):
+            batch.closed_loop.run(s, steps)
+        batch.closed_loop.episodes(s, 3)
+        return batch
+
+    a, ref = used(CtkMppiMlpBatch(3, **kw)), used(CtkMppiMlpBatch(3, **kw))
+    saved = [(a.get_state(q), a.rng_position(q)) for q in range(3)]
+    a.close()
+    a = CtkMppiMlpBatch(3, **kw)
+    a.set_problem_weights(w)
+    for q, (state, position) in enumerate(saved):
+        np.testing.assert_array_equal(state, ref.get_state(q))
+        a.set_state(q, state)
+        a.set_rng_position(q, position)
+    np.testing.assert_array_equal(a.step(s_next), ref.step(s_next))
+    for q in range(3):
+        for name in ("U_NOM", "J"):
+            np.testing.assert_array_equal(a.read(name, q), ref.read(name, q), err_msg=f"{name} of problem {q}")
+        np.testing.assert_array_equal(a.get_state(q), ref.get_state(q), err_msg=f"state vector of problem {q}")
+        assert a.rng_position(q) == ref.rng_position(q)
+    a.close()
+    ref.close()

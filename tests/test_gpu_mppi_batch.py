@@ -324,3 +324,40 @@ def test_dominant_kernel_names():
     e.step(np.zeros(4, np.float32))
     assert e.dominant_kernel() == "ctk_mppi_rollout<0, 0, false, false>"
     e.close()
+
+
+# ---- 7. what a batch allocates: buffers that grow, destroy, create again --------------------------------------------------------------------------
+def test_state_survives_destroy_and_create_after_buffers_grew():
+    """The staging buffer grows (host draws for one problem, then for all), the run buffer grows (a run of 2 steps, of 5, episodes of 3);
+    then every problem's state is read, the batch destroyed, created again from the same seeds and given the states and Philox positions
+    back: its next step, by the in-kernel sampler, equals bit for bit that of a batch that took the same steps and was never destroyed."""
+    env, N, H, p, extra, _ = CONFIGS["cartpole_small"]
+    kw = dict(seeds=[7, 8, 9], num_rollouts=N, mpc_horizon=H, dt=0.02, period_interpolation_inducing_points=p, environment=env, **extra)
+    rng = np.random.default_rng(41)
+    s, s_next = first_states(rng, 3, 4), first_states(rng, 3, 4)
+
+    def used(batch):
+        draws = np.random.default_rng(42).standard_normal((3, N, batch.samples_needed() // (N * batch.C), batch.C)).astype(np.float32)
+        batch.step(s[1:2], draws[:1], ids=[1])
+        batch.step(s, draws)
+        for steps in (2, 5):
+            batch.closed_loop.run(s, steps)
+        batch.closed_loop.episodes(s, 3)
+        return batch
+
+    a, ref = used(CtkMppiBatch(3, **kw)), used(CtkMppiBatch(3, **kw))
+    saved = [(a.get_state(q), a.rng_position(q)) for q in range(3)]
+    a.close()
+    a = CtkMppiBatch(3, **kw)
+    for q, (state, position) in enumerate(saved):
+        np.testing.assert_array_equal(state, ref.get_state(q))
+        a.set_state(q, state)
+        a.set_rng_position(q, position)
+    np.testing.assert_array_equal(a.step(s_next), ref.step(s_next))
+    for q in range(3):
+        for name in ("U_NOM", "J"):
+            np.testing.assert_array_equal(a.read(name, q), ref.read(name, q), err_msg=f"{name} of problem {q}")
+        np.testing.assert_array_equal(a.get_state(q), ref.get_state(q), err_msg=f"state vector of problem {q}")
+        assert a.rng_position(q) == ref.rng_position(q)
+    a.close()
+    ref.close()

@@ -368,3 +368,39 @@ def test_dominant_kernel_names():
         assert batch.dominant_kernel() == f"ctk_g_rpgd_batch<{env_id}>"
         assert handles[0].dominant_kernel() == f"ctk_g_rpgd_descent<{env_id}>"          # the handle the contract refers to
         close_all(batch, handles)
+
+
+# ---- what a batch allocates: a staging buffer that grows, destroy, create again ------------------------------------------------------------------
+def test_state_survives_destroy_and_create_after_buffers_grew():
+    """The staging buffer grows (host draws for one problem, then for all); then every problem's state is read, the batch destroyed,
+    created again from the same seeds and given the states and Philox positions back: its next step, by the in-kernel sampler, equals
+    bit for bit that of a batch that took the same steps and was never destroyed."""
+    kw = dict(seeds=[11, 14, 17], **CONFIGS["cartpole_small"]())
+    rng = np.random.default_rng(47)
+    s, s_next = states(rng, 3, 4), states(rng, 3, 4)
+
+    def used(batch):
+        draws = np.random.default_rng(48)
+        batch.reset()
+        for ids in ([1], [0, 1, 2]):
+            blocks = [draw_block(draws, batch, batch.N - batch.K).ravel() for q in ids if batch.samples_needed(q)]
+            assert blocks                                   # the step after a reset resamples: there are draws to stage
+            batch.step(s[ids], np.concatenate(blocks), ids=ids)
+        return batch
+
+    a, ref = used(CtkRpgdBatch(3, **kw)), used(CtkRpgdBatch(3, **kw))
+    saved = [(a.get_state(q), a.rng_position(q)) for q in range(3)]
+    a.close()
+    a = CtkRpgdBatch(3, **kw)
+    for q, (state, position) in enumerate(saved):
+        np.testing.assert_array_equal(state, ref.get_state(q))
+        a.set_state(q, state)                               # marks the problem reset
+        a.set_rng_position(q, position)
+    np.testing.assert_array_equal(a.step(s_next), ref.step(s_next))
+    for q in range(3):
+        for name in BUFFERS:
+            np.testing.assert_array_equal(a.read(name, q), ref.read(name, q), err_msg=f"{name} of problem {q}")
+        np.testing.assert_array_equal(a.get_state(q), ref.get_state(q), err_msg=f"state vector of problem {q}")
+        assert a.rng_position(q) == ref.rng_position(q)
+    a.close()
+    ref.close()
