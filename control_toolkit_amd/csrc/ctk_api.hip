@@ -154,6 +154,9 @@ struct ctk_handle {
     std::unordered_map<const float*, const float*> res_follow;   // sample buffer -> the buffer that followed it last time
     const float* res_prev_samples = nullptr;
     bool res_readahead = false;           // ctk_resident_enable(h, 2, ...): the caller's sample buffers are immutable while enabled, so they may be read ahead
+    // every device and pinned allocation of the handle, entered where it is made (ctk_host.h); behind the fields the step path reads
+    Owner own;
+    ~ctk_handle();                        // ctk_destroy is `delete h`, and so is the end of a failed creation
 };
 
 namespace {
@@ -514,13 +517,6 @@ std::vector<float> permute_gru_weights_g(const float* raw, int S, int C) {
     return out;
 }
 
-template <class T>
-int dev_alloc(ctk_handle* h, T** p, size_t n) {
-    HIP_TRY(h, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-    HIP_TRY(h, hipMemsetAsync(*p, 0, (n ? n : 1) * sizeof(T), h->stream));
-    return CTK_OK;
-}
-
 int cem_iterations(const ctk_handle* h) {   // optimizer_cem_tf.py:92
     return (h->cfg.warmup && h->count == 0) ? h->cfg.warmup_iterations : h->cfg.cem_outer_it;
 }
@@ -550,12 +546,7 @@ int resolve_samples(ctk_handle* h, const float* samples, int loc, size_t n, cons
     if (samples == nullptr) return fail(h, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
     if (loc == CTK_LOC_DEVICE) { *out = samples; return CTK_OK; }
     if (loc != CTK_LOC_HOST) return fail(h, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
-    if (n > h->samples_cap) {
-        if (h->d_samples) HIP_TRY(h, hipFree(h->d_samples));
-        h->d_samples = nullptr; h->samples_cap = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->d_samples, n * sizeof(float)));
-        h->samples_cap = n;
-    }
+    HIP_TRY(h, h->own.grow_dev(h->d_samples, h->samples_cap, n));
     HIP_TRY(h, hipMemcpyAsync(h->d_samples, samples, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     *out = h->d_samples;
     return CTK_OK;
@@ -660,6 +651,13 @@ size_t log_slot_floats(const ctk_handle* h, int i) {
 }
 
 // append this step's tensors to the rings: one launch, behind the step on the stream (the result is out already)
+// the four rings leave the owner and are freed; the first error, if any
+hipError_t log_release(ctk_handle* h) {
+    hipError_t first = hipSuccess;
+    for (float*& ring : h->d_log) { const hipError_t e = h->own.free_dev(ring); if (first == hipSuccess) first = e; }
+    return first;
+}
+
 int log_step(ctk_handle* h) {
     static const int which[4] = {CTK_BUF_Q, CTK_BUF_J, CTK_BUF_TRAJ, CTK_BUF_AGES_LOGGED};
     const size_t slot = h->log_count % h->log_cap;
@@ -1301,6 +1299,19 @@ int fill_const(ctk_handle* h, float* d, float v, int n) {
 
 }  // namespace
 
+// everything a handle opened: no HIP call for one that opened nothing.  Outside the owner are only the peers' IPC mappings
+// (ctk_p2p_close) and the profiling events.
+inline ctk_handle::~ctk_handle() {
+    if (!stream && own.empty() && events.empty() && p2p_world == 0) return;
+    hipSetDevice(cfg.device);
+    (void)resident_quiesce(this);
+    hipStreamSynchronize(stream);   // also correct for the null (default) stream handed in by ctk_set_stream
+    for (auto& e : events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
+    ctk_p2p_close(this);
+    own.release();
+    if (own_stream && stream) hipStreamDestroy(stream);
+}
+
 // =============================================================================================
 extern "C" {
 
@@ -1377,7 +1388,8 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     hipDeviceProp_t prop;
     if (int rc = probe_device("ctk_create", cfg->device, &prop)) return rc;
 
-    ctk_handle* h = new ctk_handle();
+    Creating<ctk_handle> made;
+    ctk_handle* h = made.p;
     h->cfg = *cfg;
     h->variant = variant;
     h->N = cfg->num_rollouts; h->H = cfg->mpc_horizon;
@@ -1389,15 +1401,12 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     default_params(h->env, h->params);
     refresh_constants(h);
 
-    auto bail = [&](int rc) { g_create_error = h->err; ctk_destroy(h); return rc; };
-#define TRY_CREATE(expr) do { int _rc = (expr); if (_rc) return bail(_rc); } while (0)
-#define HIP_CREATE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(_e); return bail(CTK_ERR_HIP); } } while (0)
-
     HIP_CREATE(hipSetDevice(cfg->device));
     HIP_CREATE(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = true;
 
     const size_t N = h->N, H = h->H, P = h->P, HC = h->HC, PC = h->PC;
+    auto zeroed = [h](auto** p, size_t n) { return h->own.dev_zero(p, n * sizeof(**p), h->stream); };   // n zeroed elements, entered in the owner
     const bool descends = cfg->optimizer == CTK_OPT_RPGD || variant == CTK_OPT_CEM_NAIVE_GRAD || variant == CTK_OPT_CEM_GRAD_BHARADHWAJ;
     // LDS budget of the rollout tiles (one wave per block): 64 * stride * 4 B <= 160 KiB
     {
@@ -1408,73 +1417,72 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
         else if (generic) lds = descends ? ctk_g_rpgd_descent_lds(h->env, (int)H, nullptr) : ctk_g_rollout_lds(cols, (int)H, h->C);
         else lds = cfg->optimizer == CTK_OPT_MPPI ? ctk_mppi_rollout_lds((int)P, (int)H, cfg->predictor, (int)N)
                  : descends ? ctk_rpgd_descent_lds(cfg->predictor, (int)H, nullptr) : ctk_affine_rollout_lds((int)H, cfg->predictor);
-        if (lds > 160 * 1024) { h->err = "horizon too long for the LDS sample tiles (160 KiB per CU)"; return bail(CTK_ERR_UNSUPPORTED); }
+        if (lds > 160 * 1024) return fail(nullptr, CTK_ERR_UNSUPPORTED, "horizon too long for the LDS sample tiles (160 KiB per CU)");
     }
 
     std::vector<InterpEntry> tab = build_interp_table((int)H, interp ? cfg->period_interpolation_inducing_points : 1, (int)P);
-    TRY_CREATE(dev_alloc(h, &h->d_interp, H));
+    HIP_CREATE(zeroed(&h->d_interp, H));
     HIP_CREATE(hipMemcpyAsync(h->d_interp, tab.data(), H * sizeof(InterpEntry), hipMemcpyHostToDevice, h->stream));
     HIP_CREATE(hipStreamSynchronize(h->stream));   // tab goes out of scope below
 
-    TRY_CREATE(dev_alloc(h, &h->d_J, N));
-    TRY_CREATE(dev_alloc(h, &h->d_Q, N * HC));
-    if (cfg->materialize_trajectories) TRY_CREATE(dev_alloc(h, &h->d_traj, N * (H + 1) * h->S));
+    HIP_CREATE(zeroed(&h->d_J, N));
+    HIP_CREATE(zeroed(&h->d_Q, N * HC));
+    if (cfg->materialize_trajectories) HIP_CREATE(zeroed(&h->d_traj, N * (H + 1) * h->S));
     const size_t nblk = (size_t)mppi_block_parts(h);
     h->parts_cap = nblk * (2 + PC);
-    TRY_CREATE(dev_alloc(h, &h->d_parts, h->parts_cap));
-    TRY_CREATE(dev_alloc(h, &h->d_parts2, ((nblk + 31) / 32) * (2 + PC)));
-    TRY_CREATE(dev_alloc(h, &h->d_parts3, ((nblk + 1023) / 1024) * (2 + PC)));
-    TRY_CREATE(dev_alloc(h, &h->d_rec, 2 + PC));
-    TRY_CREATE(dev_alloc(h, &h->d_counter, 1));
+    HIP_CREATE(zeroed(&h->d_parts, h->parts_cap));
+    HIP_CREATE(zeroed(&h->d_parts2, ((nblk + 31) / 32) * (2 + PC)));
+    HIP_CREATE(zeroed(&h->d_parts3, ((nblk + 1023) / 1024) * (2 + PC)));
+    HIP_CREATE(zeroed(&h->d_rec, 2 + PC));
+    HIP_CREATE(zeroed(&h->d_counter, 1));
     if (ctk_ll_records_ok((int)nblk, (int)PC) && !std::getenv("CTK_NO_LL"))
-        TRY_CREATE(dev_alloc(h, &h->d_ll, nblk * (2 + PC)));
+        HIP_CREATE(zeroed(&h->d_ll, nblk * (2 + PC)));
     if (cfg->optimizer == CTK_OPT_CEM && variant != CTK_OPT_CEM_GMM && ctk_cem_fusable(cfg->predictor, (int)N, (int)HC) && !std::getenv("CTK_NO_CEM_FUSED"))
-        TRY_CREATE(dev_alloc(h, &h->d_cem_ll, ctk_cem_fused_ll_words((int)N, (int)HC)));   // tuned and template path alike
-    TRY_CREATE(dev_alloc(h, &h->d_unom[0], HC));
-    TRY_CREATE(dev_alloc(h, &h->d_unom[1], HC));
-    TRY_CREATE(dev_alloc(h, &h->d_std, HC));
+        HIP_CREATE(zeroed(&h->d_cem_ll, ctk_cem_fused_ll_words((int)N, (int)HC)));   // tuned and template path alike
+    HIP_CREATE(zeroed(&h->d_unom[0], HC));
+    HIP_CREATE(zeroed(&h->d_unom[1], HC));
+    HIP_CREATE(zeroed(&h->d_std, HC));
     if (variant == CTK_OPT_CEM_GMM) {
-        TRY_CREATE(dev_alloc(h, &h->d_mix, 4 * HC + 2));
-        TRY_CREATE(dev_alloc(h, &h->d_mix_label, (size_t)cfg->cem_best_k));
-        TRY_CREATE(dev_alloc(h, &h->d_plans, N * HC));
+        HIP_CREATE(zeroed(&h->d_mix, 4 * HC + 2));
+        HIP_CREATE(zeroed(&h->d_mix_label, (size_t)cfg->cem_best_k));
+        HIP_CREATE(zeroed(&h->d_plans, N * HC));
         h->gmm_two_launches = std::getenv("CTK_GMM_TWO_LAUNCH") != nullptr;
         h->gmm_in_rollout = cfg->predictor == CTK_PRED_ODE && !std::getenv("CTK_GMM_MATERIALIZE") &&
                             ctk_affine_rollout_mix_lds(h->env, (int)H) <= 160 * 1024;
     }
-    TRY_CREATE(dev_alloc(h, &h->d_base, HC));
-    TRY_CREATE(dev_alloc(h, &h->d_scale, HC));
-    TRY_CREATE(dev_alloc(h, &h->d_idx, N));
-    TRY_CREATE(dev_alloc(h, &h->d_u, CTK_MAX_INPUTS));
-    TRY_CREATE(dev_alloc(h, &h->d_weights, std::max<size_t>(1, weight_count(cfg->predictor, h->S, h->C, h->hid))));
-    TRY_CREATE(dev_alloc(h, &h->d_wperm, generic ? ctk_g_net_table_floats(wide_net ? NET_MLP64 : cfg->predictor == CTK_PRED_GRU ? CTK_PRED_GRU : CTK_PRED_MLP) + GRU_HIDDEN_FLOATS
+    HIP_CREATE(zeroed(&h->d_base, HC));
+    HIP_CREATE(zeroed(&h->d_scale, HC));
+    HIP_CREATE(zeroed(&h->d_idx, N));
+    HIP_CREATE(zeroed(&h->d_u, CTK_MAX_INPUTS));
+    HIP_CREATE(zeroed(&h->d_weights, std::max<size_t>(1, weight_count(cfg->predictor, h->S, h->C, h->hid))));
+    HIP_CREATE(zeroed(&h->d_wperm, generic ? ctk_g_net_table_floats(wide_net ? NET_MLP64 : cfg->predictor == CTK_PRED_GRU ? CTK_PRED_GRU : CTK_PRED_MLP) + GRU_HIDDEN_FLOATS
                                          : cfg->predictor == CTK_PRED_GRU ? (size_t)GRU_TABLE_FLOATS + GRU_HIDDEN_FLOATS
                                                                           : (size_t)64 * (MLP_FWD_PER_LANE + MLP_BWD_PER_LANE)));
-    HIP_CREATE(hipHostMalloc((void**)&h->h_u, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(h->h_u, 0, 64);
+    HIP_CREATE(h->own.pinned_zero(&h->h_u, 64, hipHostMallocMapped | hipHostMallocCoherent));
     HIP_CREATE(hipHostGetDevicePointer((void**)&h->h_u_dev, h->h_u, 0));
     h->rp_pers.err_word = reinterpret_cast<uint32_t*>(h->h_u_dev) + 2;
 
     if (descends) {
         for (int b = 0; b < 2; ++b) {
-            TRY_CREATE(dev_alloc(h, &h->d_pop[b], N * HC));
-            TRY_CREATE(dev_alloc(h, &h->d_m[b], N * HC));
-            TRY_CREATE(dev_alloc(h, &h->d_v[b], N * HC));
-            TRY_CREATE(dev_alloc(h, &h->d_ages[b], N));
+            HIP_CREATE(zeroed(&h->d_pop[b], N * HC));
+            HIP_CREATE(zeroed(&h->d_m[b], N * HC));
+            HIP_CREATE(zeroed(&h->d_v[b], N * HC));
+            HIP_CREATE(zeroed(&h->d_ages[b], N));
         }
         const std::vector<float> bc = adam_bias_corrections(cfg->adam_beta_1, cfg->adam_beta_2);   // ctk_host.h
         h->bc_len = (int)(bc.size() / 2);
         if (cfg->materialize_trajectories) {   // the logging rollout of the descended plans (rpgd_materialize): u = 0 + plan * 1
-            TRY_CREATE(dev_alloc(h, &h->d_Jlog, N));
+            HIP_CREATE(zeroed(&h->d_Jlog, N));
             std::vector<float> zo(2 * HC, 0.0f);
             for (size_t i = 0; i < HC; ++i) zo[HC + i] = 1.0f;
             HIP_CREATE(hipMemcpyAsync(h->d_base, zo.data(), HC * sizeof(float), hipMemcpyHostToDevice, h->stream));
             HIP_CREATE(hipMemcpyAsync(h->d_scale, zo.data() + HC, HC * sizeof(float), hipMemcpyHostToDevice, h->stream));
             HIP_CREATE(hipStreamSynchronize(h->stream));
         }
-        TRY_CREATE(dev_alloc(h, &h->d_bc, bc.size()));
+        HIP_CREATE(zeroed(&h->d_bc, bc.size()));
         HIP_CREATE(hipMemcpyAsync(h->d_bc, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
         HIP_CREATE(hipStreamSynchronize(h->stream));
-        TRY_CREATE(dev_alloc(h, &h->d_scratch, !generic ? ctk_rpgd_scratch_floats(cfg->predictor, (int)N, (int)H)
+        HIP_CREATE(zeroed(&h->d_scratch, !generic ? ctk_rpgd_scratch_floats(cfg->predictor, (int)N, (int)H)
                                                : cfg->predictor != CTK_PRED_ODE ? ctk_g_rpgd_scratch_floats_net(h->net, (int)N, (int)H)
                                                                                 : ctk_g_rpgd_scratch_floats(h->env, (int)N, (int)H)));
     }
@@ -1491,36 +1499,15 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     if (cfg->optimizer == CTK_OPT_MPPI && mppi_env_kernel(h)) h->dominant = ctk_mppi_rollout_env_name(h->env, mat);
     if (!descends && cfg->optimizer != CTK_OPT_MPPI && affine_env_kernel(h) && !(h->d_cem_ll && h->variant == CTK_OPT_CEM)) h->dominant = ctk_affine_rollout_env_name(h->env, mat);
     if (h->gmm_in_rollout) h->dominant = ctk_affine_rollout_mix_name(h->env, mat);
-    if (cfg->optimizer != CTK_OPT_RPGD) TRY_CREATE(ctk_reset(h, nullptr, CTK_LOC_NONE));
+    if (cfg->optimizer != CTK_OPT_RPGD)
+        if (int rc = ctk_reset(h, nullptr, CTK_LOC_NONE)) { g_create_error = h->err; return rc; }
     HIP_CREATE(hipStreamSynchronize(h->stream));
-    *out = h;
+    *out = made.release();
     return CTK_OK;
-#undef TRY_CREATE
-#undef HIP_CREATE
 }
 
-void ctk_destroy(ctk_handle* h) {
-    if (!h) return;
-    hipSetDevice(h->cfg.device);
-    (void)resident_quiesce(h);
-    if (h->res_box) { if (h->res_local) hipFree(h->res_box); else hipHostFree(h->res_box); }
-    if (h->res_stat) hipHostFree(h->res_stat);
-    if (h->d_res_relay) hipFree(h->d_res_relay);
-    if (h->d_res_args) hipFree(h->d_res_args);
-    hipStreamSynchronize(h->stream);   // also correct for the null (default) stream handed in by ctk_set_stream
-    for (auto& e : h->events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
-    void* bufs[] = {h->d_interp, h->d_samples, h->d_J, h->d_Q, h->d_traj, h->d_parts, h->d_parts2, h->d_parts3, h->d_unom[0], h->d_unom[1],
-                    h->d_std, h->d_base, h->d_scale, h->d_idx, h->d_u, h->d_weights, h->d_wperm, h->d_counter, h->d_ll, h->d_cem_ll, h->d_rec,
-                    h->d_pop[0], h->d_pop[1], h->d_m[0], h->d_m[1], h->d_v[0], h->d_v[1], h->d_ages[0], h->d_ages[1], h->d_bc, h->d_scratch, h->d_Jlog,
-                    h->d_mix, h->d_mix_label, h->d_plans};
-    for (void* b : bufs) if (b) hipFree(b);
-    if (h->d_shard_idx) hipFree(h->d_shard_idx);
-    for (float* p : h->d_log) if (p) hipFree(p);
-    ctk_p2p_close(h);
-    if (h->h_u) hipHostFree(h->h_u);
-    if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    delete h;
-}
+void ctk_destroy(ctk_handle* h) { delete h; }
+
 
 int ctk_set_stream(ctk_handle* h, void* hip_stream) {
     RES_Q(h);
@@ -1865,12 +1852,7 @@ int ctk_shard_iter_end(ctk_handle* h, const float* cands_all_dev, int n_ranks) {
     if (!h->shard_pending) return fail(h, CTK_ERR_STATE, "ctk_shard_iter_end: no iteration pending");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const int K = shard_k(h), rs = 2 + h->HC, M = n_ranks * K;
-    if ((size_t)M > h->shard_idx_cap) {
-        if (h->d_shard_idx) HIP_TRY(h, hipFree(h->d_shard_idx));
-        h->d_shard_idx = nullptr; h->shard_idx_cap = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->d_shard_idx, (size_t)M * sizeof(int)));
-        h->shard_idx_cap = (size_t)M;
-    }
+    HIP_TRY(h, h->own.grow_dev(h->d_shard_idx, h->shard_idx_cap, (size_t)M));
     // global best K of the union of the per-shard best-K lists: positions are ordered like global indices
     // among equal costs (rank-major, each list sorted), so the positional tie-break is the global one
     HIP_TRY(h, ctk_launch_select_topk(h->stream, cands_all_dev, M, K, h->d_shard_idx, rs));
@@ -1952,12 +1934,7 @@ int ctk_rpgd_step_end(ctk_handle* h, const float* keep_all_dev, int n_ranks, con
     const ctk_config& c = h->cfg;
     const int kl = rpgd_local_keep(h), M = n_ranks * kl, rs = 3 + 3 * h->HC;
     if (c.opt_keep_k > M) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_step_end: opt_keep_k exceeds the gathered candidates");
-    if ((size_t)M > h->shard_idx_cap) {
-        if (h->d_shard_idx) HIP_TRY(h, hipFree(h->d_shard_idx));
-        h->d_shard_idx = nullptr; h->shard_idx_cap = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->d_shard_idx, (size_t)M * sizeof(int)));
-        h->shard_idx_cap = (size_t)M;
-    }
+    HIP_TRY(h, h->own.grow_dev(h->d_shard_idx, h->shard_idx_cap, (size_t)M));
     // global keep-k (sorted) out of the union of the shards' sorted best lists (positional tie-break == global index)
     HIP_TRY(h, ctk_launch_select_topk(h->stream, keep_all_dev, M, c.opt_keep_k, h->d_shard_idx, rs));
     const bool resample = (h->count % c.resamp_per) == 0;
@@ -1988,12 +1965,11 @@ int ctk_rollout(ctk_handle* h, const float* s, const float* u_prev, const float*
     const float* d_s = nullptr;
     if (int rc = resolve_samples(h, Q, CTK_LOC_HOST, (size_t)n * H, &d_s)) return rc;
     float* d_traj = h->d_traj;
-    float* tmp_traj = nullptr;
-    if (traj_out && !d_traj) { HIP_TRY(h, hipMalloc((void**)&tmp_traj, (size_t)n * (Hs + 1) * h->S * sizeof(float))); d_traj = tmp_traj; }
+    ScopedDev tmp_traj, zero_one;   // freed on every return
+    if (traj_out && !d_traj) { HIP_TRY(h, hipMalloc(&tmp_traj.p, (size_t)n * (Hs + 1) * h->S * sizeof(float))); d_traj = (float*)tmp_traj.p; }
     // base 0, scale 1, no clipping: the plans are taken as given
-    float *d_zero = nullptr, *d_one = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&d_zero, 2 * H * sizeof(float)));
-    d_one = d_zero + H;
+    HIP_TRY(h, hipMalloc(&zero_one.p, 2 * H * sizeof(float)));
+    float *d_zero = (float*)zero_one.p, *d_one = d_zero + H;
     std::vector<float> zo(2 * H, 0.0f);
     for (size_t i = 0; i < H; ++i) zo[H + i] = 1.0f;
     HIP_TRY(h, hipMemcpyAsync(d_zero, zo.data(), 2 * H * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -2011,8 +1987,6 @@ int ctk_rollout(ctk_handle* h, const float* s, const float* u_prev, const float*
         e = hipMemcpyAsync(traj_out, d_traj, (size_t)n * (Hs + 1) * h->S * sizeof(float), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && J_out) e = hipMemcpyAsync(J_out, h->d_J, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream);
     hipError_t e2 = hipStreamSynchronize(h->stream);
-    hipFree(d_zero);
-    if (tmp_traj) hipFree(tmp_traj);
     HIP_TRY(h, e);
     HIP_TRY(h, e2);
     return CTK_OK;
@@ -2032,99 +2006,48 @@ int ctk_read(ctk_handle* h, int which, float* dst, size_t cap, size_t* n_out) {
     return CTK_OK;
 }
 
-size_t ctk_state_size(const ctk_handle* h) {
-    if (!h) return 0;
-    const size_t H = h->HC, C = h->C;   // [H,C] rows; the optimizer's last output u is C floats
+// THE description of a handle's state (ctk_host.h: StateItem), in the order of its layout: ctk_state_size sums it, ctk_get_state and
+// ctk_set_state walk it.  Empty: an optimizer without one.
+static std::vector<StateItem> handle_state(ctk_handle* h) {
+    const size_t H = h->HC, C = h->C, NH = (size_t)h->N * H;   // [H,C] rows; the optimizer's last output u is C floats
     switch (h->cfg.optimizer) {
-        case CTK_OPT_MPPI: return H + C;
+        case CTK_OPT_MPPI: return {state_seg(h->d_unom[h->cur], H), state_seg(h->d_u, C)};
         case CTK_OPT_CEM:
-            if (is_gmm(h)) return 4 * H + 2 + C + 1;   // mu[2,H,C] | std[2,H,C] | probs[2] | u[C] | count
-            return 2 * H + C + 1 + (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ ? 2 * (size_t)h->N * H + 1 : 0);
-        case CTK_OPT_RANDOM_ACTION: return C;
-        case CTK_OPT_RPGD: return 3 * (size_t)h->N * H + (size_t)h->N + C + 2;
+            if (is_gmm(h)) return {state_seg(h->d_mix, 4 * H + 2), state_seg(h->d_u, C), state_counter(&h->count)};   // mu[2,H,C] | std[2,H,C] | probs[2] | u[C] | count
+            if (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ)   // and the Keras optimizer's persistent moments and step count
+                return {state_seg(h->d_unom[0], H), state_seg(h->d_std, H), state_seg(h->d_u, C), state_counter(&h->count),
+                        state_seg(h->d_m[0], NH), state_seg(h->d_v[0], NH), state_counter(&h->adam_step)};
+            return {state_seg(h->d_unom[0], H), state_seg(h->d_std, H), state_seg(h->d_u, C), state_counter(&h->count)};
+        case CTK_OPT_RANDOM_ACTION: return {state_seg(h->d_u, C)};
+        case CTK_OPT_RPGD:
+            return {state_seg(h->d_pop[h->rcur], NH), state_seg(h->d_m[h->rcur], NH), state_seg(h->d_v[h->rcur], NH), state_seg(h->d_ages[h->rcur], h->N),
+                    state_seg(h->d_u, C), state_counter(&h->adam_step), state_counter(&h->count)};
     }
-    return 0;
+    return {};
 }
+
+size_t ctk_state_size(const ctk_handle* h) { return h ? state_floats(handle_state(const_cast<ctk_handle*>(h))) : 0; }
 
 int ctk_get_state(ctk_handle* h, float* dst, size_t cap) {
     RES_Q(h);
     if (!h || !dst) return CTK_ERR_INVALID_ARGUMENT;
-    const size_t n = ctk_state_size(h), H = h->HC, C = h->C;
-    if (cap < n) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_get_state: destination too small");
+    const std::vector<StateItem> st = handle_state(h);
+    if (cap < state_floats(st)) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_get_state: destination too small");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    size_t o = 0;
-    auto pull = [&](const float* src, size_t cnt) -> hipError_t {
-        hipError_t e = hipMemcpyAsync(dst + o, src, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-        o += cnt; return e;
-    };
-    switch (h->cfg.optimizer) {
-        case CTK_OPT_MPPI: HIP_TRY(h, pull(h->d_unom[h->cur], H)); HIP_TRY(h, pull(h->d_u, C)); break;
-        case CTK_OPT_CEM:
-            if (is_gmm(h)) {
-                HIP_TRY(h, pull(h->d_mix, 4 * H + 2)); HIP_TRY(h, pull(h->d_u, C));
-                HIP_TRY(h, hipStreamSynchronize(h->stream)); dst[o++] = (float)h->count;
-                break;
-            }
-            HIP_TRY(h, pull(h->d_unom[0], H)); HIP_TRY(h, pull(h->d_std, H)); HIP_TRY(h, pull(h->d_u, C));
-            HIP_TRY(h, hipStreamSynchronize(h->stream)); dst[o++] = (float)h->count;
-            if (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ) {   // the Keras optimizer's persistent moments and step count
-                HIP_TRY(h, pull(h->d_m[0], (size_t)h->N * H)); HIP_TRY(h, pull(h->d_v[0], (size_t)h->N * H));
-                HIP_TRY(h, hipStreamSynchronize(h->stream)); dst[o++] = (float)h->adam_step;
-            }
-            break;
-        case CTK_OPT_RANDOM_ACTION: HIP_TRY(h, pull(h->d_u, C)); break;
-        case CTK_OPT_RPGD: {
-            const size_t NH = (size_t)h->N * H;
-            HIP_TRY(h, pull(h->d_pop[h->rcur], NH)); HIP_TRY(h, pull(h->d_m[h->rcur], NH)); HIP_TRY(h, pull(h->d_v[h->rcur], NH));
-            HIP_TRY(h, pull(h->d_ages[h->rcur], h->N)); HIP_TRY(h, pull(h->d_u, C));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            dst[o++] = (float)h->adam_step; dst[o++] = (float)h->count;
-            break;
-        }
-        default: return fail(h, CTK_ERR_UNSUPPORTED, "ctk_get_state: not built for this optimizer");
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (st.empty()) return fail(h, CTK_ERR_UNSUPPORTED, "ctk_get_state: not built for this optimizer");
+    HIP_TRY(h, state_walk(st, dst, true, h->stream));
     return CTK_OK;
 }
 
 int ctk_set_state(ctk_handle* h, const float* src, size_t n) {
     RES_Q(h);
     if (!h || !src) return CTK_ERR_INVALID_ARGUMENT;
-    if (n != ctk_state_size(h)) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_set_state: wrong state size");
+    const std::vector<StateItem> st = handle_state(h);
+    if (n != state_floats(st)) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_set_state: wrong state size");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t H = h->HC, C = h->C;
-    size_t o = 0;
-    auto push = [&](float* dstp, size_t cnt) -> hipError_t {
-        hipError_t e = hipMemcpyAsync(dstp, src + o, cnt * sizeof(float), hipMemcpyHostToDevice, h->stream);
-        o += cnt; return e;
-    };
-    switch (h->cfg.optimizer) {
-        case CTK_OPT_MPPI: HIP_TRY(h, push(h->d_unom[h->cur], H)); HIP_TRY(h, push(h->d_u, C)); break;
-        case CTK_OPT_CEM:
-            if (is_gmm(h)) {
-                HIP_TRY(h, push(h->d_mix, 4 * H + 2)); HIP_TRY(h, push(h->d_u, C));
-                h->count = (int)src[o++];
-                break;
-            }
-            HIP_TRY(h, push(h->d_unom[0], H)); HIP_TRY(h, push(h->d_std, H)); HIP_TRY(h, push(h->d_u, C));
-            h->count = (int)src[o++];
-            if (h->variant == CTK_OPT_CEM_GRAD_BHARADHWAJ) {
-                HIP_TRY(h, push(h->d_m[0], (size_t)h->N * H)); HIP_TRY(h, push(h->d_v[0], (size_t)h->N * H));
-                h->adam_step = (int)src[o++];
-            }
-            break;
-        case CTK_OPT_RANDOM_ACTION: HIP_TRY(h, push(h->d_u, C)); break;
-        case CTK_OPT_RPGD: {
-            const size_t NH = (size_t)h->N * H;
-            HIP_TRY(h, push(h->d_pop[h->rcur], NH)); HIP_TRY(h, push(h->d_m[h->rcur], NH)); HIP_TRY(h, push(h->d_v[h->rcur], NH));
-            HIP_TRY(h, push(h->d_ages[h->rcur], h->N)); HIP_TRY(h, push(h->d_u, C));
-            h->adam_step = (int)src[o++]; h->count = (int)src[o++];
-            h->rpgd_ready = true;
-            break;
-        }
-        default: return fail(h, CTK_ERR_UNSUPPORTED, "ctk_set_state: not built for this optimizer");
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (st.empty()) return fail(h, CTK_ERR_UNSUPPORTED, "ctk_set_state: not built for this optimizer");
+    HIP_TRY(h, state_walk(st, const_cast<float*>(src), false, h->stream));
+    if (h->cfg.optimizer == CTK_OPT_RPGD) h->rpgd_ready = true;
     return CTK_OK;
 }
 
@@ -2165,10 +2088,10 @@ int ctk_p2p_close(ctk_handle* h) {
     hipStreamSynchronize(h->stream);
     for (int w = 0; w < h->p2p_world; ++w) {
         if (!h->p2p_bufs[w]) continue;
-        if (w == h->p2p_rank) hipFree(h->p2p_bufs[w]); else hipIpcCloseMemHandle(h->p2p_bufs[w]);
+        if (w == h->p2p_rank) (void)h->own.free_dev(h->p2p_bufs[w]); else hipIpcCloseMemHandle(h->p2p_bufs[w]);
         h->p2p_bufs[w] = nullptr;
     }
-    if (h->d_p2p_args) { hipFree(h->d_p2p_args); h->d_p2p_args = nullptr; }
+    (void)h->own.free_dev(h->d_p2p_args);
     h->p2p_world = 0; h->p2p_rank = -1; h->p2p_connected = false;
     return CTK_OK;
 }
@@ -2184,15 +2107,15 @@ int ctk_p2p_alloc(ctk_handle* h, int rank, int world, void* handle_out) {
     ctk_p2p_close(h);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t bytes = ctk_p2p_buffer_floats(world, h->P) * sizeof(float);
-    float* buf = nullptr;
-    HIP_TRY(h, hipExtMallocWithFlags((void**)&buf, bytes, hipDeviceMallocUncached));
-    HIP_TRY(h, hipMemset(buf, 0, bytes));
+    ScopedDev buf;   // freed on every return until the handle takes it
+    HIP_TRY(h, hipExtMallocWithFlags(&buf.p, bytes, hipDeviceMallocUncached));
+    HIP_TRY(h, hipMemset(buf.p, 0, bytes));
     HIP_TRY(h, hipDeviceSynchronize());
     hipIpcMemHandle_t hd;
-    hipError_t e = hipIpcGetMemHandle(&hd, buf);
-    if (e != hipSuccess) { hipFree(buf); return fail(h, CTK_ERR_HIP, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e)); }
+    hipError_t e = hipIpcGetMemHandle(&hd, buf.p);
+    if (e != hipSuccess) return fail(h, CTK_ERR_HIP, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e));
     std::memcpy(handle_out, &hd, sizeof(hd));
-    h->p2p_rank = rank; h->p2p_world = world; h->p2p_bufs[rank] = buf; h->p2p_seq = 1; h->p2p_connected = false;
+    h->p2p_rank = rank; h->p2p_world = world; h->p2p_bufs[rank] = (float*)h->own.own_dev(buf.release()); h->p2p_seq = 1; h->p2p_connected = false;
     if (const char* t = std::getenv("CTK_P2P_TIMEOUT_S")) { const double v = std::atof(t); if (v > 0.0) h->p2p_timeout_s = v; }
     return CTK_OK;
 }
@@ -2214,7 +2137,7 @@ int ctk_p2p_connect(ctk_handle* h, const void* handles) {
     {   // description of the exchange for the in-launch form (the rollout launch's block 0 does it)
         std::vector<char> host(ctk_p2p_args_bytes());
         ctk_p2p_fill_args(host.data(), h->p2p_bufs, h->p2p_rank, h->p2p_world, h->P, reinterpret_cast<uint32_t*>(h->h_u_dev) + 2, h->p2p_timeout_s);
-        if (!h->d_p2p_args) HIP_TRY(h, hipMalloc(&h->d_p2p_args, host.size()));
+        if (!h->d_p2p_args) { HIP_TRY(h, hipMalloc(&h->d_p2p_args, host.size())); h->own.own_dev(h->d_p2p_args); }
         HIP_TRY(h, hipMemcpy(h->d_p2p_args, host.data(), host.size(), hipMemcpyHostToDevice));
     }
     h->p2p_connected = true;
@@ -2271,11 +2194,13 @@ int ctk_resident_enable(ctk_handle* h, int on, double idle_us) {
         return fail(h, CTK_ERR_UNSUPPORTED, "ctk_resident_enable: needs the one-launch step with the {value, seq} hand-off (<= 128 workgroups, no materialised trajectories)");
     if (!(idle_us >= 1.0 && idle_us <= 1.0e6)) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_resident_enable: idle_us must be within [1, 1e6]");
     if (!h->res_box) {
-        HIP_TRY(h, hipHostMalloc((void**)&h->res_stat, sizeof(CtkResidentStat), hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(h->res_stat, 0, sizeof(CtkResidentStat));
+        // (a call that failed half-way left res_box NULL: what it allocated stays with the owner until the handle is destroyed)
+        HIP_TRY(h, h->own.pinned_zero(&h->res_stat, sizeof(CtkResidentStat), hipHostMallocMapped | hipHostMallocCoherent));
         HIP_TRY(h, hipHostGetDevicePointer((void**)&h->res_stat_dev, h->res_stat, 0));
         HIP_TRY(h, hipMalloc((void**)&h->d_res_relay, sizeof(CtkResidentBox)));
+        h->own.own_dev(h->d_res_relay);
         HIP_TRY(h, hipMalloc(&h->d_res_args, CTK_RES_ARGS_BYTES));
+        h->own.own_dev(h->d_res_args);
         HIP_TRY(h, hipMemsetAsync(h->d_res_relay, 0, sizeof(CtkResidentBox), h->stream));
         // the mailbox in device memory the HOST can store into (fine-grained allocation, reached through the PCIe BAR) — probed: a pattern
         // stored by the host must read back through a device-side copy.  CTK_RES_HOST_MAILBOX forces the pinned-host fallback (A/B, tests)
@@ -2295,7 +2220,8 @@ int ctk_resident_enable(ctk_handle* h, int on, double idle_us) {
                     for (int i = 0; i < 32; ++i) local = local && back[i] == 0xC0DE0000u + (uint32_t)i;
                 }
             }
-            if (!local) { (void)hipFree(vram); vram = nullptr; }
+            if (!local) { (void)hipFree(vram); vram = nullptr; }   // the rejected block never enters the owner
+            else h->own.own_dev(vram);
         }
         (void)hipGetLastError();
         if (local) {
@@ -2303,8 +2229,7 @@ int ctk_resident_enable(ctk_handle* h, int on, double idle_us) {
             HIP_TRY(h, hipDeviceSynchronize());
             h->res_box = static_cast<CtkResidentBox*>(vram); h->res_box_dev = h->res_box; h->res_local = true;
         } else {
-            HIP_TRY(h, hipHostMalloc((void**)&h->res_box, sizeof(CtkResidentBox), hipHostMallocMapped | hipHostMallocCoherent));
-            std::memset(h->res_box, 0, sizeof(CtkResidentBox));
+            HIP_TRY(h, h->own.pinned_zero(&h->res_box, sizeof(CtkResidentBox), hipHostMallocMapped | hipHostMallocCoherent));
             HIP_TRY(h, hipHostGetDevicePointer((void**)&h->res_box_dev, h->res_box, 0));
             h->res_local = false;
         }
@@ -2366,16 +2291,17 @@ int ctk_log_enable(ctk_handle* h, size_t capacity_steps) {
     if (!h) return CTK_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int i = 0; i < 4; ++i) { if (h->d_log[i]) HIP_TRY(h, hipFree(h->d_log[i])); h->d_log[i] = nullptr; }
+    HIP_TRY(h, log_release(h));
     h->log_cap = 0; h->log_count = 0;
     if (capacity_steps == 0) return CTK_OK;
     for (int i = 0; i < 4; ++i) {
         const size_t n = log_slot_floats(h, i);
         if (n == 0) continue;
         if (hipMalloc((void**)&h->d_log[i], capacity_steps * n * sizeof(float)) != hipSuccess) {
-            for (int j = 0; j < 4; ++j) { if (h->d_log[j]) hipFree(h->d_log[j]); h->d_log[j] = nullptr; }
+            (void)log_release(h);
             return fail(h, CTK_ERR_HIP, "ctk_log_enable: not enough device memory for the requested capacity");
         }
+        h->own.own_dev(h->d_log[i]);
     }
     h->log_cap = capacity_steps;
     return CTK_OK;

@@ -34,7 +34,7 @@ struct BatchCore {
     float* h_u_dev = nullptr;
     float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
     float *d_J = nullptr, *d_Q = nullptr, *d_traj = nullptr;   // [B][N] | [B][N,H,C] | [B][N,H+1,S] (materialize_trajectories); RPGD has J alone
-    std::vector<void*> dev_owned, pin_owned;   // every device / pinned allocation of the batch, entered where it is made (batch_core_release)
+    Owner own;                              // every device / pinned allocation of the batch, entered where it is made (ctk_host.h; batch_core_release)
     std::vector<uint32_t> seq, call;        // [B] the sequence number of the problem's next step, its Philox position
     std::string err, dominant;
     bool mlp_names = false;                 // the MLP family: its messages carry its own entry points' names (bfail)
@@ -86,48 +86,24 @@ void batch_env_lowers(const char* name, int* limit) {
 // the seed of problem p: the caller's, or consecutive ones from the configuration's
 uint64_t batch_seed(const ctk_config* cfg, const uint64_t* seeds, int p) { return seeds ? seeds[p] : cfg->seed + (uint64_t)p; }
 
-// ---- the owner: every allocation of a batch is entered in dev_owned / pin_owned where it is made; batch_core_release frees them ----
-// a zeroed device allocation of at least one byte (the memset on the batch's stream); a zeroed pinned allocation with the caller's flags
-template <class T>
-hipError_t batch_dev_zero(BatchCore* b, T** p, size_t bytes) {
-    const hipError_t e = hipMalloc((void**)p, bytes ? bytes : 1);
-    if (e == hipSuccess) b->dev_owned.push_back(*p);
-    return e != hipSuccess ? e : hipMemsetAsync(*p, 0, bytes ? bytes : 1, b->stream);
-}
-template <class T>
-hipError_t batch_pinned_zero(BatchCore* b, T** p, size_t bytes, unsigned flags = hipHostMallocDefault) {
-    const hipError_t e = hipHostMalloc((void**)p, bytes, flags);
-    if (e == hipSuccess) { b->pin_owned.push_back(*p); std::memset(*p, 0, bytes); }
-    return e;
-}
-// A buffer that grows on demand (d_samples; d_run / h_run) is freed and allocated where it grows, by the calls and in the order it always
-// was; the old pointer leaves the owner there and the new one is entered, so nothing is freed twice or kept twice.
-void batch_disown(std::vector<void*>& owned, void* p) { owned.erase(std::remove(owned.begin(), owned.end(), p), owned.end()); }
-
 // everything a batch owns on the device and in pinned memory; no HIP call for a batch that was refused before it opened anything
 void batch_core_release(BatchCore* b) {
-    if (!b->stream && b->dev_owned.empty() && b->pin_owned.empty()) return;
+    if (!b->stream && b->own.empty()) return;
     hipSetDevice(b->cfg.device);
     if (b->stream) hipStreamSynchronize(b->stream);
-    for (void* p : b->dev_owned) hipFree(p);
-    for (void* p : b->pin_owned) hipHostFree(p);
+    b->own.release();
     if (b->stream) hipStreamDestroy(b->stream);
 }
 BatchCore::~BatchCore() { batch_core_release(this); }
 
-// a HIP call of a creation, from batch_core_open on: a failure stores a text that names the call, and the caller deletes the batch
-// (BatchMade: a batch under creation, deleted on every return but the one that hands it over)
-#define BHIP_CREATE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(_e); return CTK_ERR_HIP; } } while (0)
-template <class B>
-struct BatchMade { B* b = new B(); ~BatchMade() { delete b; } B* release() { B* r = b; b = nullptr; return r; } };
-
-// what every family's creation starts its device state with: the stream, u of every problem, the mapped result slots
+// what every family's creation starts its device state with: the stream, u of every problem, the mapped result slots (HIP_CREATE and
+// Creating<>, the creation macro and guard of ctk_host.h: a failure stores its text, and the batch is deleted on the way out)
 int batch_core_open(BatchCore* b) {
-    BHIP_CREATE(hipSetDevice(b->cfg.device));
-    BHIP_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_u, (size_t)b->B * CTK_MAX_INPUTS * sizeof(float)));
-    BHIP_CREATE(batch_pinned_zero(b, &b->h_u, (size_t)b->B * 64, hipHostMallocMapped | hipHostMallocCoherent));
-    BHIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
+    HIP_CREATE(hipSetDevice(b->cfg.device));
+    HIP_CREATE(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    HIP_CREATE(b->own.dev_zero(&b->d_u, (size_t)b->B * CTK_MAX_INPUTS * sizeof(float), b->stream));
+    HIP_CREATE(b->own.pinned_zero(&b->h_u, (size_t)b->B * 64, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
     return CTK_OK;
 }
 
@@ -163,14 +139,7 @@ RolloutArgs batch_common_args(const BatchCore* b) {
 
 // host-supplied draws into the staging buffer (ctk_api.hip: resolve_samples of a handle): n floats
 int batch_stage(BatchCore* b, const float* src, size_t n) {
-    if (n > b->samples_cap) {
-        batch_disown(b->dev_owned, b->d_samples);
-        if (b->d_samples) BHIP_TRY(b, hipFree(b->d_samples));
-        b->d_samples = nullptr; b->samples_cap = 0;
-        BHIP_TRY(b, hipMalloc((void**)&b->d_samples, n * sizeof(float)));
-        b->dev_owned.push_back(b->d_samples);
-        b->samples_cap = n;
-    }
+    BHIP_TRY(b, b->own.grow_dev(b->d_samples, b->samples_cap, n));
     BHIP_TRY(b, hipMemcpyAsync(b->d_samples, src, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
     return CTK_OK;
 }
@@ -295,33 +264,25 @@ int batch_rng_set_position(BatchCore* b, const char* who, int problem, uint32_t 
 }
 
 // ---- the transfers of every family's *_get_state / *_set_state and *_read ----
-// A problem's state as a family describes it: segments on the device in the order of the state's layout, then its host-side counters,
-// one float each.  `mark`: a flag that set_state raises (RPGD: the problem counts as reset).
-struct StateSeg { float* dev; size_t n; };
-struct BatchState { std::vector<StateSeg> segs; std::vector<int*> counters; unsigned char* mark = nullptr; };
+// A problem's state as a family describes it: the state list of ctk_host.h (segments on the device in the order of the state's layout,
+// then — the batch families' case of that list — its host-side counters last).  `mark`: a flag that set_state raises (RPGD: the problem
+// counts as reset).
+struct BatchState { std::vector<StateItem> items; unsigned char* mark = nullptr; };
 
-// get (device to host) or set (host to device) of a problem's state through host[n]: the checks, the copies in the list's order, ONE
-// synchronisation; set writes the counters ahead of it, get reads them behind it.  name_size: the size messages name the size (RPGD's do)
+// get (device to host) or set (host to device) of a problem's state through host[n]: the checks here, the transfers in state_walk.
+// name_size: the size messages name the size (RPGD's do)
 template <class B>
 int batch_state_io(B* b, const char* who, int problem, float* host, size_t n, bool get, bool name_size, BatchState (*describe)(B*, int)) {
     if (!b || !host) return CTK_ERR_INVALID_ARGUMENT;
     if (int rc = batch_problem(b, who, problem)) return rc;
     const BatchState st = describe(b, problem);
-    size_t size = st.counters.size();
-    for (const StateSeg& g : st.segs) size += g.n;
+    const size_t size = state_floats(st.items);
     if (get ? n < size : n != size)
         return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + (get ? ": destination too small" : ": wrong state size") +
                      (name_size ? " (" + std::to_string(size) + " floats)" : std::string()));
     BHIP_TRY(b, hipSetDevice(b->cfg.device));
-    float* at = host;
-    for (const StateSeg& g : st.segs) {
-        BHIP_TRY(b, hipMemcpyAsync(get ? at : g.dev, get ? g.dev : at, g.n * sizeof(float), get ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, b->stream));
-        at += g.n;
-    }
-    for (size_t i = 0; !get && i < st.counters.size(); ++i) *st.counters[i] = (int)at[i];
+    BHIP_TRY(b, state_walk(st.items, host, get, b->stream));
     if (!get && st.mark) *st.mark = 1;
-    BHIP_TRY(b, hipStreamSynchronize(b->stream));
-    for (size_t i = 0; get && i < st.counters.size(); ++i) at[i] = (float)*st.counters[i];
     return CTK_OK;
 }
 
@@ -395,7 +356,7 @@ struct ctk_batch : BatchCore {
     unsigned char* d_kplant = nullptr;      // [B][kstride]
     unsigned char* h_run = nullptr;         // pinned: the step records, plant operands and traces of one segment or plant step (LoopLayout)
     unsigned char* d_run = nullptr;         // the same on the device; both grow on demand (batch_run_buffers)
-    size_t run_cap = 0;
+    size_t d_run_cap = 0, h_run_cap = 0;    // bytes
     int run_segment = 256;                  // steps per segment of a run: a diagnostic switch may lower it (ctk_batch_create)
     // the stochastic plant (include/ctk_hip_episode.h: ctk_batch_episodes / ctk_batch_plant_step_noisy; kernel ctk_batch_plant_noisy<ENV>)
     std::vector<float> noise_sigma;         // [B][2][CTK_MAX_STATES] process | measurement standard deviations (0: none)
@@ -517,18 +478,8 @@ static_assert(sizeof(CtkPlantNoise) % 16 == 0, "the traces lie behind the noise 
 
 // the run buffer (device and pinned), grown to the layout's bytes on demand
 int batch_run_buffers(ctk_batch* b, const LoopLayout& lay) {
-    if (lay.total <= b->run_cap) return CTK_OK;
-    batch_disown(b->dev_owned, b->d_run);
-    if (b->d_run) BHIP_TRY(b, hipFree(b->d_run));
-    b->d_run = nullptr; b->run_cap = 0;
-    batch_disown(b->pin_owned, b->h_run);
-    if (b->h_run) BHIP_TRY(b, hipHostFree(b->h_run));
-    b->h_run = nullptr;
-    BHIP_TRY(b, hipMalloc((void**)&b->d_run, lay.total));
-    b->dev_owned.push_back(b->d_run);
-    BHIP_TRY(b, hipHostMalloc((void**)&b->h_run, lay.total, hipHostMallocDefault));
-    b->pin_owned.push_back(b->h_run);
-    b->run_cap = lay.total;
+    BHIP_TRY(b, b->own.grow_dev(b->d_run, b->d_run_cap, lay.total));
+    BHIP_TRY(b, b->own.grow_pin(b->h_run, b->h_run_cap, lay.total));
     return CTK_OK;
 }
 
@@ -872,23 +823,23 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
 
     if (int rc = batch_core_open(b)) return rc;
     const size_t Bz = (size_t)n_problems, rec = (size_t)blocks * (2 + b->PC);
-    BHIP_CREATE(batch_dev_zero(b, &b->d_interp, (size_t)H * sizeof(InterpEntry)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_J, Bz * N * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_Q, Bz * N * b->HC * sizeof(float)));
-    if (cfg->materialize_trajectories) BHIP_CREATE(batch_dev_zero(b, &b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_parts, Bz * rec * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_ll, Bz * rec * sizeof(unsigned long long)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_unom, Bz * b->unom_stride() * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_desc, Bz * sizeof(CtkBatchDesc)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_steps, Bz * sizeof(CtkBatchStep)));
-    BHIP_CREATE(batch_pinned_zero(b, &b->h_steps, Bz * sizeof(CtkBatchStep)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_k, Bz * b->kstride));
-    BHIP_CREATE(batch_pinned_zero(b, &b->h_k, Bz * b->kstride));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_kplant, Bz * b->kstride));
-    BHIP_CREATE(batch_pinned_zero(b, &b->h_kplant, Bz * b->kstride));
+    HIP_CREATE(b->own.dev_zero(&b->d_interp, (size_t)H * sizeof(InterpEntry), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_J, Bz * N * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_Q, Bz * N * b->HC * sizeof(float), b->stream));
+    if (cfg->materialize_trajectories) HIP_CREATE(b->own.dev_zero(&b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_parts, Bz * rec * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_ll, Bz * rec * sizeof(unsigned long long), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_unom, Bz * b->unom_stride() * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_desc, Bz * sizeof(CtkBatchDesc), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_steps, Bz * sizeof(CtkBatchStep), b->stream));
+    HIP_CREATE(b->own.pinned_zero(&b->h_steps, Bz * sizeof(CtkBatchStep)));
+    HIP_CREATE(b->own.dev_zero(&b->d_k, Bz * b->kstride, b->stream));
+    HIP_CREATE(b->own.pinned_zero(&b->h_k, Bz * b->kstride));
+    HIP_CREATE(b->own.dev_zero(&b->d_kplant, Bz * b->kstride, b->stream));
+    HIP_CREATE(b->own.pinned_zero(&b->h_kplant, Bz * b->kstride));
     if (mlp) {
-        BHIP_CREATE(batch_dev_zero(b, &b->d_w, Bz * b->wtab * sizeof(float)));
-        BHIP_CREATE(batch_pinned_zero(b, &b->h_w, Bz * b->wtab * sizeof(float)));
+        HIP_CREATE(b->own.dev_zero(&b->d_w, Bz * b->wtab * sizeof(float), b->stream));
+        HIP_CREATE(b->own.pinned_zero(&b->h_w, Bz * b->wtab * sizeof(float)));
     }
 
     const std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, P);
@@ -906,10 +857,10 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
         d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
         for (int i = 0; i < b->HC; ++i) plan[z * b->unom_stride() + i] = 0.5f * (cfg->action_low[i % b->C] + cfg->action_high[i % b->C]);
     }
-    BHIP_CREATE(hipMemcpyAsync(b->d_interp, tab.data(), (size_t)H * sizeof(InterpEntry), hipMemcpyHostToDevice, b->stream));
-    BHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkBatchDesc), hipMemcpyHostToDevice, b->stream));
-    BHIP_CREATE(hipMemcpyAsync(b->d_unom, plan.data(), plan.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    BHIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
+    HIP_CREATE(hipMemcpyAsync(b->d_interp, tab.data(), (size_t)H * sizeof(InterpEntry), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkBatchDesc), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(hipMemcpyAsync(b->d_unom, plan.data(), plan.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
     return CTK_OK;
 }
 
@@ -998,7 +949,7 @@ int ctk_batch_read(ctk_batch* b, int problem, int buffer, float* dst, size_t cap
 }
 
 // the state of a problem: its current plan, its last output
-static BatchState batch_state(ctk_batch* b, int p) { return {{{b->unom(p, b->cur[(size_t)p]), (size_t)b->HC}, {b->u(p), (size_t)b->C}}, {}}; }
+static BatchState batch_state(ctk_batch* b, int p) { return {{state_seg(b->unom(p, b->cur[(size_t)p]), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C)}}; }
 int ctk_batch_get_state(ctk_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_batch_get_state", problem, dst, cap, true, false, batch_state); }
 int ctk_batch_set_state(ctk_batch* b, int problem, const float* src, size_t n) {
     return batch_state_io(b, "ctk_batch_set_state", problem, const_cast<float*>(src), n, false, false, batch_state);
@@ -1401,8 +1352,8 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
     hipDeviceProp_t prop;
     if (int rc = probe_device("ctk_cem_batch_create", cfg->device, &prop)) return rc;
 
-    BatchMade<ctk_cem_batch> made;
-    ctk_cem_batch* b = made.b;
+    Creating<ctk_cem_batch> made;
+    ctk_cem_batch* b = made.p;
     batch_core_init(b, cfg, einfo, n_problems);
     b->K = cfg->cem_best_k; b->nblk = nblk;
     b->llw = ctk_cem_fused_ll_words(N, HC);
@@ -1419,17 +1370,17 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
 
     if (int rc = batch_core_open(b)) return rc;
     const size_t Bz = (size_t)n_problems;
-    BHIP_CREATE(batch_dev_zero(b, &b->d_ll, Bz * b->llw * sizeof(unsigned long long)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_mu, Bz * HC * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_sd, Bz * HC * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_J, Bz * N * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_Q, Bz * N * HC * sizeof(float)));
-    if (cfg->materialize_trajectories) BHIP_CREATE(batch_dev_zero(b, &b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_idx, Bz * N * sizeof(int)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_desc, Bz * sizeof(CtkCemBatchDesc)));
+    HIP_CREATE(b->own.dev_zero(&b->d_ll, Bz * b->llw * sizeof(unsigned long long), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_mu, Bz * HC * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_sd, Bz * HC * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_J, Bz * N * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_Q, Bz * N * HC * sizeof(float), b->stream));
+    if (cfg->materialize_trajectories) HIP_CREATE(b->own.dev_zero(&b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_idx, Bz * N * sizeof(int), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_desc, Bz * sizeof(CtkCemBatchDesc), b->stream));
     const size_t steps_bytes = Bz * (sizeof(CtkCemBatchStep) + b->kstride);   // the records, then room for as many elements of constants
-    BHIP_CREATE(batch_dev_zero(b, &b->d_steps, steps_bytes));
-    BHIP_CREATE(batch_pinned_zero(b, &b->h_steps, steps_bytes));
+    HIP_CREATE(b->own.dev_zero(&b->d_steps, steps_bytes, b->stream));
+    HIP_CREATE(b->own.pinned_zero(&b->h_steps, steps_bytes));
 
     std::vector<CtkCemBatchDesc> desc(Bz);
     std::vector<float> mu(Bz * HC), sd(Bz * HC);                   // optimizer_reset() of every problem
@@ -1445,10 +1396,10 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
         d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
         cem_batch_initial(b, mu.data() + z * HC, sd.data() + z * HC);
     }
-    BHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkCemBatchDesc), hipMemcpyHostToDevice, b->stream));
-    BHIP_CREATE(hipMemcpyAsync(b->d_mu, mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    BHIP_CREATE(hipMemcpyAsync(b->d_sd, sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    BHIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
+    HIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkCemBatchDesc), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(hipMemcpyAsync(b->d_mu, mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(hipMemcpyAsync(b->d_sd, sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
     *out = made.release();
     return CTK_OK;
 }
@@ -1573,7 +1524,7 @@ int ctk_cem_batch_read(ctk_cem_batch* b, int problem, int buffer, float* dst, si
 
 // the state of a problem: mean, standard deviation, last output; its step count
 static BatchState cem_batch_state(ctk_cem_batch* b, int p) {
-    return {{{b->mu(p), (size_t)b->HC}, {b->sd(p), (size_t)b->HC}, {b->u(p), (size_t)b->C}}, {&b->count[(size_t)p]}};
+    return {{state_seg(b->mu(p), (size_t)b->HC), state_seg(b->sd(p), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C), state_counter(&b->count[(size_t)p])}};
 }
 int ctk_cem_batch_get_state(ctk_cem_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_cem_batch_get_state", problem, dst, cap, true, false, cem_batch_state); }
 int ctk_cem_batch_set_state(ctk_cem_batch* b, int problem, const float* src, size_t n) {
@@ -1722,8 +1673,8 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
     hipDeviceProp_t prop;
     if (int rc = probe_device("ctk_rpgd_batch_create", cfg->device, &prop)) return rc;
 
-    BatchMade<ctk_rpgd_batch> made;
-    ctk_rpgd_batch* b = made.b;
+    Creating<ctk_rpgd_batch> made;
+    ctk_rpgd_batch* b = made.p;
     batch_core_init(b, cfg, einfo, n_problems);
     b->K = cfg->opt_keep_k;
     b->P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
@@ -1737,27 +1688,27 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
     if (int rc = batch_core_open(b)) return rc;
     const size_t Bz = (size_t)n_problems, NHC = b->NHC();
     for (int i = 0; i < 2; ++i) {
-        BHIP_CREATE(batch_dev_zero(b, &b->d_pop[i], Bz * NHC * sizeof(float)));
-        BHIP_CREATE(batch_dev_zero(b, &b->d_m[i], Bz * NHC * sizeof(float)));
-        BHIP_CREATE(batch_dev_zero(b, &b->d_v[i], Bz * NHC * sizeof(float)));
-        BHIP_CREATE(batch_dev_zero(b, &b->d_ages[i], Bz * N * sizeof(float)));
+        HIP_CREATE(b->own.dev_zero(&b->d_pop[i], Bz * NHC * sizeof(float), b->stream));
+        HIP_CREATE(b->own.dev_zero(&b->d_m[i], Bz * NHC * sizeof(float), b->stream));
+        HIP_CREATE(b->own.dev_zero(&b->d_v[i], Bz * NHC * sizeof(float), b->stream));
+        HIP_CREATE(b->own.dev_zero(&b->d_ages[i], Bz * N * sizeof(float), b->stream));
     }
-    BHIP_CREATE(batch_dev_zero(b, &b->d_J, Bz * N * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_idx, Bz * N * sizeof(int)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_unom, Bz * HC * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_scratch, Bz * b->scratch_stride * sizeof(float)));
-    BHIP_CREATE(batch_dev_zero(b, &b->d_desc, Bz * sizeof(CtkRpgdBatchDesc)));
+    HIP_CREATE(b->own.dev_zero(&b->d_J, Bz * N * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_idx, Bz * N * sizeof(int), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_unom, Bz * HC * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_scratch, Bz * b->scratch_stride * sizeof(float), b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_desc, Bz * sizeof(CtkRpgdBatchDesc), b->stream));
     const size_t steps_bytes = Bz * (sizeof(CtkRpgdBatchStep) + b->kstride);   // the records, then room for as many elements of constants
-    BHIP_CREATE(batch_dev_zero(b, &b->d_steps, steps_bytes));
-    BHIP_CREATE(batch_pinned_zero(b, &b->h_steps, steps_bytes));
+    HIP_CREATE(b->own.dev_zero(&b->d_steps, steps_bytes, b->stream));
+    HIP_CREATE(b->own.pinned_zero(&b->h_steps, steps_bytes));
 
     std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, b->P);
-    BHIP_CREATE(batch_dev_zero(b, &b->d_interp, (size_t)H * sizeof(InterpEntry)));
-    BHIP_CREATE(hipMemcpyAsync(b->d_interp, tab.data(), (size_t)H * sizeof(InterpEntry), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_interp, (size_t)H * sizeof(InterpEntry), b->stream));
+    HIP_CREATE(hipMemcpyAsync(b->d_interp, tab.data(), (size_t)H * sizeof(InterpEntry), hipMemcpyHostToDevice, b->stream));
     const std::vector<float> bc = adam_bias_corrections(cfg->adam_beta_1, cfg->adam_beta_2);   // the table of a handle (ctk_host.h)
     b->bc_len = (int)(bc.size() / 2);
-    BHIP_CREATE(batch_dev_zero(b, &b->d_bc, bc.size() * sizeof(float)));
-    BHIP_CREATE(hipMemcpyAsync(b->d_bc, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(b->own.dev_zero(&b->d_bc, bc.size() * sizeof(float), b->stream));
+    HIP_CREATE(hipMemcpyAsync(b->d_bc, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
 
     std::vector<CtkRpgdBatchDesc> desc(Bz);
     for (int p = 0; p < n_problems; ++p) {
@@ -1773,8 +1724,8 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
         d.scratch = b->d_scratch + z * b->scratch_stride;
         d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
     }
-    BHIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkRpgdBatchDesc), hipMemcpyHostToDevice, b->stream));
-    BHIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
+    HIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkRpgdBatchDesc), hipMemcpyHostToDevice, b->stream));
+    HIP_CREATE(hipStreamSynchronize(b->stream));               // the host vectors go out of scope below
     *out = made.release();
     return CTK_OK;
 }
@@ -1917,8 +1868,9 @@ int ctk_rpgd_batch_read(ctk_rpgd_batch* b, int problem, int buffer, float* dst, 
 static BatchState rpgd_batch_state(ctk_rpgd_batch* b, int p) {
     const size_t z = (size_t)p, N = (size_t)b->N, NHC = b->NHC();
     const int cur = b->cur[z];
-    return {{{b->d_pop[cur] + z * NHC, NHC}, {b->d_m[cur] + z * NHC, NHC}, {b->d_v[cur] + z * NHC, NHC}, {b->d_ages[cur] + z * N, N}, {b->u(p), (size_t)b->C}},
-            {&b->adam_step[z], &b->count[z]}, &b->ready[z]};
+    return {{state_seg(b->d_pop[cur] + z * NHC, NHC), state_seg(b->d_m[cur] + z * NHC, NHC), state_seg(b->d_v[cur] + z * NHC, NHC),
+             state_seg(b->d_ages[cur] + z * N, N), state_seg(b->u(p), (size_t)b->C), state_counter(&b->adam_step[z]), state_counter(&b->count[z])},
+            &b->ready[z]};
 }
 int ctk_rpgd_batch_get_state(ctk_rpgd_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_rpgd_batch_get_state", problem, dst, cap, true, true, rpgd_batch_state); }
 int ctk_rpgd_batch_set_state(ctk_rpgd_batch* b, int problem, const float* src, size_t n) {

@@ -155,6 +155,28 @@ def test_a_refused_creation_is_read_through_every_last_error():
     assert texts == [texts[0]] * len(readers)
 
 
+def test_handle_creation_failures_keep_their_code_text_and_null_handle():
+    """ctk_create's own failure path: a refusal by configuration is read through every family's *_last_error(NULL); a valid
+    configuration on a machine without a GPU fails at the device probe with CTK_ERR_NO_DEVICE (4) and its text; both leave *out NULL"""
+    import torch
+    from control_toolkit_amd._capi import load_library
+    lib = load_library()
+    readers = ("ctk_last_error", "ctk_batch_last_error", "ctk_mlp_batch_last_error", "ctk_cem_batch_last_error", "ctk_rpgd_batch_last_error")
+    out = ctypes.c_void_p(1)                                  # not NULL: the call itself must clear it
+    bad = make_cfg(struct_size=8)
+    assert lib.ctk_create(ctypes.byref(bad), ctypes.byref(out)) == 1 and out.value is None
+    assert [getattr(lib, r)(None).decode() for r in readers] == ["ctk_create: ctk_config size mismatch (ABI)"] * len(readers)
+    out = ctypes.c_void_p(1)
+    cfg = make_cfg()
+    rc = lib.ctk_create(ctypes.byref(cfg), ctypes.byref(out))
+    if torch.cuda.is_available():                             # with a device the same call succeeds
+        assert rc == 0 and out.value
+        lib.ctk_destroy(out)
+        return
+    assert rc == 4 and out.value is None
+    assert [getattr(lib, r)(None).decode() for r in readers] == ["ctk_create: no HIP device visible (libctk_hip has no CPU fallback)"] * len(readers)
+
+
 def test_valid_batch_without_a_gpu_fails_loudly():
     import torch
     from control_toolkit_amd import CtkMppiBatch, CtkError

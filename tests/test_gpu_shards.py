@@ -392,6 +392,69 @@ def test_rpgd_end_against_float64_without_resampling(envname):
 
 
 # =====================================================================================================================================
+# a. record level — one handle at 1, then 3, then 2 gathered ranks: the index buffer of *_end grows once (1 -> 3) and is then reused
+# (3 -> 2); every result bit for bit that of a fresh handle at that rank count
+# =====================================================================================================================================
+RANK_COUNTS = (1, 3, 2)
+
+
+def cem_end_at(e, n_ranks, K, N_local, H):
+    C, s0 = ENVS["CartPole"]["C"], ENVS["CartPole"]["s0"]
+    rng = np.random.default_rng(n_ranks)
+    buf = device_buffer(n_ranks * K * (2 + H * C))
+    cands = topk_lists(n_ranks, K, N_local, H, "CartPole", False, seed0=7 * K + n_ranks)
+    e.set_state(np.concatenate([rng.uniform(-0.3, 0.3, H * C).astype(np.float32), np.full(H * C, 0.4, np.float32), np.zeros(C, np.float32), [1.0]]))
+    e.shard_iter_begin(s0, buf.data_ptr(), rng.standard_normal((N_local, H, C)).astype(np.float32))
+    overwrite(buf, cands)
+    e.shard_iter_end(buf.data_ptr(), n_ranks)
+    refit = [e.read("U_NOM"), e.read("STD")]
+    return refit + [e.shard_finish(), e.read("U_NOM"), e.read("STD"), e.get_state()]
+
+
+def test_cem_iter_end_index_buffer_grows_once_and_is_reused():
+    K, N_local, H = 13, 64, 6
+    kw = dict(mpc_horizon=H, cem_outer_it=1, cem_best_k=K)
+    e = engine("cem", "CartPole", N_local, **kw)
+    for n_ranks in RANK_COUNTS:
+        got = cem_end_at(e, n_ranks, K, N_local, H)
+        fresh = engine("cem", "CartPole", N_local, **kw)
+        want = cem_end_at(fresh, n_ranks, K, N_local, H)
+        fresh.close()
+        for i, (g, w) in enumerate(zip(got, want)):
+            np.testing.assert_array_equal(g, w, err_msg=f"shards cem_end reused handle, ranks={n_ranks}, result {i}")
+    e.close()
+
+
+def rpgd_end_at(e, n_ranks, k):
+    C, s0 = ENVS["CartPole"]["C"], ENVS["CartPole"]["s0"]
+    H = e.H
+    rng = np.random.default_rng(n_ranks)
+    buf = device_buffer(n_ranks * min(k, NL_RPGD) * (3 + 3 * H * C))
+    recs = rpgd_lists(n_ranks, k, H, "CartPole", False, seed0=100 * n_ranks + k)
+    e.set_state(rpgd_state(*rpgd_population(rng, NL_RPGD, H, "CartPole"), np.zeros(C), 3, 0))      # count 0: a resampling step
+    e.rpgd_step_begin(s0, buf.data_ptr())
+    overwrite(buf, recs)
+    nf = e.rpgd_fresh_rows(n_ranks)
+    assert nf == R.rpgd_fresh_rows_ref(k, n_ranks, NL_RPGD, 0, True) and nf > 0
+    u = e.rpgd_step_end(buf.data_ptr(), n_ranks, rng.random((nf, e.inducing_points(), C), dtype=np.float32))
+    return [u] + [e.read(n) for n in ("PLAN", "ADAM_M", "ADAM_V", "AGES", "U_NOM")] + [e.get_state()]
+
+
+def test_rpgd_step_end_index_buffer_grows_once_and_is_reused():
+    k = 5                                       # <= the records of ONE rank, so that every rank count is accepted
+    kw = rpgd_kw("CartPole", k, 0)
+    e = engine("rpgd", "CartPole", NL_RPGD, **kw)
+    for n_ranks in RANK_COUNTS:
+        got = rpgd_end_at(e, n_ranks, k)
+        fresh = engine("rpgd", "CartPole", NL_RPGD, **kw)
+        want = rpgd_end_at(fresh, n_ranks, k)
+        fresh.close()
+        for i, (g, w) in enumerate(zip(got, want)):
+            np.testing.assert_array_equal(g, w, err_msg=f"shards rpgd_end reused handle, ranks={n_ranks}, result {i}")
+    e.close()
+
+
+# =====================================================================================================================================
 # b. end to end: G shards == one handle (and the oracle)
 # =====================================================================================================================================
 NL = 40
