@@ -160,9 +160,9 @@ def cem_ref(env, N, H, th, om, dt, isteps, own=(), predictor=O.Predictor):
 
 
 @functools.lru_cache(maxsize=None)
-def random_ref(env, N, H, th, om, dt, isteps, predictor=O.Predictor):
+def random_ref(env, N, H, th, om, dt, isteps, predictor=O.Predictor, own=()):
     """one oracle random-action step: uniform plans between the limits, the arg-min's first input"""
-    pars, pred, cost = _models(env, dt, isteps, (), predictor)
+    pars, pred, cost = _models(env, dt, isteps, own, predictor)
     lo, hi = L.LIMITS[env]
     o = O.RandomAction(pred, cost, lo, hi, num_rollouts=N, mpc_horizon=H)
     u01 = np.random.default_rng(seed_for("random", env, N, H, dt, isteps, RANDOM_SEED + N + H)).random((N, H, lo.size), dtype=np.float32)
@@ -172,9 +172,9 @@ def random_ref(env, N, H, th, om, dt, isteps, predictor=O.Predictor):
 
 
 @functools.lru_cache(maxsize=None)
-def rollout_ref(env, N, H, th, om, dt, isteps, predictor=O.Predictor):
+def rollout_ref(env, N, H, th, om, dt, isteps, predictor=O.Predictor, own=()):
     """plain rollouts of plans that nobody clips (ROLLOUT_GAIN * normals_for), u_prev = 0.1"""
-    pars, pred, cost = _models(env, dt, isteps, (), predictor)
+    pars, pred, cost = _models(env, dt, isteps, own, predictor)
     Q = (ROLLOUT_GAIN * L.normals_for(env, N, H, seed_for("rollout", env, N, H, dt, isteps, None))).astype(np.float32)
     up = np.full(pars.C, 0.1, np.float32)
     s = L.base_state(env, th, om)
@@ -193,10 +193,10 @@ def gmm_draws(env, N, H, dt, k):
 
 
 @functools.lru_cache(maxsize=None)
-def gmm_ref(env, N, H, K, th, om, dt, isteps, predictor=O.Predictor):
+def gmm_ref(env, N, H, K, th, om, dt, isteps, predictor=O.Predictor, own=()):
     """one outer iteration of CEM-GMM from the initial mixture (tests/gmm_oracle.py), as the large-angle file runs it"""
     from gmm_oracle import CEMGMM
-    pars, pred, cost = _models(env, dt, isteps, (), predictor)
+    pars, pred, cost = _models(env, dt, isteps, own, predictor)
     lo, hi = L.LIMITS[env]
     o = CEMGMM(pred, cost, *((float(lo[0]), float(hi[0])) if lo.size == 1 else (lo, hi)), num_rollouts=N, mpc_horizon=H, cem_outer_it=1, cem_best_k=K)
     normals, uniforms = gmm_draws(env, N, H, dt, isteps)

@@ -344,11 +344,13 @@ def test_rpgd_two_inputs_matches_reference(case):
 
 
 # ---- the oracle's hand-written reverse modes against torch autograd in fp64 (build container and GPU box: torch-CPU) ------------
-@pytest.mark.parametrize("kind,envname", [("GRU", "CartPole"), ("GRU", "Quad2D"), ("MLP", "Quad2D"), ("ODE", "Quad2D"), ("ODE", "Hover"), ("MLP", "Hover"), ("GRU", "Hover")])
+@pytest.mark.parametrize("kind,envname", [("ODE", "CartPole"), ("MLP", "CartPole"), ("GRU", "CartPole"), ("GRU", "Quad2D"), ("MLP", "Quad2D"), ("ODE", "Quad2D"), ("ODE", "Hover"), ("MLP", "Hover"), ("GRU", "Hover")])
 def test_oracle_adjoints_match_torch_autograd_fp64(kind, envname):
     """d(sum_n J_n)/dQ from rollout_cost_and_grad (what the HIP reverse sweeps are tested against) == autograd through a
-    float64 torch restatement of the same rollout and cost (what the reference does at optimizer_rpgd.py:329-333)."""
+    float64 torch restatement of the same rollout and cost (what the reference does at optimizer_rpgd.py:329-333).  CartPole's ODE
+    step and cost are param_cases.PlantF64's: the float64 statement from the primary parameters alone."""
     import torch
+    from param_cases import PlantF64
     env = O.ENVIRONMENTS[envname](terminal_weight=0.3)
     S, C = env.S, env.C
     weights = None if kind == "ODE" else (O.gru_default_weights(4, S + C, S) if kind == "GRU" else O.mlp_default_weights(4, S + C, S))
@@ -366,8 +368,11 @@ def test_oracle_adjoints_match_torch_autograd_fp64(kind, envname):
     T = lambda a: torch.tensor(np.asarray(a, np.float64))
     Qt = T(Q).requires_grad_(True)
     k = {kk: float(v) for kk, v in O.derived_constants(env, 0.02, 1).items()}
+    plant = PlantF64(envname, env)
 
     def step(s, u, hid):
+        if kind == "ODE" and envname == "CartPole":
+            return plant.step(s, u), hid
         if kind == "MLP":
             W1, b1, W2, b2, W3, b3 = (T(a) for a in O.mlp_unpack(weights, S + C, S))
             x = torch.cat([s, u], 1)
@@ -399,6 +404,8 @@ def test_oracle_adjoints_match_torch_autograd_fp64(kind, envname):
 
     def stage(s, u, upv):
         e = env
+        if kind in ("ODE", "MLP") and envname == "CartPole":
+            return plant.stage_cost(s, u, upv), plant.state_cost(s)
         if envname == "Hover":
             pos = k["pos_c"] * ((s[:, 0] - e.target_x) ** 2 + (s[:, 2] - e.target_y) ** 2) + e.ang_weight * (1 - torch.cos(s[:, 4]))
             return (pos + e.vel_weight * (s[:, 1] ** 2 + s[:, 3] ** 2) + e.angvel_weight * s[:, 5] ** 2 + e.wheel_weight * s[:, 6] ** 2
