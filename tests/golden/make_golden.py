@@ -17,6 +17,10 @@ What they do NOT pin (build-defined, "parity unpinned"): the predictor, the conc
 primitives (the stand-ins'), and everything that needs tf.keras.optimizers.Adam (optimizer_gradient_tf, cem_grad_bharadhwaj, RPGD's
 TF branch).
 
+Hyper-parameters away from their defaults (record_hyper_cases, the `*hyper*` files): the same unmodified modules at other values of
+cc_weight / R / LBD / NU / SQRTRHOINV, of Adam's scalars, the clip, shift_previous, resamp_per and the sampling constants, of CEM's
+initial deviation, clamp and elite count, between asymmetric limits; RPGD with opt_keep_k_ratio 1.0 (k = N) runs last, on its own.
+
 Usage (build container only):  python tests/golden/make_golden.py
 Neither this script nor the stand-ins run on the GPU box; only the .npz outputs travel.
 """
@@ -83,7 +87,12 @@ class RecordingRng:
         g = self._snapshot()
         out = self.gen.normal(shape, dtype=dtype, mean=mean, stddev=stddev)
         raw = torch.normal(mean=0.0, std=1.0, size=shape, generator=g, dtype=dtype)
-        assert torch.equal(raw * stddev + mean, out) or torch.allclose(raw * stddev + mean, out, rtol=0, atol=0)
+        # torch scales its draws in one fused multiply-add where the build contracts it: with a mean other than 0 every element is
+        # either the twice-rounded raw * stddev + mean or the once-rounded one.  (This checks the recovery of the raw draws, not the
+        # library: which rounding an element took is not recorded, and the 1-ulp ambiguity it leaves in the first plans is absorbed
+        # where the oracle and the kernels are compared with Q_init, at rtol 1e-6.)
+        fused = (raw.double() * float(stddev) + float(mean)).to(dtype)
+        assert bool(((raw * stddev + mean == out) | (fused == out)).all())
         self.raw.append(raw.numpy().copy())
         return out
 
@@ -339,6 +348,225 @@ def record_tf_only_optimizers(out_dir, cm, envs, dt):
                 s = plant_step(plant, s, u)
             d["steps"] = np.int32(c["steps"])
             save_fixture(os.path.join(out_dir, f"cem_naive_grad_{name}.npz"), **d)
+    finally:
+        set_computation_library("pytorch")
+        pw.ENVIRONMENT = "CartPole"
+
+
+# ---- hyper-parameters away from their defaults (tests/hyper_cases.py, tests/test_hyper_cases_cpu.py, tests/test_gpu_hyper.py) ---------
+# Every fixture above runs MPPI at cc_weight = R = 1, LBD 100, NU 1000, SQRTRHOINV 0.03, RPGD at Adam 0.9 / 0.999 / 1e-8 with a clip
+# that never binds, CEM with symmetric limits and a clamp that rarely binds.  The cases below run the SAME unmodified reference modules
+# with every one of these moved, from states near the target (where the correction cost is a visible share of J), at small sizes:
+# a period > 1 with (H - 1) % period != 0, 3+ closed-loop steps, trajectories kept.  Every file stores its hyper-parameters, limits,
+# environment and parameters; u_prev is stored as [C] in all of them.
+HYPER_MPPI = {
+    "hyper_all":       dict(cc_weight=0.37, R=2.3, LBD=30.0, NU=2.0, SQRTRHOINV=0.08),
+    "hyper_saturated": dict(cc_weight=0.37, R=2.3, LBD=30.0, NU=2.0, SQRTRHOINV=0.2),
+}
+HYPER_LIMITS = {"CartPole": ([-0.3], [0.9]), "Quad2D": ([-0.5, -0.9], [0.8, 0.35]), "Hover": ([-0.6, -0.2, -0.9], [0.4, 0.7, 0.3])}
+HYPER_STATES = {"CartPole": [0.06, -0.12, 0.15, 0.3], "Quad2D": [0.16, -0.1, 0.94, 0.08, 0.1, -0.2],
+                "Hover": [0.26, -0.08, -0.14, 0.06, 0.15, -0.1, 0.4]}
+HYPER_RPGD_ADAM = dict(learning_rate=0.2, adam_beta_1=0.7, adam_beta_2=0.9, adam_epsilon=1e-3, gradmax_clip=0.05)
+
+
+def record_hyper_cases(out_dir, cm, envs, dt, which):
+    """which = "main": every case but the last; "keep_all": RPGD with opt_keep_k_ratio 1.0 (k = N: a resampling step draws a [0, P, C]
+    block and keeps every row), run last and on its own so that a failure of the reference there is seen for what it is"""
+    import Control_Toolkit.Optimizers as tmpl
+    import SI_Toolkit.Predictors.predictor_wrapper as pw
+
+    def limits_of(envname):
+        lo, hi = HYPER_LIMITS[envname]
+        return np.array(lo, np.float32), np.array(hi, np.float32)
+
+    def header(envname, pred, cfg, lo, hi):
+        e = envs[envname]
+        d = dict(e["common"], low=lo, high=hi, predictor=np.array(pred), environment=np.array(envname),
+                 **{k: (np.float32(v) if isinstance(v, float) else np.array(v)) for k, v in cfg.items()})
+        if pred != "MLP":
+            d.pop("mlp_weights", None)
+        return d
+
+    def make(opt_name, cfg, pred, envname, lo, hi):
+        envs[envname]["inject"]()
+        pw.ENVIRONMENT = envname
+        cm.config_optimizers[opt_name] = dict(cfg)
+        ctrl = cm.controller_mpc(envname, (lo, hi), {})
+        ctrl.configure(optimizer_name=opt_name, predictor_specification=pred)
+        return ctrl
+
+    def u_prev_of(opt, C):
+        return np.broadcast_to(np.asarray(opt.u, np.float32).reshape(-1), (C,)).copy()
+
+    def rpgd_case(name, envname, c):
+        e = envs[envname]
+        lo, hi = c["limits"]
+        pred = c.get("pred", "ODE")
+        cfg = dict(seed=1, mpc_horizon=c["H"], num_rollouts=c["N"], outer_its=c["its"], sample_stdev=0.8, sample_mean=0.3,
+                   sample_whole_control_space=c["whole"], uniform_dist_min=-0.6, uniform_dist_max=0.2, resamp_per=3,
+                   period_interpolation_inducing_points=c["p"], SAMPLING_DISTRIBUTION=c["dist"], shift_previous=c["shift"], warmup=False,
+                   warmup_iterations=250, opt_keep_k_ratio=c["keep"], rtol=1e-3, mpc_timestep=dt, **HYPER_RPGD_ADAM)
+        orig_create, holder = tmpl.create_rng, {}
+
+        def recording_create(id, seed, computation_library=None):
+            holder["rec"] = RecordingRng(orig_create(id, seed, computation_library=computation_library))
+            return holder["rec"]
+        tmpl.create_rng = recording_create
+        try:
+            ctrl = make("rpgd", cfg, pred, envname, lo, hi)
+        finally:
+            tmpl.create_rng = orig_create
+        opt, rec = ctrl.optimizer, holder["rec"]
+        d = header(envname, pred, cfg, lo, hi)
+        d["reset_draws"] = rec.raw[0]
+        d["Q_init"] = opt.Q_tf.detach().numpy().copy()
+        plant = O.Predictor(kind="ODE", dt=dt, env=e["env"])
+        s = np.array(HYPER_STATES[envname], np.float32)
+        bound = 0
+        for t in range(c["steps"]):
+            ndraw = len(rec.raw)
+            u_prev = u_prev_of(opt, e["C"])
+            u = ctrl.step(s.copy())
+            d[f"s_{t}"] = s.copy(); d[f"u_prev_{t}"] = u_prev
+            d[f"u_{t}"] = np.asarray(u, np.float32).reshape(-1)
+            if len(rec.raw) > ndraw:
+                d[f"resample_draws_{t}"] = rec.raw[-1]
+            d[f"Q_{t}"] = opt.Q_tf.detach().numpy().copy()
+            d[f"u_nom_{t}"] = opt.u_nom.detach().numpy().copy()
+            stp, m_arr, v_arr = opt.opt.get_weights()
+            d[f"adam_step_{t}"] = np.int32(stp); d[f"m_{t}"] = m_arr.copy(); d[f"v_{t}"] = v_arr.copy()
+            d[f"ages_{t}"] = opt.trajectory_ages.numpy().copy()
+            s = plant_step(plant, s, u)
+        d["steps"] = np.int32(c["steps"])
+        record_rpgd_logged_outputs(d, lambda: make("rpgd", cfg, pred, envname, lo, hi), c["steps"])
+        save_fixture(os.path.join(out_dir, f"rpgd_{name}.npz"), **d)
+
+    sym = {"CartPole": (np.array([-1.0], np.float32), np.array([1.0], np.float32)), "Quad2D": (envs["Quad2D"]["low"], envs["Quad2D"]["high"])}
+    if which == "keep_all":
+        rpgd_case("hyper_keep_all", "CartPole", dict(N=24, H=12, p=4, its=2, steps=4, dist="normal", whole=True, shift=1, keep=1.0, limits=sym["CartPole"]))
+        return
+
+    # ---- MPPI: CartPole ODE and MLP, Quad2D (C = 2), Hover (C = 3) -------------------------------------------------------------------
+    for hyper, hp in HYPER_MPPI.items():
+        for tag, envname, pred, N, H, p, seed in (("cartpole", "CartPole", "ODE", 48, 14, 4, 81), ("cartpole_mlp", "CartPole", "MLP", 48, 14, 4, 82),
+                                                   ("quad2d", "Quad2D", "ODE", 40, 12, 3, 83), ("hover", "Hover", "ODE", 36, 11, 3, 84)):
+            e = envs[envname]
+            lo, hi = limits_of(envname)
+            cfg = dict(seed=seed, mpc_horizon=H, num_rollouts=N, period_interpolation_inducing_points=p, mpc_timestep=dt, **hp)
+            assert p > 1 and (H - 1) % p != 0
+            ctrl = make("mppi", cfg, pred, envname, lo, hi)
+            ctrl.controller_logging = True
+            ctrl.optimizer.optimizer_logging = True
+            opt = ctrl.optimizer
+            rec = RecordingRng(opt.rng); opt.rng = rec
+            plant = O.Predictor(kind="ODE", dt=dt, env=e["env"])
+            s = np.array(HYPER_STATES[envname], np.float32)
+            d = header(envname, pred, cfg, lo, hi)
+            d["u_nom_init"] = opt.u_nom.numpy().copy()
+            clipped = []
+            for t in range(3):
+                u_prev = u_prev_of(opt, e["C"])
+                u = ctrl.step(s.copy())
+                lv = opt.logging_values
+                d[f"s_{t}"] = s.copy(); d[f"u_prev_{t}"] = u_prev
+                d[f"noise_{t}"] = rec.raw[-1]
+                d[f"u_{t}"] = np.asarray(u, np.float32).reshape(-1)
+                d[f"u_nom_{t}"] = opt.u_nom.numpy().copy()
+                d[f"J_{t}"] = lv["J_logged"].copy(); d[f"u_run_{t}"] = lv["Q_logged"].copy()
+                d[f"traj_{t}"] = lv["rollout_trajectories_logged"].copy()
+                clipped.append(float(np.mean((d[f"u_run_{t}"] == lo) | (d[f"u_run_{t}"] == hi))))
+                s = plant_step(plant, s, u)
+            if hyper == "hyper_saturated" and envname == "CartPole":
+                assert min(clipped) > 0.5, clipped                      # more than half of the perturbed inputs sit on a limit
+            d["steps"] = np.int32(3)
+            d["clipped_share"] = np.array(clipped, np.float32)
+            save_fixture(os.path.join(out_dir, f"mppi_{hyper}_{tag}.npz"), **d)
+
+    # ---- RPGD (in-repo torch Adam): every Adam scalar moved, a clip that binds on every row, shift_previous 2 and 0 -----------------
+    rpgd_case("hyper_normal_cartpole", "CartPole", dict(N=32, H=12, p=4, its=3, steps=4, dist="normal", whole=True, shift=2, keep=0.25, limits=sym["CartPole"]))
+    rpgd_case("hyper_normal_quad2d", "Quad2D", dict(N=32, H=12, p=4, its=3, steps=4, dist="normal", whole=True, shift=2, keep=0.25, limits=sym["Quad2D"]))
+    rpgd_case("hyper_normal_cartpole_mlp", "CartPole", dict(N=48, H=12, p=4, its=3, steps=4, dist="normal", whole=True, shift=2, keep=0.25, limits=sym["CartPole"], pred="MLP"))
+    rpgd_case("hyper_uniform_cartpole", "CartPole", dict(N=32, H=12, p=4, its=3, steps=4, dist="uniform", whole=False, shift=0, keep=0.25, limits=limits_of("CartPole")))
+    rpgd_case("hyper_uniform_quad2d", "Quad2D", dict(N=32, H=12, p=4, its=3, steps=4, dist="uniform", whole=False, shift=0, keep=0.25, limits=limits_of("Quad2D")))
+
+    # ---- CEM, random-action, cem-naive-grad through the torch-backed `tf` stand-in: asymmetric limits, a saturating initial stdev, a
+    #      clamp that binds on most elements ------------------------------------------------------------------------------------------
+    def tf_controller(opt_name, cfg, envname, lo, hi):
+        orig_create, holder = tmpl.create_rng, {}
+
+        def recording_create(id, seed, computation_library=None):
+            holder["rec"] = RecordingRng(orig_create(id, seed, computation_library=computation_library))
+            return holder["rec"]
+        tmpl.create_rng = recording_create
+        try:
+            ctrl = make(opt_name, cfg, "ODE", envname, lo, hi)
+        finally:
+            tmpl.create_rng = orig_create
+        ctrl.controller_logging = True
+        ctrl.optimizer.optimizer_logging = True
+        assert ctrl.lib.lib == "TF"
+        return ctrl, holder["rec"]
+
+    set_computation_library("tensorflow")
+    try:
+        for opt_name, stem, envname, N, H in (("cem-tf", "cem_hyper_cartpole", "CartPole", 48, 12), ("cem-tf", "cem_hyper_hover", "Hover", 40, 10),
+                                              ("cem-naive-grad-tf", "cem_naive_grad_hyper_cartpole", "CartPole", 48, 12),
+                                              ("cem-naive-grad-tf", "cem_naive_grad_hyper_quad2d", "Quad2D", 40, 10)):
+            e = envs[envname]
+            lo, hi = limits_of(envname)
+            cfg = dict(seed=1, mpc_horizon=H, cem_outer_it=2, cem_initial_action_stdev=1.3, num_rollouts=N, cem_stdev_min=0.4, cem_best_k=2,
+                       mpc_timestep=dt)
+            if opt_name == "cem-tf":
+                cfg.update(warmup=False, warmup_iterations=250)
+            else:
+                cfg.update(learning_rate=0.3, gradmax_clip=0.05)
+            ctrl, rec = tf_controller(opt_name, cfg, envname, lo, hi)
+            opt = ctrl.optimizer
+            d = header(envname, "ODE", cfg, lo, hi)
+            if opt_name == "cem-tf":
+                d["dist_mue_init"] = opt.dist_mue.numpy().copy(); d["stdev_init"] = opt.stdev.numpy().copy()
+            plant = O.Predictor(kind="ODE", dt=dt, env=e["env"])
+            s = np.array(HYPER_STATES[envname], np.float32)
+            clamped = []
+            for t in range(3):
+                ndraw = len(rec.raw)
+                u_prev = u_prev_of(opt, e["C"])
+                u = ctrl.step(s.copy())
+                lv = opt.logging_values
+                d[f"s_{t}"] = s.copy(); d[f"u_prev_{t}"] = u_prev
+                d[f"noise_{t}"] = np.stack(rec.raw[ndraw:])
+                d[f"u_{t}"] = np.asarray(u, np.float32).reshape(-1)
+                d[f"dist_mue_{t}"] = opt.dist_mue.numpy().copy(); d[f"stdev_{t}"] = opt.stdev.numpy().copy()
+                d[f"J_{t}"] = np.asarray(lv["J_logged"]).copy(); d[f"Q_{t}"] = np.asarray(lv["Q_logged"]).copy()
+                if opt_name == "cem-tf":
+                    d[f"traj_{t}"] = np.asarray(lv["rollout_trajectories_logged"]).copy()
+                clamped.append(float(np.mean(d[f"stdev_{t}"][:, :-1, :] == np.float32(0.4))))
+                s = plant_step(plant, s, u)
+            d["steps"] = np.int32(3)
+            d["clamped_share"] = np.array(clamped, np.float32)
+            save_fixture(os.path.join(out_dir, f"{stem}.npz"), **d)
+
+        for stem, envname, N, H in (("random_hyper_cartpole", "CartPole", 48, 12), ("random_hyper_hover", "Hover", 40, 10)):
+            e = envs[envname]
+            lo, hi = limits_of(envname)
+            cfg = dict(seed=1, mpc_horizon=H, num_rollouts=N, mpc_timestep=dt)
+            ctrl, rec = tf_controller("random-action-tf", cfg, envname, lo, hi)
+            opt = ctrl.optimizer
+            d = header(envname, "ODE", cfg, lo, hi)
+            plant = O.Predictor(kind="ODE", dt=dt, env=e["env"])
+            s = np.array(HYPER_STATES[envname], np.float32)
+            for t in range(3):
+                u_prev = u_prev_of(opt, e["C"])
+                u = ctrl.step(s.copy())
+                lv = opt.logging_values
+                d[f"s_{t}"] = s.copy(); d[f"u_prev_{t}"] = u_prev
+                d[f"u01_{t}"] = rec.raw[-1]
+                d[f"u_{t}"] = np.asarray(u, np.float32).reshape(-1)
+                d[f"Q_{t}"] = np.asarray(lv["Q_logged"]).copy(); d[f"J_{t}"] = np.asarray(lv["J_logged"]).copy()
+                d[f"traj_{t}"] = np.asarray(lv["rollout_trajectories_logged"]).copy()
+                s = plant_step(plant, s, u)
+            d["steps"] = np.int32(3)
+            save_fixture(os.path.join(out_dir, f"{stem}.npz"), **d)
     finally:
         set_computation_library("pytorch")
         pw.ENVIRONMENT = "CartPole"
@@ -738,6 +966,11 @@ def main():
             s = plant_step(plant, s, u)
         d["steps"] = np.int32(3)
         save_fixture(os.path.join(out_dir, f"mppi_{name}.npz"), **d)
+    inject_constants(env, dt, mlp_w)
+
+    # ---- hyper-parameters away from their defaults; k = N last and on its own -----------------------------------------------------------
+    record_hyper_cases(out_dir, cm, envs, dt, "main")
+    record_hyper_cases(out_dir, cm, envs, dt, "keep_all")
     inject_constants(env, dt, mlp_w)
 
     print("golden fixtures written to", out_dir)
