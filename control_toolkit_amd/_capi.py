@@ -237,6 +237,11 @@ _PLANT_EPISODE = {
 }
 EPISODE_SYMBOLS = {f"{family}_{name}": sig for family in ("ctk_batch", "ctk_mlp_batch") for name, sig in _PLANT_EPISODE.items()}
 
+# the same closed loops for the CEM and RPGD batches (include/ctk_hip_loop.h, which ctk_hip.h includes): the entries of the two tables
+# above under these families' names, with the same signatures; a fourth table, bound with the other three
+LOOP_SYMBOLS = {f"{family}_{name}": sig for family in ("ctk_cem_batch", "ctk_rpgd_batch")
+                for name, sig in list(_PLANT_RUN.items()) + list(_PLANT_EPISODE.items())}
+
 
 # user environments (include/ctk_user_env.h): name -> path of the library that was compiled with that model (control_toolkit_amd/build_env.py:
 # register_environment); their environment id inside that library is CTK_ENV_USER
@@ -280,7 +285,7 @@ def _bind_library(path: str):
         lib = C.CDLL(path)
     except OSError as e:
         raise CtkError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()) + list(LOOP_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctk_abi_version() != 6:
@@ -1125,12 +1130,16 @@ class CtkMppiBatch(_CtkBatch):
         return self._get_state(problem, self.H * self.C + self.C)
 
 
-# ---- closed-loop episodes of an MPPI batch on the device (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_*) ---------------------------
+# ---- closed-loop episodes of a batch on the device (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_*; ctk_hip_loop.h) ------------------
 class BatchClosedLoop:
-    """CtkMppiBatch.closed_loop / CtkMppiMlpBatch.closed_loop: the batch's closed loops run on the device (kernel ctk_batch_plant<ENV>
-    between the controller launches), and the plants they run against.  Problem p's plant has, for every parameter, the value set here
-    (set_plant_params), else the problem's own current controller value: a batch that sets none controls exactly the plant it models.
-    For the MLP batch the learned network plans and the plant is the analytic CartPole."""
+    """CtkMppiBatch.closed_loop / CtkMppiMlpBatch.closed_loop, and BatchClosedLoop(cem_batch) / BatchClosedLoop(rpgd_batch) for a
+    CtkCemBatch or CtkRpgdBatch (the constructor is their way in: those classes have no closed_loop attribute): the batch's closed loops
+    run on the device (kernel ctk_batch_plant<ENV>, or the family's ctk_cem_batch_plant<ENV> / ctk_rpgd_batch_plant<ENV>, between the
+    controller launches), and the plants they run against.  A view of the batch: it owns nothing.  Problem p's plant has, for every
+    parameter, the value set here (set_plant_params), else the problem's own current controller value: a batch that sets none controls
+    exactly the plant it models.  For the MLP batch the learned network plans and the plant is the analytic CartPole.  With equal noise
+    seeds, positions, sigmas and plant tables the noisy plants of all families draw the same disturbances: optimizers can be compared
+    under common random numbers.  An RPGD problem must have been reset before its first run, as before its first step."""
 
     def __init__(self, batch):
         self._batch = batch

@@ -1,4 +1,4 @@
-// ctk_batch.hip — the batch families of the C ABI (include/ctk_hip.h, ctk_hip_run.h, ctk_hip_episode.h): ctk_batch_*, ctk_mlp_batch_*,
+// ctk_batch.hip — the batch families of the C ABI (include/ctk_hip.h, ctk_hip_run.h, ctk_hip_episode.h, ctk_hip_loop.h): ctk_batch_*, ctk_mlp_batch_*,
 // ctk_cem_batch_*, ctk_rpgd_batch_*.  The single handle is in ctk_api.hip; what the two files share is declared in ctk_host.h.
 #include <algorithm>
 #include <atomic>
@@ -20,7 +20,27 @@ using namespace ctk_host;
 // =============================================================================================
 namespace {
 
-struct BatchCore {
+// The closed loop on the device, what every family keeps for it (ctk_batch_run / ctk_batch_plant_step and their ctk_cem_batch_ /
+// ctk_rpgd_batch_ forms; kernels ctk_batch_plant<ENV> ..., ctk_plant.hip).  Problem p's PLANT has, for parameter id, the override if one
+// was set (*_plant_set_param), else the problem's own controller value table(p)[id]
+struct PlantSide {
+    std::vector<float> plant_over;          // [B][CTK_MAX_PARAMS] the overrides
+    std::vector<unsigned char> plant_has;   // [B][CTK_MAX_PARAMS] an override was set
+    std::vector<float> plant_tab;           // [B][CTK_MAX_PARAMS] the effective table the constants in h_kplant were derived from
+    std::vector<int> plant_sub;             // [B] ... and their Euler sub-step count (0: nothing derived yet)
+    unsigned char* h_kplant = nullptr;      // pinned [B][kstride] the plants' derived constants, the staging of the copy to d_kplant
+    unsigned char* d_kplant = nullptr;      // [B][kstride]
+    unsigned char* h_run = nullptr;         // pinned: the step records, plant operands and traces of one segment or plant step (LoopLayout)
+    unsigned char* d_run = nullptr;         // the same on the device; both grow on demand (batch_run_buffers)
+    size_t d_run_cap = 0, h_run_cap = 0;    // bytes
+    int run_segment = 256;                  // steps per segment of a run: a diagnostic switch may lower it (batch_core_init)
+    // the stochastic plant (include/ctk_hip_episode.h: ctk_batch_episodes / ctk_batch_plant_step_noisy; kernel ctk_batch_plant_noisy<ENV>)
+    std::vector<float> noise_sigma;         // [B][2][CTK_MAX_STATES] process | measurement standard deviations (0: none)
+    std::vector<uint64_t> noise_seed;       // [B] Philox key of the problem's noise (at creation: its controller seed)
+    std::vector<uint32_t> noise_pos;        // [B] noise position: one per transition of the noisy plant
+};
+
+struct BatchCore : PlantSide {
     ctk_config cfg{};
     int B = 0, N = 0, H = 0, env = CTK_ENV_CARTPOLE, S = CTK_S, C = CTK_C, HC = 0;
     float params[CTK_MAX_PARAMS]{};         // the shared table: the last whole-batch value of every id (*_batch_set_param / get_param)
@@ -65,8 +85,16 @@ int bfail(BatchCore* b, int code, const std::string& msg) {
             return bfail((b), CTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
     } while (0)
 
+// a diagnostic switch of the environment that only lowers a limit (values from 1 up to the limit)
+void batch_env_lowers(const char* name, int* limit) {
+    const char* e = std::getenv(name);
+    if (e && std::atoi(e) >= 1 && std::atoi(e) < *limit) *limit = std::atoi(e);
+}
+// the seed of problem p: the caller's, or consecutive ones from the configuration's
+uint64_t batch_seed(const ctk_config* cfg, const uint64_t* seeds, int p) { return seeds ? seeds[p] : cfg->seed + (uint64_t)p; }
+
 // the fields of the core that depend on the configuration alone (every family's create, after its refusals)
-void batch_core_init(BatchCore* b, const ctk_config* cfg, const EnvInfo* einfo, int n_problems) {
+void batch_core_init(BatchCore* b, const ctk_config* cfg, const EnvInfo* einfo, int n_problems, const uint64_t* seeds) {
     b->cfg = *cfg;
     b->B = n_problems; b->N = cfg->num_rollouts; b->H = cfg->mpc_horizon;
     b->env = cfg->environment; b->S = einfo->S; b->C = einfo->C; b->HC = b->H * b->C;
@@ -76,15 +104,18 @@ void batch_core_init(BatchCore* b, const ctk_config* cfg, const EnvInfo* einfo, 
     b->dirty.assign((size_t)n_problems, 1);            // nothing derived yet: the per-problem form derives what it steps (MPPI: all of them)
     b->kstride = ctk_mppi_batch_k_stride(b->env);
     b->seq.assign((size_t)n_problems, 1u); b->call.assign((size_t)n_problems, 0u);
+    // A long run goes in segments of this many steps, so that its record buffer stays bounded (256 steps of 128 problems: 2.5 MiB of
+    // records).  CTK_BATCH_RUN_SEGMENT_STEPS (diagnostic) only lowers it; the results do not depend on it.
+    batch_env_lowers("CTK_BATCH_RUN_SEGMENT_STEPS", &b->run_segment);
+    b->plant_over.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
+    b->plant_has.assign((size_t)n_problems * CTK_MAX_PARAMS, 0);
+    b->plant_tab.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
+    b->plant_sub.assign((size_t)n_problems, 0);
+    b->noise_sigma.assign((size_t)n_problems * 2 * CTK_MAX_STATES, 0.0f);
+    b->noise_seed.resize((size_t)n_problems);
+    for (int p = 0; p < n_problems; ++p) b->noise_seed[(size_t)p] = batch_seed(cfg, seeds, p);   // the controller's
+    b->noise_pos.assign((size_t)n_problems, 0u);
 }
-
-// a diagnostic switch of the environment that only lowers a limit (values from 1 up to the limit)
-void batch_env_lowers(const char* name, int* limit) {
-    const char* e = std::getenv(name);
-    if (e && std::atoi(e) >= 1 && std::atoi(e) < *limit) *limit = std::atoi(e);
-}
-// the seed of problem p: the caller's, or consecutive ones from the configuration's
-uint64_t batch_seed(const ctk_config* cfg, const uint64_t* seeds, int p) { return seeds ? seeds[p] : cfg->seed + (uint64_t)p; }
 
 // everything a batch owns on the device and in pinned memory; no HIP call for a batch that was refused before it opened anything
 void batch_core_release(BatchCore* b) {
@@ -104,6 +135,8 @@ int batch_core_open(BatchCore* b) {
     HIP_CREATE(b->own.dev_zero(&b->d_u, (size_t)b->B * CTK_MAX_INPUTS * sizeof(float), b->stream));
     HIP_CREATE(b->own.pinned_zero(&b->h_u, (size_t)b->B * 64, hipHostMallocMapped | hipHostMallocCoherent));
     HIP_CREATE(hipHostGetDevicePointer((void**)&b->h_u_dev, b->h_u, 0));
+    HIP_CREATE(b->own.dev_zero(&b->d_kplant, (size_t)b->B * b->kstride, b->stream));
+    HIP_CREATE(b->own.pinned_zero(&b->h_kplant, (size_t)b->B * b->kstride));
     return CTK_OK;
 }
 
@@ -152,6 +185,20 @@ void batch_record_io(const BatchCore* b, Rec& q, int j, const float* s, const fl
     for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
 }
 
+// The per-problem form of the CEM and RPGD kernels takes the constants by record index: those of the n listed problems into h_k, in
+// listed order.  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses; kcache is by
+// problem id.
+void batch_stage_constants(BatchCore* b, unsigned char* kcache, const int32_t* ids, int n, unsigned char* h_k) {
+    for (int j = 0; j < n; ++j) {
+        const size_t z = (size_t)(ids ? ids[j] : j);
+        if (b->dirty[z]) {
+            ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, kcache + z * b->kstride);
+            b->dirty[z] = 0;
+        }
+        std::memcpy(h_k + (size_t)j * b->kstride, kcache + z * b->kstride, b->kstride);
+    }
+}
+
 // The step records of the CEM and RPGD steps to the device, n of `rec` bytes each.  In the per-problem form the constants of the n
 // problems lie right behind the n records, in the records' order, so that ONE transfer carries both (*d_ksteps: where they land, else
 // NULL).  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses (ctk_set_param ->
@@ -161,15 +208,7 @@ hipError_t batch_send_records(BatchCore* b, unsigned char* kcache, const int32_t
     size_t bytes = (size_t)n * rec;
     *d_ksteps = nullptr;
     if (b->differ) {
-        unsigned char* h_k = static_cast<unsigned char*>(h_steps) + bytes;
-        for (int j = 0; j < n; ++j) {
-            const size_t z = (size_t)(ids ? ids[j] : j);
-            if (b->dirty[z]) {
-                ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, kcache + z * b->kstride);
-                b->dirty[z] = 0;
-            }
-            std::memcpy(h_k + (size_t)j * b->kstride, kcache + z * b->kstride, b->kstride);
-        }
+        batch_stage_constants(b, kcache, ids, n, static_cast<unsigned char*>(h_steps) + bytes);
         *d_ksteps = static_cast<const unsigned char*>(d_steps) + bytes;
         bytes += (size_t)n * b->kstride;
     }
@@ -316,6 +355,448 @@ int batch_read_out(BatchCore* b, const char* who, const float* src, size_t n, bo
     return CTK_OK;
 }
 
+// =============================================================================================
+// The closed loop on the device (include/ctk_hip_run.h, ctk_hip_episode.h, ctk_hip_loop.h): ONE driver for every family.  What is a
+// family's own is a small trait (MppiLoop, CemLoop, RpgdLoop, each below its family's struct):
+//   Batch, Rec            the handle and its step record (every record type has id, s[], u_prev[] and dev_uprev)
+//   carries_k             the per-problem form's constants travel behind the step records and are taken by record index (CEM, RPGD);
+//                         else they live in an array by problem id that `constants` refreshes (MPPI)
+//   error_word            the kernel has an in-launch hand-off whose error word is read and cleared (MPPI, CEM)
+//   refuse(b, who, n, ids)               the family's own refusal, before anything is launched
+//   context(b)                           what all its launches share
+//   constants(b, ids, n, h_k)            the per-problem form's constants ahead of a segment's records
+//   fill(b, q, p, t)                     the record of the step problem p takes t steps from now: every counter, no draws
+//   launch(b, ctx, d_rec, n, d_k, &launched)   the controller launches of n records of ONE step, split as the family's step splits them
+//   advance(b, p, ctrl, tried, issued)   the counters of problem p after `ctrl` steps that were launched in full and, if `tried`, one more
+//                                        whose launches failed, this problem's among them (`issued`) or not
+// =============================================================================================
+
+// The plants' constants ahead of a run or a plant step: problem p's effective table (override, else its own controller value) and the
+// sub-step count against what h_kplant was derived from; those that changed are re-derived with the function the controller's
+// constants come from, and the span from the first to the last of them travels in ONE transfer on the batch's stream (none when
+// nothing changed).  The caller synchronises before it returns, so the staging is free again at the next call.
+hipError_t batch_plant_flush(BatchCore* b, int substeps) {
+    int lo = b->B, hi = -1;
+    float eff[CTK_MAX_PARAMS];
+    for (int p = 0; p < b->B; ++p) {
+        const size_t z = (size_t)p * CTK_MAX_PARAMS;
+        for (int i = 0; i < CTK_MAX_PARAMS; ++i) eff[i] = b->plant_has[z + i] ? b->plant_over[z + i] : b->table(p)[i];
+        if (b->plant_sub[(size_t)p] == substeps && std::memcmp(eff, &b->plant_tab[z], sizeof(eff)) == 0) continue;
+        ctk_mppi_batch_derive_k(b->env, eff, b->cfg.dt, substeps, b->h_kplant + (size_t)p * b->kstride);
+        std::memcpy(&b->plant_tab[z], eff, sizeof(eff));
+        b->plant_sub[(size_t)p] = substeps;
+        lo = std::min(lo, p); hi = p;
+    }
+    if (hi < 0) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(b->d_kplant + (size_t)lo * b->kstride, b->h_kplant + (size_t)lo * b->kstride, (size_t)(hi - lo + 1) * b->kstride,
+                                        hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess) for (int p = lo; p <= hi; ++p) b->plant_sub[(size_t)p] = 0;      // nothing reached the device: derive and copy again
+    return e;
+}
+
+// Where the parts of the run buffer lie for a segment of n problems and L steps (bytes from its start; every part 16-aligned).  What
+// travels to the device in ONE transfer lies in front (up to `states`), what comes back in ONE copy behind it:
+//   step records [L][n] | per-problem constants [n] | inputs of a plant step [n][C] | true start states [n][S] |
+//   previous inputs of the first step [n][C] | noise records [n] || state trace [n][L][S] | observation trace [n][L][S] |
+//   input trace [n][L][C] | realised costs [n][L]
+// The constants are there only in the per-problem form of a family whose kernels take them by record index (kbytes, else 0): ONE block
+// of n elements in listed order behind all L * n records, which every step's launches read.  The parts only the noisy plant has
+// (s_start, u_start, noise, obs, costs) are empty without it: what then remains is
+//   step records | constants | inputs of a plant step || state trace | input trace.
+struct LoopLayout {
+    size_t k, u_in, s_start, u_start, noise, states, obs, inputs, costs, total;
+    LoopLayout(const BatchCore* b, size_t rec, size_t kbytes, int n, int L, bool noisy) {
+        auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        auto ep = [&](size_t x) { return noisy ? x : 0; };
+        k = (size_t)L * n * rec;
+        u_in = k + up(kbytes);
+        s_start = u_in + up((size_t)n * b->C * sizeof(float));
+        u_start = s_start + ep(up((size_t)n * b->S * sizeof(float)));
+        noise = u_start + ep(up((size_t)n * b->C * sizeof(float)));
+        states = noise + ep((size_t)n * sizeof(CtkPlantNoise));
+        obs = states + up((size_t)n * L * b->S * sizeof(float));
+        inputs = obs + ep(up((size_t)n * L * b->S * sizeof(float)));
+        costs = inputs + up((size_t)n * L * b->C * sizeof(float));
+        total = costs + ep(up((size_t)n * L * sizeof(float)));
+    }
+};
+static_assert(sizeof(CtkBatchStep) % 16 == 0 && sizeof(CtkCemBatchStep) % 16 == 0 && sizeof(CtkRpgdBatchStep) % 16 == 0,
+              "the parts of the run buffer lie behind the step records, 16-aligned");
+static_assert(sizeof(CtkPlantNoise) % 16 == 0, "the traces lie behind the noise records, 16-aligned");
+
+// the run buffer (device and pinned), grown to the layout's bytes on demand
+int batch_run_buffers(BatchCore* b, const LoopLayout& lay) {
+    BHIP_TRY(b, b->own.grow_dev(b->d_run, b->d_run_cap, lay.total));
+    BHIP_TRY(b, b->own.grow_pin(b->h_run, b->h_run_cap, lay.total));
+    return CTK_OK;
+}
+
+// problem p's noise record at its current position
+void batch_noise_record(const BatchCore* b, int p, CtkPlantNoise* q) {
+    const float* sg = &b->noise_sigma[(size_t)p * 2 * CTK_MAX_STATES];
+    q->any = 0u;
+    for (int i = 0; i < CTK_MAX_STATES; ++i) {
+        q->sigma_w[i] = i < b->S ? sg[i] : 0.0f;
+        q->sigma_v[i] = i < b->S ? sg[CTK_MAX_STATES + i] : 0.0f;
+        if (q->sigma_w[i] != 0.0f || q->sigma_v[i] != 0.0f) q->any = 1u;
+    }
+    q->seed_lo = (uint32_t)(b->noise_seed[(size_t)p] & 0xFFFFFFFFull); q->seed_hi = (uint32_t)(b->noise_seed[(size_t)p] >> 32);
+    q->pos = b->noise_pos[(size_t)p];
+}
+
+int batch_substeps(BatchCore* b, const char* who, int substeps, int* out) {
+    if (substeps < 0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": the plant's sub-step count must be >= 1, or 0 for cfg.intermediate_steps (" + std::to_string(substeps) + ")");
+    *out = substeps ? substeps : b->cfg.intermediate_steps;
+    return CTK_OK;
+}
+
+// One plant step of the listed problems (*_plant_step; with y_next, *_plant_step_noisy): the records, the inputs and what the noisy
+// plant reads besides travel in ONE transfer, one launch, one copy back, one synchronisation.
+template <class F>
+int batch_plant_step(typename F::Batch* b, const char* who, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev,
+                     int substeps, float* s_next, float* y_next, float* cost) {
+    using Rec = typename F::Rec;
+    const bool noisy = y_next != nullptr;
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (int rc = batch_substeps(b, who, substeps, &sub)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const LoopLayout lay(b, sizeof(Rec), 0, n, 1, noisy);
+    if (int rc = batch_run_buffers(b, lay)) return rc;
+    // the records carry the problem and, for the plain plant, its state; the noisy plant reads the state from a row of its own
+    Rec* rec = reinterpret_cast<Rec*>(b->h_run);
+    CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
+    for (int j = 0; j < n; ++j) {
+        std::memset(&rec[j], 0, sizeof(Rec));
+        rec[j].id = ids ? ids[j] : j;
+        if (noisy) batch_noise_record(b, rec[j].id, &nz[j]);
+        else for (int i = 0; i < S; ++i) rec[j].s[i] = s[(size_t)j * S + i];
+    }
+    std::memcpy(b->h_run + lay.u_in, u, (size_t)n * C * sizeof(float));
+    if (noisy) {
+        std::memcpy(b->h_run + lay.s_start, s, (size_t)n * S * sizeof(float));
+        std::memcpy(b->h_run + lay.u_start, u_prev, (size_t)n * C * sizeof(float));
+    }
+    const Rec* d_rec = reinterpret_cast<const Rec*>(b->d_run);
+    auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+    const size_t back = noisy ? lay.total - lay.states : (size_t)n * S * sizeof(float);      // the plain plant wrote the next states alone
+    hipError_t le = batch_plant_flush(b, sub);
+    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
+    bool launched = false;
+    if (le == hipSuccess) {
+        if (noisy)
+            le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec, nullptr, b->d_kplant,
+                                              reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise), dev(lay.u_in), dev(lay.s_start), (size_t)S,
+                                              dev(lay.u_start), (size_t)C, 0u, dev(lay.states), dev(lay.obs), nullptr, dev(lay.costs), n, (size_t)S, 0, 1);
+        else
+            le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec, nullptr, b->d_kplant, dev(lay.u_in), dev(lay.states), nullptr, n,
+                                        (size_t)S, 0);
+        launched = le == hipSuccess;
+    }
+    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, back, hipMemcpyDeviceToHost, b->stream);
+    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
+    if (le == hipSuccess) le = se;
+    if (noisy && launched)
+        for (int j = 0; j < n; ++j) ++b->noise_pos[(size_t)rec[j].id];         // by the plant launch that was issued
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string(who) + ": " + hipGetErrorString(le));
+    std::memcpy(s_next, b->h_run + lay.states, (size_t)n * S * sizeof(float));
+    if (noisy) {
+        std::memcpy(y_next, b->h_run + lay.obs, (size_t)n * S * sizeof(float));
+        std::memcpy(cost, b->h_run + lay.costs, (size_t)n * sizeof(float));
+    }
+    return CTK_OK;
+}
+
+// The counters after a segment of L steps whose launches ended with `le`.  `ctrl` steps had the controllers of all n listed problems
+// launched; if the launches of the step after them failed (part >= 0), those of its first `part` problems were; `plants` launches of
+// the noisy plant were issued (a run: 0).  The family's counters and noise_pos are left as if exactly these had run, by the rule of the
+// family's step (F::advance).  Only where nothing failed, a problem whose slot does not show the segment's last step is listed in
+// `late`; the hand-off's error word, where the family has one, is read and cleared into timed[j] whatever happened.
+template <class F>
+void batch_loop_account(typename F::Batch* b, int n, const int32_t* ids, hipError_t le, int L, int ctrl, int part, int plants, std::string& late,
+                        std::vector<unsigned char>& timed) {
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
+        if (le == hipSuccess && slot[1] != b->seq[(size_t)p] + (uint32_t)(L - 1)) list_problem(late, p);
+        if (F::error_word && slot[2]) { slot[2] = 0; timed[(size_t)j] = 1; }  // the hand-off's error word, read and cleared
+        F::advance(b, p, ctrl, part >= 0, j < part);
+        b->noise_pos[(size_t)p] += (uint32_t)plants;
+    }
+}
+
+// a closed-loop call: *_run, or with obs_out (and costs_out) *_episodes
+struct LoopCall {
+    const char* who;                        // the entry point, for the messages
+    const char* noun;                       // "a run" / "an episode"
+    int n_ids; const int32_t* ids;
+    const float *s0, *y0, *u_prev;
+    int n_steps, plant_substeps;
+    float *states_out, *obs_out, *inputs_out, *costs_out;
+    int32_t* first_bad;
+};
+
+// The closed loop on the device, in segments of at most run_segment steps.  A segment is ONE transfer of its step records (and what the
+// noisy plant reads at its first step), per step the controller launches and one plant launch, ONE copy of the traces back and ONE
+// synchronisation; the plant launch of step t writes the state (the noisy plant: the observation) into the records of step t + 1 on the
+// device.  The noisy plant differs in where it reads from (the true state and the previous input have rows of their own, see
+// ctk_plant.hip), in its noise positions and in the two further traces.
+template <class F>
+int batch_closed_loop(typename F::Batch* b, const LoopCall& c) {
+    using Rec = typename F::Rec;
+    const bool noisy = c.obs_out != nullptr;
+    const int32_t* ids = c.ids;
+    const float* u_prev = c.u_prev;
+    const int n_steps = c.n_steps;
+    int n = 0, sub = 0;
+    if (int rc = batch_ids(b, c.who, c.n_ids, ids, &n)) return rc;
+    if (n_steps < 1)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(c.who) + ": " + c.noun + " has at least one step (n_steps == " + std::to_string(n_steps) + ")");
+    if (int rc = batch_substeps(b, c.who, c.plant_substeps, &sub)) return rc;
+    if (int rc = F::refuse(b, c.who, n, ids)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C;
+    const size_t srow = ((size_t)n_steps + 1) * S, urow = (size_t)n_steps * C;       // one problem's rows of the traces
+    for (int j = 0; j < n; ++j) {
+        std::memcpy(c.states_out + (size_t)j * srow, c.s0 + (size_t)j * S, (size_t)S * sizeof(float));
+        if (noisy) std::memcpy(c.obs_out + (size_t)j * srow, (c.y0 ? c.y0 : c.s0) + (size_t)j * S, (size_t)S * sizeof(float));
+        if (c.first_bad) c.first_bad[j] = -1;
+    }
+    // The noisy plant without u_prev: the first step's previous input is what the first controller launch reads as its own — the problem's
+    // last output in d_u (*_set_state writes it too, the pinned result slot only holds what a step published).  That launch
+    // overwrites it, so the span of the listed problems is read here, once per call, ahead of everything else.  A run has no use for it.
+    const int p_lo = ids ? ids[0] : 0, p_hi = ids ? ids[n - 1] : n - 1;
+    std::vector<float> own_u;
+    if (noisy && !u_prev) {
+        own_u.resize((size_t)(p_hi - p_lo + 1) * CTK_MAX_INPUTS);
+        BHIP_TRY(b, hipMemcpyAsync(own_u.data(), b->d_u + (size_t)p_lo * CTK_MAX_INPUTS, own_u.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+        BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    }
+    const float* first_s = noisy ? c.obs_out : c.states_out;                   // what the controllers see: of a run the state itself
+    std::vector<unsigned char> timed((size_t)n, 0);
+    std::string late;
+    const auto ctx = F::context(b);
+    const size_t kbytes = (F::carries_k && b->differ) ? (size_t)n * b->kstride : 0;
+    hipError_t le = batch_plant_flush(b, sub);
+    for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
+        const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
+        const LoopLayout lay(b, sizeof(Rec), kbytes, n, L, noisy);
+        if (int rc = batch_run_buffers(b, lay)) { hipStreamSynchronize(b->stream); return rc; }
+        // every record of the segment: all but the state is known in advance.  The state of the segment's first step is the host's (the
+        // start state or observation, or the previous segment's last one from the copied trace); the later ones the plant launches write
+        // on the device.
+        Rec* rec = reinterpret_cast<Rec*>(b->h_run);
+        for (int t = 0; t < L; ++t) {
+            const bool given = k0 + t == 0 && u_prev;                          // from the second step on: the problem's own last output
+            for (int j = 0; j < n; ++j) {
+                Rec& q = rec[(size_t)t * n + j];
+                F::fill(b, q, ids ? ids[j] : j, t);
+                q.dev_uprev = given ? 0u : 1u;
+                for (int i = 0; i < CTK_MAX_STATES; ++i) q.s[i] = (t == 0 && i < S) ? first_s[(size_t)j * srow + (size_t)k0 * S + i] : 0.0f;
+                for (int i = 0; i < CTK_MAX_INPUTS; ++i) q.u_prev[i] = (given && i < C) ? u_prev[(size_t)j * C + i] : 0.0f;
+            }
+        }
+        // what the first noisy plant launch of the segment reads in place of trace rows: the true state, and the input before the
+        // segment's first one — the given u_prev, the previous segment's last input, or the problem's own last output (read above)
+        if (noisy) {
+            float* h_s = reinterpret_cast<float*>(b->h_run + lay.s_start);
+            float* h_up = reinterpret_cast<float*>(b->h_run + lay.u_start);
+            CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
+            for (int j = 0; j < n; ++j) {
+                const int p = ids ? ids[j] : j;
+                std::memcpy(h_s + (size_t)j * S, c.states_out + (size_t)j * srow + (size_t)k0 * S, (size_t)S * sizeof(float));
+                if (k0 > 0) std::memcpy(h_up + (size_t)j * C, c.inputs_out + (size_t)j * urow + ((size_t)k0 - 1) * C, (size_t)C * sizeof(float));
+                else if (u_prev) std::memcpy(h_up + (size_t)j * C, u_prev + (size_t)j * C, (size_t)C * sizeof(float));
+                else std::memcpy(h_up + (size_t)j * C, &own_u[(size_t)(p - p_lo) * CTK_MAX_INPUTS], (size_t)C * sizeof(float));
+                batch_noise_record(b, p, &nz[j]);
+            }
+        }
+        Rec* d_rec = reinterpret_cast<Rec*>(b->d_run);
+        auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+        const CtkPlantNoise* d_nz = reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise);
+        const unsigned char* d_k = kbytes ? b->d_run + lay.k : nullptr;        // behind all L * n records: every step's launches read it
+        float *d_st = dev(lay.states), *d_ob = dev(lay.obs), *d_in = dev(lay.inputs), *d_co = dev(lay.costs);
+        le = F::constants(b, ids, n, b->h_run + lay.k);                        // MPPI: a transfer of its own, ahead of the step records'
+        if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, noisy ? lay.states : lay.u_in, hipMemcpyHostToDevice, b->stream);
+        int ctrl = 0, part = -1, plants = 0;           // steps whose controllers were all launched; of the step whose launches failed, how
+                                                       // many were; the noisy plant launches that were issued
+        for (int t = 0; le == hipSuccess && t < L; ++t) {
+            int launched = 0;
+            le = F::launch(b, ctx, d_rec + (size_t)t * n, n, d_k, &launched);
+            if (le != hipSuccess) { part = launched; break; }
+            ++ctrl;
+            Rec* next = t + 1 < L ? d_rec + (size_t)(t + 1) * n : nullptr;
+            if (noisy) {
+                le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, next, b->d_kplant, d_nz, nullptr,
+                                                  t ? d_st + (size_t)(t - 1) * S : dev(lay.s_start), t ? (size_t)L * S : (size_t)S,
+                                                  t ? d_in + (size_t)(t - 1) * C : dev(lay.u_start), t ? (size_t)L * C : (size_t)C, (uint32_t)t,
+                                                  d_st + (size_t)t * S, d_ob + (size_t)t * S, d_in + (size_t)t * C, d_co + t, n, (size_t)L * S, (size_t)L * C,
+                                                  (size_t)L);
+                if (le == hipSuccess) ++plants;
+            } else {
+                le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, next, b->d_kplant, nullptr, d_st + (size_t)t * S,
+                                            d_in + (size_t)t * C, n, (size_t)L * S, (size_t)L * C);
+            }
+        }
+        if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
+        const hipError_t se = hipStreamSynchronize(b->stream);                 // ONE synchronisation per segment, whatever happened
+        if (le == hipSuccess) le = se;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        batch_loop_account<F>(b, n, ids, le, L, ctrl, part, plants, late, timed);  // the counters reflect what was launched
+        if (le != hipSuccess) break;
+        auto host = [&](size_t at) { return reinterpret_cast<const float*>(b->h_run + at); };
+        const float *h_st = host(lay.states), *h_ob = host(lay.obs), *h_in = host(lay.inputs), *h_co = host(lay.costs);
+        for (int j = 0; j < n; ++j) {
+            std::memcpy(c.states_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_st + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+            std::memcpy(c.inputs_out + (size_t)j * urow + (size_t)k0 * C, h_in + (size_t)j * L * C, (size_t)L * C * sizeof(float));
+            if (noisy) {
+                std::memcpy(c.obs_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_ob + (size_t)j * L * S, (size_t)L * S * sizeof(float));
+                std::memcpy(c.costs_out + (size_t)j * n_steps + (size_t)k0, h_co + (size_t)j * L, (size_t)L * sizeof(float));
+            }
+            if (c.first_bad && c.first_bad[j] < 0)
+                for (int i = 0; i < L * C; ++i)
+                    if (!std::isfinite(h_in[(size_t)j * L * C + i])) { c.first_bad[j] = k0 + i / C; break; }
+        }
+        k0 += L;
+    }
+    if (le != hipSuccess)
+        return bfail(b, CTK_ERR_HIP, std::string(c.who) + ": " + hipGetErrorString(le) + " (the counters reflect the steps that were launched; the traces are not valid)");
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, std::string(c.who) + ": a segment finished without publishing the last result of problem(s) " + late);
+    std::string timed_out;
+    for (int j = 0; j < n; ++j)
+        if (timed[(size_t)j]) list_problem(timed_out, ids ? ids[j] : j);
+    if (!timed_out.empty())
+        return bfail(b, CTK_ERR_STATE, std::string(c.who) + ": in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
+                     "; such a step publishes NaN and the plant propagates it: their traces show where (first_bad), the other problems' traces are valid");
+    return CTK_OK;
+}
+
+// ---- the bodies of every family's plant and noise entries (include/ctk_hip_run.h, ctk_hip_episode.h, ctk_hip_loop.h); `who` is the entry's name ----
+int plant_set_param(BatchCore* b, const char* who, int n_ids, const int32_t* ids, int id, const float* values) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (int rc = batch_param_id(b, who, id)) return rc;
+    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL values (one value per listed problem)");
+    for (int j = 0; j < n; ++j) {
+        const size_t z = (size_t)(ids ? ids[j] : j) * CTK_MAX_PARAMS + (size_t)id;
+        b->plant_over[z] = values[j];                  // derived at the next run or plant step (batch_plant_flush compares the tables)
+        b->plant_has[z] = 1;
+    }
+    return CTK_OK;
+}
+int plant_get_param(const BatchCore* b, int problem, int id, float* value) {
+    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
+    const size_t z = (size_t)problem * CTK_MAX_PARAMS + (size_t)id;
+    *value = b->plant_has[z] ? b->plant_over[z] : b->table(problem)[id];
+    return CTK_OK;
+}
+int plant_clear_params(BatchCore* b) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    std::fill(b->plant_has.begin(), b->plant_has.end(), (unsigned char)0);
+    return CTK_OK;
+}
+int plant_set_noise(BatchCore* b, const char* who, int n_ids, const int32_t* ids, int kind, const float* sigma) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (kind != 0 && kind != 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": kind is 0 (process noise) or 1 (measurement noise), not " + std::to_string(kind));
+    if (!sigma) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL sigma (one row of num_states values per listed problem)");
+    for (int i = 0; i < n * b->S; ++i)
+        if (!(std::isfinite(sigma[i]) && sigma[i] >= 0.0f))
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": a standard deviation is finite and >= 0 (" + std::to_string(sigma[i]) + " for problem " +
+                         std::to_string(ids ? ids[i / b->S] : i / b->S) + ", state " + std::to_string(i % b->S) + "); nothing was written");
+    for (int j = 0; j < n; ++j) {
+        float* dst = &b->noise_sigma[((size_t)(ids ? ids[j] : j) * 2 + (size_t)kind) * CTK_MAX_STATES];
+        for (int i = 0; i < b->S; ++i) dst[i] = sigma[(size_t)j * b->S + i] == 0.0f ? 0.0f : sigma[(size_t)j * b->S + i];   // -0.0 is "none" too
+    }
+    return CTK_OK;
+}
+int plant_get_noise(const BatchCore* b, int problem, int kind, float* sigma) {
+    if (!b || !sigma || problem < 0 || problem >= b->B || (kind != 0 && kind != 1)) return CTK_ERR_INVALID_ARGUMENT;
+    std::memcpy(sigma, &b->noise_sigma[((size_t)problem * 2 + (size_t)kind) * CTK_MAX_STATES], (size_t)b->S * sizeof(float));
+    return CTK_OK;
+}
+int plant_clear_noise(BatchCore* b) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    std::fill(b->noise_sigma.begin(), b->noise_sigma.end(), 0.0f);
+    return CTK_OK;
+}
+int plant_set_noise_seed(BatchCore* b, const char* who, int n_ids, const int32_t* ids, const uint64_t* seeds) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (!seeds) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL seeds (one per listed problem)");
+    for (int j = 0; j < n; ++j) b->noise_seed[(size_t)(ids ? ids[j] : j)] = seeds[j];
+    return CTK_OK;
+}
+int plant_get_noise_seed(const BatchCore* b, int problem, uint64_t* seed) {
+    if (!b || !seed || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *seed = b->noise_seed[(size_t)problem];
+    return CTK_OK;
+}
+int plant_noise_get_position(const BatchCore* b, int problem, uint32_t* pos) {
+    if (!b || !pos || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    *pos = b->noise_pos[(size_t)problem];
+    return CTK_OK;
+}
+int plant_noise_set_position(BatchCore* b, const char* who, int problem, uint32_t pos) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = batch_problem(b, who, problem)) return rc;
+    b->noise_pos[(size_t)problem] = pos;
+    return CTK_OK;
+}
+
+// The fourteen closed-loop entries of a family, FAM in {ctk_batch, ctk_cem_batch, ctk_rpgd_batch} with its trait: the bodies above under
+// the family's names (the MLP family forwards to ctk_batch's, further down)
+#define CTK_LOOP_ENTRIES(FAM, TRAIT)                                                                                                                  \
+    int FAM##_plant_set_param(FAM* b, int n_ids, const int32_t* ids, int id, const float* values) {                                                   \
+        return plant_set_param(b, #FAM "_plant_set_param", n_ids, ids, id, values);                                                                   \
+    }                                                                                                                                                 \
+    int FAM##_plant_get_param(const FAM* b, int problem, int id, float* value) { return plant_get_param(b, problem, id, value); }                     \
+    int FAM##_plant_clear_params(FAM* b) { return plant_clear_params(b); }                                                                            \
+    int FAM##_plant_step(FAM* b, int n_ids, const int32_t* ids, const float* s, const float* u, int substeps, float* s_next) {                        \
+        if (!b) return CTK_ERR_INVALID_ARGUMENT;                                                                                                      \
+        if (!s || !u || !s_next) return bfail(b, CTK_ERR_INVALID_ARGUMENT, #FAM "_plant_step: NULL state, input or destination");                     \
+        return batch_plant_step<TRAIT>(b, #FAM "_plant_step", n_ids, ids, s, u, nullptr, substeps, s_next, nullptr, nullptr);                         \
+    }                                                                                                                                                 \
+    int FAM##_run(FAM* b, int n_ids, const int32_t* ids, const float* s0, const float* u_prev, int n_steps, int plant_substeps, float* states_out,    \
+                  float* inputs_out, int32_t* first_bad) {                                                                                            \
+        if (!b) return CTK_ERR_INVALID_ARGUMENT;                                                                                                      \
+        if (!s0 || !states_out || !inputs_out) return bfail(b, CTK_ERR_INVALID_ARGUMENT, #FAM "_run: NULL start states or trace destination");        \
+        return batch_closed_loop<TRAIT>(b, LoopCall{#FAM "_run", "a run", n_ids, ids, s0, nullptr, u_prev, n_steps, plant_substeps, states_out,       \
+                                                    nullptr, inputs_out, nullptr, first_bad});                                                        \
+    }                                                                                                                                                 \
+    int FAM##_plant_set_noise(FAM* b, int n_ids, const int32_t* ids, int kind, const float* sigma) {                                                  \
+        return plant_set_noise(b, #FAM "_plant_set_noise", n_ids, ids, kind, sigma);                                                                  \
+    }                                                                                                                                                 \
+    int FAM##_plant_get_noise(const FAM* b, int problem, int kind, float* sigma) { return plant_get_noise(b, problem, kind, sigma); }                 \
+    int FAM##_plant_clear_noise(FAM* b) { return plant_clear_noise(b); }                                                                              \
+    int FAM##_plant_set_noise_seed(FAM* b, int n_ids, const int32_t* ids, const uint64_t* seeds) {                                                    \
+        return plant_set_noise_seed(b, #FAM "_plant_set_noise_seed", n_ids, ids, seeds);                                                              \
+    }                                                                                                                                                 \
+    int FAM##_plant_get_noise_seed(const FAM* b, int problem, uint64_t* seed) { return plant_get_noise_seed(b, problem, seed); }                      \
+    int FAM##_plant_noise_get_position(const FAM* b, int problem, uint32_t* pos) { return plant_noise_get_position(b, problem, pos); }                \
+    int FAM##_plant_noise_set_position(FAM* b, int problem, uint32_t pos) {                                                                           \
+        return plant_noise_set_position(b, #FAM "_plant_noise_set_position", problem, pos);                                                           \
+    }                                                                                                                                                 \
+    int FAM##_plant_step_noisy(FAM* b, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev, int substeps,              \
+                               float* s_next, float* y_next, float* cost) {                                                                           \
+        if (!b) return CTK_ERR_INVALID_ARGUMENT;                                                                                                      \
+        if (!s || !u || !u_prev || !s_next || !y_next || !cost)                                                                                       \
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, #FAM "_plant_step_noisy: NULL state, input, previous input or destination");                    \
+        return batch_plant_step<TRAIT>(b, #FAM "_plant_step_noisy", n_ids, ids, s, u, u_prev, substeps, s_next, y_next, cost);                        \
+    }                                                                                                                                                 \
+    int FAM##_episodes(FAM* b, int n_ids, const int32_t* ids, const float* s0, const float* y0, const float* u_prev, int n_steps, int plant_substeps, \
+                       float* states_out, float* obs_out, float* inputs_out, float* costs_out, int32_t* first_bad) {                                  \
+        if (!b) return CTK_ERR_INVALID_ARGUMENT;                                                                                                      \
+        if (!s0 || !states_out || !obs_out || !inputs_out || !costs_out)                                                                              \
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, #FAM "_episodes: NULL start states or trace destination");                                      \
+        return batch_closed_loop<TRAIT>(b, LoopCall{#FAM "_episodes", "an episode", n_ids, ids, s0, y0, u_prev, n_steps, plant_substeps, states_out,  \
+                                                    obs_out, inputs_out, costs_out, first_bad});                                                      \
+    }
+
 }  // namespace
 
 // =============================================================================================
@@ -346,22 +827,6 @@ struct ctk_batch : BatchCore {
     float* d_w = nullptr;                   // [B][wtab] problem p's table, in the layout of a handle's d_wperm
     float* h_w = nullptr;                   // pinned [B][wtab]: the staging of ONE transfer per weight call
     std::vector<unsigned char> have_w;      // [B] the problem has received weights
-    // the closed loop on the device (ctk_batch_run / ctk_batch_plant_step; kernel ctk_batch_plant<ENV>, ctk_plant.hip).  Problem p's PLANT
-    // has, for parameter id, the override if one was set (ctk_batch_plant_set_param), else the problem's own controller value table(p)[id]
-    std::vector<float> plant_over;          // [B][CTK_MAX_PARAMS] the overrides
-    std::vector<unsigned char> plant_has;   // [B][CTK_MAX_PARAMS] an override was set
-    std::vector<float> plant_tab;           // [B][CTK_MAX_PARAMS] the effective table the constants in h_kplant were derived from
-    std::vector<int> plant_sub;             // [B] ... and their Euler sub-step count (0: nothing derived yet)
-    unsigned char* h_kplant = nullptr;      // pinned [B][kstride] the plants' derived constants, the staging of the copy to d_kplant
-    unsigned char* d_kplant = nullptr;      // [B][kstride]
-    unsigned char* h_run = nullptr;         // pinned: the step records, plant operands and traces of one segment or plant step (LoopLayout)
-    unsigned char* d_run = nullptr;         // the same on the device; both grow on demand (batch_run_buffers)
-    size_t d_run_cap = 0, h_run_cap = 0;    // bytes
-    int run_segment = 256;                  // steps per segment of a run: a diagnostic switch may lower it (ctk_batch_create)
-    // the stochastic plant (include/ctk_hip_episode.h: ctk_batch_episodes / ctk_batch_plant_step_noisy; kernel ctk_batch_plant_noisy<ENV>)
-    std::vector<float> noise_sigma;         // [B][2][CTK_MAX_STATES] process | measurement standard deviations (0: none)
-    std::vector<uint64_t> noise_seed;       // [B] Philox key of the problem's noise (at creation: its controller seed)
-    std::vector<uint32_t> noise_pos;        // [B] noise position: one per transition of the noisy plant
     size_t unom_stride() const { return (size_t)2 * HC; }
     float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
 };
@@ -426,82 +891,6 @@ int batch_reset_one(ctk_batch* b, int p) {
     return CTK_OK;
 }
 
-// ---- the closed loop on the device: the plants' constants and the run buffer (ctk_batch_run / ctk_batch_plant_step) ----
-
-// The plants' constants ahead of a run or a plant step: problem p's effective table (override, else its own controller value) and the
-// sub-step count against what h_kplant was derived from; those that changed are re-derived with the function the controller's
-// constants come from, and the span from the first to the last of them travels in ONE transfer on the batch's stream (none when
-// nothing changed).  The caller synchronises before it returns, so the staging is free again at the next call.
-hipError_t batch_plant_flush(ctk_batch* b, int substeps) {
-    int lo = b->B, hi = -1;
-    float eff[CTK_MAX_PARAMS];
-    for (int p = 0; p < b->B; ++p) {
-        const size_t z = (size_t)p * CTK_MAX_PARAMS;
-        for (int i = 0; i < CTK_MAX_PARAMS; ++i) eff[i] = b->plant_has[z + i] ? b->plant_over[z + i] : b->table(p)[i];
-        if (b->plant_sub[(size_t)p] == substeps && std::memcmp(eff, &b->plant_tab[z], sizeof(eff)) == 0) continue;
-        ctk_mppi_batch_derive_k(b->env, eff, b->cfg.dt, substeps, b->h_kplant + (size_t)p * b->kstride);
-        std::memcpy(&b->plant_tab[z], eff, sizeof(eff));
-        b->plant_sub[(size_t)p] = substeps;
-        lo = std::min(lo, p); hi = p;
-    }
-    if (hi < 0) return hipSuccess;
-    const hipError_t e = hipMemcpyAsync(b->d_kplant + (size_t)lo * b->kstride, b->h_kplant + (size_t)lo * b->kstride, (size_t)(hi - lo + 1) * b->kstride,
-                                        hipMemcpyHostToDevice, b->stream);
-    if (e != hipSuccess) for (int p = lo; p <= hi; ++p) b->plant_sub[(size_t)p] = 0;      // nothing reached the device: derive and copy again
-    return e;
-}
-
-// Where the parts of the run buffer lie for a segment of n problems and L steps (bytes from its start; every part 16-aligned).  What
-// travels to the device in ONE transfer lies in front (up to `states`), what comes back in ONE copy behind it:
-//   step records [L][n] | inputs of a plant step [n][C] | true start states [n][S] | previous inputs of the first step [n][C] |
-//   noise records [n] || state trace [n][L][S] | observation trace [n][L][S] | input trace [n][L][C] | realised costs [n][L]
-// The parts only the noisy plant has (s_start, u_start, noise, obs, costs) are empty without it (ctk_batch_run / ctk_batch_plant_step):
-// what then remains is  step records | inputs of a plant step || state trace | input trace.
-struct LoopLayout {
-    size_t u_in, s_start, u_start, noise, states, obs, inputs, costs, total;
-    LoopLayout(const ctk_batch* b, int n, int L, bool noisy) {
-        auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-        auto ep = [&](size_t x) { return noisy ? x : 0; };
-        u_in = (size_t)L * n * sizeof(CtkBatchStep);
-        s_start = u_in + up((size_t)n * b->C * sizeof(float));
-        u_start = s_start + ep(up((size_t)n * b->S * sizeof(float)));
-        noise = u_start + ep(up((size_t)n * b->C * sizeof(float)));
-        states = noise + ep((size_t)n * sizeof(CtkPlantNoise));
-        obs = states + up((size_t)n * L * b->S * sizeof(float));
-        inputs = obs + ep(up((size_t)n * L * b->S * sizeof(float)));
-        costs = inputs + up((size_t)n * L * b->C * sizeof(float));
-        total = costs + ep(up((size_t)n * L * sizeof(float)));
-    }
-};
-static_assert(sizeof(CtkBatchStep) % 16 == 0, "the parts of the run buffer lie behind the step records, 16-aligned");
-static_assert(sizeof(CtkPlantNoise) % 16 == 0, "the traces lie behind the noise records, 16-aligned");
-
-// the run buffer (device and pinned), grown to the layout's bytes on demand
-int batch_run_buffers(ctk_batch* b, const LoopLayout& lay) {
-    BHIP_TRY(b, b->own.grow_dev(b->d_run, b->d_run_cap, lay.total));
-    BHIP_TRY(b, b->own.grow_pin(b->h_run, b->h_run_cap, lay.total));
-    return CTK_OK;
-}
-
-// problem p's noise record at its current position
-void batch_noise_record(const ctk_batch* b, int p, CtkPlantNoise* q) {
-    const float* sg = &b->noise_sigma[(size_t)p * 2 * CTK_MAX_STATES];
-    q->any = 0u;
-    for (int i = 0; i < CTK_MAX_STATES; ++i) {
-        q->sigma_w[i] = i < b->S ? sg[i] : 0.0f;
-        q->sigma_v[i] = i < b->S ? sg[CTK_MAX_STATES + i] : 0.0f;
-        if (q->sigma_w[i] != 0.0f || q->sigma_v[i] != 0.0f) q->any = 1u;
-    }
-    q->seed_lo = (uint32_t)(b->noise_seed[(size_t)p] & 0xFFFFFFFFull); q->seed_hi = (uint32_t)(b->noise_seed[(size_t)p] >> 32);
-    q->pos = b->noise_pos[(size_t)p];
-}
-
-int batch_substeps(ctk_batch* b, const char* who, int substeps, int* out) {
-    if (substeps < 0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": the plant's sub-step count must be >= 1, or 0 for cfg.intermediate_steps (" + std::to_string(substeps) + ")");
-    *out = substeps ? substeps : b->cfg.intermediate_steps;
-    return CTK_OK;
-}
-
 // what a step record says of the step that problem p takes t steps from now (ctk_batch_step: t == 0; a segment of the closed loop: t in
 // [0, L)): its counters, and no draws.  The state and the previous input are the caller's.
 void batch_fill_record(const ctk_batch* b, CtkBatchStep& q, int p, int t) {
@@ -510,224 +899,29 @@ void batch_fill_record(const ctk_batch* b, CtkBatchStep& q, int p, int t) {
     q.pad = 0u; q.samples = nullptr;
 }
 
-// One plant step of the listed problems (ctk_batch_plant_step; with y_next, ctk_batch_plant_step_noisy): the records, the inputs and
-// what the noisy plant reads besides travel in ONE transfer, one launch, one copy back, one synchronisation.
-int batch_plant_step(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev,
-                     int substeps, float* s_next, float* y_next, float* cost) {
-    const bool noisy = y_next != nullptr;
-    int n = 0, sub = 0;
-    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
-    if (int rc = batch_substeps(b, who, substeps, &sub)) return rc;
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));
-    const int S = b->S, C = b->C;
-    const LoopLayout lay(b, n, 1, noisy);
-    if (int rc = batch_run_buffers(b, lay)) return rc;
-    // the records carry the problem and, for the plain plant, its state; the noisy plant reads the state from a row of its own
-    CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
-    CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
-    for (int j = 0; j < n; ++j) {
-        std::memset(&rec[j], 0, sizeof(CtkBatchStep));
-        rec[j].id = ids ? ids[j] : j;
-        if (noisy) batch_noise_record(b, rec[j].id, &nz[j]);
-        else for (int i = 0; i < S; ++i) rec[j].s[i] = s[(size_t)j * S + i];
+// the MPPI family's part of the closed loop (the trait of batch_closed_loop, above); the MLP family runs it too
+struct MppiLoop {
+    using Batch = ctk_batch;
+    using Rec = CtkBatchStep;
+    static constexpr bool carries_k = false, error_word = true;
+    static int refuse(Batch*, const char*, int, const int32_t*) { return CTK_OK; }       // (the MLP family's missing weights: its own entries)
+    static RolloutArgs context(const Batch* b) { return batch_args(b); }
+    static hipError_t constants(Batch* b, const int32_t*, int, unsigned char*) { return b->differ ? batch_flush_constants(b) : hipSuccess; }
+    static void fill(const Batch* b, Rec& q, int p, int t) { batch_fill_record(b, q, p, t); }
+    static hipError_t launch(Batch* b, const RolloutArgs& a, const Rec* d_rec, int n, const unsigned char*, int* launched) {
+        return batch_launch_records(b, a, d_rec, n, launched);
     }
-    std::memcpy(b->h_run + lay.u_in, u, (size_t)n * C * sizeof(float));
-    if (noisy) {
-        std::memcpy(b->h_run + lay.s_start, s, (size_t)n * S * sizeof(float));
-        std::memcpy(b->h_run + lay.u_start, u_prev, (size_t)n * C * sizeof(float));
-    }
-    const CtkBatchStep* d_rec = reinterpret_cast<const CtkBatchStep*>(b->d_run);
-    auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
-    const size_t back = noisy ? lay.total - lay.states : (size_t)n * S * sizeof(float);      // the plain plant wrote the next states alone
-    hipError_t le = batch_plant_flush(b, sub);
-    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.states, hipMemcpyHostToDevice, b->stream);
-    bool launched = false;
-    if (le == hipSuccess) {
-        if (noisy)
-            le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec, nullptr, b->d_kplant,
-                                              reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise), dev(lay.u_in), dev(lay.s_start), (size_t)S,
-                                              dev(lay.u_start), (size_t)C, 0u, dev(lay.states), dev(lay.obs), nullptr, dev(lay.costs), n, (size_t)S, 0, 1);
-        else
-            le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec, nullptr, b->d_kplant, dev(lay.u_in), dev(lay.states), nullptr, n,
-                                        (size_t)S, 0);
-        launched = le == hipSuccess;
-    }
-    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, back, hipMemcpyDeviceToHost, b->stream);
-    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
-    if (le == hipSuccess) le = se;
-    if (noisy && launched)
-        for (int j = 0; j < n; ++j) ++b->noise_pos[(size_t)rec[j].id];         // by the plant launch that was issued
-    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string(who) + ": " + hipGetErrorString(le));
-    std::memcpy(s_next, b->h_run + lay.states, (size_t)n * S * sizeof(float));
-    if (noisy) {
-        std::memcpy(y_next, b->h_run + lay.obs, (size_t)n * S * sizeof(float));
-        std::memcpy(cost, b->h_run + lay.costs, (size_t)n * sizeof(float));
-    }
-    return CTK_OK;
-}
-
-// The counters after a segment of L steps whose launches ended with `le`.  `ctrl` steps had the controllers of all n listed problems
-// launched; if the launches of the step after them failed (part >= 0), those of its first `part` problems were; `plants` launches of
-// the noisy plant were issued (a run: 0).  seq, call, cur and noise_pos are left as if exactly these had run, by the rule of
-// ctk_batch_step: a listed problem consumes its sequence number launched or not, its Philox position and plan buffer only if launched.
-// Only where nothing failed, a problem whose slot does not show the segment's last step is listed in `late`; the hand-off's error word
-// is read and cleared into timed[j] whatever happened.
-void batch_loop_account(ctk_batch* b, int n, const int32_t* ids, hipError_t le, int L, int ctrl, int part, int plants, std::string& late,
-                        std::vector<unsigned char>& timed) {
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
-        if (le == hipSuccess && slot[1] != b->seq[(size_t)p] + (uint32_t)(L - 1)) list_problem(late, p);
-        if (slot[2]) { slot[2] = 0; timed[(size_t)j] = 1; }                   // the hand-off's error word, read and cleared
-        b->seq[(size_t)p] += (uint32_t)ctrl; b->call[(size_t)p] += (uint32_t)ctrl; b->cur[(size_t)p] ^= ctrl & 1;
-        if (part >= 0) {
-            ++b->seq[(size_t)p];
-            if (j < part) { ++b->call[(size_t)p]; b->cur[(size_t)p] ^= 1; }
+    // by the rule of ctk_batch_step: a listed problem consumes its sequence number launched or not, its Philox position and plan buffer
+    // only if launched
+    static void advance(Batch* b, int p, int ctrl, bool tried, bool issued) {
+        const size_t z = (size_t)p;
+        b->seq[z] += (uint32_t)ctrl; b->call[z] += (uint32_t)ctrl; b->cur[z] ^= ctrl & 1;
+        if (tried) {
+            ++b->seq[z];
+            if (issued) { ++b->call[z]; b->cur[z] ^= 1; }
         }
-        b->noise_pos[(size_t)p] += (uint32_t)plants;
     }
-}
-
-// a closed-loop call: ctk_batch_run, or with obs_out (and costs_out) ctk_batch_episodes
-struct LoopCall {
-    const char* who;                        // the entry point, for the messages
-    const char* noun;                       // "a run" / "an episode"
-    int n_ids; const int32_t* ids;
-    const float *s0, *y0, *u_prev;
-    int n_steps, plant_substeps;
-    float *states_out, *obs_out, *inputs_out, *costs_out;
-    int32_t* first_bad;
 };
-
-// The closed loop on the device, in segments of at most run_segment steps.  A segment is ONE transfer of its step records (and what the
-// noisy plant reads at its first step), per step the controller launches and one plant launch, ONE copy of the traces back and ONE
-// synchronisation; the plant launch of step t writes the state (the noisy plant: the observation) into the records of step t + 1 on the
-// device.  The noisy plant differs in where it reads from (the true state and the previous input have rows of their own, see
-// ctk_plant.hip), in its noise positions and in the two further traces.
-int batch_closed_loop(ctk_batch* b, const LoopCall& c) {
-    const bool noisy = c.obs_out != nullptr;
-    const int32_t* ids = c.ids;
-    const float* u_prev = c.u_prev;
-    const int n_steps = c.n_steps;
-    int n = 0, sub = 0;
-    if (int rc = batch_ids(b, c.who, c.n_ids, ids, &n)) return rc;
-    if (n_steps < 1)
-        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(c.who) + ": " + c.noun + " has at least one step (n_steps == " + std::to_string(n_steps) + ")");
-    if (int rc = batch_substeps(b, c.who, c.plant_substeps, &sub)) return rc;
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));
-    const int S = b->S, C = b->C;
-    const size_t srow = ((size_t)n_steps + 1) * S, urow = (size_t)n_steps * C;       // one problem's rows of the traces
-    for (int j = 0; j < n; ++j) {
-        std::memcpy(c.states_out + (size_t)j * srow, c.s0 + (size_t)j * S, (size_t)S * sizeof(float));
-        if (noisy) std::memcpy(c.obs_out + (size_t)j * srow, (c.y0 ? c.y0 : c.s0) + (size_t)j * S, (size_t)S * sizeof(float));
-        if (c.first_bad) c.first_bad[j] = -1;
-    }
-    // The noisy plant without u_prev: the first step's previous input is what the first controller launch reads as its own — the problem's
-    // last output in d_u (ctk_batch_set_state writes it too, the pinned result slot only holds what a step published).  That launch
-    // overwrites it, so the span of the listed problems is read here, once per call, ahead of everything else.  A run has no use for it.
-    const int p_lo = ids ? ids[0] : 0, p_hi = ids ? ids[n - 1] : n - 1;
-    std::vector<float> own_u;
-    if (noisy && !u_prev) {
-        own_u.resize((size_t)(p_hi - p_lo + 1) * CTK_MAX_INPUTS);
-        BHIP_TRY(b, hipMemcpyAsync(own_u.data(), b->d_u + (size_t)p_lo * CTK_MAX_INPUTS, own_u.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-        BHIP_TRY(b, hipStreamSynchronize(b->stream));
-    }
-    const float* first_s = noisy ? c.obs_out : c.states_out;                   // what the controllers see: of a run the state itself
-    std::vector<unsigned char> timed((size_t)n, 0);
-    std::string late;
-    const RolloutArgs a = batch_args(b);
-    hipError_t le = batch_plant_flush(b, sub);
-    for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
-        const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
-        const LoopLayout lay(b, n, L, noisy);
-        if (int rc = batch_run_buffers(b, lay)) { hipStreamSynchronize(b->stream); return rc; }
-        // every record of the segment: all but the state is known in advance.  The state of the segment's first step is the host's (the
-        // start state or observation, or the previous segment's last one from the copied trace); the later ones the plant launches write
-        // on the device.
-        CtkBatchStep* rec = reinterpret_cast<CtkBatchStep*>(b->h_run);
-        for (int t = 0; t < L; ++t) {
-            const bool given = k0 + t == 0 && u_prev;                          // from the second step on: the problem's own last output
-            for (int j = 0; j < n; ++j) {
-                CtkBatchStep& q = rec[(size_t)t * n + j];
-                batch_fill_record(b, q, ids ? ids[j] : j, t);
-                q.dev_uprev = given ? 0u : 1u;
-                for (int i = 0; i < CTK_MAX_STATES; ++i) q.s[i] = (t == 0 && i < S) ? first_s[(size_t)j * srow + (size_t)k0 * S + i] : 0.0f;
-                for (int i = 0; i < CTK_MAX_INPUTS; ++i) q.u_prev[i] = (given && i < C) ? u_prev[(size_t)j * C + i] : 0.0f;
-            }
-        }
-        // what the first noisy plant launch of the segment reads in place of trace rows: the true state, and the input before the
-        // segment's first one — the given u_prev, the previous segment's last input, or the problem's own last output (read above)
-        if (noisy) {
-            float* h_s = reinterpret_cast<float*>(b->h_run + lay.s_start);
-            float* h_up = reinterpret_cast<float*>(b->h_run + lay.u_start);
-            CtkPlantNoise* nz = reinterpret_cast<CtkPlantNoise*>(b->h_run + lay.noise);
-            for (int j = 0; j < n; ++j) {
-                const int p = ids ? ids[j] : j;
-                std::memcpy(h_s + (size_t)j * S, c.states_out + (size_t)j * srow + (size_t)k0 * S, (size_t)S * sizeof(float));
-                if (k0 > 0) std::memcpy(h_up + (size_t)j * C, c.inputs_out + (size_t)j * urow + ((size_t)k0 - 1) * C, (size_t)C * sizeof(float));
-                else if (u_prev) std::memcpy(h_up + (size_t)j * C, u_prev + (size_t)j * C, (size_t)C * sizeof(float));
-                else std::memcpy(h_up + (size_t)j * C, &own_u[(size_t)(p - p_lo) * CTK_MAX_INPUTS], (size_t)C * sizeof(float));
-                batch_noise_record(b, p, &nz[j]);
-            }
-        }
-        CtkBatchStep* d_rec = reinterpret_cast<CtkBatchStep*>(b->d_run);
-        auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
-        const CtkPlantNoise* d_nz = reinterpret_cast<const CtkPlantNoise*>(b->d_run + lay.noise);
-        float *d_st = dev(lay.states), *d_ob = dev(lay.obs), *d_in = dev(lay.inputs), *d_co = dev(lay.costs);
-        if (b->differ) le = batch_flush_constants(b);                          // the constants' transfer goes ahead of the step records'
-        if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, noisy ? lay.states : lay.u_in, hipMemcpyHostToDevice, b->stream);
-        int ctrl = 0, part = -1, plants = 0;           // steps whose controllers were all launched; of the step whose launches failed, how
-                                                       // many were; the noisy plant launches that were issued
-        for (int t = 0; le == hipSuccess && t < L; ++t) {
-            int launched = 0;
-            le = batch_launch_records(b, a, d_rec + (size_t)t * n, n, &launched);
-            if (le != hipSuccess) { part = launched; break; }
-            ++ctrl;
-            CtkBatchStep* next = t + 1 < L ? d_rec + (size_t)(t + 1) * n : nullptr;
-            if (noisy) {
-                le = ctk_launch_batch_plant_noisy(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, next, b->d_kplant, d_nz, nullptr,
-                                                  t ? d_st + (size_t)(t - 1) * S : dev(lay.s_start), t ? (size_t)L * S : (size_t)S,
-                                                  t ? d_in + (size_t)(t - 1) * C : dev(lay.u_start), t ? (size_t)L * C : (size_t)C, (uint32_t)t,
-                                                  d_st + (size_t)t * S, d_ob + (size_t)t * S, d_in + (size_t)t * C, d_co + t, n, (size_t)L * S, (size_t)L * C,
-                                                  (size_t)L);
-                if (le == hipSuccess) ++plants;
-            } else {
-                le = ctk_launch_batch_plant(b->stream, b->env, b->d_desc, d_rec + (size_t)t * n, next, b->d_kplant, nullptr, d_st + (size_t)t * S,
-                                            d_in + (size_t)t * C, n, (size_t)L * S, (size_t)L * C);
-            }
-        }
-        if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.states, b->d_run + lay.states, lay.total - lay.states, hipMemcpyDeviceToHost, b->stream);
-        const hipError_t se = hipStreamSynchronize(b->stream);                 // ONE synchronisation per segment, whatever happened
-        if (le == hipSuccess) le = se;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        batch_loop_account(b, n, ids, le, L, ctrl, part, plants, late, timed);  // the counters reflect what was launched
-        if (le != hipSuccess) break;
-        auto host = [&](size_t at) { return reinterpret_cast<const float*>(b->h_run + at); };
-        const float *h_st = host(lay.states), *h_ob = host(lay.obs), *h_in = host(lay.inputs), *h_co = host(lay.costs);
-        for (int j = 0; j < n; ++j) {
-            std::memcpy(c.states_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_st + (size_t)j * L * S, (size_t)L * S * sizeof(float));
-            std::memcpy(c.inputs_out + (size_t)j * urow + (size_t)k0 * C, h_in + (size_t)j * L * C, (size_t)L * C * sizeof(float));
-            if (noisy) {
-                std::memcpy(c.obs_out + (size_t)j * srow + ((size_t)k0 + 1) * S, h_ob + (size_t)j * L * S, (size_t)L * S * sizeof(float));
-                std::memcpy(c.costs_out + (size_t)j * n_steps + (size_t)k0, h_co + (size_t)j * L, (size_t)L * sizeof(float));
-            }
-            if (c.first_bad && c.first_bad[j] < 0)
-                for (int i = 0; i < L * C; ++i)
-                    if (!std::isfinite(h_in[(size_t)j * L * C + i])) { c.first_bad[j] = k0 + i / C; break; }
-        }
-        k0 += L;
-    }
-    if (le != hipSuccess)
-        return bfail(b, CTK_ERR_HIP, std::string(c.who) + ": " + hipGetErrorString(le) + " (the counters reflect the steps that were launched; the traces are not valid)");
-    if (!late.empty()) return bfail(b, CTK_ERR_HIP, std::string(c.who) + ": a segment finished without publishing the last result of problem(s) " + late);
-    std::string timed_out;
-    for (int j = 0; j < n; ++j)
-        if (timed[(size_t)j]) list_problem(timed_out, ids ? ids[j] : j);
-    if (!timed_out.empty())
-        return bfail(b, CTK_ERR_STATE, std::string(c.who) + ": in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
-                     "; such a step publishes NaN and the plant propagates it: their traces show where (first_bad), the other problems' traces are valid");
-    return CTK_OK;
-}
 
 }  // namespace
 
@@ -796,7 +990,7 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
     hipDeviceProp_t prop;
     if (int rc = probe_device(who, cfg->device, &prop)) return rc;
 
-    batch_core_init(b, cfg, einfo, n_problems);        // dirty: no constants in d_k yet, the first step of the per-problem form derives them all
+    batch_core_init(b, cfg, einfo, n_problems, seeds);        // dirty: no constants in d_k yet, the first step of the per-problem form derives them all
     b->mlp_names = mlp;
     b->pred = pred; b->hid1 = hw1; b->hid2 = hw2;
     b->P = P; b->PC = P * b->C; b->blocks = blocks;
@@ -806,17 +1000,6 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
     // so every other workgroup finds a place whatever the dispatch order.  CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH (diagnostic) only lowers it.
     b->max_per_launch = std::max(1, prop.multiProcessorCount / 2);
     batch_env_lowers("CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH", &b->max_per_launch);
-    // A long run goes in segments of this many steps, so that its record buffer stays bounded (256 steps of 128 problems: 2.5 MiB of
-    // records).  CTK_BATCH_RUN_SEGMENT_STEPS (diagnostic) only lowers it; the results do not depend on it.
-    batch_env_lowers("CTK_BATCH_RUN_SEGMENT_STEPS", &b->run_segment);
-    b->plant_over.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
-    b->plant_has.assign((size_t)n_problems * CTK_MAX_PARAMS, 0);
-    b->plant_tab.assign((size_t)n_problems * CTK_MAX_PARAMS, 0.0f);
-    b->plant_sub.assign((size_t)n_problems, 0);
-    b->noise_sigma.assign((size_t)n_problems * 2 * CTK_MAX_STATES, 0.0f);
-    b->noise_seed.resize((size_t)n_problems);
-    for (int p = 0; p < n_problems; ++p) b->noise_seed[(size_t)p] = batch_seed(cfg, seeds, p);   // the controller's (below)
-    b->noise_pos.assign((size_t)n_problems, 0u);
     b->cur.assign((size_t)n_problems, 0);
     b->dominant = mlp ? ctk_mppi_batch_mlp_name(cfg->materialize_trajectories != 0) : ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
     if (mlp) { b->wtab = ctk_mppi_batch_mlp_table_floats(); b->have_w.assign((size_t)n_problems, 0); }
@@ -835,8 +1018,6 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
     HIP_CREATE(b->own.pinned_zero(&b->h_steps, Bz * sizeof(CtkBatchStep)));
     HIP_CREATE(b->own.dev_zero(&b->d_k, Bz * b->kstride, b->stream));
     HIP_CREATE(b->own.pinned_zero(&b->h_k, Bz * b->kstride));
-    HIP_CREATE(b->own.dev_zero(&b->d_kplant, Bz * b->kstride, b->stream));
-    HIP_CREATE(b->own.pinned_zero(&b->h_kplant, Bz * b->kstride));
     if (mlp) {
         HIP_CREATE(b->own.dev_zero(&b->d_w, Bz * b->wtab * sizeof(float), b->stream));
         HIP_CREATE(b->own.pinned_zero(&b->h_w, Bz * b->wtab * sizeof(float)));
@@ -969,122 +1150,9 @@ int ctk_problem_params_differ(const ctk_batch* b) { return batch_params_differ(b
 int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
 int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) { return batch_rng_set_position(b, "ctk_batch_rng_set_position", problem, call); }
 
-// ---- the closed loop on the device (include/ctk_hip_run.h: ctk_batch_plant_* / ctk_batch_run) ----
-int ctk_batch_plant_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = batch_ids(b, "ctk_batch_plant_set_param", n_ids, ids, &n)) return rc;
-    if (int rc = batch_param_id(b, "ctk_batch_plant_set_param", id)) return rc;
-    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_param: NULL values (one value per listed problem)");
-    for (int j = 0; j < n; ++j) {
-        const size_t z = (size_t)(ids ? ids[j] : j) * CTK_MAX_PARAMS + (size_t)id;
-        b->plant_over[z] = values[j];                  // derived at the next run or plant step (batch_plant_flush compares the tables)
-        b->plant_has[z] = 1;
-    }
-    return CTK_OK;
-}
-
-int ctk_batch_plant_get_param(const ctk_batch* b, int problem, int id, float* value) {
-    if (!b || !value || problem < 0 || problem >= b->B || id < 0 || id >= env_info(b->env)->n_params) return CTK_ERR_INVALID_ARGUMENT;
-    const size_t z = (size_t)problem * CTK_MAX_PARAMS + (size_t)id;
-    *value = b->plant_has[z] ? b->plant_over[z] : b->table(problem)[id];
-    return CTK_OK;
-}
-
-int ctk_batch_plant_clear_params(ctk_batch* b) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    std::fill(b->plant_has.begin(), b->plant_has.end(), (unsigned char)0);
-    return CTK_OK;
-}
-
-int ctk_batch_plant_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u, int substeps, float* s_next) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (!s || !u || !s_next) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_step: NULL state, input or destination");
-    return batch_plant_step(b, "ctk_batch_plant_step", n_ids, ids, s, u, nullptr, substeps, s_next, nullptr, nullptr);
-}
-
-int ctk_batch_run(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, const float* u_prev, int n_steps, int plant_substeps,
-                  float* states_out, float* inputs_out, int32_t* first_bad) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (!s0 || !states_out || !inputs_out) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_run: NULL start states or trace destination");
-    return batch_closed_loop(b, LoopCall{"ctk_batch_run", "a run", n_ids, ids, s0, nullptr, u_prev, n_steps, plant_substeps, states_out, nullptr, inputs_out,
-                                         nullptr, first_bad});
-}
-
-// ---- the stochastic plant and the realised cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes) ----
-int ctk_batch_plant_set_noise(ctk_batch* b, int n_ids, const int32_t* ids, int kind, const float* sigma) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = batch_ids(b, "ctk_batch_plant_set_noise", n_ids, ids, &n)) return rc;
-    if (kind != 0 && kind != 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: kind is 0 (process noise) or 1 (measurement noise), not " + std::to_string(kind));
-    if (!sigma) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: NULL sigma (one row of num_states values per listed problem)");
-    for (int i = 0; i < n * b->S; ++i)
-        if (!(std::isfinite(sigma[i]) && sigma[i] >= 0.0f))
-            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise: a standard deviation is finite and >= 0 (" + std::to_string(sigma[i]) + " for problem " +
-                         std::to_string(ids ? ids[i / b->S] : i / b->S) + ", state " + std::to_string(i % b->S) + "); nothing was written");
-    for (int j = 0; j < n; ++j) {
-        float* dst = &b->noise_sigma[((size_t)(ids ? ids[j] : j) * 2 + (size_t)kind) * CTK_MAX_STATES];
-        for (int i = 0; i < b->S; ++i) dst[i] = sigma[(size_t)j * b->S + i] == 0.0f ? 0.0f : sigma[(size_t)j * b->S + i];   // -0.0 is "none" too
-    }
-    return CTK_OK;
-}
-
-int ctk_batch_plant_get_noise(const ctk_batch* b, int problem, int kind, float* sigma) {
-    if (!b || !sigma || problem < 0 || problem >= b->B || (kind != 0 && kind != 1)) return CTK_ERR_INVALID_ARGUMENT;
-    std::memcpy(sigma, &b->noise_sigma[((size_t)problem * 2 + (size_t)kind) * CTK_MAX_STATES], (size_t)b->S * sizeof(float));
-    return CTK_OK;
-}
-
-int ctk_batch_plant_clear_noise(ctk_batch* b) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    std::fill(b->noise_sigma.begin(), b->noise_sigma.end(), 0.0f);
-    return CTK_OK;
-}
-
-int ctk_batch_plant_set_noise_seed(ctk_batch* b, int n_ids, const int32_t* ids, const uint64_t* seeds) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = batch_ids(b, "ctk_batch_plant_set_noise_seed", n_ids, ids, &n)) return rc;
-    if (!seeds) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_set_noise_seed: NULL seeds (one per listed problem)");
-    for (int j = 0; j < n; ++j) b->noise_seed[(size_t)(ids ? ids[j] : j)] = seeds[j];
-    return CTK_OK;
-}
-
-int ctk_batch_plant_get_noise_seed(const ctk_batch* b, int problem, uint64_t* seed) {
-    if (!b || !seed || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
-    *seed = b->noise_seed[(size_t)problem];
-    return CTK_OK;
-}
-
-int ctk_batch_plant_noise_get_position(const ctk_batch* b, int problem, uint32_t* pos) {
-    if (!b || !pos || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
-    *pos = b->noise_pos[(size_t)problem];
-    return CTK_OK;
-}
-
-int ctk_batch_plant_noise_set_position(ctk_batch* b, int problem, uint32_t pos) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (int rc = batch_problem(b, "ctk_batch_plant_noise_set_position", problem)) return rc;
-    b->noise_pos[(size_t)problem] = pos;
-    return CTK_OK;
-}
-
-int ctk_batch_plant_step_noisy(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev, int substeps,
-                               float* s_next, float* y_next, float* cost) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (!s || !u || !u_prev || !s_next || !y_next || !cost)
-        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_plant_step_noisy: NULL state, input, previous input or destination");
-    return batch_plant_step(b, "ctk_batch_plant_step_noisy", n_ids, ids, s, u, u_prev, substeps, s_next, y_next, cost);
-}
-
-int ctk_batch_episodes(ctk_batch* b, int n_ids, const int32_t* ids, const float* s0, const float* y0, const float* u_prev, int n_steps,
-                       int plant_substeps, float* states_out, float* obs_out, float* inputs_out, float* costs_out, int32_t* first_bad) {
-    if (!b) return CTK_ERR_INVALID_ARGUMENT;
-    if (!s0 || !states_out || !obs_out || !inputs_out || !costs_out)
-        return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_episodes: NULL start states or trace destination");
-    return batch_closed_loop(b, LoopCall{"ctk_batch_episodes", "an episode", n_ids, ids, s0, y0, u_prev, n_steps, plant_substeps, states_out, obs_out,
-                                         inputs_out, costs_out, first_bad});
-}
+// ---- the closed loop on the device (include/ctk_hip_run.h: ctk_batch_plant_* / ctk_batch_run) and the stochastic plant with the realised
+// cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes) ----
+CTK_LOOP_ENTRIES(ctk_batch, MppiLoop)
 
 }  // extern "C"
 
@@ -1291,7 +1359,9 @@ struct ctk_cem_batch : BatchCore {
     std::vector<unsigned char> idx_stale;
     float* mu(int p) const { return d_mu + (size_t)p * HC; }
     float* sd(int p) const { return d_sd + (size_t)p * HC; }
-    int its(int p) const { return (cfg.warmup && count[(size_t)p] == 0) ? cfg.warmup_iterations : cfg.cem_outer_it; }   // cem_iterations
+    // cem_iterations of the step the problem takes t steps from now: the warm-up count exactly at its first step after creation or reset
+    int its_at(int p, int t) const { return (cfg.warmup && count[(size_t)p] + t == 0) ? cfg.warmup_iterations : cfg.cem_outer_it; }
+    int its(int p) const { return its_at(p, 0); }
 };
 
 namespace {
@@ -1303,6 +1373,68 @@ RolloutArgs cem_batch_args(const ctk_cem_batch* b) {
     a.p_magic = ctk_magic_of(b->H);
     return a;
 }
+
+// the first hand-off tag of a step of `its` iterations for a problem whose next unused tag is `tag` (cem_step: a step's tags are
+// consecutive; where tag + its would wrap, the step restarts at 1, so that tag 0 stays the never-written value)
+uint32_t cem_tag0(uint32_t tag, int its) { return (uint32_t)(tag + (uint32_t)its) < tag ? 1u : tag; }
+
+// what all launches of a CEM batch share
+struct CemBatchCtx { RolloutArgs a; CemFusedLaunch cl; bool log; };
+CemBatchCtx cem_batch_context(const ctk_cem_batch* b) {
+    return {cem_batch_args(b),
+            CemFusedLaunch{0, b->K, nullptr, 0u, b->cfg.cem_stdev_min, 1.0e8f, b->cfg.cem_initial_action_stdev, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0.5},
+            b->cfg.materialize_trajectories != 0};
+}
+
+// The controller launches of n step records from steps_dev on (ctk_cem_batch_step; every step of ctk_cem_batch_run): consecutive launches
+// of at most max_per_launch problems; a problem never spans launches.  d_ksteps: the per-problem form's constants by record index (else
+// NULL).  *launched: the records that were launched.
+hipError_t cem_batch_launch_records(ctk_cem_batch* b, const CemBatchCtx& x, const CtkCemBatchStep* steps_dev, int n, const unsigned char* d_ksteps,
+                                    int* launched) {
+    hipError_t le = hipSuccess;
+    *launched = 0;
+    while (le == hipSuccess && *launched < n) {
+        const int cnt = std::min(b->max_per_launch, n - *launched);
+        le = ctk_launch_cem_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, x.a, x.cl, b->d_desc, steps_dev + *launched, cnt, x.log,
+                                  d_ksteps ? d_ksteps + (size_t)*launched * b->kstride : nullptr);
+        if (le == hipSuccess) *launched += cnt;
+    }
+    return le;
+}
+
+// the CEM family's part of the closed loop (the trait of batch_closed_loop)
+struct CemLoop {
+    using Batch = ctk_cem_batch;
+    using Rec = CtkCemBatchStep;
+    static constexpr bool carries_k = true, error_word = true;
+    static int refuse(Batch*, const char*, int, const int32_t*) { return CTK_OK; }
+    static CemBatchCtx context(const Batch* b) { return cem_batch_context(b); }
+    static hipError_t constants(Batch* b, const int32_t* ids, int n, unsigned char* h_k) {
+        if (b->differ) batch_stage_constants(b, b->kcache.data(), ids, n, h_k);
+        return hipSuccess;
+    }
+    // its from count + t; the tags of the t steps before it consumed one after the other, each by the wrap rule; seq and call + 1 per step
+    static void fill(const Batch* b, Rec& q, int p, int t) {
+        const size_t z = (size_t)p;
+        uint32_t tag = b->cem_tag[z];
+        for (int i = 0; i < t; ++i) tag = cem_tag0(tag, b->its_at(p, i)) + (uint32_t)b->its_at(p, i);
+        q = Rec{};
+        q.id = p; q.seq = b->seq[z] + (uint32_t)t; q.call = b->call[z] + (uint32_t)t;
+        q.its = b->its_at(p, t); q.tag0 = cem_tag0(tag, q.its);
+    }
+    static hipError_t launch(Batch* b, const CemBatchCtx& x, const Rec* d_rec, int n, const unsigned char* d_k, int* launched) {
+        return cem_batch_launch_records(b, x, d_rec, n, d_k, launched);
+    }
+    // by the rule of ctk_cem_batch_step: a listed problem consumes its sequence number and its tags launched or not; its step count and
+    // Philox position advance, and BEST_IDX goes stale, only if launched
+    static void advance(Batch* b, int p, int ctrl, bool tried, bool issued) {
+        const size_t z = (size_t)p;
+        const int listed = ctrl + (tried ? 1 : 0), ran = ctrl + (tried && issued ? 1 : 0);
+        for (int i = 0; i < listed; ++i) b->cem_tag[z] = cem_tag0(b->cem_tag[z], b->its_at(p, i)) + (uint32_t)b->its_at(p, i);
+        b->seq[z] += (uint32_t)listed; b->call[z] += (uint32_t)ran; b->count[z] += ran;
+        if (ran) b->idx_stale[z] = 1;
+    }
+};
 
 // mean at mid-range, std = cem_initial_action_stdev, u = 0 of problem p into the host images (ctk_reset of a CEM handle)
 void cem_batch_initial(const ctk_cem_batch* b, float* mu, float* sd) {
@@ -1354,7 +1486,7 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
 
     Creating<ctk_cem_batch> made;
     ctk_cem_batch* b = made.p;
-    batch_core_init(b, cfg, einfo, n_problems);
+    batch_core_init(b, cfg, einfo, n_problems, seeds);
     b->K = cfg->cem_best_k; b->nblk = nblk;
     b->llw = ctk_cem_fused_ll_words(N, HC);
     b->kcache.assign((size_t)n_problems * b->kstride, 0);
@@ -1443,7 +1575,7 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
         const size_t z = (size_t)p;
         const int its = b->its(p);
         CtkCemBatchStep& q = b->h_steps[j];
-        if ((uint32_t)(b->cem_tag[z] + (uint32_t)its) < b->cem_tag[z]) b->cem_tag[z] = 1;
+        b->cem_tag[z] = cem_tag0(b->cem_tag[z], its);
         q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.tag0 = b->cem_tag[z]; q.its = its;
         b->cem_tag[z] += (uint32_t)its;
         q.samples = d_s ? d_s + (size_t)j * per : nullptr;
@@ -1451,17 +1583,8 @@ int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const fl
     }
     const unsigned char* d_ksteps = nullptr;           // the per-problem form: the constants behind the records, in the same transfer
     hipError_t le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(CtkCemBatchStep), b->h_steps, b->d_steps, &d_ksteps);
-    const RolloutArgs a = cem_batch_args(b);
-    const bool log = b->cfg.materialize_trajectories != 0;
-    const CemFusedLaunch cl{0, b->K, nullptr, 0u, b->cfg.cem_stdev_min, 1.0e8f, b->cfg.cem_initial_action_stdev,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0.5};
     int launched = 0;                                  // consecutive launches of at most max_per_launch problems; a problem never spans launches
-    while (le == hipSuccess && launched < n) {
-        const int cnt = std::min(b->max_per_launch, n - launched);
-        le = ctk_launch_cem_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, cl, b->d_desc, b->d_steps + launched, cnt, log,
-                                  d_ksteps ? d_ksteps + (size_t)launched * b->kstride : nullptr);
-        if (le == hipSuccess) launched += cnt;
-    }
+    if (le == hipSuccess) le = cem_batch_launch_records(b, cem_batch_context(b), b->d_steps, n, d_ksteps, &launched);
     const std::string late = batch_poll(b, ids, launched);
     std::string timed_out;
     for (int j = 0; j < n; ++j) {
@@ -1546,6 +1669,9 @@ int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call)
     return batch_rng_set_position(b, "ctk_cem_batch_rng_set_position", problem, call);
 }
 
+// ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_cem_batch_plant_* / ctk_cem_batch_run / ctk_cem_batch_episodes) ----
+CTK_LOOP_ENTRIES(ctk_cem_batch, CemLoop)
+
 }  // extern "C"
 
 // =============================================================================================
@@ -1578,11 +1704,14 @@ struct ctk_rpgd_batch : BatchCore {
     std::vector<int> count, adam_step;
     std::vector<unsigned char> cur, ready;
     size_t NHC() const { return (size_t)N * HC; }
-    int its(int p) const {                  // rpgd_iterations
+    // rpgd_iterations and the resampling rule (optimizer_rpgd.py:449) of the step the problem takes t steps from now: both from count + t
+    int its_at(int p, int t) const {
         const int first = cfg.warmup ? cfg.warmup_iterations : cfg.outer_its;
-        return count[(size_t)p] == 0 ? first : cfg.outer_its;
+        return count[(size_t)p] + t == 0 ? first : cfg.outer_its;
     }
-    bool resamples(int p) const { return count[(size_t)p] % cfg.resamp_per == 0; }   // optimizer_rpgd.py:449
+    bool resamples_at(int p, int t) const { return (count[(size_t)p] + t) % cfg.resamp_per == 0; }
+    int its(int p) const { return its_at(p, 0); }
+    bool resamples(int p) const { return resamples_at(p, 0); }
     size_t needs(int p) const { return (resamples(p) && K < N) ? (size_t)(N - K) * PC : 0; }   // samples_needed of an RPGD handle
 };
 
@@ -1606,6 +1735,71 @@ RpgdFusedWarm rpgd_batch_warm(const ctk_rpgd_batch* b) {
 }
 
 constexpr int RPGD_BATCH_MAX_GRID_Y = 65535;   // problems of one launch: the grid's y limit, nothing else bounds it
+
+// what all launches of an RPGD batch share
+struct RpgdBatchCtx { RolloutArgs a; RpgdFusedWarm f; };
+
+// The controller launches of n step records from steps_dev on (ctk_rpgd_batch_step; every step of ctk_rpgd_batch_run): consecutive
+// launches only past the grid's y limit; a problem never spans launches.  d_ksteps: the per-problem form's constants by record index
+// (else NULL).  *launched: the records that were launched.
+hipError_t rpgd_batch_launch_records(ctk_rpgd_batch* b, const RpgdBatchCtx& x, const CtkRpgdBatchStep* steps_dev, int n, const unsigned char* d_ksteps,
+                                     int* launched) {
+    const ctk_config& c = b->cfg;
+    hipError_t le = hipSuccess;
+    *launched = 0;
+    while (le == hipSuccess && *launched < n) {
+        const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - *launched);
+        le = ctk_launch_g_rpgd_batch(b->stream, b->env, x.a, b->params, c.dt, c.intermediate_steps, c.learning_rate, c.adam_beta_1, c.adam_beta_2,
+                                     c.adam_epsilon, c.gradmax_clip, c.adam_rule == 1 ? 1 : 0, b->d_bc, b->bc_len, x.f, b->d_desc, steps_dev + *launched, cnt,
+                                     d_ksteps ? d_ksteps + (size_t)*launched * b->kstride : nullptr);
+        if (le == hipSuccess) *launched += cnt;
+    }
+    return le;
+}
+
+// a listed problem that was never reset: nothing is launched (ctk_rpgd_batch_step and the closed loop)
+int rpgd_batch_ready(ctk_rpgd_batch* b, const char* who, int n, const int32_t* ids) {
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        if (!b->ready[(size_t)p])
+            return bfail(b, CTK_ERR_STATE, std::string(who) + ": problem " + std::to_string(p) + " was never reset: call ctk_rpgd_batch_reset (optimizer_reset) "
+                         "before its first step; nothing was launched");
+    }
+    return CTK_OK;
+}
+
+// the RPGD family's part of the closed loop (the trait of batch_closed_loop)
+struct RpgdLoop {
+    using Batch = ctk_rpgd_batch;
+    using Rec = CtkRpgdBatchStep;
+    static constexpr bool carries_k = true, error_word = false;      // this kernel has no in-launch hand-off
+    static int refuse(Batch* b, const char* who, int n, const int32_t* ids) { return rpgd_batch_ready(b, who, n, ids); }
+    static RpgdBatchCtx context(const Batch* b) { return {rpgd_batch_args(b), rpgd_batch_warm(b)}; }
+    static hipError_t constants(Batch* b, const int32_t* ids, int n, unsigned char* h_k) {
+        if (b->differ) batch_stage_constants(b, b->kcache.data(), ids, n, h_k);
+        return hipSuccess;
+    }
+    // iters and resample from count + t; t0 = the Adam steps taken plus those of the t steps before it; cur flips, seq and call + 1 per
+    // step; the draws are the in-kernel Philox's
+    static void fill(const Batch* b, Rec& q, int p, int t) {
+        const size_t z = (size_t)p;
+        q = Rec{};
+        q.id = p; q.seq = b->seq[z] + (uint32_t)t; q.call = b->call[z] + (uint32_t)t; q.cur = (uint32_t)(b->cur[z] ^ (t & 1));
+        q.iters = b->its_at(p, t); q.t0 = b->adam_step[z];
+        for (int i = 0; i < t; ++i) q.t0 += b->its_at(p, i);
+        q.resample = b->resamples_at(p, t) ? 1 : 0;
+    }
+    static hipError_t launch(Batch* b, const RpgdBatchCtx& x, const Rec* d_rec, int n, const unsigned char* d_k, int* launched) {
+        return rpgd_batch_launch_records(b, x, d_rec, n, d_k, launched);
+    }
+    // by the rule of ctk_rpgd_batch_step, on purpose: a problem never issued consumes nothing, not even its sequence number
+    static void advance(Batch* b, int p, int ctrl, bool tried, bool issued) {
+        const size_t z = (size_t)p;
+        const int ran = ctrl + (tried && issued ? 1 : 0);
+        for (int i = 0; i < ran; ++i) b->adam_step[z] += b->its_at(p, i);      // (ahead of count, which its_at reads)
+        b->seq[z] += (uint32_t)ran; b->call[z] += (uint32_t)ran; b->cur[z] ^= ran & 1; b->count[z] += ran;
+    }
+};
 
 }  // namespace
 
@@ -1675,7 +1869,7 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
 
     Creating<ctk_rpgd_batch> made;
     ctk_rpgd_batch* b = made.p;
-    batch_core_init(b, cfg, einfo, n_problems);
+    batch_core_init(b, cfg, einfo, n_problems, seeds);
     b->K = cfg->opt_keep_k;
     b->P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
     b->PC = b->P * einfo->C;
@@ -1775,14 +1969,9 @@ int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const 
     if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
     int n = 0;
     if (int rc = batch_ids(b, "ctk_rpgd_batch_step", n_ids, ids, &n)) return rc;
+    if (int rc = rpgd_batch_ready(b, "ctk_rpgd_batch_step", n, ids)) return rc;
     size_t need = 0;
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        if (!b->ready[(size_t)p])
-            return bfail(b, CTK_ERR_STATE, "ctk_rpgd_batch_step: problem " + std::to_string(p) + " was never reset: call ctk_rpgd_batch_reset (optimizer_reset) "
-                         "before its first step; nothing was launched");
-        need += b->needs(p);
-    }
+    for (int j = 0; j < n; ++j) need += b->needs(ids ? ids[j] : j);
     if (samples_loc != CTK_LOC_NONE) {
         if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
         if (n_samples != need)                          // refused before a sample is read
@@ -1814,17 +2003,8 @@ int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const 
     }
     const unsigned char* d_ksteps = nullptr;           // the per-problem form: the constants behind the records, in the same transfer
     hipError_t le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(CtkRpgdBatchStep), b->h_steps, b->d_steps, &d_ksteps);
-    const RolloutArgs a = rpgd_batch_args(b);
-    const RpgdFusedWarm f = rpgd_batch_warm(b);
-    const ctk_config& c = b->cfg;
     int launched = 0;                                  // consecutive launches only past the grid's y limit; a problem never spans launches
-    while (le == hipSuccess && launched < n) {
-        const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - launched);
-        le = ctk_launch_g_rpgd_batch(b->stream, b->env, a, b->params, c.dt, c.intermediate_steps, c.learning_rate, c.adam_beta_1, c.adam_beta_2,
-                                     c.adam_epsilon, c.gradmax_clip, c.adam_rule == 1 ? 1 : 0, b->d_bc, b->bc_len, f, b->d_desc, b->d_steps + launched, cnt,
-                                     d_ksteps ? d_ksteps + (size_t)launched * b->kstride : nullptr);
-        if (le == hipSuccess) launched += cnt;
-    }
+    if (le == hipSuccess) le = rpgd_batch_launch_records(b, RpgdBatchCtx{rpgd_batch_args(b), rpgd_batch_warm(b)}, b->d_steps, n, d_ksteps, &launched);
     // h_steps is both the source of the transfer above and, below, the host's memory of id / seq / iters for the bookkeeping: that holds
     // because the call is synchronous (nothing refills h_steps before it returns); an asynchronous step would need its own copy.
     const std::string late = batch_poll(b, ids, launched);
@@ -1891,5 +2071,8 @@ int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32
 int ctk_rpgd_batch_rng_set_position(ctk_rpgd_batch* b, int problem, uint32_t call) {
     return batch_rng_set_position(b, "ctk_rpgd_batch_rng_set_position", problem, call);
 }
+
+// ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_rpgd_batch_plant_* / ctk_rpgd_batch_run / ctk_rpgd_batch_episodes) ----
+CTK_LOOP_ENTRIES(ctk_rpgd_batch, RpgdLoop)
 
 }  // extern "C"

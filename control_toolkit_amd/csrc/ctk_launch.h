@@ -239,6 +239,31 @@ hipError_t ctk_launch_batch_plant_noisy(hipStream_t st, int env, const CtkBatchD
                                         size_t s_true_stride, const float* u_last_dev, size_t u_last_stride, uint32_t t, float* states_out,
                                         float* obs_out, float* inputs_out, float* costs_out, int n_records, size_t state_stride,
                                         size_t input_stride, size_t cost_stride);
+// ---- ctk_plant.hip : the same two plants for the CEM and RPGD batches (include/ctk_hip_loop.h: ctk_cem_batch_run / ctk_rpgd_batch_run ...) ----
+// Kernels ctk_cem_batch_plant<env> / ctk_cem_batch_plant_noisy<env> and ctk_rpgd_batch_plant<env> / ctk_rpgd_batch_plant_noisy<env>: the
+// bodies of ctk_batch_plant / ctk_batch_plant_noisy over the family's descriptor and step record (id, s and u_dev are all they touch),
+// so the launchers are overloads of the two above with the same arguments and meaning.
+struct CtkCemBatchDesc; struct CtkCemBatchStep; struct CtkRpgdBatchDesc; struct CtkRpgdBatchStep;
+const char* ctk_cem_batch_plant_name(int env);
+const char* ctk_cem_batch_plant_noisy_name(int env);
+const char* ctk_rpgd_batch_plant_name(int env);
+const char* ctk_rpgd_batch_plant_noisy_name(int env);
+hipError_t ctk_launch_batch_plant(hipStream_t st, int env, const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* cur_dev, CtkCemBatchStep* next_dev,
+                                  const void* kplant_dev, const float* u_in_dev, float* states_out, float* inputs_out, int n_records,
+                                  size_t state_stride, size_t input_stride);
+hipError_t ctk_launch_batch_plant(hipStream_t st, int env, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* cur_dev, CtkRpgdBatchStep* next_dev,
+                                  const void* kplant_dev, const float* u_in_dev, float* states_out, float* inputs_out, int n_records,
+                                  size_t state_stride, size_t input_stride);
+hipError_t ctk_launch_batch_plant_noisy(hipStream_t st, int env, const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* cur_dev, CtkCemBatchStep* next_dev,
+                                        const void* kplant_dev, const CtkPlantNoise* noise_dev, const float* u_in_dev, const float* s_true_dev,
+                                        size_t s_true_stride, const float* u_last_dev, size_t u_last_stride, uint32_t t, float* states_out,
+                                        float* obs_out, float* inputs_out, float* costs_out, int n_records, size_t state_stride,
+                                        size_t input_stride, size_t cost_stride);
+hipError_t ctk_launch_batch_plant_noisy(hipStream_t st, int env, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* cur_dev, CtkRpgdBatchStep* next_dev,
+                                        const void* kplant_dev, const CtkPlantNoise* noise_dev, const float* u_in_dev, const float* s_true_dev,
+                                        size_t s_true_stride, const float* u_last_dev, size_t u_last_stride, uint32_t t, float* states_out,
+                                        float* obs_out, float* inputs_out, float* costs_out, int n_records, size_t state_stride,
+                                        size_t input_stride, size_t cost_stride);
 hipError_t ctk_launch_mppi_merge_partial(hipStream_t st, const float* parts, int n_parts, int per_block, int P,
                                          float neg_inv_lbd, float* out_rec);
 // direct peer-to-peer record exchange + merge + update (ctk_mppi.hip: ctk_mppi_p2p_exchange)

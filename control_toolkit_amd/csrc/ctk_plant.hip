@@ -1,4 +1,6 @@
-// ctk_plant.hip — the plant of a batch's closed loop on the device (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_step).
+// ctk_plant.hip — the plant of a batch's closed loop on the device (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_step; for
+// the CEM and RPGD batches include/ctk_hip_loop.h: the same two bodies as ctk_cem_batch_plant[_noisy]<ENV> and
+// ctk_rpgd_batch_plant[_noisy]<ENV>, over those families' descriptors and step records).
 //
 //   ctk_batch_plant<ENV>   one lane per step record: s' = Env<ENV>::step(k_plant[problem], s, u) — the one-step plant the rollout
 //        kernels integrate (ctk_generic.hip: ctk_g_rollout calls the same function once per horizon step), with the checked sin / cos.
@@ -14,17 +16,18 @@
 
 constexpr int PLANT_BLOCK = 64;
 
-template <int ENV>
-__global__ __launch_bounds__(PLANT_BLOCK) void ctk_batch_plant(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ cur,
-                                                              CtkBatchStep* __restrict__ next, const unsigned char* __restrict__ kplant,
-                                                              const float* __restrict__ u_in, float* __restrict__ states_out,
-                                                              float* __restrict__ inputs_out, int n, size_t state_stride,
-                                                              size_t input_stride) {
+// the body of the plant kernels of every batch family: Desc / Rec are the family's descriptor and step record (ctk_launch.h), of which
+// only id, s and u_dev are touched
+template <int ENV, class Desc, class Rec>
+__device__ __forceinline__ void plant_body(const Desc* __restrict__ desc, const Rec* __restrict__ cur, Rec* __restrict__ next,
+                                           const unsigned char* __restrict__ kplant, const float* __restrict__ u_in,
+                                           float* __restrict__ states_out, float* __restrict__ inputs_out, int n, size_t state_stride,
+                                           size_t input_stride) {
     using E = Env<ENV>;
     constexpr int S = E::S, C = E::C;
     const int j = blockIdx.x * PLANT_BLOCK + threadIdx.x;
     if (j >= n) return;
-    const CtkBatchStep& q = cur[j];
+    const Rec& q = cur[j];
     const int p = q.id;
     const typename E::K k = *reinterpret_cast<const typename E::K*>(kplant + (size_t)p * CtkBatchKStride<ENV>::value);
     const float* up = u_in ? u_in + (size_t)j * C : desc[p].u_dev;
@@ -46,19 +49,39 @@ __global__ __launch_bounds__(PLANT_BLOCK) void ctk_batch_plant(const CtkBatchDes
     }
 }
 
+#define CTK_PLANT_KERNEL(NAME, DESC, REC)                                                                                              \
+    template <int ENV>                                                                                                                 \
+    __global__ __launch_bounds__(PLANT_BLOCK) void NAME(const DESC* __restrict__ desc, const REC* __restrict__ cur, REC* __restrict__ next, \
+                                                        const unsigned char* __restrict__ kplant, const float* __restrict__ u_in,      \
+                                                        float* __restrict__ states_out, float* __restrict__ inputs_out, int n,         \
+                                                        size_t state_stride, size_t input_stride) {                                    \
+        plant_body<ENV>(desc, cur, next, kplant, u_in, states_out, inputs_out, n, state_stride, input_stride);                         \
+    }
+CTK_PLANT_KERNEL(ctk_batch_plant, CtkBatchDesc, CtkBatchStep)
+CTK_PLANT_KERNEL(ctk_cem_batch_plant, CtkCemBatchDesc, CtkCemBatchStep)        // the CEM batch's closed loop (include/ctk_hip_loop.h)
+CTK_PLANT_KERNEL(ctk_rpgd_batch_plant, CtkRpgdBatchDesc, CtkRpgdBatchStep)     // the RPGD batch's
+#undef CTK_PLANT_KERNEL
+
 const char* ctk_batch_plant_name(int env) { return ctk_kernel_name("ctk_batch_plant<%d>", env); }
 
-hipError_t ctk_launch_batch_plant(hipStream_t st, int env, const CtkBatchDesc* desc_dev, const CtkBatchStep* cur_dev, CtkBatchStep* next_dev,
-                                  const void* kplant_dev, const float* u_in_dev, float* states_out, float* inputs_out, int n_records,
-                                  size_t state_stride, size_t input_stride) {
-    if (n_records < 1 || !desc_dev || !cur_dev || !kplant_dev || !states_out) return hipErrorInvalidValue;
-    const dim3 grid((n_records + PLANT_BLOCK - 1) / PLANT_BLOCK), block(PLANT_BLOCK);
-    CTK_FOR_ENV(env, EV, {
-        hipLaunchKernelGGL((ctk_batch_plant<EV>), grid, block, 0, st, desc_dev, cur_dev, next_dev, static_cast<const unsigned char*>(kplant_dev),
-                           u_in_dev, states_out, inputs_out, n_records, state_stride, input_stride);
-    });
-    return hipGetLastError();
-}
+#define CTK_PLANT_LAUNCHER(KERNEL, DESC, REC)                                                                                          \
+    hipError_t ctk_launch_batch_plant(hipStream_t st, int env, const DESC* desc_dev, const REC* cur_dev, REC* next_dev, const void* kplant_dev, \
+                                      const float* u_in_dev, float* states_out, float* inputs_out, int n_records, size_t state_stride, \
+                                      size_t input_stride) {                                                                           \
+        if (n_records < 1 || !desc_dev || !cur_dev || !kplant_dev || !states_out) return hipErrorInvalidValue;                         \
+        const dim3 grid((n_records + PLANT_BLOCK - 1) / PLANT_BLOCK), block(PLANT_BLOCK);                                              \
+        CTK_FOR_ENV(env, EV, {                                                                                                         \
+            hipLaunchKernelGGL((KERNEL<EV>), grid, block, 0, st, desc_dev, cur_dev, next_dev, static_cast<const unsigned char*>(kplant_dev), \
+                               u_in_dev, states_out, inputs_out, n_records, state_stride, input_stride);                               \
+        });                                                                                                                            \
+        return hipGetLastError();                                                                                                      \
+    }
+CTK_PLANT_LAUNCHER(ctk_batch_plant, CtkBatchDesc, CtkBatchStep)
+CTK_PLANT_LAUNCHER(ctk_cem_batch_plant, CtkCemBatchDesc, CtkCemBatchStep)
+CTK_PLANT_LAUNCHER(ctk_rpgd_batch_plant, CtkRpgdBatchDesc, CtkRpgdBatchStep)
+#undef CTK_PLANT_LAUNCHER
+const char* ctk_cem_batch_plant_name(int env) { return ctk_kernel_name("ctk_cem_batch_plant<%d>", env); }
+const char* ctk_rpgd_batch_plant_name(int env) { return ctk_kernel_name("ctk_rpgd_batch_plant<%d>", env); }
 
 // ---- the stochastic plant (include/ctk_hip_episode.h: ctk_batch_episodes / ctk_batch_plant_step_noisy) ----
 //   ctk_batch_plant_noisy<ENV>   one lane per step record, beside ctk_batch_plant<ENV>:
@@ -76,15 +99,14 @@ hipError_t ctk_launch_batch_plant(hipStream_t st, int env, const CtkBatchDesc* d
 //        row for a segment's first step), because u_dev no longer holds it.  The noise record of lane j lies behind the step records
 //        and travels with them; `t` is the step within the segment, added to the record's position.
 // Plain vector loads and stores, no LDS, no scratch; ordered by the stream like ctk_batch_plant.
-template <int ENV>
-__global__ __launch_bounds__(PLANT_BLOCK) void ctk_batch_plant_noisy(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ cur,
-                                                                    CtkBatchStep* __restrict__ next, const unsigned char* __restrict__ kplant,
-                                                                    const CtkPlantNoise* __restrict__ noise, const float* __restrict__ u_in,
-                                                                    const float* __restrict__ s_true, const float* __restrict__ u_last,
-                                                                    float* __restrict__ states_out, float* __restrict__ obs_out,
-                                                                    float* __restrict__ inputs_out, float* __restrict__ costs_out, int n,
-                                                                    uint32_t t, size_t s_true_stride, size_t u_last_stride, size_t state_stride,
-                                                                    size_t input_stride, size_t cost_stride) {
+template <int ENV, class Desc, class Rec>
+__device__ __forceinline__ void plant_noisy_body(const Desc* __restrict__ desc, const Rec* __restrict__ cur, Rec* __restrict__ next,
+                                                 const unsigned char* __restrict__ kplant,
+                                                 const CtkPlantNoise* __restrict__ noise, const float* __restrict__ u_in,
+                                                 const float* __restrict__ s_true, const float* __restrict__ u_last,
+                                                 float* __restrict__ states_out, float* __restrict__ obs_out, float* __restrict__ inputs_out,
+                                                 float* __restrict__ costs_out, int n, uint32_t t, size_t s_true_stride, size_t u_last_stride,
+                                                 size_t state_stride, size_t input_stride, size_t cost_stride) {
     using E = Env<ENV>;
     constexpr int S = E::S, C = E::C, NB = (2 * S + 3) / 4;
     const int j = blockIdx.x * PLANT_BLOCK + threadIdx.x;
@@ -139,20 +161,47 @@ __global__ __launch_bounds__(PLANT_BLOCK) void ctk_batch_plant_noisy(const CtkBa
     }
 }
 
+
+#define CTK_PLANT_NOISY_KERNEL(NAME, DESC, REC)                                                                                        \
+    template <int ENV>                                                                                                                 \
+    __global__ __launch_bounds__(PLANT_BLOCK) void NAME(const DESC* __restrict__ desc, const REC* __restrict__ cur, REC* __restrict__ next, \
+                                                        const unsigned char* __restrict__ kplant, const CtkPlantNoise* __restrict__ noise, \
+                                                        const float* __restrict__ u_in, const float* __restrict__ s_true,              \
+                                                        const float* __restrict__ u_last, float* __restrict__ states_out,              \
+                                                        float* __restrict__ obs_out, float* __restrict__ inputs_out,                   \
+                                                        float* __restrict__ costs_out, int n, uint32_t t, size_t s_true_stride,        \
+                                                        size_t u_last_stride, size_t state_stride, size_t input_stride,                \
+                                                        size_t cost_stride) {                                                          \
+        plant_noisy_body<ENV>(desc, cur, next, kplant, noise, u_in, s_true, u_last, states_out, obs_out, inputs_out, costs_out, n, t,  \
+                              s_true_stride, u_last_stride, state_stride, input_stride, cost_stride);                                  \
+    }
+CTK_PLANT_NOISY_KERNEL(ctk_batch_plant_noisy, CtkBatchDesc, CtkBatchStep)
+CTK_PLANT_NOISY_KERNEL(ctk_cem_batch_plant_noisy, CtkCemBatchDesc, CtkCemBatchStep)      // the CEM batch's episodes (include/ctk_hip_loop.h)
+CTK_PLANT_NOISY_KERNEL(ctk_rpgd_batch_plant_noisy, CtkRpgdBatchDesc, CtkRpgdBatchStep)   // the RPGD batch's
+#undef CTK_PLANT_NOISY_KERNEL
+
 const char* ctk_batch_plant_noisy_name(int env) { return ctk_kernel_name("ctk_batch_plant_noisy<%d>", env); }
 
-hipError_t ctk_launch_batch_plant_noisy(hipStream_t st, int env, const CtkBatchDesc* desc_dev, const CtkBatchStep* cur_dev, CtkBatchStep* next_dev,
-                                        const void* kplant_dev, const CtkPlantNoise* noise_dev, const float* u_in_dev, const float* s_true_dev,
-                                        size_t s_true_stride, const float* u_last_dev, size_t u_last_stride, uint32_t t, float* states_out,
-                                        float* obs_out, float* inputs_out, float* costs_out, int n_records, size_t state_stride,
-                                        size_t input_stride, size_t cost_stride) {
-    if (n_records < 1 || !desc_dev || !cur_dev || !kplant_dev || !noise_dev || !s_true_dev || !u_last_dev || !states_out || !obs_out || !costs_out)
-        return hipErrorInvalidValue;
-    const dim3 grid((n_records + PLANT_BLOCK - 1) / PLANT_BLOCK), block(PLANT_BLOCK);
-    CTK_FOR_ENV(env, EV, {
-        hipLaunchKernelGGL((ctk_batch_plant_noisy<EV>), grid, block, 0, st, desc_dev, cur_dev, next_dev, static_cast<const unsigned char*>(kplant_dev),
-                           noise_dev, u_in_dev, s_true_dev, u_last_dev, states_out, obs_out, inputs_out, costs_out, n_records, t, s_true_stride,
-                           u_last_stride, state_stride, input_stride, cost_stride);
-    });
-    return hipGetLastError();
-}
+#define CTK_PLANT_NOISY_LAUNCHER(KERNEL, DESC, REC)                                                                                    \
+    hipError_t ctk_launch_batch_plant_noisy(hipStream_t st, int env, const DESC* desc_dev, const REC* cur_dev, REC* next_dev,          \
+                                            const void* kplant_dev, const CtkPlantNoise* noise_dev, const float* u_in_dev,             \
+                                            const float* s_true_dev, size_t s_true_stride, const float* u_last_dev, size_t u_last_stride, \
+                                            uint32_t t, float* states_out, float* obs_out, float* inputs_out, float* costs_out,        \
+                                            int n_records, size_t state_stride, size_t input_stride, size_t cost_stride) {             \
+        if (n_records < 1 || !desc_dev || !cur_dev || !kplant_dev || !noise_dev || !s_true_dev || !u_last_dev || !states_out || !obs_out || \
+            !costs_out)                                                                                                                \
+            return hipErrorInvalidValue;                                                                                               \
+        const dim3 grid((n_records + PLANT_BLOCK - 1) / PLANT_BLOCK), block(PLANT_BLOCK);                                              \
+        CTK_FOR_ENV(env, EV, {                                                                                                         \
+            hipLaunchKernelGGL((KERNEL<EV>), grid, block, 0, st, desc_dev, cur_dev, next_dev, static_cast<const unsigned char*>(kplant_dev), \
+                               noise_dev, u_in_dev, s_true_dev, u_last_dev, states_out, obs_out, inputs_out, costs_out, n_records, t,  \
+                               s_true_stride, u_last_stride, state_stride, input_stride, cost_stride);                                 \
+        });                                                                                                                            \
+        return hipGetLastError();                                                                                                      \
+    }
+CTK_PLANT_NOISY_LAUNCHER(ctk_batch_plant_noisy, CtkBatchDesc, CtkBatchStep)
+CTK_PLANT_NOISY_LAUNCHER(ctk_cem_batch_plant_noisy, CtkCemBatchDesc, CtkCemBatchStep)
+CTK_PLANT_NOISY_LAUNCHER(ctk_rpgd_batch_plant_noisy, CtkRpgdBatchDesc, CtkRpgdBatchStep)
+#undef CTK_PLANT_NOISY_LAUNCHER
+const char* ctk_cem_batch_plant_noisy_name(int env) { return ctk_kernel_name("ctk_cem_batch_plant_noisy<%d>", env); }
+const char* ctk_rpgd_batch_plant_noisy_name(int env) { return ctk_kernel_name("ctk_rpgd_batch_plant_noisy<%d>", env); }

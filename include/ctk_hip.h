@@ -738,4 +738,6 @@ int ctk_mlp_problem_have_weights(const ctk_mlp_batch* b, int problem);          
 /* closed-loop episodes of the MPPI batches on the device (a run with the plant step included): declared in a header of their own */
 #include "ctk_hip_run.h"
 #include "ctk_hip_episode.h"
+/* the same closed loops for the CEM and RPGD batches */
+#include "ctk_hip_loop.h"
 #endif /* CTK_HIP_H */
