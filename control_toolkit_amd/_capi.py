@@ -126,89 +126,51 @@ SYMBOLS = {
     "ctk_resident_enable": (C.c_int, [_H, C.c_int, C.c_double]),
     "ctk_resident_stop": (C.c_int, [_H]),
     "ctk_resident_stats": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    # batched MPPI (ctk_batch_*): _H is the ctk_batch* there
-    "ctk_batch_create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
-    "ctk_batch_destroy": (None, [_H]),
-    "ctk_batch_last_error": (C.c_char_p, [_H]),
-    "ctk_batch_size": (C.c_int, [_H]),
-    "ctk_batch_samples_needed": (C.c_size_t, [_H]),
-    "ctk_batch_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "ctk_batch_reset": (C.c_int, [_H, C.c_int, C.c_void_p]),
-    "ctk_batch_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_batch_get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_batch_set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_batch_set_param": (C.c_int, [_H, C.c_int, C.c_float]),
-    "ctk_batch_get_param": (C.c_int, [_H, C.c_int, _FP]),
-    "ctk_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
-    "ctk_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
-    "ctk_batch_dominant_kernel": (C.c_char_p, [_H]),
-    # per-problem parameters of a batch (the ctk_batch* again)
-    "ctk_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "ctk_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
-    "ctk_problem_params_differ": (C.c_int, [_H]),
-    # batched CEM (ctk_cem_batch_*): _H is the ctk_cem_batch* there
-    "ctk_cem_batch_create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
-    "ctk_cem_batch_destroy": (None, [_H]),
-    "ctk_cem_batch_last_error": (C.c_char_p, [_H]),
-    "ctk_cem_batch_size": (C.c_int, [_H]),
+}
+
+# the four batch families (ctk_batch_*, ctk_mlp_batch_*, ctk_cem_batch_*, ctk_rpgd_batch_*; _H is the family's batch pointer there): the
+# signatures they share under a family's (batch prefix, problem prefix), then what differs, by name
+_BATCH_FAMILIES = (("ctk_batch", "ctk_problem"), ("ctk_mlp_batch", "ctk_mlp_problem"), ("ctk_cem_batch", "ctk_cem_problem"),
+                   ("ctk_rpgd_batch", "ctk_rpgd_problem"))
+_BATCH_SHARED = {
+    "create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
+    "destroy": (None, [_H]),
+    "last_error": (C.c_char_p, [_H]),
+    "size": (C.c_int, [_H]),
+    "samples_needed": (C.c_size_t, [_H]),
+    "step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "reset": (C.c_int, [_H, C.c_int, C.c_void_p]),
+    "read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "set_param": (C.c_int, [_H, C.c_int, C.c_float]),
+    "get_param": (C.c_int, [_H, C.c_int, _FP]),
+    "rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
+    "rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
+    "dominant_kernel": (C.c_char_p, [_H]),
+}
+_PROBLEM_SHARED = {                                   # per-problem parameters of a batch (the batch pointer again)
+    "set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
+    "params_differ": (C.c_int, [_H]),
+}
+for _batch, _problem in _BATCH_FAMILIES:
+    SYMBOLS.update({f"{_batch}_{name}": sig for name, sig in _BATCH_SHARED.items()})
+    SYMBOLS.update({f"{_problem}_{name}": sig for name, sig in _PROBLEM_SHARED.items()})
+SYMBOLS.update({
+    # the draws of a CEM or RPGD problem's next step depend on the problem
     "ctk_cem_batch_samples_needed": (C.c_size_t, [_H, C.c_int]),
-    "ctk_cem_batch_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "ctk_cem_batch_reset": (C.c_int, [_H, C.c_int, C.c_void_p]),
-    "ctk_cem_batch_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_cem_batch_get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_cem_batch_set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_cem_batch_set_param": (C.c_int, [_H, C.c_int, C.c_float]),
-    "ctk_cem_batch_get_param": (C.c_int, [_H, C.c_int, _FP]),
-    "ctk_cem_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
-    "ctk_cem_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
-    "ctk_cem_batch_dominant_kernel": (C.c_char_p, [_H]),
-    "ctk_cem_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "ctk_cem_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
-    "ctk_cem_problem_params_differ": (C.c_int, [_H]),
-    # batched RPGD (ctk_rpgd_batch_*): _H is the ctk_rpgd_batch* there
-    "ctk_rpgd_batch_create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
-    "ctk_rpgd_batch_destroy": (None, [_H]),
-    "ctk_rpgd_batch_last_error": (C.c_char_p, [_H]),
-    "ctk_rpgd_batch_size": (C.c_int, [_H]),
     "ctk_rpgd_batch_samples_needed": (C.c_size_t, [_H, C.c_int]),
+    # an RPGD step takes the count of the caller's samples, an RPGD reset draws
     "ctk_rpgd_batch_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "ctk_rpgd_batch_reset": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
-    "ctk_rpgd_batch_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_rpgd_batch_get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_rpgd_batch_set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_rpgd_batch_set_param": (C.c_int, [_H, C.c_int, C.c_float]),
-    "ctk_rpgd_batch_get_param": (C.c_int, [_H, C.c_int, _FP]),
-    "ctk_rpgd_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
-    "ctk_rpgd_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
-    "ctk_rpgd_batch_dominant_kernel": (C.c_char_p, [_H]),
-    "ctk_rpgd_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "ctk_rpgd_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
-    "ctk_rpgd_problem_params_differ": (C.c_int, [_H]),
     "ctk_rpgd_template_descent_lds": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
-    # batched MPPI with the MLP predictor (ctk_mlp_batch_* / ctk_mlp_problem_*): _H is the ctk_mlp_batch* there; the signatures of ctk_batch_*
-    "ctk_mlp_batch_create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
-    "ctk_mlp_batch_destroy": (None, [_H]),
-    "ctk_mlp_batch_last_error": (C.c_char_p, [_H]),
-    "ctk_mlp_batch_size": (C.c_int, [_H]),
-    "ctk_mlp_batch_samples_needed": (C.c_size_t, [_H]),
-    "ctk_mlp_batch_step": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "ctk_mlp_batch_reset": (C.c_int, [_H, C.c_int, C.c_void_p]),
-    "ctk_mlp_batch_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_mlp_batch_get_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_mlp_batch_set_state": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
-    "ctk_mlp_batch_set_param": (C.c_int, [_H, C.c_int, C.c_float]),
-    "ctk_mlp_batch_get_param": (C.c_int, [_H, C.c_int, _FP]),
-    "ctk_mlp_batch_rng_get_position": (C.c_int, [_H, C.c_int, C.POINTER(C.c_uint32)]),
-    "ctk_mlp_batch_rng_set_position": (C.c_int, [_H, C.c_int, C.c_uint32]),
-    "ctk_mlp_batch_dominant_kernel": (C.c_char_p, [_H]),
-    "ctk_mlp_problem_set_param": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "ctk_mlp_problem_get_param": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
-    "ctk_mlp_problem_params_differ": (C.c_int, [_H]),
+    # the networks of the MLP family
     "ctk_mlp_batch_weight_count": (C.c_size_t, [_H]),
     "ctk_mlp_batch_set_weights": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
     "ctk_mlp_problem_set_weights": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ctk_mlp_problem_have_weights": (C.c_int, [_H, C.c_int]),
-}
+})
 
 # closed-loop episodes of the MPPI batches on the device (include/ctk_hip_run.h, which ctk_hip.h includes): the same table for the entry
 # points declared there; _bind_library binds both

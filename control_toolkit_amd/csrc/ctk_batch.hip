@@ -1,5 +1,11 @@
 // ctk_batch.hip — the batch families of the C ABI (include/ctk_hip.h, ctk_hip_run.h, ctk_hip_episode.h, ctk_hip_loop.h): ctk_batch_*, ctk_mlp_batch_*,
 // ctk_cem_batch_*, ctk_rpgd_batch_*.  The single handle is in ctk_api.hip; what the two files share is declared in ctk_host.h.
+// The file in order: the host core (BatchCore and the bodies every family shares), the two drivers — batch_step<F> for a step,
+// batch_closed_loop<F> for runs and episodes — and the two macros that write a family's C entries over them (CTK_BATCH_ENTRIES,
+// CTK_LOOP_ENTRIES); then each family: its struct, its trait F (MppiFamily, MlpFamily, CemFamily, RpgdFamily: what the drivers ask of
+// it), and the entries that are its own (create, samples_needed, step, reset, read).  A message names the entry that was called: every
+// entry passes its exported name (`who`) to the body that builds the text, the MLP family included — it runs the MPPI family's code
+// under its own names.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -12,7 +18,7 @@
 using namespace ctk_host;
 
 // =============================================================================================
-// The host core of the batch families (ctk_batch, ctk_cem_batch, ctk_rpgd_batch derive from it; ctk_mlp_batch holds a ctk_batch): what
+// The host core of the batch families (ctk_batch, ctk_cem_batch, ctk_rpgd_batch derive from it; ctk_mlp_batch is a ctk_batch): what
 // every family keeps per batch and per problem, and the one copy of what they all do with it — the id checks, the owner of every device
 // and pinned allocation, the staging of host draws, the step records' common fields, the completion poll, the read-out of u, the
 // transfers of read / get_state / set_state, the parameter tables and the Philox positions.  Plain data and free functions, private to
@@ -57,7 +63,6 @@ struct BatchCore : PlantSide {
     Owner own;                              // every device / pinned allocation of the batch, entered where it is made (ctk_host.h; batch_core_release)
     std::vector<uint32_t> seq, call;        // [B] the sequence number of the problem's next step, its Philox position
     std::string err, dominant;
-    bool mlp_names = false;                 // the MLP family: its messages carry its own entry points' names (bfail)
     float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
     float* slot(int p) const { return h_u + (size_t)p * 16; }
     float* table(int p) { return pparams.data() + (size_t)p * CTK_MAX_PARAMS; }
@@ -65,17 +70,8 @@ struct BatchCore : PlantSide {
     ~BatchCore();                           // batch_core_release: `delete` is every family's destroy and the end of a failed creation
 };
 
-// the MLP family runs the MPPI family's code; its messages carry its own entry points' names (ctk_batch_x -> ctk_mlp_batch_x,
-// ctk_problem_x -> ctk_mlp_problem_x), substituted here where a message is stored, so that the MPPI family's texts are the literals
-std::string mlp_family_names(std::string msg) {
-    for (const char* from : {"ctk_batch_", "ctk_problem_"}) {
-        const std::string to = std::string("ctk_mlp_") + (from + 4);
-        for (size_t at = msg.find(from); at != std::string::npos; at = msg.find(from, at + to.size())) msg.replace(at, std::strlen(from), to);
-    }
-    return msg;
-}
 int bfail(BatchCore* b, int code, const std::string& msg) {
-    if (b) b->err = b->mlp_names ? mlp_family_names(msg) : msg; else g_create_error = msg;
+    if (b) b->err = msg; else g_create_error = msg;
     return code;
 }
 #define BHIP_TRY(b, expr)                                                                       \
@@ -267,9 +263,9 @@ int batch_get_param(const BatchCore* b, int id, float* value) {
     *value = b->params[id];
     return CTK_OK;
 }
-// *flipped: this call turned `differ` on, the family names its per-problem kernel in `dominant`
-int batch_problem_set_param(BatchCore* b, const char* who, int n_ids, const int32_t* ids, int id, const float* values, bool* flipped) {
-    *flipped = false;
+// the call that turns `differ` on names the family's per-problem kernel in `dominant` (F::per_problem_kernel)
+template <class F>
+int batch_problem_set_param(typename F::Batch* b, const char* who, int n_ids, const int32_t* ids, int id, const float* values) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     int n = 0;
     if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
@@ -280,7 +276,7 @@ int batch_problem_set_param(BatchCore* b, const char* who, int n_ids, const int3
         b->table(p)[id] = values[j];
         b->dirty[(size_t)p] = 1;                       // derived at a later step (MPPI: the next one, CEM and RPGD: the problem's next one)
     }
-    *flipped = !b->differ;
+    if (!b->differ) b->dominant = F::per_problem_kernel(b);
     b->differ = true;                                  // sticky: the tables are never compared again
     return CTK_OK;
 }
@@ -308,17 +304,17 @@ int batch_rng_set_position(BatchCore* b, const char* who, int problem, uint32_t 
 // counts as reset).
 struct BatchState { std::vector<StateItem> items; unsigned char* mark = nullptr; };
 
-// get (device to host) or set (host to device) of a problem's state through host[n]: the checks here, the transfers in state_walk.
-// name_size: the size messages name the size (RPGD's do)
-template <class B>
-int batch_state_io(B* b, const char* who, int problem, float* host, size_t n, bool get, bool name_size, BatchState (*describe)(B*, int)) {
+// get (device to host) or set (host to device) of a problem's state (F::state) through host[n]: the checks here, the transfers in
+// state_walk.  F::state_size_named: the size messages name the size (RPGD's do)
+template <class F>
+int batch_state_io(typename F::Batch* b, const char* who, int problem, float* host, size_t n, bool get) {
     if (!b || !host) return CTK_ERR_INVALID_ARGUMENT;
     if (int rc = batch_problem(b, who, problem)) return rc;
-    const BatchState st = describe(b, problem);
+    const BatchState st = F::state(b, problem);
     const size_t size = state_floats(st.items);
     if (get ? n < size : n != size)
         return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + (get ? ": destination too small" : ": wrong state size") +
-                     (name_size ? " (" + std::to_string(size) + " floats)" : std::string()));
+                     (F::state_size_named ? " (" + std::to_string(size) + " floats)" : std::string()));
     BHIP_TRY(b, hipSetDevice(b->cfg.device));
     BHIP_TRY(b, state_walk(st.items, host, get, b->stream));
     if (!get && st.mark) *st.mark = 1;
@@ -356,20 +352,106 @@ int batch_read_out(BatchCore* b, const char* who, const float* src, size_t n, bo
 }
 
 // =============================================================================================
-// The closed loop on the device (include/ctk_hip_run.h, ctk_hip_episode.h, ctk_hip_loop.h): ONE driver for every family.  What is a
-// family's own is a small trait (MppiLoop, CemLoop, RpgdLoop, each below its family's struct):
-//   Batch, Rec            the handle and its step record (every record type has id, s[], u_prev[] and dev_uprev)
+// The two drivers: ONE step (batch_step, the *_step entries) and ONE closed loop on the device (batch_closed_loop: *_run, *_episodes;
+// include/ctk_hip_run.h, ctk_hip_episode.h, ctk_hip_loop.h) for every family.  What is a family's own is a small trait (MppiFamily and
+// its MLP form MlpFamily, CemFamily, RpgdFamily, each below its family's struct):
+//   Batch, Rec            the handle and its step record (every record type has id, seq, s[], u_prev[] and dev_uprev)
 //   carries_k             the per-problem form's constants travel behind the step records and are taken by record index (CEM, RPGD);
 //                         else they live in an array by problem id that `constants` refreshes (MPPI)
-//   error_word            the kernel has an in-launch hand-off whose error word is read and cleared (MPPI, CEM)
+//   error_word            the kernel has an in-launch hand-off whose error word is read and cleared (MPPI, CEM); `handoff_outputs`:
+//                         what a step's message says of the outputs then
 //   refuse(b, who, n, ids)               the family's own refusal, before anything is launched
 //   context(b)                           what all its launches share
 //   constants(b, ids, n, h_k)            the per-problem form's constants ahead of a segment's records
 //   fill(b, q, p, t)                     the record of the step problem p takes t steps from now: every counter, no draws
 //   launch(b, ctx, d_rec, n, d_k, &launched)   the controller launches of n records of ONE step, split as the family's step splits them
-//   advance(b, p, ctrl, tried, issued)   the counters of problem p after `ctrl` steps that were launched in full and, if `tried`, one more
-//                                        whose launches failed, this problem's among them (`issued`) or not
+//   advance(b, p, ctrl, tried, issued)   the family's counter rule, stated once: problem p after `ctrl` steps that were launched in full
+//                                        and, if `tried`, one more whose launches failed, this problem's among them (`issued`) or not
+//   unpublished_keeps_position           where a step and the closed loop differ (see the families): batch_step takes back the one
+//                                        position that `advance` counted for a launched problem whose slot never shows the step's seq
+// and, of the step alone, a caller's draws (StepDraws):
+//   device_ahead_of_draws                hipSetDevice runs ahead of the check of the draws (MPPI), else behind it
+//   draws_of(b, p)                       floats of problem p's row: row j starts where the rows of the listed problems before it end
+//   check_draws(b, who, n, ids, d, total)   the family's checks of a caller's draws and their messages; total: the rows' sum
+//   draws(q)                             the record's pointer to its row
+// and of the entries that CTK_BATCH_ENTRIES writes: state(b, p), state_size_named, per_problem_kernel(b).
 // =============================================================================================
+
+// a caller's draws for a step: the pointer, where it points (CTK_LOC_*), and the count the caller states (RPGD's entry alone has one)
+struct StepDraws { const float* samples; size_t n_samples; int loc; };
+
+// what the MPPI and CEM steps check of a caller's draws (the RPGD step has its own order and a count to check)
+int batch_check_draws(BatchCore* b, const StepDraws& d) {
+    if (d.loc == CTK_LOC_NONE) return CTK_OK;
+    if (d.samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+    if (d.loc != CTK_LOC_DEVICE && d.loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+    return CTK_OK;
+}
+
+// One step of the listed problems (every family's *_step): the step records — states and previous inputs travel with them — in ONE
+// transfer ahead of the launch(es), the completion poll, then the counters and u of every listed problem.  The call is synchronous:
+// h_steps is both the source of the transfer and, afterwards, the host's memory of id and seq for the bookkeeping (nothing refills
+// it before the call returns; an asynchronous step would need its own copy).
+template <class F>
+int batch_step(typename F::Batch* b, const char* who, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const StepDraws& d,
+               float* u_out) {
+    using Rec = typename F::Rec;
+    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL state") : CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (int rc = F::refuse(b, who, n, ids)) return rc;
+    if (F::device_ahead_of_draws) BHIP_TRY(b, hipSetDevice(b->cfg.device));    // by history: the MPPI step; behind the check in the CEM and RPGD steps
+    size_t total = 0;
+    for (int j = 0; j < n; ++j) total += F::draws_of(b, ids ? ids[j] : j);
+    if (int rc = F::check_draws(b, who, n, ids, d, total)) return rc;          // refused before a sample is read, anything is launched or consumed
+    if (!F::device_ahead_of_draws) BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const float* d_s = nullptr;                        // the first row; the rows follow one another in the order of the listed problems
+    if (d.loc == CTK_LOC_DEVICE && total) d_s = d.samples;
+    else if (d.loc == CTK_LOC_HOST && total) {
+        if (int rc = batch_stage(b, d.samples, total)) return rc;
+        d_s = b->d_samples;
+    }
+    size_t off = 0;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        Rec& q = b->h_steps[j];
+        F::fill(b, q, p, 0);
+        const size_t cnt = F::draws_of(b, p);
+        F::draws(q) = (d_s && cnt) ? d_s + off : nullptr;
+        off += cnt;
+        batch_record_io(b, q, j, s, u_prev);
+    }
+    const unsigned char* d_k = nullptr;                // carries_k, the per-problem form: the constants behind the records, in the same transfer
+    hipError_t le;
+    if constexpr (F::carries_k) le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(Rec), b->h_steps, b->d_steps, &d_k);
+    else {
+        le = F::constants(b, ids, n, nullptr);         // MPPI: the constants' transfer goes ahead of the step records'
+        if (le == hipSuccess) le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(Rec), hipMemcpyHostToDevice, b->stream);
+    }
+    const auto ctx = F::context(b);
+    int launched = 0;
+    if (le == hipSuccess) le = F::launch(b, ctx, b->d_steps, n, d_k, &launched);
+    const std::string late = batch_poll(b, ids, launched);
+    std::string timed_out;
+    for (int j = 0; j < n; ++j) {                      // the counters reflect what was launched (F::advance)
+        const int p = b->h_steps[j].id;
+        volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(b->slot(p));
+        F::advance(b, p, j < launched ? 1 : 0, j >= launched, false);
+        if (j >= launched) continue;
+        // a launched problem that never published: where the family says so (unpublished_keeps_position), the Philox position that
+        // advance has just moved with the launch is taken back, and neither u nor the error word is read
+        if (F::unpublished_keeps_position && slot[1] != b->h_steps[j].seq) { --b->call[(size_t)p]; continue; }
+        batch_read_u(b, p, j, u_out);
+        if (F::error_word && slot[2]) { slot[2] = 0; list_problem(timed_out, p); }   // the hand-off's error word, read and cleared
+    }
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string(who) + ": " + hipGetErrorString(le));
+    if (!late.empty()) return bfail(b, CTK_ERR_HIP, std::string(who) + ": the step finished without publishing the result of problem(s) " + late);
+    if constexpr (F::error_word)
+        if (!timed_out.empty())
+            return bfail(b, CTK_ERR_STATE, std::string(who) + ": in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " +
+                         timed_out + F::handoff_outputs);
+    return CTK_OK;
+}
 
 // The plants' constants ahead of a run or a plant step: problem p's effective table (override, else its own controller value) and the
 // sub-step count against what h_kplant was derived from; those that changed are re-derived with the function the controller's
@@ -748,8 +830,28 @@ int plant_noise_set_position(BatchCore* b, const char* who, int problem, uint32_
     return CTK_OK;
 }
 
-// The fourteen closed-loop entries of a family, FAM in {ctk_batch, ctk_cem_batch, ctk_rpgd_batch} with its trait: the bodies above under
-// the family's names (the MLP family forwards to ctk_batch's, further down)
+// The thirteen entries of a family that are one line over a shared body, FAM in {ctk_batch, ctk_mlp_batch, ctk_cem_batch, ctk_rpgd_batch}
+// with the prefix PROB of its per-problem parameter entries and its trait: the bodies above under the family's names
+#define CTK_BATCH_ENTRIES(FAM, PROB, TRAIT)                                                                                                           \
+    const char* FAM##_last_error(const FAM* b) { return b ? b->err.c_str() : g_create_error.c_str(); }                                                \
+    int FAM##_size(const FAM* b) { return b ? b->B : 0; }                                                                                             \
+    const char* FAM##_dominant_kernel(const FAM* b) { return b ? b->dominant.c_str() : ""; }                                                          \
+    void FAM##_destroy(FAM* b) { delete b; }                                                                                                          \
+    int FAM##_set_param(FAM* b, int id, float value) { return batch_set_param(b, #FAM "_set_param", id, value); }                                     \
+    int FAM##_get_param(const FAM* b, int id, float* value) { return batch_get_param(b, id, value); }                                                 \
+    int PROB##_set_param(FAM* b, int n_ids, const int32_t* ids, int id, const float* values) {                                                        \
+        return batch_problem_set_param<TRAIT>(b, #PROB "_set_param", n_ids, ids, id, values);                                                         \
+    }                                                                                                                                                 \
+    int PROB##_get_param(const FAM* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }                  \
+    int PROB##_params_differ(const FAM* b) { return batch_params_differ(b); }                                                                         \
+    int FAM##_rng_get_position(const FAM* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }                        \
+    int FAM##_rng_set_position(FAM* b, int problem, uint32_t call) { return batch_rng_set_position(b, #FAM "_rng_set_position", problem, call); }     \
+    int FAM##_get_state(FAM* b, int problem, float* dst, size_t cap) { return batch_state_io<TRAIT>(b, #FAM "_get_state", problem, dst, cap, true); } \
+    int FAM##_set_state(FAM* b, int problem, const float* src, size_t n) {                                                                            \
+        return batch_state_io<TRAIT>(b, #FAM "_set_state", problem, const_cast<float*>(src), n, false);                                               \
+    }
+
+// The fourteen closed-loop entries of a family, FAM and its trait as above: the bodies above under the family's names
 #define CTK_LOOP_ENTRIES(FAM, TRAIT)                                                                                                                  \
     int FAM##_plant_set_param(FAM* b, int n_ids, const int32_t* ids, int id, const float* values) {                                                   \
         return plant_set_param(b, #FAM "_plant_set_param", n_ids, ids, id, values);                                                                   \
@@ -899,20 +1001,24 @@ void batch_fill_record(const ctk_batch* b, CtkBatchStep& q, int p, int t) {
     q.pad = 0u; q.samples = nullptr;
 }
 
-// the MPPI family's part of the closed loop (the trait of batch_closed_loop, above); the MLP family runs it too
-struct MppiLoop {
+// the MPPI family's part of the drivers (the trait of batch_step and batch_closed_loop, above)
+struct MppiFamily {
     using Batch = ctk_batch;
     using Rec = CtkBatchStep;
-    static constexpr bool carries_k = false, error_word = true;
-    static int refuse(Batch*, const char*, int, const int32_t*) { return CTK_OK; }       // (the MLP family's missing weights: its own entries)
+    static constexpr bool carries_k = false, error_word = true, device_ahead_of_draws = true, state_size_named = false;
+    static constexpr const char* handoff_outputs = "; their outputs are NaN, the other problems' outputs are valid and written";   // this family's text alone says "their outputs are NaN"
+    static int refuse(Batch*, const char*, int, const int32_t*) { return CTK_OK; }       // (the MLP family's missing weights: MlpFamily)
+    static size_t draws_of(const Batch* b, int) { return (size_t)b->N * b->PC; }
+    static int check_draws(Batch* b, const char*, int, const int32_t*, const StepDraws& d, size_t) { return batch_check_draws(b, d); }
+    static const float*& draws(Rec& q) { return q.samples; }
     static RolloutArgs context(const Batch* b) { return batch_args(b); }
     static hipError_t constants(Batch* b, const int32_t*, int, unsigned char*) { return b->differ ? batch_flush_constants(b) : hipSuccess; }
     static void fill(const Batch* b, Rec& q, int p, int t) { batch_fill_record(b, q, p, t); }
     static hipError_t launch(Batch* b, const RolloutArgs& a, const Rec* d_rec, int n, const unsigned char*, int* launched) {
         return batch_launch_records(b, a, d_rec, n, launched);
     }
-    // by the rule of ctk_batch_step: a listed problem consumes its sequence number launched or not, its Philox position and plan buffer
-    // only if launched
+    // The counter rule: every listed problem, launched or not, consumes its sequence number (ctk_api.hip: guarded(); as CEM, RPGD
+    // differs on purpose); its Philox position and plan buffer only if launched
     static void advance(Batch* b, int p, int ctrl, bool tried, bool issued) {
         const size_t z = (size_t)p;
         b->seq[z] += (uint32_t)ctrl; b->call[z] += (uint32_t)ctrl; b->cur[z] ^= ctrl & 1;
@@ -921,28 +1027,24 @@ struct MppiLoop {
             if (issued) { ++b->call[z]; b->cur[z] ^= 1; }
         }
     }
+    // A launched step whose slot never shows the step's seq (a device fault).  By history this family's step advances the Philox
+    // position and reads u for every launched problem, published or not (CEM and RPGD: only if its slot shows the step's seq); the
+    // closed loop does not look per step in any family.
+    static constexpr bool unpublished_keeps_position = false;
+    // the state of a problem: its current plan, its last output
+    static BatchState state(Batch* b, int p) { return {{state_seg(b->unom(p, b->cur[(size_t)p]), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C)}}; }
+    static const char* per_problem_kernel(const Batch* b) {
+        return b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
+                                       : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    }
 };
-
-}  // namespace
-
-extern "C" {
-
-const char* ctk_batch_last_error(const ctk_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
-int ctk_batch_size(const ctk_batch* b) { return b ? b->B : 0; }
-size_t ctk_batch_samples_needed(const ctk_batch* b) { return b ? (size_t)b->N * b->PC : 0; }
-const char* ctk_batch_dominant_kernel(const ctk_batch* b) { return b ? b->dominant.c_str() : ""; }
-
-}  // extern "C"
-
-namespace {
 
 // ctk_batch_create (pred == CTK_PRED_ODE) and ctk_mlp_batch_create (CTK_PRED_MLP) into the caller's fresh struct: the refusals that need
 // only the configuration, the device probe, the buffers.  On failure the message is in g_create_error and the caller deletes the struct.
-int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problems, const uint64_t* seeds) {
+int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* cfg, int n_problems, const uint64_t* seeds) {
     const bool mlp = pred == CTK_PRED_MLP;
-    const char* who = mlp ? "ctk_mlp_batch_create" : "ctk_batch_create";
-    auto refuse = [&](int code, const std::string& msg) { return bfail(nullptr, code, mlp ? mlp_family_names(msg) : msg); };
-    if (n_problems < 1) return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
+    auto refuse = [&](int code, const std::string& msg) { return bfail(nullptr, code, std::string(who) + ": " + msg); };
+    if (n_problems < 1) return refuse(CTK_ERR_UNSUPPORTED, "a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
     const EnvInfo* einfo = nullptr;
     if (int rc = check_config(who, cfg, &einfo)) return rc;
     const int N = cfg->num_rollouts, H = cfg->mpc_horizon, P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
@@ -952,12 +1054,12 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
         : " (num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ", " + std::to_string(P) + " inducing points, network " +
           std::to_string(einfo->S + einfo->C) + "IN-" + std::to_string(hw1) + "H1-" + std::to_string(hw2) + "H2-" + std::to_string(einfo->S) + "OUT)";
     if (cfg->optimizer != CTK_OPT_MPPI)
-        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: a batch steps MPPI controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
+        return refuse(CTK_ERR_UNSUPPORTED, "a batch steps MPPI controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
                       "); the other optimizers run as single handles (ctk_create)" + sizes);
     if (!mlp && cfg->predictor != CTK_PRED_ODE)
-        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
+        return refuse(CTK_ERR_UNSUPPORTED, "the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
                       std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
-    if (mlp) {
+    if (mlp) {                                         // this family's own refusals, under its name; the first one names ctk_batch_create
         if (cfg->predictor == CTK_PRED_ODE)
             return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: this family rolls out the MLP predictor (cfg.predictor == " + std::to_string(cfg->predictor) +
                          " is the analytic one: use ctk_batch_create)" + sizes);
@@ -972,7 +1074,7 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
             return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: the batch kernel holds 32 units per hidden layer (narrower layers are embedded exactly); wider "
                          "networks run the 64-unit template kernels, which have no batch form (ctk_create)" + sizes);
     }
-    if (!(cfg->LBD > 0.0f && cfg->NU != 0.0f)) return refuse(CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: MPPI needs LBD > 0 and NU != 0");
+    if (!(cfg->LBD > 0.0f && cfg->NU != 0.0f)) return refuse(CTK_ERR_INVALID_ARGUMENT, "MPPI needs LBD > 0 and NU != 0");
     size_t lds = 0;
     int blocks = 0;
     if (const int why = mlp ? ctk_mppi_batch_mlp_fit(N, H, P, &lds, &blocks) : ctk_mppi_batch_fit(cfg->environment, N, H, P, &lds, &blocks)) {
@@ -983,7 +1085,7 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
                            : why == 2 ? ": the batch kernel has the narrow in-launch hand-off only (at most 128 records and 2048 record words per problem)"
                            : why == 3 ? ": the block records do not fit the hand-off's LDS staging"
                                       : ": the rollout tiles need more than 160 KiB of LDS";
-        return refuse(CTK_ERR_UNSUPPORTED, "ctk_batch_create: per-problem population outside the batch kernel's sizes (" + sizes + ")" + reason +
+        return refuse(CTK_ERR_UNSUPPORTED, "per-problem population outside the batch kernel's sizes (" + sizes + ")" + reason +
                       (why == 4 ? " (" + std::to_string(lds) + " bytes)" : std::string()) + "; such a controller runs as a single handle (ctk_create)");
     }
 
@@ -991,7 +1093,6 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
     if (int rc = probe_device(who, cfg->device, &prop)) return rc;
 
     batch_core_init(b, cfg, einfo, n_problems, seeds);        // dirty: no constants in d_k yet, the first step of the per-problem form derives them all
-    b->mlp_names = mlp;
     b->pred = pred; b->hid1 = hw1; b->hid2 = hw2;
     b->P = P; b->PC = P * b->C; b->blocks = blocks;
     b->mk = mppi_constants(b->cfg);
@@ -1045,130 +1146,52 @@ int batch_create_in(ctk_batch* b, int pred, const ctk_config* cfg, int n_problem
     return CTK_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-void ctk_batch_destroy(ctk_batch* b) { delete b; }
-
-int ctk_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_batch** out) {
+// *_create of the family's two forms (FAM: ctk_batch, ctk_mlp_batch)
+template <class FAM>
+int mppi_batch_create(const char* who, int pred, const ctk_config* cfg, int n_problems, const uint64_t* seeds, FAM** out) {
     if (out) *out = nullptr;
-    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_create: NULL argument");
-    ctk_batch* b = new ctk_batch();
-    if (int rc = batch_create_in(b, CTK_PRED_ODE, cfg, n_problems, seeds)) { delete b; return rc; }
+    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+    FAM* b = new FAM();
+    if (int rc = batch_create_in(b, who, pred, cfg, n_problems, seeds)) { delete b; return rc; }
     *out = b;
     return CTK_OK;
 }
 
-int ctk_batch_step(ctk_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
-                   float* u_out) {
-    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = batch_ids(b, "ctk_batch_step", n_ids, ids, &n)) return rc;
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // by history: ahead of the check of `samples` here, behind it in the CEM and RPGD steps
-    const size_t per = (size_t)b->N * b->PC;
-    const float* d_s = nullptr;                        // draws of the step's first problem; row j follows at j * per
-    if (samples_loc != CTK_LOC_NONE) {
-        if (samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
-        if (samples_loc == CTK_LOC_DEVICE) d_s = samples;
-        else if (samples_loc == CTK_LOC_HOST) {
-            if (int rc = batch_stage(b, samples, (size_t)n * per)) return rc;
-            d_s = b->d_samples;
-        } else return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
-    }
-    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es)
-    for (int j = 0; j < n; ++j) {
-        CtkBatchStep& q = b->h_steps[j];
-        batch_fill_record(b, q, ids ? ids[j] : j, 0);
-        if (d_s) q.samples = d_s + (size_t)j * per;
-        batch_record_io(b, q, j, s, u_prev);
-    }
-    hipError_t le = b->differ ? batch_flush_constants(b) : hipSuccess;          // the constants' transfer goes ahead of the step records'
-    if (le == hipSuccess) le = hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkBatchStep), hipMemcpyHostToDevice, b->stream);
-    const RolloutArgs a = batch_args(b);
-    int launched = 0;
-    if (le == hipSuccess) le = batch_launch_records(b, a, b->d_steps, n, &launched);
-    for (int j = 0; j < launched; ++j) b->cur[(size_t)b->h_steps[j].id] ^= 1;
-    const std::string late = batch_poll(b, ids, launched);
-    std::string timed_out;
-    for (int j = 0; j < n; ++j) {
-        const int p = b->h_steps[j].id;
-        ++b->seq[(size_t)p];                           // every listed problem, launched or not, consumes its sequence number (ctk_api.hip: guarded()); as CEM, RPGD differs on purpose
-        if (j >= launched) continue;
-        ++b->call[(size_t)p];                          // by history: for every launched problem, published or not (CEM and RPGD: only if its slot shows the step's seq)
-        batch_read_u(b, p, j, u_out);
-        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;   // the hand-off's error word (MPPI and CEM; RPGD has none)
-        if (errw[0]) { errw[0] = 0; list_problem(timed_out, p); }
-    }
-    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_batch_step: ") + hipGetErrorString(le));
-    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_batch_step: the step finished without publishing the result of problem(s) " + late);
-    if (!timed_out.empty())                            // this family's text alone says "their outputs are NaN"
-        return bfail(b, CTK_ERR_STATE, "ctk_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
-                     "; their outputs are NaN, the other problems' outputs are valid and written");
-    return CTK_OK;
-}
-
-int ctk_batch_reset(ctk_batch* b, int n_ids, const int32_t* ids) {
+// *_reset: optimizer_reset() of the listed problems
+int mppi_batch_reset(ctk_batch* b, const char* who, int n_ids, const int32_t* ids) {
     if (!b) return CTK_ERR_INVALID_ARGUMENT;
     int n = 0;
-    if (int rc = batch_ids(b, "ctk_batch_reset", n_ids, ids, &n)) return rc;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
     BHIP_TRY(b, hipSetDevice(b->cfg.device));
     for (int j = 0; j < n; ++j)
         if (int rc = batch_reset_one(b, ids ? ids[j] : j)) return rc;
     return CTK_OK;
 }
 
-int ctk_batch_read(ctk_batch* b, int problem, int buffer, float* dst, size_t cap) {
-    if (int rc = batch_read_check(b, "ctk_batch_read", problem, dst)) return rc;
+int mppi_batch_read(ctk_batch* b, const char* who, int problem, int buffer, float* dst, size_t cap) {
+    if (int rc = batch_read_check(b, who, problem, dst)) return rc;
     const float* src = nullptr; size_t n = 0;
-    if (int rc = batch_locate_rollouts(b, "ctk_batch_read", problem, buffer, &src, &n)) return rc;
+    if (int rc = batch_locate_rollouts(b, who, problem, buffer, &src, &n)) return rc;
     if (!src) {
-        if (buffer != CTK_BUF_U_NOM) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_batch_read: a batch has Q, J, TRAJ and U_NOM");
+        if (buffer != CTK_BUF_U_NOM) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": a batch has Q, J, TRAJ and U_NOM");
         src = b->unom(problem, b->cur[(size_t)problem]); n = (size_t)b->HC;
     }
-    return batch_read_out(b, "ctk_batch_read", src, n, false, dst, cap);
+    return batch_read_out(b, who, src, n, false, dst, cap);
 }
 
-// the state of a problem: its current plan, its last output
-static BatchState batch_state(ctk_batch* b, int p) { return {{state_seg(b->unom(p, b->cur[(size_t)p]), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C)}}; }
-int ctk_batch_get_state(ctk_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_batch_get_state", problem, dst, cap, true, false, batch_state); }
-int ctk_batch_set_state(ctk_batch* b, int problem, const float* src, size_t n) {
-    return batch_state_io(b, "ctk_batch_set_state", problem, const_cast<float*>(src), n, false, false, batch_state);
-}
-
-int ctk_batch_set_param(ctk_batch* b, int id, float value) { return batch_set_param(b, "ctk_batch_set_param", id, value); }
-int ctk_batch_get_param(const ctk_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
-int ctk_problem_set_param(ctk_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
-    bool flipped = false;
-    const int rc = batch_problem_set_param(b, "ctk_problem_set_param", n_ids, ids, id, values, &flipped);
-    if (flipped) b->dominant = b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
-                                                       : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
-    return rc;
-}
-int ctk_problem_get_param(const ctk_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
-int ctk_problem_params_differ(const ctk_batch* b) { return batch_params_differ(b); }
-int ctk_batch_rng_get_position(const ctk_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
-int ctk_batch_rng_set_position(ctk_batch* b, int problem, uint32_t call) { return batch_rng_set_position(b, "ctk_batch_rng_set_position", problem, call); }
-
-// ---- the closed loop on the device (include/ctk_hip_run.h: ctk_batch_plant_* / ctk_batch_run) and the stochastic plant with the realised
-// cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes) ----
-CTK_LOOP_ENTRIES(ctk_batch, MppiLoop)
-
-}  // extern "C"
+}  // namespace
 
 // =============================================================================================
 // Batched MPPI with the MLP predictor (include/ctk_hip.h: ctk_mlp_batch_* / ctk_mlp_problem_*): the ctk_batch above with pred == CTK_PRED_MLP
 // — the same struct, step records, completion poll, constants flush, reset and read paths — launched as ctk_mppi_batch_mlp<LOG> /
 // ctk_mppi_batch_mlp_pp<LOG>, plus what a learned plant adds: one per-lane weight table per problem (d_w [B][wtab], permute_mlp_weights as
 // for a handle's d_wperm), written by ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights through ONE transfer per call, and
-// `have_w`, without which a problem is not stepped.
+// `have_w`, without which a problem is not stepped (MlpFamily::refuse: its one difference from MppiFamily).  Its entries come from the
+// macros that write ctk_batch's, under its own names.
 // =============================================================================================
-struct ctk_mlp_batch { ctk_batch b; };
+struct ctk_mlp_batch : ctk_batch {};
 
 namespace {
-
-ctk_batch* core(ctk_mlp_batch* m) { return m ? &m->b : nullptr; }
-const ctk_batch* core(const ctk_mlp_batch* m) { return m ? &m->b : nullptr; }
 
 size_t mlp_batch_weight_count(const ctk_batch* b) { return shaped_weight_count(CTK_PRED_MLP, b->S, b->C, b->hid1, b->hid2); }
 
@@ -1199,47 +1222,55 @@ int mlp_batch_put_weights(ctk_batch* b, int n, const int32_t* ids, const float* 
     return CTK_OK;
 }
 
-// a problem without a network is not stepped, and then none of the listed ones is: nothing is launched, no plan, output or Philox
-// position moves (a handle's ctk_step fails the same way: check_predictor)
-int mlp_batch_have_weights(ctk_batch* b, const char* who, int n_ids, const int32_t* ids) {
-    int n = 0;
-    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
-    std::string missing;
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        if (!b->have_w[(size_t)p]) list_problem(missing, p);
+// the MPPI family under the MLP family's names, and its one refusal: a problem without a network is not stepped, and then none of the
+// listed ones is: nothing is launched, no plan, output or Philox position moves (a handle's ctk_step fails the same way: check_predictor)
+struct MlpFamily : MppiFamily {
+    using Batch = ctk_mlp_batch;
+    static int refuse(ctk_batch* b, const char* who, int n, const int32_t* ids) {
+        std::string missing;
+        for (int j = 0; j < n; ++j) {
+            const int p = ids ? ids[j] : j;
+            if (!b->have_w[(size_t)p]) list_problem(missing, p);
+        }
+        if (!missing.empty())
+            return bfail(b, CTK_ERR_STATE, std::string(who) + ": no network weights for problem(s) " + missing +
+                         " (ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights before stepping); nothing was launched");
+        return CTK_OK;
     }
-    if (!missing.empty())
-        return bfail(b, CTK_ERR_STATE, std::string(who) + ": no network weights for problem(s) " + missing +
-                     " (ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights before stepping); nothing was launched");
-    return CTK_OK;
-}
+};
 
 }  // namespace
 
 extern "C" {
 
-const char* ctk_mlp_batch_last_error(const ctk_mlp_batch* m) { return ctk_batch_last_error(core(m)); }
-int ctk_mlp_batch_size(const ctk_mlp_batch* m) { return ctk_batch_size(core(m)); }
-size_t ctk_mlp_batch_samples_needed(const ctk_mlp_batch* m) { return ctk_batch_samples_needed(core(m)); }
-const char* ctk_mlp_batch_dominant_kernel(const ctk_mlp_batch* m) { return ctk_batch_dominant_kernel(core(m)); }
+// create, samples_needed, step, reset and read of the family's two forms, FAM in {ctk_batch, ctk_mlp_batch}
+#define CTK_MPPI_ENTRIES(FAM, TRAIT, PRED)                                                                                                            \
+    int FAM##_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, FAM** out) {                                                       \
+        return mppi_batch_create(#FAM "_create", PRED, cfg, n_problems, seeds, out);                                                                  \
+    }                                                                                                                                                 \
+    size_t FAM##_samples_needed(const FAM* b) { return b ? (size_t)b->N * b->PC : 0; }                                                                \
+    int FAM##_step(FAM* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc, float* u_out) { \
+        return batch_step<TRAIT>(b, #FAM "_step", n_ids, ids, s, u_prev, StepDraws{samples, 0, samples_loc}, u_out);                                  \
+    }                                                                                                                                                 \
+    int FAM##_reset(FAM* b, int n_ids, const int32_t* ids) { return mppi_batch_reset(b, #FAM "_reset", n_ids, ids); }                                 \
+    int FAM##_read(FAM* b, int problem, int buffer, float* dst, size_t cap) { return mppi_batch_read(b, #FAM "_read", problem, buffer, dst, cap); }
 
-void ctk_mlp_batch_destroy(ctk_mlp_batch* m) { delete m; }
+CTK_MPPI_ENTRIES(ctk_batch, MppiFamily, CTK_PRED_ODE)
+CTK_BATCH_ENTRIES(ctk_batch, ctk_problem, MppiFamily)
+// the closed loop on the device (include/ctk_hip_run.h: ctk_batch_plant_* / ctk_batch_run) and the stochastic plant with the realised
+// cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes)
+CTK_LOOP_ENTRIES(ctk_batch, MppiFamily)
 
-int ctk_mlp_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_mlp_batch** out) {
-    if (out) *out = nullptr;
-    if (!cfg || !out) return bfail(nullptr, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_create: NULL argument");
-    ctk_mlp_batch* m = new ctk_mlp_batch();
-    if (int rc = batch_create_in(&m->b, CTK_PRED_MLP, cfg, n_problems, seeds)) { delete m; return rc; }
-    *out = m;
-    return CTK_OK;
-}
+// the same under the MLP family's names: the network plans, the plant of its closed loop is the analytic CartPole with the problem's
+// parameter table (and the overrides set there)
+CTK_MPPI_ENTRIES(ctk_mlp_batch, MlpFamily, CTK_PRED_MLP)
+CTK_BATCH_ENTRIES(ctk_mlp_batch, ctk_mlp_problem, MlpFamily)
+CTK_LOOP_ENTRIES(ctk_mlp_batch, MlpFamily)
 
-size_t ctk_mlp_batch_weight_count(const ctk_mlp_batch* m) { return m ? mlp_batch_weight_count(&m->b) : 0; }
+size_t ctk_mlp_batch_weight_count(const ctk_mlp_batch* b) { return b ? mlp_batch_weight_count(b) : 0; }
 
-int ctk_mlp_batch_set_weights(ctk_mlp_batch* m, const float* w, size_t n) {
-    if (!m) return CTK_ERR_INVALID_ARGUMENT;
-    ctk_batch* b = &m->b;
+int ctk_mlp_batch_set_weights(ctk_mlp_batch* b, const float* w, size_t n) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
     if (!w) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_set_weights: NULL weights");
     if (n != mlp_batch_weight_count(b))
         return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_set_weights: expected " + std::to_string(mlp_batch_weight_count(b)) + " floats for the " +
@@ -1248,9 +1279,8 @@ int ctk_mlp_batch_set_weights(ctk_mlp_batch* m, const float* w, size_t n) {
     return mlp_batch_put_weights(b, b->B, nullptr, w, n, false);
 }
 
-int ctk_mlp_problem_set_weights(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* w, size_t n) {
-    if (!m) return CTK_ERR_INVALID_ARGUMENT;
-    ctk_batch* b = &m->b;
+int ctk_mlp_problem_set_weights(ctk_mlp_batch* b, int n_ids, const int32_t* ids, const float* w, size_t n) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
     int cnt = 0;
     if (int rc = batch_ids(b, "ctk_mlp_problem_set_weights", n_ids, ids, &cnt)) return rc;
     if (!w) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_problem_set_weights: NULL weights (one network per listed problem)");
@@ -1261,75 +1291,7 @@ int ctk_mlp_problem_set_weights(ctk_mlp_batch* m, int n_ids, const int32_t* ids,
     return mlp_batch_put_weights(b, cnt, ids, w, n, true);
 }
 
-int ctk_mlp_problem_have_weights(const ctk_mlp_batch* m, int problem) {
-    return (m && problem >= 0 && problem < m->b.B && m->b.have_w[(size_t)problem]) ? 1 : 0;
-}
-
-int ctk_mlp_batch_step(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
-                       float* u_out) {
-    if (!m) return CTK_ERR_INVALID_ARGUMENT;
-    ctk_batch* b = &m->b;
-    if (!s) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_step: NULL state");
-    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_step", n_ids, ids)) return rc;
-    return ctk_batch_step(b, n_ids, ids, s, u_prev, samples, samples_loc, u_out);
-}
-
-// the closed loop on the device: ctk_batch_plant_* / ctk_batch_run under this family's names.  The network plans, the plant is the
-// analytic CartPole with the problem's parameter table (and the overrides set here)
-int ctk_mlp_batch_plant_set_param(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int id, const float* values) {
-    return ctk_batch_plant_set_param(core(m), n_ids, ids, id, values);
-}
-int ctk_mlp_batch_plant_get_param(const ctk_mlp_batch* m, int problem, int id, float* value) { return ctk_batch_plant_get_param(core(m), problem, id, value); }
-int ctk_mlp_batch_plant_clear_params(ctk_mlp_batch* m) { return ctk_batch_plant_clear_params(core(m)); }
-int ctk_mlp_batch_plant_step(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u, int substeps, float* s_next) {
-    return ctk_batch_plant_step(core(m), n_ids, ids, s, u, substeps, s_next);
-}
-int ctk_mlp_batch_run(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s0, const float* u_prev, int n_steps, int plant_substeps,
-                      float* states_out, float* inputs_out, int32_t* first_bad) {
-    if (!m) return CTK_ERR_INVALID_ARGUMENT;
-    ctk_batch* b = &m->b;
-    if (!s0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_run: NULL start states or trace destination");
-    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_run", n_ids, ids)) return rc;
-    return ctk_batch_run(b, n_ids, ids, s0, u_prev, n_steps, plant_substeps, states_out, inputs_out, first_bad);
-}
-// the stochastic plant and the realised cost (include/ctk_hip_episode.h), under this family's names
-int ctk_mlp_batch_plant_set_noise(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int kind, const float* sigma) {
-    return ctk_batch_plant_set_noise(core(m), n_ids, ids, kind, sigma);
-}
-int ctk_mlp_batch_plant_get_noise(const ctk_mlp_batch* m, int problem, int kind, float* sigma) { return ctk_batch_plant_get_noise(core(m), problem, kind, sigma); }
-int ctk_mlp_batch_plant_clear_noise(ctk_mlp_batch* m) { return ctk_batch_plant_clear_noise(core(m)); }
-int ctk_mlp_batch_plant_set_noise_seed(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const uint64_t* seeds) {
-    return ctk_batch_plant_set_noise_seed(core(m), n_ids, ids, seeds);
-}
-int ctk_mlp_batch_plant_get_noise_seed(const ctk_mlp_batch* m, int problem, uint64_t* seed) { return ctk_batch_plant_get_noise_seed(core(m), problem, seed); }
-int ctk_mlp_batch_plant_noise_get_position(const ctk_mlp_batch* m, int problem, uint32_t* pos) { return ctk_batch_plant_noise_get_position(core(m), problem, pos); }
-int ctk_mlp_batch_plant_noise_set_position(ctk_mlp_batch* m, int problem, uint32_t pos) { return ctk_batch_plant_noise_set_position(core(m), problem, pos); }
-int ctk_mlp_batch_plant_step_noisy(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s, const float* u, const float* u_prev, int substeps,
-                                   float* s_next, float* y_next, float* cost) {
-    return ctk_batch_plant_step_noisy(core(m), n_ids, ids, s, u, u_prev, substeps, s_next, y_next, cost);
-}
-int ctk_mlp_batch_episodes(ctk_mlp_batch* m, int n_ids, const int32_t* ids, const float* s0, const float* y0, const float* u_prev, int n_steps,
-                           int plant_substeps, float* states_out, float* obs_out, float* inputs_out, float* costs_out, int32_t* first_bad) {
-    if (!m) return CTK_ERR_INVALID_ARGUMENT;
-    ctk_batch* b = &m->b;
-    if (!s0) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_mlp_batch_episodes: NULL start states or trace destination");
-    if (int rc = mlp_batch_have_weights(b, "ctk_mlp_batch_episodes", n_ids, ids)) return rc;
-    return ctk_batch_episodes(b, n_ids, ids, s0, y0, u_prev, n_steps, plant_substeps, states_out, obs_out, inputs_out, costs_out, first_bad);
-}
-
-int ctk_mlp_batch_reset(ctk_mlp_batch* m, int n_ids, const int32_t* ids) { return ctk_batch_reset(core(m), n_ids, ids); }
-int ctk_mlp_batch_read(ctk_mlp_batch* m, int problem, int buffer, float* dst, size_t cap) { return ctk_batch_read(core(m), problem, buffer, dst, cap); }
-int ctk_mlp_batch_get_state(ctk_mlp_batch* m, int problem, float* dst, size_t cap) { return ctk_batch_get_state(core(m), problem, dst, cap); }
-int ctk_mlp_batch_set_state(ctk_mlp_batch* m, int problem, const float* src, size_t n) { return ctk_batch_set_state(core(m), problem, src, n); }
-int ctk_mlp_batch_set_param(ctk_mlp_batch* m, int id, float value) { return ctk_batch_set_param(core(m), id, value); }
-int ctk_mlp_batch_get_param(const ctk_mlp_batch* m, int id, float* value) { return ctk_batch_get_param(core(m), id, value); }
-int ctk_mlp_problem_set_param(ctk_mlp_batch* m, int n_ids, const int32_t* ids, int id, const float* values) {
-    return ctk_problem_set_param(core(m), n_ids, ids, id, values);
-}
-int ctk_mlp_problem_get_param(const ctk_mlp_batch* m, int problem, int id, float* value) { return ctk_problem_get_param(core(m), problem, id, value); }
-int ctk_mlp_problem_params_differ(const ctk_mlp_batch* m) { return ctk_problem_params_differ(core(m)); }
-int ctk_mlp_batch_rng_get_position(const ctk_mlp_batch* m, int problem, uint32_t* call) { return ctk_batch_rng_get_position(core(m), problem, call); }
-int ctk_mlp_batch_rng_set_position(ctk_mlp_batch* m, int problem, uint32_t call) { return ctk_batch_rng_set_position(core(m), problem, call); }
+int ctk_mlp_problem_have_weights(const ctk_mlp_batch* b, int problem) { return (b && problem >= 0 && problem < b->B && b->have_w[(size_t)problem]) ? 1 : 0; }
 
 }  // extern "C"
 
@@ -1402,12 +1364,32 @@ hipError_t cem_batch_launch_records(ctk_cem_batch* b, const CemBatchCtx& x, cons
     return le;
 }
 
-// the CEM family's part of the closed loop (the trait of batch_closed_loop)
-struct CemLoop {
+// the CEM family's part of the drivers (the trait of batch_step and batch_closed_loop)
+struct CemFamily {
     using Batch = ctk_cem_batch;
     using Rec = CtkCemBatchStep;
-    static constexpr bool carries_k = true, error_word = true;
+    static constexpr bool carries_k = true, error_word = true, device_ahead_of_draws = false, state_size_named = false;
+    static constexpr const char* handoff_outputs = "; the other problems' outputs are valid and written";
     static int refuse(Batch*, const char*, int, const int32_t*) { return CTK_OK; }
+    static size_t draws_of(const Batch* b, int p) { return (size_t)b->its(p) * b->N * b->HC; }
+    // the rows of a caller's buffer have ONE length: mixed iteration counts are refused before anything is launched or consumed
+    static int check_draws(Batch* b, const char* who, int n, const int32_t* ids, const StepDraws& d, size_t) {
+        if (int rc = batch_check_draws(b, d)) return rc;
+        if (d.loc == CTK_LOC_NONE) return CTK_OK;
+        const int its0 = b->its(ids ? ids[0] : 0);
+        bool mixed = false;
+        for (int j = 1; j < n; ++j) mixed |= b->its(ids ? ids[j] : j) != its0;
+        if (!mixed) return CTK_OK;
+        std::string each;
+        for (int j = 0; j < n; ++j) {
+            const int p = ids ? ids[j] : j;
+            each += (j ? ", " : "") + std::to_string(p) + ": " + std::to_string(b->its(p));
+        }
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": with caller-supplied samples every listed problem must run the same number of outer "
+                     "iterations, but (problem: iterations) " + each + " — the warm-up step of a problem after its creation or reset is longer; step them in "
+                     "separate calls (the in-kernel sampler has no such restriction)");
+    }
+    static const float*& draws(Rec& q) { return q.samples; }
     static CemBatchCtx context(const Batch* b) { return cem_batch_context(b); }
     static hipError_t constants(Batch* b, const int32_t* ids, int n, unsigned char* h_k) {
         if (b->differ) batch_stage_constants(b, b->kcache.data(), ids, n, h_k);
@@ -1425,8 +1407,9 @@ struct CemLoop {
     static hipError_t launch(Batch* b, const CemBatchCtx& x, const Rec* d_rec, int n, const unsigned char* d_k, int* launched) {
         return cem_batch_launch_records(b, x, d_rec, n, d_k, launched);
     }
-    // by the rule of ctk_cem_batch_step: a listed problem consumes its sequence number and its tags launched or not; its step count and
-    // Philox position advance, and BEST_IDX goes stale, only if launched
+    // The counter rule: every listed problem, launched or not, consumes its sequence number (ctk_api.hip: guarded(); as MPPI, RPGD
+    // differs on purpose) and, as every launch attempt does, its tags (cem_step: the wrap rule keeps tag 0 the never-written value);
+    // its step count and Philox position advance, and BEST_IDX goes stale, only if launched (as cem_step: with the launch)
     static void advance(Batch* b, int p, int ctrl, bool tried, bool issued) {
         const size_t z = (size_t)p;
         const int listed = ctrl + (tried ? 1 : 0), ran = ctrl + (tried && issued ? 1 : 0);
@@ -1434,6 +1417,15 @@ struct CemLoop {
         b->seq[z] += (uint32_t)listed; b->call[z] += (uint32_t)ran; b->count[z] += ran;
         if (ran) b->idx_stale[z] = 1;
     }
+    // A launched step whose slot never shows the step's seq (a device fault): ctk_api.hip's finish_step returns before it advances the
+    // Philox position or reads u, and so does this family's step (as RPGD; MPPI advances it regardless, by history); the closed loop
+    // does not look per step in any family.
+    static constexpr bool unpublished_keeps_position = true;
+    // the state of a problem: mean, standard deviation, last output; its step count
+    static BatchState state(Batch* b, int p) {
+        return {{state_seg(b->mu(p), (size_t)b->HC), state_seg(b->sd(p), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C), state_counter(&b->count[(size_t)p])}};
+    }
+    static const char* per_problem_kernel(const Batch* b) { return ctk_cem_batch_name(b->env, b->cfg.materialize_trajectories != 0, true); }
 };
 
 // mean at mid-range, std = cem_initial_action_stdev, u = 0 of problem p into the host images (ctk_reset of a CEM handle)
@@ -1448,14 +1440,11 @@ void cem_batch_initial(const ctk_cem_batch* b, float* mu, float* sd) {
 
 extern "C" {
 
-const char* ctk_cem_batch_last_error(const ctk_cem_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
-int ctk_cem_batch_size(const ctk_cem_batch* b) { return b ? b->B : 0; }
-size_t ctk_cem_batch_samples_needed(const ctk_cem_batch* b, int problem) {
-    return (b && problem >= 0 && problem < b->B) ? (size_t)b->its(problem) * b->N * b->HC : 0;
-}
-const char* ctk_cem_batch_dominant_kernel(const ctk_cem_batch* b) { return b ? b->dominant.c_str() : ""; }
+CTK_BATCH_ENTRIES(ctk_cem_batch, ctk_cem_problem, CemFamily)
+// ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_cem_batch_plant_* / ctk_cem_batch_run / ctk_cem_batch_episodes) ----
+CTK_LOOP_ENTRIES(ctk_cem_batch, CemFamily)
 
-void ctk_cem_batch_destroy(ctk_cem_batch* b) { delete b; }
+size_t ctk_cem_batch_samples_needed(const ctk_cem_batch* b, int problem) { return (b && problem >= 0 && problem < b->B) ? CemFamily::draws_of(b, problem) : 0; }
 
 int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_cem_batch** out) {
     if (out) *out = nullptr;
@@ -1538,73 +1527,7 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
 
 int ctk_cem_batch_step(ctk_cem_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples, int samples_loc,
                        float* u_out) {
-    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = batch_ids(b, "ctk_cem_batch_step", n_ids, ids, &n)) return rc;
-    const size_t per_it = (size_t)b->N * b->HC;
-    const int its0 = b->its(ids ? ids[0] : 0);
-    if (samples_loc != CTK_LOC_NONE) {
-        if (samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
-        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
-        // the rows of a caller's buffer have ONE length: refused before anything is launched or consumed
-        bool mixed = false;
-        for (int j = 1; j < n; ++j) mixed |= b->its(ids ? ids[j] : j) != its0;
-        if (mixed) {
-            std::string who;
-            for (int j = 0; j < n; ++j) {
-                const int p = ids ? ids[j] : j;
-                who += (j ? ", " : "") + std::to_string(p) + ": " + std::to_string(b->its(p));
-            }
-            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_step: with caller-supplied samples every listed problem must run the same number of outer "
-                         "iterations, but (problem: iterations) " + who + " — the warm-up step of a problem after its creation or reset is longer; step them in "
-                         "separate calls (the in-kernel sampler has no such restriction)");
-        }
-    }
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // behind the checks of `samples`, as in the RPGD step (the MPPI step: ahead of them, by history)
-    const size_t per = per_it * (size_t)its0;          // draws per problem (caller-supplied samples: the same for all listed problems)
-    const float* d_s = nullptr;                        // draws of the step's first problem; row j follows at j * per
-    if (samples_loc == CTK_LOC_DEVICE) d_s = samples;
-    else if (samples_loc == CTK_LOC_HOST) {
-        if (int rc = batch_stage(b, samples, (size_t)n * per)) return rc;
-        d_s = b->d_samples;
-    }
-    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es).  Every launch attempt
-    // consumes the problem's tags, as it consumes its sequence number (cem_step: the wrap rule keeps tag 0 the never-written value)
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        const size_t z = (size_t)p;
-        const int its = b->its(p);
-        CtkCemBatchStep& q = b->h_steps[j];
-        b->cem_tag[z] = cem_tag0(b->cem_tag[z], its);
-        q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.tag0 = b->cem_tag[z]; q.its = its;
-        b->cem_tag[z] += (uint32_t)its;
-        q.samples = d_s ? d_s + (size_t)j * per : nullptr;
-        batch_record_io(b, q, j, s, u_prev);
-    }
-    const unsigned char* d_ksteps = nullptr;           // the per-problem form: the constants behind the records, in the same transfer
-    hipError_t le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(CtkCemBatchStep), b->h_steps, b->d_steps, &d_ksteps);
-    int launched = 0;                                  // consecutive launches of at most max_per_launch problems; a problem never spans launches
-    if (le == hipSuccess) le = cem_batch_launch_records(b, cem_batch_context(b), b->d_steps, n, d_ksteps, &launched);
-    const std::string late = batch_poll(b, ids, launched);
-    std::string timed_out;
-    for (int j = 0; j < n; ++j) {
-        const int p = b->h_steps[j].id;
-        const size_t z = (size_t)p;
-        ++b->seq[z];                                   // every listed problem, launched or not, consumes its sequence number (ctk_api.hip: guarded()); as MPPI, RPGD differs on purpose
-        if (j >= launched) continue;
-        ++b->count[z]; b->idx_stale[z] = 1;            // as cem_step: with the launch
-        if (reinterpret_cast<volatile uint32_t*>(b->slot(p))[1] != b->h_steps[j].seq) continue;   // never published (a device fault): ctk_api.hip's finish_step
-        ++b->call[z];                                  // returns before it advances the Philox position or reads u (as RPGD; MPPI advances it regardless, by history)
-        batch_read_u(b, p, j, u_out);
-        volatile uint32_t* errw = reinterpret_cast<volatile uint32_t*>(b->slot(p)) + 2;   // the hand-off's error word (MPPI and CEM; RPGD has none)
-        if (errw[0]) { errw[0] = 0; list_problem(timed_out, p); }
-    }
-    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_cem_batch_step: ") + hipGetErrorString(le));
-    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_cem_batch_step: the step finished without publishing the result of problem(s) " + late);
-    if (!timed_out.empty())
-        return bfail(b, CTK_ERR_STATE, "ctk_cem_batch_step: in-launch record hand-off timed out (a workgroup's record never arrived) for problem(s) " + timed_out +
-                     "; the other problems' outputs are valid and written");
-    return CTK_OK;
+    return batch_step<CemFamily>(b, "ctk_cem_batch_step", n_ids, ids, s, u_prev, StepDraws{samples, 0, samples_loc}, u_out);
 }
 
 int ctk_cem_batch_reset(ctk_cem_batch* b, int n_ids, const int32_t* ids) {
@@ -1644,33 +1567,6 @@ int ctk_cem_batch_read(ctk_cem_batch* b, int problem, int buffer, float* dst, si
         return CTK_OK;
     });
 }
-
-// the state of a problem: mean, standard deviation, last output; its step count
-static BatchState cem_batch_state(ctk_cem_batch* b, int p) {
-    return {{state_seg(b->mu(p), (size_t)b->HC), state_seg(b->sd(p), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C), state_counter(&b->count[(size_t)p])}};
-}
-int ctk_cem_batch_get_state(ctk_cem_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_cem_batch_get_state", problem, dst, cap, true, false, cem_batch_state); }
-int ctk_cem_batch_set_state(ctk_cem_batch* b, int problem, const float* src, size_t n) {
-    return batch_state_io(b, "ctk_cem_batch_set_state", problem, const_cast<float*>(src), n, false, false, cem_batch_state);
-}
-
-int ctk_cem_batch_set_param(ctk_cem_batch* b, int id, float value) { return batch_set_param(b, "ctk_cem_batch_set_param", id, value); }
-int ctk_cem_batch_get_param(const ctk_cem_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
-int ctk_cem_problem_set_param(ctk_cem_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
-    bool flipped = false;
-    const int rc = batch_problem_set_param(b, "ctk_cem_problem_set_param", n_ids, ids, id, values, &flipped);
-    if (flipped) b->dominant = ctk_cem_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
-    return rc;
-}
-int ctk_cem_problem_get_param(const ctk_cem_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
-int ctk_cem_problem_params_differ(const ctk_cem_batch* b) { return batch_params_differ(b); }
-int ctk_cem_batch_rng_get_position(const ctk_cem_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
-int ctk_cem_batch_rng_set_position(ctk_cem_batch* b, int problem, uint32_t call) {
-    return batch_rng_set_position(b, "ctk_cem_batch_rng_set_position", problem, call);
-}
-
-// ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_cem_batch_plant_* / ctk_cem_batch_run / ctk_cem_batch_episodes) ----
-CTK_LOOP_ENTRIES(ctk_cem_batch, CemLoop)
 
 }  // extern "C"
 
@@ -1768,12 +1664,26 @@ int rpgd_batch_ready(ctk_rpgd_batch* b, const char* who, int n, const int32_t* i
     return CTK_OK;
 }
 
-// the RPGD family's part of the closed loop (the trait of batch_closed_loop)
-struct RpgdLoop {
+// the RPGD family's part of the drivers (the trait of batch_step and batch_closed_loop)
+struct RpgdFamily {
     using Batch = ctk_rpgd_batch;
     using Rec = CtkRpgdBatchStep;
     static constexpr bool carries_k = true, error_word = false;      // this kernel has no in-launch hand-off
+    static constexpr bool device_ahead_of_draws = false, state_size_named = true;
     static int refuse(Batch* b, const char* who, int n, const int32_t* ids) { return rpgd_batch_ready(b, who, n, ids); }
+    // one [num_rollouts - opt_keep_k, P, C] block for every listed problem that resamples at this step, none for the others
+    static size_t draws_of(const Batch* b, int p) { return b->needs(p); }
+    static int check_draws(Batch* b, const char* who, int, const int32_t*, const StepDraws& d, size_t need) {
+        if (d.loc == CTK_LOC_NONE) return CTK_OK;
+        if (d.loc != CTK_LOC_DEVICE && d.loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
+        if (d.n_samples != need)                       // refused before a sample is read
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(d.n_samples) + " samples given, the listed problems need " +
+                         std::to_string(need) + " (one [num_rollouts - opt_keep_k, P, C] block for every listed problem whose ctk_rpgd_batch_samples_needed is "
+                         "non-zero, in id order); nothing was launched");
+        if (need != 0 && d.samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
+        return CTK_OK;
+    }
+    static const float*& draws(Rec& q) { return q.draws; }
     static RpgdBatchCtx context(const Batch* b) { return {rpgd_batch_args(b), rpgd_batch_warm(b)}; }
     static hipError_t constants(Batch* b, const int32_t* ids, int n, unsigned char* h_k) {
         if (b->differ) batch_stage_constants(b, b->kcache.data(), ids, n, h_k);
@@ -1792,13 +1702,29 @@ struct RpgdLoop {
     static hipError_t launch(Batch* b, const RpgdBatchCtx& x, const Rec* d_rec, int n, const unsigned char* d_k, int* launched) {
         return rpgd_batch_launch_records(b, x, d_rec, n, d_k, launched);
     }
-    // by the rule of ctk_rpgd_batch_step, on purpose: a problem never issued consumes nothing, not even its sequence number
+    // The counter rule, on purpose: a problem never issued consumes nothing, not even its sequence number (the MPPI and CEM families
+    // consume seq for every listed problem); the Adam step number, the buffer and the step count move with the launch (as rpgd_descent /
+    // rpgd_step)
     static void advance(Batch* b, int p, int ctrl, bool tried, bool issued) {
         const size_t z = (size_t)p;
         const int ran = ctrl + (tried && issued ? 1 : 0);
         for (int i = 0; i < ran; ++i) b->adam_step[z] += b->its_at(p, i);      // (ahead of count, which its_at reads)
         b->seq[z] += (uint32_t)ran; b->call[z] += (uint32_t)ran; b->cur[z] ^= ran & 1; b->count[z] += ran;
     }
+    // A launched step whose slot never shows the step's seq (a device fault): ctk_api.hip's finish_step returns before it advances the
+    // Philox position or reads u, and so does this family's step (as CEM; MPPI advances it regardless, by history); the closed loop
+    // does not look per step in any family.
+    static constexpr bool unpublished_keeps_position = true;
+    // the state of a problem (ctk_state_size of an RPGD handle): population, Adam moments, ages, last output; Adam step and step count.
+    // A problem whose state was set counts as reset.
+    static BatchState state(Batch* b, int p) {
+        const size_t z = (size_t)p, N = (size_t)b->N, NHC = b->NHC();
+        const int cur = b->cur[z];
+        return {{state_seg(b->d_pop[cur] + z * NHC, NHC), state_seg(b->d_m[cur] + z * NHC, NHC), state_seg(b->d_v[cur] + z * NHC, NHC),
+                 state_seg(b->d_ages[cur] + z * N, N), state_seg(b->u(p), (size_t)b->C), state_counter(&b->adam_step[z]), state_counter(&b->count[z])},
+                &b->ready[z]};
+    }
+    static const char* per_problem_kernel(const Batch* b) { return ctk_g_rpgd_batch_name(b->env, true); }
 };
 
 }  // namespace
@@ -1814,12 +1740,11 @@ size_t ctk_rpgd_template_descent_lds(int environment, int mpc_horizon, int* tape
     return lds;
 }
 
-const char* ctk_rpgd_batch_last_error(const ctk_rpgd_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
-int ctk_rpgd_batch_size(const ctk_rpgd_batch* b) { return b ? b->B : 0; }
-size_t ctk_rpgd_batch_samples_needed(const ctk_rpgd_batch* b, int problem) { return (b && problem >= 0 && problem < b->B) ? b->needs(problem) : 0; }
-const char* ctk_rpgd_batch_dominant_kernel(const ctk_rpgd_batch* b) { return b ? b->dominant.c_str() : ""; }
+CTK_BATCH_ENTRIES(ctk_rpgd_batch, ctk_rpgd_problem, RpgdFamily)
+// ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_rpgd_batch_plant_* / ctk_rpgd_batch_run / ctk_rpgd_batch_episodes) ----
+CTK_LOOP_ENTRIES(ctk_rpgd_batch, RpgdFamily)
 
-void ctk_rpgd_batch_destroy(ctk_rpgd_batch* b) { delete b; }
+size_t ctk_rpgd_batch_samples_needed(const ctk_rpgd_batch* b, int problem) { return (b && problem >= 0 && problem < b->B) ? b->needs(problem) : 0; }
 
 int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, ctk_rpgd_batch** out) {
     if (out) *out = nullptr;
@@ -1966,61 +1891,7 @@ int ctk_rpgd_batch_reset(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const
 
 int ctk_rpgd_batch_step(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev, const float* samples,
                         size_t n_samples, int samples_loc, float* u_out) {
-    if (!b || !s) return b ? bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: NULL state") : CTK_ERR_INVALID_ARGUMENT;
-    int n = 0;
-    if (int rc = batch_ids(b, "ctk_rpgd_batch_step", n_ids, ids, &n)) return rc;
-    if (int rc = rpgd_batch_ready(b, "ctk_rpgd_batch_step", n, ids)) return rc;
-    size_t need = 0;
-    for (int j = 0; j < n; ++j) need += b->needs(ids ? ids[j] : j);
-    if (samples_loc != CTK_LOC_NONE) {
-        if (samples_loc != CTK_LOC_DEVICE && samples_loc != CTK_LOC_HOST) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "bad samples_loc");
-        if (n_samples != need)                          // refused before a sample is read
-            return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_rpgd_batch_step: " + std::to_string(n_samples) + " samples given, the listed problems need " +
-                         std::to_string(need) + " (one [num_rollouts - opt_keep_k, P, C] block for every listed problem whose ctk_rpgd_batch_samples_needed is "
-                         "non-zero, in id order); nothing was launched");
-        if (need != 0 && samples == nullptr) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "samples pointer is NULL but samples_loc != CTK_LOC_NONE");
-    }
-    BHIP_TRY(b, hipSetDevice(b->cfg.device));         // behind the checks of `samples`, as in the CEM step (the MPPI step: ahead of them, by history)
-    const float* d_s = nullptr;                        // the first block; the blocks follow one another in the order of the listed problems that draw
-    if (samples_loc == CTK_LOC_DEVICE && need) d_s = samples;
-    else if (samples_loc == CTK_LOC_HOST && need) {
-        if (int rc = batch_stage(b, samples, need)) return rc;
-        d_s = b->d_samples;
-    }
-    // the step records: states and previous inputs travel with them, in ONE transfer ahead of the launch(es)
-    size_t off = 0;
-    for (int j = 0; j < n; ++j) {
-        const int p = ids ? ids[j] : j;
-        const size_t z = (size_t)p;
-        CtkRpgdBatchStep& q = b->h_steps[j];
-        q.id = p; q.seq = b->seq[z]; q.call = b->call[z]; q.cur = b->cur[z];
-        q.iters = b->its(p); q.t0 = b->adam_step[z]; q.resample = b->resamples(p) ? 1 : 0;
-        const size_t cnt = b->needs(p);
-        q.draws = (d_s && cnt) ? d_s + off : nullptr;
-        off += d_s ? cnt : 0;
-        q.pad = 0;
-        batch_record_io(b, q, j, s, u_prev);
-    }
-    const unsigned char* d_ksteps = nullptr;           // the per-problem form: the constants behind the records, in the same transfer
-    hipError_t le = batch_send_records(b, b->kcache.data(), ids, n, sizeof(CtkRpgdBatchStep), b->h_steps, b->d_steps, &d_ksteps);
-    int launched = 0;                                  // consecutive launches only past the grid's y limit; a problem never spans launches
-    if (le == hipSuccess) le = rpgd_batch_launch_records(b, RpgdBatchCtx{rpgd_batch_args(b), rpgd_batch_warm(b)}, b->d_steps, n, d_ksteps, &launched);
-    // h_steps is both the source of the transfer above and, below, the host's memory of id / seq / iters for the bookkeeping: that holds
-    // because the call is synchronous (nothing refills h_steps before it returns); an asynchronous step would need its own copy.
-    const std::string late = batch_poll(b, ids, launched);
-    for (int j = 0; j < launched; ++j) {               // on purpose: a problem never issued consumes no sequence number, nothing of it advances
-        const int p = b->h_steps[j].id;                // (the MPPI and CEM steps consume seq for every listed problem)
-        const size_t z = (size_t)p;
-        ++b->seq[z];
-        b->adam_step[z] += b->h_steps[j].iters;        // as rpgd_descent / rpgd_step: with the launch
-        b->cur[z] ^= 1; ++b->count[z];
-        if (reinterpret_cast<volatile uint32_t*>(b->slot(p))[1] != b->h_steps[j].seq) continue;   // never published (a device fault): ctk_api.hip's finish_step
-        ++b->call[z];                                  // returns before it advances the Philox position or reads u (as CEM; MPPI advances it regardless, by history)
-        batch_read_u(b, p, j, u_out);                  // no error word to read here: this kernel has no in-launch hand-off (MPPI and CEM have)
-    }
-    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, std::string("ctk_rpgd_batch_step: ") + hipGetErrorString(le));
-    if (!late.empty()) return bfail(b, CTK_ERR_HIP, "ctk_rpgd_batch_step: the step finished without publishing the result of problem(s) " + late);
-    return CTK_OK;
+    return batch_step<RpgdFamily>(b, "ctk_rpgd_batch_step", n_ids, ids, s, u_prev, StepDraws{samples, n_samples, samples_loc}, u_out);
 }
 
 int ctk_rpgd_batch_read(ctk_rpgd_batch* b, int problem, int buffer, float* dst, size_t cap) {
@@ -2042,37 +1913,5 @@ int ctk_rpgd_batch_read(ctk_rpgd_batch* b, int problem, int buffer, float* dst, 
     }
     return batch_read_out(b, "ctk_rpgd_batch_read", src, n, is_int, dst, cap);
 }
-
-// the state of a problem (ctk_state_size of an RPGD handle): population, Adam moments, ages, last output; Adam step and step count.
-// A problem whose state was set counts as reset.
-static BatchState rpgd_batch_state(ctk_rpgd_batch* b, int p) {
-    const size_t z = (size_t)p, N = (size_t)b->N, NHC = b->NHC();
-    const int cur = b->cur[z];
-    return {{state_seg(b->d_pop[cur] + z * NHC, NHC), state_seg(b->d_m[cur] + z * NHC, NHC), state_seg(b->d_v[cur] + z * NHC, NHC),
-             state_seg(b->d_ages[cur] + z * N, N), state_seg(b->u(p), (size_t)b->C), state_counter(&b->adam_step[z]), state_counter(&b->count[z])},
-            &b->ready[z]};
-}
-int ctk_rpgd_batch_get_state(ctk_rpgd_batch* b, int problem, float* dst, size_t cap) { return batch_state_io(b, "ctk_rpgd_batch_get_state", problem, dst, cap, true, true, rpgd_batch_state); }
-int ctk_rpgd_batch_set_state(ctk_rpgd_batch* b, int problem, const float* src, size_t n) {
-    return batch_state_io(b, "ctk_rpgd_batch_set_state", problem, const_cast<float*>(src), n, false, true, rpgd_batch_state);
-}
-
-int ctk_rpgd_batch_set_param(ctk_rpgd_batch* b, int id, float value) { return batch_set_param(b, "ctk_rpgd_batch_set_param", id, value); }
-int ctk_rpgd_batch_get_param(const ctk_rpgd_batch* b, int id, float* value) { return batch_get_param(b, id, value); }
-int ctk_rpgd_problem_set_param(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, int id, const float* values) {
-    bool flipped = false;
-    const int rc = batch_problem_set_param(b, "ctk_rpgd_problem_set_param", n_ids, ids, id, values, &flipped);
-    if (flipped) b->dominant = ctk_g_rpgd_batch_name(b->env, true);
-    return rc;
-}
-int ctk_rpgd_problem_get_param(const ctk_rpgd_batch* b, int problem, int id, float* value) { return batch_problem_get_param(b, problem, id, value); }
-int ctk_rpgd_problem_params_differ(const ctk_rpgd_batch* b) { return batch_params_differ(b); }
-int ctk_rpgd_batch_rng_get_position(const ctk_rpgd_batch* b, int problem, uint32_t* call) { return batch_rng_get_position(b, problem, call); }
-int ctk_rpgd_batch_rng_set_position(ctk_rpgd_batch* b, int problem, uint32_t call) {
-    return batch_rng_set_position(b, "ctk_rpgd_batch_rng_set_position", problem, call);
-}
-
-// ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_rpgd_batch_plant_* / ctk_rpgd_batch_run / ctk_rpgd_batch_episodes) ----
-CTK_LOOP_ENTRIES(ctk_rpgd_batch, RpgdLoop)
 
 }  // extern "C"
