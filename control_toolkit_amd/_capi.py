@@ -128,10 +128,10 @@ SYMBOLS = {
     "ctk_resident_stats": (C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
-# the four batch families (ctk_batch_*, ctk_mlp_batch_*, ctk_cem_batch_*, ctk_rpgd_batch_*; _H is the family's batch pointer there): the
-# signatures they share under a family's (batch prefix, problem prefix), then what differs, by name
-_BATCH_FAMILIES = (("ctk_batch", "ctk_problem"), ("ctk_mlp_batch", "ctk_mlp_problem"), ("ctk_cem_batch", "ctk_cem_problem"),
-                   ("ctk_rpgd_batch", "ctk_rpgd_problem"))
+# the five batch families (ctk_batch_*, ctk_mlp_batch_*, ctk_gru_batch_*, ctk_cem_batch_*, ctk_rpgd_batch_*; _H is the family's batch
+# pointer there): the signatures they share under a family's (batch prefix, problem prefix), then what differs, by name
+_BATCH_FAMILIES = (("ctk_batch", "ctk_problem"), ("ctk_mlp_batch", "ctk_mlp_problem"), ("ctk_gru_batch", "ctk_gru_problem"),
+                   ("ctk_cem_batch", "ctk_cem_problem"), ("ctk_rpgd_batch", "ctk_rpgd_problem"))
 _BATCH_SHARED = {
     "create": (C.c_int, [C.POINTER(CtkConfig), C.c_int, C.c_void_p, C.POINTER(_H)]),
     "destroy": (None, [_H]),
@@ -170,6 +170,14 @@ SYMBOLS.update({
     "ctk_mlp_batch_set_weights": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
     "ctk_mlp_problem_set_weights": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ctk_mlp_problem_have_weights": (C.c_int, [_H, C.c_int]),
+    # the networks and carried hidden states of the GRU family; its fit needs no batch
+    "ctk_gru_batch_weight_count": (C.c_size_t, [_H]),
+    "ctk_gru_batch_set_weights": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
+    "ctk_gru_problem_set_weights": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ctk_gru_problem_have_weights": (C.c_int, [_H, C.c_int]),
+    "ctk_gru_problem_get_hidden": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
+    "ctk_gru_problem_set_hidden": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
+    "ctk_gru_batch_fit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
 })
 
 # closed-loop episodes of the MPPI batches on the device (include/ctk_hip_run.h, which ctk_hip.h includes): the same table for the entry
@@ -203,6 +211,9 @@ EPISODE_SYMBOLS = {f"{family}_{name}": sig for family in ("ctk_batch", "ctk_mlp_
 # above under these families' names, with the same signatures; a fourth table, bound with the other three
 LOOP_SYMBOLS = {f"{family}_{name}": sig for family in ("ctk_cem_batch", "ctk_rpgd_batch")
                 for name, sig in list(_PLANT_RUN.items()) + list(_PLANT_EPISODE.items())}
+
+# ... and for the GRU batch (include/ctk_hip_gru.h, which ctk_hip.h includes): a fifth table, bound with the other four
+GRU_LOOP_SYMBOLS = {f"ctk_gru_batch_{name}": sig for name, sig in list(_PLANT_RUN.items()) + list(_PLANT_EPISODE.items())}
 
 
 # user environments (include/ctk_user_env.h): name -> path of the library that was compiled with that model (control_toolkit_amd/build_env.py:
@@ -247,7 +258,8 @@ def _bind_library(path: str):
         lib = C.CDLL(path)
     except OSError as e:
         raise CtkError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()) + list(LOOP_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()) + list(LOOP_SYMBOLS.items()) + \
+            list(GRU_LOOP_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctk_abi_version() != 6:
@@ -1094,7 +1106,7 @@ class CtkMppiBatch(_CtkBatch):
 
 # ---- closed-loop episodes of a batch on the device (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_*; ctk_hip_loop.h) ------------------
 class BatchClosedLoop:
-    """CtkMppiBatch.closed_loop / CtkMppiMlpBatch.closed_loop, and BatchClosedLoop(cem_batch) / BatchClosedLoop(rpgd_batch) for a
+    """CtkMppiBatch.closed_loop / CtkMppiMlpBatch.closed_loop / CtkMppiGruBatch.closed_loop, and BatchClosedLoop(cem_batch) / BatchClosedLoop(rpgd_batch) for a
     CtkCemBatch or CtkRpgdBatch (the constructor is their way in: those classes have no closed_loop attribute): the batch's closed loops
     run on the device (kernel ctk_batch_plant<ENV>, or the family's ctk_cem_batch_plant<ENV> / ctk_rpgd_batch_plant<ENV>, between the
     controller launches), and the plants they run against.  A view of the batch: it owns nothing.  Problem p's plant has, for every
@@ -1343,6 +1355,117 @@ class CtkMppiMlpBatch(CtkMppiBatch):
 
     def have_weights(self, problem: int) -> bool:
         return bool(self._lib.ctk_mlp_problem_have_weights(self._h, self._problem(problem)))
+
+
+# ---- batched MPPI with the GRU predictor (include/ctk_hip.h: ctk_gru_batch_* / ctk_gru_problem_*) --------------------------------------
+GRU_HIDDEN_SHAPE = (2, 32)                            # a problem's carried hidden state: h1[32], h2[32] (ctk_predictor_get_hidden's 64 floats)
+
+
+def gru_weight_count(num_states: int, num_control_inputs: int, hidden=(32, 32)) -> int:
+    """floats of one (S+C)-h1-h2-S GRU in the layout of ctk_set_predictor_weights: per layer W_i, W_h, b_i, b_h (gate rows r|z|n), then
+    W_o, b_o (ctk_gru_batch_weight_count)"""
+    i, s, (a, b) = int(num_states) + int(num_control_inputs), int(num_states), (int(hidden[0]), int(hidden[1]))
+    return (3 * a * i + 3 * a * a + 6 * a) + (3 * b * a + 3 * b * b + 6 * b) + (b * s + s)
+
+
+def gru_batch_fit(num_rollouts: int, mpc_horizon: int, period_interpolation_inducing_points: int = 1):
+    """what CtkMppiGruBatch decides from the sizes alone, without a device (ctk_gru_batch_fit): (fits, block records per problem, words
+    of one record, whether the launches take the wide {value, seq} tail, dynamic LDS bytes of a launch)"""
+    blocks, words, wide, lds = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+    rc = load_library().ctk_gru_batch_fit(int(num_rollouts), int(mpc_horizon), int(period_interpolation_inducing_points), C.byref(blocks),
+                                          C.byref(words), C.byref(wide), C.byref(lds))
+    if rc == 1:
+        raise ValueError("num_rollouts, mpc_horizon and period_interpolation_inducing_points must be >= 1")
+    return rc == 0, blocks.value, words.value, bool(wide.value), int(lds.value)
+
+
+class CtkMppiGruBatch(CtkMppiBatch):
+    """Owns one ctk_gru_batch: num_problems independent MPPI controllers of ONE configuration whose plant model is a recurrent network
+    (2 x 32 GRU + dense), stepped by one rollout launch and one hidden-state launch per step.  Problem p behaves bit for bit like
+    CtkEngine("mppi", "GRU", seed=seeds[p], predictor_hidden=...) given the same calls — set_predictor_weights, set_param, step, reset,
+    set_state, predictor_get_hidden / predictor_set_hidden among them — the carried hidden state after every step included: a stepped
+    problem's advances by (the state it was given, the u it published), an unlisted problem's does not move.  The methods are
+    CtkMppiMlpBatch's, plus get_hidden / set_hidden.  predictor_hidden = (h1, h2): the hidden widths of all the batch's networks (default
+    32 / 32, at most 32; narrower ones are embedded exactly).  CartPole only."""
+
+    _BATCH, _PROBLEM = "ctk_gru_batch", "ctk_gru_problem"
+
+    def __init__(self, num_problems: int, *, seeds=None, predictor_hidden=None, environment: str = "CartPole", optimizer: str = "mppi",
+                 predictor: str = "GRU", num_rollouts: int, mpc_horizon: int, dt: float, action_low: float = -1.0, action_high: float = 1.0,
+                 period_interpolation_inducing_points: int = 1, seed: int = 0, device: int = 0, intermediate_steps: int = 1,
+                 materialize_trajectories: bool = False, global_rollout_offset: int = 0, num_states: int = None,
+                 num_control_inputs: int = None, generic_kernels: bool = False, **kw):
+        B = self._count(num_problems)
+        if optimizer != "mppi":
+            raise NotImplementedError(f"a batch steps MPPI controllers only (optimizer {optimizer!r}); the other optimizers run as CtkEngine")
+        if predictor != "GRU":
+            raise NotImplementedError(f"this batch rolls out the GRU predictor only (predictor {predictor!r}): the analytic one is CtkMppiBatch, "
+                                      "the MLP is CtkMppiMlpBatch")
+        if environment != "CartPole" or generic_kernels:
+            raise NotImplementedError(f"the GRU batch kernel is CartPole's matrix-core kernel (environment {environment!r}, generic_kernels "
+                                      f"{bool(generic_kernels)}); the template network kernels run as CtkEngine")
+        hidden = (32, 32) if predictor_hidden is None else tuple(int(x) for x in np.asarray(predictor_hidden).reshape(-1))
+        if len(hidden) != 2 or min(hidden) < 1:
+            raise ValueError(f"predictor_hidden must be two widths >= 1 (h1, h2), got {predictor_hidden!r}")
+        if max(hidden) > 32:
+            raise NotImplementedError(f"the GRU batch kernel holds 32 units per hidden layer (predictor_hidden {hidden}); no GRU kernel is built "
+                                      "for wider networks")
+        self.predictor_hidden = hidden
+        if predictor_hidden is not None:
+            kw = dict(kw, predictor_hidden1=hidden[0], predictor_hidden2=hidden[1])
+        self._open(B, self._seeds(B, seeds), "mppi", "GRU", environment, num_rollouts=num_rollouts, mpc_horizon=mpc_horizon, dt=dt,
+                   action_low=action_low, action_high=action_high,
+                   period_interpolation_inducing_points=period_interpolation_inducing_points, seed=seed, device=device,
+                   intermediate_steps=intermediate_steps, materialize_trajectories=materialize_trajectories,
+                   global_rollout_offset=global_rollout_offset, num_states=num_states, num_control_inputs=num_control_inputs,
+                   generic_kernels=generic_kernels, **kw)
+        self._per = int(self._b.samples_needed(self._h))
+        self._wn = gru_weight_count(self.S, self.C, hidden)
+
+    def weight_count(self) -> int:
+        """floats of one problem's network (predictor_hidden's widths)"""
+        return int(self._lib.ctk_gru_batch_weight_count(self._h))
+
+    def set_weights(self, w):
+        """one network [weight_count()] for every problem; every problem's hidden state becomes zero"""
+        w = _f32(w).ravel()
+        if w.size != self._wn:
+            raise ValueError(f"a GRU of hidden widths {self.predictor_hidden} has {self._wn} weights, got {w.size}")
+        self._check(self._lib.ctk_gru_batch_set_weights(self._h, _ptr(w), w.size))
+
+    def set_problem_weights(self, W, ids=None):
+        """W [n, weight_count()]: one network per problem in ids (None: all problems), in the order of ids.  The listed problems' hidden
+        states become zero; no other problem's weights or hidden state is touched"""
+        idv = batch_ids(self.B, ids)
+        n = self.B if idv is None else int(idv.size)
+        W = _f32(W)
+        if W.shape != (n, self._wn) and not (n == 1 and W.shape == (self._wn,)):
+            raise ValueError(f"weights must have shape ({n}, {self._wn}): one network per listed problem, got {tuple(W.shape)}")
+        self._check(self._lib.ctk_gru_problem_set_weights(self._h, n, _ptr(idv), _ptr(W), self._wn))
+
+    def have_weights(self, problem: int) -> bool:
+        return bool(self._lib.ctk_gru_problem_have_weights(self._h, self._problem(problem)))
+
+    def get_hidden(self, ids=None) -> np.ndarray:
+        """[n, 2, 32]: the carried hidden state (h1, h2) of every problem in ids (None: all), in the order of ids"""
+        idv = batch_ids(self.B, ids)
+        n = self.B if idv is None else int(idv.size)
+        out = np.empty((n,) + GRU_HIDDEN_SHAPE, np.float32)
+        self._check(self._lib.ctk_gru_problem_get_hidden(self._h, n, _ptr(idv), _ptr(out)))
+        return out
+
+    def set_hidden(self, H=None, ids=None):
+        """the hidden state of every problem in ids (None: all): H [n, 2, 32] (one [2, 32] broadcasts), or None for zeros"""
+        idv = batch_ids(self.B, ids)
+        n = self.B if idv is None else int(idv.size)
+        if H is not None:
+            H = _f32(H)
+            if H.shape == GRU_HIDDEN_SHAPE or H.shape == (64,):
+                H = np.broadcast_to(H.reshape(GRU_HIDDEN_SHAPE), (n,) + GRU_HIDDEN_SHAPE)
+            if H.size != n * 64:
+                raise ValueError(f"hidden states must have shape ({n}, 2, 32): one per listed problem, got {tuple(H.shape)}")
+            H = np.ascontiguousarray(H, np.float32)
+        self._check(self._lib.ctk_gru_problem_set_hidden(self._h, n, _ptr(idv), _ptr(H)))
 
 
 # ---- batched CEM (include/ctk_hip.h: ctk_cem_batch_*) ---------------------------------------------------------------------------------

@@ -335,6 +335,71 @@ void embed_mlp_rows(const float* w, int S, int I, int h1, int h2, int W, float* 
     rows(S, h2, S, W); rows(1, S, 1, S);           // W3, b3
 }
 
+// ... and a GRU's: I-h1-h2-S (h1, h2 <= 32) into the zero-initialised raw layout of the I-32-32-S one the kernels hold.  Per layer W_i, W_h, b_i,
+// b_h with the gate rows r|z|n, then W_o, b_o (ctk_set_predictor_weights_shaped; the GRU batch's weight calls)
+void embed_gru_rows(const float* w, int S, int I, int h1, int h2, float* full) {
+    const float* p = w;
+    float* q = full;
+    auto rows = [&](int r_src, int c_src, int r_dst, int c_dst) {      // a [r_src, c_src] matrix into the top-left of a [r_dst, c_dst] one
+        for (int r = 0; r < r_src; ++r) std::memcpy(q + (size_t)r * c_dst, p + (size_t)r * c_src, (size_t)c_src * sizeof(float));
+        p += (size_t)r_src * c_src; q += (size_t)r_dst * c_dst;
+    };
+    auto gates = [&](int hs, int c_src, int c_dst) {               // [3 hs, c_src] (rows r|z|n) -> [96, c_dst]
+        for (int gte = 0; gte < 3; ++gte) {
+            for (int r = 0; r < hs; ++r) std::memcpy(q + ((size_t)gte * 32 + r) * c_dst, p + ((size_t)gte * hs + r) * c_src, (size_t)c_src * sizeof(float));
+        }
+        p += (size_t)3 * hs * c_src; q += (size_t)96 * c_dst;
+    };
+    gates(h1, I, I); gates(h1, h1, 32); gates(h1, 1, 1); gates(h1, 1, 1);          // layer 1: W_i, W_h, b_i, b_h
+    gates(h2, h1, 32); gates(h2, h2, 32); gates(h2, 1, 1); gates(h2, 1, 1);        // layer 2
+    rows(S, h2, S, 32); rows(1, S, 1, S);                                           // W_o, b_o
+}
+
+// max_g (sum_j |W_o[g,j]| + |b_o[g]|) of CartPole's GRU in its raw layout: no predicted state component exceeds it while |h2| <= 1 (a convex
+// mix of tanh values and the previous state, which starts at 0 or at what the caller set)
+float gru_out_bound(const float* w) {
+    const float* Wo = w + GRU_NW_RAW - 4 * 32 - 4; const float* bo = Wo + 4 * 32;
+    float bound = 0.0f;
+    for (int g = 0; g < 4; ++g) { float r = std::fabs(bo[g]); for (int j = 0; j < 32; ++j) r += std::fabs(Wo[g * 32 + j]); bound = std::max(bound, r); }
+    return bound;
+}
+
+// Per-lane MFMA operands of the GRU weights for the four waves of a workgroup (ctk_gru.h header comment and
+// struct GruW): out[wave][lane][72].  Wave (m, q) = wave index 2m + q owns hidden-unit tile m; its A rows are the
+// r (q = 0) or z (q = 1) rows, its B rows the n rows (input products for q = 0, recurrent products for q = 1).
+// raw: per layer W_i[96,I] W_h[96,32] b_i[96] b_h[96] (rows r|z|n), then W_o[4,32] b_o[4].
+std::vector<float> permute_gru_weights(const float* raw) {
+    std::vector<float> out((size_t)GRU_TABLE_FLOATS, 0.0f);
+    for (int wv = 0; wv < 4; ++wv)
+        for (int l = 0; l < 64; ++l) {
+            const int m = wv >> 1, q = wv & 1, i = l & 15, g = l >> 4;
+            float* e = out.data() + (size_t)(wv * 64 + l) * GRU_W_PER_LANE;
+            const float* p = raw;
+            for (int L = 0; L < 2; ++L) {
+                const int I = L == 0 ? CTK_MLP_IN : 32, KS = L == 0 ? 2 : 8, base = L == 0 ? 0 : 18;
+                const float* Wi = p;              const float* Wh = Wi + 96 * I;
+                const float* bi = Wh + 96 * 32;   const float* bh = bi + 96;
+                p = bh + 96;
+                const int rowA = 32 * q + 16 * m + i, rowN = 64 + 16 * m + i;
+                auto kk = [&](int ks) { return L == 0 ? 4 * ks + g : mlp_hid(ks, g); };
+                auto wi = [&](int row, int ks) { return (L == 0 && kk(ks) >= CTK_MLP_IN) ? 0.0f : Wi[row * I + kk(ks)]; };
+                for (int ks = 0; ks < KS; ++ks) e[base + ks] = wi(rowA, ks);
+                for (int j = 0; j < 8; ++j) e[base + KS + j] = Wh[rowA * 32 + mlp_hid(j, g)];
+                if (q == 0) for (int ks = 0; ks < KS; ++ks) e[base + KS + 8 + ks] = wi(rowN, ks);
+                else for (int j = 0; j < 8; ++j) e[base + KS + 8 + j] = Wh[rowN * 32 + mlp_hid(j, g)];
+                for (int r = 0; r < 4; ++r) {
+                    const int unit = 16 * m + 4 * g + r;
+                    e[50 + 8 * L + r] = bi[32 * q + unit] + bh[32 * q + unit];   // r or z: both biases feed one accumulator
+                    e[54 + 8 * L + r] = q == 0 ? bi[64 + unit] : bh[64 + unit];  // n: input part / recurrent part (scaled by r)
+                }
+            }
+            const float* Wo = p; const float* bo = Wo + 4 * 32;
+            for (int j = 0; j < 8; ++j) e[42 + j] = (i % 4 == 0) ? Wo[(i / 4) * 32 + mlp_hid(j, g)] : 0.0f;
+            for (int r = 0; r < 4; ++r) e[66 + r] = r == 0 ? bo[g] : 0.0f;
+        }
+    return out;
+}
+
 // what ctk_create and ctk_batch_create check alike, with the caller's name in the message: the struct, the environment and its
 // dimensions, the sizes, the limits (creation failures go to ctk_last_error(NULL))
 int check_config(const char* who, const ctk_config* cfg, const EnvInfo** einfo_out) {
@@ -415,42 +480,6 @@ std::vector<float> permute_mlp_weights_wide(const float* raw, int S, int C) {
         const int inp = (i % 4 < 3 && io_of_row(i) < I) ? io_of_row(i) : -1;                                           // rows: network inputs
         for (int j = 0; j < KH; ++j) b[o++] = inp >= 0 ? W1[mlp_hid(j, g) * I + inp] : 0.0f;
     }
-    return out;
-}
-
-// Per-lane MFMA operands of the GRU weights for the four waves of a workgroup (ctk_gru.h header comment and
-// struct GruW): out[wave][lane][72].  Wave (m, q) = wave index 2m + q owns hidden-unit tile m; its A rows are the
-// r (q = 0) or z (q = 1) rows, its B rows the n rows (input products for q = 0, recurrent products for q = 1).
-// raw: per layer W_i[96,I] W_h[96,32] b_i[96] b_h[96] (rows r|z|n), then W_o[4,32] b_o[4].
-std::vector<float> permute_gru_weights(const float* raw) {
-    std::vector<float> out((size_t)GRU_TABLE_FLOATS, 0.0f);
-    for (int wv = 0; wv < 4; ++wv)
-        for (int l = 0; l < 64; ++l) {
-            const int m = wv >> 1, q = wv & 1, i = l & 15, g = l >> 4;
-            float* e = out.data() + (size_t)(wv * 64 + l) * GRU_W_PER_LANE;
-            const float* p = raw;
-            for (int L = 0; L < 2; ++L) {
-                const int I = L == 0 ? CTK_MLP_IN : 32, KS = L == 0 ? 2 : 8, base = L == 0 ? 0 : 18;
-                const float* Wi = p;              const float* Wh = Wi + 96 * I;
-                const float* bi = Wh + 96 * 32;   const float* bh = bi + 96;
-                p = bh + 96;
-                const int rowA = 32 * q + 16 * m + i, rowN = 64 + 16 * m + i;
-                auto kk = [&](int ks) { return L == 0 ? 4 * ks + g : mlp_hid(ks, g); };
-                auto wi = [&](int row, int ks) { return (L == 0 && kk(ks) >= CTK_MLP_IN) ? 0.0f : Wi[row * I + kk(ks)]; };
-                for (int ks = 0; ks < KS; ++ks) e[base + ks] = wi(rowA, ks);
-                for (int j = 0; j < 8; ++j) e[base + KS + j] = Wh[rowA * 32 + mlp_hid(j, g)];
-                if (q == 0) for (int ks = 0; ks < KS; ++ks) e[base + KS + 8 + ks] = wi(rowN, ks);
-                else for (int j = 0; j < 8; ++j) e[base + KS + 8 + j] = Wh[rowN * 32 + mlp_hid(j, g)];
-                for (int r = 0; r < 4; ++r) {
-                    const int unit = 16 * m + 4 * g + r;
-                    e[50 + 8 * L + r] = bi[32 * q + unit] + bh[32 * q + unit];   // r or z: both biases feed one accumulator
-                    e[54 + 8 * L + r] = q == 0 ? bi[64 + unit] : bh[64 + unit];  // n: input part / recurrent part (scaled by r)
-                }
-            }
-            const float* Wo = p; const float* bo = Wo + 4 * 32;
-            for (int j = 0; j < 8; ++j) e[42 + j] = (i % 4 == 0) ? Wo[(i / 4) * 32 + mlp_hid(j, g)] : 0.0f;
-            for (int r = 0; r < 4; ++r) e[66 + r] = r == 0 ? bo[g] : 0.0f;
-        }
     return out;
 }
 
@@ -1632,12 +1661,7 @@ int ctk_set_predictor_weights(ctk_handle* h, const float* w, size_t n) {
     const std::vector<float> perm = h->net == NET_MLP64 ? permute_mlp_weights_wide(w, h->S, h->C)
                                   : !gru ? permute_mlp_weights(w, h->S, h->C)
                                   : h->generic ? permute_gru_weights_g(w, h->S, h->C) : permute_gru_weights(w);
-    if (gru && !h->generic) {   // |h2| <= 1 (convex mix of tanh values and the previous state, which starts at 0 or at what the caller set)
-        const float* Wo = w + GRU_NW_RAW - 4 * 32 - 4; const float* bo = Wo + 4 * 32;
-        float bound = 0.0f;
-        for (int g = 0; g < 4; ++g) { float r = std::fabs(bo[g]); for (int j = 0; j < 32; ++j) r += std::fabs(Wo[g * 32 + j]); bound = std::max(bound, r); }
-        h->net_out_bound = bound;
-    }
+    if (gru && !h->generic) h->net_out_bound = gru_out_bound(w);
     HIP_TRY(h, hipMemcpyAsync(h->d_wperm, perm.data(), perm.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->have_weights = true;
@@ -1666,25 +1690,8 @@ int ctk_set_predictor_weights_shaped(ctk_handle* h, const float* w, size_t n, in
                     std::to_string(shaped_weight_count(h->cfg.predictor, h->S, h->C, h1, h2)) + " floats for " + std::to_string(I) + "IN-" +
                     std::to_string(h1) + "H1-" + std::to_string(h2) + "H2-" + std::to_string(S) + "OUT, got " + std::to_string(n));
     std::vector<float> full(weight_count(h->cfg.predictor, h->S, h->C, W), 0.0f);
-    const float* p = w;
-    float* q = full.data();
-    auto rows = [&](int r_src, int c_src, int r_dst, int c_dst) {      // a [r_src, c_src] matrix into the top-left of a [r_dst, c_dst] one
-        for (int r = 0; r < r_src; ++r) std::memcpy(q + (size_t)r * c_dst, p + (size_t)r * c_src, (size_t)c_src * sizeof(float));
-        p += (size_t)r_src * c_src; q += (size_t)r_dst * c_dst;
-    };
-    if (h->cfg.predictor == CTK_PRED_MLP) {
-        embed_mlp_rows(w, S, I, h1, h2, W, full.data());
-    } else {
-        auto gates = [&](int hs, int c_src, int c_dst) {               // [3 hs, c_src] (rows r|z|n) -> [96, c_dst]
-            for (int gte = 0; gte < 3; ++gte) {
-                for (int r = 0; r < hs; ++r) std::memcpy(q + ((size_t)gte * 32 + r) * c_dst, p + ((size_t)gte * hs + r) * c_src, (size_t)c_src * sizeof(float));
-            }
-            p += (size_t)3 * hs * c_src; q += (size_t)96 * c_dst;
-        };
-        gates(h1, I, I); gates(h1, h1, 32); gates(h1, 1, 1); gates(h1, 1, 1);          // layer 1: W_i, W_h, b_i, b_h
-        gates(h2, h1, 32); gates(h2, h2, 32); gates(h2, 1, 1); gates(h2, 1, 1);        // layer 2
-        rows(S, h2, S, 32); rows(1, S, 1, S);                                           // W_o, b_o
-    }
+    if (h->cfg.predictor == CTK_PRED_MLP) embed_mlp_rows(w, S, I, h1, h2, W, full.data());
+    else embed_gru_rows(w, S, I, h1, h2, full.data());
     return ctk_set_predictor_weights(h, full.data(), full.size());
 }
 

@@ -1,8 +1,8 @@
 // ctk_batch.hip — the batch families of the C ABI (include/ctk_hip.h, ctk_hip_run.h, ctk_hip_episode.h, ctk_hip_loop.h): ctk_batch_*, ctk_mlp_batch_*,
-// ctk_cem_batch_*, ctk_rpgd_batch_*.  The single handle is in ctk_api.hip; what the two files share is declared in ctk_host.h.
+// ctk_gru_batch_*, ctk_cem_batch_*, ctk_rpgd_batch_*.  The single handle is in ctk_api.hip; what the two files share is declared in ctk_host.h.
 // The file in order: the host core (BatchCore and the bodies every family shares), the two drivers — batch_step<F> for a step,
 // batch_closed_loop<F> for runs and episodes — and the two macros that write a family's C entries over them (CTK_BATCH_ENTRIES,
-// CTK_LOOP_ENTRIES); then each family: its struct, its trait F (MppiFamily, MlpFamily, CemFamily, RpgdFamily: what the drivers ask of
+// CTK_LOOP_ENTRIES); then each family: its struct, its trait F (MppiFamily, MlpFamily, GruFamily, CemFamily, RpgdFamily: what the drivers ask of
 // it), and the entries that are its own (create, samples_needed, step, reset, read).  A message names the entry that was called: every
 // entry passes its exported name (`who`) to the body that builds the text, the MLP family included — it runs the MPPI family's code
 // under its own names.
@@ -14,6 +14,7 @@
 
 #include "ctk_launch.h"
 #include "ctk_host.h"
+#include "ctk_device.h"   // CTK_SINCOS_FAST_LIMIT
 
 using namespace ctk_host;
 
@@ -830,7 +831,7 @@ int plant_noise_set_position(BatchCore* b, const char* who, int problem, uint32_
     return CTK_OK;
 }
 
-// The thirteen entries of a family that are one line over a shared body, FAM in {ctk_batch, ctk_mlp_batch, ctk_cem_batch, ctk_rpgd_batch}
+// The thirteen entries of a family that are one line over a shared body, FAM in {ctk_batch, ctk_mlp_batch, ctk_gru_batch, ctk_cem_batch, ctk_rpgd_batch}
 // with the prefix PROB of its per-problem parameter entries and its trait: the bodies above under the family's names
 #define CTK_BATCH_ENTRIES(FAM, PROB, TRAIT)                                                                                                           \
     const char* FAM##_last_error(const FAM* b) { return b ? b->err.c_str() : g_create_error.c_str(); }                                                \
@@ -929,6 +930,15 @@ struct ctk_batch : BatchCore {
     float* d_w = nullptr;                   // [B][wtab] problem p's table, in the layout of a handle's d_wperm
     float* h_w = nullptr;                   // pinned [B][wtab]: the staging of ONE transfer per weight call
     std::vector<unsigned char> have_w;      // [B] the problem has received weights
+    // the GRU family (include/ctk_hip.h: ctk_gru_batch_*): pred == CTK_PRED_GRU, ctk_mppi_batch_gru<LOG, FORM> / ctk_mppi_batch_gru_pp<LOG, FORM>.
+    // Problem p's block of d_w (wtab floats) is [table (wrow) | carried hidden state (64) | fast-cosine word | pad]: the kernels write
+    // the hidden state, so the block has NO host mirror — h_w stages tables alone ([B][wrow]), and every transfer names its part
+    int form = 0;                           // CTK_MPPI_FORM_* of every launch: what a handle of this configuration launches (ctk_mppi_batch_gru_fit)
+    size_t wrow = 0;                        // floats of the table part of a block (ctk_mppi_batch_gru_table_floats)
+    float* h_hid = nullptr;                 // pinned [B][64]: the staging of a hidden-state call (rows by problem id)
+    uint32_t* h_flag = nullptr;             // pinned [B]: net_out_bound * hidden_scale <= CTK_SINCOS_FAST_LIMIT, the word of every block
+    std::vector<float> net_out_bound;       // [B] what a handle keeps under these names (ctk_api.hip): INFINITY until weights arrive,
+    std::vector<float> hidden_scale;        // [B] 1, or max(1, max |h|) of a caller-set hidden state
     size_t unom_stride() const { return (size_t)2 * HC; }
     float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
 };
@@ -972,7 +982,10 @@ hipError_t batch_launch_records(ctk_batch* b, const RolloutArgs& a, const CtkBat
     *launched = 0;
     while (le == hipSuccess && *launched < n) {
         const int cnt = std::min(b->max_per_launch, n - *launched);
-        if (b->pred == CTK_PRED_MLP)
+        if (b->pred == CTK_PRED_GRU)
+            le = ctk_launch_mppi_batch_gru(b->stream, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
+                                           b->form, b->d_w, b->differ ? b->d_k : nullptr);
+        else if (b->pred == CTK_PRED_MLP)
             le = ctk_launch_mppi_batch_mlp(b->stream, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
                                            b->d_w, b->differ ? b->d_k : nullptr);
         else
@@ -1034,29 +1047,30 @@ struct MppiFamily {
     // the state of a problem: its current plan, its last output
     static BatchState state(Batch* b, int p) { return {{state_seg(b->unom(p, b->cur[(size_t)p]), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C)}}; }
     static const char* per_problem_kernel(const Batch* b) {
-        return b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
+        return b->pred == CTK_PRED_GRU ? ctk_mppi_batch_gru_name(b->cfg.materialize_trajectories != 0, b->form, true)
+             : b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
                                        : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
     }
 };
 
-// ctk_batch_create (pred == CTK_PRED_ODE) and ctk_mlp_batch_create (CTK_PRED_MLP) into the caller's fresh struct: the refusals that need
+// ctk_batch_create (pred == CTK_PRED_ODE), ctk_mlp_batch_create (CTK_PRED_MLP) and ctk_gru_batch_create (CTK_PRED_GRU) into the caller's fresh struct: the refusals that need
 // only the configuration, the device probe, the buffers.  On failure the message is in g_create_error and the caller deletes the struct.
 int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* cfg, int n_problems, const uint64_t* seeds) {
-    const bool mlp = pred == CTK_PRED_MLP;
+    const bool mlp = pred == CTK_PRED_MLP, gru = pred == CTK_PRED_GRU;
     auto refuse = [&](int code, const std::string& msg) { return bfail(nullptr, code, std::string(who) + ": " + msg); };
     if (n_problems < 1) return refuse(CTK_ERR_UNSUPPORTED, "a batch holds at least one problem (n_problems == " + std::to_string(n_problems) + ")");
     const EnvInfo* einfo = nullptr;
     if (int rc = check_config(who, cfg, &einfo)) return rc;
     const int N = cfg->num_rollouts, H = cfg->mpc_horizon, P = num_inducing_points(H, cfg->period_interpolation_inducing_points);
     const int hw1 = cfg->predictor_hidden1 ? cfg->predictor_hidden1 : 32, hw2 = cfg->predictor_hidden2 ? cfg->predictor_hidden2 : 32;
-    // the MLP family's refusals name the sizes refused: population, horizon, inducing points and the network as the reference names it
-    const std::string sizes = !mlp ? std::string()
+    // the network families' refusals name the sizes refused: population, horizon, inducing points and the network as the reference names it
+    const std::string sizes = !(mlp || gru) ? std::string()
         : " (num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ", " + std::to_string(P) + " inducing points, network " +
           std::to_string(einfo->S + einfo->C) + "IN-" + std::to_string(hw1) + "H1-" + std::to_string(hw2) + "H2-" + std::to_string(einfo->S) + "OUT)";
     if (cfg->optimizer != CTK_OPT_MPPI)
         return refuse(CTK_ERR_UNSUPPORTED, "a batch steps MPPI controllers only (cfg.optimizer == " + std::to_string(cfg->optimizer) +
                       "); the other optimizers run as single handles (ctk_create)" + sizes);
-    if (!mlp && cfg->predictor != CTK_PRED_ODE)
+    if (!mlp && !gru && cfg->predictor != CTK_PRED_ODE)
         return refuse(CTK_ERR_UNSUPPORTED, "the batch kernel rolls out the analytic (ODE) predictor only (cfg.predictor == " +
                       std::to_string(cfg->predictor) + "); network predictors run as single handles (ctk_create)");
     if (mlp) {                                         // this family's own refusals, under its name; the first one names ctk_batch_create
@@ -1074,15 +1088,34 @@ int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* c
             return bfail(nullptr, CTK_ERR_UNSUPPORTED, "ctk_mlp_batch_create: the batch kernel holds 32 units per hidden layer (narrower layers are embedded exactly); wider "
                          "networks run the 64-unit template kernels, which have no batch form (ctk_create)" + sizes);
     }
+    if (gru) {                                         // the GRU family's refusals: every one CTK_ERR_UNSUPPORTED, each other predictor's names its family
+        if (cfg->predictor == CTK_PRED_ODE)
+            return refuse(CTK_ERR_UNSUPPORTED, "this family rolls out the GRU predictor (cfg.predictor == " + std::to_string(cfg->predictor) +
+                          " is the analytic one: use ctk_batch_create)" + sizes);
+        if (cfg->predictor == CTK_PRED_MLP)
+            return refuse(CTK_ERR_UNSUPPORTED, "this family rolls out the GRU predictor (cfg.predictor == " + std::to_string(cfg->predictor) +
+                          " is the MLP: use ctk_mlp_batch_create)" + sizes);
+        if (cfg->predictor != CTK_PRED_GRU)
+            return refuse(CTK_ERR_UNSUPPORTED, "this family rolls out the GRU predictor only (cfg.predictor == " + std::to_string(cfg->predictor) + ")" + sizes);
+        if (cfg->environment != CTK_ENV_CARTPOLE || cfg->generic_kernels != 0)
+            return refuse(CTK_ERR_UNSUPPORTED, std::string("the batch kernel is CartPole's four-wave matrix-core GRU kernel (environment ") + einfo->name +
+                          ", generic_kernels == " + std::to_string(cfg->generic_kernels) + "): such handles run the template network kernels, which have no batch form (ctk_create)" + sizes);
+        if (hw1 < 1 || hw2 < 1 || std::max(hw1, hw2) > 32)
+            return refuse(CTK_ERR_UNSUPPORTED, "the batch kernel holds 1 to 32 units per hidden layer (narrower layers are embedded exactly); no GRU kernel is "
+                          "built for other widths" + sizes);
+    }
     if (!(cfg->LBD > 0.0f && cfg->NU != 0.0f)) return refuse(CTK_ERR_INVALID_ARGUMENT, "MPPI needs LBD > 0 and NU != 0");
     size_t lds = 0;
-    int blocks = 0;
-    if (const int why = mlp ? ctk_mppi_batch_mlp_fit(N, H, P, &lds, &blocks) : ctk_mppi_batch_fit(cfg->environment, N, H, P, &lds, &blocks)) {
+    int blocks = 0, form = 0;
+    if (const int why = gru ? ctk_mppi_batch_gru_fit(N, H, P, &lds, &blocks, &form)
+                      : mlp ? ctk_mppi_batch_mlp_fit(N, H, P, &lds, &blocks) : ctk_mppi_batch_fit(cfg->environment, N, H, P, &lds, &blocks)) {
         const std::string sizes = "num_rollouts " + std::to_string(N) + ", mpc_horizon " + std::to_string(H) + ", " + std::to_string(P) + " inducing points x " +
                                   std::to_string(einfo->C) + " inputs = " + std::to_string(blocks) + " block records of " + std::to_string(2 + P * einfo->C) + " words";
         const char* reason = why == 1 ? (mlp ? ": a handle of this size does not run the pair form of the MLP kernel (more than 8192 rollouts, or CTK_MPPI_NO_PAIR is set), the only one a batch has"
                                              : ": populations from 32768 rollouts on run the throughput kernels, which a batch does not have")
-                           : why == 2 ? ": the batch kernel has the narrow in-launch hand-off only (at most 128 records and 2048 record words per problem)"
+                           : why == 2 ? (gru ? ": a handle of this size does not hand its block records over in-launch (more than 128 records that hold more than 4096 words, or more "
+                                               "than 512 records) but runs rollout, merge and update as separate launches, a path the batch does not have"
+                                             : ": the batch kernel has the narrow in-launch hand-off only (at most 128 records and 2048 record words per problem)")
                            : why == 3 ? ": the block records do not fit the hand-off's LDS staging"
                                       : ": the rollout tiles need more than 160 KiB of LDS";
         return refuse(CTK_ERR_UNSUPPORTED, "per-problem population outside the batch kernel's sizes (" + sizes + ")" + reason +
@@ -1093,7 +1126,7 @@ int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* c
     if (int rc = probe_device(who, cfg->device, &prop)) return rc;
 
     batch_core_init(b, cfg, einfo, n_problems, seeds);        // dirty: no constants in d_k yet, the first step of the per-problem form derives them all
-    b->pred = pred; b->hid1 = hw1; b->hid2 = hw2;
+    b->pred = pred; b->hid1 = hw1; b->hid2 = hw2; b->form = form;
     b->P = P; b->PC = P * b->C; b->blocks = blocks;
     b->mk = mppi_constants(b->cfg);
     // Progress: the only workgroup of a launch that ever waits is block 0 of a problem, for workgroups of its own problem.  With at most
@@ -1102,8 +1135,13 @@ int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* c
     b->max_per_launch = std::max(1, prop.multiProcessorCount / 2);
     batch_env_lowers("CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH", &b->max_per_launch);
     b->cur.assign((size_t)n_problems, 0);
-    b->dominant = mlp ? ctk_mppi_batch_mlp_name(cfg->materialize_trajectories != 0) : ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
-    if (mlp) { b->wtab = ctk_mppi_batch_mlp_table_floats(); b->have_w.assign((size_t)n_problems, 0); }
+    b->dominant = gru ? ctk_mppi_batch_gru_name(cfg->materialize_trajectories != 0, form)
+                : mlp ? ctk_mppi_batch_mlp_name(cfg->materialize_trajectories != 0) : ctk_mppi_batch_name(b->env, cfg->materialize_trajectories != 0);
+    if (mlp) { b->wtab = b->wrow = ctk_mppi_batch_mlp_table_floats(); b->have_w.assign((size_t)n_problems, 0); }
+    if (gru) {
+        b->wtab = ctk_mppi_batch_gru_block_floats(); b->wrow = ctk_mppi_batch_gru_table_floats(); b->have_w.assign((size_t)n_problems, 0);
+        b->net_out_bound.assign((size_t)n_problems, INFINITY); b->hidden_scale.assign((size_t)n_problems, 1.0f);
+    }
 
     if (int rc = batch_core_open(b)) return rc;
     const size_t Bz = (size_t)n_problems, rec = (size_t)blocks * (2 + b->PC);
@@ -1119,9 +1157,13 @@ int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* c
     HIP_CREATE(b->own.pinned_zero(&b->h_steps, Bz * sizeof(CtkBatchStep)));
     HIP_CREATE(b->own.dev_zero(&b->d_k, Bz * b->kstride, b->stream));
     HIP_CREATE(b->own.pinned_zero(&b->h_k, Bz * b->kstride));
-    if (mlp) {
+    if (mlp || gru) {
         HIP_CREATE(b->own.dev_zero(&b->d_w, Bz * b->wtab * sizeof(float), b->stream));
-        HIP_CREATE(b->own.pinned_zero(&b->h_w, Bz * b->wtab * sizeof(float)));
+        HIP_CREATE(b->own.pinned_zero(&b->h_w, Bz * b->wrow * sizeof(float)));
+    }
+    if (gru) {
+        HIP_CREATE(b->own.pinned_zero(&b->h_hid, Bz * ctk_mppi_batch_gru_hidden_floats() * sizeof(float)));
+        HIP_CREATE(b->own.pinned_zero(&b->h_flag, Bz * sizeof(uint32_t)));
     }
 
     const std::vector<InterpEntry> tab = build_interp_table(H, cfg->period_interpolation_inducing_points, P);
@@ -1146,7 +1188,7 @@ int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* c
     return CTK_OK;
 }
 
-// *_create of the family's two forms (FAM: ctk_batch, ctk_mlp_batch)
+// *_create of the family's three forms (FAM: ctk_batch, ctk_mlp_batch, ctk_gru_batch)
 template <class FAM>
 int mppi_batch_create(const char* who, int pred, const ctk_config* cfg, int n_problems, const uint64_t* seeds, FAM** out) {
     if (out) *out = nullptr;
@@ -1243,7 +1285,7 @@ struct MlpFamily : MppiFamily {
 
 extern "C" {
 
-// create, samples_needed, step, reset and read of the family's two forms, FAM in {ctk_batch, ctk_mlp_batch}
+// create, samples_needed, step, reset and read of the family's three forms, FAM in {ctk_batch, ctk_mlp_batch, ctk_gru_batch}
 #define CTK_MPPI_ENTRIES(FAM, TRAIT, PRED)                                                                                                            \
     int FAM##_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, FAM** out) {                                                       \
         return mppi_batch_create(#FAM "_create", PRED, cfg, n_problems, seeds, out);                                                                  \
@@ -1292,6 +1334,213 @@ int ctk_mlp_problem_set_weights(ctk_mlp_batch* b, int n_ids, const int32_t* ids,
 }
 
 int ctk_mlp_problem_have_weights(const ctk_mlp_batch* b, int problem) { return (b && problem >= 0 && problem < b->B && b->have_w[(size_t)problem]) ? 1 : 0; }
+
+}  // extern "C"
+
+// =============================================================================================
+// Batched MPPI with the GRU predictor (include/ctk_hip.h: ctk_gru_batch_* / ctk_gru_problem_*): the ctk_batch above with pred == CTK_PRED_GRU,
+// launched as ctk_mppi_batch_gru<LOG, FORM> / ctk_mppi_batch_gru_pp<LOG, FORM> in the form a handle of the configuration launches, plus
+// what a recurrent plant model adds.  Problem p's block of d_w is [per-lane table | carried hidden state | fast-cosine word | pad]
+// (ctk_launch.h).  The hidden state is advanced ON THE DEVICE behind every step (ctk_gru_advance_batch, one workgroup per step record,
+// issued once behind the step's rollout launches: GruFamily::launch), so the host has no copy of it and no transfer may span a block:
+// a weight call moves table parts, zeroes the hidden parts and rewrites the words of the LISTED problems only, by pitched copies, one per
+// run of consecutive ids.  The fast-cosine word is the half of a handle's per-step decision (ctk_api.hip: make_args, a.fast_cos_ok) that
+// does not depend on the state: net_out_bound * hidden_scale <= CTK_SINCOS_FAST_LIMIT, kept per problem as a handle keeps them; the
+// kernel joins it with |s[2]| of the step record, so the decision is also a handle's inside a run, whose states exist on the device only.
+// =============================================================================================
+struct ctk_gru_batch : ctk_batch {};
+
+namespace {
+
+size_t gru_batch_weight_count(const ctk_batch* b) { return shaped_weight_count(CTK_PRED_GRU, b->S, b->C, b->hid1, b->hid2); }
+float* gru_batch_hidden(const ctk_batch* b, int p) { return b->d_w + (size_t)p * b->wtab + b->wrow; }
+uint32_t gru_batch_flag(const ctk_batch* b, int p) {
+    return b->net_out_bound[(size_t)p] * b->hidden_scale[(size_t)p] <= CTK_SINCOS_FAST_LIMIT ? 1u : 0u;
+}
+
+// fn(first problem, count) for every run of consecutive problems among the n listed ones (ids ascending: batch_ids; NULL: all in one run)
+template <class Fn>
+hipError_t gru_batch_runs(int n, const int32_t* ids, Fn&& fn) {
+    for (int j = 0; j < n;) {
+        int e = j + 1;
+        while (ids && e < n && ids[e] == ids[e - 1] + 1) ++e;
+        if (!ids) e = n;
+        if (const hipError_t err = fn(ids ? ids[j] : 0, e - j)) return err;
+        j = e;
+    }
+    return hipSuccess;
+}
+
+// the hidden rows (h_hid, by problem id) and the fast-cosine words (from the host's bounds) of the listed problems into their blocks
+hipError_t gru_batch_send_hidden(ctk_batch* b, int n, const int32_t* ids) {
+    const size_t hid = ctk_mppi_batch_gru_hidden_floats() * sizeof(float), pitch = b->wtab * sizeof(float);
+    for (int j = 0; j < n; ++j) { const int p = ids ? ids[j] : j; b->h_flag[p] = gru_batch_flag(b, p); }
+    return gru_batch_runs(n, ids, [&](int p0, int cnt) {
+        hipError_t e = hipMemcpy2DAsync(gru_batch_hidden(b, p0), pitch, b->h_hid + (size_t)p0 * ctk_mppi_batch_gru_hidden_floats(), hid, hid, (size_t)cnt,
+                                        hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess)
+            e = hipMemcpy2DAsync(gru_batch_hidden(b, p0) + ctk_mppi_batch_gru_hidden_floats(), pitch, b->h_flag + p0, sizeof(uint32_t), sizeof(uint32_t),
+                                 (size_t)cnt, hipMemcpyHostToDevice, b->stream);
+        return e;
+    });
+}
+
+// networks of the n listed problems (ids == NULL: problems 0 .. n-1) from w [n][cnt] (each_own) or from the one network w [cnt], as
+// ctk_set_predictor_weights[_shaped] gives a handle one: the table, a zero hidden state, net_out_bound (hidden_scale stays).  Table parts,
+// hidden parts and words of the listed problems only: what lies between two runs of ids is not touched (the other problems' hidden states
+// live on the device alone)
+int gru_batch_put_weights(ctk_batch* b, int n, const int32_t* ids, const float* w, size_t cnt, bool each_own) {
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const size_t HF = ctk_mppi_batch_gru_hidden_floats();
+    std::vector<float> full(weight_count(CTK_PRED_GRU, b->S, b->C, 32));
+    std::vector<float> perm, bound((size_t)n);
+    const bool narrow = b->hid1 != 32 || b->hid2 != 32;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        if (j == 0 || each_own) {
+            const float* src = w + (each_own ? (size_t)j * cnt : 0);
+            if (narrow) {
+                std::fill(full.begin(), full.end(), 0.0f);
+                embed_gru_rows(src, b->S, b->S + b->C, b->hid1, b->hid2, full.data());
+                src = full.data();
+            }
+            perm = permute_gru_weights(src);
+            bound[(size_t)j] = gru_out_bound(src);
+        } else bound[(size_t)j] = bound[0];
+        std::memcpy(b->h_w + (size_t)p * b->wrow, perm.data(), b->wrow * sizeof(float));
+        std::memset(b->h_hid + (size_t)p * HF, 0, HF * sizeof(float));
+    }
+    const std::vector<float> before = b->net_out_bound;
+    for (int j = 0; j < n; ++j) b->net_out_bound[(size_t)(ids ? ids[j] : j)] = bound[(size_t)j];
+    const size_t row = b->wrow * sizeof(float), pitch = b->wtab * sizeof(float);
+    hipError_t e = gru_batch_runs(n, ids, [&](int p0, int c) {
+        return hipMemcpy2DAsync(b->d_w + (size_t)p0 * b->wtab, pitch, b->h_w + (size_t)p0 * b->wrow, row, row, (size_t)c, hipMemcpyHostToDevice, b->stream);
+    });
+    if (e == hipSuccess) e = gru_batch_send_hidden(b, n, ids);
+    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) { b->net_out_bound = before; return bfail(b, CTK_ERR_HIP, std::string("the GRU batch's weight transfer: ") + hipGetErrorString(e)); }
+    for (int j = 0; j < n; ++j) b->have_w[(size_t)(ids ? ids[j] : j)] = 1;
+    return CTK_OK;
+}
+
+int gru_batch_weight_args(ctk_batch* b, const char* who, const float* w, size_t n, const char* each) {
+    if (!w) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL weights" + each);
+    if (n != gru_batch_weight_count(b))
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": expected " + std::to_string(gru_batch_weight_count(b)) + " floats for the GRU-" +
+                     std::to_string(b->S + b->C) + "IN-" + std::to_string(b->hid1) + "H1-" + std::to_string(b->hid2) + "H2-" + std::to_string(b->S) +
+                     "OUT network (ctk_gru_batch_weight_count), got " + std::to_string(n));
+    return CTK_OK;
+}
+
+// the MPPI family under the GRU family's names: a problem without a network is not stepped (as the MLP family's), and the launches of a
+// step end with the advance of the stepped problems' hidden states
+struct GruFamily : MppiFamily {
+    using Batch = ctk_gru_batch;
+    static int refuse(ctk_batch* b, const char* who, int n, const int32_t* ids) {
+        std::string missing;
+        for (int j = 0; j < n; ++j) {
+            const int p = ids ? ids[j] : j;
+            if (!b->have_w[(size_t)p]) list_problem(missing, p);
+        }
+        if (!missing.empty())
+            return bfail(b, CTK_ERR_STATE, std::string(who) + ": no network weights for problem(s) " + missing +
+                         " (ctk_gru_batch_set_weights / ctk_gru_problem_set_weights before stepping); nothing was launched, no hidden state moved");
+        return CTK_OK;
+    }
+    // the rollout launches of the n records (split at max_per_launch), then ONE advance of the launched records' hidden states, each by
+    // (the state of its record, the u its rollout launch published): mppi_advance_hidden of a handle (ctk_api.hip).  In a closed loop the
+    // plant launch follows on the stream and writes the NEXT step's records, so the advance has read this step's state by then
+    static hipError_t launch(ctk_batch* b, const RolloutArgs& a, const Rec* d_rec, int n, const unsigned char*, int* launched) {
+        hipError_t le = batch_launch_records(b, a, d_rec, n, launched);
+        if (*launched > 0) {
+            const hipError_t ae = ctk_launch_gru_advance_batch(b->stream, b->d_desc, d_rec, *launched, b->d_w);
+            if (le == hipSuccess) le = ae;
+        }
+        return le;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// the MPPI family's entries under the GRU family's names; ctk_gru_batch_reset is ctk_reset of an MPPI handle, which leaves the hidden
+// state alone; the plant of the closed loop is the analytic CartPole with the problem's parameter table, as for the MLP batch
+CTK_MPPI_ENTRIES(ctk_gru_batch, GruFamily, CTK_PRED_GRU)
+CTK_BATCH_ENTRIES(ctk_gru_batch, ctk_gru_problem, GruFamily)
+CTK_LOOP_ENTRIES(ctk_gru_batch, GruFamily)
+
+int ctk_gru_batch_fit(int num_rollouts, int mpc_horizon, int period, int* blocks, int* record_words, int* wide_tail, size_t* lds_bytes) {
+    if (num_rollouts < 1 || mpc_horizon < 1 || period < 1) return CTK_ERR_INVALID_ARGUMENT;
+    const int P = num_inducing_points(mpc_horizon, period);
+    size_t lds = 0;
+    int nb = 0, form = 0;
+    const int why = ctk_mppi_batch_gru_fit(num_rollouts, mpc_horizon, P, &lds, &nb, &form);
+    if (blocks) *blocks = nb;
+    if (record_words) *record_words = 2 + P;
+    if (wide_tail) *wide_tail = (!why && (form & CTK_MPPI_FORM_WIDE_TAIL)) ? 1 : 0;
+    if (lds_bytes) *lds_bytes = lds;
+    return why ? CTK_ERR_UNSUPPORTED : CTK_OK;
+}
+
+size_t ctk_gru_batch_weight_count(const ctk_gru_batch* b) { return b ? gru_batch_weight_count(b) : 0; }
+
+int ctk_gru_batch_set_weights(ctk_gru_batch* b, const float* w, size_t n) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (int rc = gru_batch_weight_args(b, "ctk_gru_batch_set_weights", w, n, "")) return rc;
+    return gru_batch_put_weights(b, b->B, nullptr, w, n, false);
+}
+
+int ctk_gru_problem_set_weights(ctk_gru_batch* b, int n_ids, const int32_t* ids, const float* w, size_t n) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int cnt = 0;
+    if (int rc = batch_ids(b, "ctk_gru_problem_set_weights", n_ids, ids, &cnt)) return rc;
+    if (int rc = gru_batch_weight_args(b, "ctk_gru_problem_set_weights", w, n, " (one network per listed problem)")) return rc;
+    return gru_batch_put_weights(b, cnt, ids, w, n, true);
+}
+
+int ctk_gru_problem_have_weights(const ctk_gru_batch* b, int problem) { return (b && problem >= 0 && problem < b->B && b->have_w[(size_t)problem]) ? 1 : 0; }
+
+// ctk_predictor_get_hidden of every listed problem: dst [n][64], rows in the order of ids
+int ctk_gru_problem_get_hidden(ctk_gru_batch* b, int n_ids, const int32_t* ids, float* dst) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_gru_problem_get_hidden", n_ids, ids, &n)) return rc;
+    if (!dst) return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_gru_problem_get_hidden: NULL destination (64 floats per listed problem)");
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const size_t HF = ctk_mppi_batch_gru_hidden_floats(), hid = HF * sizeof(float);
+    BHIP_TRY(b, gru_batch_runs(n, ids, [&](int p0, int c) {
+        return hipMemcpy2DAsync(b->h_hid + (size_t)p0 * HF, hid, gru_batch_hidden(b, p0), b->wtab * sizeof(float), hid, (size_t)c, hipMemcpyDeviceToHost, b->stream);
+    }));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    for (int j = 0; j < n; ++j) std::memcpy(dst + (size_t)j * HF, b->h_hid + (size_t)(ids ? ids[j] : j) * HF, hid);
+    return CTK_OK;
+}
+
+// ctk_predictor_set_hidden of every listed problem: src [n][64], or NULL for zeros; hidden_scale as a handle's entry leaves it
+int ctk_gru_problem_set_hidden(ctk_gru_batch* b, int n_ids, const int32_t* ids, const float* src) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, "ctk_gru_problem_set_hidden", n_ids, ids, &n)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const size_t HF = ctk_mppi_batch_gru_hidden_floats();
+    const std::vector<float> before = b->hidden_scale;
+    for (int j = 0; j < n; ++j) {
+        const size_t p = (size_t)(ids ? ids[j] : j);
+        float* row = b->h_hid + p * HF;
+        b->hidden_scale[p] = 1.0f;
+        for (size_t i = 0; i < HF; ++i) {
+            row[i] = src ? src[(size_t)j * HF + i] : 0.0f;
+            b->hidden_scale[p] = std::max(b->hidden_scale[p], std::fabs(row[i]));
+        }
+    }
+    hipError_t e = gru_batch_send_hidden(b, n, ids);
+    const hipError_t se = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) { b->hidden_scale = before; return bfail(b, CTK_ERR_HIP, std::string("ctk_gru_problem_set_hidden: ") + hipGetErrorString(e)); }
+    return CTK_OK;
+}
 
 }  // extern "C"
 

@@ -29,7 +29,10 @@ constexpr int GRU_BLOCK = 256;
 constexpr int GRU_W_PER_LANE = 72;                         // 18 float4: see GruW
 constexpr int GRU_TABLE_FLOATS = 4 * 64 * GRU_W_PER_LANE;  // [wave][lane][72]
 constexpr int GRU_HIDDEN_FLOATS = 64;                      // carried state: h1[32] h2[32]
-constexpr int GRU_EX_FLOATS = (2 * 4 + 2 * 2) * 64 * 4;    // LDS exchange: per layer [4 waves][64] + [2 tiles][64] float4
+// a problem's block in the GRU batch (ctk_launch.h: ctk_launch_mppi_batch_gru): table | hidden | fast-cosine word | pad to 16 bytes
+constexpr int GRU_BATCH_WORD = GRU_TABLE_FLOATS + GRU_HIDDEN_FLOATS;
+constexpr int GRU_BATCH_BLOCK_FLOATS = GRU_BATCH_WORD + 4;
+constexpr int GRU_EX_FLOATS =(2 * 4 + 2 * 2) * 64 * 4;    // LDS exchange: per layer [4 waves][64] + [2 tiles][64] float4
 
 // per-lane operands of wave (m, q), in table order
 struct GruW {

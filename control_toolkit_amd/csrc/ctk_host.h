@@ -26,6 +26,11 @@ std::vector<float> permute_mlp_weights(const float* raw, int S = CTK_S, int C = 
 size_t weight_count(int predictor, int S, int C, int hid = 32);
 size_t shaped_weight_count(int predictor, int S, int C, int h1, int h2);
 void embed_mlp_rows(const float* w, int S, int I, int h1, int h2, int W, float* full);
+// CartPole's 2 x 32 GRU: a narrower network into the raw layout of the full one, the per-lane table of the full one
+// (ctk_launch.h: ctk_mppi_batch_gru_table_floats() floats), the bound on its outputs behind a handle's net_out_bound
+void embed_gru_rows(const float* w, int S, int I, int h1, int h2, float* full);
+std::vector<float> permute_gru_weights(const float* raw);
+float gru_out_bound(const float* raw);
 int check_config(const char* who, const ctk_config* cfg, const EnvInfo** einfo_out);
 int probe_device(const char* who, int device, hipDeviceProp_t* prop);
 

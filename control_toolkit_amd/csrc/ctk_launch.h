@@ -207,6 +207,27 @@ size_t ctk_mppi_batch_mlp_table_floats();
 hipError_t ctk_launch_mppi_batch_mlp(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                      const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
                                      const float* w_dev, const void* k_dev = nullptr);
+// the GRU forms of the batch kernel (ctk_mppi.hip: ctk_mppi_batch_gru<LOG, FORM> / ctk_mppi_batch_gru_pp<LOG, FORM>; include/ctk_hip.h:
+// ctk_gru_batch_*): CartPole's GRU predictor, 16 trajectories per workgroup, the same descriptors and step records, in the FORM a handle
+// of the configuration launches (0 or CTK_MPPI_FORM_WIDE_TAIL: mppi_form over the {value, seq} tail).  Problem p's block of w_dev, at
+// p * ctk_mppi_batch_gru_block_floats(), is
+//   [ per-lane table, ctk_mppi_batch_gru_table_floats() | carried hidden state h1[32] h2[32] | fast-cosine word | pad to 16 bytes ]
+// — table | hidden as in a handle's d_wperm (ctk_api.hip: permute_gru_weights), so the body reads both where it reads a handle's.  The word
+// is 1 where the network's outputs stay inside the unchecked cosine's range whatever the state (the host's net_out_bound * hidden_scale
+// <= CTK_SINCOS_FAST_LIMIT); the kernel forms a.fast_cos_ok from it and |s[2]| of the step record, a handle's per-step decision.
+// fit: 0 for exactly the sizes at which a handle hands its block records over in-launch through the {value, seq} words, else why not —
+// 2 the records are too many for that tail (ctk_ll_records_ok), 3 they do not fit its LDS staging, 4 LDS over 160 KiB; *form_out: the FORM
+int ctk_mppi_batch_gru_fit(int N, int H, int P, size_t* lds_out, int* blocks_out, int* form_out);
+const char* ctk_mppi_batch_gru_name(bool log, int form, bool per_problem = false);
+size_t ctk_mppi_batch_gru_table_floats();
+size_t ctk_mppi_batch_gru_hidden_floats();
+size_t ctk_mppi_batch_gru_block_floats();
+hipError_t ctk_launch_mppi_batch_gru(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
+                                     const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log, int form,
+                                     const float* w_dev, const void* k_dev = nullptr);
+// ctk_sampled.hip: ctk_gru_advance_batch, the hidden-state advance behind a step of the GRU batch — one workgroup per step record, the
+// record's problem advanced by (the record's state, the problem's own last output desc[id].u_dev), in place in its block of w_dev
+hipError_t ctk_launch_gru_advance_batch(hipStream_t st, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_records, float* w_dev);
 // ---- ctk_plant.hip : the plant of a batch's closed loop (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_step) ----
 // ONE launch of ctk_batch_plant<env>, one lane per record: record j of cur_dev (its id = the problem, its s = the state) advanced by
 // Env<env>::step with element id of kplant_dev (stride ctk_mppi_batch_k_stride(env), filled by ctk_mppi_batch_derive_k from the PLANT's

@@ -496,6 +496,46 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_mlp_pp(const CtkBat
 #include "ctk_mppi_body.inc"
 }
 
+// The GRU forms of the batch kernel (include/ctk_hip.h: ctk_gru_batch_*): the same prologue around the body of
+// ctk_mppi_rollout<0, CTK_PRED_GRU, LOG, false[, FORM]> — 16 trajectories per workgroup shared by its four waves (ctk_gru.h), grid
+// (ceil(N / 16), problems of this launch).  FORM is the launch's, as for a handle: 0 or CTK_MPPI_FORM_WIDE_TAIL (64 records of cfg2's
+// 52 words are more than the narrow tail's one poll batch); the tail addresses its problem through blockIdx.x, gridDim.x and fz alone
+// in either form.  wbase is the base of the per-problem blocks ([B][wstride] floats: table | carried hidden state | fast-cosine word |
+// pad, ctk_gru.h: GRU_BATCH_*): the body reads the table at wperm and the hidden state at wperm + GRU_TABLE_FLOATS, as in a handle's
+// launch; nothing here writes the block (the hidden state advances in ctk_gru_advance_batch, ctk_sampled.hip, behind the launch).
+// a.fast_cos_ok is a handle's per-step decision (ctk_api.hip: make_args): |s[2]| inside the unchecked cosine's range — the record's
+// state, which in a run the plant kernel wrote — and the block's word, the half of it the host keeps.  q.id is uniform: scalar work.
+template <bool LOG, int FORM>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_gru(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                 const InterpEntry* __restrict__ interp, const float* __restrict__ wbase,
+                                                                 const void* spare, int N_, int H_, int P_, uint32_t pmagic_, uint32_t wstride,
+                                                                 RolloutArgs a_tpl, EnvK k, MppiK m, FuseArgs fz_tpl) {
+    constexpr int ENV = CTK_ENV_CARTPOLE, PRED = CTK_PRED_GRU;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+#include "ctk_mppi_batch_pro.inc"
+    (void)spare;
+    const float* wperm = wbase + (size_t)q.id * wstride;
+    a_in.fast_cos_ok = (fabsf(q.s[2]) <= CTK_SINCOS_FAST_LIMIT && reinterpret_cast<const uint32_t*>(wperm)[GRU_BATCH_WORD] != 0u) ? 1 : 0;
+#include "ctk_mppi_body.inc"
+}
+
+// ... with per-problem cost constants (ctk_gru_problem_set_param): k from kdev [B], exactly as ctk_mppi_batch_pp takes it
+template <bool LOG, int FORM>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_gru_pp(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                    const InterpEntry* __restrict__ interp, const float* __restrict__ wbase,
+                                                                    const unsigned char* __restrict__ kdev, int N_, int H_, int P_, uint32_t pmagic_,
+                                                                    uint32_t wstride, RolloutArgs a_tpl, MppiK m, FuseArgs fz_tpl) {
+    constexpr int ENV = CTK_ENV_CARTPOLE, PRED = CTK_PRED_GRU;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+#include "ctk_mppi_batch_pro.inc"
+    const EnvK k = *reinterpret_cast<const EnvK*>(kdev + (size_t)q.id * CtkBatchKStride<CTK_ENV_CARTPOLE>::value);
+    const float* wperm = wbase + (size_t)q.id * wstride;
+    a_in.fast_cos_ok = (fabsf(q.s[2]) <= CTK_SINCOS_FAST_LIMIT && reinterpret_cast<const uint32_t*>(wperm)[GRU_BATCH_WORD] != 0u) ? 1 : 0;
+#include "ctk_mppi_body.inc"
+}
+
 // ---------------------------------------------------------------------------------------------
 // Throughput variant (ODE, N >= CTK_MPPI_THROUGHPUT_MIN_N): one wave per block, 64 trajectories, the
 // inputs formed inline in the recurrence instead of through an LDS input buffer.  LDS per block is the
@@ -1083,6 +1123,56 @@ hipError_t ctk_launch_mppi_batch_mlp(hipStream_t st, const float* params, float 
                                static_cast<const void*>(nullptr), a.N, a.H, a.P, pmagic, wstride, a, k, m, fz);
         });
     }
+    return hipGetLastError();
+}
+
+// ---- the GRU batch form (ctk_mppi_batch_gru): the GRU form of the 4-wave kernel with the {value, seq} tail in the FORM a handle's launch
+// of these sizes takes.  Blocks, LDS, the staging test and the form come from the functions launch_mppi_4wave takes them from.
+int ctk_mppi_batch_gru_fit(int N, int H, int P, size_t* lds_out, int* blocks_out, int* form_out) {
+    const int blocks = ctk_mppi_num_blocks(N, CTK_PRED_GRU);
+    if (blocks_out) *blocks_out = blocks;
+    if (form_out) *form_out = 0;
+    if (!ctk_ll_records_ok(blocks, P)) return 2;
+    int stage_ok;
+    const size_t lds = rollout_launch_lds(P, H, CTK_PRED_GRU, N, blocks, &stage_ok);
+    if (lds_out) *lds_out = lds;
+    if (!stage_ok) return 3;
+    if (lds > 160 * 1024) return 4;
+    if (form_out) *form_out = mppi_form(CTK_PRED_GRU, blocks, P, true);
+    return 0;
+}
+const char* ctk_mppi_batch_gru_name(bool log, int form, bool per_problem) {
+    return ctk_kernel_name(per_problem ? "ctk_mppi_batch_gru_pp<%4$s, %1$d>" : "ctk_mppi_batch_gru<%4$s, %1$d>", form, 0, 0, log ? "true" : "false");
+}
+size_t ctk_mppi_batch_gru_table_floats() { return (size_t)GRU_TABLE_FLOATS; }
+size_t ctk_mppi_batch_gru_hidden_floats() { return (size_t)GRU_HIDDEN_FLOATS; }
+size_t ctk_mppi_batch_gru_block_floats() { return (size_t)GRU_BATCH_BLOCK_FLOATS; }
+
+hipError_t ctk_launch_mppi_batch_gru(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
+                                     const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log, int form,
+                                     const float* w_dev, const void* k_dev) {
+    size_t lds;
+    int blocks, fit_form;
+    if (n_problems < 1 || w_dev == nullptr || ctk_mppi_batch_gru_fit(a.N, a.H, a.P, &lds, &blocks, &fit_form) != 0 || form != fit_form) return hipErrorInvalidValue;
+    const dim3 grid(blocks, n_problems), block(MPPI_BLOCK);
+    FuseArgs fz{};                                     // as ctk_launch_mppi_batch: merge + update by block 0 of every problem
+    fz.mode = 1; fz.stage_ok = 1;
+    fz.up = mppi_update_args(a, CTK_C, nullptr, nullptr, nullptr, nullptr, 0u);
+    const uint32_t pmagic = ctk_magic_of(a.P), wstride = (uint32_t)GRU_BATCH_BLOCK_FLOATS;
+    with_mppi_form<false>(form, [&](auto form_c) {
+        ctk_with_bool(log, [&](auto log_c) {
+            constexpr int FV = decltype(form_c)::value;
+            constexpr bool LV = decltype(log_c)::value;
+            if (k_dev) {
+                hipLaunchKernelGGL((ctk_mppi_batch_gru_pp<LV, FV>), grid, block, lds, st, desc_dev, steps_dev, a.interp, w_dev,
+                                   static_cast<const unsigned char*>(k_dev), a.N, a.H, a.P, pmagic, wstride, a, m, fz);
+            } else {
+                const EnvK k = Env<CTK_ENV_CARTPOLE>::derive(params, dt, isteps);
+                hipLaunchKernelGGL((ctk_mppi_batch_gru<LV, FV>), grid, block, lds, st, desc_dev, steps_dev, a.interp, w_dev,
+                                   static_cast<const void*>(nullptr), a.N, a.H, a.P, pmagic, wstride, a, k, m, fz);
+            }
+        });
+    });
     return hipGetLastError();
 }
 

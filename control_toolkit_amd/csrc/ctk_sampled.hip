@@ -305,6 +305,39 @@ hipError_t ctk_launch_gru_advance(hipStream_t st, const float* s, const float* u
     return hipGetLastError();
 }
 
+// The same advance for the GRU batch (include/ctk_hip.h: ctk_gru_batch_*), behind the rollout launches of a step: one workgroup per step
+// record, ctk_gru_advance's statements around the record's state, its problem's own last output (desc[id].u_dev, which the step's
+// rollout launch published) and its problem's block of wbase (ctk_gru.h: GRU_BATCH_BLOCK_FLOATS; table | hidden, as a handle's d_wperm).
+// A problem appears in at most one record of a launch, so no two workgroups touch one hidden state; the fast-cosine word behind it stays.
+__global__ __launch_bounds__(GRU_BLOCK) void ctk_gru_advance_batch(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                   float* __restrict__ wbase) {
+    __shared__ __attribute__((aligned(16))) float ex[GRU_EX_FLOATS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const CtkBatchStep& q = steps[blockIdx.x];
+    float* wperm = wbase + (size_t)q.id * GRU_BATCH_BLOCK_FLOATS;
+    float* hidden = wperm + GRU_TABLE_FLOATS;
+    const GruW w = gru_load_weights(wperm, wave, lane);
+    GruState st = gru_load_state(hidden, g);
+    const float sv = g == 0 ? q.s[0] : (g == 1 ? q.s[1] : (g == 2 ? q.s[2] : q.s[3]));
+    const float u = *desc[q.id].u_dev;
+    (void)gru_step(w, st, sv, u, g, ex, wave, lane);   // its barriers order every wave's loads of `hidden` before the stores below
+    if (wave == 0 && c == 0) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                hidden[16 * m + 4 * g + r] = st.h1[m][r];
+                hidden[32 + 16 * m + 4 * g + r] = st.h2[m][r];
+            }
+    }
+}
+
+hipError_t ctk_launch_gru_advance_batch(hipStream_t st, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_records, float* w_dev) {
+    if (n_records < 1 || w_dev == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ctk_gru_advance_batch, dim3(n_records), dim3(GRU_BLOCK), 0, st, desc_dev, steps_dev, w_dev);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // rank-by-counting selection: rank(i) = #{ j : (J_j, j) < (J_i, i) }, a permutation under the total
 // order (cost, index), so idx_out[rank] = i for rank < K is a race-free scatter and idx_out comes

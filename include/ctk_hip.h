@@ -732,6 +732,64 @@ int ctk_mlp_batch_set_weights(ctk_mlp_batch* b, const float* w, size_t n);      
 int ctk_mlp_problem_set_weights(ctk_mlp_batch* b, int n_ids, const int32_t* ids, const float* w, size_t n);   /* ... of every listed problem, w [n_ids][n] */
 int ctk_mlp_problem_have_weights(const ctk_mlp_batch* b, int problem);                          /* 1 once the problem has received weights */
 
+/* -------------------------------------------------------------------------------------------
+ * batched MPPI with the GRU predictor: B independent MPPI controllers of ONE configuration whose plant model is a recurrent network (the
+ * reference's template configuration names one: `GRU-6IN-32H1-32H2-5OUT-0`), stepped by one rollout launch and one hidden-state launch
+ * per step.  The counterpart of ctk_mlp_batch_* for cfg.predictor == CTK_PRED_GRU, a family of its own, added without an ABI bump.
+ * Everything said of ctk_mlp_batch_* holds, with ctk_gru_batch_* / ctk_gru_problem_* for its names.  What differs:
+ *  - CONTRACT: problem p behaves bit for bit like ctk_create(cfg with predictor = CTK_PRED_GRU, seed = seeds[p]) that received the same
+ *    calls — ctk_set_predictor_weights[_shaped], ctk_set_param, ctk_step, ctk_reset, ctk_set_state, ctk_rng_set_position,
+ *    ctk_predictor_get_hidden / ctk_predictor_set_hidden — the carried hidden state after every step included: a listed problem's hidden
+ *    state advances by (the state it was given, the u it published), as a handle's does behind its step; an unlisted problem's does not
+ *    move.  The kernel runs in the form a handle of the configuration launches (the narrow or the wide {value, seq} tail), and takes a
+ *    handle's per-step choice between the unchecked and the checked cosine per problem and per step, inside runs and episodes as well;
+ *  - every problem has its own network and its own hidden state [2][32] (ctk_gru_problem_get_hidden / _set_hidden: 64 floats per listed
+ *    problem, rows in the order of ids; src NULL: zeros).  Setting weights zeroes the hidden state of the LISTED problems, as
+ *    ctk_set_predictor_weights does a handle's, and touches no other problem's.  Neither weights nor hidden state are part of the
+ *    ctk_gru_batch_get_state vector; ctk_gru_batch_reset and ctk_gru_batch_set_state leave both alone, as ctk_reset and ctk_set_state do;
+ *  - a step, run or episode that lists a problem without weights is CTK_ERR_STATE; nothing is launched and no hidden state moves;
+ *  - in ctk_gru_batch_run the hidden state advances by the state the controller was given, in ctk_gru_batch_episodes by the observation
+ *    (ctk_hip_gru.h declares the closed-loop entries);
+ *  - refused at creation from the configuration alone (CTK_ERR_UNSUPPORTED, the sizes in ctk_gru_batch_last_error(NULL)): an optimizer
+ *    other than MPPI; a predictor other than GRU (ODE: ctk_batch_create, MLP: ctk_mlp_batch_create); an environment other than CartPole,
+ *    or generic_kernels != 0; hidden widths outside 1 .. 32 (narrower than 32 is embedded exactly, as by
+ *    ctk_set_predictor_weights_shaped); n_problems < 1; per-problem sizes at which a handle does not hand its block records (16
+ *    rollouts each) over inside the launch: more than 128 records that hold more than 4096 words, or more than 512 records.
+ *    ctk_gru_batch_fit answers that last question for sizes alone, without a device: CTK_OK or CTK_ERR_UNSUPPORTED, the records per
+ *    problem, the words of one, whether the launches take the wide tail, and their dynamic LDS;
+ *  - not offered: a hidden-state advance with a caller's u (ctk_predictor_update), the template kernels' GRU (other environments), GRU
+ *    with the CEM or RPGD batches, widths above 32, the resident form.
+ * Each entry corresponds to the single-handle call named beside it.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct ctk_gru_batch ctk_gru_batch;
+int ctk_gru_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds /* NULL: cfg->seed + p */, ctk_gru_batch** out); /* ctk_create */
+void ctk_gru_batch_destroy(ctk_gru_batch* b);                                                   /* ctk_destroy */
+const char* ctk_gru_batch_last_error(const ctk_gru_batch* b);                                   /* ctk_last_error; b may be NULL */
+int ctk_gru_batch_size(const ctk_gru_batch* b);                                                 /* B */
+size_t ctk_gru_batch_samples_needed(const ctk_gru_batch* b);                                    /* ctk_samples_needed, per problem: N*P*C */
+int ctk_gru_batch_step(ctk_gru_batch* b, int n_ids, const int32_t* ids, const float* s, const float* u_prev,
+                       const float* samples, int samples_loc, float* u_out);                    /* ctk_step of every listed problem */
+int ctk_gru_batch_reset(ctk_gru_batch* b, int n_ids, const int32_t* ids);                       /* ctk_reset of every listed problem */
+int ctk_gru_batch_read(ctk_gru_batch* b, int problem, int buffer, float* dst, size_t cap);      /* ctk_read: CTK_BUF_Q, J, TRAJ, U_NOM */
+int ctk_gru_batch_get_state(ctk_gru_batch* b, int problem, float* dst, size_t cap);             /* ctk_get_state: u_nom [H,C], u [C] */
+int ctk_gru_batch_set_state(ctk_gru_batch* b, int problem, const float* src, size_t n);         /* ctk_set_state */
+int ctk_gru_batch_set_param(ctk_gru_batch* b, int id, float value);                             /* ctk_set_param, all problems */
+int ctk_gru_batch_get_param(const ctk_gru_batch* b, int id, float* value);                      /* ctk_get_param */
+int ctk_gru_batch_rng_get_position(const ctk_gru_batch* b, int problem, uint32_t* call);        /* ctk_rng_get_position */
+int ctk_gru_batch_rng_set_position(ctk_gru_batch* b, int problem, uint32_t call);               /* ctk_rng_set_position */
+const char* ctk_gru_batch_dominant_kernel(const ctk_gru_batch* b);                              /* ctk_dominant_kernel */
+int ctk_gru_problem_set_param(ctk_gru_batch* b, int n_ids, const int32_t* ids, int id, const float* values);   /* ctk_set_param of every listed problem */
+int ctk_gru_problem_get_param(const ctk_gru_batch* b, int problem, int id, float* value);       /* ctk_get_param of one problem */
+int ctk_gru_problem_params_differ(const ctk_gru_batch* b);                                      /* 1 once a ctk_gru_problem_set_param has succeeded */
+size_t ctk_gru_batch_weight_count(const ctk_gru_batch* b);                                      /* ctk_predictor_weight_count_shaped for cfg.predictor_hidden1/2 */
+int ctk_gru_batch_set_weights(ctk_gru_batch* b, const float* w, size_t n);                      /* ctk_set_predictor_weights[_shaped] of every problem, one network */
+int ctk_gru_problem_set_weights(ctk_gru_batch* b, int n_ids, const int32_t* ids, const float* w, size_t n);   /* ... of every listed problem, w [n_ids][n] */
+int ctk_gru_problem_have_weights(const ctk_gru_batch* b, int problem);                          /* 1 once the problem has received weights */
+int ctk_gru_problem_get_hidden(ctk_gru_batch* b, int n_ids, const int32_t* ids, float* dst);    /* ctk_predictor_get_hidden of every listed problem, dst [n_ids][64] */
+int ctk_gru_problem_set_hidden(ctk_gru_batch* b, int n_ids, const int32_t* ids, const float* src);   /* ctk_predictor_set_hidden ..., src [n_ids][64] or NULL: zeros */
+int ctk_gru_batch_fit(int num_rollouts, int mpc_horizon, int period_interpolation_inducing_points, int* blocks, int* record_words,
+                      int* wide_tail, size_t* lds_bytes);                                       /* no device needed; every out pointer may be NULL */
+
 #ifdef __cplusplus
 }
 #endif
@@ -740,4 +798,6 @@ int ctk_mlp_problem_have_weights(const ctk_mlp_batch* b, int problem);          
 #include "ctk_hip_episode.h"
 /* the same closed loops for the CEM and RPGD batches */
 #include "ctk_hip_loop.h"
+/* ... and for the GRU batch */
+#include "ctk_hip_gru.h"
 #endif /* CTK_HIP_H */
