@@ -47,7 +47,20 @@ class controller_mpc(template_controller):
         self.optimizer.configure(dt=dt, predictor_specification=predictor_specification,                            # :84-89
                                  num_states=self.predictor.num_states, num_control_inputs=self.predictor.num_control_inputs)
         self.controller_data_for_csv = self.cost_function.cost_function.logged_attributes                           # :91
-        self.step = self.lib.set_device(cc.get("device", "gpu"))(self.step)                                         # :93-96
+        self.step = self._bind_native_step(self.lib.set_device(cc.get("device", "gpu"))(self.step))                 # :93-96
+
+    def _bind_native_step(self, step):
+        """`step` behind the bound controller step (csrc/ctk_pystep.cpp: bind_controller) where the optimizer has a bound step of its
+        own and this class's step is the one it restates; it calls `step` with the caller's arguments whenever there is more to do
+        than the optimizer's step (a cost reload pending, updated attributes, logging) or the optimizer's bound step declines"""
+        from .._capi import _pystep_module
+        step = getattr(step, "__wrapped__", step)   # configure() called again: not a bound step around the last one
+        fast, mod = getattr(self.optimizer, "_fast", None), _pystep_module()
+        if fast is None or mod is None or not hasattr(mod, "bind_controller") or type(self).step is not controller_mpc.step \
+                or type(self).update_logs is not template_controller.update_logs \
+                or type(self).update_attributes is not template_controller.update_attributes:
+            return step
+        return mod.bind_controller(self, self.optimizer, fast, step)
 
     def _make_optimizer(self, optimizer_name: str, opt_cfg: dict):
         kwargs = dict(opt_cfg)

@@ -26,7 +26,7 @@ def caller_side_library_ok(lib) -> bool:
 def logging_kwargs(kwargs: dict) -> dict:
     """the optional YAML keys of this build that every optimizer forwards to template_optimizer"""
     return {k: kwargs[k] for k in ("logging_on_device", "logging_capacity", "environment_name", "generic_kernels",
-                                   "predictor_parameters", "predictor_weights_file", "predictor_intermediate_steps") if k in kwargs}
+                                   "predictor_parameters", "predictor_weights_file", "predictor_intermediate_steps", "native_step") if k in kwargs}
 
 
 class DeviceLogEntry:
@@ -110,6 +110,47 @@ class template_optimizer:
         self.optimal_trajectory = None
         self.rollout_trajectories = None
         self._lazy = {}   # device buffers fetched on first access after a step (u_nom: no D2H copy on the step path)
+        # optional key `native_step: false` of the optimizer's YAML entry: keep step() on its Python body even where the bound step
+        # (csrc/ctk_pystep.cpp: bind_optimizer) is available; see step_path
+        self.native_step = bool(kwargs.get("native_step", True))
+        self._fast = None
+
+    # step() of an optimizer whose class names its own step as _native_step_fn starts by calling self._fast (None: not there), which
+    # does the whole step in one C++ call or returns NotImplemented before anything has happened
+    _native_step_fn = None
+    _native_step_flags = 0   # ctk_pystep.cpp: STEP_CLEARS_LAZY = 1 (MPPI), STEP_COUNTS = 2 (CEM)
+
+    def _bind_native_step(self):
+        """the bound step for this optimizer, or None: the class has none (or a subclass replaced step), `native_step: false`,
+        CTK_PYSTEP=0 / module not built, an engine without a valid bound call, or cost / predictor objects that are not this
+        build's own wrappers (their parameters are keyed by _parameter_values every step, in Python)"""
+        from .._capi import _pystep_module
+        from ..others.globals_and_utils import DeviceRng, DeviceBufferRng
+        cls, eng, cf = type(self), self.engine, self.cost_function
+        mod = _pystep_module()
+        if (not self.native_step or cls._native_step_fn is None or cls.step is not cls._native_step_fn or mod is None
+                or not hasattr(mod, "bind_optimizer") or eng is None or getattr(eng, "_bound", None) is None or not eng._bound.valid
+                or not (hasattr(cf, "version") and isinstance(getattr(cf, "parameters", None), dict))):
+            return None
+        fast = mod.bind_optimizer(self, eng, eng._bound, eng._u, tuple(eng.param_names), DeviceRng, DeviceBufferRng,
+                                  cls._native_step_flags)
+        eng._fast_step = fast
+        return fast
+
+    @property
+    def step_path(self) -> str:
+        """which path the last step took: "native" (the bound step) or "python" """
+        return "native" if self._fast is not None and self._fast.last_native else "python"
+
+    @property
+    def native_step_count(self) -> int:
+        """steps the bound step made"""
+        return 0 if self._fast is None else self._fast.native_steps
+
+    @property
+    def declined_step_count(self) -> int:
+        """steps the bound step handed to the Python body"""
+        return 0 if self._fast is None else self._fast.declined_steps
 
     # The reference converts u_nom to NumPy every step (optimizer_mppi.py:220, optimizer_rpgd.py:426,435); here the
     # plan stays in HBM and is copied when somebody looks at it.
@@ -229,7 +270,9 @@ class template_optimizer:
         self._param_cache = {}
         self._cost_version = None
         self._sync_key = None
+        self._fast = None
         self._sync_parameters(force=True)
+        self._fast = self._bind_native_step()
 
     def _parameter_values(self) -> dict:
         """Every value the kernels take as a constant, from the objects the controller wired in.  Provider chain, later
@@ -303,7 +346,10 @@ class template_optimizer:
         else:
             vals = self._parameter_values()
             key = tuple(vals.values())
+        fast = self._fast
         if not force and key == self._sync_key:
+            if fast is not None and fast.stale:   # it declined over something this key does not see (a dictionary replaced by an equal one)
+                fast.resync()
             return
         self._sync_key = key
         if vals is None:
@@ -312,6 +358,8 @@ class template_optimizer:
             if force or self._param_cache.get(name) != v:
                 self.engine.set_param(name, v)
                 self._param_cache[name] = v
+        if fast is not None:
+            fast.resync()   # the bound step's own snapshot of what this key covers
 
     def _draws(self, kind: str, shape):
         """None => on-device Philox; otherwise RAW host draws of `shape`."""

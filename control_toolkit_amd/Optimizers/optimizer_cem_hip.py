@@ -39,6 +39,11 @@ class optimizer_cem_hip(template_optimizer):
         self.optimizer_reset()
 
     def step(self, s: np.ndarray, time=None):
+        fast = self._fast   # the whole step in one C++ call; NotImplemented: nothing has happened, the body below runs
+        if fast is not None:
+            u = fast(s)
+            if u is not NotImplemented:
+                return u
         if self.optimizer_logging:
             self.logging_values = {"s_logged": np.asarray(s).copy()}
         s = self._prepare_state(s)
@@ -63,3 +68,7 @@ class optimizer_cem_hip(template_optimizer):
         self.engine.reset()
         self.count = 0
         self.u = 0.0
+
+
+optimizer_cem_hip._native_step_flags = 2   # count += 1; a warm-up run's first step stays here
+optimizer_cem_hip._native_step_fn = optimizer_cem_hip.step   # the step the bound step restates (template_optimizer._bind_native_step)

@@ -41,6 +41,11 @@ class optimizer_mppi_hip(template_optimizer):
         self.optimizer_reset()
 
     def step(self, s: np.ndarray, time=None):
+        fast = self._fast   # the whole step in one C++ call; NotImplemented: nothing has happened, the body below runs
+        if fast is not None:
+            u = fast(s)
+            if u is not NotImplemented:
+                return u
         if self.optimizer_logging:
             self.logging_values = {"s_logged": np.asarray(s).copy()}
         s = self._prepare_state(s)
@@ -57,3 +62,7 @@ class optimizer_mppi_hip(template_optimizer):
     def optimizer_reset(self):
         self.engine.reset()                                                       # :227-231
         self._lazy.clear()
+
+
+optimizer_mppi_hip._native_step_flags = 1
+optimizer_mppi_hip._native_step_fn = optimizer_mppi_hip.step   # the step the bound step restates (template_optimizer._bind_native_step)

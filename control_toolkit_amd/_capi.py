@@ -418,6 +418,7 @@ class CtkEngine:
         self._u_p, self._s_p, self._up_p = self._u.ctypes.data, self._s.ctypes.data, self._up.ctypes.data
         self._step_fn = lib.ctk_step
         self._bound = None
+        self._fast_step = None   # the optimizer's bound step around this engine (Optimizers/__init__.py: _bind_native_step), for close()
         if pystep is None or pystep:
             self._bind_step()
 
@@ -440,6 +441,9 @@ class CtkEngine:
             raise (ValueError if rc == 1 else NotImplementedError if rc == 2 else CtkError)(f"[ctk {rc}] {msg}")
 
     def close(self):
+        if getattr(self, "_fast_step", None) is not None:   # first of all: it calls ctk_step with this handle on its own
+            self._fast_step.invalidate()
+            self._fast_step = None
         if getattr(self, "_bound", None) is not None:   # before ctk_destroy: the bound call must never see a freed handle
             self._bound.invalidate()
             self._bound = None
