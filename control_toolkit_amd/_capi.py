@@ -215,6 +215,21 @@ LOOP_SYMBOLS = {f"{family}_{name}": sig for family in ("ctk_cem_batch", "ctk_rpg
 # ... and for the GRU batch (include/ctk_hip_gru.h, which ctk_hip.h includes): a fifth table, bound with the other four
 GRU_LOOP_SYMBOLS = {f"ctk_gru_batch_{name}": sig for name, sig in list(_PLANT_RUN.items()) + list(_PLANT_EPISODE.items())}
 
+# per-problem MPPI hyper-parameters and input limits of the three MPPI batches (include/ctk_hip_hyper.h, which ctk_hip.h includes): a
+# sixth table, bound with the other five.  HYPERS: enum ctk_hyper.
+HYPERS = {"cc_weight": 0, "R": 1, "LBD": 2, "NU": 3, "SQRTRHOINV": 4}
+_PROBLEM_HYPER = {
+    "set_hyper": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "get_hyper": (C.c_int, [_H, C.c_int, C.c_int, _FP]),
+    "set_limits": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "get_limits": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
+    "hypers_differ": (C.c_int, [_H]),
+}
+HYPER_SYMBOLS = {}
+for _batch, _problem in _BATCH_FAMILIES[:3]:
+    HYPER_SYMBOLS.update({f"{_problem}_{name}": sig for name, sig in _PROBLEM_HYPER.items()})
+    HYPER_SYMBOLS[f"{_batch}_set_hyper"] = (C.c_int, [_H, C.c_int, C.c_float])
+
 
 # user environments (include/ctk_user_env.h): name -> path of the library that was compiled with that model (control_toolkit_amd/build_env.py:
 # register_environment); their environment id inside that library is CTK_ENV_USER
@@ -259,7 +274,7 @@ def _bind_library(path: str):
     except OSError as e:
         raise CtkError(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()) + list(LOOP_SYMBOLS.items()) + \
-            list(GRU_LOOP_SYMBOLS.items()):
+            list(GRU_LOOP_SYMBOLS.items()) + list(HYPER_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctk_abi_version() != 6:
@@ -883,6 +898,72 @@ def batch_param_args(param_names, num_problems: int, name, values, ids=None):
     return param_names.index(name), idv, n, out
 
 
+def batch_hyper_args(num_problems: int, name, values, ids=None, Cn: int = 1):
+    """Checks the arguments of CtkMppiBatch.set_problem_hypers / set_hyper / set_problem_limits without touching a device: the name
+    against HYPERS, ids (batch_ids), values a scalar (every listed problem) or one value per listed problem ([n]), each finite in fp32,
+    LBD > 0, NU != 0.  Returns (hyper id, ids, n, values as fp32 [n]).  name "limits": values is (low, high), each a scalar, [Cn] or
+    [n, Cn] with low <= high (batch_limit_args); returns (None, ids, n, (low, high) as fp32 [n, Cn])."""
+    if name == "limits":
+        try:
+            low, high = values
+        except (TypeError, ValueError):
+            raise ValueError(f"limits are a pair (low, high), got {values!r}") from None
+        idv, n, lo, hi = batch_limit_args(num_problems, Cn, low, high, ids)
+        return None, idv, n, (lo, hi)
+    if name not in HYPERS:
+        raise ValueError(f"unknown hyper-parameter {name!r} (MPPI has {', '.join(HYPERS)}; \"limits\" for the input limits)")
+    idv = batch_ids(num_problems, ids)
+    n = num_problems if idv is None else int(idv.size)
+    try:
+        vals = np.asarray(values, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"values of {name!r} must be a number or an array of numbers, got {values!r}") from None
+    if vals.ndim == 0:
+        vals = np.full(n, float(vals))
+    if vals.shape != (n,):
+        raise ValueError(f"{name!r}: one value per listed problem ({n}) or a scalar, got shape {tuple(vals.shape)}")
+    ok = np.abs(vals) <= _F32_MAX                                  # NaN compares false: refused with the infinities and what overflows fp32
+    what = "must be finite in fp32"
+    with np.errstate(over="ignore"):
+        out = vals.astype(np.float32)
+    if ok.all() and name == "LBD":
+        ok, what = out > 0.0, "must be > 0"                        # as the library sees it: after the rounding to fp32
+    if ok.all() and name == "NU":
+        ok, what = out != 0.0, "must not be 0"
+    if not ok.all():
+        j = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"{name!r} {what}: {float(vals[j])!r} for problem {j if idv is None else int(idv[j])}")
+    return HYPERS[name], idv, n, out
+
+
+def batch_limit_args(num_problems: int, Cn: int, low, high, ids=None):
+    """Checks the arguments of CtkMppiBatch.set_problem_limits without touching a device: ids (batch_ids), low and high each a scalar,
+    [C] or [n, C], finite in fp32, low <= high for every input.  Returns (ids, n, low, high as fp32 [n, C])."""
+    idv = batch_ids(num_problems, ids)
+    n = num_problems if idv is None else int(idv.size)
+    out = []
+    for what, v in (("low", low), ("high", high)):
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a number or an array of numbers, got {v!r}") from None
+        if a.ndim == 0 or a.shape == (Cn,):
+            a = np.broadcast_to(a, (n, Cn))
+        if a.shape != (n, Cn):
+            raise ValueError(f"{what} must be a scalar, ({Cn},) or ({n}, {Cn}): one row per listed problem, got shape {tuple(a.shape)}")
+        ok = np.abs(a) <= _F32_MAX
+        if not ok.all():
+            j, c = (int(x[0]) for x in np.nonzero(~ok))
+            raise ValueError(f"{what} must be finite in fp32: {float(a[j, c])!r} for problem {j if idv is None else int(idv[j])}, input {c}")
+        out.append(np.ascontiguousarray(a, dtype=np.float32))
+    bad = ~(out[0] <= out[1])
+    if bad.any():
+        j, c = (int(x[0]) for x in np.nonzero(bad))
+        raise ValueError(f"low must be <= high for every input: {float(out[0][j, c])!r} > {float(out[1][j, c])!r} for problem "
+                         f"{j if idv is None else int(idv[j])}, input {c}")
+    return idv, n, out[0], out[1]
+
+
 class _CtkBatch:
     """What the batch classes share: the handle, the argument buffers, the error mapping, the parameter tables and the Philox positions.
     A family is its two entry-point prefixes (_BATCH: the calls on a batch, _PROBLEM: the per-problem parameter calls); its entries are
@@ -1051,7 +1132,8 @@ class CtkMppiBatch(_CtkBatch):
     """Owns one ctk_batch: num_problems independent MPPI controllers of ONE configuration (the MPPI keywords of CtkEngine), stepped by
     one kernel launch per step.  Problem p behaves bit for bit like CtkEngine("mppi", "ODE", seed=seeds[p], ...) given the same calls,
     set_param among them: set_problem_params gives every problem its own plant, cost weights and targets, set_param the same value to all.
-    seeds: one per problem (default seed + p)."""
+    batch.hypers (BatchHypers: set_problem_hypers, set_hyper, set_problem_limits ...) gives every problem its own MPPI hyper-parameters
+    and input limits: problem p is then the CtkEngine created with those values.  seeds: one per problem (default seed + p)."""
 
     _BATCH, _PROBLEM = "ctk_batch", "ctk_problem"
 
@@ -1073,6 +1155,23 @@ class CtkMppiBatch(_CtkBatch):
                    global_rollout_offset=global_rollout_offset, num_states=num_states, num_control_inputs=num_control_inputs,
                    generic_kernels=generic_kernels, **kw)
         self._per = int(self._b.samples_needed(self._h))
+
+    # ---- per-problem MPPI hyper-parameters and input limits (include/ctk_hip_hyper.h); the MLP and GRU batches inherit them ----
+    @property
+    def hypers(self) -> "BatchHypers":
+        """THE interface to the per-problem MPPI hyper-parameters and input limits: hypers.set_problem_hypers(name, values, ids),
+        .set_hyper(name, value), .get_problem_hyper(name, problem), .get_problem_hypers(name), .set_problem_limits(low, high, ids),
+        .get_problem_limits(problem), .hypers_differ() (BatchHypers).  A view of this batch, as closed_loop is: it owns nothing, and it is
+        not kept (a kept view would tie the batch into a reference cycle and delay the release of its device memory)."""
+        return BatchHypers(self)
+
+    def __getattr__(self, name):
+        # CONVENIENCE ONLY, and deliberately not methods: batch.set_problem_hypers(...) is batch.hypers.set_problem_hypers(...) for the
+        # seven names of BatchHypers.CALLS.  The batch classes' method lists are pinned (tests/test_batch_cpu.py), so the calls are
+        # defined, documented and introspectable on the view; dir(batch), help() and completion show them there, not here.
+        if name in BatchHypers.CALLS:
+            return getattr(self.hypers, name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def samples_needed(self) -> int:
         """draws one problem's step consumes (N * P * C)"""
@@ -1106,6 +1205,72 @@ class CtkMppiBatch(_CtkBatch):
 
     def get_state(self, problem: int) -> np.ndarray:
         return self._get_state(problem, self.H * self.C + self.C)
+
+
+# ---- per-problem MPPI hyper-parameters and input limits of an MPPI batch (include/ctk_hip_hyper.h) ----------------------------------------------
+class BatchHypers:
+    """CtkMppiBatch.hypers / CtkMppiMlpBatch.hypers / CtkMppiGruBatch.hypers: every problem's own cc_weight, R, LBD, NU, SQRTRHOINV and
+    input limits, settable at any time between steps.  Problem p then behaves bit for bit like CtkEngine("mppi", ..., seed=seeds[p])
+    created with p's values; a change makes it equal to a fresh such handle that received the problem's state vector and Philox position
+    (and hidden state).  A view of the batch: it owns nothing.  CEM and RPGD batches have no such view."""
+
+    CALLS = ("set_problem_hypers", "set_hyper", "get_problem_hyper", "get_problem_hypers", "set_problem_limits", "get_problem_limits", "hypers_differ")
+
+    def __init__(self, batch):
+        self._batch = batch
+
+    def _entry(self, entry: str):
+        """the family's hyper-parameter entry `entry` (of the problem prefix; "batch_set_hyper": the whole-batch one)"""
+        b = self._batch
+        return getattr(b._lib, f"{b._BATCH}_set_hyper" if entry == "batch_set_hyper" else f"{b._PROBLEM}_{entry}")
+
+    def set_problem_hypers(self, name: str, values, ids=None):
+        """MPPI hyper-parameter `name` (cc_weight, R, LBD, NU, SQRTRHOINV: the constructor arguments of that name, NOT the environment's
+        cost parameters R / cc_weight, which set_problem_params sets) of the problems in ids (None: all): values a scalar or [n], one
+        per listed problem in the order of ids.  Takes effect at the next step; from the first call on the batch runs the _hp form of
+        its kernel (hypers_differ, dominant_kernel).  Problem p then behaves like CtkEngine("mppi", ..., seed=seeds[p], <name>=value)."""
+        b = self._batch
+        hid, idv, n, vals = batch_hyper_args(b.B, name, values, ids)
+        b._check(self._entry("set_hyper")(b._h, n, _ptr(idv), hid, _ptr(vals)))
+
+    def set_hyper(self, name: str, value: float):
+        """MPPI hyper-parameter `name` of every problem"""
+        b = self._batch
+        hid, _, _, vals = batch_hyper_args(b.B, name, value, None)
+        b._check(self._entry("batch_set_hyper")(b._h, hid, float(vals[0])))
+
+    def get_problem_hyper(self, name: str, problem: int) -> float:
+        b = self._batch
+        if name not in HYPERS:
+            raise ValueError(f"unknown hyper-parameter {name!r} (MPPI has {', '.join(HYPERS)})")
+        v = C.c_float()
+        if self._entry("get_hyper")(b._h, b._problem(problem), HYPERS[name], C.byref(v)) != 0:
+            raise CtkError(f"{b._PROBLEM}_get_hyper({problem}, {name!r}) failed")
+        return v.value
+
+    def get_problem_hypers(self, name: str) -> np.ndarray:
+        """[B] hyper-parameter `name` of every problem"""
+        return np.array([self.get_problem_hyper(name, p) for p in range(self._batch.B)], np.float32)
+
+    def set_problem_limits(self, low, high, ids=None):
+        """the input limits (action_low, action_high) of the problems in ids (None: all): each a scalar, [C] or [n, C].  As
+        set_problem_hypers: the next step clips to them, reset() refills the plan with their middle."""
+        b = self._batch
+        _, idv, n, (lo, hi) = batch_hyper_args(b.B, "limits", (low, high), ids, b.C)
+        b._check(self._entry("set_limits")(b._h, n, _ptr(idv), _ptr(lo), _ptr(hi)))
+
+    def get_problem_limits(self, problem: int):
+        """(low [C], high [C]) of a problem"""
+        b = self._batch
+        lo, hi = np.empty(b.C, np.float32), np.empty(b.C, np.float32)
+        if self._entry("get_limits")(b._h, b._problem(problem), _ptr(lo), _ptr(hi)) != 0:
+            raise CtkError(f"{b._PROBLEM}_get_limits({problem}) failed")
+        return lo, hi
+
+    def hypers_differ(self) -> int:
+        """1 once a set_problem_hypers, set_hyper or set_problem_limits has succeeded on this batch (sticky), else 0"""
+        b = self._batch
+        return int(self._entry("hypers_differ")(b._h))
 
 
 # ---- closed-loop episodes of a batch on the device (include/ctk_hip_run.h: ctk_batch_run / ctk_batch_plant_*; ctk_hip_loop.h) ------------------

@@ -908,6 +908,9 @@ int plant_noise_set_position(BatchCore* b, const char* who, int problem, uint32_
 // Per-problem host state is what a handle keeps: the sequence number of its next step, its Philox position, which u_nom buffer is current,
 // its parameter table.  While no ctk_problem_set_param has succeeded the launches take the constants of the shared table by value; from
 // then on (`differ`, sticky) they read every problem's constants from d_k, which ctk_batch_step refreshes for the problems marked dirty.
+// The optimizer's own numbers go the same way (include/ctk_hip_hyper.h): the five MPPI hyper-parameters and the input limits are the
+// configuration's until a *_problem_set_hyper / *_problem_set_limits / *_batch_set_hyper has succeeded; from then on (`hyper`, sticky) the
+// launches take the _hp form, which reads every problem's constants AND its MppiK and limits from the two-part elements of d_kh (batch_flush_kh).
 // =============================================================================================
 struct ctk_batch : BatchCore {
     int P = 0, PC = 0, blocks = 0;
@@ -939,6 +942,17 @@ struct ctk_batch : BatchCore {
     uint32_t* h_flag = nullptr;             // pinned [B]: net_out_bound * hidden_scale <= CTK_SINCOS_FAST_LIMIT, the word of every block
     std::vector<float> net_out_bound;       // [B] what a handle keeps under these names (ctk_api.hip): INFINITY until weights arrive,
     std::vector<float> hidden_scale;        // [B] 1, or max(1, max |h|) of a caller-set hidden state
+    // per-problem optimizer hyper-parameters and input limits (include/ctk_hip_hyper.h): the table of primary values, initialised from
+    // cfg; `hyper` (sticky, as `differ`) once a setter has succeeded: the _hp form of the kernel from then on, fed from d_kh
+    std::vector<float> hyp;                 // [B][HYP_ROW]: the five of enum ctk_hyper | low [CTK_MAX_INPUTS] | high [CTK_MAX_INPUTS]
+    std::vector<unsigned char> hdirty;      // [B] the row changed since the problem's element was last derived and copied to d_kh
+    bool hyper = false;
+    size_t khstride = 0;                    // ctk_mppi_batch_kh_stride(env): bytes of one two-part element [K | CtkBatchHyper]
+    unsigned char* h_kh = nullptr;          // pinned [B][khstride]: the staging of the copy to d_kh, and its mirror
+    unsigned char* d_kh = nullptr;          // [B][khstride] what the _hp form takes in the place of d_k
+    static constexpr int HYP_LOW = CTK_HYPER_COUNT, HYP_HIGH = CTK_HYPER_COUNT + CTK_MAX_INPUTS, HYP_ROW = CTK_HYPER_COUNT + 2 * CTK_MAX_INPUTS;
+    float* hrow(int p) { return hyp.data() + (size_t)p * HYP_ROW; }
+    const float* hrow(int p) const { return hyp.data() + (size_t)p * HYP_ROW; }
     size_t unom_stride() const { return (size_t)2 * HC; }
     float* unom(int p, int which) const { return d_unom + (size_t)p * unom_stride() + (size_t)which * HC; }
 };
@@ -974,23 +988,63 @@ hipError_t batch_flush_constants(ctk_batch* b) {
     return e;
 }
 
+// the five hyper-parameters of a configuration in the order of enum ctk_hyper, and back into a copy of it
+void hyper_from_config(const ctk_config& c, float* v) {
+    v[CTK_HYPER_CC_WEIGHT] = c.cc_weight; v[CTK_HYPER_R] = c.R; v[CTK_HYPER_LBD] = c.LBD; v[CTK_HYPER_NU] = c.NU; v[CTK_HYPER_SQRTRHOINV] = c.SQRTRHOINV;
+}
+void hyper_into_config(const float* v, ctk_config* c) {
+    c->cc_weight = v[CTK_HYPER_CC_WEIGHT]; c->R = v[CTK_HYPER_R]; c->LBD = v[CTK_HYPER_LBD]; c->NU = v[CTK_HYPER_NU]; c->SQRTRHOINV = v[CTK_HYPER_SQRTRHOINV];
+}
+
+// The _hp form's per-problem array, by the scheme of batch_flush_constants.  Element p is [K | CtkBatchHyper]: the first part is
+// re-derived where the problem's parameter table changed (`dirty`, with the function a handle uses), the second where its
+// hyper-parameters or limits did (`hdirty`: MppiK by mppi_constants, the function behind a handle's, on a copy of the configuration
+// that carries the problem's values); the span from the first to the last such problem (stepped now or not) travels in ONE transfer
+// on the batch's stream, none when nothing changed.  h_kh mirrors d_kh.  The caller synchronises before it returns, so the staging
+// is free again at the next call.
+hipError_t batch_flush_kh(ctk_batch* b) {
+    int lo = b->B, hi = -1;
+    for (int p = 0; p < b->B; ++p) {
+        if (!b->dirty[(size_t)p] && !b->hdirty[(size_t)p]) continue;
+        unsigned char* elem = b->h_kh + (size_t)p * b->khstride;
+        if (b->dirty[(size_t)p]) ctk_mppi_batch_derive_k(b->env, b->table(p), b->cfg.dt, b->cfg.intermediate_steps, elem);
+        if (b->hdirty[(size_t)p]) {
+            const float* row = b->hrow(p);
+            ctk_config c = b->cfg;
+            hyper_into_config(row, &c);
+            CtkBatchHyper e{};
+            e.m = mppi_constants(c);
+            for (int i = 0; i < CTK_MAX_INPUTS; ++i) { e.lo[i] = row[ctk_batch::HYP_LOW + i]; e.hi[i] = row[ctk_batch::HYP_HIGH + i]; }
+            std::memcpy(elem + b->kstride, &e, sizeof(e));
+        }
+        b->dirty[(size_t)p] = 0; b->hdirty[(size_t)p] = 0;
+        lo = std::min(lo, p); hi = p;
+    }
+    if (hi < 0) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(b->d_kh + (size_t)lo * b->khstride, b->h_kh + (size_t)lo * b->khstride, (size_t)(hi - lo + 1) * b->khstride,
+                                        hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess) for (int p = lo; p <= hi; ++p) b->dirty[(size_t)p] = b->hdirty[(size_t)p] = 1;   // nothing reached the device: derive and copy again
+    return e;
+}
+
 // The controller launches of n step records from steps_dev on (ctk_batch_step; every step of ctk_batch_run): consecutive launches of at
 // most max_per_launch problems — the results do not depend on the split.  *launched: the records that were launched.
 hipError_t batch_launch_records(ctk_batch* b, const RolloutArgs& a, const CtkBatchStep* steps_dev, int n, int* launched) {
     const bool log = b->cfg.materialize_trajectories != 0;
     hipError_t le = hipSuccess;
     *launched = 0;
+    const void* d_k = b->hyper ? b->d_kh : b->differ ? b->d_k : nullptr;     // the _hp form: the two-part elements in d_k's place
     while (le == hipSuccess && *launched < n) {
         const int cnt = std::min(b->max_per_launch, n - *launched);
         if (b->pred == CTK_PRED_GRU)
             le = ctk_launch_mppi_batch_gru(b->stream, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
-                                           b->form, b->d_w, b->differ ? b->d_k : nullptr);
+                                           b->form, b->d_w, d_k, b->hyper);
         else if (b->pred == CTK_PRED_MLP)
             le = ctk_launch_mppi_batch_mlp(b->stream, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
-                                           b->d_w, b->differ ? b->d_k : nullptr);
+                                           b->d_w, d_k, b->hyper);
         else
             le = ctk_launch_mppi_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, a, b->mk, b->d_desc, steps_dev + *launched, cnt, log,
-                                       b->differ ? b->d_k : nullptr);
+                                       d_k, b->hyper);
         if (le == hipSuccess) *launched += cnt;
     }
     return le;
@@ -999,7 +1053,8 @@ hipError_t batch_launch_records(ctk_batch* b, const RolloutArgs& a, const CtkBat
 // optimizer_reset() of problem p (ctk_reset of an MPPI handle): the plan at mid-range in buffer 0; u, the Philox position stay
 int batch_reset_one(ctk_batch* b, int p) {
     std::vector<float> tmp((size_t)b->HC);
-    for (int i = 0; i < b->HC; ++i) tmp[(size_t)i] = 0.5f * (b->cfg.action_low[i % b->C] + b->cfg.action_high[i % b->C]);
+    const float* row = b->hrow(p);                     // the problem's own limits (the configuration's until *_problem_set_limits)
+    for (int i = 0; i < b->HC; ++i) tmp[(size_t)i] = 0.5f * (row[ctk_batch::HYP_LOW + i % b->C] + row[ctk_batch::HYP_HIGH + i % b->C]);
     b->cur[(size_t)p] = 0;
     BHIP_TRY(b, hipMemcpyAsync(b->unom(p, 0), tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
     BHIP_TRY(b, hipStreamSynchronize(b->stream));
@@ -1025,7 +1080,10 @@ struct MppiFamily {
     static int check_draws(Batch* b, const char*, int, const int32_t*, const StepDraws& d, size_t) { return batch_check_draws(b, d); }
     static const float*& draws(Rec& q) { return q.samples; }
     static RolloutArgs context(const Batch* b) { return batch_args(b); }
-    static hipError_t constants(Batch* b, const int32_t*, int, unsigned char*) { return b->differ ? batch_flush_constants(b) : hipSuccess; }
+    // (the _hp form reads every problem's k too, from d_kh: entering it marks them all dirty, hyper_enter)
+    static hipError_t constants(Batch* b, const int32_t*, int, unsigned char*) {
+        return b->hyper ? batch_flush_kh(b) : b->differ ? batch_flush_constants(b) : hipSuccess;
+    }
     static void fill(const Batch* b, Rec& q, int p, int t) { batch_fill_record(b, q, p, t); }
     static hipError_t launch(Batch* b, const RolloutArgs& a, const Rec* d_rec, int n, const unsigned char*, int* launched) {
         return batch_launch_records(b, a, d_rec, n, launched);
@@ -1046,10 +1104,10 @@ struct MppiFamily {
     static constexpr bool unpublished_keeps_position = false;
     // the state of a problem: its current plan, its last output
     static BatchState state(Batch* b, int p) { return {{state_seg(b->unom(p, b->cur[(size_t)p]), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C)}}; }
-    static const char* per_problem_kernel(const Batch* b) {
-        return b->pred == CTK_PRED_GRU ? ctk_mppi_batch_gru_name(b->cfg.materialize_trajectories != 0, b->form, true)
-             : b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true)
-                                       : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    static const char* per_problem_kernel(const Batch* b) {     // (the _hp form stays the _hp form)
+        return b->pred == CTK_PRED_GRU ? ctk_mppi_batch_gru_name(b->cfg.materialize_trajectories != 0, b->form, true, b->hyper)
+             : b->pred == CTK_PRED_MLP ? ctk_mppi_batch_mlp_name(b->cfg.materialize_trajectories != 0, true, b->hyper)
+                                       : ctk_mppi_batch_name(b->env, b->cfg.materialize_trajectories != 0, true, b->hyper);
     }
 };
 
@@ -1129,6 +1187,12 @@ int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* c
     b->pred = pred; b->hid1 = hw1; b->hid2 = hw2; b->form = form;
     b->P = P; b->PC = P * b->C; b->blocks = blocks;
     b->mk = mppi_constants(b->cfg);
+    b->hyp.assign((size_t)n_problems * ctk_batch::HYP_ROW, 0.0f);
+    for (int p = 0; p < n_problems; ++p) {
+        hyper_from_config(b->cfg, b->hrow(p));
+        for (int c = 0; c < b->C; ++c) { b->hrow(p)[ctk_batch::HYP_LOW + c] = cfg->action_low[c]; b->hrow(p)[ctk_batch::HYP_HIGH + c] = cfg->action_high[c]; }
+    }
+    b->hdirty.assign((size_t)n_problems, 1);               // nothing in d_kh yet: the first step of the _hp form derives them all
     // Progress: the only workgroup of a launch that ever waits is block 0 of a problem, for workgroups of its own problem.  With at most
     // CUs / 2 problems in a launch the waiting workgroups cannot fill the machine (every CU holds at least one workgroup of this kernel),
     // so every other workgroup finds a place whatever the dispatch order.  CTK_BATCH_MAX_PROBLEMS_PER_LAUNCH (diagnostic) only lowers it.
@@ -1157,6 +1221,9 @@ int batch_create_in(ctk_batch* b, const char* who, int pred, const ctk_config* c
     HIP_CREATE(b->own.pinned_zero(&b->h_steps, Bz * sizeof(CtkBatchStep)));
     HIP_CREATE(b->own.dev_zero(&b->d_k, Bz * b->kstride, b->stream));
     HIP_CREATE(b->own.pinned_zero(&b->h_k, Bz * b->kstride));
+    b->khstride = ctk_mppi_batch_kh_stride(b->env);
+    HIP_CREATE(b->own.dev_zero(&b->d_kh, Bz * b->khstride, b->stream));
+    HIP_CREATE(b->own.pinned_zero(&b->h_kh, Bz * b->khstride));
     if (mlp || gru) {
         HIP_CREATE(b->own.dev_zero(&b->d_w, Bz * b->wtab * sizeof(float), b->stream));
         HIP_CREATE(b->own.pinned_zero(&b->h_w, Bz * b->wrow * sizeof(float)));
@@ -1219,6 +1286,82 @@ int mppi_batch_read(ctk_batch* b, const char* who, int problem, int buffer, floa
         src = b->unom(problem, b->cur[(size_t)problem]); n = (size_t)b->HC;
     }
     return batch_read_out(b, who, src, n, false, dst, cap);
+}
+
+// ---- per-problem hyper-parameters and limits (include/ctk_hip_hyper.h): the bodies of the three forms' entries; `who` is the entry's name ----
+// the rules ctk_batch_create applies to the same fields (check_config, batch_create_in), and finiteness
+int hyper_check(ctk_batch* b, const char* who, int hyper, float v, int p) {
+    static const char* const names[CTK_HYPER_COUNT] = {"cc_weight", "R", "LBD", "NU", "SQRTRHOINV"};
+    const char* why = !std::isfinite(v) ? ": a hyper-parameter is finite"
+                    : hyper == CTK_HYPER_LBD && !(v > 0.0f) ? ": MPPI needs LBD > 0"
+                    : hyper == CTK_HYPER_NU && v == 0.0f ? ": MPPI needs NU != 0" : nullptr;
+    if (!why) return CTK_OK;                           // the text is built for a refused value only
+    return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + why + " (" + names[hyper] + " == " + std::to_string(v) + " for problem " + std::to_string(p) +
+                 "); nothing was written");
+}
+// the first successful setter: the _hp form from now on (sticky)
+void hyper_enter(ctk_batch* b) {
+    if (b->hyper) return;
+    b->hyper = true;
+    b->dominant = MppiFamily::per_problem_kernel(b);
+    std::fill(b->dirty.begin(), b->dirty.end(), (unsigned char)1);            // every problem's k into d_kh, whatever d_k holds
+    std::fill(b->hdirty.begin(), b->hdirty.end(), (unsigned char)1);
+}
+// values == NULL: `all` for every listed problem (the whole-batch entry)
+int batch_set_hyper(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, int hyper, const float* values, float all) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (hyper < 0 || hyper >= CTK_HYPER_COUNT)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown hyper-parameter " + std::to_string(hyper) + " (enum ctk_hyper: cc_weight, R, LBD, NU, SQRTRHOINV)");
+    for (int j = 0; j < n; ++j)
+        if (int rc = hyper_check(b, who, hyper, values ? values[j] : all, ids ? ids[j] : j)) return rc;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        b->hrow(p)[hyper] = values ? values[j] : all;
+        b->hdirty[(size_t)p] = 1;                      // derived and copied ahead of the next step's launches (batch_flush_kh)
+    }
+    hyper_enter(b);
+    return CTK_OK;
+}
+int batch_problem_set_hyper(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, int hyper, const float* values) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL values (one value per listed problem)");
+    return batch_set_hyper(b, who, n_ids, ids, hyper, values, 0.0f);
+}
+int batch_problem_get_hyper(const ctk_batch* b, int problem, int hyper, float* out) {
+    if (!b || !out || problem < 0 || problem >= b->B || hyper < 0 || hyper >= CTK_HYPER_COUNT) return CTK_ERR_INVALID_ARGUMENT;
+    *out = b->hrow(problem)[hyper];
+    return CTK_OK;
+}
+int batch_problem_set_limits(ctk_batch* b, const char* who, int n_ids, const int32_t* ids, const float* low, const float* high) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (!low || !high) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL limits (one row of num_control_inputs values per listed problem)");
+    for (int i = 0; i < n * b->C; ++i) {
+        const bool finite = std::isfinite(low[i]) && std::isfinite(high[i]);
+        if (finite && low[i] <= high[i]) continue;
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + (finite ? ": action_low must be <= action_high for every control input" : ": a limit is finite") +
+                     " (" + std::to_string(low[i]) + ", " + std::to_string(high[i]) + " for problem " + std::to_string(ids ? ids[i / b->C] : i / b->C) +
+                     ", input " + std::to_string(i % b->C) + "); nothing was written");
+    }
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        for (int c = 0; c < b->C; ++c) {
+            b->hrow(p)[ctk_batch::HYP_LOW + c] = low[(size_t)j * b->C + c];
+            b->hrow(p)[ctk_batch::HYP_HIGH + c] = high[(size_t)j * b->C + c];
+        }
+        b->hdirty[(size_t)p] = 1;
+    }
+    hyper_enter(b);
+    return CTK_OK;
+}
+int batch_problem_get_limits(const ctk_batch* b, int problem, float* low, float* high) {
+    if (!b || !low || !high || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    std::memcpy(low, b->hrow(problem) + ctk_batch::HYP_LOW, (size_t)b->C * sizeof(float));
+    std::memcpy(high, b->hrow(problem) + ctk_batch::HYP_HIGH, (size_t)b->C * sizeof(float));
+    return CTK_OK;
 }
 
 }  // namespace
@@ -1285,8 +1428,9 @@ struct MlpFamily : MppiFamily {
 
 extern "C" {
 
-// create, samples_needed, step, reset and read of the family's three forms, FAM in {ctk_batch, ctk_mlp_batch, ctk_gru_batch}
-#define CTK_MPPI_ENTRIES(FAM, TRAIT, PRED)                                                                                                            \
+// create, samples_needed, step, reset and read of the family's three forms, FAM in {ctk_batch, ctk_mlp_batch, ctk_gru_batch}, and the six
+// hyper-parameter entries of include/ctk_hip_hyper.h under the prefix PROB of its per-problem entries
+#define CTK_MPPI_ENTRIES(FAM, PROB, TRAIT, PRED)                                                                                                            \
     int FAM##_create(const ctk_config* cfg, int n_problems, const uint64_t* seeds, FAM** out) {                                                       \
         return mppi_batch_create(#FAM "_create", PRED, cfg, n_problems, seeds, out);                                                                  \
     }                                                                                                                                                 \
@@ -1295,9 +1439,19 @@ extern "C" {
         return batch_step<TRAIT>(b, #FAM "_step", n_ids, ids, s, u_prev, StepDraws{samples, 0, samples_loc}, u_out);                                  \
     }                                                                                                                                                 \
     int FAM##_reset(FAM* b, int n_ids, const int32_t* ids) { return mppi_batch_reset(b, #FAM "_reset", n_ids, ids); }                                 \
-    int FAM##_read(FAM* b, int problem, int buffer, float* dst, size_t cap) { return mppi_batch_read(b, #FAM "_read", problem, buffer, dst, cap); }
+    int FAM##_read(FAM* b, int problem, int buffer, float* dst, size_t cap) { return mppi_batch_read(b, #FAM "_read", problem, buffer, dst, cap); } \
+    int PROB##_set_hyper(FAM* b, int n_ids, const int32_t* ids, int hyper, const float* values) {                                                     \
+        return batch_problem_set_hyper(b, #PROB "_set_hyper", n_ids, ids, hyper, values);                                                             \
+    }                                                                                                                                                 \
+    int PROB##_get_hyper(const FAM* b, int problem, int hyper, float* out) { return batch_problem_get_hyper(b, problem, hyper, out); }                \
+    int PROB##_set_limits(FAM* b, int n_ids, const int32_t* ids, const float* low, const float* high) {                                               \
+        return batch_problem_set_limits(b, #PROB "_set_limits", n_ids, ids, low, high);                                                               \
+    }                                                                                                                                                 \
+    int PROB##_get_limits(const FAM* b, int problem, float* low, float* high) { return batch_problem_get_limits(b, problem, low, high); }             \
+    int PROB##_hypers_differ(const FAM* b) { return b && b->hyper ? 1 : 0; }                                                                          \
+    int FAM##_set_hyper(FAM* b, int hyper, float value) { return batch_set_hyper(b, #FAM "_set_hyper", 0, nullptr, hyper, nullptr, value); }
 
-CTK_MPPI_ENTRIES(ctk_batch, MppiFamily, CTK_PRED_ODE)
+CTK_MPPI_ENTRIES(ctk_batch, ctk_problem, MppiFamily, CTK_PRED_ODE)
 CTK_BATCH_ENTRIES(ctk_batch, ctk_problem, MppiFamily)
 // the closed loop on the device (include/ctk_hip_run.h: ctk_batch_plant_* / ctk_batch_run) and the stochastic plant with the realised
 // cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes)
@@ -1305,7 +1459,7 @@ CTK_LOOP_ENTRIES(ctk_batch, MppiFamily)
 
 // the same under the MLP family's names: the network plans, the plant of its closed loop is the analytic CartPole with the problem's
 // parameter table (and the overrides set there)
-CTK_MPPI_ENTRIES(ctk_mlp_batch, MlpFamily, CTK_PRED_MLP)
+CTK_MPPI_ENTRIES(ctk_mlp_batch, ctk_mlp_problem, MlpFamily, CTK_PRED_MLP)
 CTK_BATCH_ENTRIES(ctk_mlp_batch, ctk_mlp_problem, MlpFamily)
 CTK_LOOP_ENTRIES(ctk_mlp_batch, MlpFamily)
 
@@ -1467,7 +1621,7 @@ extern "C" {
 
 // the MPPI family's entries under the GRU family's names; ctk_gru_batch_reset is ctk_reset of an MPPI handle, which leaves the hidden
 // state alone; the plant of the closed loop is the analytic CartPole with the problem's parameter table, as for the MLP batch
-CTK_MPPI_ENTRIES(ctk_gru_batch, GruFamily, CTK_PRED_GRU)
+CTK_MPPI_ENTRIES(ctk_gru_batch, ctk_gru_problem, GruFamily, CTK_PRED_GRU)
 CTK_BATCH_ENTRIES(ctk_gru_batch, ctk_gru_problem, GruFamily)
 CTK_LOOP_ENTRIES(ctk_gru_batch, GruFamily)
 

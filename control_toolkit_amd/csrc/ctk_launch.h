@@ -181,32 +181,45 @@ struct CtkBatchStep {
     float s[CTK_MAX_STATES];
     float u_prev[CTK_MAX_INPUTS];
 };
+// One problem's optimizer constants and input limits (include/ctk_hip_hyper.h: *_problem_set_hyper / *_problem_set_limits; kernels
+// ctk_mppi_batch_hp<ENV, LOG>, ctk_mppi_batch_mlp_hp<LOG>, ctk_mppi_batch_gru_hp<LOG, FORM>).  m is mppi_constants of the problem's
+// values, the function behind a handle's; lo / hi are what a handle's launch carries in RolloutArgs and in the update's arguments.  For
+// the _hp forms the per-problem array has elements of two parts, [K (ctk_mppi_batch_k_stride bytes) | CtkBatchHyper], at stride
+// ctk_mppi_batch_kh_stride(env): both parts are read by scalar loads on the record's id off ONE pointer, in one round trip.
+struct alignas(16) CtkBatchHyper {
+    MppiK m;
+    float lo[CTK_MAX_INPUTS], hi[CTK_MAX_INPUTS];
+};
+static_assert(sizeof(CtkBatchHyper) % 16 == 0, "the elements of the per-problem array stay 16-byte aligned");
+size_t ctk_mppi_batch_kh_stride(int env);
 // 0: a problem of these sizes runs in the batch kernel; else why not (1 throughput sizes, 2 more records / words than the FORM 0 tail takes,
 // 3 the records do not fit the tail's LDS staging, 4 LDS over 160 KiB); *lds_out: dynamic LDS of a launch, *blocks_out: workgroups per problem
 int ctk_mppi_batch_fit(int env, int N, int H, int P, size_t* lds_out, int* blocks_out);
 // per_problem: the form whose constants come from an array in device memory (ctk_mppi_batch_pp<ENV, LOG>), one element per problem
-const char* ctk_mppi_batch_name(int env, bool log, bool per_problem = false);
+// hyper: the form that also takes the optimizer constants and limits per problem (ctk_mppi_batch_hp<ENV, LOG>, CtkBatchHyper)
+const char* ctk_mppi_batch_name(int env, bool log, bool per_problem = false, bool hyper = false);
 // that array: element p at byte p * ctk_mppi_batch_k_stride(env) (sizeof(Env<env>::K) rounded up to 16), filled by
 // ctk_mppi_batch_derive_k = Env<env>::derive(params, dt, isteps), the function behind a handle's constants (double -> fp32 once)
 size_t ctk_mppi_batch_k_stride(int env);
 void ctk_mppi_batch_derive_k(int env, const float* params, float dt, int isteps, void* dst);
 // n_problems step records from `steps_dev` on, as ONE launch; a: the shared template (limits, sizes, interpolation table; s0 / u_prev / the
 // output pointers / seed / call come from the records and descriptors).  k_dev == nullptr: ctk_mppi_batch, every problem with the
-// constants of `params`; else ctk_mppi_batch_pp, problem p with element p of k_dev (`params` unused)
+// constants of `params`; else ctk_mppi_batch_pp, problem p with element p of k_dev (`params` unused).  hyper (needs k_dev):
+// ctk_mppi_batch_hp, k_dev has the two-part elements [K | CtkBatchHyper], whose second part stands in place of `m` and of a's limits
 hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                  const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
-                                 const void* k_dev = nullptr);
+                                 const void* k_dev = nullptr, bool hyper = false);
 // the MLP forms of the batch kernel (ctk_mppi.hip: ctk_mppi_batch_mlp<LOG> / ctk_mppi_batch_mlp_pp<LOG>; include/ctk_hip.h: ctk_mlp_batch_*):
 // CartPole's MLP predictor in the pair form (32 trajectories per workgroup), the same descriptors and step records, plus per-problem
 // weight tables w_dev [B][ctk_mppi_batch_mlp_table_floats()] in the per-lane layout of a handle's launch (ctk_api.hip: permute_mlp_weights).
 // fit: 0, or why not — 1 a handle of this N does not run the pair form (N > CTK_MPPI_PAIR_MAX_N, or the diagnostic switch
 // CTK_MPPI_NO_PAIR), 2 / 3 / 4 as ctk_mppi_batch_fit
 int ctk_mppi_batch_mlp_fit(int N, int H, int P, size_t* lds_out, int* blocks_out);
-const char* ctk_mppi_batch_mlp_name(bool log, bool per_problem = false);
+const char* ctk_mppi_batch_mlp_name(bool log, bool per_problem = false, bool hyper = false);
 size_t ctk_mppi_batch_mlp_table_floats();
 hipError_t ctk_launch_mppi_batch_mlp(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                      const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
-                                     const float* w_dev, const void* k_dev = nullptr);
+                                     const float* w_dev, const void* k_dev = nullptr, bool hyper = false);
 // the GRU forms of the batch kernel (ctk_mppi.hip: ctk_mppi_batch_gru<LOG, FORM> / ctk_mppi_batch_gru_pp<LOG, FORM>; include/ctk_hip.h:
 // ctk_gru_batch_*): CartPole's GRU predictor, 16 trajectories per workgroup, the same descriptors and step records, in the FORM a handle
 // of the configuration launches (0 or CTK_MPPI_FORM_WIDE_TAIL: mppi_form over the {value, seq} tail).  Problem p's block of w_dev, at
@@ -218,13 +231,13 @@ hipError_t ctk_launch_mppi_batch_mlp(hipStream_t st, const float* params, float 
 // fit: 0 for exactly the sizes at which a handle hands its block records over in-launch through the {value, seq} words, else why not —
 // 2 the records are too many for that tail (ctk_ll_records_ok), 3 they do not fit its LDS staging, 4 LDS over 160 KiB; *form_out: the FORM
 int ctk_mppi_batch_gru_fit(int N, int H, int P, size_t* lds_out, int* blocks_out, int* form_out);
-const char* ctk_mppi_batch_gru_name(bool log, int form, bool per_problem = false);
+const char* ctk_mppi_batch_gru_name(bool log, int form, bool per_problem = false, bool hyper = false);
 size_t ctk_mppi_batch_gru_table_floats();
 size_t ctk_mppi_batch_gru_hidden_floats();
 size_t ctk_mppi_batch_gru_block_floats();
 hipError_t ctk_launch_mppi_batch_gru(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                      const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log, int form,
-                                     const float* w_dev, const void* k_dev = nullptr);
+                                     const float* w_dev, const void* k_dev = nullptr, bool hyper = false);
 // ctk_sampled.hip: ctk_gru_advance_batch, the hidden-state advance behind a step of the GRU batch — one workgroup per step record, the
 // record's problem advanced by (the record's state, the problem's own last output desc[id].u_dev), in place in its block of w_dev
 hipError_t ctk_launch_gru_advance_batch(hipStream_t st, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_records, float* w_dev);

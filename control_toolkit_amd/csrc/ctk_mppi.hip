@@ -536,6 +536,58 @@ __global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_gru_pp(const CtkBat
 #include "ctk_mppi_body.inc"
 }
 
+// The PER-PROBLEM-HYPER-PARAMETER forms (include/ctk_hip_hyper.h: *_problem_set_hyper / *_problem_set_limits): the _pp forms with the
+// optimizer's own constants per problem as well.  The array in kdev's slot has, for these forms, elements of two parts — the problem's
+// derived constants K (CtkBatchKStride<ENV> bytes, as in _pp) and right behind them its CtkBatchHyper (ctk_launch.h: MppiK written by the
+// host with mppi_constants, as a handle's is, and the input limits), stride CtkBatchKhStride<ENV> — so `k`, `m` and the limits all hang
+// on the preloaded pointer and the record's id alone and are fetched in ONE scalar round trip, the one that fetches k in _pp
+// (ctk_mppi_batch_hyp.inc).  The by-value `m` is gone; the preloaded dwords are where they were.
+template <int ENV>
+struct CtkBatchKhStride {
+    static constexpr size_t value = CtkBatchKStride<ENV>::value + sizeof(CtkBatchHyper);
+};
+template <int ENV, bool LOG>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_hp(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                const InterpEntry* __restrict__ interp, const float* __restrict__ wperm,
+                                                                const unsigned char* __restrict__ kdev, int N_, int H_, int P_, uint32_t pmagic_,
+                                                                RolloutArgs a_tpl, FuseArgs fz_tpl) {
+    constexpr int PRED = CTK_PRED_ODE, FORM = 0;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+#include "ctk_mppi_batch_pro.inc"
+#include "ctk_mppi_batch_hyp.inc"
+#include "ctk_mppi_body.inc"
+}
+
+template <bool LOG>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_mlp_hp(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                    const InterpEntry* __restrict__ interp, const float* __restrict__ wbase,
+                                                                    const unsigned char* __restrict__ kdev, int N_, int H_, int P_, uint32_t pmagic_,
+                                                                    uint32_t wstride, RolloutArgs a_tpl, FuseArgs fz_tpl) {
+    constexpr int ENV = CTK_ENV_CARTPOLE, PRED = CTK_PRED_MLP_PAIR, FORM = 0;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+#include "ctk_mppi_batch_pro.inc"
+#include "ctk_mppi_batch_hyp.inc"
+    const float* wperm = wbase + (size_t)q.id * wstride;
+#include "ctk_mppi_body.inc"
+}
+
+template <bool LOG, int FORM>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_batch_gru_hp(const CtkBatchDesc* __restrict__ desc, const CtkBatchStep* __restrict__ steps,
+                                                                    const InterpEntry* __restrict__ interp, const float* __restrict__ wbase,
+                                                                    const unsigned char* __restrict__ kdev, int N_, int H_, int P_, uint32_t pmagic_,
+                                                                    uint32_t wstride, RolloutArgs a_tpl, FuseArgs fz_tpl) {
+    constexpr int ENV = CTK_ENV_CARTPOLE, PRED = CTK_PRED_GRU;
+    constexpr bool P2P = false;
+    extern __shared__ float lds[];
+#include "ctk_mppi_batch_pro.inc"
+#include "ctk_mppi_batch_hyp.inc"
+    const float* wperm = wbase + (size_t)q.id * wstride;
+    a_in.fast_cos_ok = (fabsf(q.s[2]) <= CTK_SINCOS_FAST_LIMIT && reinterpret_cast<const uint32_t*>(wperm)[GRU_BATCH_WORD] != 0u) ? 1 : 0;
+#include "ctk_mppi_body.inc"
+}
+
 // ---------------------------------------------------------------------------------------------
 // Throughput variant (ODE, N >= CTK_MPPI_THROUGHPUT_MIN_N): one wave per block, 64 trajectories, the
 // inputs formed inline in the recurrence instead of through an LDS input buffer.  LDS per block is the
@@ -1023,6 +1075,20 @@ const char* ctk_mppi_rollout_env_name(int env, bool log) {
     return ctk_kernel_name("ctk_mppi_rollout<%d, 0, %4$s, false>", env, 0, 0, log ? "true" : "false");
 }
 
+// the launches of the _hp forms (per-problem optimizer constants and limits).  LAYOUT STEERING, on purpose: these are plain functions
+// defined at the END of the file only so that their kernels are instantiated last and laid out in the code object behind every kernel
+// that was there before them — the existing kernels then keep their text to the byte, pc-relative displacements included (the check
+// that accompanied their introduction compared the disassembly of every existing symbol).  launch_batch_hp dispatches on the
+// environment a second time for the same reason.  Do not fold them back into the launchers above.
+static void launch_batch_hp(hipStream_t st, int env, dim3 grid, dim3 block, size_t lds, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev,
+                            const unsigned char* k_dev, uint32_t pmagic, const RolloutArgs& a, const FuseArgs& fz, bool log);
+static void launch_batch_mlp_hp(hipStream_t st, dim3 grid, dim3 block, size_t lds, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, const float* w_dev,
+                                const unsigned char* k_dev, uint32_t pmagic, uint32_t wstride, const RolloutArgs& a,
+                                const FuseArgs& fz, bool log);
+static void launch_batch_gru_hp(hipStream_t st, dim3 grid, dim3 block, size_t lds, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, const float* w_dev,
+                                const unsigned char* k_dev, uint32_t pmagic, uint32_t wstride, const RolloutArgs& a,
+                                const FuseArgs& fz, bool log, int form);
+
 // ---- the batch form (ctk_mppi_batch): FORM 0 of the 4-wave kernel with the {value, seq} tail, nothing else
 int ctk_mppi_batch_fit(int env, int N, int H, int P, size_t* lds_out, int* blocks_out) {
     int C = 1;
@@ -1038,8 +1104,14 @@ int ctk_mppi_batch_fit(int env, int N, int H, int P, size_t* lds_out, int* block
     if (lds > 160 * 1024) return 4;
     return 0;
 }
-const char* ctk_mppi_batch_name(int env, bool log, bool per_problem) {
-    return ctk_kernel_name(per_problem ? "ctk_mppi_batch_pp<%d, %4$s>" : "ctk_mppi_batch<%d, %4$s>", env, 0, 0, log ? "true" : "false");
+const char* ctk_mppi_batch_name(int env, bool log, bool per_problem, bool hyper) {
+    return ctk_kernel_name(hyper ? "ctk_mppi_batch_hp<%d, %4$s>" : per_problem ? "ctk_mppi_batch_pp<%d, %4$s>" : "ctk_mppi_batch<%d, %4$s>", env, 0, 0,
+                           log ? "true" : "false");
+}
+size_t ctk_mppi_batch_kh_stride(int env) {
+    size_t stride = 0;
+    CTK_FOR_ENV(env, EV, { stride = CtkBatchKhStride<EV>::value; });
+    return stride;
 }
 size_t ctk_mppi_batch_k_stride(int env) {
     size_t stride = 0;
@@ -1054,10 +1126,11 @@ void ctk_mppi_batch_derive_k(int env, const float* params, float dt, int isteps,
 }
 
 hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
-                                 const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log, const void* k_dev) {
+                                 const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log, const void* k_dev,
+                                 bool hyper) {
     size_t lds;
     int blocks;
-    if (n_problems < 1 || ctk_mppi_batch_fit(env, a.N, a.H, a.P, &lds, &blocks) != 0) return hipErrorInvalidValue;
+    if (n_problems < 1 || (hyper && !k_dev) || ctk_mppi_batch_fit(env, a.N, a.H, a.P, &lds, &blocks) != 0) return hipErrorInvalidValue;
     const dim3 grid(blocks, n_problems), block(MPPI_BLOCK);
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
@@ -1065,7 +1138,9 @@ hipError_t ctk_launch_mppi_batch(hipStream_t st, int env, const float* params, f
         fz.mode = 1; fz.stage_ok = 1;                  // the pointers and the sequence number are the descriptors' / the step records'
         fz.up = mppi_update_args(a, E::C, nullptr, nullptr, nullptr, nullptr, 0u);
         const uint32_t pmagic = ctk_magic_of(a.P * E::C);
-        if (k_dev) {                                   // per-problem constants: the array the host derived (ctk_mppi_batch_derive_k)
+        if (hyper) {                                   // ... with each problem's optimizer constants and limits behind them (ctk_mppi_batch_kh_stride)
+            launch_batch_hp(st, EV, grid, block, lds, desc_dev, steps_dev, static_cast<const unsigned char*>(k_dev), pmagic, a, fz, log);
+        } else if (k_dev) {                            // per-problem constants: the array the host derived (ctk_mppi_batch_derive_k)
             ctk_with_bool(log, [&](auto log_c) {
                 hipLaunchKernelGGL((ctk_mppi_batch_pp<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp,
                                    static_cast<const float*>(nullptr), static_cast<const unsigned char*>(k_dev), a.N, a.H, a.P, pmagic, a, m, fz);
@@ -1095,23 +1170,25 @@ int ctk_mppi_batch_mlp_fit(int N, int H, int P, size_t* lds_out, int* blocks_out
     if (lds > 160 * 1024) return 4;
     return 0;
 }
-const char* ctk_mppi_batch_mlp_name(bool log, bool per_problem) {
-    return per_problem ? (log ? "ctk_mppi_batch_mlp_pp<true>" : "ctk_mppi_batch_mlp_pp<false>") : (log ? "ctk_mppi_batch_mlp<true>" : "ctk_mppi_batch_mlp<false>");
+const char* ctk_mppi_batch_mlp_name(bool log, bool per_problem, bool hyper) {
+    return hyper ? (log ? "ctk_mppi_batch_mlp_hp<true>" : "ctk_mppi_batch_mlp_hp<false>") : per_problem ? (log ? "ctk_mppi_batch_mlp_pp<true>" : "ctk_mppi_batch_mlp_pp<false>") : (log ? "ctk_mppi_batch_mlp<true>" : "ctk_mppi_batch_mlp<false>");
 }
 size_t ctk_mppi_batch_mlp_table_floats() { return (size_t)64 * (MLP_FWD_PER_LANE + MLP_BWD_PER_LANE); }
 
 hipError_t ctk_launch_mppi_batch_mlp(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                      const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log,
-                                     const float* w_dev, const void* k_dev) {
+                                     const float* w_dev, const void* k_dev, bool hyper) {
     size_t lds;
     int blocks;
-    if (n_problems < 1 || w_dev == nullptr || ctk_mppi_batch_mlp_fit(a.N, a.H, a.P, &lds, &blocks) != 0) return hipErrorInvalidValue;
+    if (n_problems < 1 || w_dev == nullptr || (hyper && !k_dev) || ctk_mppi_batch_mlp_fit(a.N, a.H, a.P, &lds, &blocks) != 0) return hipErrorInvalidValue;
     const dim3 grid(blocks, n_problems), block(MPPI_BLOCK);
     FuseArgs fz{};                                     // as ctk_launch_mppi_batch: merge + update by block 0 of every problem
     fz.mode = 1; fz.stage_ok = 1;
     fz.up = mppi_update_args(a, CTK_C, nullptr, nullptr, nullptr, nullptr, 0u);
     const uint32_t pmagic = ctk_magic_of(a.P), wstride = (uint32_t)ctk_mppi_batch_mlp_table_floats();
-    if (k_dev) {
+    if (hyper) {
+        launch_batch_mlp_hp(st, grid, block, lds, desc_dev, steps_dev, w_dev, static_cast<const unsigned char*>(k_dev), pmagic, wstride, a, fz, log);
+    } else if (k_dev) {
         ctk_with_bool(log, [&](auto log_c) {
             hipLaunchKernelGGL((ctk_mppi_batch_mlp_pp<decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp, w_dev,
                                static_cast<const unsigned char*>(k_dev), a.N, a.H, a.P, pmagic, wstride, a, m, fz);
@@ -1141,8 +1218,8 @@ int ctk_mppi_batch_gru_fit(int N, int H, int P, size_t* lds_out, int* blocks_out
     if (form_out) *form_out = mppi_form(CTK_PRED_GRU, blocks, P, true);
     return 0;
 }
-const char* ctk_mppi_batch_gru_name(bool log, int form, bool per_problem) {
-    return ctk_kernel_name(per_problem ? "ctk_mppi_batch_gru_pp<%4$s, %1$d>" : "ctk_mppi_batch_gru<%4$s, %1$d>", form, 0, 0, log ? "true" : "false");
+const char* ctk_mppi_batch_gru_name(bool log, int form, bool per_problem, bool hyper) {
+    return ctk_kernel_name(hyper ? "ctk_mppi_batch_gru_hp<%4$s, %1$d>" : per_problem ? "ctk_mppi_batch_gru_pp<%4$s, %1$d>" : "ctk_mppi_batch_gru<%4$s, %1$d>", form, 0, 0, log ? "true" : "false");
 }
 size_t ctk_mppi_batch_gru_table_floats() { return (size_t)GRU_TABLE_FLOATS; }
 size_t ctk_mppi_batch_gru_hidden_floats() { return (size_t)GRU_HIDDEN_FLOATS; }
@@ -1150,15 +1227,19 @@ size_t ctk_mppi_batch_gru_block_floats() { return (size_t)GRU_BATCH_BLOCK_FLOATS
 
 hipError_t ctk_launch_mppi_batch_gru(hipStream_t st, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
                                      const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, int n_problems, bool log, int form,
-                                     const float* w_dev, const void* k_dev) {
+                                     const float* w_dev, const void* k_dev, bool hyper) {
     size_t lds;
     int blocks, fit_form;
-    if (n_problems < 1 || w_dev == nullptr || ctk_mppi_batch_gru_fit(a.N, a.H, a.P, &lds, &blocks, &fit_form) != 0 || form != fit_form) return hipErrorInvalidValue;
+    if (n_problems < 1 || w_dev == nullptr || (hyper && !k_dev) || ctk_mppi_batch_gru_fit(a.N, a.H, a.P, &lds, &blocks, &fit_form) != 0 || form != fit_form) return hipErrorInvalidValue;
     const dim3 grid(blocks, n_problems), block(MPPI_BLOCK);
     FuseArgs fz{};                                     // as ctk_launch_mppi_batch: merge + update by block 0 of every problem
     fz.mode = 1; fz.stage_ok = 1;
     fz.up = mppi_update_args(a, CTK_C, nullptr, nullptr, nullptr, nullptr, 0u);
     const uint32_t pmagic = ctk_magic_of(a.P), wstride = (uint32_t)GRU_BATCH_BLOCK_FLOATS;
+    if (hyper) {
+        launch_batch_gru_hp(st, grid, block, lds, desc_dev, steps_dev, w_dev, static_cast<const unsigned char*>(k_dev), pmagic, wstride, a, fz, log, form);
+        return hipGetLastError();
+    }
     with_mppi_form<false>(form, [&](auto form_c) {
         ctk_with_bool(log, [&](auto log_c) {
             constexpr int FV = decltype(form_c)::value;
@@ -1226,4 +1307,33 @@ hipError_t ctk_launch_mppi_update(hipStream_t st, const float* parts, int n_part
                        parts, n_parts, n_parts, P, neg_inv_lbd, (float*)nullptr,
                        MppiUpdateArgs{nullptr, nullptr, nullptr, nullptr, H, interp, u_nom_in, u_nom_out, lo, hi, u_dev, u_host, seq}, stage ? 1 : 0);
     return hipGetLastError();
+}
+
+// ---- the launches of the _hp forms of the batch kernels (declared above ctk_mppi_batch_fit): the _pp launches without `m` (k_dev: the array of two-part elements)
+static void launch_batch_hp(hipStream_t st, int env, dim3 grid, dim3 block, size_t lds, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev,
+                            const unsigned char* k_dev, uint32_t pmagic, const RolloutArgs& a, const FuseArgs& fz, bool log) {
+    CTK_FOR_ENV(env, EV, {
+        ctk_with_bool(log, [&](auto log_c) {
+            hipLaunchKernelGGL((ctk_mppi_batch_hp<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp,
+                               static_cast<const float*>(nullptr), k_dev, a.N, a.H, a.P, pmagic, a, fz);
+        });
+    });
+}
+static void launch_batch_mlp_hp(hipStream_t st, dim3 grid, dim3 block, size_t lds, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, const float* w_dev,
+                                const unsigned char* k_dev, uint32_t pmagic, uint32_t wstride, const RolloutArgs& a,
+                                const FuseArgs& fz, bool log) {
+    ctk_with_bool(log, [&](auto log_c) {
+        hipLaunchKernelGGL((ctk_mppi_batch_mlp_hp<decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.interp, w_dev, k_dev, a.N, a.H,
+                           a.P, pmagic, wstride, a, fz);
+    });
+}
+static void launch_batch_gru_hp(hipStream_t st, dim3 grid, dim3 block, size_t lds, const CtkBatchDesc* desc_dev, const CtkBatchStep* steps_dev, const float* w_dev,
+                                const unsigned char* k_dev, uint32_t pmagic, uint32_t wstride, const RolloutArgs& a,
+                                const FuseArgs& fz, bool log, int form) {
+    with_mppi_form<false>(form, [&](auto form_c) {
+        ctk_with_bool(log, [&](auto log_c) {
+            hipLaunchKernelGGL((ctk_mppi_batch_gru_hp<decltype(log_c)::value, decltype(form_c)::value>), grid, block, lds, st, desc_dev, steps_dev,
+                               a.interp, w_dev, k_dev, a.N, a.H, a.P, pmagic, wstride, a, fz);
+        });
+    });
 }

@@ -800,4 +800,6 @@ int ctk_gru_batch_fit(int num_rollouts, int mpc_horizon, int period_interpolatio
 #include "ctk_hip_loop.h"
 /* ... and for the GRU batch */
 #include "ctk_hip_gru.h"
+/* per-problem MPPI hyper-parameters and input limits of the three MPPI batches */
+#include "ctk_hip_hyper.h"
 #endif /* CTK_HIP_H */
