@@ -28,6 +28,8 @@ class optimizer_mppi_hip(template_optimizer):
         # optional key of the optimizer entry (swallowed by **kwargs in the reference's constructors): resident_idle_us > 0 serves the steps
         # from a kernel that stays on the device (include/ctk_hip.h: ctk_resident_*); it leaves by itself after that long without a step
         self.resident_idle_us = float(kwargs.get("resident_idle_us", 0.0) or 0.0)
+        # optional key `launch_ahead: false`: never launch the next step's kernel ahead (include/ctk_hip_ahead.h; on by default)
+        self.launch_ahead = bool(kwargs.get("launch_ahead", True))
 
     def configure(self, num_states: int, num_control_inputs: int, dt: float, predictor_specification: str, **kwargs):
         super().configure(num_states=num_states, num_control_inputs=num_control_inputs, default_configure=False)
@@ -38,6 +40,8 @@ class optimizer_mppi_hip(template_optimizer):
         self.number_of_interpolation_inducing_points = self.engine.inducing_points()
         if self.resident_idle_us > 0.0:
             self.engine.resident_enable(True, self.resident_idle_us)
+        if not self.launch_ahead:
+            self.engine.launch_ahead(False)
         self.optimizer_reset()
 
     def step(self, s: np.ndarray, time=None):

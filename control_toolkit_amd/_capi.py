@@ -231,6 +231,26 @@ for _batch, _problem in _BATCH_FAMILIES[:3]:
     HYPER_SYMBOLS[f"{_batch}_set_hyper"] = (C.c_int, [_H, C.c_int, C.c_float])
 
 
+# the launched-ahead form of the MPPI step (include/ctk_hip_ahead.h, which ctk_hip.h includes): a table of its own, bound with the others
+class AheadRule(C.Structure):
+    _fields_ = [("streak", C.c_int32), ("armed", C.c_int32), ("untaken", C.c_int32), ("arms", C.c_int32)]
+
+
+class AheadCounters(C.Structure):
+    _fields_ = [("launched", C.c_uint64), ("taken", C.c_uint64), ("untaken", C.c_uint64), ("cancelled", C.c_uint64), ("arms", C.c_uint64),
+                ("armed", C.c_int32), ("pending", C.c_int32), ("available", C.c_int32), ("on", C.c_int32)]
+
+
+AHEAD_ARM_AFTER, AHEAD_DISARM_AFTER, AHEAD_DEFAULT_FUSE_US = 8, 2, 20.0
+AHEAD_NONE, AHEAD_TAKEN, AHEAD_UNTAKEN = 0, 1, 2
+AHEAD_SYMBOLS = {
+    "ctk_ahead_rule_step": (C.c_int, [C.POINTER(AheadRule), C.c_int, C.c_double, C.c_double, C.c_int]),
+    "ctk_ahead_enable": (C.c_int, [_H, C.c_int, C.c_double]),
+    "ctk_ahead_stats": (C.c_int, [_H, C.POINTER(AheadCounters), C.POINTER(C.c_double)]),
+    "ctk_ahead_kernel": (C.c_char_p, [_H]),
+}
+
+
 # user environments (include/ctk_user_env.h): name -> path of the library that was compiled with that model (control_toolkit_amd/build_env.py:
 # register_environment); their environment id inside that library is CTK_ENV_USER
 USER_ENVIRONMENTS = {}
@@ -274,7 +294,7 @@ def _bind_library(path: str):
     except OSError as e:
         raise CtkError(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()) + list(LOOP_SYMBOLS.items()) + \
-            list(GRU_LOOP_SYMBOLS.items()) + list(HYPER_SYMBOLS.items()):
+            list(GRU_LOOP_SYMBOLS.items()) + list(HYPER_SYMBOLS.items()) + list(AHEAD_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctk_abi_version() != 6:
@@ -732,6 +752,24 @@ class CtkEngine:
         a, b, r, m = C.c_uint64(0), C.c_uint64(0), C.c_int(0), C.c_int(0)
         self._check(self._lib.ctk_resident_stats(self._h, C.byref(a), C.byref(b), C.byref(r), C.byref(m)))
         return {"launches": int(a.value), "steps": int(b.value), "running": bool(r.value), "mailbox": "device memory" if m.value else "pinned host memory"}
+
+    # launched-ahead MPPI step (include/ctk_hip_ahead.h): in a tight loop the kernel of the next step is launched while this one runs and
+    # waits, for at most fuse_us, for its request.  On by default where the handle can use it; the results do not depend on it.
+    def launch_ahead(self, on: bool = True, fuse_us: float = 0.0):
+        """fuse_us <= 0 keeps the current fuse (default AHEAD_DEFAULT_FUSE_US)"""
+        self._check(self._lib.ctk_ahead_enable(self._h, 1 if on else 0, float(fuse_us)))
+
+    def ahead_stats(self) -> dict:
+        c, f = AheadCounters(), C.c_double()
+        self._check(self._lib.ctk_ahead_stats(self._h, C.byref(c), C.byref(f)))
+        out = {n: int(getattr(c, n)) for n, _ in AheadCounters._fields_}
+        out["fuse_us"] = f.value
+        return out
+
+    def ahead_kernel(self) -> str:
+        """the kernel that serves the steps launched ahead, as a kernel trace prints it; "" until one was served (dominant_kernel() keeps
+        naming the launched kernel)"""
+        return (self._lib.ctk_ahead_kernel(self._h) or b"").decode()
 
     # device-resident step log (include/ctk_hip.h: ctk_log_*)
     def log_enable(self, capacity_steps: int):

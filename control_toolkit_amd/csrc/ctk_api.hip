@@ -154,6 +154,21 @@ struct ctk_handle {
     std::unordered_map<const float*, const float*> res_follow;   // sample buffer -> the buffer that followed it last time
     const float* res_prev_samples = nullptr;
     bool res_readahead = false;           // ctk_resident_enable(h, 2, ...): the caller's sample buffers are immutable while enabled, so they may be read ahead
+    // the launched-ahead form (include/ctk_hip_ahead.h; ctk_mppi.hip: ctk_mppi_ahead)
+    bool ah_on = true;                    // the switch (ctk_ahead_enable; CTK_MPPI_NO_AHEAD)
+    bool ah_avail = false;                // sizes, stream and mailbox allow the form (ahead_setup, at creation)
+    bool ah_pending = false;              // a kernel is queued that waits for request ah_req
+    bool ah_have_result = false;
+    double ah_fuse_us = CTK_AHEAD_DEFAULT_FUSE_US;
+    CtkAheadBox* ah_box = nullptr;        // fine-grained device memory the host stores into through the BAR
+    uint32_t* ah_state = nullptr;         // pinned host memory: the pending kernel's state word (ctk_launch.h: ctk_ahead_state)
+    uint32_t* ah_state_dev = nullptr;
+    uint32_t* d_ah_relay = nullptr;
+    uint32_t ah_req = 0;                  // last request number issued to a launch
+    int ah_outcome = CTK_AHEAD_NONE;      // fate of the launch the previous step issued, for the arming rule
+    ctk_ahead_rule ah_rule{};
+    std::chrono::steady_clock::time_point ah_t_result{};   // when the previous step's result was seen
+    uint64_t ah_launched = 0, ah_taken = 0, ah_untaken = 0, ah_cancelled = 0;
     // every device and pinned allocation of the handle, entered where it is made (ctk_host.h); behind the fields the step path reads
     Owner own;
     ~ctk_handle();                        // ctk_destroy is `delete h`, and so is the end of a failed creation
@@ -776,6 +791,28 @@ int guarded(ctk_handle* h, F&& body) {
     return rc;
 }
 
+// ---- the launched-ahead form of the MPPI step (ctk_mppi.hip: ctk_mppi_ahead; include/ctk_hip_ahead.h) ---------------------------
+// Cancels a queued kernel (cmd = EXIT under the number it waits for: it leaves at once, having written nothing) and waits for it; every
+// API entry other than an eligible ctk_step does this first (RES_Q), so that nothing of the handle is ever queued behind it, nothing
+// reads what it might still write, and nothing it was launched with (sequence number, Philox position, plan buffer, constants) changes
+// under it.
+int ahead_quiesce(ctk_handle* h) {
+    if (!h->ah_pending) return CTK_OK;
+    if (*const_cast<volatile uint32_t*>(h->ah_state) != ctk_ahead_state(h->ah_req, CTK_RES_LEFT)) {
+        volatile CtkAheadBox* b = h->ah_box;
+        b->cmd = CTK_RES_CMD_EXIT;
+        b->tail = h->ah_req;
+        __builtin_ia32_sfence();                         // (write-combined stores into device memory: payload before the number)
+        b->req = h->ah_req;
+        __builtin_ia32_sfence();
+    }
+    h->ah_pending = false;
+    h->ah_outcome = CTK_AHEAD_NONE;
+    ++h->ah_cancelled;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // bounded on the device side: EXIT, or the fuse
+    return CTK_OK;
+}
+
 // ---- the resident form of the MPPI step (ctk_mppi.hip: ctk_mppi_resident) -------------------------------------------------------
 // Ends a running resident kernel at once (cmd = EXIT) and waits for it; every API entry other than ctk_step does this first, so that
 // nothing is ever queued behind it and nothing reads state it is still writing.
@@ -879,7 +916,8 @@ int resident_step(ctk_handle* h, const float* s, const float* u_prev, const floa
     return finish_step(h, u_out);        // sees the result at once; error word, sequence / Philox counters as for a launched step
 }
 
-#define RES_Q(h) do { if ((h) != nullptr && (h)->res_running) { const int _q = resident_quiesce(h); if (_q != CTK_OK) return _q; } } while (0)
+#define RES_Q(h) do { if ((h) != nullptr && (h)->ah_pending) { const int _a = ahead_quiesce(h); if (_a != CTK_OK) return _a; }                  \
+                      if ((h) != nullptr && (h)->res_running) { const int _q = resident_quiesce(h); if (_q != CTK_OK) return _q; } } while (0)
 
 int check_predictor(ctk_handle* h) {
     if (h->cfg.predictor != CTK_PRED_ODE && !h->have_weights)
@@ -940,6 +978,127 @@ int mppi_rollout(ctk_handle* h, const float* s, const float* u_prev, const float
     CTK_HSTAMP(h, 2);
     if (ran != h->dominant_ran) { h->dominant_ran = ran; h->dominant = ran; }   // string literals: pointer compare
     return CTK_OK;
+}
+
+// ---- the launched-ahead form: the step path (include/ctk_hip_ahead.h) ----------------------------------------------
+// CTK_MPPI_NO_AHEAD: diagnostic switch, read once per process — no handle ever launches ahead
+bool ahead_off_for_process() {
+    static const bool off = std::getenv("CTK_MPPI_NO_AHEAD") != nullptr;
+    return off;
+}
+
+// Once, at creation: can this handle use the form at all, and if so its mailbox (fine-grained device memory the host can store into,
+// probed as ctk_resident_enable probes its own), state word and relay word.  Where anything is missing the form is simply off.
+void ahead_setup(ctk_handle* h) {
+    h->ah_avail = false;
+    // CTK_MPPI_AHEAD_FUSE_US: diagnostic switch — the fuse a handle starts with (measuring the candidates under an unchanged caller)
+    if (const char* f = std::getenv("CTK_MPPI_AHEAD_FUSE_US")) { const double v = std::atof(f); if (v >= 1.0 && v <= 1.0e4) h->ah_fuse_us = v; }
+    if (ahead_off_for_process() || h->cfg.optimizer != CTK_OPT_MPPI || h->cfg.predictor != CTK_PRED_ODE || h->cfg.materialize_trajectories ||
+        !h->own_stream || h->d_ll == nullptr || !mppi_can_fuse(h) || (h->generic && !mppi_env_kernel(h)) ||
+        !ctk_mppi_ahead_ok(h->env, h->N, h->H, h->P))
+        return;
+    int large_bar = 0;                                  // without a large BAR the host cannot address device memory at all: do not touch it
+    if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->cfg.device) != hipSuccess || !large_bar) { (void)hipGetLastError(); return; }
+    void* vram = nullptr;
+    if (hipExtMallocWithFlags(&vram, 4096, hipDeviceMallocFinegrained) != hipSuccess || !vram) { (void)hipGetLastError(); return; }
+    bool local = false;
+    if (hipMemset(vram, 0, 4096) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
+        volatile uint32_t* pv = static_cast<volatile uint32_t*>(vram);
+        for (int i = 0; i < 32; ++i) pv[i] = 0xA4EAD000u + (uint32_t)i;
+        __builtin_ia32_sfence();
+        uint32_t back[32] = {};
+        if (hipMemcpy(back, vram, sizeof(back), hipMemcpyDeviceToHost) == hipSuccess) {
+            local = true;
+            for (int i = 0; i < 32; ++i) local = local && back[i] == 0xA4EAD000u + (uint32_t)i;
+        }
+    }
+    if (!local || hipMemset(vram, 0, 4096) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(vram); (void)hipGetLastError(); return; }
+    h->own.own_dev(vram);
+    h->ah_box = static_cast<CtkAheadBox*>(vram);
+    h->d_ah_relay = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(vram) + 2048);     // (the same block: zeroed above, never a request number)
+    if (h->own.pinned_zero(&h->ah_state, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&h->ah_state_dev, h->ah_state, 0) != hipSuccess) { (void)hipGetLastError(); return; }
+    h->ah_avail = true;
+}
+
+bool ahead_eligible(const ctk_handle* h, int samples_loc) {
+    return h->ah_avail && h->ah_on && h->own_stream && samples_loc != CTK_LOC_HOST && h->log_cap == 0 && !h->prof && !h->mppi_pending &&
+           !h->res_enabled && !h->p2p_connected;
+}
+
+// the kernel of the NEXT step, behind this step's on the stream: called between this step's launch (or request) and finish_step, so
+// h->seq / h->call are still this step's and h->cur is already the next step's
+int ahead_launch(ctk_handle* h) {
+    float zs[CTK_MAX_STATES] = {};
+    RolloutArgs a = make_args(h, zs, nullptr, h->N, h->P);      // s0 / u_prev / samples come from the mailbox; u_prev_dev = d_u unless the request says otherwise
+    a.call = h->call + 1u;
+    MppiFuse fz;
+    fz.mode = 1; fz.counter = h->d_counter; fz.ll = h->d_ll;
+    fz.u_nom_out = h->d_unom[h->cur ^ 1]; fz.u_dev = h->d_u; fz.u_host = h->h_u_dev; fz.seq = h->seq + 1u;
+    CtkAheadGate g{};
+    g.box = h->ah_box; g.state = h->ah_state_dev; g.relay = h->d_ah_relay; g.req = ++h->ah_req;
+    g.fuse_ticks = (unsigned long long)(h->ah_fuse_us * 100.0);   // wall_clock64: 100 MHz
+    HIP_TRY(h, ctk_launch_mppi_ahead(h->stream, h->env, h->params, h->cfg.dt, h->cfg.intermediate_steps, a, h->mk, h->d_unom[h->cur], h->d_parts, fz, g));
+    h->ah_pending = true;
+    ++h->ah_launched;
+    return CTK_OK;
+}
+
+// One eligible MPPI step.  A queued kernel gets its request and the host waits for workgroup 0's word on it — taken, or left on its
+// fuse — BEFORE the next kernel is launched: the launch call still runs under this step's kernel (it has ~10 us to go), and a launch
+// that assumed a served step never has to be taken back.  Not taken: the step is launched as ever, under the next sequence number
+// (workgroups other than 0 may have rolled out under the old one, ctk_mppi.hip).
+int ahead_step(ctk_handle* h, const float* s, const float* u_prev, const float* samples, int samples_loc, float* u_out) {
+    const auto t_in = std::chrono::steady_clock::now();
+    const double gap_us = h->ah_have_result ? std::chrono::duration<double, std::micro>(t_in - h->ah_t_result).count() : -1.0;
+    bool served = false;
+    if (h->ah_pending) {
+        const float* d_s = nullptr;
+        if (int rc = resolve_samples(h, samples, samples_loc, (size_t)h->N * h->PC, &d_s)) { (void)ahead_quiesce(h); return rc; }
+        volatile uint32_t* st = h->ah_state;
+        const uint32_t R = h->ah_req, taken = ctk_ahead_state(R, CTK_RES_RUNNING), left = ctk_ahead_state(R, CTK_RES_LEFT);
+        uint32_t seen = *st;
+        if (seen != left) {
+            volatile CtkAheadBox* b = h->ah_box;
+            b->cmd = CTK_RES_CMD_STEP; b->dev_uprev = u_prev ? 0u : 1u; b->samples = d_s;
+            for (int i = 0; i < h->S; ++i) b->s[i] = s[i];
+            for (int c = 0; c < h->C; ++c) b->u_prev[c] = u_prev ? u_prev[c] : 0.0f;
+            b->tail = R;
+            __builtin_ia32_sfence();                            // payload before the number (write-combined stores into device memory)
+            b->req = R;
+            __builtin_ia32_sfence();
+            CTK_HSTAMP(h, 1);                                   // (diagnostic build: "request stored" stands where "launch call begins" stands)
+            const auto t0 = std::chrono::steady_clock::now();
+            for (uint64_t spin = 1;; ++spin) {
+                seen = *st;
+                if (seen == taken || seen == left) break;
+                if ((spin & 4095) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
+                    HIP_TRY(h, hipStreamSynchronize(h->stream));    // a device fault surfaces here; else the kernel has ended either way
+                    seen = *st;
+                    if (seen != taken) seen = left;
+                    break;
+                }
+                __builtin_ia32_pause();
+            }
+            CTK_HSTAMP(h, 2);
+        }
+        h->ah_pending = false;
+        served = seen == taken;
+        h->ah_outcome = served ? CTK_AHEAD_TAKEN : CTK_AHEAD_UNTAKEN;
+        if (served) ++h->ah_taken;
+        else { ++h->ah_untaken; ++h->seq; }
+    }
+    const bool armed = ctk_ahead_rule_step(&h->ah_rule, 1, gap_us, h->ah_fuse_us, h->ah_outcome) != 0;
+    h->ah_outcome = CTK_AHEAD_NONE;
+    // (ctk_dominant_kernel keeps naming the launched kernel of the handle's configuration — the kernel a timed launch runs, the same
+    //  body text; ctk_ahead_kernel names the kernel that serves the steps launched ahead)
+    if (!served) if (int rc = mppi_rollout(h, s, u_prev, samples, samples_loc, 1, nullptr)) return rc;
+    h->cur ^= 1;
+    if (armed) if (int rc = ahead_launch(h)) return rc;
+    const int rc = finish_step(h, u_out);
+    h->ah_t_result = std::chrono::steady_clock::now();
+    h->ah_have_result = true;
+    return rc;
 }
 
 // reduce the block records to <= 2048 records (hierarchical when the grid was huge)
@@ -1333,6 +1492,11 @@ int fill_const(ctk_handle* h, float* d, float v, int n) {
 inline ctk_handle::~ctk_handle() {
     if (!stream && own.empty() && events.empty() && p2p_world == 0) return;
     hipSetDevice(cfg.device);
+    if (ah_launched && std::getenv("CTK_AHEAD_TRACE"))   // diagnostic: the counters of a caller that cannot be asked (ctk_ahead_stats has them)
+        fprintf(stderr, "[ctk ahead] fuse %.0f us: launched %llu taken %llu untaken %llu cancelled %llu pending %d arms %d\n", ah_fuse_us,
+                (unsigned long long)ah_launched, (unsigned long long)ah_taken, (unsigned long long)ah_untaken, (unsigned long long)ah_cancelled,
+                ah_pending ? 1 : 0, (int)ah_rule.arms);
+    (void)ahead_quiesce(this);
     (void)resident_quiesce(this);
     hipStreamSynchronize(stream);   // also correct for the null (default) stream handed in by ctk_set_stream
     for (auto& e : events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
@@ -1531,6 +1695,7 @@ int ctk_create(const ctk_config* cfg, ctk_handle** out) {
     if (cfg->optimizer != CTK_OPT_RPGD)
         if (int rc = ctk_reset(h, nullptr, CTK_LOC_NONE)) { g_create_error = h->err; return rc; }
     HIP_CREATE(hipStreamSynchronize(h->stream));
+    ahead_setup(h);
     *out = made.release();
     return CTK_OK;
 }
@@ -1741,6 +1906,7 @@ int ctk_rng_get_position(const ctk_handle* h, uint32_t* call) {
 
 int ctk_rng_set_position(ctk_handle* h, uint32_t call) {
     if (!h) return CTK_ERR_INVALID_ARGUMENT;
+    RES_Q(h);                                             // (a kernel launched ahead carries the position it was launched with)
     h->call = call;
     return CTK_OK;
 }
@@ -1755,11 +1921,18 @@ int ctk_step(ctk_handle* h, const float* s, const float* u_prev, const float* sa
         case CTK_OPT_MPPI: {
             for (int i = 0; i < h->S; ++i) h->mppi_s[i] = s[i];
             if (resident_ok(h, samples_loc)) {   // opt-in: the step is served by the kernel that stays on the device
+                if (int rc = ahead_quiesce(h)) return rc;
                 const float* d_s = nullptr;
                 if (int rc = resolve_samples(h, samples, samples_loc, (size_t)h->N * h->PC, &d_s)) return rc;
                 return resident_step(h, s, u_prev, d_s, u_out);
             }
             if (int rc = resident_quiesce(h)) return rc;
+            if (ahead_eligible(h, samples_loc)) return ahead_step(h, s, u_prev, samples, samples_loc, u_out);   // (may launch the next step's kernel too)
+            if (h->ah_avail) {        // not eligible: a queued kernel is cancelled, and the rule starts over
+                if (int rc = ahead_quiesce(h)) return rc;
+                (void)ctk_ahead_rule_step(&h->ah_rule, 0, -1.0, h->ah_fuse_us, CTK_AHEAD_NONE);
+                h->ah_have_result = false;
+            }
             if (mppi_can_fuse(h)) {   // one launch: the last block to finish merges and updates
                 if (int rc = mppi_rollout(h, s, u_prev, samples, samples_loc, 1, nullptr)) return rc;
                 h->cur ^= 1;
@@ -2267,10 +2440,49 @@ int ctk_resident_enable(ctk_handle* h, int on, double idle_us) {
     return CTK_OK;
 }
 
+// ---- the launched-ahead form: its rule, switch and counters (include/ctk_hip_ahead.h) --------------------------------------------------
+int ctk_ahead_rule_step(ctk_ahead_rule* r, int eligible, double gap_us, double fuse_us, int outcome) {
+    if (!r) return 0;
+    if (outcome == CTK_AHEAD_TAKEN) r->untaken = 0;
+    else if (outcome == CTK_AHEAD_UNTAKEN && ++r->untaken >= CTK_AHEAD_DISARM_AFTER) { r->armed = 0; r->streak = 0; r->untaken = 0; }
+    if (!eligible) { r->streak = 0; r->armed = 0; r->untaken = 0; return 0; }
+    if (gap_us >= 0.0 && gap_us <= fuse_us) { if (r->streak < CTK_AHEAD_ARM_AFTER) ++r->streak; }
+    else r->streak = 0;                                  // the first step, or one that came late: the count starts over
+    if (!r->armed && r->streak >= CTK_AHEAD_ARM_AFTER) { r->armed = 1; r->untaken = 0; ++r->arms; }
+    return r->armed;
+}
+
+int ctk_ahead_enable(ctk_handle* h, int on, double fuse_us) {
+    if (!h) return CTK_ERR_INVALID_ARGUMENT;
+    RES_Q(h);
+    if (on != 0 && on != 1) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_ahead_enable: on must be 0 or 1");
+    if (fuse_us > 0.0 && !(fuse_us >= 1.0 && fuse_us <= 1.0e4)) return fail(h, CTK_ERR_INVALID_ARGUMENT, "ctk_ahead_enable: fuse_us must be within [1, 1e4] (<= 0 keeps the current value)");
+    if (fuse_us > 0.0) h->ah_fuse_us = fuse_us;
+    h->ah_on = on == 1 && !ahead_off_for_process();
+    h->ah_rule = ctk_ahead_rule{};
+    h->ah_have_result = false;
+    return CTK_OK;
+}
+
+const char* ctk_ahead_kernel(const ctk_handle* h) { return (h && h->ah_taken) ? ctk_mppi_ahead_name(h->env) : ""; }
+
+int ctk_ahead_stats(const ctk_handle* h, ctk_ahead_counters* out, double* fuse_us) {
+    if (!h) return CTK_ERR_INVALID_ARGUMENT;
+    if (out) {
+        *out = ctk_ahead_counters{};
+        out->launched = h->ah_launched; out->taken = h->ah_taken; out->untaken = h->ah_untaken; out->cancelled = h->ah_cancelled;
+        out->arms = (uint64_t)h->ah_rule.arms; out->armed = h->ah_rule.armed; out->pending = h->ah_pending ? 1 : 0;
+        out->available = h->ah_avail ? 1 : 0; out->on = (h->ah_on && !ahead_off_for_process()) ? 1 : 0;
+    }
+    if (fuse_us) *fuse_us = h->ah_fuse_us;
+    return CTK_OK;
+}
+
 int ctk_resident_stop(ctk_handle* h) {
     if (!h) return CTK_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    return resident_quiesce(h);
+    RES_Q(h);
+    return CTK_OK;
 }
 
 int ctk_resident_stats(const ctk_handle* h, uint64_t* launches, uint64_t* steps, int* running, int* mailbox_in_device_memory) {

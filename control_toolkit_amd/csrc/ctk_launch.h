@@ -154,6 +154,41 @@ hipError_t ctk_launch_mppi_resident(hipStream_t st, int env, const float* params
 constexpr size_t CTK_RES_ARGS_BYTES = 1024;   // device + host staging block for the resident kernel's argument struct
 const char* ctk_mppi_resident_name(int env, int N, int P);   // N rollouts, P inducing points (per control input)
 const char* ctk_mppi_rollout_env_name(int env, bool log);
+// The LAUNCHED-AHEAD form of the same kernel (ctk_mppi.hip: ctk_mppi_ahead<ENV>; include/ctk_hip_ahead.h): still one launch per step, but
+// the launch of step k+1 is issued while the device works on step k.  What is known at that time travels as kernel arguments (the
+// buffers, the next sequence number, Philox position and plan buffer); what only the step's caller knows — state, previous input, sample
+// pointer — arrives in a MAILBOX the kernel waits for at its entry: fine-grained device memory the host stores into through the PCIe
+// BAR (payload + tail, sfence, request number, as CtkResidentBox).  The wait is bounded by a wall-clock fuse; a kernel that saw no
+// request leaves having written nothing but its state word.
+struct alignas(128) CtkAheadBox {        // one 128-byte line: a reader's single pass over it sees the host's stores in their order
+    uint32_t req;                       // request number (monotonic within a handle; each launch waits for exactly ONE number); written LAST
+    uint32_t cmd;                       // CTK_RES_CMD_STEP | CTK_RES_CMD_EXIT (cancel: the kernel leaves at once)
+    uint32_t dev_uprev;                 // 1: the previous input is the optimizer's own last output on the device (u_prev == NULL at the API)
+    uint32_t pad;
+    const float* samples;               // this step's draws (device pointer), or nullptr: the in-kernel sampler
+    float s[CTK_MAX_STATES];
+    float u_prev[CTK_MAX_INPUTS];
+    uint32_t tail;                      // == req, written with the payload BEFORE req (CtkResidentBox::tail)
+};
+constexpr int CTK_AHEAD_BOX_WORDS = 19;  // dwords of CtkAheadBox up to and including tail
+// the state word (pinned host memory, written by workgroup 0 only): (request number << 2) | CTK_RES_RUNNING (the request was taken) /
+// CTK_RES_LEAVING (the fuse ran out; the request is looked for once more) / CTK_RES_LEFT (left without a step: the kernel's last store)
+constexpr uint32_t ctk_ahead_state(uint32_t req, uint32_t code) { return (req << 2) | code; }
+struct CtkAheadGate {
+    const CtkAheadBox* box;             // device address of the mailbox
+    uint32_t* state;                    // device address of the state word (pinned host memory)
+    uint32_t* relay;                    // device memory: workgroup 0 stores `req` here when it leaves, the other workgroups follow
+    uint32_t req;                       // the request number this launch waits for
+    uint32_t pad;
+    unsigned long long fuse_ticks;      // wall_clock64 ticks (100 MHz)
+};
+// may a handle of these sizes step through ctk_mppi_ahead?  (the one-launch step with the narrow {value, seq} tail, FORM 0)
+bool ctk_mppi_ahead_ok(int env, int N, int H, int P);
+const char* ctk_mppi_ahead_name(int env);
+// a: make_args of a zero state with u_prev == NULL (u_prev_dev = the handle's d_u) and the NEXT step's Philox position; fuse: mode 1
+// with the next step's sequence number and plan buffers, as mppi_rollout would fill it for that step
+hipError_t ctk_launch_mppi_ahead(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
+                                 const float* u_nom, float* parts, const MppiFuse& fuse, const CtkAheadGate& gate);
 // the BATCH form of the same kernel (ctk_mppi.hip: ctk_mppi_batch<ENV, LOG>; include/ctk_hip.h: ctk_batch_*): B independent problems of ONE
 // configuration, grid (workgroups per problem, problems of this launch).  What differs per problem reaches the kernel through two arrays in
 // device memory: the descriptor [B] (where the problem's buffers are; written once, at creation) and the step records [problems of this

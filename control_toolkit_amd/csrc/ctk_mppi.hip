@@ -1337,3 +1337,122 @@ static void launch_batch_gru_hp(hipStream_t st, dim3 grid, dim3 block, size_t ld
         });
     });
 }
+
+// ---------------------------------------------------------------------------------------------
+// The LAUNCHED-AHEAD form (ctk_launch.h: CtkAheadBox / CtkAheadGate; include/ctk_hip_ahead.h): ctk_mppi_rollout<ENV, 0,
+// false, false> — the same body text, FORM 0, the early order of u where FORM 0 takes it — behind a GATE.  The launch is issued while
+// the previous step's kernel still runs, so it carries what was known then; at its entry every workgroup waits for the request that
+// brings the rest (state, previous input, sample pointer), and only then touches anything: nothing is read ahead, so a sample buffer
+// refilled in place is read as the request finds it (the system-scope acquire behind the gate drops what the caches held of it).
+//   * wave 0 of every workgroup reads the mailbox in ONE pass per look (its dwords by as many lanes, uncached): req == the launch's
+//     number and tail == req is a complete request (the host writes payload + tail, sfence, req);
+//   * workgroup 0 decides.  Its wait is bounded by the wall-clock fuse: LEAVING, fence, one more look — a request that slipped in is
+//     served — else it stores the launch's number into the relay word, LEFT as its last store, and the kernel has written nothing else.
+//     The host takes LEFT for "not served", consumes a sequence number and launches the step as ever;
+//   * the other workgroups take the request from the mailbox themselves (no relay hop on the path) and leave when the relay word or
+//     cmd = EXIT says so, or after 4 x the fuse + 1 ms.  A request that lands between workgroup 0's last look and their next one is
+//     rolled out by them for nothing: their record words carry a sequence number the host has consumed, only workgroup 0 ever merges,
+//     updates and publishes, and the stream orders the next launch behind them.
+// Defined LAST in this file, like the _hp launches above and for their reason: every kernel that was here before keeps its text.
+// ---------------------------------------------------------------------------------------------
+#define CTK_BODY_EARLY_U
+template <int ENV>
+__global__ __launch_bounds__(MPPI_BLOCK) void ctk_mppi_ahead(const CtkAheadBox* box, const float* __restrict__ u_nom,
+                                                             const InterpEntry* __restrict__ interp, const float* __restrict__ wperm,
+                                                             float* __restrict__ parts, int N_, int H_, int P_, uint32_t pmagic_,
+                                                             RolloutArgs a_tpl, typename Env<ENV>::K k, MppiK m, FuseArgs fz, CtkAheadGate g) {
+    constexpr int PRED = CTK_PRED_ODE, FORM = 0;
+    constexpr bool LOG = false, P2P = false;
+    constexpr int BOXW = CTK_AHEAD_BOX_WORDS, TAILW = BOXW - 1;
+    static_assert(offsetof(CtkAheadBox, req) == 0 && offsetof(CtkAheadBox, cmd) == 4 && offsetof(CtkAheadBox, tail) == 4 * TAILW && BOXW <= 64 &&
+                  sizeof(CtkAheadBox) == 128, "request layout");
+    extern __shared__ float lds[];
+    __shared__ uint32_t req_s[BOXW];
+    __shared__ int leave_s;
+    if (threadIdx.x < 64) {                                      // wave 0 (wave-uniform below: every lane takes every turn)
+        const int gl = threadIdx.x;
+        const unsigned long long t0 = wall_clock64();
+        uint32_t w = 0;
+        auto look = [&]() {
+            const uint32_t x = gl < BOXW ? __hip_atomic_load(reinterpret_cast<const uint32_t*>(box) + gl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
+            w = x;
+            return (uint32_t)__builtin_amdgcn_readlane((int)x, 0) == g.req && (uint32_t)__builtin_amdgcn_readlane((int)x, TAILW) == g.req;
+        };
+        // (relaxed: the state word orders nothing — a release here would write the L2 back on the request's path)
+        auto state_store = [&](uint32_t v) { __hip_atomic_store(g.state, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
+        int leave = 0;
+        if (blockIdx.x == 0) {
+            for (;;) {
+                if (look()) break;
+                if (wall_clock64() - t0 > g.fuse_ticks) {
+                    if (gl == 0) { state_store(ctk_ahead_state(g.req, CTK_RES_LEAVING)); __threadfence_system(); }
+                    if (!look()) leave = 1;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(1);
+            }
+            if (!leave && (uint32_t)__builtin_amdgcn_readlane((int)w, 1) != (uint32_t)CTK_RES_CMD_STEP) leave = 1;   // cancelled
+            if (gl == 0) {
+                if (leave) {
+                    __hip_atomic_store(g.relay, g.req, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                    state_store(ctk_ahead_state(g.req, CTK_RES_LEFT));
+                } else {
+                    state_store(ctk_ahead_state(g.req, CTK_RES_RUNNING));
+                }
+            }
+        } else {
+            leave = 1;
+            for (;;) {
+                if (look()) { leave = (uint32_t)__builtin_amdgcn_readlane((int)w, 1) != (uint32_t)CTK_RES_CMD_STEP ? 1 : 0; break; }
+                const uint32_t rr = gl == 0 ? __hip_atomic_load(g.relay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+                if ((uint32_t)__builtin_amdgcn_readfirstlane((int)rr) == g.req) break;            // workgroup 0 has left
+                if (wall_clock64() - t0 > 4 * g.fuse_ticks + 100000ull) break;                    // never wait for ever
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
+        if (gl < BOXW) req_s[gl] = w;
+        if (gl == 0) leave_s = leave;
+    }
+    __syncthreads();
+    if (leave_s) return;                                         // workgroup-uniform
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");                // draws written by the host or by a kernel of another stream since this launch began
+    // ---- what ctk_mppi_rollout takes as arguments, from the template and the request (uniform: into scalar registers)
+    auto rq = [&](int i) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)req_s[i]); };
+    RolloutArgs a_in = a_tpl;
+#pragma unroll
+    for (int i = 0; i < Env<ENV>::S; ++i) a_in.s0[i] = __builtin_bit_cast(float, rq(6 + i));
+#pragma unroll
+    for (int c = 0; c < Env<ENV>::C; ++c) a_in.u_prev[c] = __builtin_bit_cast(float, rq(14 + c));
+    if (rq(2) == 0u) a_in.u_prev_dev = nullptr;
+    const float* samples = reinterpret_cast<const float*>((unsigned long long)rq(4) | ((unsigned long long)rq(5) << 32));
+#include "ctk_mppi_body.inc"
+}
+#undef CTK_BODY_EARLY_U
+
+bool ctk_mppi_ahead_ok(int env, int N, int H, int P) {
+    if (N < 1 || ctk_mppi_uses_throughput_kernel(CTK_PRED_ODE, N) || mppi_late_u()) return false;
+    bool ok = false;
+    CTK_FOR_ENV(env, EV, {
+        const int blocks = (N + MPPI_TRAJ - 1) / MPPI_TRAJ;
+        int stage_ok;
+        const size_t lds = rollout_launch_lds(P, H, CTK_PRED_ODE, N, blocks, &stage_ok, Env<EV>::C);
+        ok = stage_ok != 0 && mppi_env_form<EV>(blocks, P * Env<EV>::C, true) == 0 && lds + 256 <= 160 * 1024;   // (+ the gate's static words)
+    });
+    return ok;
+}
+const char* ctk_mppi_ahead_name(int env) { return ctk_kernel_name("ctk_mppi_ahead<%d>", env); }
+
+hipError_t ctk_launch_mppi_ahead(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const MppiK& m,
+                                 const float* u_nom, float* parts, const MppiFuse& fuse, const CtkAheadGate& gate) {
+    const dim3 grid((a.N + MPPI_TRAJ - 1) / MPPI_TRAJ), block(MPPI_BLOCK);
+    CTK_FOR_ENV(env, EV, {
+        using E = Env<EV>;
+        int stage_ok;
+        const size_t lds = rollout_launch_lds(a.P, a.H, CTK_PRED_ODE, a.N, (int)grid.x, &stage_ok, E::C);
+        if (!stage_ok || fuse.ll == nullptr || fuse.mode != 1) return hipErrorInvalidValue;   // the merge + update step with the {value, seq} tail only
+        const FuseArgs fz = mppi_fuse_args(fuse, stage_ok, a, E::C, u_nom, fuse.u_nom_out);
+        hipLaunchKernelGGL((ctk_mppi_ahead<EV>), grid, block, lds, st, gate.box, u_nom, a.interp, static_cast<const float*>(nullptr), parts, a.N, a.H, a.P,
+                           ctk_magic_of(a.P * E::C), a, E::derive(params, dt, isteps), m, fz, gate);
+    });
+    return hipGetLastError();
+}

@@ -320,6 +320,9 @@ int ctk_predictor_set_hidden(ctk_handle* h, const float* src, size_t n); /* src 
  * per record that u needs) runs out, this step returns CTK_ERR_STATE and u_out is NaN, as ever.  If only the SECOND (the whole records,
  * for the plan update) runs out, the host has left with a valid u_out by then: the plan holds NaN, and it is the NEXT ctk_step that
  * finds the error word and returns CTK_ERR_STATE.
+ * MPPI in a tight loop (ctk_hip_ahead.h): after ctk_step returns, ONE kernel of the handle may be queued on the handle's own stream that
+ * waits, for at most the fuse (20 us by default), for the next step's request; it reads and writes nothing until that request is
+ * there, every other call on the handle cancels it first, and a device-wide synchronize waits at most the fuse for it.
  * ----------------------------------------------------------------------------------------- */
 int ctk_step(ctk_handle* h, const float* s, const float* u_prev,
              const float* samples, int samples_loc, float* u_out);
@@ -802,4 +805,6 @@ int ctk_gru_batch_fit(int num_rollouts, int mpc_horizon, int period_interpolatio
 #include "ctk_hip_gru.h"
 /* per-problem MPPI hyper-parameters and input limits of the three MPPI batches */
 #include "ctk_hip_hyper.h"
+/* the launched-ahead form of the MPPI step: its switch, fuse and counters */
+#include "ctk_hip_ahead.h"
 #endif /* CTK_HIP_H */

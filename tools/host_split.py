@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--build", action="store_true")
     ap.add_argument("--steps", type=int, default=500, help="steps per block")
     ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--no-ahead", action="store_true", help="switch the launched-ahead form off (the split of the launched step)")
     a = ap.parse_args()
     if a.build:
         return build()
@@ -43,6 +44,8 @@ def main():
 
     N, H = 1024, 50
     e = CtkEngine("mppi", "ODE", num_rollouts=N, mpc_horizon=H, dt=0.02, period_interpolation_inducing_points=1, seed=1)
+    if a.no_ahead:
+        e.launch_ahead(False)
     read = e._lib.ctk_diag_host_split
     read.restype, read.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
     out = (ctypes.c_double * 4)()
@@ -53,8 +56,15 @@ def main():
     for i in range(100):
         e.step(s, ptrs[i & 15])
     read(e._h, out)
-    print(f"MPPI N={N} H={H} p=1, device sample buffers, step_path {e.step_path}, kernel {e.dominant_kernel()}")
-    print("block  steps  wall us/step  entry->launch call  inside launch call  launch return->{u,seq} seen  sum  (us per step)")
+    ahead = e.ahead_stats()["taken"] > 0
+    print(f"MPPI N={N} H={H} p=1, device sample buffers, step_path {e.step_path}, kernel {e.ahead_kernel() if ahead else e.dominant_kernel()}")
+    if ahead:
+        # a step served by the kernel launched ahead (include/ctk_hip_ahead.h): the stamps stand at the request's store and at workgroup 0's
+        # "taken" word; the launch call of the NEXT step's kernel lies inside the third interval, under this step's kernel
+        print(f"launched ahead: {e.ahead_stats()}")
+        print("block  steps  wall us/step  entry->request stored  request stored->taken seen  taken seen->{u,seq} seen  sum  (us per step)")
+    else:
+        print("block  steps  wall us/step  entry->launch call  inside launch call  launch return->{u,seq} seen  sum  (us per step)")
     rows = []
     for b in range(a.blocks):
         t0 = time.perf_counter()
@@ -68,6 +78,8 @@ def main():
     med = np.median(np.array(rows), axis=0)
     print(f"median        {med[0]:12.2f}  {med[1]:18.2f}  {med[2]:18.2f}  {med[3]:27.2f}  {med[1] + med[2] + med[3]:5.2f}")
     print(f"(wall - sum = {med[0] - med[1] - med[2] - med[3]:.2f} us: the Python wrapper, the call into the library and ctk_step's return)")
+    if ahead:
+        print(f"request stored -> {{u, seq}} seen: {med[2] + med[3]:.2f} us; launched ahead at the end: {e.ahead_stats()}")
     e.close()
 
 
