@@ -230,6 +230,19 @@ for _batch, _problem in _BATCH_FAMILIES[:3]:
     HYPER_SYMBOLS.update({f"{_problem}_{name}": sig for name, sig in _PROBLEM_HYPER.items()})
     HYPER_SYMBOLS[f"{_batch}_set_hyper"] = (C.c_int, [_H, C.c_int, C.c_float])
 
+# per-problem hyper-parameters and input limits of the CEM and RPGD batches (include/ctk_hip_family_hyper.h, which ctk_hip.h includes): a
+# table of its own, bound with the others.  CEM_HYPERS: enum ctk_cem_hyper; RPGD_HYPERS: enum ctk_rpgd_hyper.  The counts cross the ABI
+# as floats and must be integral (_FAMILY_COUNTS).
+CEM_HYPERS = {"cem_best_k": 0, "cem_initial_action_stdev": 1, "cem_stdev_min": 2, "cem_outer_it": 3}
+RPGD_HYPERS = {"learning_rate": 0, "adam_beta_1": 1, "adam_beta_2": 2, "adam_epsilon": 3, "gradmax_clip": 4, "sample_stdev": 5, "sample_mean": 6,
+               "uniform_dist_min": 7, "uniform_dist_max": 8, "outer_its": 9, "resamp_per": 10}
+_FAMILY_HYPERS = {"cem": CEM_HYPERS, "rpgd": RPGD_HYPERS}
+_FAMILY_COUNTS = {"cem_best_k": 1, "cem_outer_it": 1, "outer_its": 0, "resamp_per": 1}        # name -> the smallest admissible value
+FAMILY_HYPER_SYMBOLS = {}
+for _batch, _problem in _BATCH_FAMILIES[3:]:
+    FAMILY_HYPER_SYMBOLS.update({f"{_problem}_{name}": sig for name, sig in _PROBLEM_HYPER.items()})
+    FAMILY_HYPER_SYMBOLS[f"{_batch}_set_hyper"] = (C.c_int, [_H, C.c_int, C.c_float])
+
 
 # the launched-ahead form of the MPPI step (include/ctk_hip_ahead.h, which ctk_hip.h includes): a table of its own, bound with the others
 class AheadRule(C.Structure):
@@ -294,7 +307,7 @@ def _bind_library(path: str):
     except OSError as e:
         raise CtkError(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()) + list(LOOP_SYMBOLS.items()) + \
-            list(GRU_LOOP_SYMBOLS.items()) + list(HYPER_SYMBOLS.items()) + list(AHEAD_SYMBOLS.items()):
+            list(GRU_LOOP_SYMBOLS.items()) + list(HYPER_SYMBOLS.items()) + list(FAMILY_HYPER_SYMBOLS.items()) + list(AHEAD_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctk_abi_version() != 6:
@@ -1002,6 +1015,51 @@ def batch_limit_args(num_problems: int, Cn: int, low, high, ids=None):
     return idv, n, out[0], out[1]
 
 
+def family_hyper_args(family: str, num_problems: int, name, values, ids=None, Cn: int = 1, num_rollouts: int = None):
+    """Checks the arguments of FamilyHypers.set_problem_hypers / set_hyper / set_problem_limits without touching a device.  family: "cem"
+    or "rpgd"; the name against CEM_HYPERS / RPGD_HYPERS, ids (batch_ids), values a scalar (every listed problem) or one value per listed
+    problem ([n]), each finite in fp32; a count (cem_best_k, cem_outer_it, outer_its, resamp_per) integral and within the rule the
+    batch's creation applies (1 <= cem_best_k <= num_rollouts where num_rollouts is given, cem_outer_it >= 1, outer_its >= 0,
+    resamp_per >= 1).  Returns (hyper id, ids, n, values as fp32 [n]).  name "limits": values is (low, high), each a scalar, [Cn] or
+    [n, Cn] with low <= high (batch_limit_args); returns (None, ids, n, (low, high) as fp32 [n, Cn])."""
+    if family not in _FAMILY_HYPERS:
+        raise ValueError(f"family is 'cem' or 'rpgd', not {family!r} (the MPPI batches have batch_hyper_args)")
+    table = _FAMILY_HYPERS[family]
+    if name == "limits":
+        try:
+            low, high = values
+        except (TypeError, ValueError):
+            raise ValueError(f"limits are a pair (low, high), got {values!r}") from None
+        idv, n, lo, hi = batch_limit_args(num_problems, Cn, low, high, ids)
+        return None, idv, n, (lo, hi)
+    if name not in table:
+        raise ValueError(f"unknown hyper-parameter {name!r} ({family.upper()} has {', '.join(table)}; \"limits\" for the input limits)")
+    idv = batch_ids(num_problems, ids)
+    n = num_problems if idv is None else int(idv.size)
+    try:
+        vals = np.asarray(values, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"values of {name!r} must be a number or an array of numbers, got {values!r}") from None
+    if vals.ndim == 0:
+        vals = np.full(n, float(vals))
+    if vals.shape != (n,):
+        raise ValueError(f"{name!r}: one value per listed problem ({n}) or a scalar, got shape {tuple(vals.shape)}")
+    ok = np.abs(vals) <= _F32_MAX                                  # NaN compares false: refused with the infinities and what overflows fp32
+    what = "must be finite in fp32"
+    with np.errstate(over="ignore"):
+        out = vals.astype(np.float32)
+    if ok.all() and name in _FAMILY_COUNTS:
+        ok, what = vals == np.floor(vals), "must be integral"
+        if ok.all():
+            ok, what = (vals >= _FAMILY_COUNTS[name]) & (vals < 2.0 ** 31), f"must be >= {_FAMILY_COUNTS[name]}"
+        if ok.all() and name == "cem_best_k" and num_rollouts is not None:
+            ok, what = vals <= num_rollouts, f"must be <= num_rollouts ({num_rollouts})"
+    if not ok.all():
+        j = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"{name!r} {what}: {float(vals[j])!r} for problem {j if idv is None else int(idv[j])}")
+    return table[name], idv, n, out
+
+
 class _CtkBatch:
     """What the batch classes share: the handle, the argument buffers, the error mapping, the parameter tables and the Philox positions.
     A family is its two entry-point prefixes (_BATCH: the calls on a batch, _PROBLEM: the per-problem parameter calls); its entries are
@@ -1250,7 +1308,8 @@ class BatchHypers:
     """CtkMppiBatch.hypers / CtkMppiMlpBatch.hypers / CtkMppiGruBatch.hypers: every problem's own cc_weight, R, LBD, NU, SQRTRHOINV and
     input limits, settable at any time between steps.  Problem p then behaves bit for bit like CtkEngine("mppi", ..., seed=seeds[p])
     created with p's values; a change makes it equal to a fresh such handle that received the problem's state vector and Philox position
-    (and hidden state).  A view of the batch: it owns nothing.  CEM and RPGD batches have no such view."""
+    (and hidden state).  A view of the batch: it owns nothing.  CEM and RPGD batches have a view of their own, with their own
+    hyper-parameters: FamilyHypers(batch)."""
 
     CALLS = ("set_problem_hypers", "set_hyper", "get_problem_hyper", "get_problem_hypers", "set_problem_limits", "get_problem_limits", "hypers_differ")
 
@@ -1295,6 +1354,79 @@ class BatchHypers:
         set_problem_hypers: the next step clips to them, reset() refills the plan with their middle."""
         b = self._batch
         _, idv, n, (lo, hi) = batch_hyper_args(b.B, "limits", (low, high), ids, b.C)
+        b._check(self._entry("set_limits")(b._h, n, _ptr(idv), _ptr(lo), _ptr(hi)))
+
+    def get_problem_limits(self, problem: int):
+        """(low [C], high [C]) of a problem"""
+        b = self._batch
+        lo, hi = np.empty(b.C, np.float32), np.empty(b.C, np.float32)
+        if self._entry("get_limits")(b._h, b._problem(problem), _ptr(lo), _ptr(hi)) != 0:
+            raise CtkError(f"{b._PROBLEM}_get_limits({problem}) failed")
+        return lo, hi
+
+    def hypers_differ(self) -> int:
+        """1 once a set_problem_hypers, set_hyper or set_problem_limits has succeeded on this batch (sticky), else 0"""
+        b = self._batch
+        return int(self._entry("hypers_differ")(b._h))
+
+
+# ---- per-problem hyper-parameters and input limits of a CEM or RPGD batch (include/ctk_hip_family_hyper.h) --------------------------------------
+class FamilyHypers:
+    """FamilyHypers(cem_batch) / FamilyHypers(rpgd_batch) — the constructor is the way in, as BatchClosedLoop(cem_batch) is: those classes
+    have no hypers attribute.  Every problem's own optimizer numbers and input limits, settable at any time between steps:
+    CEM (CEM_HYPERS): cem_best_k, cem_initial_action_stdev, cem_stdev_min, cem_outer_it;
+    RPGD (RPGD_HYPERS): learning_rate, adam_beta_1, adam_beta_2, adam_epsilon, gradmax_clip, sample_stdev, sample_mean, uniform_dist_min,
+    uniform_dist_max, outer_its, resamp_per.
+    Problem p then behaves bit for bit like CtkEngine("cem", "ODE", seed=seeds[p], ...) / CtkEngine("rpgd", "ODE", generic_kernels=True,
+    seed=seeds[p], ...) created with p's values; a change makes it equal to a fresh such handle that received the problem's state vector
+    and Philox position.  reset() keeps the values and refills from them.  From the first successful setter on the batch runs the _hp
+    form of its kernel (hypers_differ, dominant_kernel).  A view of the batch: it owns nothing."""
+
+    CALLS = BatchHypers.CALLS
+
+    def __init__(self, batch):
+        family = {"ctk_cem_batch": "cem", "ctk_rpgd_batch": "rpgd"}.get(getattr(batch, "_BATCH", None))
+        if family is None:
+            raise TypeError(f"FamilyHypers is the view of a CtkCemBatch or a CtkRpgdBatch, not of {type(batch).__name__} "
+                            "(an MPPI batch has batch.hypers; a CtkEngine takes its hyper-parameters at creation)")
+        self._batch, self.family, self.names = batch, family, _FAMILY_HYPERS[family]
+
+    def _entry(self, entry: str):
+        """the family's hyper-parameter entry `entry` (of the problem prefix; "batch_set_hyper": the whole-batch one)"""
+        b = self._batch
+        return getattr(b._lib, f"{b._BATCH}_set_hyper" if entry == "batch_set_hyper" else f"{b._PROBLEM}_{entry}")
+
+    def set_problem_hypers(self, name: str, values, ids=None):
+        """hyper-parameter `name` of the problems in ids (None: all): values a scalar or [n], one per listed problem in the order of
+        ids.  Takes effect at the problem's next step."""
+        b = self._batch
+        hid, idv, n, vals = family_hyper_args(self.family, b.B, name, values, ids, num_rollouts=b.N)
+        b._check(self._entry("set_hyper")(b._h, n, _ptr(idv), hid, _ptr(vals)))
+
+    def set_hyper(self, name: str, value: float):
+        """hyper-parameter `name` of every problem"""
+        b = self._batch
+        hid, _, _, vals = family_hyper_args(self.family, b.B, name, value, None, num_rollouts=b.N)
+        b._check(self._entry("batch_set_hyper")(b._h, hid, float(vals[0])))
+
+    def get_problem_hyper(self, name: str, problem: int) -> float:
+        b = self._batch
+        if name not in self.names:
+            raise ValueError(f"unknown hyper-parameter {name!r} ({self.family.upper()} has {', '.join(self.names)})")
+        v = C.c_float()
+        if self._entry("get_hyper")(b._h, b._problem(problem), self.names[name], C.byref(v)) != 0:
+            raise CtkError(f"{b._PROBLEM}_get_hyper({problem}, {name!r}) failed")
+        return v.value
+
+    def get_problem_hypers(self, name: str) -> np.ndarray:
+        """[B] hyper-parameter `name` of every problem"""
+        return np.array([self.get_problem_hyper(name, p) for p in range(self._batch.B)], np.float32)
+
+    def set_problem_limits(self, low, high, ids=None):
+        """the input limits (action_low, action_high) of the problems in ids (None: all): each a scalar, [C] or [n, C].  The next step
+        clips to them; reset() refills from them (CEM: the mean with their middle; RPGD: the draws mapped onto them)."""
+        b = self._batch
+        _, idv, n, (lo, hi) = family_hyper_args(self.family, b.B, "limits", (low, high), ids, b.C)
         b._check(self._entry("set_limits")(b._h, n, _ptr(idv), _ptr(lo), _ptr(hi)))
 
     def get_problem_limits(self, problem: int):
@@ -1737,8 +1869,13 @@ class CtkCemBatch(_CtkBatch):
 
     def read(self, name: str, problem: int) -> np.ndarray:
         N, H, S, Cn = self.N, self.H, self.S, self.C
+        K = self.K
+        if name == "BEST_IDX":                             # the problem's own cem_best_k (FamilyHypers; self.K until a setter changed it)
+            v = C.c_float()
+            self._check(self._lib.ctk_cem_problem_get_hyper(self._h, self._problem(problem), CEM_HYPERS["cem_best_k"], C.byref(v)))
+            K = int(v.value)
         return self._read("a CEM batch", {"Q": (N, H, Cn), "J": (N,), "TRAJ": (N, H + 1, S), "U_NOM": (1, H, Cn), "STD": (1, H, Cn),
-                                          "BEST_IDX": (self.K,)}, name, problem)
+                                          "BEST_IDX": (K,)}, name, problem)
 
     def get_state(self, problem: int) -> np.ndarray:
         """mu[H,C] | std[H,C] | u[C] | count of one problem (CtkEngine.get_state of a CEM engine)"""

@@ -55,6 +55,23 @@ struct BatchCore : PlantSide {
     std::vector<unsigned char> dirty;       // [B] the table changed since the problem's constants were last derived (MPPI: and copied to d_k)
     bool differ = false;                    // a *_problem_set_param has succeeded: the per-problem form of the kernel from now on
     size_t kstride = 0;                     // ctk_mppi_batch_k_stride(env): bytes of one problem's derived constants
+    // the CEM and RPGD families' per-problem hyper-parameters and limits (include/ctk_hip_family_hyper.h; the MPPI families keep theirs in
+    // ctk_batch): the table of primary values, initialised from cfg, and every problem's hyper block as the _hp form of the kernel
+    // reads it, refreshed by the setters.  `fhyper` (sticky, as `differ`) once a setter has succeeded: the _hp form from then on, whose
+    // records carry two-part elements [K | hyper block] (elem) in place of the _pp form's K
+    std::vector<float> fhyp;                // [B][frow]: the family's enum values | low [CTK_MAX_INPUTS] | high [CTK_MAX_INPUTS]
+    int fcount = 0, frow = 0;               // the family's CTK_*_HYPER_COUNT; fcount + 2 * CTK_MAX_INPUTS
+    std::vector<unsigned char> hcache;      // [B][hbytes] hyper blocks by problem id (host only; the step copies them behind the K parts)
+    size_t hbytes = 0;                      // ctk_cem_batch_hyper_bytes() / ctk_rpgd_batch_hyper_bytes()
+    bool fhyper = false;
+    bool carries() const { return differ || fhyper; }                         // the step records carry an element per record
+    size_t elem() const { return kstride + (fhyper ? hbytes : 0); }           // ... of this many bytes
+    float* frow_of(int p) { return fhyp.data() + (size_t)p * frow; }
+    const float* frow_of(int p) const { return fhyp.data() + (size_t)p * frow; }
+    float* flow(int p) { return frow_of(p) + fcount; }
+    const float* flow(int p) const { return frow_of(p) + fcount; }
+    float* fhigh(int p) { return frow_of(p) + fcount + CTK_MAX_INPUTS; }
+    const float* fhigh(int p) const { return frow_of(p) + fcount + CTK_MAX_INPUTS; }
     hipStream_t stream = nullptr;
     float* d_u = nullptr;                   // [B][CTK_MAX_INPUTS]
     float* h_u = nullptr;                   // pinned [B][16]: {u, seq}, error words, u[C] (the layout of a handle's slot)
@@ -182,17 +199,20 @@ void batch_record_io(const BatchCore* b, Rec& q, int j, const float* s, const fl
     for (int c = 0; c < b->C; ++c) q.u_prev[c] = u_prev ? u_prev[(size_t)j * b->C + c] : 0.0f;
 }
 
-// The per-problem form of the CEM and RPGD kernels takes the constants by record index: those of the n listed problems into h_k, in
+// The per-problem forms of the CEM and RPGD kernels take the constants by record index: those of the n listed problems into h_k, in
 // listed order.  A problem whose table changed is re-derived here, when it is stepped, with the function a handle uses; kcache is by
-// problem id.
+// problem id.  In the _hp form (fhyper) an element has two parts, [K | hyper block], at stride elem(): the block is the problem's
+// current one (hcache, which the setters refresh), and the K part is current even where no parameter was ever set (`dirty` starts set).
 void batch_stage_constants(BatchCore* b, unsigned char* kcache, const int32_t* ids, int n, unsigned char* h_k) {
+    const size_t stride = b->elem();
     for (int j = 0; j < n; ++j) {
         const size_t z = (size_t)(ids ? ids[j] : j);
         if (b->dirty[z]) {
             ctk_mppi_batch_derive_k(b->env, b->table((int)z), b->cfg.dt, b->cfg.intermediate_steps, kcache + z * b->kstride);
             b->dirty[z] = 0;
         }
-        std::memcpy(h_k + (size_t)j * b->kstride, kcache + z * b->kstride, b->kstride);
+        std::memcpy(h_k + (size_t)j * stride, kcache + z * b->kstride, b->kstride);
+        if (b->fhyper) std::memcpy(h_k + (size_t)j * stride + b->kstride, b->hcache.data() + z * b->hbytes, b->hbytes);
     }
 }
 
@@ -204,13 +224,13 @@ hipError_t batch_send_records(BatchCore* b, unsigned char* kcache, const int32_t
                               const unsigned char** d_ksteps) {
     size_t bytes = (size_t)n * rec;
     *d_ksteps = nullptr;
-    if (b->differ) {
+    if (b->carries()) {
         batch_stage_constants(b, kcache, ids, n, static_cast<unsigned char*>(h_steps) + bytes);
         *d_ksteps = static_cast<const unsigned char*>(d_steps) + bytes;
-        bytes += (size_t)n * b->kstride;
+        bytes += (size_t)n * b->elem();
     }
     const hipError_t e = hipMemcpyAsync(d_steps, h_steps, bytes, hipMemcpyHostToDevice, b->stream);
-    if (e != hipSuccess && b->differ)                  // nothing reached the device: derive and copy again at the next step
+    if (e != hipSuccess && b->carries())               // nothing reached the device: derive and copy again at the next step
         for (int j = 0; j < n; ++j) b->dirty[(size_t)(ids ? ids[j] : j)] = 1;
     return e;
 }
@@ -660,7 +680,7 @@ int batch_closed_loop(typename F::Batch* b, const LoopCall& c) {
     std::vector<unsigned char> timed((size_t)n, 0);
     std::string late;
     const auto ctx = F::context(b);
-    const size_t kbytes = (F::carries_k && b->differ) ? (size_t)n * b->kstride : 0;
+    const size_t kbytes = (F::carries_k && b->carries()) ? (size_t)n * b->elem() : 0;
     hipError_t le = batch_plant_flush(b, sub);
     for (int k0 = 0; le == hipSuccess && k0 < n_steps;) {
         const int L = std::min(b->run_segment, n_steps - k0);                  // this segment: steps k0 .. k0 + L - 1
@@ -1699,6 +1719,116 @@ int ctk_gru_problem_set_hidden(ctk_gru_batch* b, int n_ids, const int32_t* ids, 
 }  // extern "C"
 
 // =============================================================================================
+// Per-problem hyper-parameters and input limits of the CEM and RPGD batches (include/ctk_hip_family_hyper.h): the bodies of the two
+// families' entries over the core's table of primary values (BatchCore::fhyp).  What is a family's own is part of its trait F:
+//   hyper_names, hyper_list        the names of enum ctk_cem_hyper / ctk_rpgd_hyper in its order, and the list a message shows
+//   hyper_rule(b, hyper, v)        the rule *_create applies to the field, and integrality for a count: why v is refused, or NULL
+//   hyper_prepare(b, who, n, ids, hyper, values, all)   what has to exist before the values are written (RPGD: the bias-correction
+//                                  tables of beta pairs that appear with this call); may fail, and then nothing was written
+//   hyper_block(b, p)              problem p's hyper block into hcache, from its row (RPGD: CTK_ERR_STATE, and the block stays, if its betas have no table)
+//   hyper_changed(b, p, hyper)     what else a new value invalidates (CEM: BEST_IDX when cem_best_k changes)
+// `who` is the entry's name.  The first successful setter turns the _hp form on (sticky): from then on every step record carries a
+// two-part element, and F::per_problem_kernel names the _hp kernel.
+// =============================================================================================
+namespace {
+
+template <class F>
+void fhyper_enter(typename F::Batch* b) {
+    if (b->fhyper) return;
+    b->fhyper = true;
+    b->dominant = F::per_problem_kernel(b);
+}
+// the core's table and blocks at creation: every problem with the configuration's values (first[]: the family's enum values)
+void fhyper_init(BatchCore* b, int count, size_t hbytes, const float* first) {
+    b->fcount = count; b->frow = count + 2 * CTK_MAX_INPUTS; b->hbytes = hbytes;
+    b->fhyp.assign((size_t)b->B * b->frow, 0.0f);
+    b->hcache.assign((size_t)b->B * hbytes, 0);
+    for (int p = 0; p < b->B; ++p) {
+        std::memcpy(b->frow_of(p), first, (size_t)count * sizeof(float));
+        for (int c = 0; c < b->C; ++c) { b->flow(p)[c] = b->cfg.action_low[c]; b->fhigh(p)[c] = b->cfg.action_high[c]; }
+    }
+}
+// values == NULL: `all` for every listed problem (the whole-batch entry)
+template <class F>
+int fam_set_hyper(typename F::Batch* b, const char* who, int n_ids, const int32_t* ids, int hyper, const float* values, float all) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (hyper < 0 || hyper >= b->fcount)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown hyper-parameter " + std::to_string(hyper) + " (" + F::hyper_list + ")");
+    for (int j = 0; j < n; ++j) {
+        const float v = values ? values[j] : all;
+        const char* why = !std::isfinite(v) ? ": a hyper-parameter is finite" : F::hyper_rule(b, hyper, v);
+        if (why)
+            return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + why + " (" + F::hyper_names[hyper] + " == " + std::to_string(v) + " for problem " +
+                         std::to_string(ids ? ids[j] : j) + "); nothing was written");
+    }
+    if (int rc = F::hyper_prepare(b, who, n, ids, hyper, values, all)) return rc;
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        b->frow_of(p)[hyper] = values ? values[j] : all;
+        F::hyper_changed(b, p, hyper);
+        if (int rc = F::hyper_block(b, p)) return rc;  // travels behind the problem's next step record (batch_stage_constants)
+    }
+    fhyper_enter<F>(b);
+    return CTK_OK;
+}
+template <class F>
+int fam_problem_set_hyper(typename F::Batch* b, const char* who, int n_ids, const int32_t* ids, int hyper, const float* values) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    if (!values) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL values (one value per listed problem)");
+    return fam_set_hyper<F>(b, who, n_ids, ids, hyper, values, 0.0f);
+}
+int fam_problem_get_hyper(const BatchCore* b, int problem, int hyper, float* out) {
+    if (!b || !out || problem < 0 || problem >= b->B || hyper < 0 || hyper >= b->fcount) return CTK_ERR_INVALID_ARGUMENT;
+    *out = b->frow_of(problem)[hyper];
+    return CTK_OK;
+}
+template <class F>
+int fam_problem_set_limits(typename F::Batch* b, const char* who, int n_ids, const int32_t* ids, const float* low, const float* high) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    int n = 0;
+    if (int rc = batch_ids(b, who, n_ids, ids, &n)) return rc;
+    if (!low || !high) return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL limits (one row of num_control_inputs values per listed problem)");
+    for (int i = 0; i < n * b->C; ++i) {
+        const bool finite = std::isfinite(low[i]) && std::isfinite(high[i]);
+        if (finite && low[i] <= high[i]) continue;
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, std::string(who) + (finite ? ": action_low must be <= action_high for every control input" : ": a limit is finite") +
+                     " (" + std::to_string(low[i]) + ", " + std::to_string(high[i]) + " for problem " + std::to_string(ids ? ids[i / b->C] : i / b->C) +
+                     ", input " + std::to_string(i % b->C) + "); nothing was written");
+    }
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        for (int c = 0; c < b->C; ++c) { b->flow(p)[c] = low[(size_t)j * b->C + c]; b->fhigh(p)[c] = high[(size_t)j * b->C + c]; }
+        if (int rc = F::hyper_block(b, p)) return rc;
+    }
+    fhyper_enter<F>(b);
+    return CTK_OK;
+}
+int fam_problem_get_limits(const BatchCore* b, int problem, float* low, float* high) {
+    if (!b || !low || !high || problem < 0 || problem >= b->B) return CTK_ERR_INVALID_ARGUMENT;
+    std::memcpy(low, b->flow(problem), (size_t)b->C * sizeof(float));
+    std::memcpy(high, b->fhigh(problem), (size_t)b->C * sizeof(float));
+    return CTK_OK;
+}
+const char* const COUNT_IS_INTEGRAL = ": a count is integral (values cross the ABI as float, and every admissible count is exact in fp32)";
+
+// the six entries of include/ctk_hip_family_hyper.h for FAM in {ctk_cem_batch, ctk_rpgd_batch} with the prefix PROB of its per-problem entries
+#define CTK_FAMILY_HYPER_ENTRIES(FAM, PROB, TRAIT)                                                                                                    \
+    int PROB##_set_hyper(FAM* b, int n_ids, const int32_t* ids, int hyper, const float* values) {                                                     \
+        return fam_problem_set_hyper<TRAIT>(b, #PROB "_set_hyper", n_ids, ids, hyper, values);                                                        \
+    }                                                                                                                                                 \
+    int PROB##_get_hyper(const FAM* b, int problem, int hyper, float* out) { return fam_problem_get_hyper(b, problem, hyper, out); }                  \
+    int PROB##_set_limits(FAM* b, int n_ids, const int32_t* ids, const float* low, const float* high) {                                               \
+        return fam_problem_set_limits<TRAIT>(b, #PROB "_set_limits", n_ids, ids, low, high);                                                          \
+    }                                                                                                                                                 \
+    int PROB##_get_limits(const FAM* b, int problem, float* low, float* high) { return fam_problem_get_limits(b, problem, low, high); }               \
+    int PROB##_hypers_differ(const FAM* b) { return b && b->fhyper ? 1 : 0; }                                                                         \
+    int FAM##_set_hyper(FAM* b, int hyper, float value) { return fam_set_hyper<TRAIT>(b, #FAM "_set_hyper", 0, nullptr, hyper, nullptr, value); }
+
+}  // namespace
+
+// =============================================================================================
 // Batched CEM (include/ctk_hip.h: ctk_cem_batch_*): B independent CEM problems of one configuration, stepped by launches of
 // ctk_cem_batch<ENV, TRAJ> (ctk_cem_fused.hip).  One allocation per buffer kind with a problem stride — no handles inside.  Per-problem
 // host state is what a CEM handle keeps: the sequence number of its next step, its Philox position, its step count (which decides the
@@ -1706,6 +1836,10 @@ int ctk_gru_problem_set_hidden(ctk_gru_batch* b, int n_ids, const int32_t* ids, 
 // table.  While no ctk_cem_problem_set_param has succeeded the launches take the constants of the shared table by value; from then on
 // (`differ`, sticky) every step writes the constants of the problems it steps BEHIND their step records, in the records' order, so they
 // travel in the records' transfer (no constants array in device memory, no second transfer).
+// The optimizer's own numbers go the same way (include/ctk_hip_family_hyper.h): cem_best_k, the two deviations, cem_outer_it and the
+// input limits are the configuration's until a ctk_cem_problem_set_hyper / _set_limits / ctk_cem_batch_set_hyper has succeeded; from
+// then on (`fhyper`, sticky) the launches take ctk_cem_batch_hp<ENV, TRAJ>, and behind every step record travels the two-part element
+// [K | hyper block] of its problem.  cem_outer_it never reaches the kernel but through the record's `its`.
 // =============================================================================================
 struct ctk_cem_batch : BatchCore {
     int K = 0, nblk = 0;
@@ -1725,8 +1859,10 @@ struct ctk_cem_batch : BatchCore {
     float* mu(int p) const { return d_mu + (size_t)p * HC; }
     float* sd(int p) const { return d_sd + (size_t)p * HC; }
     // cem_iterations of the step the problem takes t steps from now: the warm-up count exactly at its first step after creation or reset
-    int its_at(int p, int t) const { return (cfg.warmup && count[(size_t)p] + t == 0) ? cfg.warmup_iterations : cfg.cem_outer_it; }
+    // (cem_outer_it: the problem's own, the configuration's until a setter changed it)
+    int its_at(int p, int t) const { return (cfg.warmup && count[(size_t)p] + t == 0) ? cfg.warmup_iterations : (int)frow_of(p)[CTK_CEM_HYPER_OUTER_IT]; }
     int its(int p) const { return its_at(p, 0); }
+    int K_of(int p) const { return (int)frow_of(p)[CTK_CEM_HYPER_BEST_K]; }   // the problem's cem_best_k
 };
 
 namespace {
@@ -1760,8 +1896,11 @@ hipError_t cem_batch_launch_records(ctk_cem_batch* b, const CemBatchCtx& x, cons
     *launched = 0;
     while (le == hipSuccess && *launched < n) {
         const int cnt = std::min(b->max_per_launch, n - *launched);
-        le = ctk_launch_cem_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, x.a, x.cl, b->d_desc, steps_dev + *launched, cnt, x.log,
-                                  d_ksteps ? d_ksteps + (size_t)*launched * b->kstride : nullptr);
+        // (the elements are indexed by the launch's record offset, as the records are)
+        const unsigned char* d_k = d_ksteps ? d_ksteps + (size_t)*launched * b->elem() : nullptr;
+        le = b->fhyper ? ctk_launch_cem_batch_hp(b->stream, b->env, x.a, x.cl, b->d_desc, steps_dev + *launched, cnt, x.log, d_k)
+                       : ctk_launch_cem_batch(b->stream, b->env, b->params, b->cfg.dt, b->cfg.intermediate_steps, x.a, x.cl, b->d_desc, steps_dev + *launched, cnt,
+                                              x.log, d_k);
         if (le == hipSuccess) *launched += cnt;
     }
     return le;
@@ -1795,7 +1934,7 @@ struct CemFamily {
     static const float*& draws(Rec& q) { return q.samples; }
     static CemBatchCtx context(const Batch* b) { return cem_batch_context(b); }
     static hipError_t constants(Batch* b, const int32_t* ids, int n, unsigned char* h_k) {
-        if (b->differ) batch_stage_constants(b, b->kcache.data(), ids, n, h_k);
+        if (b->carries()) batch_stage_constants(b, b->kcache.data(), ids, n, h_k);
         return hipSuccess;
     }
     // its from count + t; the tags of the t steps before it consumed one after the other, each by the wrap rule; seq and call + 1 per step
@@ -1828,14 +1967,37 @@ struct CemFamily {
     static BatchState state(Batch* b, int p) {
         return {{state_seg(b->mu(p), (size_t)b->HC), state_seg(b->sd(p), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C), state_counter(&b->count[(size_t)p])}};
     }
-    static const char* per_problem_kernel(const Batch* b) { return ctk_cem_batch_name(b->env, b->cfg.materialize_trajectories != 0, true); }
+    static const char* per_problem_kernel(const Batch* b) {     // (the _hp form stays the _hp form)
+        return b->fhyper ? ctk_cem_batch_hp_name(b->env, b->cfg.materialize_trajectories != 0) : ctk_cem_batch_name(b->env, b->cfg.materialize_trajectories != 0, true);
+    }
+    // ---- per-problem hyper-parameters (include/ctk_hip_family_hyper.h: enum ctk_cem_hyper) ----
+    static constexpr const char* hyper_names[CTK_CEM_HYPER_COUNT] = {"cem_best_k", "cem_initial_action_stdev", "cem_stdev_min", "cem_outer_it"};
+    static constexpr const char* hyper_list = "enum ctk_cem_hyper: cem_best_k, cem_initial_action_stdev, cem_stdev_min, cem_outer_it";
+    // the rules ctk_cem_batch_create applies to the same fields
+    static const char* hyper_rule(const Batch* b, int hyper, float v) {
+        if (hyper != CTK_CEM_HYPER_BEST_K && hyper != CTK_CEM_HYPER_OUTER_IT) return nullptr;
+        if (v != std::floor(v)) return COUNT_IS_INTEGRAL;
+        if (hyper == CTK_CEM_HYPER_BEST_K) return v >= 1.0f && v <= (float)b->N ? nullptr : ": CEM needs 1 <= cem_best_k <= num_rollouts";
+        return v >= 1.0f && v <= 2147483520.0f ? nullptr : ": CEM needs cem_outer_it >= 1";
+    }
+    static int hyper_prepare(Batch*, const char*, int, const int32_t*, int, const float*, float) { return CTK_OK; }
+    static int hyper_block(Batch* b, int p) {
+        const float* row = b->frow_of(p);
+        ctk_cem_batch_fill_hyper(b->hcache.data() + (size_t)p * b->hbytes, b->K_of(p), row[CTK_CEM_HYPER_STDEV_MIN], row[CTK_CEM_HYPER_INITIAL_ACTION_STDEV],
+                                 b->flow(p), b->fhigh(p), b->C);
+        return CTK_OK;
+    }
+    // BEST_IDX is materialised on demand with the problem's K: a new K makes what a step left there stale (before the problem's first
+    // step after its creation or reset there is nothing to select from, as in a handle)
+    static void hyper_changed(Batch* b, int p, int hyper) { if (hyper == CTK_CEM_HYPER_BEST_K && b->count[(size_t)p] > 0) b->idx_stale[(size_t)p] = 1; }
 };
 
-// mean at mid-range, std = cem_initial_action_stdev, u = 0 of problem p into the host images (ctk_reset of a CEM handle)
-void cem_batch_initial(const ctk_cem_batch* b, float* mu, float* sd) {
+// mean at the middle of problem p's limits, std = its cem_initial_action_stdev (the configuration's until a setter changed them) into
+// the host images (ctk_reset of a CEM handle created with p's values)
+void cem_batch_initial(const ctk_cem_batch* b, int p, float* mu, float* sd) {
     for (int i = 0; i < b->HC; ++i) {
-        mu[i] = 0.5f * (b->cfg.action_low[i % b->C] + b->cfg.action_high[i % b->C]);
-        sd[i] = b->cfg.cem_initial_action_stdev;
+        mu[i] = 0.5f * (b->flow(p)[i % b->C] + b->fhigh(p)[i % b->C]);
+        sd[i] = b->frow_of(p)[CTK_CEM_HYPER_INITIAL_ACTION_STDEV];
     }
 }
 
@@ -1846,6 +2008,8 @@ extern "C" {
 CTK_BATCH_ENTRIES(ctk_cem_batch, ctk_cem_problem, CemFamily)
 // ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_cem_batch_plant_* / ctk_cem_batch_run / ctk_cem_batch_episodes) ----
 CTK_LOOP_ENTRIES(ctk_cem_batch, CemFamily)
+// ---- per-problem hyper-parameters and limits (include/ctk_hip_family_hyper.h: ctk_cem_problem_*_hyper / _limits, ctk_cem_batch_set_hyper) ----
+CTK_FAMILY_HYPER_ENTRIES(ctk_cem_batch, ctk_cem_problem, CemFamily)
 
 size_t ctk_cem_batch_samples_needed(const ctk_cem_batch* b, int problem) { return (b && problem >= 0 && problem < b->B) ? CemFamily::draws_of(b, problem) : 0; }
 
@@ -1891,6 +2055,9 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
     b->cem_tag.assign((size_t)n_problems, 1u);
     b->count.assign((size_t)n_problems, 0); b->idx_stale.assign((size_t)n_problems, 0);
     b->dominant = ctk_cem_batch_name(b->env, cfg->materialize_trajectories != 0);
+    const float first[CTK_CEM_HYPER_COUNT] = {(float)cfg->cem_best_k, cfg->cem_initial_action_stdev, cfg->cem_stdev_min, (float)cfg->cem_outer_it};
+    fhyper_init(b, CTK_CEM_HYPER_COUNT, ctk_cem_batch_hyper_bytes(), first);
+    for (int p = 0; p < n_problems; ++p) CemFamily::hyper_block(b, p);   // (cannot fail)
 
     if (int rc = batch_core_open(b)) return rc;
     const size_t Bz = (size_t)n_problems;
@@ -1902,7 +2069,7 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
     if (cfg->materialize_trajectories) HIP_CREATE(b->own.dev_zero(&b->d_traj, Bz * N * (H + 1) * b->S * sizeof(float), b->stream));
     HIP_CREATE(b->own.dev_zero(&b->d_idx, Bz * N * sizeof(int), b->stream));
     HIP_CREATE(b->own.dev_zero(&b->d_desc, Bz * sizeof(CtkCemBatchDesc), b->stream));
-    const size_t steps_bytes = Bz * (sizeof(CtkCemBatchStep) + b->kstride);   // the records, then room for as many elements of constants
+    const size_t steps_bytes = Bz * (sizeof(CtkCemBatchStep) + b->kstride + b->hbytes);   // the records, then room for as many two-part elements
     HIP_CREATE(b->own.dev_zero(&b->d_steps, steps_bytes, b->stream));
     HIP_CREATE(b->own.pinned_zero(&b->h_steps, steps_bytes));
 
@@ -1918,7 +2085,7 @@ int ctk_cem_batch_create(const ctk_config* cfg, int n_problems, const uint64_t* 
         d.traj_out = b->d_traj ? b->d_traj + z * N * (H + 1) * b->S : nullptr;
         d.u_dev = b->u(p); d.u_host = b->h_u_dev + z * 16; d.idx_out = b->d_idx + z * N;
         d.seed_lo = (uint32_t)(seed & 0xFFFFFFFFull); d.seed_hi = (uint32_t)(seed >> 32);
-        cem_batch_initial(b, mu.data() + z * HC, sd.data() + z * HC);
+        cem_batch_initial(b, p, mu.data() + z * HC, sd.data() + z * HC);
     }
     HIP_CREATE(hipMemcpyAsync(b->d_desc, desc.data(), Bz * sizeof(CtkCemBatchDesc), hipMemcpyHostToDevice, b->stream));
     HIP_CREATE(hipMemcpyAsync(b->d_mu, mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
@@ -1938,13 +2105,14 @@ int ctk_cem_batch_reset(ctk_cem_batch* b, int n_ids, const int32_t* ids) {
     int n = 0;
     if (int rc = batch_ids(b, "ctk_cem_batch_reset", n_ids, ids, &n)) return rc;
     BHIP_TRY(b, hipSetDevice(b->cfg.device));
-    std::vector<float> mu((size_t)b->HC), sd((size_t)b->HC), zero((size_t)b->C, 0.0f);
-    cem_batch_initial(b, mu.data(), sd.data());
-    for (int j = 0; j < n; ++j) {                      // ctk_reset of a CEM handle: parameters, tags and the Philox position stay
+    const size_t HC = (size_t)b->HC;                   // every listed problem's own images: the copies below read them until the synchronisation
+    std::vector<float> mu((size_t)n * HC), sd((size_t)n * HC), zero((size_t)b->C, 0.0f);
+    for (int j = 0; j < n; ++j) {                      // ctk_reset of a CEM handle: parameters, hyper-parameters, tags and the Philox position stay
         const int p = ids ? ids[j] : j;
+        cem_batch_initial(b, p, mu.data() + (size_t)j * HC, sd.data() + (size_t)j * HC);
         b->count[(size_t)p] = 0;
-        BHIP_TRY(b, hipMemcpyAsync(b->mu(p), mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
-        BHIP_TRY(b, hipMemcpyAsync(b->sd(p), sd.data(), sd.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        BHIP_TRY(b, hipMemcpyAsync(b->mu(p), mu.data() + (size_t)j * HC, HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        BHIP_TRY(b, hipMemcpyAsync(b->sd(p), sd.data() + (size_t)j * HC, HC * sizeof(float), hipMemcpyHostToDevice, b->stream));
         BHIP_TRY(b, hipMemcpyAsync(b->u(p), zero.data(), zero.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
     }
     BHIP_TRY(b, hipStreamSynchronize(b->stream));
@@ -1959,13 +2127,13 @@ int ctk_cem_batch_read(ctk_cem_batch* b, int problem, int buffer, float* dst, si
     if (!src) switch (buffer) {
         case CTK_BUF_U_NOM: src = b->mu(problem); n = (size_t)b->HC; break;
         case CTK_BUF_STD: src = b->sd(problem); n = (size_t)b->HC; break;
-        case CTK_BUF_BEST_IDX: src = reinterpret_cast<const float*>(b->d_idx + z * N); n = (size_t)b->K; is_int = true; break;
+        case CTK_BUF_BEST_IDX: src = reinterpret_cast<const float*>(b->d_idx + z * N); n = (size_t)b->K_of(problem); is_int = true; break;
         default: return bfail(b, CTK_ERR_INVALID_ARGUMENT, "ctk_cem_batch_read: a CEM batch has Q, J, TRAJ, U_NOM, STD and BEST_IDX");
     }
     return batch_read_out(b, "ctk_cem_batch_read", src, n, is_int, dst, cap, [&]() -> int {
         if (!is_int || !b->idx_stale[z]) return CTK_OK;
         // the sorted elite indices are materialised from the last iteration's costs (ctk_api.hip: locate_buffer)
-        BHIP_TRY(b, ctk_launch_select_topk(b->stream, b->d_J + z * N, b->N, b->K, b->d_idx + z * N));
+        BHIP_TRY(b, ctk_launch_select_topk(b->stream, b->d_J + z * N, b->N, b->K_of(problem), b->d_idx + z * N));
         b->idx_stale[z] = 0;
         return CTK_OK;
     });
@@ -1984,12 +2152,21 @@ int ctk_cem_batch_read(ctk_cem_batch* b, int problem, int buffer, float* dst, si
 // constants of the shared table by value; from then on (`differ`, sticky) every step writes the constants of the problems it steps
 // BEHIND their step records, in the records' order, so they travel in the records' transfer (no constants array in device memory, no
 // second transfer).
+// The optimizer's own numbers go the same way (include/ctk_hip_family_hyper.h): the Adam constants, the clip, the sampling constants,
+// outer_its, resamp_per and the input limits are the configuration's until a ctk_rpgd_problem_set_hyper / _set_limits /
+// ctk_rpgd_batch_set_hyper has succeeded; from then on (`fhyper`, sticky) the launches take ctk_g_rpgd_batch_hp<ENV>, and behind every
+// step record travels the two-part element [K | hyper block] of its problem.  The block names the problem's bias-correction table: one
+// device table per distinct (adam_beta_1, adam_beta_2) in use (bc_tabs), each adam_bias_corrections of its pair, the function behind a
+// handle's table.  outer_its and resamp_per never reach the kernel but through the record's iters / resample.
 // =============================================================================================
 struct ctk_rpgd_batch : BatchCore {
     int P = 0, PC = 0, K = 0;
     std::vector<unsigned char> kcache;      // [B][kstride] derived constants by problem id (host only; the step copies them into h_steps)
     InterpEntry* d_interp = nullptr;        // [H] shared
-    float* d_bc = nullptr; int bc_len = 0;  // shared bias-correction table
+    float* d_bc = nullptr; int bc_len = 0;  // the bias-correction table of the configuration's betas (bc_tabs[0])
+    struct BcTab { float b1, b2; float* d; };
+    std::vector<BcTab> bc_tabs;             // the device tables, [2 * bc_len] floats each; one that no problem names is written over by the next new pair
+    std::vector<int> bc_of;                 // [B] the problem's table
     float* d_pop[2] = {nullptr, nullptr};   // [B][N,H,C] each
     float* d_m[2] = {nullptr, nullptr};
     float* d_v[2] = {nullptr, nullptr};
@@ -2004,11 +2181,13 @@ struct ctk_rpgd_batch : BatchCore {
     std::vector<unsigned char> cur, ready;
     size_t NHC() const { return (size_t)N * HC; }
     // rpgd_iterations and the resampling rule (optimizer_rpgd.py:449) of the step the problem takes t steps from now: both from count + t
+    // (outer_its, resamp_per: the problem's own, the configuration's until a setter changed them)
     int its_at(int p, int t) const {
-        const int first = cfg.warmup ? cfg.warmup_iterations : cfg.outer_its;
-        return count[(size_t)p] + t == 0 ? first : cfg.outer_its;
+        const int outer = (int)frow_of(p)[CTK_RPGD_HYPER_OUTER_ITS];
+        const int first = cfg.warmup ? cfg.warmup_iterations : outer;
+        return count[(size_t)p] + t == 0 ? first : outer;
     }
-    bool resamples_at(int p, int t) const { return (count[(size_t)p] + t) % cfg.resamp_per == 0; }
+    bool resamples_at(int p, int t) const { return (count[(size_t)p] + t) % (int)frow_of(p)[CTK_RPGD_HYPER_RESAMP_PER] == 0; }
     int its(int p) const { return its_at(p, 0); }
     bool resamples(int p) const { return resamples_at(p, 0); }
     size_t needs(int p) const { return (resamples(p) && K < N) ? (size_t)(N - K) * PC : 0; }   // samples_needed of an RPGD handle
@@ -2048,9 +2227,12 @@ hipError_t rpgd_batch_launch_records(ctk_rpgd_batch* b, const RpgdBatchCtx& x, c
     *launched = 0;
     while (le == hipSuccess && *launched < n) {
         const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - *launched);
-        le = ctk_launch_g_rpgd_batch(b->stream, b->env, x.a, b->params, c.dt, c.intermediate_steps, c.learning_rate, c.adam_beta_1, c.adam_beta_2,
-                                     c.adam_epsilon, c.gradmax_clip, c.adam_rule == 1 ? 1 : 0, b->d_bc, b->bc_len, x.f, b->d_desc, steps_dev + *launched, cnt,
-                                     d_ksteps ? d_ksteps + (size_t)*launched * b->kstride : nullptr);
+        // (the elements are indexed by the launch's record offset, as the records are)
+        const unsigned char* d_k = d_ksteps ? d_ksteps + (size_t)*launched * b->elem() : nullptr;
+        le = b->fhyper ? ctk_launch_g_rpgd_batch_hp(b->stream, b->env, x.a, b->bc_len, x.f, b->d_desc, steps_dev + *launched, cnt, d_k)
+                       : ctk_launch_g_rpgd_batch(b->stream, b->env, x.a, b->params, c.dt, c.intermediate_steps, c.learning_rate, c.adam_beta_1, c.adam_beta_2,
+                                                 c.adam_epsilon, c.gradmax_clip, c.adam_rule == 1 ? 1 : 0, b->d_bc, b->bc_len, x.f, b->d_desc,
+                                                 steps_dev + *launched, cnt, d_k);
         if (le == hipSuccess) *launched += cnt;
     }
     return le;
@@ -2089,7 +2271,7 @@ struct RpgdFamily {
     static const float*& draws(Rec& q) { return q.draws; }
     static RpgdBatchCtx context(const Batch* b) { return {rpgd_batch_args(b), rpgd_batch_warm(b)}; }
     static hipError_t constants(Batch* b, const int32_t* ids, int n, unsigned char* h_k) {
-        if (b->differ) batch_stage_constants(b, b->kcache.data(), ids, n, h_k);
+        if (b->carries()) batch_stage_constants(b, b->kcache.data(), ids, n, h_k);
         return hipSuccess;
     }
     // iters and resample from count + t; t0 = the Adam steps taken plus those of the t steps before it; cur flips, seq and call + 1 per
@@ -2127,7 +2309,76 @@ struct RpgdFamily {
                  state_seg(b->d_ages[cur] + z * N, N), state_seg(b->u(p), (size_t)b->C), state_counter(&b->adam_step[z]), state_counter(&b->count[z])},
                 &b->ready[z]};
     }
-    static const char* per_problem_kernel(const Batch* b) { return ctk_g_rpgd_batch_name(b->env, true); }
+    static const char* per_problem_kernel(const Batch* b) {     // (the _hp form stays the _hp form)
+        return b->fhyper ? ctk_g_rpgd_batch_hp_name(b->env) : ctk_g_rpgd_batch_name(b->env, true);
+    }
+    // ---- per-problem hyper-parameters (include/ctk_hip_family_hyper.h: enum ctk_rpgd_hyper) ----
+    static constexpr const char* hyper_names[CTK_RPGD_HYPER_COUNT] = {"learning_rate", "adam_beta_1", "adam_beta_2", "adam_epsilon", "gradmax_clip", "sample_stdev",
+                                                                      "sample_mean", "uniform_dist_min", "uniform_dist_max", "outer_its", "resamp_per"};
+    static constexpr const char* hyper_list = "enum ctk_rpgd_hyper: learning_rate, adam_beta_1, adam_beta_2, adam_epsilon, gradmax_clip, sample_stdev, sample_mean, "
+                                              "uniform_dist_min, uniform_dist_max, outer_its, resamp_per";
+    // the rules ctk_rpgd_batch_create applies to the same fields
+    static const char* hyper_rule(const Batch*, int hyper, float v) {
+        if (hyper != CTK_RPGD_HYPER_OUTER_ITS && hyper != CTK_RPGD_HYPER_RESAMP_PER) return nullptr;
+        if (v != std::floor(v)) return COUNT_IS_INTEGRAL;
+        if (hyper == CTK_RPGD_HYPER_OUTER_ITS) return v >= 0.0f && v <= 2147483520.0f ? nullptr : ": RPGD needs outer_its >= 0";
+        return v >= 1.0f && v <= 2147483520.0f ? nullptr : ": RPGD needs resamp_per >= 1";
+    }
+    // the table of (b1, b2), or -1
+    static int bc_find(const Batch* b, float b1, float b2) {
+        for (size_t i = 0; i < b->bc_tabs.size(); ++i)
+            if (b->bc_tabs[i].b1 == b1 && b->bc_tabs[i].b2 == b2) return (int)i;
+        return -1;
+    }
+    // A new beta makes a new (beta_1, beta_2) pair for its problem: every pair that appears with this call gets its device table here,
+    // before anything is written — adam_bias_corrections of the pair, into a table that no problem names (the configuration's, table 0,
+    // is kept) or a new allocation.  No launch is in flight between two calls (every step, run and reset ends synchronised), so such
+    // a table may be written over — but never one that a problem of THIS call is about to name: `needed` holds every table the call has
+    // found or written for a listed problem, whether or not a problem names it yet.
+    static int hyper_prepare(Batch* b, const char*, int n, const int32_t* ids, int hyper, const float* values, float all) {
+        if (hyper != CTK_RPGD_HYPER_ADAM_BETA_1 && hyper != CTK_RPGD_HYPER_ADAM_BETA_2) return CTK_OK;
+        std::vector<int> needed;
+        for (int j = 0; j < n; ++j) {
+            const int p = ids ? ids[j] : j;
+            const float v = values ? values[j] : all;
+            const float b1 = hyper == CTK_RPGD_HYPER_ADAM_BETA_1 ? v : b->frow_of(p)[CTK_RPGD_HYPER_ADAM_BETA_1];
+            const float b2 = hyper == CTK_RPGD_HYPER_ADAM_BETA_2 ? v : b->frow_of(p)[CTK_RPGD_HYPER_ADAM_BETA_2];
+            const int have = bc_find(b, b1, b2);
+            if (have >= 0) { needed.push_back(have); continue; }             // (it may be named by no problem at this moment)
+            int slot = -1;
+            for (size_t i = 1; i < b->bc_tabs.size() && slot < 0; ++i)
+                if (std::find(b->bc_of.begin(), b->bc_of.end(), (int)i) == b->bc_of.end() && std::find(needed.begin(), needed.end(), (int)i) == needed.end())
+                    slot = (int)i;
+            BHIP_TRY(b, hipSetDevice(b->cfg.device));
+            const std::vector<float> bc = adam_bias_corrections(b1, b2);       // the table of a handle created with the pair (ctk_host.h)
+            if (slot < 0) {
+                float* d = nullptr;
+                BHIP_TRY(b, b->own.dev_zero(&d, bc.size() * sizeof(float), b->stream));
+                b->bc_tabs.push_back({NAN, NAN, d});   // (no pair yet: found by nobody until the copy below has succeeded)
+                slot = (int)b->bc_tabs.size() - 1;
+            }
+            b->bc_tabs[(size_t)slot].b1 = b->bc_tabs[(size_t)slot].b2 = NAN;
+            BHIP_TRY(b, hipMemcpyAsync(b->bc_tabs[(size_t)slot].d, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+            BHIP_TRY(b, hipStreamSynchronize(b->stream));                      // bc goes out of scope
+            b->bc_tabs[(size_t)slot].b1 = b1; b->bc_tabs[(size_t)slot].b2 = b2;
+            needed.push_back(slot);
+        }
+        return CTK_OK;
+    }
+    static int hyper_block(Batch* b, int p) {
+        const float* r = b->frow_of(p);
+        const int tab = bc_find(b, r[CTK_RPGD_HYPER_ADAM_BETA_1], r[CTK_RPGD_HYPER_ADAM_BETA_2]);   // (hyper_prepare has made it)
+        if (tab < 0)                                   // never an address that is not a table's: the problem keeps the block and table it had
+            return bfail(b, CTK_ERR_STATE, "no bias-correction table for adam_beta_1 " + std::to_string(r[CTK_RPGD_HYPER_ADAM_BETA_1]) + ", adam_beta_2 " +
+                         std::to_string(r[CTK_RPGD_HYPER_ADAM_BETA_2]) + " of problem " + std::to_string(p) + " (hyper_prepare makes one for every pair a call brings)");
+        b->bc_of[(size_t)p] = tab;
+        ctk_rpgd_batch_fill_hyper(b->hcache.data() + (size_t)p * b->hbytes, r[CTK_RPGD_HYPER_LEARNING_RATE], r[CTK_RPGD_HYPER_ADAM_BETA_1],
+                                  r[CTK_RPGD_HYPER_ADAM_BETA_2], r[CTK_RPGD_HYPER_ADAM_EPSILON], r[CTK_RPGD_HYPER_GRADMAX_CLIP], b->cfg.adam_rule == 1 ? 1 : 0,
+                                  b->bc_tabs[(size_t)tab].d, r[CTK_RPGD_HYPER_SAMPLE_STDEV], r[CTK_RPGD_HYPER_SAMPLE_MEAN], r[CTK_RPGD_HYPER_UNIFORM_DIST_MIN],
+                                  r[CTK_RPGD_HYPER_UNIFORM_DIST_MAX], b->flow(p), b->fhigh(p), b->C);
+        return CTK_OK;
+    }
+    static void hyper_changed(Batch*, int, int) {}
 };
 
 }  // namespace
@@ -2146,6 +2397,8 @@ size_t ctk_rpgd_template_descent_lds(int environment, int mpc_horizon, int* tape
 CTK_BATCH_ENTRIES(ctk_rpgd_batch, ctk_rpgd_problem, RpgdFamily)
 // ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_rpgd_batch_plant_* / ctk_rpgd_batch_run / ctk_rpgd_batch_episodes) ----
 CTK_LOOP_ENTRIES(ctk_rpgd_batch, RpgdFamily)
+// ---- per-problem hyper-parameters and limits (include/ctk_hip_family_hyper.h: ctk_rpgd_problem_*_hyper / _limits, ctk_rpgd_batch_set_hyper) ----
+CTK_FAMILY_HYPER_ENTRIES(ctk_rpgd_batch, ctk_rpgd_problem, RpgdFamily)
 
 size_t ctk_rpgd_batch_samples_needed(const ctk_rpgd_batch* b, int problem) { return (b && problem >= 0 && problem < b->B) ? b->needs(problem) : 0; }
 
@@ -2206,6 +2459,10 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
     b->count.assign((size_t)n_problems, 0); b->adam_step.assign((size_t)n_problems, 0);
     b->cur.assign((size_t)n_problems, 0); b->ready.assign((size_t)n_problems, 0);
     b->dominant = ctk_g_rpgd_batch_name(b->env);
+    const float first[CTK_RPGD_HYPER_COUNT] = {cfg->learning_rate, cfg->adam_beta_1, cfg->adam_beta_2, cfg->adam_epsilon, cfg->gradmax_clip, cfg->sample_stdev,
+                                               cfg->sample_mean, cfg->sample_min, cfg->sample_max, (float)cfg->outer_its, (float)cfg->resamp_per};
+    fhyper_init(b, CTK_RPGD_HYPER_COUNT, ctk_rpgd_batch_hyper_bytes(), first);
+    b->bc_of.assign((size_t)n_problems, 0);
 
     if (int rc = batch_core_open(b)) return rc;
     const size_t Bz = (size_t)n_problems, NHC = b->NHC();
@@ -2220,7 +2477,7 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
     HIP_CREATE(b->own.dev_zero(&b->d_unom, Bz * HC * sizeof(float), b->stream));
     HIP_CREATE(b->own.dev_zero(&b->d_scratch, Bz * b->scratch_stride * sizeof(float), b->stream));
     HIP_CREATE(b->own.dev_zero(&b->d_desc, Bz * sizeof(CtkRpgdBatchDesc), b->stream));
-    const size_t steps_bytes = Bz * (sizeof(CtkRpgdBatchStep) + b->kstride);   // the records, then room for as many elements of constants
+    const size_t steps_bytes = Bz * (sizeof(CtkRpgdBatchStep) + b->kstride + b->hbytes);   // the records, then room for as many two-part elements
     HIP_CREATE(b->own.dev_zero(&b->d_steps, steps_bytes, b->stream));
     HIP_CREATE(b->own.pinned_zero(&b->h_steps, steps_bytes));
 
@@ -2231,6 +2488,9 @@ int ctk_rpgd_batch_create(const ctk_config* cfg, int n_problems, const uint64_t*
     b->bc_len = (int)(bc.size() / 2);
     HIP_CREATE(b->own.dev_zero(&b->d_bc, bc.size() * sizeof(float), b->stream));
     HIP_CREATE(hipMemcpyAsync(b->d_bc, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    b->bc_tabs.push_back({cfg->adam_beta_1, cfg->adam_beta_2, b->d_bc});
+    for (int p = 0; p < n_problems; ++p)
+        if (int rc = RpgdFamily::hyper_block(b, p)) { g_create_error = "ctk_rpgd_batch_create: " + b->err; return rc; }
 
     std::vector<CtkRpgdBatchDesc> desc(Bz);
     for (int p = 0; p < n_problems; ++p) {
@@ -2276,10 +2536,19 @@ int ctk_rpgd_batch_reset(ctk_rpgd_batch* b, int n_ids, const int32_t* ids, const
         q.draws = d_draws ? d_draws + (size_t)j * per : nullptr;
     }
     BHIP_TRY(b, hipMemcpyAsync(b->d_steps, b->h_steps, (size_t)n * sizeof(CtkRpgdBatchStep), hipMemcpyHostToDevice, b->stream));
-    const RolloutArgs a = rpgd_batch_args(b);
-    const RpgdFusedWarm f = rpgd_batch_warm(b);
+    RolloutArgs a = rpgd_batch_args(b);
+    RpgdFusedWarm f = rpgd_batch_warm(b);
     for (int done = 0; done < n;) {                    // ONE launch for the call (more only past the grid's y limit)
-        const int cnt = std::min(RPGD_BATCH_MAX_GRID_Y, n - done);
+        // ... but with per-problem hyper-parameters one per listed problem: the reset kernel takes the sampling constants and the
+        // limits by value, and a problem's draws are mapped with ITS values (a reset is not a step: no form of its own for it)
+        const int cnt = b->fhyper ? 1 : std::min(RPGD_BATCH_MAX_GRID_Y, n - done);
+        if (b->fhyper) {
+            const int p = ids ? ids[done] : done;
+            const float* r = b->frow_of(p);
+            f.sample_stdev = r[CTK_RPGD_HYPER_SAMPLE_STDEV]; f.sample_mean = r[CTK_RPGD_HYPER_SAMPLE_MEAN];
+            f.sample_min = r[CTK_RPGD_HYPER_UNIFORM_DIST_MIN]; f.sample_max = r[CTK_RPGD_HYPER_UNIFORM_DIST_MAX];
+            for (int c = 0; c < b->C; ++c) { a.lo[c] = b->flow(p)[c]; a.hi[c] = b->fhigh(p)[c]; }
+        }
         BHIP_TRY(b, ctk_launch_rpgd_batch_reset(b->stream, a, f, b->d_desc, b->d_steps + done, cnt));
         done += cnt;
     }

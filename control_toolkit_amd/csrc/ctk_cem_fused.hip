@@ -331,3 +331,76 @@ hipError_t ctk_launch_cem_batch(hipStream_t st, int env, const float* params, fl
     });
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// The PER-PROBLEM-HYPER-PARAMETER form of the batch kernel (include/ctk_hip_family_hyper.h: ctk_cem_problem_set_hyper / _set_limits),
+// defined LAST in this file with its launcher, so that every kernel that was here before keeps its text.  The prologue and the body of
+// ctk_cem_batch_pp, statement for statement; ctk_cem_batch_hyp.inc takes, besides k, the problem's cem_best_k, cem_stdev_min,
+// cem_initial_action_stdev, the middle of its limits and the limits from the SECOND part of the element behind the step records
+// ([K | CtkCemBatchHyper], by record index as _pp's k: blockIdx.y alone, uniform, scalar loads).  All workgroups of a problem read
+// the same element, so each selects the same K rows and refits with the same 1 / K: the progress argument above ctk_cem_batch stands
+// as written — this form adds no wait, atomic or hand-off.
+// ---------------------------------------------------------------------------------------------
+struct alignas(16) CtkCemBatchHyper {
+    int32_t K;                          // cem_best_k
+    float std_min, init_std;            // cem_stdev_min, cem_initial_action_stdev
+    uint32_t pad;
+    float mid[CTK_MAX_INPUTS];          // 0.5f * (lo + hi), the launcher's expression, formed on the host
+    float lo[CTK_MAX_INPUTS], hi[CTK_MAX_INPUTS];
+};
+static_assert(sizeof(CtkCemBatchHyper) % 16 == 0, "the elements behind the step records stay 16-byte aligned");
+template <int ENV>
+struct CtkCemKhStride {
+    static constexpr size_t value = CtkBatchKStride<ENV>::value + sizeof(CtkCemBatchHyper);
+};
+
+template <int ENV, bool WTRAJ>
+__global__ __launch_bounds__(CF_BLOCK) void ctk_cem_batch_hp(const CtkCemBatchDesc* __restrict__ desc, const CtkCemBatchStep* __restrict__ steps,
+                                                             int N_, int H_, int P_, uint32_t pmagic_, int nblk_,
+                                                             const unsigned char* __restrict__ kh_steps, RolloutArgs a_tpl, CemFusedK cf_tpl) {
+    using E = Env<ENV>;
+    constexpr int C = E::C, S = E::S;
+    extern __shared__ float lds[];
+#define CTK_CEM_BATCH_HP
+#include "ctk_cem_batch_pro.inc"
+#undef CTK_CEM_BATCH_HP
+#include "ctk_cem_batch_hyp.inc"
+#include "ctk_cem_body.inc"
+}
+
+size_t ctk_cem_batch_hyper_bytes() { return sizeof(CtkCemBatchHyper); }
+size_t ctk_cem_batch_kh_stride(int env) {
+    size_t stride = 0;
+    CTK_FOR_ENV(env, EV, { stride = CtkCemKhStride<EV>::value; });
+    return stride;
+}
+void ctk_cem_batch_fill_hyper(void* dst, int K, float std_min, float init_std, const float* lo, const float* hi, int C) {
+    CtkCemBatchHyper e{};
+    e.K = K; e.std_min = std_min; e.init_std = init_std;
+    for (int i = 0; i < C; ++i) { e.lo[i] = lo[i]; e.hi[i] = hi[i]; e.mid[i] = 0.5f * (lo[i] + hi[i]); }   // ctk_launch_cem_batch's expression
+    __builtin_memcpy(dst, &e, sizeof(e));
+}
+const char* ctk_cem_batch_hp_name(int env, bool log) { return ctk_kernel_name("ctk_cem_batch_hp<%d, %4$s>", env, 0, 0, log ? "true" : "false"); }
+
+hipError_t ctk_launch_cem_batch_hp(hipStream_t st, int env, const RolloutArgs& a_in, const CemFusedLaunch& c, const CtkCemBatchDesc* desc_dev,
+                                   const CtkCemBatchStep* steps_dev, int n_problems, bool log, const void* kh_steps_dev) {
+    const int nblk = ctk_cem_fused_blocks(a_in.N);
+    if (n_problems < 1 || nblk > CTK_CEM_FUSED_MAX_BLOCKS || !kh_steps_dev) return hipErrorInvalidValue;
+    const dim3 grid(nblk, n_problems), block(CF_BLOCK);
+    CTK_FOR_ENV(env, EV, {
+        using E = Env<EV>;
+        const int HC = a_in.H * E::C;
+        const RolloutArgs a = ctk_rollout_args(a_in, E::C, HC);
+        CemFusedK cf{};                                // K, std_min, init_std and mid[] come from the elements; std_max is a handle's
+        cf.nblk = nblk; cf.per_it = (unsigned long long)a.N * HC;
+        cf.std_max = c.std_max;
+        cf.timeout_ticks = (unsigned long long)(c.timeout_s * 1.0e8);
+        const size_t lds = ctk_cem_fused_lds(a.N, HC);
+        if (lds > 128 * 1024) return hipErrorInvalidValue;
+        ctk_with_bool(log, [&](auto log_c) {
+            hipLaunchKernelGGL((ctk_cem_batch_hp<EV, decltype(log_c)::value>), grid, block, lds, st, desc_dev, steps_dev, a.N, a.H, a.P, a.p_magic, nblk,
+                               static_cast<const unsigned char*>(kh_steps_dev), a, cf);
+        });
+    });
+    return hipGetLastError();
+}

@@ -1,7 +1,11 @@
 // ctk_g_rpgd_batch_epi.inc — what follows ctk_g_rpgd_body.inc in both forms of the batched RPGD step (ctk_generic.hip: ctk_g_rpgd_batch,
 // ctk_g_rpgd_batch_pp): the keep-k selection and the warm start of the problem (ctk_rpgd_warm.h: rpgd_fused_tail), described by the step
-// record and the descriptor.  Expects what ctk_g_rpgd_batch_pro.inc and the body leave, and fw_tpl.
+// record and the descriptor.  Expects what ctk_g_rpgd_batch_pro.inc and the body leave, and fw_tpl; under CTK_RPGD_BATCH_HP also hy
+// (ctk_g_rpgd_batch_hyp.inc), whose sampling constants replace the launcher's.
     FusedWarm fw = fw_tpl;                         // K, P, shift_previous, the sampling constants, interp (launcher)
+#ifdef CTK_RPGD_BATCH_HP
+    fw.w.sample_stdev = hy.sample_stdev; fw.w.sample_mean = hy.sample_mean; fw.w.sample_min = hy.sample_min; fw.w.sample_max = hy.sample_max;
+#endif
     fw.idx_out = d.idx;
     fw.w.n_new = rec.resample ? a.N - fw.K : 0;
     fw.w.gather = rec.resample ? 1 : 0;

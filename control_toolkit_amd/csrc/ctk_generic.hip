@@ -355,12 +355,13 @@ size_t ctk_g_rpgd_scratch_floats(int env, int N, int H) {
     return (size_t)((N + G_TRAJ - 1) / G_TRAJ) * H * NT * 64;
 }
 
+static AdamK ctk_g_adam_k(float lr, float b1, float b2, float eps, float clip, int rule);   // below, with the _hp form's launcher
 const char* ctk_g_rpgd_descent_name(int env) { return ctk_kernel_name("ctk_g_rpgd_descent<%d>", env); }
 
 hipError_t ctk_launch_g_rpgd_descent(hipStream_t st, int env, const RolloutArgs& a_in, const float* params, float dt, int isteps, float lr,
                                      float b1, float b2, float eps, float clip, float* Q, float* m, float* v, const float* bc_table,
                                      int bc_len, int t0, int iters, float* scratch, hipEvent_t e0, hipEvent_t e1, int rule) {
-    AdamK ad{lr, b1, b2, (float)(1.0 - (double)b1), (float)(1.0 - (double)b2), eps, clip, rule};
+    const AdamK ad = ctk_g_adam_k(lr, b1, b2, eps, clip, rule);
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
         const RolloutArgs a = ctk_descent_args(a_in, E::C);
@@ -383,7 +384,7 @@ hipError_t ctk_launch_g_rpgd_batch(hipStream_t st, int env, const RolloutArgs& a
                                    float b1, float b2, float eps, float clip, int rule, const float* bc_table, int bc_len,
                                    const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems,
                                    const void* k_steps_dev) {
-    AdamK ad{lr, b1, b2, (float)(1.0 - (double)b1), (float)(1.0 - (double)b2), eps, clip, rule};
+    const AdamK ad = ctk_g_adam_k(lr, b1, b2, eps, clip, rule);
     CTK_FOR_ENV(env, EV, {
         using E = Env<EV>;
         const RolloutArgs a = ctk_descent_args(a_in, E::C);
@@ -402,6 +403,80 @@ hipError_t ctk_launch_g_rpgd_batch(hipStream_t st, int env, const RolloutArgs& a
             const typename E::K k = E::derive(params, dt, isteps);
             hipLaunchKernelGGL((ctk_g_rpgd_batch<EV>), grid, block, lds, st, a, k, ad, bc_table, bc_len, tape_in_lds ? 1 : 0, fw, desc_dev, steps_dev);
         }
+    });
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The PER-PROBLEM-HYPER-PARAMETER form of the batched RPGD step (include/ctk_hip_family_hyper.h: ctk_rpgd_problem_set_hyper / _set_limits),
+// defined LAST in this file with its launcher, so that every kernel that was here before keeps its text.  The prologue, body and tail
+// of ctk_g_rpgd_batch_pp, statement for statement; ctk_g_rpgd_batch_hyp.inc takes, besides k, the problem's Adam constants, the address
+// of the bias-correction table of its betas, its sampling constants and its limits from the SECOND part of the element behind the step
+// records ([K | CtkRpgdBatchHyper], by record index as _pp's k).  No workgroup waits for another in this form either.
+// ---------------------------------------------------------------------------------------------------------------
+struct alignas(16) CtkRpgdBatchHyper {
+    AdamK ad;                           // ctk_g_adam_k of the problem's learning_rate, betas, epsilon, clip and the batch's rule
+    const float* bc_table;              // device table of the problem's (beta_1, beta_2): adam_bias_corrections, one per distinct pair
+    uint64_t pad;
+    float sample_stdev, sample_mean, sample_min, sample_max;
+    float lo[CTK_MAX_INPUTS], hi[CTK_MAX_INPUTS];
+};
+static_assert(sizeof(AdamK) == 32 && sizeof(CtkRpgdBatchHyper) % 16 == 0, "the elements behind the step records stay 16-byte aligned");
+template <int ENV>
+struct CtkRpgdKhStride {
+    static constexpr size_t value = CtkBatchKStride<ENV>::value + sizeof(CtkRpgdBatchHyper);
+};
+
+template <int ENV>
+__global__ __launch_bounds__(GR_BLOCK) void ctk_g_rpgd_batch_hp(RolloutArgs a_tpl, const unsigned char* __restrict__ kh_steps, int bc_len, int tape_in_lds,
+                                                               FusedWarm fw_tpl, const CtkRpgdBatchDesc* __restrict__ desc,
+                                                               const CtkRpgdBatchStep* __restrict__ steps) {
+#define CTK_RPGD_BATCH_HP
+#include "ctk_g_rpgd_batch_pro.inc"
+#include "ctk_g_rpgd_batch_hyp.inc"
+#include "ctk_g_rpgd_body.inc"
+#include "ctk_g_rpgd_batch_epi.inc"
+#undef CTK_RPGD_BATCH_HP
+}
+
+// the Adam constants of every template launch (ctk_launch_g_rpgd_descent, ctk_launch_g_rpgd_batch) and of a problem's hyper block
+static AdamK ctk_g_adam_k(float lr, float b1, float b2, float eps, float clip, int rule) {
+    return AdamK{lr, b1, b2, (float)(1.0 - (double)b1), (float)(1.0 - (double)b2), eps, clip, rule};
+}
+
+size_t ctk_rpgd_batch_hyper_bytes() { return sizeof(CtkRpgdBatchHyper); }
+size_t ctk_rpgd_batch_kh_stride(int env) {
+    size_t stride = 0;
+    CTK_FOR_ENV(env, EV, { stride = CtkRpgdKhStride<EV>::value; });
+    return stride;
+}
+void ctk_rpgd_batch_fill_hyper(void* dst, float lr, float b1, float b2, float eps, float clip, int rule, const float* bc_table_dev,
+                               float sample_stdev, float sample_mean, float sample_min, float sample_max, const float* lo, const float* hi, int C) {
+    CtkRpgdBatchHyper e{};
+    e.ad = ctk_g_adam_k(lr, b1, b2, eps, clip, rule);
+    e.bc_table = bc_table_dev;
+    e.sample_stdev = sample_stdev; e.sample_mean = sample_mean; e.sample_min = sample_min; e.sample_max = sample_max;
+    for (int i = 0; i < C; ++i) { e.lo[i] = lo[i]; e.hi[i] = hi[i]; }
+    __builtin_memcpy(dst, &e, sizeof(e));
+}
+const char* ctk_g_rpgd_batch_hp_name(int env) { return ctk_kernel_name("ctk_g_rpgd_batch_hp<%d>", env); }
+
+hipError_t ctk_launch_g_rpgd_batch_hp(hipStream_t st, int env, const RolloutArgs& a_in, int bc_len, const RpgdFusedWarm& f,
+                                      const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems,
+                                      const void* kh_steps_dev) {
+    if (n_problems < 1 || !kh_steps_dev) return hipErrorInvalidValue;
+    CTK_FOR_ENV(env, EV, {
+        using E = Env<EV>;
+        const RolloutArgs a = ctk_descent_args(a_in, E::C);
+        bool tape_in_lds = false;
+        const size_t lds = ctk_g_rpgd_descent_lds(env, a.H, &tape_in_lds);
+        FusedWarm fw{};                                // as ctk_launch_g_rpgd_batch; the sampling constants come from the elements
+        fw.enabled = 1; fw.K = f.K;
+        fw.w = WarmArgs{a.N, a.H, f.P, 0, 0, f.shift_previous, f.sampling_distribution, 0, 0.0f, 0.0f, 0.0f, 0.0f, f.whole_space, nullptr, 0, 0, 0};
+        fw.p.interp = f.interp;
+        const dim3 grid(1, n_problems), block(GR_BLOCK);
+        hipLaunchKernelGGL((ctk_g_rpgd_batch_hp<EV>), grid, block, lds, st, a, static_cast<const unsigned char*>(kh_steps_dev), bc_len,
+                           tape_in_lds ? 1 : 0, fw, desc_dev, steps_dev);
     });
     return hipGetLastError();
 }

@@ -464,6 +464,17 @@ const char* ctk_cem_batch_name(int env, bool log, bool per_problem = false);
 hipError_t ctk_launch_cem_batch(hipStream_t st, int env, const float* params, float dt, int isteps, const RolloutArgs& a, const CemFusedLaunch& c,
                                 const CtkCemBatchDesc* desc_dev, const CtkCemBatchStep* steps_dev, int n_problems, bool log,
                                 const void* k_steps_dev = nullptr);
+// The form with per-problem hyper-parameters and limits (include/ctk_hip_family_hyper.h; ctk_cem_batch_hp<ENV, TRAJ>).  Behind the step
+// records lies one two-part element per record, in record order, [K (ctk_mppi_batch_k_stride bytes) | hyper block] at stride
+// ctk_cem_batch_kh_stride(env): the block (cem_best_k, the two deviations, the middle and the limits of every input) stands in place
+// of c.K, c.std_min, c.init_std and a's limits.  ctk_cem_batch_fill_hyper writes a block; the middle is the launcher's 0.5f * (lo + hi).
+size_t ctk_cem_batch_hyper_bytes();
+size_t ctk_cem_batch_kh_stride(int env);
+void ctk_cem_batch_fill_hyper(void* dst, int K, float std_min, float init_std, const float* lo, const float* hi, int C);
+const char* ctk_cem_batch_hp_name(int env, bool log);
+// c: timeout_s only; kh_steps_dev: element j belongs to record j of steps_dev
+hipError_t ctk_launch_cem_batch_hp(hipStream_t st, int env, const RolloutArgs& a, const CemFusedLaunch& c, const CtkCemBatchDesc* desc_dev,
+                                   const CtkCemBatchStep* steps_dev, int n_problems, bool log, const void* kh_steps_dev);
 int ctk_cem_fused_blocks(int N);        // workgroups of a problem (64 rollouts each)
 size_t ctk_cem_fused_lds(int N, int H); // dynamic LDS of a launch, bytes
 
@@ -581,6 +592,19 @@ hipError_t ctk_launch_g_rpgd_batch(hipStream_t st, int env, const RolloutArgs& a
                                    float b1, float b2, float eps, float clip, int rule, const float* bc_table, int bc_len,
                                    const RpgdFusedWarm& f, const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems,
                                    const void* k_steps_dev = nullptr);
+// The form with per-problem hyper-parameters and limits (include/ctk_hip_family_hyper.h; ctk_g_rpgd_batch_hp<ENV>).  Behind the step
+// records lies one two-part element per record, in record order, [K (ctk_mppi_batch_k_stride bytes) | hyper block] at stride
+// ctk_rpgd_batch_kh_stride(env): the block (the Adam constants, formed by the function behind every launch's; the device address of the
+// bias-correction table of the problem's betas; the four sampling constants; the limits) stands in place of lr .. clip, bc_table, f's
+// sampling constants and a's limits.  ctk_rpgd_batch_fill_hyper writes a block.
+size_t ctk_rpgd_batch_hyper_bytes();
+size_t ctk_rpgd_batch_kh_stride(int env);
+void ctk_rpgd_batch_fill_hyper(void* dst, float lr, float b1, float b2, float eps, float clip, int rule, const float* bc_table_dev,
+                               float sample_stdev, float sample_mean, float sample_min, float sample_max, const float* lo, const float* hi, int C);
+const char* ctk_g_rpgd_batch_hp_name(int env);
+hipError_t ctk_launch_g_rpgd_batch_hp(hipStream_t st, int env, const RolloutArgs& a, int bc_len, const RpgdFusedWarm& f,
+                                      const CtkRpgdBatchDesc* desc_dev, const CtkRpgdBatchStep* steps_dev, int n_problems,
+                                      const void* kh_steps_dev);
 
 // ---- ctk_generic_net.hip : the template kernels with a network predictor (net = CTK_PRED_MLP | CTK_PRED_GRU; ctk_net.h) -----
 // wperm: the policy's per-lane operand tables (forward | reverse), followed by the GRU's carried hidden state [64]

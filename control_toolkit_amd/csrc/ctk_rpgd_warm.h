@@ -28,6 +28,11 @@ struct WarmArgs {
                            // (optimizer_gradient_tf.py:137-144) instead of a repeat of the last input
 };
 
+// per-problem limits where they lie in device memory (ctk_g_rpgd_batch_hp): read as lim.lo[c] / lim.hi[c], like a RolloutArgs'.  A
+// local copy indexed by a lane's c would live in scratch; these are loads from the element the host wrote, as the other forms' are
+// loads from the kernel-argument segment
+struct RpgdLimits { const float* lo; const float* hi; };
+
 // pointers of one warm start (old population -> new population)
 struct WarmPtrs {
     const float* draws; const int* idx; const float* Q_old; const float* m_old; const float* v_old; const float* ages_old;
@@ -38,8 +43,10 @@ struct WarmPtrs {
 // element `gid` (= (row * H + h) * C + c) of the new population [N,H,C]; elements 0..H*C-1 also copy the best plan out and
 // element 0 publishes u.  C = a.C control inputs: the reference's tensors are [N,H,C] throughout (optimizer_rpgd.py:275-296,
 // :377-379, :454-513), a step is C contiguous floats.
-// lim: the RolloutArgs whose limits lo / hi are read (a itself; the batch kernels pass their shared kernel argument, see ctk_g_rpgd_body.inc)
-CTK_DEV void rpgd_warm_element(const WarmArgs& w, const RolloutArgs& a, const RolloutArgs& lim, const WarmPtrs& p, int gid) {
+// lim: whose limits lo / hi are read — a RolloutArgs (a itself; the batch kernels pass their shared kernel argument, see
+// ctk_g_rpgd_body.inc) or, in the batch form with per-problem limits, two pointers into device memory (RpgdLimits)
+template <class Lim>
+CTK_DEV void rpgd_warm_element(const WarmArgs& w, const RolloutArgs& a, const Lim& lim, const WarmPtrs& p, int gid) {
     const float* __restrict__ draws = p.draws; const int* __restrict__ idx = p.idx;
     const float* __restrict__ Q_old = p.Q_old; const float* __restrict__ m_old = p.m_old; const float* __restrict__ v_old = p.v_old;
     const float* __restrict__ ages_old = p.ages_old;
@@ -135,7 +142,8 @@ struct FusedWarm {
 
 // keep-k selection + warm start as the tail of a descent launch whose ONE workgroup holds the whole population.  HC = H * a.C floats per
 // plan; g_s: 128 dead words of LDS (the gradient tile, running into the clip scales behind it when HC == 1)
-CTK_DEV void rpgd_fused_tail(const RolloutArgs& a, const RolloutArgs& lim, const FusedWarm& fw, float* g_s, int t, int HC) {
+template <class Lim>
+CTK_DEV void rpgd_fused_tail(const RolloutArgs& a, const Lim& lim, const FusedWarm& fw, float* g_s, int t, int HC) {
     __threadfence();
     __syncthreads();                                   // Q, m, v, J of this launch are visible to every thread of the block
     uint32_t* key_s = reinterpret_cast<uint32_t*>(g_s);   // g_s is dead: [64] keys, then [64] indices

@@ -805,6 +805,8 @@ int ctk_gru_batch_fit(int num_rollouts, int mpc_horizon, int period_interpolatio
 #include "ctk_hip_gru.h"
 /* per-problem MPPI hyper-parameters and input limits of the three MPPI batches */
 #include "ctk_hip_hyper.h"
+/* ... and the CEM and RPGD batches' own */
+#include "ctk_hip_family_hyper.h"
 /* the launched-ahead form of the MPPI step: its switch, fuse and counters */
 #include "ctk_hip_ahead.h"
 #endif /* CTK_HIP_H */
