@@ -6,7 +6,7 @@ this package is the host-side mirror of the reference's plugin interface
 (`template_optimizer`, `template_controller`, `controller_mpc`) so that
 `optimizer: mppi-hip` selects it with no edits to the caller.  There is no CPU fallback.
 """
-from ._capi import CEM_HYPERS, FAMILY_HYPER_SYMBOLS, HYPERS, RPGD_HYPERS, BatchClosedLoop, BatchHypers, Episodes, FamilyHypers, CtkCemBatch, CtkEngine, CtkError, CtkMppiBatch, CtkMppiGruBatch, CtkMppiMlpBatch, CtkRpgdBatch, batch_hyper_args, family_hyper_args, library_path, load_library  # noqa: F401
+from ._capi import CEM_HYPERS, FAMILY_HYPER_SYMBOLS, HYPERS, RPGD_HYPERS, BatchClosedLoop, BatchHypers, BatchRollout, Episodes, FamilyHypers, CtkCemBatch, CtkEngine, CtkError, CtkMppiBatch, CtkMppiGruBatch, CtkMppiMlpBatch, CtkRpgdBatch, batch_hyper_args, batch_rollout_args, family_hyper_args, library_path, load_library  # noqa: F401
 from .computation_library import HipLibrary  # noqa: F401
 
-__all__ = ["BatchClosedLoop", "BatchHypers", "CEM_HYPERS", "Episodes", "FAMILY_HYPER_SYMBOLS", "FamilyHypers", "RPGD_HYPERS", "family_hyper_args", "CtkCemBatch", "CtkEngine", "CtkError", "CtkMppiBatch", "CtkMppiGruBatch", "CtkMppiMlpBatch", "CtkRpgdBatch", "HipLibrary", "HYPERS", "batch_hyper_args", "library_path", "load_library"]
+__all__ = ["BatchClosedLoop", "BatchHypers", "BatchRollout", "batch_rollout_args", "CEM_HYPERS", "Episodes", "FAMILY_HYPER_SYMBOLS", "FamilyHypers", "RPGD_HYPERS", "family_hyper_args", "CtkCemBatch", "CtkEngine", "CtkError", "CtkMppiBatch", "CtkMppiGruBatch", "CtkMppiMlpBatch", "CtkRpgdBatch", "HipLibrary", "HYPERS", "batch_hyper_args", "library_path", "load_library"]

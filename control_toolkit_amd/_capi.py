@@ -244,6 +244,13 @@ for _batch, _problem in _BATCH_FAMILIES[3:]:
     FAMILY_HYPER_SYMBOLS[f"{_batch}_set_hyper"] = (C.c_int, [_H, C.c_int, C.c_float])
 
 
+# rollouts of caller-supplied plans on every batch family (include/ctk_hip_rollout.h, which ctk_hip.h includes): one signature under the
+# five families' names; a table of its own, bound with the others.  ROLLOUT_MODELS: enum ctk_rollout_model.
+ROLLOUT_MODELS = {"controller": 0, "plant": 1}
+_BATCH_ROLLOUT = (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p])
+ROLLOUT_SYMBOLS = {f"{_batch}_rollout": _BATCH_ROLLOUT for _batch, _problem in _BATCH_FAMILIES}
+
+
 # the launched-ahead form of the MPPI step (include/ctk_hip_ahead.h, which ctk_hip.h includes): a table of its own, bound with the others
 class AheadRule(C.Structure):
     _fields_ = [("streak", C.c_int32), ("armed", C.c_int32), ("untaken", C.c_int32), ("arms", C.c_int32)]
@@ -307,7 +314,8 @@ def _bind_library(path: str):
     except OSError as e:
         raise CtkError(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SYMBOLS.items()) + list(RUN_SYMBOLS.items()) + list(EPISODE_SYMBOLS.items()) + list(LOOP_SYMBOLS.items()) + \
-            list(GRU_LOOP_SYMBOLS.items()) + list(HYPER_SYMBOLS.items()) + list(FAMILY_HYPER_SYMBOLS.items()) + list(AHEAD_SYMBOLS.items()):
+            list(GRU_LOOP_SYMBOLS.items()) + list(HYPER_SYMBOLS.items()) + list(FAMILY_HYPER_SYMBOLS.items()) + list(AHEAD_SYMBOLS.items()) + \
+            list(ROLLOUT_SYMBOLS.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctk_abi_version() != 6:
@@ -917,6 +925,71 @@ def batch_episode_args(num_problems: int, S: int, Cn: int, states, steps, u_prev
     return idv, n, sub
 
 
+def batch_rollout_args(num_problems: int, S: int, Cn: int, H: int, num_rollouts: int, states, plans=None, u_prev=None, ids=None,
+                       model="controller", plant_substeps=None):
+    """Checks the arguments of BatchRollout.rollout without touching a device, the way batch_step_args checks a step's.  ids: None (all
+    problems) or problem indices in any order, each at most once (the rows of a rollout are independent).  states [n, S]; u_prev None
+    (zeros), a scalar, [C] or [n, C]; plans None (every listed problem's own current plan), an int device pointer to [n, M, H, C] —
+    then M is taken as 1 unless plans is a (pointer, M) pair —, [n, M, H, C], or [M, H, C] (for C == 1 also without the last axis),
+    which is given to every listed problem; 1 <= M <= num_rollouts; model "controller" or "plant"; plant_substeps None or an integer
+    >= 1, for the plant model only.  Returns (ids as int32 or None, n, states fp32 [n, S], u_prev fp32 [n, C] or None, plans: None,
+    the int pointer or fp32 [n, M, H, C], M, the model's number, the sub-step count as the library takes it)."""
+    idv = None
+    if ids is not None:
+        idv = np.ascontiguousarray(np.asarray(ids).reshape(-1))
+        if idv.size < 1 or not np.issubdtype(idv.dtype, np.integer):
+            raise ValueError("ids must be a non-empty list of problem indices (or None: all problems)")
+        if idv.min() < 0 or idv.max() >= num_problems:
+            raise ValueError(f"ids must lie in 0 .. {num_problems - 1} (the batch holds {num_problems} problems)")
+        if np.unique(idv).size != idv.size:
+            raise ValueError("ids must name each problem at most once (any order)")
+        idv = idv.astype(np.int32)
+    n = num_problems if idv is None else int(idv.size)
+    st = np.asarray(states)
+    if st.shape != (n, S) and not (n == 1 and st.shape == (S,)):
+        raise ValueError(f"states must have shape ({n}, {S}): one row per listed problem, got {tuple(st.shape)}")
+    st = _f32(st).reshape(n, S)
+    up = None
+    if u_prev is not None:
+        up = np.asarray(u_prev, dtype=np.float32)
+        if up.ndim == 0 or up.shape == (Cn,):
+            up = np.broadcast_to(up, (n, Cn))
+        elif Cn == 1 and up.shape == (n,):
+            up = up.reshape(n, 1)
+        if up.shape != (n, Cn):
+            raise ValueError(f"u_prev must be a scalar, ({Cn},) or ({n}, {Cn}): one row per listed problem, got {tuple(np.shape(u_prev))}")
+        up = np.ascontiguousarray(up, dtype=np.float32)
+    if model not in ROLLOUT_MODELS:
+        raise ValueError(f"model must be one of {sorted(ROLLOUT_MODELS)}, got {model!r}")
+    sub = 0
+    if plant_substeps is not None:
+        if model != "plant":
+            raise ValueError("plant_substeps belongs to model='plant' (the controller model rolls out with the controller's intermediate_steps)")
+        if isinstance(plant_substeps, bool) or not isinstance(plant_substeps, (int, np.integer)) or plant_substeps < 1:
+            raise ValueError(f"plant_substeps must be an integer >= 1 or None (the controller's intermediate_steps), got {plant_substeps!r}")
+        sub = int(plant_substeps)
+    M = 1
+    if plans is not None:
+        if isinstance(plans, tuple) and len(plans) == 2 and type(plans[0]) is int:
+            plans, M = plans[0], plans[1]
+            if isinstance(M, bool) or not isinstance(M, (int, np.integer)):
+                raise ValueError(f"a device-pointer plans is (pointer, M) with an integer M, got M == {M!r}")
+            M = int(M)
+        elif type(plans) is not int:
+            pl = np.asarray(plans, dtype=np.float32)
+            if Cn == 1 and pl.ndim in (2, 3) and pl.shape[-1] == H and not (pl.ndim == 3 and pl.shape[1:] == (H, 1)):
+                pl = pl[..., None]
+            if pl.ndim == 3 and pl.shape[1:] == (H, Cn):
+                pl = np.broadcast_to(pl, (n,) + pl.shape)
+            if pl.ndim != 4 or pl.shape[0] != n or pl.shape[2:] != (H, Cn):
+                raise ValueError(f"plans must have shape ({n}, M, {H}, {Cn}) or (M, {H}, {Cn}) for every listed problem, got {tuple(np.shape(plans))}")
+            M = int(pl.shape[1])
+            plans = np.ascontiguousarray(pl, dtype=np.float32)
+        if not 1 <= M <= num_rollouts:
+            raise ValueError(f"a rollout takes 1 <= M <= num_rollouts ({num_rollouts}) plans per problem, got M == {M}")
+    return idv, n, st, up, plans, M, ROLLOUT_MODELS[model], sub
+
+
 class Episodes(NamedTuple):
     """what BatchClosedLoop.episodes returns: the true states [n, steps + 1, S], what the controllers were given [n, steps + 1, S], the
     inputs [n, steps, C] and the realised stage costs [n, steps]"""
@@ -1223,6 +1296,12 @@ class _CtkBatch:
     def dominant_kernel(self) -> str:
         return self._b.dominant_kernel(self._h).decode()
 
+    @property
+    def rollouts(self) -> "BatchRollout":
+        """rollouts of caller-supplied plans, every listed problem in one launch: rollouts.rollout(S, plans), .optimal_trajectory(S)
+        (BatchRollout).  A view of this batch, as closed_loop and hypers are: it owns nothing and is not kept."""
+        return BatchRollout(self)
+
 
 class CtkMppiBatch(_CtkBatch):
     """Owns one ctk_batch: num_problems independent MPPI controllers of ONE configuration (the MPPI keywords of CtkEngine), stepped by
@@ -1301,6 +1380,47 @@ class CtkMppiBatch(_CtkBatch):
 
     def get_state(self, problem: int) -> np.ndarray:
         return self._get_state(problem, self.H * self.C + self.C)
+
+
+# ---- rollouts of caller-supplied plans on a batch (include/ctk_hip_rollout.h) ------------------------------------------------------------------
+class BatchRollout:
+    """batch.rollouts of any of the five batch classes, or BatchRollout(batch): predictor.predict_core + cost.get_trajectory_cost of
+    caller-supplied plans for every listed problem in ONE launch (kernels ctk_batch_rollout<ENV, PRED, TRAJ> / ctk_g_batch_rollout<ENV, TRAJ>).
+    Row j equals, bit for bit, CtkEngine(<the batch's configuration>).rollout(S[j], plans[j], u_prev[j]) of an engine that was given
+    problem ids[j]'s parameters, weights and hidden state.  A view of the batch: it owns nothing, and a rollout changes nothing — no
+    plan, output, J / Q / TRAJ buffer, Philox position, sequence number or hidden state of any problem."""
+
+    CALLS = ("rollout", "optimal_trajectory")
+
+    def __init__(self, batch):
+        self._batch = batch
+
+    def rollout(self, S, plans=None, u_prev=None, ids=None, model="controller", plant_substeps=None, want_traj=True):
+        """S [n, num_states], one row per problem in ids (None: all; any order).  plans [n, M, H, C], or [M, H, C] given to every listed
+        problem (a robustness sweep over the problems' parameters), or None: every problem's own current plan (M = 1), read on the
+        device; a device pointer goes in as (int pointer, M).  Plans are taken as given, not clipped.  u_prev: the input before the
+        first one (None: zeros, as CtkEngine.rollout).  model "controller": each problem's own controller parameters, weights and hidden
+        state; "plant": the analytic plant of its closed loop (closed_loop.set_plant_params; plant_substeps Euler sub-steps, None =
+        intermediate_steps) — for an MLP or GRU batch, what the true plant does with the plan against what the network predicts.
+        Returns (traj [n, M, H + 1, num_states] or None, J [n, M])."""
+        b = self._batch
+        idv, n, st, up, plans, M, model_id, sub = batch_rollout_args(b.B, b.S, b.C, b.H, b.N, S, plans, u_prev, ids, model, plant_substeps)
+        if plans is None:
+            pp, loc = None, LOC_NONE
+        elif type(plans) is int:
+            pp, loc = plans, LOC_DEVICE
+        else:
+            pp, loc = plans.ctypes.data, LOC_HOST
+        traj = np.empty((n, M, b.H + 1, b.S), np.float32) if want_traj else None
+        J = np.empty((n, M), np.float32)
+        fn = getattr(b._lib, f"{b._BATCH}_rollout")
+        b._check(fn(b._h, n, _ptr(idv), _ptr(st), _ptr(up), pp, loc, M, model_id, sub, _ptr(traj), _ptr(J)))
+        return traj, J
+
+    def optimal_trajectory(self, S, ids=None) -> np.ndarray:
+        """[n, H + 1, num_states]: the trajectory every listed problem's current plan predicts from S — the reference's
+        optimal_trajectory (optimizer_mppi.py:199-202) for a whole batch"""
+        return self.rollout(S, None, ids=ids)[0][:, 0]
 
 
 # ---- per-problem MPPI hyper-parameters and input limits of an MPPI batch (include/ctk_hip_hyper.h) ----------------------------------------------

@@ -1,8 +1,8 @@
 // ctk_batch.hip — the batch families of the C ABI (include/ctk_hip.h, ctk_hip_run.h, ctk_hip_episode.h, ctk_hip_loop.h): ctk_batch_*, ctk_mlp_batch_*,
 // ctk_gru_batch_*, ctk_cem_batch_*, ctk_rpgd_batch_*.  The single handle is in ctk_api.hip; what the two files share is declared in ctk_host.h.
 // The file in order: the host core (BatchCore and the bodies every family shares), the two drivers — batch_step<F> for a step,
-// batch_closed_loop<F> for runs and episodes — and the two macros that write a family's C entries over them (CTK_BATCH_ENTRIES,
-// CTK_LOOP_ENTRIES); then each family: its struct, its trait F (MppiFamily, MlpFamily, GruFamily, CemFamily, RpgdFamily: what the drivers ask of
+// batch_closed_loop<F> for runs and episodes —, batch_rollout<F> for rollouts of caller-supplied plans (include/ctk_hip_rollout.h) and the
+// macros that write a family's C entries over them (CTK_BATCH_ENTRIES, CTK_LOOP_ENTRIES, CTK_ROLLOUT_ENTRY); then each family: its struct, its trait F (MppiFamily, MlpFamily, GruFamily, CemFamily, RpgdFamily: what the drivers ask of
 // it), and the entries that are its own (create, samples_needed, step, reset, read).  A message names the entry that was called: every
 // entry passes its exported name (`who`) to the body that builds the text, the MLP family included — it runs the MPPI family's code
 // under its own names.
@@ -78,7 +78,8 @@ struct BatchCore : PlantSide {
     float* h_u_dev = nullptr;
     float* d_samples = nullptr; size_t samples_cap = 0;   // staging for host-supplied draws
     float *d_J = nullptr, *d_Q = nullptr, *d_traj = nullptr;   // [B][N] | [B][N,H,C] | [B][N,H+1,S] (materialize_trajectories); RPGD has J alone
-    Owner own;                              // every device / pinned allocation of the batch, entered where it is made (ctk_host.h; batch_core_release)
+    float* d_zero_one = nullptr;            // [2][H,C] zeros | ones: base and scale of a rollout of given plans (batch_rollout; made at the first one)
+    Owner own;                             // every device / pinned allocation of the batch, entered where it is made (ctk_host.h; batch_core_release)
     std::vector<uint32_t> seq, call;        // [B] the sequence number of the problem's next step, its Philox position
     std::string err, dominant;
     float* u(int p) const { return d_u + (size_t)p * CTK_MAX_INPUTS; }
@@ -851,6 +852,138 @@ int plant_noise_set_position(BatchCore* b, const char* who, int problem, uint32_
     return CTK_OK;
 }
 
+// ---- rollouts of caller-supplied plans (include/ctk_hip_rollout.h: *_batch_rollout; kernels in ctk_batch_rollout.hip) ----
+// a rollout call: the entry's arguments
+struct RolloutCall {
+    const char* who;                        // the entry point, for the messages
+    int n; const int32_t* ids;
+    const float *S, *u_prev, *plans;
+    int plans_loc, m, model, plant_substeps;
+    float *traj_out, *J_out;
+};
+
+// Where the parts of the run buffer lie for a rollout of n records of m plans (bytes from its start; every part 16-aligned).  What
+// travels to the device in ONE transfer lies in front (up to `J`), what comes back in ONE copy behind it, and behind that what stays
+// on the device:
+//   records [n] | per-problem constants [kelems] | plans [n][m][H,C] (host plans only) || J [n][m] | trajectories [n][m][H+1][S] (if asked) ||
+//   the body's copy of the plans [n][m][H,C]
+struct RolloutLayout {
+    size_t k, plans, J, traj, Q, back, total;
+    RolloutLayout(const BatchCore* b, size_t kelems, int n, int m, bool host_plans, bool want_traj) {
+        auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        const size_t rows = (size_t)n * m;
+        k = (size_t)n * sizeof(CtkBatchRolloutRec);
+        plans = k + kelems * b->kstride;
+        J = plans + (host_plans ? up(rows * b->HC * sizeof(float)) : 0);
+        traj = J + up(rows * sizeof(float));
+        Q = traj + (want_traj ? up(rows * ((size_t)b->H + 1) * b->S * sizeof(float)) : 0);
+        back = Q;
+        total = Q + up(rows * b->HC * sizeof(float));
+    }
+};
+
+// The rollout of the listed problems' plans, for every family: the checks, n records (with the constants and the caller's plans behind
+// them) in ONE transfer, ONE launch, ONE copy back, ONE synchronisation.  It works in the run buffer, which no call keeps anything in:
+// the problems' J, Q, TRAJ, plans, outputs, hidden states, counters and Philox positions are not touched.  What is a family's own:
+//   rollout_pred(b)                      the predictor of model = controller (CTK_PRED_*)
+//   rollout_weights(b, &stride)          the per-problem network blocks and their stride in floats (nullptr: analytic)
+//   rollout_refuse(b, who, n, ids, own, net)   its refusals: a problem without weights where the network rolls out, an RPGD problem that
+//                                        was never reset where its own plan is asked for
+//   own_plan(b, p)                       where read(U_NOM, p) reads from
+// ids may come in any order here (rows are independent), but each problem once.
+template <class F>
+int batch_rollout(typename F::Batch* b, const RolloutCall& c) {
+    if (!b) return CTK_ERR_INVALID_ARGUMENT;
+    const std::string who = c.who;
+    if (!c.S) return bfail(b, CTK_ERR_INVALID_ARGUMENT, who + ": NULL states (one row per listed problem)");
+    int n = b->B;
+    if (c.ids) {
+        if (c.n < 1 || c.n > b->B) return bfail(b, CTK_ERR_INVALID_ARGUMENT, who + ": n must be 1 .. " + std::to_string(b->B) + " (the batch size)");
+        std::vector<unsigned char> seen((size_t)b->B, 0);
+        for (int j = 0; j < c.n; ++j) {
+            if (c.ids[j] < 0 || c.ids[j] >= b->B)
+                return bfail(b, CTK_ERR_INVALID_ARGUMENT, who + ": problem index " + std::to_string(c.ids[j]) + " is outside 0 .. " + std::to_string(b->B - 1));
+            if (seen[(size_t)c.ids[j]]++) return bfail(b, CTK_ERR_INVALID_ARGUMENT, who + ": problem " + std::to_string(c.ids[j]) + " is listed twice");
+        }
+        n = c.n;
+    }
+    const int32_t* ids = c.ids;
+    if (c.m < 1 || c.m > b->N)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, who + ": need 1 <= m <= num_rollouts (" + std::to_string(b->N) + "), the bound of a handle's ctk_rollout (m == " + std::to_string(c.m) + ")");
+    const bool own = c.plans == nullptr;
+    if (own && c.m != 1) return bfail(b, CTK_ERR_INVALID_ARGUMENT, who + ": plans == NULL rolls out every listed problem's own current plan: m must be 1");
+    if (!own && c.plans_loc != CTK_LOC_HOST && c.plans_loc != CTK_LOC_DEVICE) return bfail(b, CTK_ERR_INVALID_ARGUMENT, who + ": plans_loc must be CTK_LOC_HOST or CTK_LOC_DEVICE");
+    if (c.model != CTK_ROLLOUT_MODEL_CONTROLLER && c.model != CTK_ROLLOUT_MODEL_PLANT)
+        return bfail(b, CTK_ERR_INVALID_ARGUMENT, who + ": model is CTK_ROLLOUT_MODEL_CONTROLLER or CTK_ROLLOUT_MODEL_PLANT, not " + std::to_string(c.model));
+    const bool plant = c.model == CTK_ROLLOUT_MODEL_PLANT;
+    int sub = 0;
+    if (plant) if (int rc = batch_substeps(b, c.who, c.plant_substeps, &sub)) return rc;
+    const int pred = plant ? CTK_PRED_ODE : F::rollout_pred(b);
+    if (int rc = F::rollout_refuse(b, c.who, n, ids, own, pred != CTK_PRED_ODE)) return rc;
+    BHIP_TRY(b, hipSetDevice(b->cfg.device));
+    const int S = b->S, C = b->C, HC = b->HC, m = c.m;
+    if (!b->d_zero_one) {                              // base 0, scale 1: once per batch
+        std::vector<float> zo((size_t)2 * HC, 0.0f);
+        std::fill(zo.begin() + HC, zo.end(), 1.0f);
+        BHIP_TRY(b, b->own.dev_zero(&b->d_zero_one, zo.size() * sizeof(float), b->stream));
+        const hipError_t e = hipMemcpyAsync(b->d_zero_one, zo.data(), zo.size() * sizeof(float), hipMemcpyHostToDevice, b->stream);
+        const hipError_t se = hipStreamSynchronize(b->stream);     // zo goes out of scope
+        if (e != hipSuccess || se != hipSuccess) { b->own.free_dev(b->d_zero_one); BHIP_TRY(b, e); BHIP_TRY(b, se); }
+    }
+    // the constants: the plants' live in d_kplant by problem id (the closed loop's table, flushed by its helper); the controller's travel
+    // behind the records — one element in the shared form, else one per record, derived from the problem's CURRENT table with the
+    // function a step uses (nothing is cached or marked here, so a later step derives what it would have derived)
+    const bool host_plans = !own && c.plans_loc == CTK_LOC_HOST, want_traj = c.traj_out != nullptr;
+    const size_t kelems = plant ? 0 : b->differ ? (size_t)n : 1;
+    const RolloutLayout lay(b, kelems, n, m, host_plans, want_traj);
+    BHIP_TRY(b, b->own.grow_dev(b->d_run, b->d_run_cap, lay.total));
+    BHIP_TRY(b, b->own.grow_pin(b->h_run, b->h_run_cap, lay.back));
+    CtkBatchRolloutRec* rec = reinterpret_cast<CtkBatchRolloutRec*>(b->h_run);
+    const size_t prow = (size_t)m * HC, trow = (size_t)m * ((size_t)b->H + 1) * S;
+    auto dev = [&](size_t at) { return reinterpret_cast<float*>(b->d_run + at); };
+    for (int j = 0; j < n; ++j) {
+        const int p = ids ? ids[j] : j;
+        CtkBatchRolloutRec& q = rec[j];
+        std::memset(&q, 0, sizeof(q));
+        q.id = p; q.m = m;
+        q.kidx = plant ? p : b->differ ? j : 0;
+        q.plans = own ? F::own_plan(b, p) : host_plans ? dev(lay.plans) + (size_t)j * prow : c.plans + (size_t)j * prow;
+        q.J = dev(lay.J) + (size_t)j * m;
+        q.traj = want_traj ? dev(lay.traj) + (size_t)j * trow : nullptr;
+        q.Q_out = dev(lay.Q) + (size_t)j * prow;
+        for (int i = 0; i < S; ++i) q.s[i] = c.S[(size_t)j * S + i];
+        for (int i = 0; i < C; ++i) q.u_prev[i] = c.u_prev ? c.u_prev[(size_t)j * C + i] : 0.0f;
+        if (!plant && (j == 0 || b->differ))
+            ctk_mppi_batch_derive_k(b->env, b->differ ? b->table(p) : b->params, b->cfg.dt, b->cfg.intermediate_steps, b->h_run + lay.k + (size_t)q.kidx * b->kstride);
+    }
+    if (host_plans) std::memcpy(b->h_run + lay.plans, c.plans, (size_t)n * prow * sizeof(float));
+    RolloutArgs a = batch_common_args(b);
+    for (int i = 0; i < C; ++i) { a.lo[i] = -INFINITY; a.hi[i] = INFINITY; }
+    a.N = m;
+    const bool generic = b->env != CTK_ENV_CARTPOLE || b->cfg.generic_kernels != 0;
+    size_t wstride = 0;
+    const float* w_dev = pred != CTK_PRED_ODE ? F::rollout_weights(b, &wstride) : nullptr;
+    hipError_t le = plant ? batch_plant_flush(b, sub) : hipSuccess;
+    if (le == hipSuccess) le = hipMemcpyAsync(b->d_run, b->h_run, lay.J, hipMemcpyHostToDevice, b->stream);
+    if (le == hipSuccess)
+        le = ctk_launch_batch_rollout(b->stream, b->env, generic, pred, a, reinterpret_cast<const CtkBatchRolloutRec*>(b->d_run), n, m,
+                                      plant ? b->d_kplant : b->d_run + lay.k, b->d_zero_one, w_dev, wstride, want_traj);
+    if (le == hipSuccess) le = hipMemcpyAsync(b->h_run + lay.J, b->d_run + lay.J, lay.back - lay.J, hipMemcpyDeviceToHost, b->stream);
+    const hipError_t se = hipStreamSynchronize(b->stream);                     // the stagings are free again, whatever happened
+    if (le == hipSuccess) le = se;
+    if (le != hipSuccess) return bfail(b, CTK_ERR_HIP, who + ": " + hipGetErrorString(le));
+    if (c.J_out) std::memcpy(c.J_out, b->h_run + lay.J, (size_t)n * m * sizeof(float));
+    if (want_traj) std::memcpy(c.traj_out, b->h_run + lay.traj, (size_t)n * trow * sizeof(float));
+    return CTK_OK;
+}
+
+// the entry of a family over it
+#define CTK_ROLLOUT_ENTRY(FAM, TRAIT)                                                                                                                 \
+    int FAM##_rollout(FAM* b, int n, const int32_t* ids, const float* S, const float* u_prev, const float* plans, int plans_loc, int m, int model,    \
+                      int plant_substeps, float* traj_out, float* J_out) {                                                                            \
+        return batch_rollout<TRAIT>(b, RolloutCall{#FAM "_rollout", n, ids, S, u_prev, plans, plans_loc, m, model, plant_substeps, traj_out, J_out}); \
+    }
+
 // The thirteen entries of a family that are one line over a shared body, FAM in {ctk_batch, ctk_mlp_batch, ctk_gru_batch, ctk_cem_batch, ctk_rpgd_batch}
 // with the prefix PROB of its per-problem parameter entries and its trait: the bodies above under the family's names
 #define CTK_BATCH_ENTRIES(FAM, PROB, TRAIT)                                                                                                           \
@@ -1122,6 +1255,11 @@ struct MppiFamily {
     // position and reads u for every launched problem, published or not (CEM and RPGD: only if its slot shows the step's seq); the
     // closed loop does not look per step in any family.
     static constexpr bool unpublished_keeps_position = false;
+    // ---- the family's part of batch_rollout ----
+    static int rollout_pred(const ctk_batch* b) { return b->pred; }
+    static const float* rollout_weights(const ctk_batch* b, size_t* stride) { *stride = b->wtab; return b->d_w; }
+    static int rollout_refuse(ctk_batch*, const char*, int, const int32_t*, bool, bool) { return CTK_OK; }   // (missing weights: MlpFamily, GruFamily)
+    static const float* own_plan(const ctk_batch* b, int p) { return b->unom(p, b->cur[(size_t)p]); }
     // the state of a problem: its current plan, its last output
     static BatchState state(Batch* b, int p) { return {{state_seg(b->unom(p, b->cur[(size_t)p]), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C)}}; }
     static const char* per_problem_kernel(const Batch* b) {     // (the _hp form stays the _hp form)
@@ -1442,6 +1580,8 @@ struct MlpFamily : MppiFamily {
                          " (ctk_mlp_batch_set_weights / ctk_mlp_problem_set_weights before stepping); nothing was launched");
         return CTK_OK;
     }
+    // a rollout through the network needs it; one through the analytic plant (model = plant) does not
+    static int rollout_refuse(ctk_batch* b, const char* who, int n, const int32_t* ids, bool, bool net) { return net ? refuse(b, who, n, ids) : CTK_OK; }
 };
 
 }  // namespace
@@ -1476,12 +1616,15 @@ CTK_BATCH_ENTRIES(ctk_batch, ctk_problem, MppiFamily)
 // the closed loop on the device (include/ctk_hip_run.h: ctk_batch_plant_* / ctk_batch_run) and the stochastic plant with the realised
 // cost (include/ctk_hip_episode.h: ctk_batch_plant_*noise* / ctk_batch_plant_step_noisy / ctk_batch_episodes)
 CTK_LOOP_ENTRIES(ctk_batch, MppiFamily)
+// rollouts of caller-supplied plans (include/ctk_hip_rollout.h), every family by the same macro
+CTK_ROLLOUT_ENTRY(ctk_batch, MppiFamily)
 
 // the same under the MLP family's names: the network plans, the plant of its closed loop is the analytic CartPole with the problem's
 // parameter table (and the overrides set there)
 CTK_MPPI_ENTRIES(ctk_mlp_batch, ctk_mlp_problem, MlpFamily, CTK_PRED_MLP)
 CTK_BATCH_ENTRIES(ctk_mlp_batch, ctk_mlp_problem, MlpFamily)
 CTK_LOOP_ENTRIES(ctk_mlp_batch, MlpFamily)
+CTK_ROLLOUT_ENTRY(ctk_mlp_batch, MlpFamily)
 
 size_t ctk_mlp_batch_weight_count(const ctk_mlp_batch* b) { return b ? mlp_batch_weight_count(b) : 0; }
 
@@ -1622,6 +1765,8 @@ struct GruFamily : MppiFamily {
                          " (ctk_gru_batch_set_weights / ctk_gru_problem_set_weights before stepping); nothing was launched, no hidden state moved");
         return CTK_OK;
     }
+    // a rollout through the network needs it; one through the analytic plant (model = plant) does not
+    static int rollout_refuse(ctk_batch* b, const char* who, int n, const int32_t* ids, bool, bool net) { return net ? refuse(b, who, n, ids) : CTK_OK; }
     // the rollout launches of the n records (split at max_per_launch), then ONE advance of the launched records' hidden states, each by
     // (the state of its record, the u its rollout launch published): mppi_advance_hidden of a handle (ctk_api.hip).  In a closed loop the
     // plant launch follows on the stream and writes the NEXT step's records, so the advance has read this step's state by then
@@ -1644,6 +1789,7 @@ extern "C" {
 CTK_MPPI_ENTRIES(ctk_gru_batch, ctk_gru_problem, GruFamily, CTK_PRED_GRU)
 CTK_BATCH_ENTRIES(ctk_gru_batch, ctk_gru_problem, GruFamily)
 CTK_LOOP_ENTRIES(ctk_gru_batch, GruFamily)
+CTK_ROLLOUT_ENTRY(ctk_gru_batch, GruFamily)
 
 int ctk_gru_batch_fit(int num_rollouts, int mpc_horizon, int period, int* blocks, int* record_words, int* wide_tail, size_t* lds_bytes) {
     if (num_rollouts < 1 || mpc_horizon < 1 || period < 1) return CTK_ERR_INVALID_ARGUMENT;
@@ -1963,6 +2109,11 @@ struct CemFamily {
     // Philox position or reads u, and so does this family's step (as RPGD; MPPI advances it regardless, by history); the closed loop
     // does not look per step in any family.
     static constexpr bool unpublished_keeps_position = true;
+    // ---- the family's part of batch_rollout: the analytic predictor; a problem's plan is its mean, where read(U_NOM) reads ----
+    static int rollout_pred(const Batch*) { return CTK_PRED_ODE; }
+    static const float* rollout_weights(const Batch*, size_t* stride) { *stride = 0; return nullptr; }
+    static int rollout_refuse(Batch*, const char*, int, const int32_t*, bool, bool) { return CTK_OK; }
+    static const float* own_plan(const Batch* b, int p) { return b->mu(p); }
     // the state of a problem: mean, standard deviation, last output; its step count
     static BatchState state(Batch* b, int p) {
         return {{state_seg(b->mu(p), (size_t)b->HC), state_seg(b->sd(p), (size_t)b->HC), state_seg(b->u(p), (size_t)b->C), state_counter(&b->count[(size_t)p])}};
@@ -2008,6 +2159,7 @@ extern "C" {
 CTK_BATCH_ENTRIES(ctk_cem_batch, ctk_cem_problem, CemFamily)
 // ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_cem_batch_plant_* / ctk_cem_batch_run / ctk_cem_batch_episodes) ----
 CTK_LOOP_ENTRIES(ctk_cem_batch, CemFamily)
+CTK_ROLLOUT_ENTRY(ctk_cem_batch, CemFamily)
 // ---- per-problem hyper-parameters and limits (include/ctk_hip_family_hyper.h: ctk_cem_problem_*_hyper / _limits, ctk_cem_batch_set_hyper) ----
 CTK_FAMILY_HYPER_ENTRIES(ctk_cem_batch, ctk_cem_problem, CemFamily)
 
@@ -2300,6 +2452,11 @@ struct RpgdFamily {
     // Philox position or reads u, and so does this family's step (as CEM; MPPI advances it regardless, by history); the closed loop
     // does not look per step in any family.
     static constexpr bool unpublished_keeps_position = true;
+    // ---- the family's part of batch_rollout: the analytic predictor; a problem's plan is u_nom, which its first reset writes ----
+    static int rollout_pred(const Batch*) { return CTK_PRED_ODE; }
+    static const float* rollout_weights(const Batch*, size_t* stride) { *stride = 0; return nullptr; }
+    static int rollout_refuse(Batch* b, const char* who, int n, const int32_t* ids, bool own, bool) { return own ? rpgd_batch_ready(b, who, n, ids) : CTK_OK; }
+    static const float* own_plan(const Batch* b, int p) { return b->d_unom + (size_t)p * b->HC; }
     // the state of a problem (ctk_state_size of an RPGD handle): population, Adam moments, ages, last output; Adam step and step count.
     // A problem whose state was set counts as reset.
     static BatchState state(Batch* b, int p) {
@@ -2397,6 +2554,7 @@ size_t ctk_rpgd_template_descent_lds(int environment, int mpc_horizon, int* tape
 CTK_BATCH_ENTRIES(ctk_rpgd_batch, ctk_rpgd_problem, RpgdFamily)
 // ---- the closed loop on the device (include/ctk_hip_loop.h: ctk_rpgd_batch_plant_* / ctk_rpgd_batch_run / ctk_rpgd_batch_episodes) ----
 CTK_LOOP_ENTRIES(ctk_rpgd_batch, RpgdFamily)
+CTK_ROLLOUT_ENTRY(ctk_rpgd_batch, RpgdFamily)
 // ---- per-problem hyper-parameters and limits (include/ctk_hip_family_hyper.h: ctk_rpgd_problem_*_hyper / _limits, ctk_rpgd_batch_set_hyper) ----
 CTK_FAMILY_HYPER_ENTRIES(ctk_rpgd_batch, ctk_rpgd_problem, RpgdFamily)
 

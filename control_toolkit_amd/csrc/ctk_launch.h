@@ -668,3 +668,34 @@ hipError_t ctk_launch_g_rpgd_descent_net(hipStream_t st, int env, int net, const
                                          RpgdPersist* pers = nullptr);
 // predictor.update(s, Q0) for the GRU under the template kernels: a.s0 = measured state, a.u_prev = applied input (u_dev overrides)
 hipError_t ctk_launch_g_gru_advance(hipStream_t st, int env, const RolloutArgs& a, const float* u_dev, float* wperm);
+
+// ---- ctk_batch_rollout.hip : caller-supplied plans rolled out per problem in ONE launch (include/ctk_hip_rollout.h: *_batch_rollout) ----
+// predictor.predict_core + get_trajectory_cost of M plans for every listed problem of a batch, whatever the batch's optimizer: grid
+// (workgroups of M rows, records).  Two kernels, because a handle's ctk_rollout launches one of two that sum the cost in different
+// orders: ctk_batch_rollout<ENV, PRED, WTRAJ> wraps affine_rollout_body (ctk_affine_body.h; what a CartPole handle with
+// generic_kernels == 0 launches: ODE, MLP, GRU), ctk_g_batch_rollout<ENV, WTRAJ> the affine mode of ctk_g_rollout (ctk_g_rollout_body.inc;
+// every other handle).  Base 0, scale 1 and infinite limits: the plans are taken as given.  No flag, no wait, no atomics.
+constexpr int CTK_G_TRAJ = 64;          // trajectories per workgroup of the template rollout kernels (ctk_generic.hip: G_TRAJ)
+struct CtkBatchRolloutRec {             // one per listed problem, blockIdx.y
+    int32_t id;                         // problem index: selects the network weights / hidden state
+    int32_t m;                          // plans of this record (the same M for all records of a call)
+    int32_t kidx;                       // element of the constants array: 0 (shared form), the record's index (per-problem form: the
+                                        // constants lie behind the records) or the problem's index (model = plant: the plant table)
+    uint32_t pad;
+    const float* plans;                 // [M,H,C] device pointer: the uploaded plans, or the problem's own current plan (M = 1)
+    float* J;                           // [M]
+    float* traj;                        // [M,H+1,S] or nullptr
+    float* Q_out;                       // [M,H,C] the body's copy of the plans (scratch)
+    float s[CTK_MAX_STATES];
+    float u_prev[CTK_MAX_INPUTS];
+};
+static_assert(sizeof(CtkBatchRolloutRec) % 16 == 0, "the per-problem constants and the plans lie behind the records, 16-aligned");
+// generic: the batch's handles run the template kernels (any environment but CartPole, or cfg.generic_kernels); pred: CTK_PRED_* of the
+// rollout (the plant model: CTK_PRED_ODE); a: the shared template (C, H, inv_Hp1, infinite limits); k_dev: constants at stride
+// ctk_mppi_batch_k_stride(env), indexed by the records' kidx; zero_one_dev: [2][H*C] zeros | ones; w_dev / wstride: the per-problem
+// network blocks of an MLP or GRU batch (floats), else nullptr / 0
+const char* ctk_batch_rollout_name(int env, bool generic, int pred, bool traj);
+int ctk_batch_rollout_blocks(bool generic, int pred, int M);
+hipError_t ctk_launch_batch_rollout(hipStream_t st, int env, bool generic, int pred, const RolloutArgs& a, const CtkBatchRolloutRec* recs_dev,
+                                    int n_records, int M, const void* k_dev, const float* zero_one_dev, const float* w_dev, size_t wstride,
+                                    bool traj);

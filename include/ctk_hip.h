@@ -809,4 +809,6 @@ int ctk_gru_batch_fit(int num_rollouts, int mpc_horizon, int period_interpolatio
 #include "ctk_hip_family_hyper.h"
 /* the launched-ahead form of the MPPI step: its switch, fuse and counters */
 #include "ctk_hip_ahead.h"
+/* the batch families' rollout of caller-supplied plans: every listed problem's plans through its model in one launch */
+#include "ctk_hip_rollout.h"
 #endif /* CTK_HIP_H */
